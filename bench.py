@@ -21,6 +21,9 @@ SGM pass of the step it overlaps (v3d_sgbm_stream_wait_lockstep).  Rank 0 prints
   e2e                  SURVEY 8(d) config (3) as specified: pinned host SBS + guide in -> kernels -> pinned host f32 4K depth
                        out, three streams, double-buffered; frames/s and per-batch latency, at the bench batch and at batch 8
   extra                (N = 1, --workload all, the default) configs[1] disparity only, configs[3] correlation lookup, MODE_HH
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last one computed (the float32 4K depth; the 1080p depth of
+--workload sgbm; the correlation volume of --workload corr) as DIR/*.npy, whole or as a fixed sample (dump_outputs()).
 """
 import argparse
 import glob
@@ -43,6 +46,8 @@ SCALE = 2
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md); 6290 GB/s measured copy
 GF_R, GF_EPS = 8, 1e-3
 N_DISTINCT = 8                  # distinct synthetic frames per rank, cycled through the batch
+DUMP_WHOLE_BYTES = 48 << 20     # --dump-outputs: an output up to this size is written whole, a larger one as frame 0 + sampled rows
+DUMP_ROWS, DUMP_SEED = 1024, 0  # rows of the fixed, seeded sample over the whole batch
 
 
 def alg_bytes_per_frame():
@@ -60,6 +65,25 @@ def alg_bytes_per_frame():
     P4 = P * SCALE * SCALE
     gf = {"guided_sweep1+2": 2 * P4 + 4 * P + 4 * P4 * 2 * 2 + 4 * P4}          # 190 771 200 B (survey figure)
     return sg, gf
+
+
+def dump_outputs(d, name, out):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, float32 `.npy` files in `d`.  An output
+    of up to DUMP_WHOLE_BYTES goes whole to `<name>.npy`; a larger batch [N, H, W] (1.1 GB of 4K depth at the default batch)
+    as frame 0 whole (`<name>_frame0.npy`), DUMP_ROWS rows drawn with a fixed seed over the whole batch (`<name>_rows.npy`,
+    [K, W]) and their (frame, row) positions (`<name>_rows_index.npy`, float64): under 50 MB in all.  The inputs depend on
+    the arguments only, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(d, exist_ok=True)
+    out = out.float()
+    if out.numel() * 4 <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(d, name + ".npy"), out.cpu().numpy())
+        return
+    n, h = out.shape[0], out.shape[1]
+    np.save(os.path.join(d, name + "_frame0.npy"), out[0].cpu().numpy())
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n * h, size=min(DUMP_ROWS, n * h), replace=False))
+    rows = out.reshape(n * h, -1).index_select(0, torch.from_numpy(pick).to(out.device))
+    np.save(os.path.join(d, name + "_rows.npy"), rows.cpu().numpy())
+    np.save(os.path.join(d, name + "_rows_index.npy"), np.stack([pick // h, pick % h], axis=1).astype(np.float64))
 
 
 def cpu_baseline(sbs, guide):
@@ -111,13 +135,15 @@ def cpu_baseline(sbs, guide):
     return out, disp, q
 
 
-def bench_corr(args, N, dev):
-    """BASELINE configs[3]: CREStereo-style correlation lookup, bf16 in / f32 accumulate on MFMA, 1080p/4 features"""
+def bench_corr(args, N, dev, line=False):
+    """BASELINE configs[3]: CREStereo-style correlation lookup, bf16 in / f32 accumulate on MFMA, 1080p/4 features.
+    line: this is the reported workload (--workload corr), so --steps timed steps exactly; as an extra leg at least 20"""
     h, w, C, G = 270, 480, 256, 4
-    fl = torch.randn((h, w, C), device=dev).to(torch.bfloat16)
-    fr = torch.randn((h, w, C), device=dev).to(torch.bfloat16)
-    flow = torch.rand((2, h, w), device=dev) * 4 - 2
-    steps = max(args.steps, 20)
+    gen = torch.Generator(device=dev).manual_seed(0)          # same inputs on every run (--dump-outputs compares builds)
+    fl = torch.randn((h, w, C), device=dev, generator=gen).to(torch.bfloat16)
+    fr = torch.randn((h, w, C), device=dev, generator=gen).to(torch.bfloat16)
+    flow = torch.rand((2, h, w), device=dev, generator=gen) * 4 - 2
+    steps = args.steps if line else max(args.steps, 20)
     for _ in range(max(args.warmup, 3)):
         N.corr_lookup(fl, fr, flow, G, 0)
     torch.cuda.synchronize()
@@ -125,11 +151,13 @@ def bench_corr(args, N, dev):
     t0 = time.perf_counter()
     e0.record()
     for _ in range(steps):
-        N.corr_lookup(fl, fr, flow, G, 0)
+        out = N.corr_lookup(fl, fr, flow, G, 0)
     e1.record()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     ms = e0.elapsed_time(e1) / steps
+    if line and args.dump_outputs:
+        dump_outputs(args.dump_outputs, "corr", out)
     alg = 2 * h * w * C * 2 + 2 * h * w * 4 + G * 9 * h * w * 4           # fl + fr bf16, flow, out f32 (~142 MB form A)
     flops = 2.0 * h * w * C * 9
     # the kernels that ran, from the options in force (v3d_get_option), not from memory
@@ -381,9 +409,15 @@ def main():
     ap.add_argument("--no-cli", action="store_true", help="skip the file-to-file product-path leg (extra.cli)")
     ap.add_argument("--dump-frame0", default=None, metavar="NPZ",
                     help="tests: rank 0 writes frame 0 of its last timed step (disp16 + 4K depth) to this .npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path computed in its last timed step to DIR/<name>.npy (float32; frame 0 + "
+                         "a fixed seeded row sample and its float64 positions when the whole batch exceeds 48 MB), to compare two "
+                         "builds output for output")
     ap.add_argument("--test-inject-lockstep-timeout", action="store_true",
                     help="tests only: make every lock-step workgroup of the first timed region report a time-out (drives the recovery path)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from video_3d_pipeline import _native as N, sharding, synthetic as syn
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -399,7 +433,7 @@ def main():
     dev = torch.device("cuda", local)
     N.lib()
     if args.workload == "corr":
-        print(json.dumps(bench_corr(args, N, dev)))
+        print(json.dumps(bench_corr(args, N, dev, line=True)))
         return 0
     if world > 1:
         sharding.init_process_group(args.dist_backend)
@@ -646,6 +680,8 @@ def main():
         if recomputed:
             res["lockstep_timeouts_after_switch"] = matcher.sync_errors()
 
+        if args.dump_outputs:           # before the legs below, which reuse these buffers
+            dump_outputs(args.dump_outputs, "depth4k" if full else "depth", hp.out4k if full else hp.depth)
         if args.dump_frame0:
             np.savez(args.dump_frame0, disp=hp.disp[0].cpu().numpy(), q=hp.out4k[0].cpu().numpy() if full else np.zeros(0, np.float32))
         # ---- the timed region's own output against the oracle (frame 0 of the last step is base frame 0) ----

@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import numpy as np
+
 from conftest import ROOT
 
 
@@ -78,8 +80,7 @@ def test_product_does_not_import_the_oracle():
                 assert "liboracle" not in src, f"{f} references the oracle library"
 
 
-def test_bench_algorithmic_bytes_match_the_survey():
-    """bench.py's per-launch shares must sum to SURVEY.md 8(d): 1 291 161 600 B (SGBM) and 190 771 200 B (guided)"""
+def _bench_module():
     import importlib.util
     import sys
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
@@ -90,5 +91,38 @@ def test_bench_algorithmic_bytes_match_the_survey():
         spec.loader.exec_module(mod)
     finally:
         sys.argv = argv
-    sg, gf = mod.alg_bytes_per_frame()
+    return mod
+
+
+def test_bench_algorithmic_bytes_match_the_survey():
+    """bench.py's per-launch shares must sum to SURVEY.md 8(d): 1 291 161 600 B (SGBM) and 190 771 200 B (guided)"""
+    sg, gf = _bench_module().alg_bytes_per_frame()
     assert int(sum(sg.values())) == 1291161600 and gf["guided_sweep1+2"] == 190771200
+
+
+def test_bench_dump_outputs_writes_whole_or_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (host side): a small output goes whole; a large batch goes as frame 0 + seeded rows whose
+    recorded (frame, row) positions hold exactly those rows, the same rows on every call, float32 / float64 only; at the
+    default 1080p -> 4K batch the files stay under 64 MB"""
+    import torch
+    mod = _bench_module()
+    small = torch.arange(3 * 5 * 7, dtype=torch.float32).reshape(3, 5, 7)
+    mod.dump_outputs(str(tmp_path / "s"), "x", small)
+    assert os.listdir(tmp_path / "s") == ["x.npy"]
+    assert np.array_equal(np.load(tmp_path / "s" / "x.npy"), small.numpy())
+
+    big = torch.rand((6, 2500, 640), generator=torch.Generator().manual_seed(1))          # 38.4 MB, the whole-file limit lowered
+    mod.DUMP_WHOLE_BYTES = 1 << 20
+    for d in ("b0", "b1"):
+        mod.dump_outputs(str(tmp_path / d), "y", big)
+    names = sorted(os.listdir(tmp_path / "b0"))
+    assert names == ["y_frame0.npy", "y_rows.npy", "y_rows_index.npy"]
+    for n in names:
+        a = np.load(tmp_path / "b0" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(tmp_path / "b1" / n)), n
+    assert np.array_equal(np.load(tmp_path / "b0" / "y_frame0.npy"), big[0].numpy())
+    rows, idx = np.load(tmp_path / "b0" / "y_rows.npy"), np.load(tmp_path / "b0" / "y_rows_index.npy").astype(np.int64)
+    assert rows.shape == (mod.DUMP_ROWS, 640) and len(set(idx[:, 0])) == 6
+    assert np.array_equal(rows, big.numpy()[idx[:, 0], idx[:, 1]])
+    # the default workload: 34 frames of 2160 x 3840 float32
+    assert 2160 * 3840 * 4 + mod.DUMP_ROWS * (3840 * 4 + 16) <= 64 << 20 < 34 * 2160 * 3840 * 4

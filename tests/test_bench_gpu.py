@@ -73,6 +73,27 @@ def test_bench_recovers_from_lockstep_timeouts_over_several_steps(tmp_path, sing
     assert np.array_equal(got["disp"], single_rank_frame0["disp"]) and np.array_equal(got["q"], single_rank_frame0["q"])
 
 
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_are_the_timed_output_and_repeat(tmp_path, single_rank_frame0):
+    """--dump-outputs: float32 / float64 files, under 64 MB in all; frame 0 of the 4K depth has the bits --dump-frame0 saw,
+    the sampled rows of frame 0 are its rows, and a second run with the same arguments writes the same arrays"""
+    dirs = [tmp_path / "o0", tmp_path / "o1"]
+    for d in dirs:
+        res = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(d)] + COMMON)
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["lockstep_timeouts"] == 0
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["depth4k_frame0.npy", "depth4k_rows.npy", "depth4k_rows_index.npy"]
+    assert sum((dirs[0] / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a = np.load(dirs[0] / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(dirs[1] / n)), n
+    f0 = np.load(dirs[0] / "depth4k_frame0.npy")
+    assert np.array_equal(f0, single_rank_frame0["q"])
+    rows, idx = np.load(dirs[0] / "depth4k_rows.npy"), np.load(dirs[0] / "depth4k_rows_index.npy").astype(np.int64)
+    own = idx[:, 0] == 0
+    assert own.any() and np.array_equal(rows[own], f0[idx[own, 1]])
+
+
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_over_rccl(tmp_path, single_rank_frame0):
     """the driver's command as it is (backend nccl = RCCL, one GPU per rank); skips on a one-GPU box"""
