@@ -172,6 +172,7 @@ __global__ __launch_bounds__(256) void k_gf(const TD* __restrict__ depth_lo, int
 #endif
 typedef double v3d_f64x2 __attribute__((ext_vector_type(2)));
 typedef float v3d_f32x2 __attribute__((ext_vector_type(2)));
+typedef float v3d_f32x4 __attribute__((ext_vector_type(4)));
 
 template <int SWEEP, int RR, typename TD>
 __global__ __launch_bounds__(256) void k_gfm(const TD* __restrict__ depth_lo, int Wlo, int Hlo,
@@ -372,74 +373,167 @@ __global__ __launch_bounds__(256) void k_gfm(const TD* __restrict__ depth_lo, in
 // Fused form for r in {4, 8}: BOTH box stages in one launch, a/b never touch HBM (the two-sweep form moves
 // 2 x 16 B per 4K pixel through HBM for the f64 a/b planes: 8 of its 11 GB per 30 frames).
 //
-// A 512-thread workgroup owns a strip of 256 columns (224 outputs at r = 8) and marches down a band of rows, two
+// A 512-thread workgroup owns a strip of 256 columns (224 outputs at r = 8) and marches down a band of rows, FOUR
 // rows per step, with its eight waves SPECIALISED:
-//   waves 0-3 (stage 1)  exactly k_gfm<1>: vertical sliding sums of {g, g*g, p, g*p} in a register ring, horizontal
-//                        window sums through LDS (pixel pairs), the per-pixel algebra -> a, b -- written to an LDS
-//                        row pair instead of HBM;
-//   waves 4-7 (stage 2)  exactly k_gfm<2>, two steps behind: pick the a/b rows up from LDS (one column per thread),
-//                        vertical sliding sums in a second register ring, horizontal window sums through LDS, q -> HBM.
+//   waves 0-3 (stage 1)  vertical sliding sums of {g, g*g, p, g*p} in a register ring (k_gfm<1>'s arithmetic), four rows of
+//                        column sums into LDS; then horizontal window sums as SLIDING RUNS and the per-pixel algebra -> a, b
+//                        of four rows -- written to LDS instead of HBM;
+//   waves 4-7 (stage 2)  two steps behind: pick the a/b rows up from LDS (one column per thread), vertical sliding sums in a
+//                        second register ring (k_gfm<2>'s arithmetic), horizontal sliding runs, q -> HBM.
 // Each role keeps ONE ring (<= 128 VGPRs, four waves per SIMD, two workgroups per CU); putting both rings into one
-// thread needs ~180 VGPRs and halves the occupancy of a kernel that lives on its waves covering each other's LDS and
-// barrier stalls.  All hand-offs are double-buffered LDS rows, so a step costs ONE workgroup barrier: in phase p
-// stage 1 runs H1(p-1) then V1(p), stage 2 runs H2(p-3) then V2(p-2).  The arithmetic is that of the two-sweep kernels; since
-// round 3 the window sums are re-associated (aligned pair sums, see PAIR SUMS below): equal to rounding, not by construction bit for bit.
+// thread needs ~180 VGPRs.  All hand-offs are double-buffered LDS rows, so a step costs ONE workgroup barrier: in phase p
+// stage 1 runs H1(p-1) then V1(p), stage 2 runs H2(p-3) then V2(p-2).
+// SLIDING RUNS (round 4).  In a horizontal phase a lane owns a run of FOUR consecutive outputs of one of the step's four rows,
+// so all 256 lanes of a role are busy (4 rows x 64 runs): the run's 2r + 4 columns arrive as r + 2 aligned 16-byte reads per
+// f64 plane (2r + 4 per int4 plane), the first window is summed once and each further output costs one add and one subtract
+// per plane; the four a/b solves (or q evaluations) are independent and interleave.  Round 3's pair form needed r + 1 pair sums
+// + 2 singles per plane for TWO outputs, plus a DPP exchange and an extra LDS row per plane in the vertical phase (gone).
+// Why the rotating-worker form of round 3 lost (97-151 us per frame against 75.7): it ran runs on a quarter or an
+// eighth of the lanes, and a step lasts as long as its longest wave.  Four rows per step give the runs to every lane.
+// LDS: I1 = 2 x 16 KB stage-1 column sums + a 3-deep ring of 16-KB a/b row groups = 80 KB (two workgroups per CU).  Stage 2
+// overwrites each a/b row group IN PLACE with its column sums (thread t reads column t and writes column t), so a/b and the
+// stage-2 sums share one ring: group j is written by H1 in phase j+1, turned into sums by V2 in phase j+2, read by H2 in phase
+// j+3.  The general (f64 stage 1) route needs 96 KB and runs one workgroup per CU; 512-column strips exist for I1 only (160 KB).
+// Rows are SWIZZLED in 16-byte chunks (gf_swz2 / gf_swz4): a run's reads stride 32 B (f64) or 64 B (int4) across the lanes,
+// 2- and 4-way ds_read_b128 bank conflicts in a plain layout, none swizzled.
+// The window sums are re-associated against the two-sweep kernels (equal to rounding, not bit for bit); stage 1's sums are
+// exact in both routes (integers or exact dyadic f64), so the I1 and f64 routes give the same bits.
 // HBM traffic: guide + depth_lo (x 256/224 strip overlap, + 4r warm-up rows per band) in, q out.
-// Measured on 30 4K frames: 2.15 ms against 2.72 ms for the two sweeps (VALU pipe 61 % busy, LDS pipe 62 %: the kernel is
-// bound by its ~170 mostly-f64 instructions per pixel, no longer by HBM).  Tried, no gain: a wave-uniform fast path that
-// skips the count reciprocals away from the border (more spills, 2.26 ms), s_setprio for the stage-1 waves (2.21-2.25 ms).
-// Round 3 (34 frames, same box, tools/gf_ab.py): a build whose horizontal phases skip a third of H1's and 60 % of H2's reads and
-// adds (a proxy build, results garbage) runs 65.7 us per frame against 75.1 -- so the window sums are worth ~15-20 %.  The form that saves them,
-// SLIDING RUNS (a lane owns 4 or 8 consecutive outputs of a row, first window summed once, then one add and one subtract per
-// output and plane; 22 or 30 adds for 4 or 8 outputs instead of 34 or 68), needs a quarter or an eighth of the lanes, so the
-// horizontal phase of a step was given to a rotating worker group of two waves (runs of 4) or one wave (runs of 8) while the
-// role's other waves went to the barrier: identical output, total instructions -15 %, and SLOWER -- 97.4 us per frame (runs of
-// 4) and 151.4 (runs of 8) against 75.7.  A step is one barrier-to-barrier interval; its length is the LATENCY of the longest
-// wave, and a worker that sums a window and then walks 8 dependent a/b solves (two reciprocal refinements each, ~25 dependent
-// f64 operations per output) is three times as long as a wave that does one pixel pair.  The pair form spreads exactly that
-// chain over all lanes; what remains is its instruction count.  (Kernel kept out of the tree; numbers in DESIGN.md.)
 // ------------------------------------------------------------------------------------------------
-// value of the lane's pair partner (lane ^ 1): two DPP moves for the halves of a double
-__device__ __forceinline__ double gf_partner(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), V3D_DPP_QUAD(1, 0, 3, 2), 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), V3D_DPP_QUAD(1, 0, 3, 2), 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ int gf_partner(int v) { return __builtin_amdgcn_update_dpp(0, v, V3D_DPP_QUAD(1, 0, 3, 2), 0xF, 0xF, true); }
+// 16-byte chunk m of a swizzled row: f64 / int2 rows (a run reads chunks 2l + c on lane l), int4 rows (4l + c)
+__device__ __forceinline__ int gf_swz2(int m) { return m ^ ((m >> 3) & 1) ^ ((m >> 4) & 1); }
+__device__ __forceinline__ int gf_swz4(int m) { return m ^ ((m >> 4) & 3); }
+__device__ __forceinline__ int gf_c8(int c) { return 2 * gf_swz2(c >> 1) + (c & 1); }     // element of 8-byte column c
 
-// PAIR SUMS (round 3).  The horizontal phases are bound by the LDS pipe: a 2r+2-column window costs r+1 16-byte reads per plane
-// and thread, ~1400 LDS cycles per workgroup and step.  The vertical phase therefore also leaves, next to every column sum, the
-// sum of each ALIGNED column pair (own value + the lane partner's, one DPP exchange): a window that starts on an even column is
-// r+1 pair sums, and the two outputs of a thread are that total minus the one column each of them does not cover --
-// r+1 8-byte reads + 2 singles instead of r+1 16-byte reads, r+2 adds instead of 2r+1.
+// window sums of the four outputs c0 .. c0+3 of a swizzled f64 row (columns c0 - RR .. c0 + 3 + RR, r + 2 chunks)
+template <int RR>
+__device__ __forceinline__ void gf_run4(const double* row, int c0, double s[4])
+{
+    const v3d_f64x2* d = reinterpret_cast<const v3d_f64x2*>(row);
+    const int m0 = (c0 - RR) >> 1;
+    double c = 0.0, l0 = 0.0, l1 = 0.0, l2 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
+#pragma unroll
+    for (int k0 = 0; k0 < RR + 2; k0 += GF_CH) {
+        v3d_f64x2 w[GF_CH];
+#pragma unroll
+        for (int i = 0; i < GF_CH; i++) if (k0 + i < RR + 2) w[i] = d[gf_swz2(m0 + k0 + i)];
+#pragma unroll
+        for (int i = 0; i < GF_CH; i++) {
+            const int k = k0 + i;
+            if (k == 0) { l0 = w[i].x; l1 = w[i].y; c = w[i].x; c += w[i].y; }
+            else if (k == 1) { l2 = w[i].x; c += w[i].x; c += w[i].y; }
+            else if (k < RR) { c += w[i].x; c += w[i].y; }
+            else if (k == RR) { c += w[i].x; r1 = w[i].y; }
+            else if (k == RR + 1) { r2 = w[i].x; r3 = w[i].y; }
+        }
+        asm volatile("" : "+v"(c) :: "memory");   // the chunk's adds cannot sink below the next chunk's reads
+    }
+    s[0] = c; s[1] = (s[0] + r1) - l0; s[2] = (s[1] + r2) - l1; s[3] = (s[2] + r3) - l2;
+}
+
+// the same for a swizzled int2 row {sum g, sum g*g} (two columns per chunk)
+template <int RR>
+__device__ __forceinline__ void gf_run4(const int2* row, int c0, int2 s[4])
+{
+    const int4* d = reinterpret_cast<const int4*>(row);
+    const int m0 = (c0 - RR) >> 1;
+    int2 c = make_int2(0, 0), l0 = c, l1 = c, l2 = c, r1 = c, r2 = c, r3 = c;
+#pragma unroll
+    for (int k0 = 0; k0 < RR + 2; k0 += 3) {
+        int4 w[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) if (k0 + i < RR + 2) w[i] = d[gf_swz2(m0 + k0 + i)];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int k = k0 + i;
+            const int2 a = make_int2(w[i].x, w[i].y), b = make_int2(w[i].z, w[i].w);
+            if (k == 0) { l0 = a; l1 = b; c = make_int2(a.x + b.x, a.y + b.y); }
+            else if (k == 1) { l2 = a; c.x += a.x + b.x; c.y += a.y + b.y; }
+            else if (k < RR) { c.x += a.x + b.x; c.y += a.y + b.y; }
+            else if (k == RR) { c.x += a.x; c.y += a.y; r1 = b; }
+            else if (k == RR + 1) { r2 = a; r3 = b; }
+        }
+        asm volatile("" : "+v"(c.x), "+v"(c.y) :: "memory");
+    }
+    s[0] = c;
+    s[1] = make_int2(s[0].x + r1.x - l0.x, s[0].y + r1.y - l0.y);
+    s[2] = make_int2(s[1].x + r2.x - l1.x, s[1].y + r2.y - l1.y);
+    s[3] = make_int2(s[2].x + r3.x - l2.x, s[2].y + r3.y - l2.y);
+}
+
+// the same for a swizzled int4 row (I1: {sum g, sum g*g, sum P, sum g*P}, one column per chunk)
+template <int RR>
+__device__ __forceinline__ void gf_run4(const int4* row, int c0, int4 s[4])
+{
+    int4 c = make_int4(0, 0, 0, 0), l0 = c, l1 = c, l2 = c, r1 = c, r2 = c, r3 = c;
+#pragma unroll
+    for (int k0 = 0; k0 < 2 * RR + 4; k0 += 3) {
+        int4 u[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) if (k0 + i < 2 * RR + 4) u[i] = row[gf_swz4(c0 - RR + k0 + i)];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int k = k0 + i;
+            if (k < 2 * RR + 1) { c.x += u[i].x; c.y += u[i].y; c.z += u[i].z; c.w += u[i].w; }
+            if (k == 0) l0 = u[i];
+            else if (k == 1) l1 = u[i];
+            else if (k == 2) l2 = u[i];
+            else if (k == 2 * RR + 1) r1 = u[i];
+            else if (k == 2 * RR + 2) r2 = u[i];
+            else if (k == 2 * RR + 3) r3 = u[i];
+        }
+        asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w) :: "memory");
+    }
+    s[0] = c;
+    s[1] = make_int4(s[0].x + r1.x - l0.x, s[0].y + r1.y - l0.y, s[0].z + r1.z - l0.z, s[0].w + r1.w - l0.w);
+    s[2] = make_int4(s[1].x + r2.x - l1.x, s[1].y + r2.y - l1.y, s[1].z + r2.z - l1.z, s[1].w + r2.w - l1.w);
+    s[3] = make_int4(s[2].x + r3.x - l2.x, s[2].y + r3.y - l2.y, s[2].z + r3.z - l2.z, s[2].w + r3.w - l2.w);
+}
+
+// a, b of the four pixels hgx .. hgx+3 of row y from their window sums {sum g, sum g*g} (exact ints), {sum p, sum g*p}
+template <int RR>
+__device__ __forceinline__ void gf_solve4(const int sg[4], const int sgg[4], const double sp[4], const double sgp[4], int hgx, int y,
+                                          int W, int H, double eps, double a[4], double b[4])
+{
+    const int cy = min(y + RR, H - 1) - max(y - RR, 0) + 1;
+    int cx[4];
+#pragma unroll
+    for (int n = 0; n < 4; n++) cx[n] = min(hgx + n + RR, W - 1) - max(hgx + n - RR, 0) + 1;
+    const double inv0 = gf_rcp((double)(cx[0] * cy));
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+        const double inv = (n == 0 || cx[n] == cx[0]) ? inv0 : gf_rcp((double)(cx[n] * cy));
+        const double mI = (double)sg[n] * (inv * (1.0 / 255.0)), mp = sp[n] * inv;
+        const double mII = (double)sgg[n] * (inv * (1.0 / 65025.0)), mIp = sgp[n] * (inv * (1.0 / 255.0));
+        const double var = fma(-mI, mI, mII), cov = fma(-mI, mp, mIp);
+        const double aa = cov * gf_rcp(var + eps);
+        a[n] = aa; b[n] = fma(-aa, mI, mp);
+    }
+}
+
 // I1 (int16 disparity in, exact 2x upscale): stage 1's four window sums are EXACT INTEGERS.  The disparity is d/16 with d <= 1023
 // and the x2 bilinear weights are {1,3}/4 per axis, so P = 256 p = sum w d (w in {1,3,9}) is an integer <= 16368; over a 17 x 17
-// window sum P < 2^23 and sum g P < 2^31.  The ring holds (P << 8 | g) in ONE register per row (17 instead of 34 + 5), the
-// vertical sums are four int32, the row pair's sums cross the lanes as one int4 per column (16 bytes instead of 24), and the
-// horizontal phase adds integers three at a time (v_add3_u32).  The a/b algebra converts the four exact sums to f64 -- the very
-// values the f64 sums of the general path hold (they are exact there too) -- so the output is bit-identical to it.
+// window sum P < 2^23 and sum g P < 2^31.  The ring holds (P << 8 | g) in ONE register per row, the vertical sums are four int32
+// and cross the lanes as one int4 per column.  The a/b algebra converts the four exact sums to f64 -- the very values the f64 sums
+// of the general path hold (they are exact there too) -- so the output is bit-identical to it.
 template <int RR, int COLS, typename TD, bool I1>
-__global__ __launch_bounds__(2 * COLS, 4) void k_gff(const TD* __restrict__ depth_lo, int Wlo, int Hlo,
+__global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restrict__ depth_lo, int Wlo, int Hlo,
                                                 const uint8_t* __restrict__ guide, int W, int H, double eps, int band_h,
                                                 float* __restrict__ out, size_t depth_stride, size_t guide_stride)
 {
-    static_assert(RR % 2 == 0, "pairs must not straddle the strip's halo boundaries");
+    static_assert(RR % 4 == 0, "runs of four must not straddle the strip's halo boundaries");
     static_assert(!I1 || std::is_same<TD, int16_t>::value, "the integer stage 1 takes the int16 disparity");
-    constexpr int R = 2 * RR + 1, NOUT = COLS - 4 * RR, HP = COLS / 2;      // HP pixel pairs per row
-    static_assert(COLS == 256 || COLS == 512, "strip width");
-    // stage 1's row-pair sums: general path {sum p, sum g*p} f64 planes + {sum g, sum g*g} int2; I1: one int4 {sum g, sum g*g, sum P, sum g*P}
-    constexpr int S1D = 2 * 2 * 2 * COLS * 8, S1I = 2 * 2 * COLS * 8;
-    __shared__ __attribute__((aligned(16))) unsigned char sS1[I1 ? 2 * 2 * COLS * 16 : S1D + S1I];
-    double (*sV1)[2][2][COLS] = reinterpret_cast<double (*)[2][2][COLS]>(sS1);               // [buffer][row of the pair][sum p | sum g*p][column]
-    int2 (*sVi)[2][COLS] = reinterpret_cast<int2 (*)[2][COLS]>(sS1 + (I1 ? 0 : S1D));         // [buffer][row][column] {sum g, sum g*g}
-    int4 (*sVq)[2][COLS] = reinterpret_cast<int4 (*)[2][COLS]>(sS1);                          // I1: [buffer][row][column]
+    static_assert(COLS == 256 || (COLS == 512 && I1), "strip width (512 columns: I1 only, the f64 route's rows exceed the LDS)");
+    constexpr int R = 2 * RR + 1, NOUT = COLS - 4 * RR, HR = COLS / 4;   // HR runs of four outputs per row
+    // stage 1's column sums of the step's four rows: I1 one int4 {sum g, sum g*g, sum P, sum g*P}; general path {sum p, sum g*p}
+    // f64 planes + {sum g, sum g*g} int2
+    constexpr int S1D = 2 * 4 * 2 * COLS * 8, S1 = I1 ? 2 * 4 * COLS * 16 : S1D + 2 * 4 * COLS * 8;
+    __shared__ __attribute__((aligned(16))) unsigned char sS1[S1];
+    double (*sV1)[4][2][COLS] = reinterpret_cast<double (*)[4][2][COLS]>(sS1);       // [buffer][row][sum p | sum g*p][column]
+    int2 (*sVi)[4][COLS] = reinterpret_cast<int2 (*)[4][COLS]>(sS1 + (I1 ? 0 : S1D));  // [buffer][row][column] {sum g, sum g*g}
+    int4 (*sVq)[4][COLS] = reinterpret_cast<int4 (*)[4][COLS]>(sS1);                  // I1: [buffer][row][column]
     (void)sV1; (void)sVi; (void)sVq;
-    __shared__ __attribute__((aligned(16))) double sAB[2][2][2][COLS];        // [buffer][row][a | b][column]   stage 1 -> stage 2
-    __shared__ __attribute__((aligned(16))) double sV2[2][2][2][COLS];        // [buffer][row][sum a | sum b][column]
-    __shared__ __attribute__((aligned(16))) double sP2[2][2][2][COLS / 2];    // [buffer][row][sum a | sum b][aligned column pair]
-    __shared__ __attribute__((aligned(16))) int4 sPq[I1 ? 2 : 1][2][I1 ? COLS / 2 : 1];   // I1: [buffer][row][aligned column pair]
-    (void)sPq;
+    __shared__ __attribute__((aligned(16))) double sAB[3][4][2][COLS];    // [ring slot][row][a | b, then sum a | sum b][column]
     {   // frame of the batch
         const size_t f = blockIdx.z, n4 = (size_t)W * H;
         depth_lo += f * depth_stride; guide += f * guide_stride; out += f * n4;
@@ -450,259 +544,150 @@ __global__ __launch_bounds__(2 * COLS, 4) void k_gff(const TD* __restrict__ dept
     const int gx = gx0 + t;                                          // vertical phases: this thread's column
     const int ya = blockIdx.y * band_h, yb = min(ya + band_h, H);
     const int nrows = (yb - ya) + 4 * RR;                            // input rows ya - 2r .. yb - 1 + 2r
-    const int NS = (nrows + 1) >> 1;                                 // steps (row pairs)
+    const int NS = (nrows + 3) >> 2;                                 // steps (four rows each)
     const int NP = NS + 3;                                           // phases: the last H2 runs three phases behind the last V1
-    const int hq = t % HP, hgx = gx0 + 2 * hq;                       // horizontal phases: pixel pair (2hq, 2hq+1) of row t / HP of the step
-
-    for (int i = threadIdx.x; i < 2 * 2 * 2 * COLS; i += 2 * COLS) (&sAB[0][0][0][0])[i] = 0.0;
-    __syncthreads();
 
     if (role == 0) {
-      if constexpr (I1) {
-        // ================= stage 1, exact integer sums (int16 disparity, exact 2x) =================
+        // ================= stage 1: guide + depth -> a, b =================
         const bool col_ok = gx >= 0 && gx < W;
-        const bool pair_in = 2 * hq >= RR && 2 * hq < COLS - RR;      // a/b columns of the strip
-        const bool px0 = pair_in && hgx >= 0 && hgx < W, px1 = pair_in && hgx + 1 >= 0 && hgx + 1 < W;
-        // x2 bilinear source columns and weights (quarters): even x = 2k: (k-1, k) x (1, 3); odd: (k, k+1) x (3, 1)
-        const int kx = gx >> 1;
-        const int bxa = min(max((gx & 1) ? kx : kx - 1, 0), Wlo - 1), bxb = min(max((gx & 1) ? kx + 1 : kx, 0), Wlo - 1);
-        const int wxa = (gx & 1) ? 3 : 1, wxb = 4 - wxa;
-        uint32_t ring[R];                        // (P << 8) | g of the last 2r+1 rows
-        int vg = 0, vgg = 0, vP = 0, vgP = 0;
+        const int gxc = min(max(gx, 0), W - 1);
+        uint32_t ring[R];                        // I1: (P << 8) | g of the last 2r+1 rows
+        double r1[I1 ? 1 : R];                   // general: p ring
+        uint32_t rgw[I1 ? 1 : (R + 3) / 4];      // general: g ring, one BYTE per row
+        int vg = 0, vgg = 0, vP = 0, vgP = 0;    // I1: the four column sums; general: sum g, sum g*g
+        double v0 = 0.0, v1 = 0.0;               // general: sum p, sum g*p
 #pragma unroll
         for (int j = 0; j < R; j++) ring[j] = 0u;
-        struct RowIn { int g, a0, a1, b0, b1; bool in; };
-        const int gxc = min(max(gx, 0), W - 1);
-        auto fetch_row = [&](int tt) -> RowIn {        // unconditional loads from clamped addresses
-            RowIn q;
-            const int e = ya - 2 * RR + tt;                                      // input row entering the window
-            q.in = col_ok && e >= 0 && e < H && tt < nrows;
-            const int ec = min(max(e, 0), H - 1), ky = ec >> 1;
-            q.g = guide[(size_t)ec * W + gxc];
-            const TD* ra = depth_lo + (size_t)min(max((ec & 1) ? ky : ky - 1, 0), Hlo - 1) * Wlo;
-            const TD* rb = depth_lo + (size_t)min(max((ec & 1) ? ky + 1 : ky, 0), Hlo - 1) * Wlo;
-            q.a0 = max((int)ra[bxa], 0); q.a1 = max((int)ra[bxb], 0); q.b0 = max((int)rb[bxa], 0); q.b1 = max((int)rb[bxb], 0);   // depth.py:374: <= 0 -> 0
-            return q;
-        };
-        RowIn nx[2] = { fetch_row(0), fetch_row(1) };
-        for (int p0 = 0; p0 < NP; p0 += R) {
 #pragma unroll
-            for (int sp = 0; sp < R; sp++) {
-                const int p = p0 + sp;
-                if (p < NP) {                                                    // uniform
-                    int tl = t;
-                    asm volatile("" : "+v"(tl));                                 // (nothing of the horizontal phase hoisted out of the loop)
-                    const int hrow = tl / HP, hq = tl % HP, hgx = gx0 + 2 * hq;
-                    // ---- H1(p-1): window sums of the row pair V1(p-1) left in LDS -> a, b of two pixels -> sAB ----
-                    const int j = p - 1;
-                    if (j >= RR && j < NS && pair_in) {
-                        const int hb = j & 1;
-                        const int y = ya - 3 * RR + 2 * j + hrow;                // centre row of this window
-                        double ab[2][2] = { { 0.0, 0.0 }, { 0.0, 0.0 } };
-                        if (y >= 0 && y < H && px0) {
-                            // columns 2hq - r .. 2hq + 1 + r = the r + 1 aligned pairs hq - r/2 .. hq + r/2: their total, then each
-                            // output drops the one column it does not cover (output 0 the last, output 1 the first)
-                            const int4* gp = &sPq[hb][hrow][hq - RR / 2];
-                            const int4 f = sVq[hb][hrow][2 * hq - RR], l = sVq[hb][hrow][2 * hq + RR + 1];
-                            int4 c = make_int4(0, 0, 0, 0);
+        for (int j = 0; j < (I1 ? 1 : R); j++) r1[j] = 0.0;
 #pragma unroll
-                            for (int ch = 0; ch <= RR; ch += 3) {
-                                int4 u[3];
-#pragma unroll
-                                for (int i = 0; i < 3; i++) if (ch + i <= RR) u[i] = gp[ch + i];
-#pragma unroll
-                                for (int i = 0; i < 3; i++) if (ch + i <= RR) { c.x += u[i].x; c.y += u[i].y; c.z += u[i].z; c.w += u[i].w; }
-                                asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w) :: "memory");
-                            }
-                            const int cy = min(y + RR, H - 1) - max(y - RR, 0) + 1;
-                            const int cx0 = min(hgx + RR, W - 1) - max(hgx - RR, 0) + 1, cx1 = min(hgx + 1 + RR, W - 1) - max(hgx + 1 - RR, 0) + 1;
-                            const double inva = gf_rcp((double)(cx0 * cy)), invb = cx1 == cx0 ? inva : gf_rcp((double)(cx1 * cy));
-#pragma unroll
-                            for (int n = 0; n < 2; n++) {
-                                const int4 e = n ? f : l;                    // the column this output does NOT cover
-                                const double inv = n ? invb : inva;
-                                const double s0 = (double)(c.z - e.z) * (1.0 / 256.0), s1 = (double)(c.w - e.w) * (1.0 / 256.0);   // sum p, sum g*p: exact
-                                const double mI = (double)(c.x - e.x) * (inv * (1.0 / 255.0)), mp = s0 * inv;
-                                const double mII = (double)(c.y - e.y) * (inv * (1.0 / 65025.0)), mIp = s1 * (inv * (1.0 / 255.0));
-                                const double var = fma(-mI, mI, mII), cov = fma(-mI, mp, mIp);
-                                const double a = cov * gf_rcp(var + eps);
-                                ab[n][0] = a; ab[n][1] = fma(-a, mI, mp);
-                            }
-                            if (!px1) { ab[1][0] = 0.0; ab[1][1] = 0.0; }
-                        }
-                        // rows and columns outside the image hand ZERO a/b to stage 2 (its windows count in-image pixels only)
-                        const v3d_f64x2 va2 = { ab[0][0], ab[1][0] }, vb2 = { ab[0][1], ab[1][1] };
-                        *reinterpret_cast<v3d_f64x2*>(&sAB[hb][hrow][0][2 * hq]) = va2;
-                        *reinterpret_cast<v3d_f64x2*>(&sAB[hb][hrow][1][2 * hq]) = vb2;
-                    }
-                    // ---- V1(p): two input rows enter the column's window ----
-                    if (p < NS) {
-                        const int tA = 2 * p;
-                        const RowIn cur[2] = { nx[0], nx[1] };
-                        nx[0] = fetch_row(tA + 2); nx[1] = fetch_row(tA + 3);
-                        const bool emit = p >= RR;                               // uniform
-#pragma unroll
-                        for (int rr = 0; rr < 2; rr++) {
-                            const int slot = (2 * sp + rr) % R;                  // compile-time ring slot
-                            int gn = 0, Pn = 0;
-                            if (cur[rr].in) {
-                                gn = cur[rr].g;
-                                const int e = ya - 2 * RR + tA + rr;             // (in the image here)
-                                const int wya = (e & 1) ? 3 : 1;
-                                Pn = wya * (wxa * cur[rr].a0 + wxb * cur[rr].a1) + (4 - wya) * (wxa * cur[rr].b0 + wxb * cur[rr].b1);   // 256 p
-                            }
-                            const int go = (int)(ring[slot] & 0xFFu), Po = (int)(ring[slot] >> 8);
-                            ring[slot] = ((uint32_t)Pn << 8) | (uint32_t)gn;
-                            vg += gn - go; vgg += gn * gn - go * go;
-                            vP += Pn - Po; vgP += gn * Pn - go * Po;
-                            if (emit) {
-                                sVq[p & 1][rr][t] = make_int4(vg, vgg, vP, vgP);
-                                const int4 ps = make_int4(vg + gf_partner(vg), vgg + gf_partner(vgg), vP + gf_partner(vP), vgP + gf_partner(vgP));
-                                if (!(t & 1)) sPq[p & 1][rr][t >> 1] = ps;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
-        }
-      } else {
-        // ================= stage 1: guide + depth -> a, b (k_gfm<1>'s arithmetic) =================
-        const bool col_ok = gx >= 0 && gx < W;
+        for (int j = 0; j < (I1 ? 1 : (R + 3) / 4); j++) rgw[j] = 0u;
+        (void)ring; (void)r1; (void)rgw;
+        // I1: x2 bilinear source columns and weights (quarters): even x = 2k: (k-1, k) x (1, 3); odd: (k, k+1) x (3, 1)
+        // general: bilinear source coordinates, separable: the x part is a per-thread constant, the y part per row
+        int bxa, bxb, wxa = 0, wxb = 0; double bwx = 0.0;
         const double sx = (double)Wlo / (double)W, sy = (double)Hlo / (double)H;
-        const bool pair_in = 2 * hq >= RR && 2 * hq < COLS - RR;      // a/b columns of the strip
-        const bool px0 = pair_in && hgx >= 0 && hgx < W, px1 = pair_in && hgx + 1 >= 0 && hgx + 1 < W;
-        int bxa, bxb; double bwx;
-        {
+        if constexpr (I1) {
+            const int kx = gx >> 1;
+            bxa = min(max((gx & 1) ? kx : kx - 1, 0), Wlo - 1); bxb = min(max((gx & 1) ? kx + 1 : kx, 0), Wlo - 1);
+            wxa = (gx & 1) ? 3 : 1; wxb = 4 - wxa;
+        } else {
             const double fx = (gx + 0.5) * sx - 0.5, x0f = floor(fx);
             bwx = fx - x0f;
             bxa = min(max((int)x0f, 0), Wlo - 1); bxb = min(max((int)x0f + 1, 0), Wlo - 1);
         }
-        double r1[R], v0 = 0.0, v1 = 0.0;        // p ring, sum p, sum g*p
-        uint32_t rgw[(R + 3) / 4];               // g ring, one BYTE per row (the guide is 8-bit): 5 registers instead of 17 keep
-        int vg = 0, vgg = 0;                     //   the kernel inside the 128 VGPRs of four waves per SIMD; sum g, sum g*g
-#pragma unroll
-        for (int j = 0; j < R; j++) r1[j] = 0.0;
-#pragma unroll
-        for (int j = 0; j < (R + 3) / 4; j++) rgw[j] = 0u;
-        struct RowIn { int g; float a0, a1, b0, b1; bool in; };
-        const int gxc = min(max(gx, 0), W - 1);
-        auto fetch_row = [&](int tt) -> RowIn {        // unconditional loads from clamped addresses (see k_gfm)
+        (void)wxa; (void)wxb; (void)bwx;
+        // inputs of the four rows a step consumes, fetched one step ahead; loads UNCONDITIONAL, from clamped addresses (see k_gfm)
+        struct RowIn { int g; typename std::conditional<I1, int, float>::type a0, a1, b0, b1; bool in; };
+        auto fetch_row = [&](int tt) -> RowIn {
             RowIn q;
             const int e = ya - 2 * RR + tt;                                      // input row entering the window
             q.in = col_ok && e >= 0 && e < H && tt < nrows;
-            const size_t o = (size_t)min(max(e, 0), H - 1) * W + gxc;
-            q.g = guide[o];
-            const double fy = (e + 0.5) * sy - 0.5, y0f = floor(fy);
-            const TD* ra = depth_lo + (size_t)min(max((int)y0f, 0), Hlo - 1) * Wlo;
-            const TD* rb = depth_lo + (size_t)min(max((int)y0f + 1, 0), Hlo - 1) * Wlo;
-            q.a0 = gf_ld(ra, bxa); q.a1 = gf_ld(ra, bxb); q.b0 = gf_ld(rb, bxa); q.b1 = gf_ld(rb, bxb);
+            const int ec = min(max(e, 0), H - 1);
+            q.g = guide[(size_t)ec * W + gxc];
+            if constexpr (I1) {
+                const int ky = ec >> 1;
+                const TD* ra = depth_lo + (size_t)min(max((ec & 1) ? ky : ky - 1, 0), Hlo - 1) * Wlo;
+                const TD* rb = depth_lo + (size_t)min(max((ec & 1) ? ky + 1 : ky, 0), Hlo - 1) * Wlo;
+                q.a0 = max((int)ra[bxa], 0); q.a1 = max((int)ra[bxb], 0); q.b0 = max((int)rb[bxa], 0); q.b1 = max((int)rb[bxb], 0);   // depth.py:374: <= 0 -> 0
+            } else {
+                const double fy = (e + 0.5) * sy - 0.5, y0f = floor(fy);
+                const TD* ra = depth_lo + (size_t)min(max((int)y0f, 0), Hlo - 1) * Wlo;
+                const TD* rb = depth_lo + (size_t)min(max((int)y0f + 1, 0), Hlo - 1) * Wlo;
+                q.a0 = gf_ld(ra, bxa); q.a1 = gf_ld(ra, bxb); q.b0 = gf_ld(rb, bxa); q.b1 = gf_ld(rb, bxb);
+            }
             return q;
         };
-        RowIn nx[2] = { fetch_row(0), fetch_row(1) };
+        RowIn nx[4] = { fetch_row(0), fetch_row(1), fetch_row(2), fetch_row(3) };
         for (int p0 = 0; p0 < NP; p0 += R) {
-#pragma unroll
+#pragma clang loop unroll(full)
             for (int sp = 0; sp < R; sp++) {
                 const int p = p0 + sp;
                 if (p < NP) {                                                    // uniform
-                    // (thread constants of the horizontal phase are re-derived per phase, see stage 2: nothing hoisted, nothing spilled)
+                    // (thread constants of the horizontal phase are re-derived per phase: nothing hoisted, nothing spilled)
                     int tl = t;
                     asm volatile("" : "+v"(tl));
-                    const int hrow = tl / HP, hq = tl % HP, hgx = gx0 + 2 * hq;
-                    // ---- H1(p-1): window sums of the row pair V1(p-1) left in LDS -> a, b of two pixels -> sAB ----
+                    const int hrow = tl / HR, c0 = 4 * (tl % HR), hgx = gx0 + c0;  // run: outputs c0 .. c0+3 of row hrow
+                    // ---- H1(p-1): window sums of the four rows V1(p-1) left in LDS -> a, b of four pixels -> the a/b ring ----
                     const int j = p - 1;
-                    if (j >= RR && j < NS && pair_in) {
-                        const int hb = j & 1;
-                        const int y = ya - 3 * RR + 2 * j + hrow;                // centre row of this window
-                        double ab[2][2] = { { 0.0, 0.0 }, { 0.0, 0.0 } };
-                        if (y >= 0 && y < H && px0) {
-                            double fq[2], lq[2], cq[2];
+                    if (j >= RR / 2 && j < NS) {                                 // uniform
+                        const int y = ya - 3 * RR + 4 * j + hrow;                // centre row of this window
+                        double a[4] = { 0.0, 0.0, 0.0, 0.0 }, b[4] = { 0.0, 0.0, 0.0, 0.0 };
+                        // a/b columns of the strip; hgx is a multiple of 4, so a run is left of the image or not at all
+                        if (c0 >= RR && c0 < COLS - RR && y >= 0 && y < H && hgx >= 0 && hgx < W) {
+                            int sg[4], sgg[4]; double sp_[4], sgp[4];
+                            if constexpr (I1) {
+                                int4 s[4];
+                                gf_run4<RR>(&sVq[j & 1][hrow][0], c0, s);
 #pragma unroll
-                            for (int q = 0; q < 2; q++) {
-                                const v3d_f64x2* d = reinterpret_cast<const v3d_f64x2*>(&sV1[hb][hrow][q][0]) + (hq - RR / 2);
-                                double f = 0.0, l = 0.0, c = 0.0;
-#pragma unroll
-                                for (int ch = 0; ch <= RR; ch += GF_CH) {
-                                    v3d_f64x2 w[GF_CH];
-#pragma unroll
-                                    for (int i = 0; i < GF_CH; i++) if (ch + i <= RR) w[i] = d[ch + i];
-#pragma unroll
-                                    for (int i = 0; i < GF_CH; i++) if (ch + i <= RR) {
-                                        if (ch + i == 0) { f = w[i].x; c = w[i].y; }
-                                        else if (ch + i == RR) { c += w[i].x; l = w[i].y; }
-                                        else { c += w[i].x; c += w[i].y; }
-                                    }
-                                    asm volatile("" : "+v"(c) :: "memory");
+                                for (int n = 0; n < 4; n++) {
+                                    sg[n] = s[n].x; sgg[n] = s[n].y;
+                                    sp_[n] = (double)s[n].z * (1.0 / 256.0); sgp[n] = (double)s[n].w * (1.0 / 256.0);   // exact
                                 }
-                                fq[q] = f; lq[q] = l; cq[q] = c;
+                            } else {
+                                int2 si[4];
+                                gf_run4<RR>(&sVi[j & 1][hrow][0], c0, si);
+                                gf_run4<RR>(&sV1[j & 1][hrow][0][0], c0, sp_);
+                                gf_run4<RR>(&sV1[j & 1][hrow][1][0], c0, sgp);
+#pragma unroll
+                                for (int n = 0; n < 4; n++) { sg[n] = si[n].x; sgg[n] = si[n].y; }
                             }
-                            int g0 = 0, gg0 = 0, gl = 0, ggl = 0, cg = 0, cgg = 0;
-                            {
-                                const int4* gi = reinterpret_cast<const int4*>(&sVi[hb][hrow][0]) + (hq - RR / 2);
+                            gf_solve4<RR>(sg, sgg, sp_, sgp, hgx, y, W, H, eps, a, b);
 #pragma unroll
-                                for (int ch = 0; ch <= RR; ch += 3) {
-                                    int4 u[3];
-#pragma unroll
-                                    for (int i = 0; i < 3; i++) if (ch + i <= RR) u[i] = gi[ch + i];
-#pragma unroll
-                                    for (int i = 0; i < 3; i++) if (ch + i <= RR) {
-                                        if (ch + i == 0) { g0 = u[i].x; gg0 = u[i].y; cg = u[i].z; cgg = u[i].w; }
-                                        else if (ch + i == RR) { cg += u[i].x; cgg += u[i].y; gl = u[i].z; ggl = u[i].w; }
-                                        else { cg += u[i].x + u[i].z; cgg += u[i].y + u[i].w; }
-                                    }
-                                    asm volatile("" : "+v"(cg), "+v"(cgg) :: "memory");
-                                }
-                            }
-                            const double s0a = cq[0] + fq[0], s0b = cq[0] + lq[0], s1a = cq[1] + fq[1], s1b = cq[1] + lq[1];
-                            const int cy = min(y + RR, H - 1) - max(y - RR, 0) + 1;
-                            const int cx0 = min(hgx + RR, W - 1) - max(hgx - RR, 0) + 1, cx1 = min(hgx + 1 + RR, W - 1) - max(hgx + 1 - RR, 0) + 1;
-                            // away from the image border every window holds (2r+1)^2 pixels: a wave whose pixels are all interior
-                            // (the common case) skips both reciprocal refinements (~10 f64 instructions per pixel pair)
-                            const double inva = gf_rcp((double)(cx0 * cy)), invb = cx1 == cx0 ? inva : gf_rcp((double)(cx1 * cy));
-                            const int sga = cg + g0, sgb = cg + gl, sgga = cgg + gg0, sggb = cgg + ggl;
-#pragma unroll
-                            for (int n = 0; n < 2; n++) {
-                                const double inv = n ? invb : inva;
-                                const double mI = (double)(n ? sgb : sga) * (inv * (1.0 / 255.0)), mp = (n ? s0b : s0a) * inv;
-                                const double mII = (double)(n ? sggb : sgga) * (inv * (1.0 / 65025.0)), mIp = (n ? s1b : s1a) * (inv * (1.0 / 255.0));
-                                const double var = fma(-mI, mI, mII), cov = fma(-mI, mp, mIp);
-                                const double a = cov * gf_rcp(var + eps);
-                                ab[n][0] = a; ab[n][1] = fma(-a, mI, mp);
-                            }
-                            if (!px1) { ab[1][0] = 0.0; ab[1][1] = 0.0; }
+                            for (int n = 0; n < 4; n++) if (hgx + n >= W) { a[n] = 0.0; b[n] = 0.0; }
                         }
-                        // rows and columns outside the image hand ZERO a/b to stage 2 (its windows count in-image pixels only)
-                        const v3d_f64x2 va2 = { ab[0][0], ab[1][0] }, vb2 = { ab[0][1], ab[1][1] };
-                        *reinterpret_cast<v3d_f64x2*>(&sAB[hb][hrow][0][2 * hq]) = va2;
-                        *reinterpret_cast<v3d_f64x2*>(&sAB[hb][hrow][1][2 * hq]) = vb2;
+                        // rows and columns outside the image (and the strip's halo) hand ZERO a/b to stage 2 (its windows count
+                        // in-image pixels only); every column of the four rows is written
+                        double* ab = &sAB[j % 3][hrow][0][0];
+                        const int e0 = 2 * gf_swz2(c0 >> 1), e1 = 2 * gf_swz2((c0 >> 1) + 1);
+                        *reinterpret_cast<v3d_f64x2*>(ab + e0) = v3d_f64x2{ a[0], a[1] };
+                        *reinterpret_cast<v3d_f64x2*>(ab + e1) = v3d_f64x2{ a[2], a[3] };
+                        *reinterpret_cast<v3d_f64x2*>(ab + COLS + e0) = v3d_f64x2{ b[0], b[1] };
+                        *reinterpret_cast<v3d_f64x2*>(ab + COLS + e1) = v3d_f64x2{ b[2], b[3] };
                     }
-                    // ---- V1(p): two input rows enter the column's window ----
+                    // ---- V1(p): four input rows enter the column's window ----
                     if (p < NS) {
-                        const int tA = 2 * p;
-                        const RowIn cur[2] = { nx[0], nx[1] };
-                        nx[0] = fetch_row(tA + 2); nx[1] = fetch_row(tA + 3);
-                        const bool emit = p >= RR;                               // uniform
+                        const int tA = 4 * p;
+                        const RowIn cur[4] = { nx[0], nx[1], nx[2], nx[3] };
 #pragma unroll
-                        for (int rr = 0; rr < 2; rr++) {
-                            const int slot = (2 * sp + rr) % R;                  // compile-time ring slot
-                            int gn = 0; double pn = 0.0;
-                            if (cur[rr].in) {
-                                gn = cur[rr].g;
-                                const int e = ya - 2 * RR + tA + rr;
-                                const double fy = (e + 0.5) * sy - 0.5, wy = fy - floor(fy);
-                                const double a0 = (double)cur[rr].a0, b0 = (double)cur[rr].b0;
-                                const double top = fma(bwx, (double)cur[rr].a1 - a0, a0);
-                                const double bot = fma(bwx, (double)cur[rr].b1 - b0, b0);
-                                pn = fma(wy, bot - top, top);
-                            }
-                            const int go = (int)((rgw[slot >> 2] >> (8 * (slot & 3))) & 0xFFu); const double po = r1[slot];
-                            rgw[slot >> 2] = (rgw[slot >> 2] & ~(0xFFu << (8 * (slot & 3)))) | ((uint32_t)gn << (8 * (slot & 3)));
-                            r1[slot] = pn;
-                            vg += gn - go; vgg += gn * gn - go * go;
-                            v0 += pn - po; v1 = fma((double)gn, pn, fma(-(double)go, po, v1));
-                            if (emit) {
-                                sV1[p & 1][rr][0][t] = v0; sV1[p & 1][rr][1][t] = v1;
-                                sVi[p & 1][rr][t] = make_int2(vg, vgg);
+                        for (int k = 0; k < 4; k++) nx[k] = fetch_row(tA + 4 + k);
+                        const bool emit = p >= RR / 2;                           // uniform (2r rows of warm-up: a multiple of 4)
+#pragma unroll
+                        for (int rr = 0; rr < 4; rr++) {
+                            const int slot = (4 * sp + rr) % R;                  // compile-time ring slot
+                            const int e = ya - 2 * RR + tA + rr;                 // (in the image when cur[rr].in)
+                            if constexpr (I1) {
+                                int gn = 0, Pn = 0;
+                                if (cur[rr].in) {
+                                    gn = cur[rr].g;
+                                    const int wya = (e & 1) ? 3 : 1;
+                                    Pn = wya * (wxa * cur[rr].a0 + wxb * cur[rr].a1) + (4 - wya) * (wxa * cur[rr].b0 + wxb * cur[rr].b1);   // 256 p
+                                }
+                                const int go = (int)(ring[slot] & 0xFFu), Po = (int)(ring[slot] >> 8);
+                                ring[slot] = ((uint32_t)Pn << 8) | (uint32_t)gn;
+                                vg += gn - go; vgg += gn * gn - go * go;
+                                vP += Pn - Po; vgP += gn * Pn - go * Po;
+                                if (emit) sVq[p & 1][rr][gf_swz4(t)] = make_int4(vg, vgg, vP, vgP);
+                            } else {
+                                int gn = 0; double pn = 0.0;
+                                if (cur[rr].in) {
+                                    gn = cur[rr].g;
+                                    const double fy = (e + 0.5) * sy - 0.5, wy = fy - floor(fy);
+                                    const double a0 = (double)cur[rr].a0, b0 = (double)cur[rr].b0;
+                                    const double top = fma(bwx, (double)cur[rr].a1 - a0, a0);
+                                    const double bot = fma(bwx, (double)cur[rr].b1 - b0, b0);
+                                    pn = fma(wy, bot - top, top);
+                                }
+                                const int go = (int)((rgw[slot >> 2] >> (8 * (slot & 3))) & 0xFFu); const double po = r1[slot];
+                                rgw[slot >> 2] = (rgw[slot >> 2] & ~(0xFFu << (8 * (slot & 3)))) | ((uint32_t)gn << (8 * (slot & 3)));
+                                r1[slot] = pn;
+                                vg += gn - go; vgg += gn * gn - go * go;
+                                v0 += pn - po; v1 = fma((double)gn, pn, fma(-(double)go, po, v1));
+                                if (emit) {
+                                    const int ct = gf_c8(t);
+                                    sV1[p & 1][rr][0][ct] = v0; sV1[p & 1][rr][1][ct] = v1;
+                                    sVi[p & 1][rr][ct] = make_int2(vg, vgg);
+                                }
                             }
                         }
                     }
@@ -710,17 +695,13 @@ __global__ __launch_bounds__(2 * COLS, 4) void k_gff(const TD* __restrict__ dept
                 }
             }
         }
-      }
     } else {
         // ================= stage 2: a, b -> q (k_gfm<2>'s arithmetic) =================
-        const bool pair_out = 2 * hq >= 2 * RR && 2 * hq < COLS - 2 * RR;           // output columns of the strip
-        const bool px0 = pair_out && hgx < W, px1 = pair_out && hgx + 1 < W;
-        const bool vec_ok = px1 && (W & 1) == 0;
         double r0[R], r1[R], va = 0.0, vb = 0.0;
 #pragma unroll
         for (int j = 0; j < R; j++) { r0[j] = 0.0; r1[j] = 0.0; }
         for (int p0 = 0; p0 < NP; p0 += R) {
-#pragma unroll
+#pragma clang loop unroll(full)
             for (int sp = 0; sp < R; sp++) {
                 const int p = p0 + sp;
                 if (p < NP) {                                                    // uniform
@@ -729,67 +710,64 @@ __global__ __launch_bounds__(2 * COLS, 4) void k_gff(const TD* __restrict__ dept
                     // room to keep LDS addresses, window widths and column indices live across phases -- hoisted, they spill.
                     int tl = t;
                     asm volatile("" : "+v"(tl));
-                    const int hrow = tl / HP, hq = tl % HP, hgx = gx0 + 2 * hq;
-                    // ---- H2(p-3): window sums of the a/b row pair -> q of two pixels ----
+                    const int hrow = tl / HR, c0 = 4 * (tl % HR), hgx = gx0 + c0;
+                    // ---- H2(p-3): window sums of the a/b column sums -> q of four pixels ----
                     {
                         const int j = p - 3;
-                        const int y = ya - 4 * RR + 2 * j + hrow;
-                        if (j >= 2 * RR && j < NS && px0 && y < yb) {
-                            const int hb = j & 1;
-                            // per plane: the total of the r + 1 aligned pair sums hq - r/2 .. hq + r/2 (columns 2hq - r .. 2hq + r + 1), then
-                            // output 0 drops the last column, output 1 the first
-                            double wa[2], wb[2];
-#pragma unroll
-                            for (int q = 0; q < 2; q++) {
-                                const double* d = &sP2[hb][hrow][q][hq - RR / 2];
-                                const double f = sV2[hb][hrow][q][2 * hq - RR], l = sV2[hb][hrow][q][2 * hq + RR + 1];
-                                double c = 0.0;
-#pragma unroll
-                                for (int ch = 0; ch <= RR; ch += 3) {
-                                    double w[3];
-#pragma unroll
-                                    for (int i = 0; i < 3; i++) if (ch + i <= RR) w[i] = d[ch + i];
-#pragma unroll
-                                    for (int i = 0; i < 3; i++) if (ch + i <= RR) c += w[i];
-                                    asm volatile("" : "+v"(c) :: "memory");
-                                }
-                                wa[q] = c - l; wb[q] = c - f;
-                                asm volatile("" : "+v"(wa[q]), "+v"(wb[q]) :: "memory");
-                            }
-                            const double s0a = wa[0], s0b = wb[0], s1a = wa[1], s1b = wb[1];
+                        const int y = ya - 4 * RR + 4 * j + hrow;
+                        if (j >= RR && j < NS && c0 >= 2 * RR && c0 < COLS - 2 * RR && hgx < W && y < yb) {
+                            double sa[4], sb[4];
+                            gf_run4<RR>(&sAB[j % 3][hrow][0][0], c0, sa);
+                            gf_run4<RR>(&sAB[j % 3][hrow][1][0], c0, sb);
                             const int cy = min(y + RR, H - 1) - max(y - RR, 0) + 1;
-                            const int cx0 = min(hgx + RR, W - 1) - max(hgx - RR, 0) + 1, cx1 = min(hgx + 1 + RR, W - 1) - max(hgx + 1 - RR, 0) + 1;
-                            const double inva = gf_rcp((double)(cx0 * cy)), invb = cx1 == cx0 ? inva : gf_rcp((double)(cx1 * cy));
+                            int cx[4];
+#pragma unroll
+                            for (int n = 0; n < 4; n++) cx[n] = min(hgx + n + RR, W - 1) - max(hgx + n - RR, 0) + 1;
+                            const double inv0 = gf_rcp((double)(cx[0] * cy));
                             const size_t o = (size_t)y * W + hgx;
-                            const double Ia = (double)guide[o] * (1.0 / 255.0);
-                            const double Ib = px1 ? (double)guide[o + 1] * (1.0 / 255.0) : 0.0;
-                            const float qa = (float)((s0a * inva) * Ia + (s1a * inva)), qb = (float)((s0b * invb) * Ib + (s1b * invb));
+                            const bool all_in = hgx + 3 < W;
+                            const bool vec_ok = all_in && (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(out + o) | reinterpret_cast<uintptr_t>(guide + o)) & 3) == 0
+                                                && (reinterpret_cast<uintptr_t>(out + o) & 15) == 0;
+                            int g[4];
                             if (vec_ok) {
-                                v3d_f32x2 vq = { qa, qb };
-                                __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x2*>(out + o));
+                                const uint32_t g4 = *reinterpret_cast<const uint32_t*>(guide + o);
+#pragma unroll
+                                for (int n = 0; n < 4; n++) g[n] = (g4 >> (8 * n)) & 0xFF;
                             } else {
-                                out[o] = qa;
-                                if (px1) out[o + 1] = qb;
+#pragma unroll
+                                for (int n = 0; n < 4; n++) g[n] = hgx + n < W ? guide[o + n] : 0;
+                            }
+                            float q[4];
+#pragma unroll
+                            for (int n = 0; n < 4; n++) {
+                                const double inv = (n == 0 || cx[n] == cx[0]) ? inv0 : gf_rcp((double)(cx[n] * cy));
+                                const double I = (double)g[n] * (1.0 / 255.0);
+                                q[n] = (float)((sa[n] * inv) * I + (sb[n] * inv));
+                            }
+                            if (vec_ok) {
+                                const v3d_f32x4 vq = { q[0], q[1], q[2], q[3] };
+                                __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x4*>(out + o));
+                            } else {
+#pragma unroll
+                                for (int n = 0; n < 4; n++) if (hgx + n < W) out[o + n] = q[n];
                             }
                         }
                     }
-                    // ---- V2(p-2): the a/b row pair H1(p-2) left in LDS enters the column's window ----
+                    // ---- V2(p-2): the four a/b rows H1(p-2) left in the ring enter the column's window; their column sums
+                    //      replace them in place ----
                     {
                         const int j = p - 2;
-                        if (j >= RR && j < NS) {
-                            const bool emit = j >= 2 * RR;                       // uniform
+                        if (j >= RR / 2 && j < NS) {
+                            const bool emit = j >= RR;                           // uniform
+                            double* col = &sAB[j % 3][0][0][gf_c8(tl)];
 #pragma unroll
-                            for (int rr = 0; rr < 2; rr++) {
-                                const int slot = (2 * sp + rr) % R;              // compile-time ring slot
-                                const double n0 = sAB[j & 1][rr][0][tl], n1 = sAB[j & 1][rr][1][tl];
+                            for (int rr = 0; rr < 4; rr++) {
+                                const int slot = (4 * sp + rr) % R;              // compile-time ring slot
+                                const double n0 = col[rr * 2 * COLS], n1 = col[rr * 2 * COLS + COLS];
                                 const double o0 = r0[slot], o1 = r1[slot];
                                 r0[slot] = n0; r1[slot] = n1;
                                 va += n0 - o0; vb += n1 - o1;
-                                if (emit) {
-                                    sV2[j & 1][rr][0][tl] = va; sV2[j & 1][rr][1][tl] = vb;
-                                    const double pa = va + gf_partner(va), pb = vb + gf_partner(vb);        // aligned pair sums (both lanes of a pair form the same)
-                                    if (!(tl & 1)) { sP2[j & 1][rr][0][tl >> 1] = pa; sP2[j & 1][rr][1][tl >> 1] = pb; }
-                                }
+                                if (emit) { col[rr * 2 * COLS] = va; col[rr * 2 * COLS + COLS] = vb; }
                             }
                         }
                     }
@@ -804,16 +782,18 @@ template <int RR, typename TD>
 static void launch_gff(const TD* depth_lo, int Wlo, int Hlo, const uint8_t* guide, int W, int H, double eps,
                        float* out, int n, size_t depth_stride, size_t guide_stride, hipStream_t st)
 {
-    const int cols = g_v3d_opt.gf_cols == 512 ? 512 : 256;
+    // int16 disparity, exact 2x: stage 1 in exact integers (80 KB of LDS: two workgroups per CU); the f64 route needs 96 KB (one)
+    bool i1 = false;
+    if constexpr (std::is_same<TD, int16_t>::value) i1 = g_v3d_opt.gf_int1 && W == 2 * Wlo && H == 2 * Hlo;
+    const int cols = g_v3d_opt.gf_cols == 512 && i1 ? 512 : 256;     // 512-column strips: I1 only (160 KB, one workgroup per CU)
     int band = g_v3d_opt.gf_band;
     if (band <= 0) {
         // auto: every band pays 4r warm-up rows and the launch runs in whole "rounds" of the resident workgroups (equal-length
-        // workgroups: two per CU at 256 columns, one at 512), so pick the band count that minimises rounds x (band + 4r) --
-        // e.g. 34 4K frames on 256 CUs: 8 bands of 270 rows are 9.56 rounds = 10 x 302 row steps, 5 bands of 432 are 5.98 = 6 x 464
+        // workgroups), so pick the band count that minimises rounds x (band + 4r)
         int dev = 0, ncu = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const long slots = (long)ncu * (cols == 512 ? 1 : 2), strips = v3d_cdiv(W, cols - 4 * RR);
+        const long slots = (long)ncu * (cols == 256 && i1 ? 2 : 1), strips = v3d_cdiv(W, cols - 4 * RR);
         long best = -1;
         for (int nb = 1; nb <= 64 && nb <= H; nb++) {
             const int b = (v3d_cdiv(H, nb) + 1) & ~1;
@@ -821,14 +801,13 @@ static void launch_gff(const TD* depth_lo, int Wlo, int Hlo, const uint8_t* guid
             if (best < 0 || cost < best) { best = cost; band = b; }
         }
     }
-    if (g_v3d_opt.gf_cols == 512) {        // 512-column strips, 16 waves, one workgroup per CU: half the strip-halo recompute
-        const dim3 grid(v3d_cdiv(W, 512 - 4 * RR), v3d_cdiv(H, band), n);
-        hipLaunchKernelGGL((k_gff<RR, 512, TD, false>), grid, dim3(1024), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
-        return;
-    }
-    const dim3 grid(v3d_cdiv(W, 256 - 4 * RR), v3d_cdiv(H, band), n);
+    const dim3 grid(v3d_cdiv(W, cols - 4 * RR), v3d_cdiv(H, band), n);
     if constexpr (std::is_same<TD, int16_t>::value) {
-        if (g_v3d_opt.gf_int1 && W == 2 * Wlo && H == 2 * Hlo) {          // int16 disparity, exact 2x: stage 1 in exact integers
+        if (i1 && cols == 512) {
+            hipLaunchKernelGGL((k_gff<RR, 512, TD, true>), grid, dim3(1024), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
+            return;
+        }
+        if (i1) {
             hipLaunchKernelGGL((k_gff<RR, 256, TD, true>), grid, dim3(512), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
             return;
         }
