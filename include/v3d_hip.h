@@ -179,9 +179,10 @@ int v3d_guided_upscale_batch(const float* depth_lo, int Wlo, int Hlo, size_t dep
    depth.py:374 `disparity[disparity <= 0] = 0` happen as the values are loaded, so the stereo-only pipeline
    (sgbm -> upscale) never writes or re-reads the float32 depth plane.  Bit-identical to v3d_disp_to_depth followed by
    v3d_guided_upscale_batch.  Frame f at disp16 + f*disp_stride (int16 elements).
-   Domain: disparities up to 16 * 113 = 1820 (this build's matcher, numDisparities = 64, never exceeds 1023).  For an exact 2x
-   upscale the filter's first stage then runs in exact int32 sums (sum of g * 256 p over a window stays below 2^31); a caller
-   feeding larger values must switch that off first: v3d_set_option("gf_int1", 0). */
+   Domain: disparities (x16 values) up to 1821 (this build's matcher, numDisparities = 64, never exceeds 1023).  For an exact 2x
+   upscale and r <= 8 the filter's first stage runs in exact int32 sums: 256 p <= 16 d, so over a 17 x 17 window
+   sum g * 256 p <= 289 * 255 * 16 * d < 2^31 => d <= 1821.  A caller feeding larger values must switch that route off first:
+   v3d_set_option("gf_int1", 0) (the f64 route takes the whole int16 range).  Nothing checks the values on the device. */
 int v3d_guided_upscale_disp16_batch(const int16_t* disp16, int Wlo, int Hlo, size_t disp_stride, const uint8_t* guide,
                                     int Whi, int Hhi, size_t guide_stride, int n, int r, float eps, float* out,
                                     void* ws, void* stream);

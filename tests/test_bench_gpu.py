@@ -106,3 +106,41 @@ def test_bench_two_ranks_over_rccl(tmp_path, single_rank_frame0):
     assert res["config"]["guide_exchange"] == "scatter"
     got = np.load(out)
     assert np.array_equal(got["disp"], single_rank_frame0["disp"]) and np.array_equal(got["q"], single_rank_frame0["q"])
+
+
+@pytest.mark.timeout(900)
+def test_bench_default_batch_dump_meets_the_oracle_on_every_frame(tmp_path, oracle):
+    """bench.py at its DEFAULT batch (one full lock-step launch, B frames; its own parity_check looks at frame 0 only): frame 0
+    of the 4K depth and every row of the dumped sample -- which reaches every frame index 0 .. B-1 -- within 1e-3 of the float64
+    oracle of the base frame that position carries (frame f holds synthetic frame f % N_DISTINCT, as bench builds it)"""
+    from concurrent.futures import ThreadPoolExecutor
+    import bench
+    from test_guided_gpu import RTOL, _rel_err
+    from video_3d_pipeline import _native as N, synthetic as syn
+    probe = N.StereoSGBM(bench.W, bench.H, 1)
+    B = probe.get_option("vdd_frames_per_launch_dpl8")
+    probe.close()
+    assert B >= 2, f"bench batch B = {B}"
+    d = tmp_path / "out"
+    res = _run([sys.executable, "bench.py", "--gpus", "1", "--workload", "full", "--steps", "1", "--warmup", "1",
+                "--no-cpu-baseline", "--no-e2e", "--dump-outputs", str(d)], timeout=600)
+    assert res["config"]["frames_per_step_per_gpu"] == B and res["lockstep_timeouts"] == 0, (B, res["config"])
+    nd = min(B, bench.N_DISTINCT)
+
+    def want(i):
+        sbs, guide = syn.sbs_frame(bench.W, bench.H, i), syn.guide_frame(bench.W, bench.H, i, bench.SCALE)
+        disp = oracle.sgbm_compute(*oracle.sbs_to_gray(sbs, True))
+        return oracle.guided_upscale(oracle.disp_to_depth(disp), guide, bench.GF_R, bench.GF_EPS)
+    with ThreadPoolExecutor(max(1, min(nd, 16, len(os.sched_getaffinity(0))))) as ex:
+        q = list(ex.map(want, range(nd)))
+    f0 = np.load(d / "depth4k_frame0.npy").astype(np.float64)
+    err = _rel_err(f0, q[0])
+    assert err.max() <= RTOL, f"B = {B}, frame 0: max rel err {err.max():.3e}"
+    rows, idx = np.load(d / "depth4k_rows.npy"), np.load(d / "depth4k_rows_index.npy").astype(np.int64)
+    assert rows.shape == (len(idx), bench.W * bench.SCALE)
+    assert set(idx[:, 0].tolist()) == set(range(B)), f"B = {B}: the sample misses frames {sorted(set(range(B)) - set(idx[:, 0].tolist()))}"
+    floor = [1e-6 * max(float(np.abs(w).max()), 1e-30) for w in q]        # _rel_err's floor, of the whole frame
+    for (f, y), row in zip(idx, rows):
+        w = q[f % nd][y]
+        err = np.abs(row.astype(np.float64) - w) / np.maximum(np.abs(w), floor[f % nd])
+        assert err.max() <= RTOL, f"B = {B}, frame {f} (base {f % nd}) row {y}: max rel err {err.max():.3e}"

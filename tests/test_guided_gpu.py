@@ -201,3 +201,70 @@ def test_integer_stage1_is_bit_identical_to_the_f64_stage1(native, oracle, Wlo, 
     assert torch.equal(a, b)
     want = oracle.guided_upscale(oracle.disp_to_depth(d[0]), g[0], r, 1e-3)
     assert _rel_err(b[0].cpu().numpy().astype(np.float64), want).max() <= RTOL
+
+
+I1_DMAX = 1821      # the integer first stage's int16 domain: 289 * 255 * 16 * d < 2^31 (include/v3d_hip.h)
+
+
+def _disp16_blocks(seed, Wlo, Hlo, lo, hi, n=2):
+    """int16 disparities (x16) and their exact-2x guides: random texture in [-16, hi] with zeros and -16 mixed in, and large
+    blocks of guide 255 over disparities in [lo, hi] (one of them the constant hi) where a window's sum g * 256 p is largest"""
+    rng = np.random.default_rng(seed)
+    d = rng.integers(-16, hi + 1, (n, Hlo, Wlo)).astype(np.int64)
+    d[rng.random(d.shape) < 0.08] = 0
+    d[rng.random(d.shape) < 0.08] = -16
+    g = rng.integers(0, 256, (n, 2 * Hlo, 2 * Wlo)).astype(np.uint8)
+    for f in range(n):
+        for k in range(6):
+            bw, bh = int(rng.integers(24, 60)), int(rng.integers(24, 50))
+            x, y = int(rng.integers(0, Wlo - bw)), int(rng.integers(0, Hlo - bh))
+            d[f, y:y + bh, x:x + bw] = hi if k == 0 else rng.integers(lo, hi + 1, (bh, bw))
+            g[f, 2 * y:2 * (y + bh), 2 * x:2 * (x + bw)] = 255
+    d[:, 0, 0], d[:, 0, 1], d[:, -1, -1] = hi, hi - 1, lo
+    return d.astype(np.int16), g
+
+
+@pytest.mark.parametrize("cols", [256, 512])
+@pytest.mark.parametrize("r", [4, 8])
+def test_integer_stage1_at_the_edge_of_its_domain(native, oracle, r, cols):
+    """int16 disparities up to the documented limit (1821 included), with 17 x 17 windows of guide 255 over d in 1700 .. 1821:
+    sum g * 256 p comes within 0.02 % of 2^31 (an 18-column partial sum would pass it).  The integer first stage has the bits
+    of the f64 first stage, and both meet the oracle"""
+    import torch
+    d, g = _disp16_blocks(1000 + 10 * r + cols // 256, 320, 180, 1700, I1_DMAX)
+    assert 289 * 255 * 16 * I1_DMAX < 2 ** 31 <= 306 * 255 * 16 * I1_DMAX
+    dd, gg = native.to_device(d), native.to_device(g)
+    try:
+        native.set_option("gf_cols", cols)
+        native.set_option("gf_int1", 0)
+        a = native.guided_upscale_batch(dd, gg, r, 1e-3)
+        native.set_option("gf_int1", 1)
+        b = native.guided_upscale_batch(dd, gg, r, 1e-3)
+    finally:
+        native.set_option("gf_int1", 1)
+        native.set_option("gf_cols", 256)
+    assert torch.equal(a, b), f"{int((a != b).sum())} pixels differ between the integer and the f64 first stage"
+    for f in range(d.shape[0]):
+        want = oracle.guided_upscale(oracle.disp_to_depth(d[f]), g[f], r, 1e-3)
+        err = _rel_err(b[f].cpu().numpy().astype(np.float64), want)
+        assert err.max() <= RTOL, f"frame {f}: max rel err {err.max():.3e} at {np.unravel_index(err.argmax(), err.shape)}"
+
+
+@pytest.mark.parametrize("r", [4, 8])
+def test_f64_stage1_takes_the_whole_int16_range(native, oracle, r):
+    """with gf_int1 = 0 the int16 route accepts any int16: values up to 32767 (blocks of them under guide 255) and down to
+    -32768 meet the oracle (nothing is asserted of the integer first stage above its domain)"""
+    d, g = _disp16_blocks(2000 + r, 300, 170, 30000, 32767)
+    rng = np.random.default_rng(3000 + r)
+    d[rng.random(d.shape) < 0.1] = -32768
+    d[:, 5:40, 5:40] = 32767
+    dd, gg = native.to_device(d), native.to_device(g)
+    try:
+        native.set_option("gf_int1", 0)
+        got = native.guided_upscale_batch(dd, gg, r, 1e-3)
+    finally:
+        native.set_option("gf_int1", 1)
+    for f in range(d.shape[0]):
+        want = oracle.guided_upscale(oracle.disp_to_depth(d[f]), g[f], r, 1e-3)
+        err = _rel_err(got[f].cpu().numpy().astype(np.float64), want)
+        assert err.max() <= RTOL, f"frame {f}: max rel err {err.max():.3e} at {np.unravel_index(err.argmax(), err.shape)}"

@@ -305,10 +305,11 @@ def test_lockstep_runtime_switch(native, oracle):
 
 
 def test_benchmarked_configuration_bit_exact(native, oracle):
-    """bench.py's own configuration: 1920x1080, 30 frames per call on a max_batch=30 handle.  That is the path the
-    headline number runs and nothing smaller reaches it: k_vdd<8> (128-column strips, the last one ragged: 1856 = 14 x 128
-    + 64), 450 co-resident lock-step workgroups, the XCD tile order of k_cost over 30 frames, batch-wide CCL.
-    Five distinct frames, cycled; EVERY frame of the batch must equal the oracle's bits."""
+    """a BELOW-capacity 1080p launch: 30 frames per call on a max_batch=30 handle, then 16 on the same handle -- k_vdd<8>
+    (128-column strips, the last one ragged: 1856 = 14 x 128 + 64) with fewer co-resident lock-step workgroups than a full
+    launch, the XCD tile order of k_cost over 30 frames, batch-wide CCL.  Five distinct frames, cycled; EVERY frame of the
+    batch must equal the oracle's bits.  bench.py's own batch (one FULL launch, vdd_frames_per_launch_dpl8 frames) and the
+    product's launch splits are tested frame by frame in tests/test_bench_config_gpu.py."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from video_3d_pipeline import synthetic as syn

@@ -484,10 +484,12 @@ __device__ __forceinline__ void gf_run4(const int4* row, int c0, int4 s[4])
         }
         asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w) :: "memory");
     }
+    // the column leaving is subtracted BEFORE the entering one is added: no intermediate spans more than the 2r + 1 columns of a
+    // window, so sum g*P stays below 2^31 on the whole documented domain (an 18-column partial sum passes it from d = 1721 on)
     s[0] = c;
-    s[1] = make_int4(s[0].x + r1.x - l0.x, s[0].y + r1.y - l0.y, s[0].z + r1.z - l0.z, s[0].w + r1.w - l0.w);
-    s[2] = make_int4(s[1].x + r2.x - l1.x, s[1].y + r2.y - l1.y, s[1].z + r2.z - l1.z, s[1].w + r2.w - l1.w);
-    s[3] = make_int4(s[2].x + r3.x - l2.x, s[2].y + r3.y - l2.y, s[2].z + r3.z - l2.z, s[2].w + r3.w - l2.w);
+    s[1] = make_int4(s[0].x - l0.x + r1.x, s[0].y - l0.y + r1.y, s[0].z - l0.z + r1.z, s[0].w - l0.w + r1.w);
+    s[2] = make_int4(s[1].x - l1.x + r2.x, s[1].y - l1.y + r2.y, s[1].z - l1.z + r2.z, s[1].w - l1.w + r2.w);
+    s[3] = make_int4(s[2].x - l2.x + r3.x, s[2].y - l2.y + r3.y, s[2].z - l2.z + r3.z, s[2].w - l2.w + r3.w);
 }
 
 // a, b of the four pixels hgx .. hgx+3 of row y from their window sums {sum g, sum g*g} (exact ints), {sum p, sum g*p}
@@ -511,9 +513,10 @@ __device__ __forceinline__ void gf_solve4(const int sg[4], const int sgg[4], con
     }
 }
 
-// I1 (int16 disparity in, exact 2x upscale): stage 1's four window sums are EXACT INTEGERS.  The disparity is d/16 with d <= 1023
-// and the x2 bilinear weights are {1,3}/4 per axis, so P = 256 p = sum w d (w in {1,3,9}) is an integer <= 16368; over a 17 x 17
-// window sum P < 2^23 and sum g P < 2^31.  The ring holds (P << 8 | g) in ONE register per row, the vertical sums are four int32
+// I1 (int16 disparity in, exact 2x upscale): stage 1's four window sums are EXACT INTEGERS.  The disparity is d/16 (the matcher
+// gives d <= 1023) and the x2 bilinear weights are {1,3}/4 per axis, so P = 256 p = sum w d (w in {1,3,9}, sum w = 16) is an
+// integer <= 16 d; over a 17 x 17 window sum g P <= 289 * 255 * 16 d, below 2^31 for d <= 1821 (the route's domain: r = 4 has
+// 81 instead of 289 and more room; the matcher's 1023 gives sum P < 2^23).  The ring holds (P << 8 | g) in ONE register per row, the vertical sums are four int32
 // and cross the lanes as one int4 per column.  The a/b algebra converts the four exact sums to f64 -- the very values the f64 sums
 // of the general path hold (they are exact there too) -- so the output is bit-identical to it.
 template <int RR, int COLS, typename TD, bool I1>

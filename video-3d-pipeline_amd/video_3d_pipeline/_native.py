@@ -405,7 +405,10 @@ def guided_upscale(depth_lo, guide, r=8, eps=1e-3, out=None):
 def guided_upscale_batch(depth_lo, guide, r=8, eps=1e-3, out=None):
     """depth_lo [N,Hlo,Wlo] (contiguous): float32 depth, or the matcher's int16 disparity x16 (then `/16` and `<= 0 -> 0`
     of depth.py:341, 374 happen inside the filter's loads: same bits, no float plane); guide u8 [N,Hhi,Whi] (frames may be
-    strided) -> f32 [N,Hhi,Whi], one launch"""
+    strided) -> f32 [N,Hhi,Whi], one launch.
+    int16 domain: values up to 1821 (the matcher's never exceed 1023).  An exact 2x upscale with r <= 8 then takes the
+    integer first stage, whose int32 window sums hold 289 * 255 * 16 * d < 2^31; larger values need set_option("gf_int1", 0)
+    first (the f64 route takes the whole int16 range).  Nothing checks this on the device: a check would cost a sync."""
     n, Hlo, Wlo = depth_lo.shape
     _, Hhi, Whi = guide.shape
     if guide.stride(2) != 1 or guide.stride(1) != Whi:
