@@ -13,7 +13,7 @@
  *   v3d_disp_to_depth      depth.py:341 .astype(float32)/16.0 and depth.py:374 clamp <=0 -> 0
  *   v3d_mono_blend         depth.py:344-374 the "hybrid" blend: cv2.resize(mono) INTER_LINEAR, min-max to [0, 64],
  *                          0.7 * disparity + 0.3 * mono, clamp <= 0 -> 0 (the mono map comes from the host: DPT or any provider)
- *   v3d_depth_to_u16       depth.py:397-406 save_depth_map min-max normalisation to uint16
+ *   v3d_depth_to_u16[_batch]  depth.py:397-406 save_depth_map min-max normalisation to uint16
  *   v3d_guided_upscale     upscale.py:21-73 upscale_depth_maps_ffmpeg (`scale` filter), re-specified
  *                          as guided-filter joint upsampling
  *   v3d_corr_lookup        CREStereo recurrent correlation lookup (BASELINE.json config 4; the
@@ -150,6 +150,12 @@ int v3d_disp_to_depth(const int16_t* disp16, size_t n, float* depth_out, void* s
 /* minmax_ws: device scratch of >= 2 floats */
 int v3d_depth_to_u16(const float* depth, size_t n, uint16_t* out, float* minmax_ws, void* stream);
 
+/* n frames in one fixed set of launches: frame f (frame_elems floats at depth + f*frame_stride) -> out + f*frame_elems with
+   its OWN min/max, bit-identical to v3d_depth_to_u16 on that frame alone (same order of operations, max == min -> 0).
+   minmax_ws: device scratch of >= 2n floats; n <= 65535 */
+int v3d_depth_to_u16_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, uint16_t* out,
+                           float* minmax_ws, void* stream);
+
 /* the upscaled depth as the 16-bit sample the PNG sink stores (stands where upscale.py:47-59 hands gray16 frames to the
    encoder): out = clamp(rint(depth), 0, 65535), round-half-to-even */
 int v3d_round_to_u16(const float* depth, size_t n, uint16_t* out, void* stream);
@@ -186,6 +192,15 @@ int v3d_guided_upscale_batch(const float* depth_lo, int Wlo, int Hlo, size_t dep
 int v3d_guided_upscale_disp16_batch(const int16_t* disp16, int Wlo, int Hlo, size_t disp_stride, const uint8_t* guide,
                                     int Whi, int Hhi, size_t guide_stride, int n, int r, float eps, float* out,
                                     void* ws, void* stream);
+/* the same filter between the two 16-bit PNG sequences of the product: depth_lo holds the normalised u16 samples of the 1080p
+   depth maps (what v3d_depth_to_u16 writes), out receives the u16 samples of the 4K maps.  Contract: for every r in [1, 16] and
+   every route (gf_fused 1/0, gf_tiled 1) the output is bit-identical to v3d_guided_upscale_batch on the samples converted to
+   float32 followed by v3d_round_to_u16 -- without the float32 4K plane or the rounding launch.  Stage 1 always runs in f64
+   (sum g * P over a window of u16 samples needs ~37 bits).  Frame f at depth_lo + f*depth_stride (elements), guide +
+   f*guide_stride (bytes), out + f*Whi*Hhi; ws as for v3d_guided_upscale_batch. */
+int v3d_guided_upscale_u16_batch(const uint16_t* depth_lo, int Wlo, int Hlo, size_t depth_stride, const uint8_t* guide,
+                                 int Whi, int Hhi, size_t guide_stride, int n, int r, float eps, uint16_t* out,
+                                 void* ws, void* stream);
 /* BGR [H][W][3] u8 -> luma u8 with the same weights as cvtColor */
 int v3d_bgr_to_gray(const uint8_t* bgr, size_t n_pixels, uint8_t* gray, void* stream);
 

@@ -1,0 +1,122 @@
+"""File-to-file rate of the one-pass SBS -> 4K depth pipeline against the two-CLI chain (depth CLI, then upscale CLI) on the same
+synthetic clip, in one process on one GPU, with the PNG sink and with a raw sink (no zlib).  Prints one JSON line.
+    python tools/pipeline_rate.py [--frames N] [--work DIR]
+The chain's rate is N / (t_depth + t_upscale); every route gets one warm-up run on the same shapes first."""
+import argparse
+import contextlib
+import io
+import json
+import os
+import shutil
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "video-3d-pipeline_amd"))
+
+import numpy as np  # noqa: E402
+
+
+class RawSink:
+    """stands where utils.PngWriterPool stands: raw little-endian samples, written synchronously"""
+
+    def submit(self, path, img_u16):
+        np.ascontiguousarray(img_u16).tofile(str(path) + ".raw")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+def kernel_times(W, H, n=34, reps=5):
+    """ms per call, 34 frames of 4K: guided_upscale_u16_batch against guided_upscale_batch + round_to_u16 on the same u16 input,
+    alternated, best of `reps`"""
+    import torch
+    from video_3d_pipeline import _native as N, synthetic as syn
+    rng = np.random.default_rng(0)
+    lo = torch.from_numpy(rng.integers(0, 65536, (n, H, W), dtype=np.uint16).view(np.int16)).cuda()
+    lo_f = (lo.to(torch.int32) & 0xFFFF).float().contiguous()
+    guide = torch.from_numpy(np.stack([syn.guide_frame(W, H, i % 4) for i in range(n)])).cuda()
+    routes = {"u16_batch": lambda: N.guided_upscale_u16_batch(lo, guide, 8, 1e-3),
+              "float_batch_then_round": lambda: N.round_to_u16(N.guided_upscale_batch(lo_f, guide, 8, 1e-3))}
+    best = {k: float("inf") for k in routes}
+    for k, f in routes.items():
+        f()
+    torch.cuda.synchronize()
+    assert torch.equal(routes["u16_batch"](), routes["float_batch_then_round"]())
+    for _ in range(reps):
+        for k, f in routes.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            best[k] = min(best[k], e0.elapsed_time(e1))
+    return {k + "_ms": v for k, v in best.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=68)
+    ap.add_argument("--work", default="/tmp/pipeline_rate")
+    args = ap.parse_args()
+    from video_3d_pipeline import synthetic as syn
+    from video_3d_pipeline.depth import HybridStereoDepthExtractor
+    from video_3d_pipeline.pipeline import SbsTo4kDepthPipeline
+    from video_3d_pipeline.upscale import SimpleDepthUpscaler
+    from video_3d_pipeline.utils import PngWriterPool
+
+    W, H, N = 1920, 1080, args.frames
+    shutil.rmtree(args.work, ignore_errors=True)
+    os.makedirs(args.work)
+    sbs = [syn.sbs_frame(W, H, i) for i in range(4)]
+    clip = os.path.join(args.work, "sbs.npy")
+    np.save(clip, np.stack([sbs[i % 4] for i in range(N)]))
+    g = [np.repeat(syn.guide_frame(W, H, i)[..., None], 3, axis=2) for i in range(4)]
+    clip4k = os.path.join(args.work, "v4k.npy")
+    np.save(clip4k, np.stack([g[i % 4] for i in range(N)]))
+    del sbs, g
+
+    out = {"frames": N, "sbs": f"{W}x{H}", "guide": f"{2 * W}x{2 * H}", "kernels": kernel_times(W, H)}
+    for sink_name, sink in (("raw", RawSink), ("png", PngWriterPool)):
+        with contextlib.redirect_stdout(io.StringIO()):
+            ex = HybridStereoDepthExtractor(work_dir=os.path.join(args.work, "w"), cache_dir=os.path.join(args.work, "w"),
+                                            stereo_only=True, batch_size=34)
+            ex.writer_pool_factory = sink
+            up = SimpleDepthUpscaler()
+            up.writer_pool_factory = sink
+            pipe = SbsTo4kDepthPipeline(work_dir=os.path.join(args.work, "w"), stereo_only=True, batch_size=34)
+            pipe.writer_pool_factory = sink
+            times = {}
+            for rep in ("warm", "timed"):
+                t0 = time.perf_counter()
+                ddir = ex.process_video_sbs(clip, force_reprocess=True)
+                t1 = time.perf_counter()
+                # the upscale CLI reads depth_*.png: with the raw sink the maps are re-encoded once, outside the timing
+                if sink is RawSink:
+                    from video_3d_pipeline.utils import write_png16
+                    for i in range(N):
+                        f = ddir / f"depth_{i:06d}.png.raw"
+                        write_png16(ddir / f"depth_{i:06d}.png", np.fromfile(f, np.uint16).reshape(H, W))
+                        os.remove(f)
+                t2 = time.perf_counter()
+                up.process_depth_upscaling(str(ddir), clip4k, output_path=os.path.join(args.work, f"cli_{rep}.json"),
+                                           force_reprocess=True)
+                t3 = time.perf_counter()
+                pipe.run(clip, clip4k, output_path=os.path.join(args.work, f"pipe_{rep}.json"), force_reprocess=True)
+                t4 = time.perf_counter()
+                times = {"depth_cli": t1 - t0, "upscale_cli": t3 - t2, "pipeline": t4 - t3}
+                for d in (ddir, os.path.join(args.work, f"cli_{rep}_frames"), os.path.join(args.work, f"pipe_{rep}_frames")):
+                    shutil.rmtree(d, ignore_errors=True)
+        out[sink_name] = {"depth_cli_fps": N / times["depth_cli"], "upscale_cli_fps": N / times["upscale_cli"],
+                          "two_cli_chain_fps": N / (times["depth_cli"] + times["upscale_cli"]),
+                          "pipeline_fps": N / times["pipeline"],
+                          "speedup": (times["depth_cli"] + times["upscale_cli"]) / times["pipeline"]}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -30,6 +30,16 @@ __device__ __forceinline__ double gf_rcp(double x)
 template <typename TD> __device__ __forceinline__ float gf_ld(const TD* p, size_t i);
 template <> __device__ __forceinline__ float gf_ld<float>(const float* p, size_t i) { return p[i]; }
 template <> __device__ __forceinline__ float gf_ld<int16_t>(const int16_t* p, size_t i) { const int d = p[i]; return d > 0 ? (float)d * 0.0625f : 0.f; }
+// or as the normalised 16-bit sample of the depth PNG (read_png16(...).astype(float32) on the device: the same float values)
+template <> __device__ __forceinline__ float gf_ld<uint16_t>(const uint16_t* p, size_t i) { return (float)p[i]; }
+
+// q leaves either as float32 or as the 16-bit sample of the 4K PNG: clamp(rint(q), 0, 65535), NaN -> 0, exactly k_round_u16
+// (v3d_pre.hip) applied to the float32 value the float instantiation stores
+typedef unsigned short v3d_u16x2v __attribute__((ext_vector_type(2)));
+typedef unsigned short v3d_u16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint16_t gf_u16(float q) { const float v = rintf(q); return (uint16_t)(v >= 65535.f ? 65535.f : v > 0.f ? v : 0.f); }
+__device__ __forceinline__ void gf_st(float* p, float q) { *p = q; }
+__device__ __forceinline__ void gf_st(uint16_t* p, float q) { *p = gf_u16(q); }
 
 #define GF_TX 64
 #define GF_RUN 8      // outputs per thread along x in the horizontal pass
@@ -51,10 +61,10 @@ __device__ __forceinline__ double gf_bilinear(const TD* __restrict__ src, int Ws
 }
 
 // NQ_IN planes staged (2), NQ_SUM planes summed (4 in sweep 1: I, p, II, Ip; 2 in sweep 2: a, b)
-template <int SWEEP, int GF_RUNY, typename TD>
+template <int SWEEP, int GF_RUNY, typename TD, typename TO>
 __global__ __launch_bounds__(256) void k_gf(const TD* __restrict__ depth_lo, int Wlo, int Hlo,
                                             const uint8_t* __restrict__ guide, int W, int H, int r, double eps,
-                                            double* __restrict__ A, double* __restrict__ B, float* __restrict__ out)
+                                            double* __restrict__ A, double* __restrict__ B, TO* __restrict__ out)
 {
     constexpr int NS = SWEEP == 1 ? 4 : 2;
     constexpr int GF_TY = 4 * GF_RUNY;
@@ -143,7 +153,9 @@ __global__ __launch_bounds__(256) void k_gf(const TD* __restrict__ depth_lo, int
                     B[(size_t)gy * W + gx] = mp - a * mI;
                 } else {
                     const double I = (double)guide[(size_t)gy * W + gx] / 255.0;
-                    out[(size_t)gy * W + gx] = (float)((s[0] / cnt) * I + (s[1] / cnt));
+                    const float q = (float)((s[0] / cnt) * I + (s[1] / cnt));
+                    if constexpr (std::is_same<TO, float>::value) out[(size_t)gy * W + gx] = q;
+                    else out[(size_t)gy * W + gx] = gf_u16(q);
                 }
             }
             if (j + 1 < GF_RUNY) {
@@ -174,10 +186,10 @@ typedef double v3d_f64x2 __attribute__((ext_vector_type(2)));
 typedef float v3d_f32x2 __attribute__((ext_vector_type(2)));
 typedef float v3d_f32x4 __attribute__((ext_vector_type(4)));
 
-template <int SWEEP, int RR, typename TD>
+template <int SWEEP, int RR, typename TD, typename TO>
 __global__ __launch_bounds__(256) void k_gfm(const TD* __restrict__ depth_lo, int Wlo, int Hlo,
                                              const uint8_t* __restrict__ guide, int W, int H, double eps, int band_h,
-                                             double* __restrict__ A, double* __restrict__ B, float* __restrict__ out,
+                                             double* __restrict__ A, double* __restrict__ B, TO* __restrict__ out,
                                              size_t depth_stride, size_t guide_stride)
 {
     static_assert(RR % 2 == 0, "pairs must not straddle the strip's halo boundary");
@@ -353,12 +365,17 @@ __global__ __launch_bounds__(256) void k_gfm(const TD* __restrict__ depth_lo, in
                             const double Ia = (double)guide[o] * (1.0 / 255.0);
                             const double Ib = px1 ? (double)guide[o + 1] * (1.0 / 255.0) : 0.0;
                             const float qa = (float)((s0a * inva) * Ia + (s1a * inva)), qb = (float)((s0b * invb) * Ib + (s1b * invb));
-                            if (vec_ok) {
-                                v3d_f32x2 vq = { qa, qb };
-                                __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x2*>(out + o));
+                            if (vec_ok && (std::is_same<TO, float>::value || (reinterpret_cast<uintptr_t>(out + o) & 3) == 0)) {
+                                if constexpr (std::is_same<TO, float>::value) {
+                                    v3d_f32x2 vq = { qa, qb };
+                                    __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x2*>(out + o));
+                                } else {
+                                    v3d_u16x2v vq = { gf_u16(qa), gf_u16(qb) };
+                                    __builtin_nontemporal_store(vq, reinterpret_cast<v3d_u16x2v*>(out + o));
+                                }
                             } else {
-                                out[o] = qa;
-                                if (px1) out[o + 1] = qb;
+                                gf_st(out + o, qa);
+                                if (px1) gf_st(out + o + 1, qb);
                             }
                         }
                     }
@@ -519,10 +536,10 @@ __device__ __forceinline__ void gf_solve4(const int sg[4], const int sgg[4], con
 // 81 instead of 289 and more room; the matcher's 1023 gives sum P < 2^23).  The ring holds (P << 8 | g) in ONE register per row, the vertical sums are four int32
 // and cross the lanes as one int4 per column.  The a/b algebra converts the four exact sums to f64 -- the very values the f64 sums
 // of the general path hold (they are exact there too) -- so the output is bit-identical to it.
-template <int RR, int COLS, typename TD, bool I1>
+template <int RR, int COLS, typename TD, bool I1, typename TO>
 __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restrict__ depth_lo, int Wlo, int Hlo,
                                                 const uint8_t* __restrict__ guide, int W, int H, double eps, int band_h,
-                                                float* __restrict__ out, size_t depth_stride, size_t guide_stride)
+                                                TO* __restrict__ out, size_t depth_stride, size_t guide_stride)
 {
     static_assert(RR % 4 == 0, "runs of four must not straddle the strip's halo boundaries");
     static_assert(!I1 || std::is_same<TD, int16_t>::value, "the integer stage 1 takes the int16 disparity");
@@ -730,7 +747,7 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                             const size_t o = (size_t)y * W + hgx;
                             const bool all_in = hgx + 3 < W;
                             const bool vec_ok = all_in && (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(out + o) | reinterpret_cast<uintptr_t>(guide + o)) & 3) == 0
-                                                && (reinterpret_cast<uintptr_t>(out + o) & 15) == 0;
+                                                && (reinterpret_cast<uintptr_t>(out + o) & (4 * sizeof(TO) - 1)) == 0;   // f32x4 / u16x4
                             int g[4];
                             if (vec_ok) {
                                 const uint32_t g4 = *reinterpret_cast<const uint32_t*>(guide + o);
@@ -748,11 +765,16 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                                 q[n] = (float)((sa[n] * inv) * I + (sb[n] * inv));
                             }
                             if (vec_ok) {
-                                const v3d_f32x4 vq = { q[0], q[1], q[2], q[3] };
-                                __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x4*>(out + o));
+                                if constexpr (std::is_same<TO, float>::value) {
+                                    const v3d_f32x4 vq = { q[0], q[1], q[2], q[3] };
+                                    __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x4*>(out + o));
+                                } else {
+                                    const v3d_u16x4 vq = { gf_u16(q[0]), gf_u16(q[1]), gf_u16(q[2]), gf_u16(q[3]) };
+                                    __builtin_nontemporal_store(vq, reinterpret_cast<v3d_u16x4*>(out + o));
+                                }
                             } else {
 #pragma unroll
-                                for (int n = 0; n < 4; n++) if (hgx + n < W) out[o + n] = q[n];
+                                for (int n = 0; n < 4; n++) if (hgx + n < W) gf_st(out + o + n, q[n]);
                             }
                         }
                     }
@@ -781,9 +803,9 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
     }
 }
 
-template <int RR, typename TD>
+template <int RR, typename TD, typename TO>
 static void launch_gff(const TD* depth_lo, int Wlo, int Hlo, const uint8_t* guide, int W, int H, double eps,
-                       float* out, int n, size_t depth_stride, size_t guide_stride, hipStream_t st)
+                       TO* out, int n, size_t depth_stride, size_t guide_stride, hipStream_t st)
 {
     // int16 disparity, exact 2x: stage 1 in exact integers (80 KB of LDS: two workgroups per CU); the f64 route needs 96 KB (one)
     bool i1 = false;
@@ -807,27 +829,27 @@ static void launch_gff(const TD* depth_lo, int Wlo, int Hlo, const uint8_t* guid
     const dim3 grid(v3d_cdiv(W, cols - 4 * RR), v3d_cdiv(H, band), n);
     if constexpr (std::is_same<TD, int16_t>::value) {
         if (i1 && cols == 512) {
-            hipLaunchKernelGGL((k_gff<RR, 512, TD, true>), grid, dim3(1024), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
+            hipLaunchKernelGGL((k_gff<RR, 512, TD, true, TO>), grid, dim3(1024), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
             return;
         }
         if (i1) {
-            hipLaunchKernelGGL((k_gff<RR, 256, TD, true>), grid, dim3(512), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
+            hipLaunchKernelGGL((k_gff<RR, 256, TD, true, TO>), grid, dim3(512), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
             return;
         }
     }
-    hipLaunchKernelGGL((k_gff<RR, 256, TD, false>), grid, dim3(512), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
+    hipLaunchKernelGGL((k_gff<RR, 256, TD, false, TO>), grid, dim3(512), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band, out, depth_stride, guide_stride);
 }
 
-template <int RR, typename TD>
+template <int RR, typename TD, typename TO>
 static void launch_gfm(const TD* depth_lo, int Wlo, int Hlo, const uint8_t* guide, int W, int H, double eps,
-                       double* A, double* B, float* out, int n, size_t depth_stride, size_t guide_stride, hipStream_t st)
+                       double* A, double* B, TO* out, int n, size_t depth_stride, size_t guide_stride, hipStream_t st)
 {
     // band heights (measured sweep, 30 x 4K frames): each band pays 2r warm-up rows; sweep 1 is VALU-bound, sweep 2
     // is bound by its re-reads of the f64 a/b planes
     const int band1 = g_v3d_opt.gf_band1, band2 = g_v3d_opt.gf_band2;
     const dim3 grid1(v3d_cdiv(W, 256 - 2 * RR), v3d_cdiv(H, band1), n), grid2(v3d_cdiv(W, 256 - 2 * RR), v3d_cdiv(H, band2), n);
-    hipLaunchKernelGGL((k_gfm<1, RR, TD>), grid1, dim3(256), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band1, A, B, out, depth_stride, guide_stride);
-    hipLaunchKernelGGL((k_gfm<2, RR, TD>), grid2, dim3(256), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band2, A, B, out, depth_stride, guide_stride);
+    hipLaunchKernelGGL((k_gfm<1, RR, TD, TO>), grid1, dim3(256), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band1, A, B, out, depth_stride, guide_stride);
+    hipLaunchKernelGGL((k_gfm<2, RR, TD, TO>), grid2, dim3(256), 0, st, depth_lo, Wlo, Hlo, guide, W, H, eps, band2, A, B, out, depth_stride, guide_stride);
 }
 
 extern "C" size_t v3d_guided_upscale_ws_bytes(int W, int H)
@@ -845,9 +867,9 @@ static size_t gf_smem(int r, int ns, int ty)
 
 // n frames: frame f at depth_lo + f*depth_stride (elements), guide + f*guide_stride (bytes), out + f*W*H;
 // ws must hold n * v3d_guided_upscale_ws_bytes(W, H)
-template <typename TD>
+template <typename TD, typename TO>
 static int guided_upscale_batch(const TD* depth_lo, int Wlo, int Hlo, size_t depth_stride, const uint8_t* guide,
-                                int W, int H, size_t guide_stride, int n, int r, float eps, float* out, void* ws, void* stream)
+                                int W, int H, size_t guide_stride, int n, int r, float eps, TO* out, void* ws, void* stream)
 {
     if (n < 1) { v3d_set_error("bad batch"); return V3D_ERR_ARG; }
     if (!depth_lo || !guide || !out || !ws) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
@@ -871,21 +893,21 @@ static int guided_upscale_batch(const TD* depth_lo, int Wlo, int Hlo, size_t dep
     }
     for (int f = 0; f < n; f++) {
     const TD* depth_lo_f = depth_lo + (size_t)f * depth_stride; const uint8_t* guide_f = guide + (size_t)f * guide_stride;
-    double* A = reinterpret_cast<double*>(ws) + (size_t)f * 2 * W * H; double* B = A + (size_t)W * H; float* out_f = out + (size_t)f * W * H;
+    double* A = reinterpret_cast<double*>(ws) + (size_t)f * 2 * W * H; double* B = A + (size_t)W * H; TO* out_f = out + (size_t)f * W * H;
     const int ty = r <= 8 ? 16 : 8;
     const dim3 grid(v3d_cdiv(W, GF_TX), v3d_cdiv(H, ty));
     const size_t sm1 = gf_smem(r, 4, ty), sm2 = gf_smem(r, 2, ty);
     if (ty == 16) {
         // above the default dynamic-LDS limit: opt in (160 KiB per CU on gfx950)
-        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<1, 4, TD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm1));
-        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<2, 4, TD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm2));
-        hipLaunchKernelGGL((k_gf<1, 4, TD>), grid, dim3(256), sm1, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
-        hipLaunchKernelGGL((k_gf<2, 4, TD>), grid, dim3(256), sm2, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
+        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<1, 4, TD, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm1));
+        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<2, 4, TD, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm2));
+        hipLaunchKernelGGL((k_gf<1, 4, TD, TO>), grid, dim3(256), sm1, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
+        hipLaunchKernelGGL((k_gf<2, 4, TD, TO>), grid, dim3(256), sm2, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
     } else {
-        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<1, 2, TD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm1));
-        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<2, 2, TD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm2));
-        hipLaunchKernelGGL((k_gf<1, 2, TD>), grid, dim3(256), sm1, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
-        hipLaunchKernelGGL((k_gf<2, 2, TD>), grid, dim3(256), sm2, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
+        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<1, 2, TD, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm1));
+        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_gf<2, 2, TD, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm2));
+        hipLaunchKernelGGL((k_gf<1, 2, TD, TO>), grid, dim3(256), sm1, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
+        hipLaunchKernelGGL((k_gf<2, 2, TD, TO>), grid, dim3(256), sm2, st, depth_lo_f, Wlo, Hlo, guide_f, W, H, r, (double)eps, A, B, out_f);
     }
     }
     V3D_LAUNCH_CHECK();
@@ -895,13 +917,13 @@ static int guided_upscale_batch(const TD* depth_lo, int Wlo, int Hlo, size_t dep
 extern "C" int v3d_guided_upscale_batch(const float* depth_lo, int Wlo, int Hlo, size_t depth_stride, const uint8_t* guide,
                                         int W, int H, size_t guide_stride, int n, int r, float eps, float* out, void* ws, void* stream)
 {
-    return guided_upscale_batch<float>(depth_lo, Wlo, Hlo, depth_stride, guide, W, H, guide_stride, n, r, eps, out, ws, stream);
+    return guided_upscale_batch<float, float>(depth_lo, Wlo, Hlo, depth_stride, guide, W, H, guide_stride, n, r, eps, out, ws, stream);
 }
 
 extern "C" int v3d_guided_upscale(const float* depth_lo, int Wlo, int Hlo, const uint8_t* guide, int W, int H,
                                   int r, float eps, float* out, void* ws, void* stream)
 {
-    return guided_upscale_batch<float>(depth_lo, Wlo, Hlo, 0, guide, W, H, 0, 1, r, eps, out, ws, stream);
+    return guided_upscale_batch<float, float>(depth_lo, Wlo, Hlo, 0, guide, W, H, 0, 1, r, eps, out, ws, stream);
 }
 
 // the same filter fed with the matcher's int16 disparity (x16, <= 0 invalid): depth.py:341 `/16` and :374 `<= 0 -> 0` are
@@ -909,5 +931,14 @@ extern "C" int v3d_guided_upscale(const float* depth_lo, int Wlo, int Hlo, const
 extern "C" int v3d_guided_upscale_disp16_batch(const int16_t* disp16, int Wlo, int Hlo, size_t disp_stride, const uint8_t* guide,
                                                int W, int H, size_t guide_stride, int n, int r, float eps, float* out, void* ws, void* stream)
 {
-    return guided_upscale_batch<int16_t>(disp16, Wlo, Hlo, disp_stride, guide, W, H, guide_stride, n, r, eps, out, ws, stream);
+    return guided_upscale_batch<int16_t, float>(disp16, Wlo, Hlo, disp_stride, guide, W, H, guide_stride, n, r, eps, out, ws, stream);
+}
+
+// the normalised 16-bit depth samples in, the 16-bit 4K samples out: bit-identical to v3d_guided_upscale_batch on the samples as
+// float32 followed by v3d_round_to_u16, without the float32 4K plane or the rounding launch.  Stage 1 runs in f64 on every
+// route: sum g * P over a window needs ~37 bits, beyond I1's int32
+extern "C" int v3d_guided_upscale_u16_batch(const uint16_t* depth_lo, int Wlo, int Hlo, size_t depth_stride, const uint8_t* guide,
+                                            int W, int H, size_t guide_stride, int n, int r, float eps, uint16_t* out, void* ws, void* stream)
+{
+    return guided_upscale_batch<uint16_t, uint16_t>(depth_lo, Wlo, Hlo, depth_stride, guide, W, H, guide_stride, n, r, eps, out, ws, stream);
 }

@@ -205,9 +205,15 @@ extern "C" int v3d_disp_to_depth(const int16_t* disp16, size_t n, float* out, vo
 __device__ __forceinline__ unsigned f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 
-__global__ void k_minmax_init(unsigned* mm) { mm[0] = 0xFFFFFFFFu; mm[1] = 0u; }
-__global__ __launch_bounds__(256) void k_minmax(const float* __restrict__ d, size_t n, unsigned* mm)
+// One launch set for n frames: blockIdx.y is the frame, each frame has its own {min, max} pair in mm[2f], mm[2f + 1].  Min and
+// max are exact and the normalisation is per element, so frame f's bits depend neither on n nor on the block count.
+__global__ void k_minmax_init(unsigned* mm, int n)
 {
+    for (int f = blockIdx.x * 256 + threadIdx.x; f < n; f += gridDim.x * 256) { mm[2 * f] = 0xFFFFFFFFu; mm[2 * f + 1] = 0u; }
+}
+__global__ __launch_bounds__(256) void k_minmax(const float* __restrict__ d, size_t n, size_t stride, unsigned* mm)
+{
+    d += blockIdx.y * stride; mm += 2 * blockIdx.y;
     unsigned lo = 0xFFFFFFFFu, hi = 0u;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const unsigned o = f2ord(d[i]);
@@ -217,8 +223,10 @@ __global__ __launch_bounds__(256) void k_minmax(const float* __restrict__ d, siz
     for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
     if ((threadIdx.x & 63) == 0) { atomicMin(mm, lo); atomicMax(mm + 1, hi); }
 }
-__global__ __launch_bounds__(256) void k_norm_u16(const float* __restrict__ d, size_t n, const unsigned* __restrict__ mm, uint16_t* __restrict__ out)
+__global__ __launch_bounds__(256) void k_norm_u16(const float* __restrict__ d, size_t n, size_t stride, const unsigned* __restrict__ mm,
+                                                  uint16_t* __restrict__ out)
 {
+    d += blockIdx.y * stride; mm += 2 * blockIdx.y; out += blockIdx.y * n;
     const float mn = ord2f(mm[0]), mx = ord2f(mm[1]);
     const bool flat = !(mx > mn);
     const float range = mx - mn;
@@ -232,18 +240,30 @@ __global__ __launch_bounds__(256) void k_norm_u16(const float* __restrict__ d, s
         out[i] = (uint16_t)v;
     }
 }
-extern "C" int v3d_depth_to_u16(const float* depth, size_t n, uint16_t* out, float* ws, void* stream)
+static int depth_to_u16(const float* depth, int n, size_t elems, size_t stride, uint16_t* out, float* ws, hipStream_t st)
 {
     if (!depth || !out || !ws) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
-    if (n == 0) return V3D_OK;
-    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || n > 65535) { v3d_set_error("bad batch %d", n); return V3D_ERR_ARG; }
+    if (n > 1 && stride < elems) { v3d_set_error("frame stride %zu below the frame size %zu", stride, elems); return V3D_ERR_ARG; }
+    if (elems == 0) return V3D_OK;
     unsigned* mm = reinterpret_cast<unsigned*>(ws);
-    const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, st, mm);
-    hipLaunchKernelGGL(k_minmax, dim3(blocks), dim3(256), 0, st, depth, n, mm);
-    hipLaunchKernelGGL(k_norm_u16, dim3(blocks), dim3(256), 0, st, depth, n, mm, out);
+    // about 1024 blocks per launch whatever n is (at least 64 per frame): a 1080p frame is 8100 blocks of 256
+    const size_t per = (size_t)(1024 / n > 64 ? 1024 / n : 64);
+    const int bx = (int)((elems + 255) / 256 < per ? (elems + 255) / 256 : per);
+    hipLaunchKernelGGL(k_minmax_init, dim3(v3d_cdiv(n, 256)), dim3(256), 0, st, mm, n);
+    hipLaunchKernelGGL(k_minmax, dim3(bx, n), dim3(256), 0, st, depth, elems, stride, mm);
+    hipLaunchKernelGGL(k_norm_u16, dim3(bx, n), dim3(256), 0, st, depth, elems, stride, mm, out);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
+}
+extern "C" int v3d_depth_to_u16(const float* depth, size_t n, uint16_t* out, float* ws, void* stream)
+{
+    return depth_to_u16(depth, 1, n, n, out, ws, (hipStream_t)stream);
+}
+extern "C" int v3d_depth_to_u16_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, uint16_t* out,
+                                      float* minmax_ws, void* stream)
+{
+    return depth_to_u16(depth, n, frame_elems, frame_stride, out, minmax_ws, (hipStream_t)stream);
 }
 
 // ---- 4K depth -> the 16-bit sample of the PNG sink: round to nearest even (numpy.rint / torch.round), clamp to [0, 65535] ----

@@ -14,6 +14,7 @@ _EXPORTS = {
     "HybridStereoDepthExtractor": ("depth", "HybridStereoDepthExtractor"),
     "IGEVStereoDepthExtractor": ("depth", "IGEVStereoDepthExtractor"),
     "SimpleDepthUpscaler": ("upscale", "SimpleDepthUpscaler"),
+    "SbsTo4kDepthPipeline": ("pipeline", "SbsTo4kDepthPipeline"),
     "get_video_info": ("utils", "get_video_info"),
     "create_work_directory": ("utils", "create_work_directory"),
 }

@@ -25,6 +25,7 @@ EXPORTS = (
     "v3d_sgbm_sync_errors", "v3d_sgbm_set_lockstep", "v3d_sgbm_profile", "v3d_sgbm_profile_stage_count", "v3d_sgbm_profile_stage_name", "v3d_sgbm_profile_read",
     "v3d_mono_blend_ws_bytes", "v3d_mono_blend", "v3d_mono_blend_batch",
     "v3d_sgbm_poll_errors", "v3d_sgbm_stream_wait_lockstep", "v3d_sgbm_set_option", "v3d_sgbm_get_option", "v3d_set_option", "v3d_get_option", "v3d_round_to_u16",
+    "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -107,6 +108,8 @@ def lib():
         L.v3d_guided_upscale_disp16_batch.argtypes = [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, C.c_float, vp, vp, vp]
         L.v3d_disp_to_depth.argtypes = [vp, sz, vp, vp]
         L.v3d_depth_to_u16.argtypes = [vp, sz, vp, vp, vp]
+        L.v3d_depth_to_u16_batch.argtypes = [vp, ci, sz, sz, vp, vp, vp]
+        L.v3d_guided_upscale_u16_batch.argtypes = [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, C.c_float, vp, vp, vp]
         L.v3d_round_to_u16.argtypes = [vp, sz, vp, vp]
         L.v3d_guided_upscale_ws_bytes.argtypes = [ci, ci]
         L.v3d_guided_upscale_ws_bytes.restype = sz
@@ -331,8 +334,11 @@ def split_sbs(sbs, unsqueeze=True):
     return L, R
 
 
-def bgr_to_gray(bgr):
-    out = torch.empty(bgr.shape[:-1], dtype=torch.uint8, device=bgr.device)
+def bgr_to_gray(bgr, out=None):
+    if out is None:
+        out = torch.empty(bgr.shape[:-1], dtype=torch.uint8, device=bgr.device)
+    if bgr.shape[-1] != 3 or tuple(out.shape) != tuple(bgr.shape[:-1]):
+        raise NativeError(f"bgr_to_gray: shapes {tuple(bgr.shape)} -> {tuple(out.shape)}")
     _check(lib().v3d_bgr_to_gray(_dev(bgr, torch.uint8, "bgr"), out.numel(), _dev(out, torch.uint8, "gray"), _stream()),
            "v3d_bgr_to_gray")
     return out
@@ -371,6 +377,27 @@ def depth_to_u16(depth):
     ws = torch.empty(2, dtype=torch.float32, device=depth.device)
     _check(lib().v3d_depth_to_u16(_dev(depth, torch.float32, "depth"), depth.numel(), _dev(out, torch.int16, "out"),
                                   _dev(ws, torch.float32, "ws"), _stream()), "v3d_depth_to_u16")
+    return out
+
+
+_mm_ws = {}
+
+
+def depth_to_u16_batch(depth, out=None):
+    """float32 [n,H,W] -> per-frame min-max normalised uint16 bit patterns in an int16 [n,H,W] tensor, one fixed launch set;
+    frame f is bit-identical to depth_to_u16(depth[f]).  The min/max scratch is allocated once per (n, device)."""
+    n = depth.shape[0]
+    if out is None:
+        out = torch.empty(depth.shape, dtype=torch.int16, device=depth.device)
+    if depth.dim() != 3 or tuple(out.shape) != tuple(depth.shape):
+        raise NativeError(f"depth_to_u16_batch: expected [n,H,W] in and out, got {tuple(depth.shape)} -> {tuple(out.shape)}")
+    key = (n, depth.device.index)
+    ws = _mm_ws.get(key)
+    if ws is None:
+        ws = _mm_ws[key] = torch.empty(2 * n, dtype=torch.float32, device=depth.device)
+    per = depth[0].numel() if n else 0
+    _check(lib().v3d_depth_to_u16_batch(_dev(depth, torch.float32, "depth"), n, per, per, _dev(out, torch.int16, "out"),
+                                        _dev(ws, torch.float32, "ws"), _stream()), "v3d_depth_to_u16_batch")
     return out
 
 
@@ -415,11 +442,7 @@ def guided_upscale_batch(depth_lo, guide, r=8, eps=1e-3, out=None):
         raise NativeError("guide frames must be dense HxW images")
     if out is None:
         out = torch.empty((n, Hhi, Whi), dtype=torch.float32, device=guide.device)
-    key = (Whi, Hhi, n, guide.device.index)
-    ws = _gf_ws.get(key)
-    if ws is None:
-        ws = torch.empty(int(lib().v3d_guided_upscale_ws_bytes(Whi, Hhi)) * n, dtype=torch.uint8, device=guide.device)
-        _gf_ws[key] = ws
+    ws = _gf_batch_ws(Whi, Hhi, n, guide.device)
     if guide.dtype != torch.uint8 or not guide.is_cuda:
         raise NativeError("guide: expected a uint8 device tensor")
     if depth_lo.dtype == torch.int16:
@@ -428,6 +451,38 @@ def guided_upscale_batch(depth_lo, guide, r=8, eps=1e-3, out=None):
         fn, name, src = lib().v3d_guided_upscale_batch, "v3d_guided_upscale_batch", _dev(depth_lo, torch.float32, "depth_lo")
     _check(fn(src, Wlo, Hlo, Hlo * Wlo, C.c_void_p(guide.data_ptr()), Whi, Hhi, guide.stride(0), n, int(r), float(eps),
               _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"), _stream()), name)
+    return out
+
+
+def _gf_batch_ws(Whi, Hhi, n, device):
+    key = (Whi, Hhi, n, device.index)
+    ws = _gf_ws.get(key)
+    if ws is None:
+        ws = _gf_ws[key] = torch.empty(int(lib().v3d_guided_upscale_ws_bytes(Whi, Hhi)) * n, dtype=torch.uint8, device=device)
+    return ws
+
+
+def guided_upscale_u16_batch(depth_u16, guide, r=8, eps=1e-3, out=None):
+    """depth_u16: the normalised 16-bit depth samples as an int16-viewed [N,Hlo,Wlo] tensor; guide u8 [N,Hhi,Whi] (frames may
+    be strided) -> the 16-bit 4K samples, int16-viewed [N,Hhi,Whi], one launch.  Bit-identical to
+    round_to_u16(guided_upscale_batch(u16 as float32)) on every route (include/v3d_hip.h)."""
+    n, Hlo, Wlo = depth_u16.shape
+    _, Hhi, Whi = guide.shape
+    if guide.shape[0] != n:
+        raise NativeError(f"guide batch {guide.shape[0]} != depth batch {n}")
+    if guide.dtype != torch.uint8 or not guide.is_cuda:
+        raise NativeError("guide: expected a uint8 device tensor")
+    if guide.stride(2) != 1 or guide.stride(1) != Whi:
+        raise NativeError("guide frames must be dense HxW images")
+    if out is None:
+        out = torch.empty((n, Hhi, Whi), dtype=torch.int16, device=guide.device)
+    if tuple(out.shape) != (n, Hhi, Whi):
+        raise NativeError(f"out: expected shape {(n, Hhi, Whi)}, got {tuple(out.shape)}")
+    ws = _gf_batch_ws(Whi, Hhi, n, guide.device)
+    _check(lib().v3d_guided_upscale_u16_batch(_dev(depth_u16, torch.int16, "depth_u16"), Wlo, Hlo, Hlo * Wlo,
+                                              C.c_void_p(guide.data_ptr()), Whi, Hhi, guide.stride(0), n, int(r), float(eps),
+                                              _dev(out, torch.int16, "out"), _dev(ws, torch.uint8, "ws"), _stream()),
+           "v3d_guided_upscale_u16_batch")
     return out
 
 

@@ -1,0 +1,247 @@
+"""One pass from the SBS clip to the 4K depth sequence: `python -m video_3d_pipeline.pipeline sbs.npy 4k.npy`.
+
+The two-step route -- `python -m video_3d_pipeline.depth` writes normalised 16-bit 1080p PNGs, `python -m
+video_3d_pipeline.upscale` reads them back and filters them against the 4K clip -- sends every depth map over PCIe twice
+and through zlib twice before the 4K filter sees it.  Here the depth stays on the device from the SBS frame to the final
+16-bit 4K sample, B frames at a time:
+
+    SBS frames -> HipStereoBackend.sbs_to_disparity (the depth CLI's own pass, neural guidance included)
+               -> v3d_depth_to_u16_batch (per-frame min-max -> u16, the depth PNG's samples)
+               -> [--keep-depth-maps: depth_%06d.png into the depth CLI's cache directory]
+               -> v3d_guided_upscale_u16_batch against the matching 4K frames' luma -> u16 4K samples -> writer pool
+
+The only lossy step between the two CLIs is the u16 quantisation of the normalised depth; it happens here on the device and
+the filter reads the same u16 samples `read_png16(...).astype(float32)` gives the upscale CLI, so every output PNG is
+byte-for-byte what the two CLIs write.  The two-step route stays the reference for this one.
+"""
+import argparse
+from pathlib import Path
+
+import numpy as np
+
+from .depth import HipStereoBackend, HybridStereoDepthExtractor
+from .upscale import GUIDED_EPS, GUIDED_RADIUS, encode_depth4k
+from .utils import PngWriterPool, get_video_info, iter_frames
+
+# 4K frames per guided launch.  A frame costs ~25 MB of pinned BGR staging + 25 MB of device BGR + 17 MB of u16 output on
+# each side, and the filter's workspace (used by its two-sweep routes) 133 MB of device memory: 8 frames keep the pinned
+# host memory near 0.4 GB whatever the SGM pass size is.  A frame's bits do not depend on the batch it is filtered in.
+GUIDE_BATCH = 8
+
+
+class HipPipelineBackend(HipStereoBackend):
+    """HipStereoBackend plus the device steps after the disparity: normalisation, guide luma, guided filter, copies out."""
+
+    def depth_to_u16_batch(self, depth):
+        """device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W]"""
+        return self.native.depth_to_u16_batch(depth)
+
+    def to_host_u16(self, u16):
+        """device u16 [n,H,W] -> NumPy uint16 [n,H,W] through pinned memory.  The pinned block comes from torch's caching host
+        allocator and goes back to it once the writers drop the last frame of it: no allocation in the steady state, and no
+        buffer is overwritten while a writer thread still encodes from it."""
+        torch = self.torch
+        host = torch.empty(tuple(u16.shape), dtype=torch.int16, pin_memory=True)
+        host.copy_(u16, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host.numpy().view(np.uint16)
+
+    def guide_luma(self, frames, height, width, capacity):
+        """4K BGR frames (None = beyond the clip: flat 128) -> device luma [n,height,width].  The frames are gathered in one
+        pinned buffer of `capacity` frames and cross PCIe in one copy; the buffer is reused by the next call, which
+        to_host_u16's synchronise has made safe."""
+        torch, nat = self.torch, self.native
+        n = len(frames)
+        host = self._staging("guide_host", (capacity, height, width, 3), torch.uint8, True)
+        dev = self._staging("guide_dev", (capacity, height, width, 3), torch.uint8, False)
+        luma = self._staging("guide_luma", (capacity, height, width), torch.uint8, False)
+        hv = host.numpy()
+        for i, f in enumerate(frames):
+            if f is not None:
+                if f.shape[:2] != (height, width):
+                    raise ValueError(f"4K frame of shape {f.shape}, expected {height}x{width}")
+                hv[i] = f if f.ndim == 3 else f[..., None]      # a luma frame: gray of (g, g, g) is g exactly
+        dev[:n].copy_(host[:n], non_blocking=True)
+        nat.bgr_to_gray(dev[:n], luma[:n])
+        for i, f in enumerate(frames):
+            if f is None:
+                luma[i].fill_(128)                              # beyond the 4K clip: flat guide, as upscale.py does
+        return luma[:n]
+
+    def guided_upscale_u16(self, u16, luma, r, eps):
+        """device u16 depth samples [n,H,W] + device luma [n,Hhi,Whi] -> device u16 4K samples [n,Hhi,Whi]"""
+        return self.native.guided_upscale_u16_batch(u16, luma, r, eps)
+
+
+class SbsTo4kDepthPipeline:
+    """SBS clip + 4K clip -> 4K 16-bit depth sequence in one pass (same files as the depth CLI followed by the upscale CLI)"""
+
+    writer_pool_factory = PngWriterPool       # sink of the 4K 16-bit maps (and of --keep-depth-maps): the CLIs' hook
+
+    def __init__(self,
+                 model_checkpoint: str = "Intel/dpt-large",
+                 work_dir: str = "temp_depth",
+                 device: str = "cuda",
+                 batch_size: int = 8,
+                 use_neural_guidance: bool = True,
+                 stereo_only: bool = False,
+                 unsqueeze_sbs: bool = True,
+                 radius: int = GUIDED_RADIUS,
+                 eps: float = GUIDED_EPS,
+                 guide_batch: int = GUIDE_BATCH,
+                 backend=None,
+                 mono_provider=None):
+        """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests)"""
+        if backend is None:
+            if not str(device).startswith("cuda"):
+                raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
+            backend = HipPipelineBackend(device)
+        self.backend = backend
+        # the depth CLI's extractor supplies the model loading, the guidance provider, the cache path and the frame count
+        self.extractor = HybridStereoDepthExtractor(
+            model_checkpoint=model_checkpoint, work_dir=work_dir, cache_dir=work_dir, device=device, batch_size=batch_size,
+            use_neural_guidance=use_neural_guidance, stereo_only=stereo_only, unsqueeze_sbs=unsqueeze_sbs, backend=backend,
+            mono_provider=mono_provider)
+        self.radius, self.eps = radius, eps
+        self.guide_batch = max(1, int(guide_batch))
+
+    def run(self, sbs_video: str, video_4k: str, output_path: str = None, start_frame: int = 0, max_frames: int = None,
+            guide_start_frame: int = 0, force_reprocess: bool = False, keep_depth_maps: bool = False) -> str:
+        """guide_start_frame: the 4K frame that belongs to SBS frame start_frame (as for the upscale CLI).  Returns the
+        output path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
+        from . import sharding
+        ex, be = self.extractor, self.backend
+        print(f"SBS -> 4K depth: {sbs_video} + {video_4k}")
+        video_info, frame_count = ex._frame_count(sbs_video, start_frame, max_frames)
+        info4k = get_video_info(video_4k)
+        if not info4k:
+            raise ValueError(f"Could not read video info: {video_4k}")
+        Whi, Hhi, fps = info4k['width'], info4k['height'], info4k['fps']
+        cache_path = ex.get_cache_path(sbs_video, start_frame, frame_count) if keep_depth_maps or output_path is None else None
+        if output_path is None:
+            output_path = f"depth_4k_{cache_path.name}.mp4"          # what the upscale CLI names its output for that directory
+        output_path = Path(output_path)
+        if output_path.exists() and not force_reprocess:
+            print(f"✓ Using existing depth video: {output_path}")
+            return str(output_path)
+        if video_info['width'] % 2 != 0:
+            raise ValueError("SBS frame width must be even")
+        if not ex.model_loaded:
+            ex.load_model()
+
+        rank, world = sharding.rank_world()
+        sharding.require_initialized(world)
+        frames_dir = Path(str(output_path.with_suffix("")) + "_frames")
+        frames_dir.mkdir(parents=True, exist_ok=True)
+        ow = video_info['width'] if ex.unsqueeze_sbs else video_info['width'] // 2
+        sizer = getattr(be, "compute_batch_size", None)
+        pass_frames = sizer(ow, video_info['height'], ex.batch_size) if sizer else ex.batch_size
+        self.last_pass_frames = pass_frames
+        gb = min(self.guide_batch, pass_frames)
+        provider = ex._guidance_provider()
+        # frame i -> rank i mod world; each rank decodes only its own frames of BOTH clips (4K frame g0 + i guides SBS frame i)
+        g0 = max(int(guide_start_frame), 0)
+        guides = iter_frames(video_4k, g0, frame_count, stride=world, offset=rank)
+        guide_state = {"delivered": 0, "ended": False}
+        flat = 0
+        batch, batch_idx = [], []
+
+        def next_guide():
+            if guide_state["ended"]:
+                return None
+            f = next(guides, None)
+            if f is None:
+                guide_state["ended"] = True
+                print(f"Warning: 4K guide video ended after {guide_state['delivered']} of this rank's frames; the "
+                      f"remaining depth frames are upsampled with a flat guide")
+                return None
+            guide_state["delivered"] += 1
+            return f
+
+        def flush(writers):
+            nonlocal flat
+            if not batch:
+                return
+            if provider is not None:
+                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, provider)
+            else:
+                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs)
+            u16 = be.depth_to_u16_batch(depth)
+            if keep_depth_maps:
+                lo = be.to_host_u16(u16)
+                for j, i in enumerate(batch_idx):
+                    writers.submit(cache_path / f"depth_{i:06d}.png", lo[j])
+            for j0 in range(0, len(batch), gb):
+                idx = batch_idx[j0:j0 + gb]
+                frames = [next_guide() for _ in idx]
+                flat += sum(f is None for f in frames)
+                q = be.to_host_u16(be.guided_upscale_u16(u16[j0:j0 + len(idx)], be.guide_luma(frames, Hhi, Whi, gb),
+                                                         self.radius, self.eps))
+                for j, i in enumerate(idx):
+                    writers.submit(frames_dir / f"depth4k_{i:06d}.png", q[j])
+            print(f"✓ Queued {len(batch)} 4K depth maps (rank {rank})")
+            batch.clear()
+            batch_idx.clear()
+
+        decoded = 0
+        with self.writer_pool_factory() as writers:
+            for k, frame in enumerate(iter_frames(sbs_video, start_frame, frame_count, stride=world, offset=rank)):
+                decoded += 1
+                batch.append(frame)
+                batch_idx.append(rank + k * world)
+                if len(batch) == pass_frames:
+                    flush(writers)
+            flush(writers)
+        self.last_decoded_frames = decoded
+        self.last_flat_guides = flat
+        n = sharding.total(decoded)
+        if n == 0:
+            raise ValueError("No frames extracted from video")
+        sharding.barrier()
+        if rank == 0:
+            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps)
+        sharding.barrier()
+        print(f"✓ Depth video saved: {output_path}")
+        return str(output_path)
+
+
+def main(argv=None):
+    """ Command line interface: SBS clip + 4K clip -> 4K depth sequence """
+    parser = argparse.ArgumentParser(description='SBS stereoscopic video + 4K video -> 4K depth sequence in one pass')
+    parser.add_argument('video', help='Path to SBS video file')
+    parser.add_argument('video_4k', help='Path to 4K 2D video (dimensions and guide frames)')
+    parser.add_argument('--output', help='Output path for 4K depth video')
+    parser.add_argument('--start-frame', type=int, default=0, help='Starting frame number (default: 0)')
+    parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to process (default: all)')
+    parser.add_argument('--batch-size', type=int, default=8, help='Batch size for GPU processing (default: 8)')
+    parser.add_argument('--model', default="Intel/dpt-large", help='Neural model checkpoint (default: Intel/dpt-large)')
+    parser.add_argument('--work-dir', default='temp_depth', help='Working directory for output (default: temp_depth)')
+    parser.add_argument('--force', action='store_true', help='Force reprocessing even if the output exists')
+    parser.add_argument('--device', default='cuda', help='Processing device (default: cuda)')
+    parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
+    parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
+    parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
+    parser.add_argument('--guide-start-frame', type=int, default=0,
+                        help='4K frame that matches the first SBS frame (alignment offset in frames; default 0)')
+    parser.add_argument('--keep-depth-maps', action='store_true',
+                        help="Also write the 1080p depth_%%06d.png maps into the depth CLI's cache directory")
+    args = parser.parse_args(argv)
+    stereo_only = args.stereo_only or args.no_neural
+    try:
+        from . import sharding
+        sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
+        pipe = SbsTo4kDepthPipeline(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device,
+                                    batch_size=args.batch_size, use_neural_guidance=not stereo_only, stereo_only=stereo_only,
+                                    unsqueeze_sbs=not args.no_unsqueeze)
+        output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
+                               max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
+                               force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps)
+        print(f"\n✓ Success! 4K depth video: {output_path}")
+    except Exception as e:
+        print(f"Error: {e}")
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    exit(main())

@@ -24,6 +24,26 @@ GUIDED_RADIUS = 8       # at 4K; the reference specifies nothing (SURVEY.md Appe
 GUIDED_EPS = 1e-3       # on [0,1]-scaled guide
 
 
+def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, radius: int, eps: float):
+    """the last step of a 4K depth run, on one process: frames_dir/depth4k_%06d.png -> H.264 at output_path when an ffmpeg
+    binary exists and the output is an .mp4, else a JSON manifest of the PNG sequence at output_path"""
+    ffmpeg = shutil.which("ffmpeg")
+    if ffmpeg and str(output_path).endswith(".mp4"):
+        cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / "depth4k_%06d.png"),
+               "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-preset", "medium", "-r", str(fps), str(output_path)]
+        res = subprocess.run(cmd, capture_output=True)
+        if res.returncode != 0:
+            print("FFmpeg error:")
+            print(res.stderr.decode())
+            raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
+    else:
+        Path(output_path).write_text(json.dumps({
+            "format": "png16-sequence", "frames_dir": str(frames_dir), "pattern": "depth4k_%06d.png",
+            "count": count, "width": width, "height": height, "fps": fps,
+            "guided_radius": radius, "guided_eps": eps,
+            "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"}, indent=1))
+
+
 class HipUpscaleBackend:
     def __init__(self, device: str = "cuda"):
         import torch
@@ -176,21 +196,7 @@ class SimpleDepthUpscaler:
         sharding.barrier()
 
         if rank == 0:
-            ffmpeg = shutil.which("ffmpeg")
-            if ffmpeg and str(output_path).endswith(".mp4"):
-                cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / "depth4k_%06d.png"),
-                       "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-preset", "medium", "-r", str(fps), str(output_path)]
-                res = subprocess.run(cmd, capture_output=True)
-                if res.returncode != 0:
-                    print("FFmpeg error:")
-                    print(res.stderr.decode())
-                    raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
-            else:
-                Path(output_path).write_text(json.dumps({
-                    "format": "png16-sequence", "frames_dir": str(frames_dir), "pattern": "depth4k_%06d.png",
-                    "count": n, "width": target_width, "height": target_height, "fps": fps,
-                    "guided_radius": self.radius, "guided_eps": self.eps,
-                    "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"}, indent=1))
+            encode_depth4k(frames_dir, output_path, n, target_width, target_height, fps, self.radius, self.eps)
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
         return output_path

@@ -1,4 +1,4 @@
-"""Path shim so that `python -m video_3d_pipeline.depth` / `.upscale` work from the repository root.
+"""Path shim so that `python -m video_3d_pipeline.depth` / `.upscale` / `.pipeline` work from the repository root.
 The real package lives in video-3d-pipeline_amd/video_3d_pipeline (a directory name with a hyphen
 cannot be imported); this file only redirects the package search path there."""
 import os as _os
