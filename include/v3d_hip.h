@@ -18,6 +18,9 @@
  *                          as guided-filter joint upsampling
  *   v3d_corr_lookup        CREStereo recurrent correlation lookup (BASELINE.json config 4; the
  *                          reference only names it: depth.py:1, CREStereo_model.txt)
+ *   v3d_xcorr[_ws_bytes]   utils.py:147 scipy.signal.correlate(a2, a1, 'full') by FFT on the device
+ *   v3d_align_audio        utils.py:137-165 find_audio_offset: normalisation, cross-correlation, peak lag and
+ *                          correlation strength (align.py's VideoAligner.find_alignment)
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -210,6 +213,19 @@ int v3d_bgr_to_gray(const uint8_t* bgr, size_t n_pixels, uint8_t* gray, void* st
 size_t v3d_corr_ws_bytes(int C, int h, int w);
 int v3d_corr_lookup(const uint16_t* fl_bf16, const uint16_t* fr_bf16, const float* flow,
                     int C, int h, int w, int G, int pattern, float* out, void* ws, void* stream);
+
+/* Audio cross-correlation (v3d_align.hip).  a1, a2: float32 tracks of n1, n2 samples; N = the smallest power of two
+   >= n1 + n2 - 1 and >= 2^10; N > 2^26 (about 25 minutes per track at 22.05 kHz) -> V3D_ERR_UNSUPPORTED.
+   ws: device scratch of v3d_xcorr_ws_bytes(n1, n2) bytes (0 = unsupported sizes), shared by both entries; each call
+   writes its own twiddle tables into it. */
+size_t v3d_xcorr_ws_bytes(int n1, int n2);
+/* out[k], k in [0, n1+n2-1): scipy.signal.correlate(a2, a1, 'full') of the RAW inputs (no normalisation) */
+int v3d_xcorr(const float* a1, int n1, const float* a2, int n2, float* out, void* ws, void* stream);
+/* result (device, 4 doubles): lag in samples (a1[n] ~ a2[n+lag]), signed c(lag) of the normalised tracks,
+   strength, min(std1, std2).  an = (a - mean) / (std + 1e-10) (f64 mean and population std, rounded to float32);
+   c(L) = sum_n a2n[n+L] a1n[n]; strength = |c(lag)| / sqrt(E1 E2), E = sum an^2.  The FFT only nominates candidate
+   lags; lag and c come from direct f64 sums over the overlap: the largest |c| wins, the smallest lag on a tie. */
+int v3d_align_audio(const float* a1, int n1, const float* a2, int n2, double* result, void* ws, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

@@ -26,6 +26,7 @@ EXPORTS = (
     "v3d_mono_blend_ws_bytes", "v3d_mono_blend", "v3d_mono_blend_batch",
     "v3d_sgbm_poll_errors", "v3d_sgbm_stream_wait_lockstep", "v3d_sgbm_set_option", "v3d_sgbm_get_option", "v3d_set_option", "v3d_get_option", "v3d_round_to_u16",
     "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
+    "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -118,6 +119,10 @@ def lib():
         L.v3d_corr_ws_bytes.argtypes = [ci, ci, ci]
         L.v3d_corr_ws_bytes.restype = sz
         L.v3d_corr_lookup.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.v3d_xcorr_ws_bytes.argtypes = [ci, ci]
+        L.v3d_xcorr_ws_bytes.restype = sz
+        L.v3d_xcorr.argtypes = [vp, ci, vp, ci, vp, vp, vp]
+        L.v3d_align_audio.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -494,6 +499,40 @@ def corr_lookup(fl, fr, flow, groups=4, pattern=0):
     _check(lib().v3d_corr_lookup(_dev(fl, torch.bfloat16, "fl"), _dev(fr, torch.bfloat16, "fr"),
                                  _dev(flow, torch.float32, "flow"), Cc, h, w, groups, pattern,
                                  _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_corr_lookup")
+    return out
+
+
+def _xcorr_args(a1, a2, what):
+    if a1.dim() != 1 or a2.dim() != 1:
+        raise NativeError(f"{what}: expected 1-D tracks, got {tuple(a1.shape)} and {tuple(a2.shape)}")
+    if a1.device != a2.device:
+        raise NativeError(f"{what}: tracks on {a1.device} and {a2.device}")
+    n1, n2 = a1.numel(), a2.numel()
+    nbytes = int(lib().v3d_xcorr_ws_bytes(n1, n2)) if 1 <= n1 < 2 ** 31 and 1 <= n2 < 2 ** 31 else 0
+    if nbytes == 0:
+        raise NativeError(f"{what}: lengths {n1}, {n2} unsupported (need >= 1 and n1 + n2 - 1 <= 2^26)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a1.device)
+    return (_dev(a1, torch.float32, "a1"), n1, _dev(a2, torch.float32, "a2"), n2), ws
+
+
+def xcorr(a1, a2):
+    """float32 device tracks [n1], [n2] -> float32 [n1 + n2 - 1]: scipy.signal.correlate(a2, a1, 'full') of the raw
+    tracks (index k = lag + n1 - 1), by FFT on the device (v3d_xcorr)"""
+    args, ws = _xcorr_args(a1, a2, "xcorr")
+    out = torch.empty(a1.numel() + a2.numel() - 1, dtype=torch.float32, device=a1.device)
+    with torch.cuda.device(a1.device):
+        _check(lib().v3d_xcorr(*args, _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_xcorr")
+    return out
+
+
+def align_audio(a1, a2):
+    """float32 device tracks -> float64 device tensor [lag, c(lag), strength, min(std1, std2)] (v3d_align_audio): the lag
+    (in samples, a1[n] ~ a2[n + lag]) that maximises |c| of find_audio_offset's normalised tracks (utils.py:137-165)"""
+    args, ws = _xcorr_args(a1, a2, "align_audio")
+    out = torch.empty(4, dtype=torch.float64, device=a1.device)
+    with torch.cuda.device(a1.device):
+        _check(lib().v3d_align_audio(*args, _dev(out, torch.float64, "result"), _dev(ws, torch.uint8, "ws"), _stream()),
+               "v3d_align_audio")
     return out
 
 

@@ -1,13 +1,221 @@
-"""Audio alignment is OUT OF SCOPE of this build (audio cross-correlation, once
-per movie, not on the per-frame path).  The class exists only so that the reference's run_pipeline.py
-(run_pipeline.py:11, 41-43) imports unchanged; run it with --skip-alignment."""
+"""Audio-only temporal alignment (mirror of the reference's align.py and of utils.py:137-165 find_audio_offset).
+
+The two audio tracks are decoded on the host (utils.load_audio) and checked there; the normalisation, the FFT
+cross-correlation and the peak search run in libv3d_hip (v3d_align_audio).  Everything that can make the alignment
+impossible -- a missing file, no audio track, no decoder, a silent track, differing sample rates -- is detected before
+the first GPU call and raised as a RuntimeError that names --skip-alignment.  No correlation plot is drawn (the
+reference's plot_audio_correlation needs matplotlib, which this package does not require).
+"""
+import argparse
+import json
+from pathlib import Path
+from typing import Dict, Optional
+
+import numpy as np
+
+from .utils import create_work_directory, get_video_info, load_audio
+
+_SKIP = "run the pipeline with --skip-alignment, or align the clips by hand and pass --guide-start-frame"
+
+
+def _fail(msg: str):
+    raise RuntimeError(f"audio alignment impossible: {msg}; {_SKIP}")
 
 
 class VideoAligner:
-    def __init__(self, *args, **kwargs):
-        self.args, self.kwargs = args, kwargs
+    """Audio-only temporal alignment - no video re-encoding.  The constructor touches neither the disk nor the GPU."""
 
-    def find_alignment(self, *args, **kwargs):
-        raise RuntimeError("audio alignment is not part of the MI355X hot-path build; "
-                           "run the pipeline with --skip-alignment (the offset is never applied downstream anyway, "
-                           "run_pipeline.py:45-50)")
+    def __init__(self, video1_path: str, video2_path: str, work_dir: str = "temp_alignment"):
+        self.video1_path = video1_path
+        self.video2_path = video2_path
+        self.work_dir = Path(work_dir)          # created by find_alignment when it writes alignment_data.json
+        self.video1_info = None
+        self.video2_info = None
+
+    def _load(self, path: str, max_audio_length: float):
+        try:
+            audio, rate = load_audio(path, max_seconds=max_audio_length)
+        except FileNotFoundError:
+            _fail(f"{path} does not exist")
+        except LookupError as e:
+            _fail(f"no audio track: {e}")
+        except (RuntimeError, ValueError, OSError) as e:
+            _fail(f"cannot decode the audio of {path}: {e}")
+        if audio.size == 0:
+            _fail(f"{path} has an empty audio track")
+        if audio.max() == audio.min():                 # population std 0: find_audio_offset would divide by 1e-10
+            _fail(f"the audio track of {path} is silent (constant)")
+        if not np.isfinite(audio).all():
+            _fail(f"the audio track of {path} holds non-finite samples")
+        return audio, rate
+
+    def _info(self, path: str):
+        info = get_video_info(path)
+        if not info or not info.get("fps"):
+            _fail(f"could not read the video information of {path}")
+        return info
+
+    def find_alignment(self, max_audio_length: float = 300) -> Dict:
+        """Find temporal alignment and return offset data (the reference's ten keys); also written to
+        work_dir/alignment_data.json."""
+        audio1, sr1 = self._load(self.video1_path, max_audio_length)
+        audio2, sr2 = self._load(self.video2_path, max_audio_length)
+        if sr1 != sr2:
+            _fail(f"sample rate mismatch: {sr1} Hz vs {sr2} Hz")
+        if audio1.size + audio2.size - 1 > 2 ** 26:
+            _fail(f"{audio1.size} + {audio2.size} samples exceed the largest correlation (2^26 lags); lower max_audio_length")
+        self.video1_info = self._info(self.video1_path)
+        self.video2_info = self._info(self.video2_path)
+        print(f"Video 1: {self.video1_info['width']}x{self.video1_info['height']} "
+              f"@ {self.video1_info['fps']:.2f} fps, {self.video1_info['duration']:.1f}s")
+        print(f"Video 2: {self.video2_info['width']}x{self.video2_info['height']} "
+              f"@ {self.video2_info['fps']:.2f} fps, {self.video2_info['duration']:.1f}s")
+
+        import torch
+        from . import _native
+        print("Computing audio cross-correlation (GPU FFT)...")
+        dev = _native.resolve_device(None)
+        with torch.cuda.device(dev):
+            res = _native.align_audio(_native.to_device(audio1, dev), _native.to_device(audio2, dev)).cpu().numpy()
+        lag, correlation_strength = int(res[0]), float(res[2])
+        time_offset = lag / sr1
+        print(f"Audio offset: {time_offset:.3f}s, correlation strength: {correlation_strength:.4f}")
+        print("Correlation plot: not drawn (matplotlib is not a dependency of this build)")
+
+        frame_duration = 1.0 / self.video1_info['fps']
+        offset_frames = time_offset / frame_duration
+        print(f"Audio alignment: {time_offset:.3f}s offset ({offset_frames:.1f} frames)")
+        print(f"Correlation strength: {correlation_strength:.4f}")
+        alignment_data = {
+            'video1_path': str(self.video1_path),
+            'video2_path': str(self.video2_path),
+            'time_offset_seconds': float(time_offset),
+            'offset_frames': float(offset_frames),
+            'correlation_strength': float(correlation_strength),
+            'frame_duration': float(frame_duration),
+            'video1_fps': self.video1_info['fps'],
+            'video2_fps': self.video2_info['fps'],
+            'sample_rate': int(sr1),
+            'audio_length_analyzed': float(max_audio_length)
+        }
+        self.work_dir = create_work_directory(str(self.work_dir))
+        alignment_file = self.work_dir / 'alignment_data.json'
+        with open(alignment_file, 'w') as f:
+            json.dump(alignment_data, f, indent=2)
+        print(f"Alignment data saved to: {alignment_file}")
+        return alignment_data
+
+    def assess_alignment_quality(self, alignment_data: Dict, tolerance_frames: float = 2.0) -> str:
+        """Assess alignment quality and provide recommendations."""
+        return assess_alignment_quality(alignment_data, tolerance_frames)
+
+
+def assess_alignment_quality(alignment_data: Dict, tolerance_frames: float = 2.0) -> str:
+    """The reference's grades: EXCELLENT (|offset| < tolerance_frames frames), else GOOD (strength > 0.8), MODERATE
+    (> 0.6) or POOR."""
+    offset = alignment_data['time_offset_seconds']
+    correlation = alignment_data['correlation_strength']
+    frame_duration = alignment_data['frame_duration']
+    precision_limit = frame_duration * tolerance_frames
+
+    print("\nAlignment Assessment:")
+    print(f"Frame precision limit: ±{precision_limit:.3f}s ({tolerance_frames} frames)")
+    if abs(offset) < precision_limit:
+        quality = "EXCELLENT"
+        print(f"✓ {quality}: Offset {offset:.3f}s is within frame precision")
+        print("Videos are already well-aligned - no adjustment needed")
+    elif correlation > 0.8:
+        quality = "GOOD"
+        print(f"✓ {quality}: Strong correlation ({correlation:.3f})")
+        print(f"Apply {offset:.3f}s offset in processing pipeline")
+    elif correlation > 0.6:
+        quality = "MODERATE"
+        print(f"⚠ {quality}: Acceptable correlation ({correlation:.3f})")
+        print(f"Apply {offset:.3f}s offset - verify results")
+    else:
+        quality = "POOR"
+        print(f"✗ {quality}: Low correlation ({correlation:.3f})")
+        print("Videos may not be from same source or need manual sync")
+    return quality
+
+
+def apply_offset_to_pipeline(alignment_file: str, target_video: str, output_path: str, start_time: float = 0,
+                             duration: Optional[float] = None) -> float:
+    """Start time (seconds) in target_video that matches start_time of the reference (video1); clamped at 0 as in the
+    reference.  output_path and duration are accepted for the reference's signature and unused there too."""
+    alignment_data = load_alignment_data(alignment_file)
+    offset = alignment_data['time_offset_seconds']
+    if target_video == alignment_data['video1_path']:
+        adjusted_start = start_time
+        print(f"Video1 (reference): start at {adjusted_start:.3f}s")
+    elif target_video == alignment_data['video2_path']:
+        adjusted_start = start_time + offset
+        print(f"Video2 (offset): start at {adjusted_start:.3f}s (original: {start_time:.3f}s + {offset:.3f}s offset)")
+    else:
+        raise ValueError(f"Target video {target_video} not found in alignment data")
+    if adjusted_start < 0:
+        print(f"Warning: Adjusted start time {adjusted_start:.3f}s < 0, using 0")
+        adjusted_start = 0
+    print(f"Use start_time={adjusted_start:.3f}s for {target_video}")
+    return adjusted_start
+
+
+def load_alignment_data(alignment_file: str) -> Dict:
+    """Load previously computed alignment data."""
+    alignment_path = Path(alignment_file)
+    if not alignment_path.exists():
+        raise FileNotFoundError(f"Alignment file not found: {alignment_file}")
+    with open(alignment_path, 'r') as f:
+        return json.load(f)
+
+
+def guide_start_frame_from(alignment_file: str, video_4k: str) -> int:
+    """--alignment-file of the upscale / pipeline CLIs: the 4K frame that matches the first SBS frame,
+    round(time_offset_seconds * fps of the 4K clip).  A negative offset (the 4K clip starts later) is not clamped:
+    ValueError naming the SBS --start-frame that compensates, round(-offset * video1_fps)."""
+    data = load_alignment_data(alignment_file)
+    offset = float(data['time_offset_seconds'])
+    info = get_video_info(video_4k)
+    if not info or not info.get("fps"):
+        raise ValueError(f"could not read the frame rate of {video_4k}")
+    if offset < 0:
+        sbs_fps = float(data.get('video1_fps') or info['fps'])
+        raise ValueError(f"{alignment_file}: the 4K clip starts {-offset:.3f}s after the SBS clip (negative offset); "
+                         f"start the SBS side at --start-frame {int(round(-offset * sbs_fps))} and pass "
+                         f"--guide-start-frame 0 instead of --alignment-file")
+    return int(round(offset * float(info['fps'])))
+
+
+def main(argv=None):
+    """Command line interface for fast audio-only alignment."""
+    parser = argparse.ArgumentParser(description='Fast audio-only video alignment (GPU FFT cross-correlation)')
+    parser.add_argument('video1', help='Path to first video (reference)')
+    parser.add_argument('video2', help='Path to second video (to be aligned)')
+    parser.add_argument('--work-dir', default='temp_alignment', help='Working directory for temporary files')
+    parser.add_argument('--max-audio', type=float, default=300.0, help='Maximum audio length for analysis (seconds)')
+    parser.add_argument('--tolerance', type=float, default=2.0, help='Alignment tolerance in frame intervals')
+    parser.add_argument('--min-correlation', type=float, default=0.6, help='Minimum correlation to proceed')
+    args = parser.parse_args(argv)
+    try:
+        aligner = VideoAligner(args.video1, args.video2, args.work_dir)
+        alignment_data = aligner.find_alignment(args.max_audio)
+        quality = aligner.assess_alignment_quality(alignment_data, args.tolerance)
+        if alignment_data['correlation_strength'] < args.min_correlation:
+            print(f"\nWarning: Correlation {alignment_data['correlation_strength']:.3f} below threshold {args.min_correlation}")
+            try:
+                response = input("Continue anyway? (y/n): ")
+            except EOFError:                     # no terminal: "no"
+                response = "n"
+            if response.strip().lower() != 'y':
+                return 1
+        print("\n✓ Alignment complete! Use alignment_data.json in pipeline steps.")
+        print(f"Quality: {quality}")
+        print(f"Offset: {alignment_data['time_offset_seconds']:.3f}s")
+        return 0
+    except Exception as e:
+        print(f"Error: {e}")
+        return 1
+
+
+if __name__ == "__main__":
+    exit(main())

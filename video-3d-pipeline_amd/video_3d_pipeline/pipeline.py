@@ -221,11 +221,23 @@ def main(argv=None):
     parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
     parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
-    parser.add_argument('--guide-start-frame', type=int, default=0,
-                        help='4K frame that matches the first SBS frame (alignment offset in frames; default 0)')
+    guide = parser.add_mutually_exclusive_group()
+    guide.add_argument('--guide-start-frame', type=int, default=0,
+                       help='4K frame that matches the first SBS frame (alignment offset in frames; default 0)')
+    guide.add_argument('--alignment-file', default=None,
+                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
+                            'round(time_offset_seconds * fps of the 4K clip)')
     parser.add_argument('--keep-depth-maps', action='store_true',
                         help="Also write the 1080p depth_%%06d.png maps into the depth CLI's cache directory")
     args = parser.parse_args(argv)
+    if args.alignment_file is not None:
+        from .align import guide_start_frame_from
+        try:
+            args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
+        except (OSError, ValueError, KeyError) as e:
+            print(f"Error: {e}")
+            return 1
+        print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
     stereo_only = args.stereo_only or args.no_neural
     try:
         from . import sharding

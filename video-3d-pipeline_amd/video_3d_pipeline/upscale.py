@@ -241,9 +241,21 @@ def main(argv=None):
     parser.add_argument('--output', help='Output path for 4K depth video')
     parser.add_argument('--no-nvenc', action='store_true', help='Disable NVENC, use CPU encoding')
     parser.add_argument('--force', action='store_true', help='Force reprocessing even if output exists')
-    parser.add_argument('--guide-start-frame', type=int, default=0,
-                        help='4K frame that matches depth_000000 (alignment offset in frames; default 0)')
+    guide = parser.add_mutually_exclusive_group()
+    guide.add_argument('--guide-start-frame', type=int, default=0,
+                       help='4K frame that matches depth_000000 (alignment offset in frames; default 0)')
+    guide.add_argument('--alignment-file', default=None,
+                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
+                            'round(time_offset_seconds * fps of the 4K clip)')
     args = parser.parse_args(argv)
+    if args.alignment_file is not None:
+        from .align import guide_start_frame_from
+        try:
+            args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
+        except (OSError, ValueError, KeyError) as e:
+            print(f"Error: {e}")
+            return 1
+        print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)

@@ -176,6 +176,82 @@ def iter_frames(video_path: str, start_frame: int = 0, max_frames: Optional[int]
         proc.wait()
 
 
+def _read_wav(path: Path):
+    """16-bit PCM WAV (stdlib `wave`) -> (int16 [n, channels], rate)"""
+    import wave
+    with wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise ValueError(f"{path}: only 16-bit PCM WAV is supported (sample width {w.getsampwidth()} bytes, "
+                             f"compression {w.getcomptype()})")
+        ch, rate = w.getnchannels(), w.getframerate()
+        data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+    return data.reshape(-1, ch), rate
+
+
+def _to_mono_float(a) -> np.ndarray:
+    """int16 (/ 32768) or float samples, [n] or [n, channels] (channels averaged, as librosa.load(mono=True)) -> float32 [n]"""
+    a = np.asarray(a)
+    if a.dtype == np.int16:
+        a = a.astype(np.float32) / 32768.0
+    elif a.dtype.kind == "f":
+        a = a.astype(np.float32, copy=False)
+    else:
+        raise ValueError(f"audio samples of dtype {a.dtype}: expected int16 or float")
+    if a.ndim == 2:
+        a = a.mean(axis=1, dtype=np.float32) if a.shape[1] > 1 else a[:, 0]
+    elif a.ndim != 1:
+        raise ValueError(f"audio of shape {a.shape}: expected [n] or [n, channels]")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def load_audio(path: str, max_seconds: float = 300.0, sample_rate: int = 22050):
+    """The first `max_seconds` of a clip's audio as float32 mono samples and their rate (what extract_audio +
+    load_audio_for_sync, utils.py:41-135, produce).  Containers, probed lazily like iter_frames:
+      - `.npz` frame stacks: keys `audio` (int16 / 32768 or float32, [n] or [n, channels]) and `audio_rate`;
+      - `.npy` stacks: the sidecar `<stem>.wav`;  frame directories: `audio.wav` inside;  `.wav` files themselves
+        (16-bit PCM, stdlib `wave`);
+      - anything else: `ffmpeg -vn -ac 1 -ar <sample_rate> -f s16le` when an ffmpeg binary is present.
+    Channels are averaged; samples are not resampled (only the ffmpeg route decodes at `sample_rate`).  Raises
+    FileNotFoundError for a missing path, LookupError when the clip has no audio track and RuntimeError when no
+    decoder can read it."""
+    p = Path(path)
+    if not p.exists():
+        raise FileNotFoundError(f"{path} does not exist")
+    kind = _container_kind(path)
+    if kind == "npz":
+        z = np.load(path)
+        if "audio" not in z.files:
+            raise LookupError(f"{path} has no audio track (no 'audio' array)")
+        if "audio_rate" not in z.files:
+            raise LookupError(f"{path} has an 'audio' array but no 'audio_rate'")
+        audio, rate = _to_mono_float(z["audio"]), int(z["audio_rate"])
+    elif kind in ("npy", "pngdir") or p.suffix.lower() == ".wav":
+        wav = p.with_suffix(".wav") if kind == "npy" else (p / "audio.wav" if kind == "pngdir" else p)
+        if not wav.exists():
+            raise LookupError(f"{path} has no audio track ({wav} not found)")
+        data, rate = _read_wav(wav)
+        audio = _to_mono_float(data)
+    else:
+        ffmpeg = shutil.which("ffmpeg")
+        if not ffmpeg:
+            raise RuntimeError(f"no audio decoder for {path}: ffmpeg is not installed "
+                               "(use a .npz stack with an 'audio' array, or a sidecar WAV)")
+        cmd = [ffmpeg, "-v", "error", "-i", str(path), "-t", str(float(max_seconds)), "-vn", "-ac", "1",
+               "-ar", str(int(sample_rate)), "-f", "s16le", "pipe:"]
+        proc = subprocess.run(cmd, capture_output=True)
+        if proc.returncode != 0:
+            msg = proc.stderr.decode(errors="replace").strip()
+            if "does not contain any stream" in msg or "matches no streams" in msg:
+                raise LookupError(f"{path} has no audio track")
+            raise RuntimeError(f"ffmpeg could not decode the audio of {path}: {msg[-300:]}")
+        audio = _to_mono_float(np.frombuffer(proc.stdout, dtype="<i2"))
+        if audio.size == 0:
+            raise LookupError(f"{path} has no audio track")
+        rate = int(sample_rate)
+    keep = int(max_seconds * rate)
+    return (audio[:keep] if audio.shape[0] > keep else audio), rate
+
+
 # writer / reader threads of the PNG pools; None = from the host cores (at most 16 writers / 8 readers).  A module
 # attribute, not an environment variable: the package reads none (tools set it directly)
 IO_THREADS = None
