@@ -21,6 +21,8 @@
  *   v3d_xcorr[_ws_bytes]   utils.py:147 scipy.signal.correlate(a2, a1, 'full') by FFT on the device
  *   v3d_align_audio        utils.py:137-165 find_audio_offset: normalisation, cross-correlation, peak lag and
  *                          correlation strength (align.py's VideoAligner.find_alignment)
+ *   v3d_render_stereo_batch  readme.md:37 step 4 (handed to VisionDepth3D there): DIBR from the 4K frame and its 4K depth
+ *                          to a side-by-side 3D frame (convert.py, the declared video-3d-convert step)
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -226,6 +228,20 @@ int v3d_xcorr(const float* a1, int n1, const float* a2, int n2, float* out, void
    c(L) = sum_n a2n[n+L] a1n[n]; strength = |c(lag)| / sqrt(E1 E2), E = sum an^2.  The FFT only nominates candidate
    lags; lag and c come from direct f64 sums over the overlap: the largest |c| wins, the smallest lag on a tie. */
 int v3d_align_audio(const float* a1, int n1, const float* a2, int n2, double* result, void* ws, void* stream);
+
+/* DIBR stereo rendering (v3d_stereo.hip): 4K BGR frame + its u16 depth (larger = nearer) -> side-by-side 3D.  Per row and eye
+   with gain g: source x lands at t = x + floor((g * (D - convergence) + 2^23) / 2^24) (round-half-up of g/256 * (D - conv)/65536
+   pixels; outside [0, W) dropped); the nearest source wins (u32 key (D << 16) | (x + 1)); a hole takes the farther of its nearest
+   left / right keys (ties left, black if the row has none); the eye pixel is the winning source's colour.  Full SBS: out
+   [n][H][2W][3], left eye first; half SBS: [n][H][W][3], eye pixel x' = (E[2x'] + E[2x'+1] + 1) >> 1 per channel.  Bit-exact
+   contract: tests/stereo_ref.py.  Frame f at frame_bgr + f*frame_stride (bytes; rows dense, W*3 bytes), depth + f*depth_stride
+   (elements; rows dense), out dense.  V3D_ERR_ARG: null pointer, n < 1, W or H < 1, strides smaller than a frame (n > 1), layout
+   not 0/1, odd W for half SBS, |gain| >= 2^24, convergence outside [0, 65535]; V3D_ERR_UNSUPPORTED: W > 8192. */
+#define V3D_STEREO_FULL_SBS 0
+#define V3D_STEREO_HALF_SBS 1
+int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
+                            size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
+                            int convergence, int layout, uint8_t* out_bgr /* dense [n][H][outW][3] */, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

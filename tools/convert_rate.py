@@ -1,0 +1,90 @@
+"""DIBR step (v3d_render_stereo_batch) on one GPU: kernel time per 4K frame from HIP events (8 distinct frames per launch,
+warm-up, 20 timed launches, both layouts), the algorithmic bytes and their share of 8 TB/s, and the convert CLI's end-to-end
+frames/s on a synthetic .npy 4K clip.  Prints one JSON line.
+
+    python tools/convert_rate.py [--frames 24] [--kernel-only]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "video-3d-pipeline_amd")]
+from video_3d_pipeline import _native as N  # noqa: E402
+
+W, H, NF, REPS, HBM = 3840, 2160, 8, 20, 8.0e12
+
+
+def inputs(n, seed=0):
+    rng = np.random.default_rng(seed)
+    x = np.arange(W)[None, :]
+    frames = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+    depth = np.empty((n, H, W), np.uint16)
+    for i in range(n):
+        d = rng.integers(0, 65536) + x * int(rng.integers(-12, 12)) + (np.arange(H)[:, None] * int(rng.integers(-20, 20)))
+        d[H // 4:H // 2, W // 3:W // 2] = rng.integers(0, 65536)
+        depth[i] = np.clip(d, 0, 65535)
+    return frames, depth
+
+
+def kernel_rates():
+    frames, depth = inputs(NF)
+    f = torch.from_numpy(frames).cuda()
+    d = torch.from_numpy(depth.view(np.int16)).cuda()
+    gl, gr, conv = N.stereo_gains()
+    res = {}
+    for name, layout, out_px in (("full_sbs", N.STEREO_FULL_SBS, 6), ("half_sbs", N.STEREO_HALF_SBS, 3)):
+        out = torch.empty((NF, H, W * (2 if layout == N.STEREO_FULL_SBS else 1), 3), dtype=torch.uint8, device="cuda")
+        for _ in range(3):
+            N.render_stereo_batch(f, d, gl, gr, conv, layout, out)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(REPS):
+            N.render_stereo_batch(f, d, gl, gr, conv, layout, out)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / (REPS * NF)
+        nbytes = W * H * (2 + 3 + out_px)
+        res[name] = {"us_per_frame": round(us, 2), "algorithmic_bytes_per_frame": nbytes,
+                     "fraction_of_8TBps": round(nbytes / (us * 1e-6) / HBM, 3)}
+    return res
+
+
+def cli_rate(n):
+    from video_3d_pipeline import convert, utils
+    frames, depth = inputs(n, seed=1)
+    with tempfile.TemporaryDirectory() as tmp:
+        np.save(os.path.join(tmp, "v4k.npy"), frames)
+        ddir = os.path.join(tmp, "d_frames")
+        os.makedirs(ddir)
+        for i in range(n):
+            utils.write_png16(os.path.join(ddir, f"depth4k_{i:06d}.png"), depth[i])
+        del frames, depth
+        conv = convert.DepthTo3DConverter()
+        conv.process_conversion(os.path.join(tmp, "v4k.npy"), ddir, os.path.join(tmp, "warm.json"), max_frames=2)
+        t0 = time.perf_counter()
+        conv.process_conversion(os.path.join(tmp, "v4k.npy"), ddir, os.path.join(tmp, "out.json"))
+        dt = time.perf_counter() - t0
+    return {"frames": n, "seconds": round(dt, 2), "frames_per_s": round(n / dt, 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=24, help="frames of the synthetic clip the CLI converts")
+    ap.add_argument("--kernel-only", action="store_true", help="skip the end-to-end CLI run (profiler runs)")
+    a = ap.parse_args()
+    res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "kernel": kernel_rates()}
+    if not a.kernel_only:
+        res["convert_cli_full_sbs"] = cli_rate(a.frames)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

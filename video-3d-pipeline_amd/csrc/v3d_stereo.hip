@@ -1,0 +1,295 @@
+// v3d_stereo.hip -- depth-image-based rendering (DIBR): 4K BGR frame + its u16 depth -> side-by-side stereo pair.
+//
+// The warp is purely horizontal, so every row is independent.  One workgroup of 256 threads marches a band of ST_BAND rows;
+// the next row's depth and BGR bytes are in flight (16-byte loads into registers) while the current row is rendered in LDS:
+//   1. stage: the row's aligned 16-byte chunks -> sD (depth), sF (BGR); both eyes' key rows sZ zeroed;
+//   2. scatter: every source pixel x, per eye: t = x + floor((g (D - conv) + 2^23) / 2^24); ds_max_u32 of
+//      (D << 16) | (x + 1) into sZ[eye][t] -- order-independent, so the result does not depend on scheduling;
+//   3. scan: thread t owns PPT consecutive targets; "last key left of my run" is a max-scan of (index + 1) over the threads,
+//      "first key right of my run" a max-scan of (WP - index) in the other direction (wave shuffles, then the four wave
+//      totals through LDS);
+//   4. fill + gather: holes take the farther neighbour (background extends into disocclusions), colours come from sF,
+//      half SBS averages pairs in registers, and each thread writes its run with the widest aligned stores.
+// Contract: tests/stereo_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "DIBR stereo rendering".
+#include "v3d_common.h"
+
+#define ST_THREADS 256
+#define ST_BAND 4                 // rows per workgroup: a 4K frame is 540 workgroups, one round of the resident slots
+#define ST_MAX_W 8192
+
+namespace {
+
+// bytes of the aligned 16-byte chunks that cover `len` bytes starting at an address with (addr & 15) <= max_off
+__host__ __device__ constexpr int st_chunks(int len, int max_off) { return (len + max_off + 15) / 16; }
+__host__ __device__ constexpr int st_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+template <int NW>
+__device__ __forceinline__ void st_store_run(uint8_t* p, const uint32_t (&w)[NW], int nbytes)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (nbytes == NW * 4) {
+        if constexpr (NW % 4 == 0) {
+            if ((a & 15) == 0) {
+#pragma unroll
+                for (int q = 0; q < NW / 4; ++q)
+                    st_stream(reinterpret_cast<uint4*>(p) + q, make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]));
+                return;
+            }
+        }
+        if constexpr (NW % 2 == 0) {
+            if ((a & 7) == 0) {
+#pragma unroll
+                for (int q = 0; q < NW / 2; ++q) st_stream(reinterpret_cast<uint2*>(p) + q, make_uint2(w[2 * q], w[2 * q + 1]));
+                return;
+            }
+        }
+        if ((a & 3) == 0) {
+#pragma unroll
+            for (int q = 0; q < NW; ++q) reinterpret_cast<uint32_t*>(p)[q] = w[q];
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NW * 4; ++i)                           // the row's last run, or an unaligned row
+        if (i < nbytes) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+
+__device__ __forceinline__ uint32_t st_fill(uint32_t a, uint32_t b)
+{
+    // a hole between keys a (left) and b (right): the farther one wins, ties go left; one side missing: the other (or 0)
+    return (a && b) ? ((a >> 16) <= (b >> 16) ? a : b) : (a ? a : b);
+}
+
+__device__ __forceinline__ int st_shift(int g, int d, int conv)
+{
+    const int64_t num = (int64_t)g * (int64_t)(d - conv);      // |num| < 2^40
+    return (int)((num + (1 << 23)) >> 24);                     // arithmetic shift = floor
+}
+
+template <int PPT>
+struct StGeom {
+    static constexpr int WP = PPT * ST_THREADS;                // padded key row per eye (targets >= W stay 0)
+    static constexpr int ND = st_cdiv(st_chunks(2 * WP, 14), ST_THREADS);   // depth chunks per thread
+    static constexpr int NF = st_cdiv(st_chunks(3 * WP, 15), ST_THREADS);   // BGR chunks per thread
+};
+
+}  // namespace
+
+template <int PPT>
+__global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __restrict__ frame, size_t frame_stride,
+                                                              const uint16_t* __restrict__ depth, size_t depth_stride, int W, int H,
+                                                              int gl, int gr, int conv, int half, uint8_t* __restrict__ out,
+                                                              int sd_bytes)
+{
+    using G = StGeom<PPT>;
+    constexpr int WP = G::WP, ND = G::ND, NF = G::NF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t* sZ = reinterpret_cast<uint32_t*>(smem);          // [2][WP]
+    unsigned char* sD = smem + 8 * WP;                         // depth row chunks (sd_bytes)
+    unsigned char* sF = sD + sd_bytes;                         // BGR row chunks
+    __shared__ uint32_t sTot[2][2][ST_THREADS / 64];           // [eye][prefix | suffix][wave]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.y;
+    const int y0 = blockIdx.x * ST_BAND, y1 = min(y0 + ST_BAND, H);
+    const uint8_t* fr = frame + (size_t)f * frame_stride;
+    const uint16_t* dp = depth + (size_t)f * depth_stride;
+    const int outW = half ? W : 2 * W;
+    const int eye_bytes = half ? (W / 2) * 3 : W * 3;
+
+    // a row's bytes as aligned 16-byte chunks: every load is unconditional (lanes past the last chunk re-read it), the
+    // chunks never leave the 16-byte blocks the row touches
+    uint4 rd[ND], rf[NF];
+    auto load_row = [&](int y) {
+        const uintptr_t ds = reinterpret_cast<uintptr_t>(dp + (size_t)y * W), fs = reinterpret_cast<uintptr_t>(fr + (size_t)y * W * 3);
+        const uint4* da = reinterpret_cast<const uint4*>(ds & ~(uintptr_t)15);
+        const uint4* fa = reinterpret_cast<const uint4*>(fs & ~(uintptr_t)15);
+        const int nd = (int)((ds + 2 * (uintptr_t)W - (ds & ~(uintptr_t)15) + 15) >> 4);
+        const int nf = (int)((fs + 3 * (uintptr_t)W - (fs & ~(uintptr_t)15) + 15) >> 4);
+#pragma unroll
+        for (int k = 0; k < ND; ++k) rd[k] = ld_stream(da + min(k * ST_THREADS + tid, nd - 1));
+#pragma unroll
+        for (int k = 0; k < NF; ++k) rf[k] = ld_stream(fa + min(k * ST_THREADS + tid, nf - 1));
+    };
+
+    load_row(y0);
+    for (int y = y0; y < y1; ++y) {
+        const uintptr_t ds = reinterpret_cast<uintptr_t>(dp + (size_t)y * W), fs = reinterpret_cast<uintptr_t>(fr + (size_t)y * W * 3);
+        const int doff = (int)(ds & 15), foff = (int)(fs & 15);
+        const int nd = (doff + 2 * W + 15) >> 4, nf = (foff + 3 * W + 15) >> 4;
+        __syncthreads();                                       // the previous row's LDS reads are done
+#pragma unroll
+        for (int k = 0; k < ND; ++k) {
+            const int c = k * ST_THREADS + tid;
+            if (c < nd) reinterpret_cast<uint4*>(sD)[c] = rd[k];
+        }
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const int c = k * ST_THREADS + tid;
+            if (c < nf) reinterpret_cast<uint4*>(sF)[c] = rf[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 2 * WP / 4 / ST_THREADS; ++k) reinterpret_cast<uint4*>(sZ)[k * ST_THREADS + tid] = make_uint4(0, 0, 0, 0);
+        if (y + 1 < y1) load_row(y + 1);                       // in flight while this row is rendered
+        __syncthreads();
+
+        // 2. scatter both eyes' keys
+        const uint16_t* drow = reinterpret_cast<const uint16_t*>(sD + doff);
+#pragma unroll 4
+        for (int j = 0; j < PPT; ++j) {
+            const int x = j * ST_THREADS + tid;
+            if (x < W) {
+                const int d = drow[x];
+                const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(x + 1);
+                const int tl = x + st_shift(gl, d, conv), tr = x + st_shift(gr, d, conv);
+                if ((unsigned)tl < (unsigned)W) atomicMax(sZ + tl, key);
+                if ((unsigned)tr < (unsigned)W) atomicMax(sZ + WP + tr, key);
+            }
+        }
+        __syncthreads();
+
+        // 3. nearest keys outside my run: (last key index + 1) from the left, (WP - first key index) from the right
+        const int x0 = tid * PPT;
+        uint32_t pre[2], suf[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
+            uint32_t lastp = 0, firstp = 0;
+#pragma unroll
+            for (int q = PPT / 4 - 1; q >= 0; --q) {
+                const uint4 v = zr[q];
+                const uint32_t k4[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+                for (int i = 3; i >= 0; --i) {
+                    if (k4[i]) {
+                        if (!lastp) lastp = (uint32_t)(x0 + 4 * q + i + 1);
+                        firstp = (uint32_t)(WP - (x0 + 4 * q + i));
+                    }
+                }
+            }
+            uint32_t p = lastp, s = firstp;                    // inclusive scans over the wave: p left to right, s right to left
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t pv = __shfl_up(p, o), sv = __shfl_down(s, o);
+                if (lane >= o) p = max(p, pv);
+                if (lane + o < 64) s = max(s, sv);
+            }
+            if (lane == 63) sTot[e][0][wave] = p;
+            if (lane == 0) sTot[e][1][wave] = s;
+            const uint32_t pe = __shfl_up(p, 1), se = __shfl_down(s, 1);
+            pre[e] = lane > 0 ? pe : 0u;
+            suf[e] = lane < 63 ? se : 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+#pragma unroll
+            for (int w = 0; w < ST_THREADS / 64; ++w) {
+                if (w < wave) pre[e] = max(pre[e], sTot[e][0][w]);
+                if (w > wave) suf[e] = max(suf[e], sTot[e][1][w]);
+            }
+        }
+
+        // 4. fill, gather, store
+        const int nvalid = min(PPT, W - x0);                   // <= 0: this thread's run lies beyond the row
+        uint8_t* orow = out + ((size_t)f * H + y) * (size_t)outW * 3;
+        const unsigned char* frow = sF + foff;
+        for (int e = 0; e < 2; ++e) {
+            uint32_t kk[PPT], rb[PPT];
+            const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
+#pragma unroll
+            for (int q = 0; q < PPT / 4; ++q) {
+                const uint4 v = zr[q];
+                kk[4 * q] = v.x; kk[4 * q + 1] = v.y; kk[4 * q + 2] = v.z; kk[4 * q + 3] = v.w;
+            }
+            uint32_t nb = suf[e] ? sZ[e * WP + WP - suf[e]] : 0u;
+            uint32_t na = pre[e] ? sZ[e * WP + pre[e] - 1] : 0u;
+#pragma unroll
+            for (int i = PPT - 1; i >= 0; --i) { rb[i] = nb; if (kk[i]) nb = kk[i]; }
+            uint32_t col[PPT];
+#pragma unroll
+            for (int i = 0; i < PPT; ++i) {
+                uint32_t k = kk[i];
+                if (k) na = k;
+                else k = st_fill(na, rb[i]);
+                const int s = k ? (int)(k & 0xFFFFu) - 1 : 0;
+                const unsigned char* px = frow + 3 * s;
+                col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
+            }
+            if (nvalid > 0 && !half) {
+                constexpr int NW = PPT * 3 / 4;
+                uint32_t wds[NW];
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) v |= ((col[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
+                    wds[w] = v;
+                }
+                st_store_run(orow + e * eye_bytes + x0 * 3, wds, nvalid * 3);
+            } else if (nvalid > 0) {
+                constexpr int NH = PPT / 2, NW = NH * 3 / 4;
+                uint32_t hc[NH];
+#pragma unroll
+                for (int i = 0; i < NH; ++i) {                 // per byte (a + b + 1) >> 1 = (a | b) - ((a ^ b) >> 1)
+                    const uint32_t a = col[2 * i], b = col[2 * i + 1];
+                    hc[i] = (a | b) - (((a ^ b) & 0xFEFEFEFEu) >> 1);
+                }
+                uint32_t wds[NW];
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) v |= ((hc[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
+                    wds[w] = v;
+                }
+                st_store_run(orow + e * eye_bytes + (x0 / 2) * 3, wds, (nvalid / 2) * 3);
+            }
+        }
+    }
+}
+
+template <int PPT>
+static int launch_stereo(const uint8_t* frame, size_t frame_stride, const uint16_t* depth, size_t depth_stride, int n, int W,
+                         int H, int gl, int gr, int conv, int half, uint8_t* out, hipStream_t stream)
+{
+    using G = StGeom<PPT>;
+    const int sd = st_chunks(2 * W, 14) * 16, sf = st_chunks(3 * W, 15) * 16;
+    const int smem = 8 * G::WP + sd + sf;
+    static bool attr_set = false;                              // per instantiation; the attribute is a property of the function
+    if (!attr_set) {
+        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_render_stereo<PPT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          8 * G::WP + st_chunks(2 * G::WP, 14) * 16 + st_chunks(3 * G::WP, 15) * 16));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(k_render_stereo<PPT>, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride,
+                       depth, depth_stride, W, H, gl, gr, conv, half, out, sd);
+    V3D_LAUNCH_CHECK();
+    return V3D_OK;
+}
+
+extern "C" int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
+                                       int n, int W, int H, int gain_left, int gain_right, int convergence, int layout,
+                                       uint8_t* out_bgr, void* stream)
+{
+    if (!frame_bgr || !depth || !out_bgr) { v3d_set_error("v3d_render_stereo_batch: null pointer"); return V3D_ERR_ARG; }
+    if (n < 1 || n > 65535 || W < 1 || H < 1) { v3d_set_error("v3d_render_stereo_batch: bad geometry n=%d W=%d H=%d", n, W, H); return V3D_ERR_ARG; }
+    if (n > 1 && (frame_stride < (size_t)W * H * 3 || depth_stride < (size_t)W * H)) {
+        v3d_set_error("v3d_render_stereo_batch: frame stride %zu B / depth stride %zu elements smaller than a frame", frame_stride, depth_stride);
+        return V3D_ERR_ARG;
+    }
+    if (layout != V3D_STEREO_FULL_SBS && layout != V3D_STEREO_HALF_SBS) { v3d_set_error("v3d_render_stereo_batch: layout %d", layout); return V3D_ERR_ARG; }
+    if (layout == V3D_STEREO_HALF_SBS && (W & 1)) { v3d_set_error("v3d_render_stereo_batch: half SBS needs an even width (W=%d)", W); return V3D_ERR_ARG; }
+    const int gmax = 1 << 24;
+    if (gain_left <= -gmax || gain_left >= gmax || gain_right <= -gmax || gain_right >= gmax) {
+        v3d_set_error("v3d_render_stereo_batch: |gain| must be < 2^24 (%d, %d)", gain_left, gain_right);
+        return V3D_ERR_ARG;
+    }
+    if (convergence < 0 || convergence > 65535) { v3d_set_error("v3d_render_stereo_batch: convergence %d outside [0, 65535]", convergence); return V3D_ERR_ARG; }
+    if (W > ST_MAX_W) { v3d_set_error("v3d_render_stereo_batch: W=%d > %d", W, ST_MAX_W); return V3D_ERR_UNSUPPORTED; }
+    const int half = layout == V3D_STEREO_HALF_SBS;
+    hipStream_t s = (hipStream_t)stream;
+    if (W <= 8 * ST_THREADS) return launch_stereo<8>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+    if (W <= 16 * ST_THREADS) return launch_stereo<16>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+    return launch_stereo<32>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+}

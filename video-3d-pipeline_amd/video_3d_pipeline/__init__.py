@@ -15,6 +15,7 @@ _EXPORTS = {
     "IGEVStereoDepthExtractor": ("depth", "IGEVStereoDepthExtractor"),
     "SimpleDepthUpscaler": ("upscale", "SimpleDepthUpscaler"),
     "SbsTo4kDepthPipeline": ("pipeline", "SbsTo4kDepthPipeline"),
+    "DepthTo3DConverter": ("convert", "DepthTo3DConverter"),
     "get_video_info": ("utils", "get_video_info"),
     "create_work_directory": ("utils", "create_work_directory"),
 }

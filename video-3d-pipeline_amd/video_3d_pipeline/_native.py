@@ -27,9 +27,12 @@ EXPORTS = (
     "v3d_sgbm_poll_errors", "v3d_sgbm_stream_wait_lockstep", "v3d_sgbm_set_option", "v3d_sgbm_get_option", "v3d_set_option", "v3d_get_option", "v3d_round_to_u16",
     "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
     "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
+    "v3d_render_stereo_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
+STEREO_FULL_SBS, STEREO_HALF_SBS = 0, 1      # V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS
+STEREO_MAX_WIDTH = 8192
 
 
 class NativeError(RuntimeError):
@@ -123,6 +126,7 @@ def lib():
         L.v3d_xcorr_ws_bytes.restype = sz
         L.v3d_xcorr.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.v3d_align_audio.argtypes = [vp, ci, vp, ci, vp, vp, vp]
+        L.v3d_render_stereo_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]
         _lib = L
     return _lib
 
@@ -533,6 +537,55 @@ def align_audio(a1, a2):
     with torch.cuda.device(a1.device):
         _check(lib().v3d_align_audio(*args, _dev(out, torch.float64, "result"), _dev(ws, torch.uint8, "ws"), _stream()),
                "v3d_align_audio")
+    return out
+
+
+def stereo_gains(max_shift=48.0, convergence=0.5, eye_split=0.5):
+    """user parameters of the DIBR step -> (gain_left, gain_right, conv), the integers v3d_render_stereo_batch takes:
+    gain_left = floor(max_shift * eye_split * 256 + 0.5), gain_right = -floor(max_shift * (1 - eye_split) * 256 + 0.5),
+    conv = floor(convergence * 65535 + 0.5).  max_shift: parallax in pixels between depth 65535 and depth 0 (>= 0, < 65536);
+    convergence: the depth at the screen plane, eye_split: the left eye's share of the shift (both in [0, 1])."""
+    import math
+    vals = {"max_shift": max_shift, "convergence": convergence, "eye_split": eye_split}
+    for k, v in vals.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError(f"{k} must be a finite number, got {v!r}")
+    if not 0 <= max_shift < 65536:
+        raise ValueError(f"max_shift must be in [0, 65536) pixels, got {max_shift}")
+    if not 0 <= convergence <= 1:
+        raise ValueError(f"convergence must be in [0, 1], got {convergence}")
+    if not 0 <= eye_split <= 1:
+        raise ValueError(f"eye_split must be in [0, 1], got {eye_split}")
+    gl = math.floor(max_shift * eye_split * 256 + 0.5)
+    gr = -math.floor(max_shift * (1 - eye_split) * 256 + 0.5)
+    conv = math.floor(convergence * 65535 + 0.5)
+    if max(abs(gl), abs(gr)) >= 1 << 24:
+        raise ValueError(f"max_shift {max_shift} gives a gain beyond 2^24")
+    return gl, gr, conv
+
+
+def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, layout=STEREO_FULL_SBS, out=None):
+    """DIBR (v3d_render_stereo_batch): frames u8 [n,H,W,3] BGR on the device (frames may be strided: rows dense), depth_u16 the
+    u16 depth samples as an int16-viewed contiguous [n,H,W] tensor -> u8 [n,H,2W,3] (full SBS, left eye first) or [n,H,W,3]
+    (half SBS).  Bit-exact contract: tests/stereo_ref.py."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
+        raise NativeError(f"frames: expected a uint8 [n,H,W,3] device tensor, got {frames.dtype} {tuple(frames.shape)}")
+    n, H, W, _ = frames.shape
+    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W:
+        raise NativeError("frames: rows must be dense HxWx3 images (only the frame stride may differ)")
+    if tuple(depth_u16.shape) != (n, H, W):
+        raise NativeError(f"depth {tuple(depth_u16.shape)} does not match frames {tuple(frames.shape)}")
+    if layout not in (STEREO_FULL_SBS, STEREO_HALF_SBS):
+        raise ValueError(f"layout must be {STEREO_FULL_SBS} (full SBS) or {STEREO_HALF_SBS} (half SBS), got {layout!r}")
+    shape = (n, H, 2 * W if layout == STEREO_FULL_SBS else W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    if tuple(out.shape) != shape:
+        raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    with torch.cuda.device(frames.device):
+        _check(lib().v3d_render_stereo_batch(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
+                                             H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout),
+                                             _dev(out, torch.uint8, "out"), _stream()), "v3d_render_stereo_batch")
     return out
 
 

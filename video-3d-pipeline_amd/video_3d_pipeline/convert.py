@@ -1,0 +1,311 @@
+"""Step 4 of the pipeline: the 4K frame and its 4K depth -> side-by-side 3D (`python -m video_3d_pipeline.convert`).
+
+The reference declares this step as the console script `video-3d-convert = "video_3d_pipeline.convert:main"` and hands the
+work to an outside tool (VisionDepth3D, "Optimized DIBR rendering").  Here it is depth-image-based rendering on the device,
+v3d_render_stereo_batch: every source pixel moves horizontally by g/256 * (D - conv)/65536 pixels per eye, the nearest
+source wins, disocclusions take the farther neighbour (background extension), and the two eyes are packed as full or half
+side-by-side.  The bit-exact contract is tests/stereo_ref.py; the parameters:
+
+    max_shift    parallax in pixels between depth 65535 (nearest) and depth 0 (default 48 = 1.25 % of a 3840 frame)
+    convergence  the depth at the screen plane, in [0, 1] (default 0.5): nearer moves right in the left eye, left in the right
+    eye_split    the left eye's share of the shift, in [0, 1] (default 0.5; 0 keeps the 4K frame itself as the left eye)
+
+Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
+cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
+pool.  The output directory `<output without suffix>_frames` is itself a clip (frame_%06d.png + info.json).
+"""
+import argparse
+import functools
+import json
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+from .utils import PngWriterPool, encode_png8, get_video_info, iter_frames, prefetch_map, read_png16
+
+LAYOUTS = {"full-sbs": 0, "half-sbs": 1}          # V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS
+DEFAULT_MAX_SHIFT, DEFAULT_CONVERGENCE, DEFAULT_EYE_SPLIT = 48.0, 0.5, 0.5
+# frames per launch: 4 x (25 MB BGR + 17 MB depth) of pinned input staging and 4 x 50 MB of pinned output (full SBS at 4K)
+CONVERT_BATCH = 4
+
+png_rgb_from_bgr = functools.partial(encode_png8, bgr=True)     # the writer pool's encoder of the stereo frames
+
+
+def add_stereo_arguments(parser):
+    """--layout / --max-shift / --convergence / --eye-split: shared by the convert CLI and the pipeline's --stereo-output"""
+    parser.add_argument('--layout', choices=list(LAYOUTS), default='full-sbs',
+                        help='full-sbs: two full-width eyes side by side (2W x H); half-sbs: each eye squeezed to W/2 (W x H)')
+    parser.add_argument('--max-shift', type=float, default=DEFAULT_MAX_SHIFT,
+                        help=f'parallax in pixels between the nearest and the farthest depth (default {DEFAULT_MAX_SHIFT:g})')
+    parser.add_argument('--convergence', type=float, default=DEFAULT_CONVERGENCE,
+                        help=f'depth at the screen plane, 0 (far) .. 1 (near) (default {DEFAULT_CONVERGENCE:g})')
+    parser.add_argument('--eye-split', type=float, default=DEFAULT_EYE_SPLIT,
+                        help=f"left eye's share of the shift, 0 .. 1; 0 keeps the 4K frame as the left eye (default {DEFAULT_EYE_SPLIT:g})")
+
+
+def stereo_options(args):
+    return dict(max_shift=args.max_shift, convergence=args.convergence, eye_split=args.eye_split, layout=args.layout)
+
+
+def stereo_settings(max_shift=DEFAULT_MAX_SHIFT, convergence=DEFAULT_CONVERGENCE, eye_split=DEFAULT_EYE_SPLIT, layout="full-sbs"):
+    """validated user parameters -> (layout code, (gain_left, gain_right, conv)); ValueError for anything out of range"""
+    from ._native import stereo_gains
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, got {layout!r}")
+    return LAYOUTS[layout], stereo_gains(max_shift, convergence, eye_split)
+
+
+def sibling_frames_dir(output_path) -> Path:
+    return Path(str(Path(output_path).with_suffix("")) + "_frames")
+
+
+def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, params: dict, gains):
+    """one process, after every frame is written: H.264 at output_path when an ffmpeg binary exists and it ends in .mp4,
+    else a JSON manifest of the PNG sequence (as encode_depth4k does for the depth)"""
+    ffmpeg = shutil.which("ffmpeg")
+    if ffmpeg and str(output_path).endswith(".mp4"):
+        cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / "frame_%06d.png"),
+               "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-preset", "medium", "-r", str(fps), str(output_path)]
+        res = subprocess.run(cmd, capture_output=True)
+        if res.returncode != 0:
+            print("FFmpeg error:")
+            print(res.stderr.decode())
+            raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
+    else:
+        Path(output_path).write_text(json.dumps({
+            "format": "png8-rgb-sequence", "frames_dir": str(frames_dir), "pattern": "frame_%06d.png",
+            "count": count, "width": width, "height": height, "fps": fps, "layout": params["layout"],
+            "max_shift": params["max_shift"], "convergence": params["convergence"], "eye_split": params["eye_split"],
+            "gain_left": gains[0], "gain_right": gains[1], "conv": gains[2],
+            "note": "no ffmpeg binary on this host: side-by-side frames kept as 8-bit RGB PNGs"}, indent=1))
+
+
+def write_clip_info(frames_dir: Path, fps: float):
+    (frames_dir / "info.json").write_text(json.dumps({"fps": fps}))
+
+
+def depth_frame_files(depth_path):
+    """the 4K depth maps of a depth run: a directory of depth4k_%06d.png, the JSON manifest the upscale CLI / the pipeline
+    write at their output path (whatever its suffix), or a file whose sibling `<path without suffix>_frames` directory holds
+    them (the upscale CLI keeps it next to its .mp4)"""
+    p = Path(depth_path)
+
+    def listing(d):
+        return sorted(Path(d).glob("depth4k_*.png"))
+
+    files = []
+    if p.is_dir():
+        files = listing(p)
+    elif p.is_file():
+        with open(p, "rb") as f:
+            head = f.read(1)
+        if head == b"{":
+            try:
+                man = json.loads(p.read_text())
+            except (UnicodeDecodeError, ValueError):
+                man = None
+            if isinstance(man, dict) and "frames_dir" in man:
+                d = Path(man["frames_dir"])
+                if not d.is_dir() and not d.is_absolute():
+                    d = p.parent / d
+                files = listing(d)[:int(man.get("count", 1 << 62))]
+        if not files:
+            files = listing(sibling_frames_dir(p))
+    if not files:
+        raise ValueError(f"No depth maps found in {depth_path}")
+    return files
+
+
+class HipRenderBackend:
+    """the device side of the convert step: pinned staging, one H2D, one v3d_render_stereo_batch launch, one D2H per batch"""
+
+    def __init__(self, device: str = "cuda"):
+        import torch
+        from . import _native
+        if not torch.cuda.is_available():
+            raise RuntimeError("CUDA not available but requested")
+        _native.lib()
+        self.torch, self.native, self.device = torch, _native, _native.resolve_device(device)
+        self._bufs = {}
+
+    def _staging(self, key, shape, dtype, pinned):
+        t = self._bufs.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self.torch.empty(shape, dtype=dtype, pin_memory=True) if pinned else self.torch.empty(shape, dtype=dtype, device=self.device)
+            self._bufs[key] = t
+        return t
+
+    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None):
+        """NumPy BGR frames [H,W,3] + u16 depth maps [H,W] -> NumPy u8 [n,H,outW,3].  The input staging holds `capacity`
+        frames and is reused (the synchronise at the end of the previous call made that safe); the output block comes from
+        torch's caching host allocator and returns to it once the writers drop the last frame of it."""
+        torch, nat = self.torch, self.native
+        n = len(frames)
+        H, W = depths[0].shape
+        cap = max(n, capacity or n)
+        oW = 2 * W if layout == LAYOUTS["full-sbs"] else W
+        fh = self._staging("frames_host", (cap, H, W, 3), torch.uint8, True)
+        dh = self._staging("depth_host", (cap, H, W), torch.int16, True)
+        fv, dv = fh.numpy(), dh.numpy()
+        for i, (f, d) in enumerate(zip(frames, depths)):
+            fv[i] = f
+            dv[i] = np.asarray(d, np.uint16).view(np.int16)
+        fd = self._staging("frames_dev", (cap, H, W, 3), torch.uint8, False)
+        dd = self._staging("depth_dev", (cap, H, W), torch.int16, False)
+        od = self._staging("out_dev", (cap, H, oW, 3), torch.uint8, False)
+        with torch.cuda.device(self.device):
+            fd[:n].copy_(fh[:n], non_blocking=True)
+            dd[:n].copy_(dh[:n], non_blocking=True)
+            nat.render_stereo_batch(fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n])
+            host = torch.empty((n, H, oW, 3), dtype=torch.uint8, pin_memory=True)
+            host.copy_(od[:n], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        return host.numpy()
+
+
+class DepthTo3DConverter:
+    """4K frames + 4K depth maps -> side-by-side 3D frames (DIBR on the GPU)"""
+
+    writer_pool_factory = PngWriterPool       # sink of the 8-bit RGB frames (the CLIs' hook)
+
+    def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
+                 eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
+                 batch_size: int = CONVERT_BATCH):
+        """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests)"""
+        self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout)
+        self.params = dict(max_shift=max_shift, convergence=convergence, eye_split=eye_split, layout=layout)
+        if backend is None:
+            if not str(device).startswith("cuda"):
+                raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
+            backend = HipRenderBackend(device)
+        self.backend = backend
+        self.batch_size = max(1, int(batch_size))
+
+    def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray) -> np.ndarray:
+        """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous)"""
+        frame_bgr, depth_u16 = np.asarray(frame_bgr), np.asarray(depth_u16)
+        if frame_bgr.shape[:2] != depth_u16.shape or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
+            raise ValueError(f"frame {frame_bgr.shape} and depth {depth_u16.shape} disagree")
+        return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code)[0])
+
+    def process_conversion(self, video_4k_path: str, depth_path: str, output_path: str = None, force_reprocess: bool = False,
+                           guide_start_frame: int = 0, max_frames: int = None) -> str:
+        """depth frame i pairs with 4K frame guide_start_frame + i (the offset the upscale CLI used).  Returns the output
+        path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
+        from . import sharding
+        print(f"4K + depth -> 3D ({self.params['layout']}): {video_4k_path} + {depth_path}")
+        depth_files = depth_frame_files(depth_path)
+        info = get_video_info(video_4k_path)
+        if not info:
+            raise ValueError(f"Could not read video info: {video_4k_path}")
+        W, H, fps = info['width'], info['height'], info['fps']
+        if output_path is None:
+            output_path = f"3d_{self.params['layout']}_{Path(depth_path).with_suffix('').name}.mp4"
+        output_path = Path(output_path)
+        if output_path.exists() and not force_reprocess:
+            print(f"✓ Using existing 3D video: {output_path}")
+            return str(output_path)
+        if self.layout_code == LAYOUTS["half-sbs"] and W % 2:
+            raise ValueError(f"half SBS needs an even frame width, the 4K clip is {W} wide")
+        n = len(depth_files) if max_frames is None else min(len(depth_files), max(int(max_frames), 0))
+
+        rank, world = sharding.rank_world()
+        sharding.require_initialized(world)
+        frames_dir = sibling_frames_dir(output_path)
+        frames_dir.mkdir(parents=True, exist_ok=True)
+        g0 = max(int(guide_start_frame), 0)
+        mine = list(range(rank, n, world))                       # frame i -> rank i mod world; both inputs decoded per rank
+        depths = prefetch_map(read_png16, [depth_files[i] for i in mine])
+        frames4k = iter_frames(video_4k_path, g0, n, stride=world, offset=rank)
+        batch_f, batch_d, batch_i = [], [], []
+        rendered = 0
+
+        def flush(writers):
+            nonlocal rendered
+            if not batch_f:
+                return
+            out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size)
+            for j, i in enumerate(batch_i):
+                writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=png_rgb_from_bgr)
+            rendered += len(batch_i)
+            batch_f.clear()
+            batch_d.clear()
+            batch_i.clear()
+
+        try:
+            with self.writer_pool_factory() as writers:
+                for k, i in enumerate(mine):
+                    f = next(frames4k, None)
+                    if f is None:
+                        print(f"Warning: 4K video ended after {k} of this rank's frames; rendering stops at depth frame {i}")
+                        break
+                    d = next(depths)
+                    if d.shape != f.shape[:2] or f.ndim != 3:
+                        raise ValueError(f"depth map {depth_files[i].name} is {d.shape[1]}x{d.shape[0]}, "
+                                         f"the 4K frame {f.shape[1]}x{f.shape[0]}")
+                    batch_f.append(f)
+                    batch_d.append(d)
+                    batch_i.append(i)
+                    if len(batch_f) == self.batch_size:
+                        flush(writers)
+                flush(writers)
+        finally:
+            depths.close()
+        self.last_rendered_frames = rendered
+        total = sharding.total(rendered)
+        if total == 0:
+            raise ValueError("No frames rendered")
+        sharding.barrier()
+        if rank == 0:
+            write_clip_info(frames_dir, fps)
+            finish_stereo_output(frames_dir, output_path, total, 2 * W if self.layout_code == 0 else W, H, fps, self.params,
+                                 self.gains)
+        sharding.barrier()
+        print(f"✓ 3D video saved: {output_path}")
+        return str(output_path)
+
+
+def main(argv=None, backend=None):
+    """ Command line interface: 4K video + 4K depth -> side-by-side 3D (backend: a stand-in for host tests) """
+    parser = argparse.ArgumentParser(description='4K video + its 4K depth maps -> side-by-side 3D (DIBR on the GPU)')
+    parser.add_argument('video_4k', help='Path to the 4K 2D video')
+    parser.add_argument('depth_4k', help='4K depth: a depth4k_%%06d.png directory, the manifest the upscale CLI or the pipeline '
+                                         'wrote, or their output path next to its _frames directory')
+    parser.add_argument('--output', help='Output path for the 3D video')
+    add_stereo_arguments(parser)
+    parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to render (default: all)')
+    parser.add_argument('--force', action='store_true', help='Force reprocessing even if the output exists')
+    parser.add_argument('--device', default='cuda', help='Processing device (default: cuda)')
+    guide = parser.add_mutually_exclusive_group()
+    guide.add_argument('--guide-start-frame', type=int, default=0,
+                       help='4K frame that matches depth frame 0 (the offset the upscale CLI used; default 0)')
+    guide.add_argument('--alignment-file', default=None,
+                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
+                            'round(time_offset_seconds * fps of the 4K clip)')
+    args = parser.parse_args(argv)
+    if args.alignment_file is not None:
+        from .align import guide_start_frame_from
+        try:
+            args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
+        except (OSError, ValueError, KeyError) as e:
+            print(f"Error: {e}")
+            return 1
+        print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
+    try:
+        from . import sharding
+        sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
+        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args))
+        output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
+                                              force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
+                                              max_frames=args.max_frames)
+        print(f"\n✓ Success! 3D video: {output_path}")
+    except Exception as e:
+        print(f"Error: {e}")
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    exit(main())

@@ -72,6 +72,21 @@ class HipPipelineBackend(HipStereoBackend):
         """device u16 depth samples [n,H,W] + device luma [n,Hhi,Whi] -> device u16 4K samples [n,Hhi,Whi]"""
         return self.native.guided_upscale_u16_batch(u16, luma, r, eps)
 
+    def render_stereo(self, u16_4k, gains, layout):
+        """--stereo-output: the 4K BGR frames guide_luma left in its device staging + their u16 4K depth [n,Hhi,Whi] (device)
+        -> NumPy side-by-side frames [n,Hhi,outW,3]: one launch, one D2H, no second H2D of the 4K frames.  Slots of frames
+        that had no 4K frame hold stale data; the caller drops them."""
+        torch, nat = self.torch, self.native
+        n, H, W = u16_4k.shape
+        dev = self._bufs["guide_dev"]
+        oW = 2 * W if layout == 0 else W
+        out = self._staging("stereo_dev", (dev.shape[0], H, oW, 3), torch.uint8, False)
+        nat.render_stereo_batch(dev[:n], u16_4k.contiguous(), *gains, layout, out[:n])
+        host = torch.empty((n, H, oW, 3), dtype=torch.uint8, pin_memory=True)
+        host.copy_(out[:n], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host.numpy()
+
 
 class SbsTo4kDepthPipeline:
     """SBS clip + 4K clip -> 4K 16-bit depth sequence in one pass (same files as the depth CLI followed by the upscale CLI)"""
@@ -106,11 +121,22 @@ class SbsTo4kDepthPipeline:
         self.guide_batch = max(1, int(guide_batch))
 
     def run(self, sbs_video: str, video_4k: str, output_path: str = None, start_frame: int = 0, max_frames: int = None,
-            guide_start_frame: int = 0, force_reprocess: bool = False, keep_depth_maps: bool = False) -> str:
+            guide_start_frame: int = 0, force_reprocess: bool = False, keep_depth_maps: bool = False,
+            stereo_output: str = None, stereo_options: dict = None) -> str:
         """guide_start_frame: the 4K frame that belongs to SBS frame start_frame (as for the upscale CLI).  Returns the
-        output path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
+        output path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence.
+        stereo_output: also render every frame that has a 4K frame to side-by-side 3D from the device-resident 4K frame and
+        depth (the files the convert CLI writes from this run's depth output); stereo_options: max_shift, convergence,
+        eye_split, layout (convert.py's defaults)."""
         from . import sharding
         ex, be = self.extractor, self.backend
+        stereo = None
+        if stereo_output is not None:
+            from .convert import png_rgb_from_bgr, sibling_frames_dir, stereo_settings
+            params = dict(max_shift=48.0, convergence=0.5, eye_split=0.5, layout="full-sbs")
+            params.update(stereo_options or {})
+            layout, gains = stereo_settings(**params)
+            stereo = dict(params=params, layout=layout, gains=gains, dir=sibling_frames_dir(stereo_output), count=0)
         print(f"SBS -> 4K depth: {sbs_video} + {video_4k}")
         video_info, frame_count = ex._frame_count(sbs_video, start_frame, max_frames)
         info4k = get_video_info(video_4k)
@@ -126,6 +152,10 @@ class SbsTo4kDepthPipeline:
             return str(output_path)
         if video_info['width'] % 2 != 0:
             raise ValueError("SBS frame width must be even")
+        if stereo is not None:
+            if stereo["layout"] == 1 and Whi % 2:
+                raise ValueError(f"half SBS needs an even frame width, the 4K clip is {Whi} wide")
+            stereo["dir"].mkdir(parents=True, exist_ok=True)
         if not ex.model_loaded:
             ex.load_model()
 
@@ -175,10 +205,16 @@ class SbsTo4kDepthPipeline:
                 idx = batch_idx[j0:j0 + gb]
                 frames = [next_guide() for _ in idx]
                 flat += sum(f is None for f in frames)
-                q = be.to_host_u16(be.guided_upscale_u16(u16[j0:j0 + len(idx)], be.guide_luma(frames, Hhi, Whi, gb),
-                                                         self.radius, self.eps))
+                q_dev = be.guided_upscale_u16(u16[j0:j0 + len(idx)], be.guide_luma(frames, Hhi, Whi, gb), self.radius, self.eps)
+                q = be.to_host_u16(q_dev)
                 for j, i in enumerate(idx):
                     writers.submit(frames_dir / f"depth4k_{i:06d}.png", q[j])
+                if stereo is not None and any(f is not None for f in frames):
+                    sbs3d = be.render_stereo(q_dev, stereo["gains"], stereo["layout"])
+                    for j, i in enumerate(idx):
+                        if frames[j] is not None:                   # no 4K frame: no stereo frame (its slot is stale)
+                            writers.submit(stereo["dir"] / f"frame_{i:06d}.png", sbs3d[j], encode=png_rgb_from_bgr)
+                            stereo["count"] += 1
             print(f"✓ Queued {len(batch)} 4K depth maps (rank {rank})")
             batch.clear()
             batch_idx.clear()
@@ -197,11 +233,19 @@ class SbsTo4kDepthPipeline:
         n = sharding.total(decoded)
         if n == 0:
             raise ValueError("No frames extracted from video")
+        n_stereo = sharding.total(stereo["count"]) if stereo is not None else 0
         sharding.barrier()
         if rank == 0:
             encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps)
+            if stereo is not None and n_stereo:
+                from .convert import finish_stereo_output, write_clip_info
+                write_clip_info(stereo["dir"], fps)
+                finish_stereo_output(stereo["dir"], stereo_output, n_stereo, 2 * Whi if stereo["layout"] == 0 else Whi, Hhi, fps,
+                                     stereo["params"], stereo["gains"])
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
+        if stereo is not None:
+            print(f"✓ 3D video saved: {stereo_output} ({n_stereo} frames)")
         return str(output_path)
 
 
@@ -229,6 +273,10 @@ def main(argv=None):
                             'round(time_offset_seconds * fps of the 4K clip)')
     parser.add_argument('--keep-depth-maps', action='store_true',
                         help="Also write the 1080p depth_%%06d.png maps into the depth CLI's cache directory")
+    parser.add_argument('--stereo-output', default=None,
+                        help='Also render side-by-side 3D to this path (what the convert CLI makes from the depth output)')
+    from .convert import add_stereo_arguments, stereo_options
+    add_stereo_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -247,7 +295,8 @@ def main(argv=None):
                                     unsqueeze_sbs=not args.no_unsqueeze)
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
-                               force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps)
+                               force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,
+                               stereo_output=args.stereo_output, stereo_options=stereo_options(args))
         print(f"\n✓ Success! 4K depth video: {output_path}")
     except Exception as e:
         print(f"Error: {e}")

@@ -286,6 +286,30 @@ def write_png16(path, img_u16: np.ndarray) -> None:
         f.write(encode_png16(img_u16))
 
 
+def encode_png8(img: np.ndarray, level: int = 1, bgr: bool = False) -> bytes:
+    """8-bit RGB PNG (colour type 2) of an HxWx3 uint8 image as bytes; bgr=True takes OpenCV's channel order and writes it as
+    RGB.  Same scheme as encode_png16: filter "sub" on every row (byte minus the byte one pixel, 3 bytes, to the left), zlib
+    deflate with the GIL released, so the writer pool's threads compress frames in parallel."""
+    import struct
+    import zlib
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"expected an HxWx3 uint8 image, got {a.dtype} {a.shape}")
+    h, w, _ = a.shape
+    rows = np.ascontiguousarray(a[..., ::-1] if bgr else a).reshape(h, 3 * w)
+    raw = np.empty((h, 1 + 3 * w), np.uint8)
+    raw[:, 0] = 1
+    raw[:, 1:4] = rows[:, :3]
+    if w > 1:
+        np.subtract(rows[:, 3:], rows[:, :-3], out=raw[:, 4:])
+
+    def chunk(tag: bytes, body: bytes) -> bytes:
+        return struct.pack(">I", len(body)) + tag + body + struct.pack(">I", zlib.crc32(tag + body) & 0xFFFFFFFF)
+
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+            + chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + chunk(b"IEND", b""))
+
+
 class PngWriterPool:
     """Bounded pool of PNG writer threads: submit() returns at once unless `max_pending` images are already queued
     (back-pressure keeps host memory flat), close() waits for all of them and re-raises the first failure.  The
@@ -306,15 +330,20 @@ class PngWriterPool:
         self._slots = threading.Semaphore(max_pending if max_pending else 4 * self.workers)
         self._futures = []
 
-    def _job(self, path, img):
+    def _job(self, path, img, encode):
         try:
-            write_png16(path, img)
+            if encode is None:
+                write_png16(path, img)
+            else:
+                with open(str(path), "wb") as f:
+                    f.write(encode(img))
         finally:
             self._slots.release()
 
-    def submit(self, path, img_u16: np.ndarray) -> None:
+    def submit(self, path, img_u16: np.ndarray, encode=None) -> None:
+        """queue one image; encode: bytes of the file from the image (default: the 16-bit gray PNG, encode_png16)"""
         self._slots.acquire()
-        self._futures.append(self._ex.submit(self._job, path, img_u16))
+        self._futures.append(self._ex.submit(self._job, path, img_u16, encode))
 
     def close(self) -> None:
         first = None
