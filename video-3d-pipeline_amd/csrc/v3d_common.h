@@ -46,6 +46,50 @@ extern v3d_lib_options g_v3d_opt;
 
 static inline int v3d_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ---- division-free integer arithmetic of the winner-take-all tail (plain C: host and device; tests/test_wta_arith_host.py
+// restates these lines in NumPy and checks them against exact division) ----
+#ifdef __HIPCC__
+#define V3D_HD __host__ __device__
+#else
+#define V3D_HD
+#endif
+// T1 = ceil(minS * 100 / uq) = (100 minS + uq - 1) / uq for uq = 100 - uniquenessRatio in [1, 100] and minS in [0, 32767], as
+// (n * mul) >> shift with mul = ceil(2^shift / uq), shift = 23 + ceil(log2 uq).  Exact: mul * uq = 2^shift + e with
+// 0 <= e < uq <= 2^(shift - 23), so n * mul / 2^shift = n / uq + n e / (uq 2^shift) and the excess n e / 2^shift < n / 2^23 < 1
+// (n < 2^22) is too small to carry n / uq's fraction (at most (uq - 1) / uq) over the next integer.  n < 2^22 and
+// 2^23 <= mul < 2^24 are 24-bit operands (the masks say so to the compiler): the full-rate v_mul_u32_u24 /
+// v_mul_hi_u32_u24 pair, not a 32-bit multiply-high.
+V3D_HD static inline void v3d_t1_magic(int uq, uint32_t* mul, int* shift)
+{
+    int c = 0;
+    while ((1 << c) < uq) c++;
+    *shift = 23 + c;
+    *mul = (uint32_t)((((uint64_t)1 << *shift) + (uint64_t)uq - 1) / (uint64_t)uq);
+}
+V3D_HD static inline int v3d_t1_ceil(int minS, int uq, uint32_t mul, int shift)
+{
+    const uint32_t n = ((uint32_t)minS * 100u + (uint32_t)(uq - 1)) & 0xFFFFFFu;
+    return (int)(((uint64_t)n * (mul & 0xFFFFFFu)) >> shift);
+}
+// sub-pixel term ((sm - sp) * 16 + den) / (den * 2), den = max(sm + sp - 2 minS, 1), truncated toward zero like the C
+// expression, from a = sm - minS and b = sp - minS (both >= 0).  |a - b| <= den, so |num| <= 17 den and the quotient's
+// magnitude is at most 8: four restoring steps for the bits 8, 4, 2, 1.  R carries the remainder above bit 4 and the quotient
+// bits found so far below it; subtracting ((32 den - 1) << bit) takes 2 den << bit off the remainder and sets quotient bit
+// `bit` in one go, and wraps to a huge unsigned number exactly when the remainder is too small, so the unsigned minimum
+// keeps the right one.  R < 2^25: nothing else overflows.
+V3D_HD static inline int v3d_subpix_q(int a, int b)
+{
+    const int den = a + b > 1 ? a + b : 1, num = (a - b) * 16 + den;
+    const uint32_t step = (uint32_t)(1 - 32 * den);
+    uint32_t R = (uint32_t)(num < 0 ? -num : num) << 4, t;
+    t = R + (step << 3); R = t < R ? t : R;
+    t = R + (step << 2); R = t < R ? t : R;
+    t = R + (step << 1); R = t < R ? t : R;
+    t = R + step; R = t < R ? t : R;
+    const int qm = (int)(R & 15u);
+    return num < 0 ? -qm : qm;
+}
+
 #ifdef __HIPCC__
 // ---- packed 2 x int16 arithmetic on one VGPR (v_pk_*_i16 / _u16 on gfx950) ----
 typedef short v3d_s16x2 __attribute__((ext_vector_type(2)));
@@ -60,6 +104,7 @@ __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) { return as_u
 __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_max(as_s(a), as_s(b))); }
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) { return as_u((v3d_s16x2)(as_s(a) + as_s(b))); }
 __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return as_u((v3d_s16x2)(as_s(a) - as_s(b))); }
+__device__ __forceinline__ uint32_t pk_subu(uint32_t a, uint32_t b) { return as_u((v3d_u16x2)(as_us(a) - as_us(b))); }      // wraps
 __device__ __forceinline__ uint32_t pk_add_sat(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_add_sat(as_s(a), as_s(b))); }
 __device__ __forceinline__ uint32_t pk_subu_sat(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_sub_sat(as_us(a), as_us(b))); }
 __device__ __forceinline__ uint32_t pk_minu(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_min(as_us(a), as_us(b))); }

@@ -383,6 +383,7 @@ struct ChainArgs {
     int W1, H, W, nframes;
     int P1, P2;
     int uniq;                 // uniquenessRatio
+    uint32_t t1_mul; int t1_shift;      // v3d_t1_magic(100 - uniq): the uniqueness threshold without a division (unused when uniq >= 100)
     uint32_t* wta;            // MODE 2: [nframes][H][W] WTA records (wta_word); columns < 64 are never written
     int xcd;                  // k_hfused: XCD-contiguous row-group order (V3D_HF_XCD=1).  Measured 4 % slower: off
     int persist;              // k_hfused: 0 = one wave per row group; 1 = the resident number of waves draws row groups from `ticket`
@@ -469,41 +470,46 @@ __device__ __forceinline__ void wta_pixel(const unsigned char* srow, bool valid,
     for (int i = 1; i < 32; i++) mpk = pk_minu(mpk, v[i]);
     const int minS = (int)min(mpk & 0xFFFFu, mpk >> 16);
     const uint32_t minpk = pk_bcast(minS), k64 = 0x00400040u;
-    uint32_t kacc = 0xFFFFFFFFu;
+    // (three passes, not one loop: the compiler assumes a forwarding hazard around every inline-asm result and would put an
+    //  s_nop on each side of the v_pk_mad_u16 if its producer and consumer stood next to it -- 57 per pixel)
+    uint32_t kacc = 0xFFFFFFFFu, key[32];
+#pragma unroll
+    for (int i = 0; i < 32; i++) key[i] = pk_subu_sat(v[i], minpk);
 #pragma unroll
     for (int i = 0; i < 32; i++) {
-        uint32_t key;
-        const uint32_t t = pk_subu_sat(v[i], minpk), dc = (uint32_t)(2 * i) | ((uint32_t)(2 * i + 1) << 16);
-        asm("v_pk_mad_u16 %0, %1, %2, %3 clamp" : "=v"(key) : "v"(t), "v"(k64), "s"(dc));
-        kacc = pk_minu(kacc, key);
+        const uint32_t dc = (uint32_t)(2 * i) | ((uint32_t)(2 * i + 1) << 16);
+        asm("v_pk_mad_u16 %0, %1, %2, %3 clamp" : "=v"(key[i]) : "v"(key[i]), "v"(k64), "s"(dc));
     }
+#pragma unroll
+    for (int i = 0; i < 32; i++) kacc = pk_minu(kacc, key[i]);
     const int best = (int)(min(kacc & 0xFFFFu, kacc >> 16) & 63u);
     // uniqueness: reject iff exists d, |d-best| > 1, S[d]*(100-uniq) < minS*100  <=>  S[d] < T1
-    const int uq = 100 - a.uniq, thr = minS * 100;
-    int T1 = uq > 0 ? (thr + uq - 1) / uq : (thr > 0 ? 32768 : 0);
-    T1 = min(T1, 32768);
-    const uint32_t T1pk = pk_bcast(T1), one = 0x00010001u;
+    // Everything below is computed on every lane and only SELECTED by uq, ok and valid, so that the tail is one basic block;
+    // the empty asm statements pin a value to this place (the compiler otherwise moves its computation behind a branch again).
+    const int uq = 100 - a.uniq;
+    int t1q = v3d_t1_ceil(minS, uq, a.t1_mul, a.t1_shift);
+    asm volatile("" : "+v"(t1q));
+    const int T1 = min(uq > 0 ? t1q : min(minS, 1) << 15, 32768);                // uq == 0: minS * 100 > 0 ? 32768 : 0
+    // count of S[d] < T1: S in [0, 32767] and T1 in [0, 32768], so S - T1 fits int16 and its sign bit IS the comparison.
+    // Per pair of words 2 subtracts + 2 shifts + one three-operand add (a half counts to 32 at most: no carry between them).
+    const uint32_t T1pk = pk_bcast(T1);
     uint32_t cntpk = 0;
 #pragma unroll
-    for (int i = 0; i < 32; i++) cntpk += pk_minu(pk_subu_sat(T1pk, v[i]), one);
+    for (int i = 0; i < 32; i += 2) cntpk += pk_shr_u(pk_subu(v[i], T1pk), 15) + pk_shr_u(pk_subu(v[i + 1], T1pk), 15);
     const int cnt = (int)(cntpk & 0xFFFFu) + (int)(cntpk >> 16);
     const unsigned short* s16 = reinterpret_cast<const unsigned short*>(srow);
+    const bool inner = best > 0 && best < V3D_D - 1;
     const int sm = best > 0 ? (int)s16[best - 1] : 0, sp = best < V3D_D - 1 ? (int)s16[best + 1] : 0;
     int cw = (minS < T1) ? 1 : 0;
     if (best > 0 && sm < T1) cw++;
     if (best < V3D_D - 1 && sp < T1) cw++;
-    const bool ok = valid && (minS < V3D_MAX_COST) && (cnt <= cw);
-    if (!valid) return;
-    uint32_t word = 0u;                                        // invalid
-    if (ok) {
-        int d16 = best * 16;
-        if (best > 0 && best < V3D_D - 1) {
-            const int den = max(sm + sp - 2 * minS, 1);
-            d16 += ((sm - sp) * 16 + den) / (den * 2);
-        }
-        word = wta_word(minS, d16, best);
-    }
-    a.wta[((size_t)frame * a.H + y) * a.W + x + V3D_D] = word;
+    const bool ok = (minS < V3D_MAX_COST) && (cnt <= cw);
+    int subpix = v3d_subpix_q(sm - minS, sp - minS);            // meaningful only where `inner`
+    asm volatile("" : "+v"(subpix));
+    uint32_t word = wta_word(minS, best * 16 + (inner ? subpix : 0), best);
+    asm volatile("" : "+v"(word));
+    word = ok ? word : 0u;                                     // 0 = invalid
+    if (valid) a.wta[((size_t)frame * a.H + y) * a.W + x + V3D_D] = word;
 }
 
 template <bool HORIZ, int XS, bool YREV, int MODE, int DPL>
@@ -651,6 +657,8 @@ __device__ __forceinline__ void hf_phase1(const unsigned char* Crow, uint32_t* c
 #pragma unroll
     for (int i = 0; i < NP; i++) p[i] = 0;
     uint32_t delta = P2pk;
+#pragma unroll
+    for (int i = 0; i < NP; i++) { if (V3D_CK_NT) __builtin_nontemporal_store(p[i], ck + i * 64); else ck[i * 64] = p[i]; }     // block 0: the zero state
     const int xend = (nblk - 1) * K;                       // the last block is recomputed in phase 2 anyway
     for (int xb = 0; xb < xend; xb += K) {
         // a block's K loads go out back to back: per row stream the DRAM sees one 2-KB burst, not 16 scattered lines
@@ -671,12 +679,58 @@ __device__ __forceinline__ void hf_phase1(const unsigned char* Crow, uint32_t* c
     }
 }
 
+// ---------------- phase 2, one K-pixel block: restore -> left path forwards, right path backwards -> S + both -> LDS ----------------
+// Cb / Sb: the lane's field of the block's first pixel in C and S; p, delta: the left path's state at the block start
+// (checkpoint); q, qdelta: the right path's state, carried from block to block; Sl: the lane's slot of the block's LAST
+// pixel in the wave's WTA rows (pixel j of the block sits K - 1 - j rows further on).
+// FULL (the block lies inside the row; nvalid == K): every load is base + a compile-time offset (j * C_PXB <= 1440 and
+// j * VOL_PX * 2 <= 1920 fit the instruction's immediate) and the block is ONE basic block.  !FULL is the row's last block
+// when W1 is not a multiple of K: pixels j >= nvalid re-read the row's last pixel (their left-path steps are never used)
+// and the right path starts at pixel nvalid - 1.
+template <int DPL, bool FULL>
+__device__ __forceinline__ void hf_block(const unsigned char* Cb, const int16_t* Sb, int nvalid, uint32_t (&p)[DPL / 2], uint32_t delta,
+                                         uint32_t (&q)[DPL / 2], uint32_t& qdelta, unsigned char* Sl, int dl, uint32_t P1pk, uint32_t P2pk)
+{
+    constexpr int NP = DPL / 2, LPP = 64 / DPL, K = 64 / DPL;
+    typedef typename VecT<DPL>::type Vec;
+    const bool first_lane = dl == 0, last_lane = dl == LPP - 1;
+    typename HfC<DPL>::Raw craw[K]; Vec cvv[K], svv[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const int xj = FULL ? j : min(j, nvalid - 1);
+        craw[j] = HfC<DPL>::load(Cb, xj);
+        svv[j] = ld_stream(reinterpret_cast<const Vec*>(Sb + (size_t)xj * VOL_PX));
+    }
+    uint32_t L0[K][NP];
+#pragma unroll
+    for (int j = 0; j < K; j++) {                          // forward recompute of the left path inside the block
+        uint32_t cv[NP];
+        cvv[j] = c_unpack(craw[j], dl, P2pk);              // unpacked once, as it arrives; the backward pass re-uses the int16 form
+        vec_unpack<NP>(cvv[j], cv);
+        delta = chain_step<NP, LPP>(p, delta, cv, L0[j], P1pk, P2pk, first_lane, last_lane);
+#pragma unroll
+        for (int i = 0; i < NP; i++) p[i] = L0[j][i];
+    }
+#pragma unroll
+    for (int jj = 0; jj < K; jj++) {                       // right path, backwards
+        const int j = K - 1 - jj;
+        if (FULL || j < nvalid) {                          // uniform
+            uint32_t cv[NP], sv[NP], L[NP];
+            vec_unpack<NP>(cvv[j], cv);
+            vec_unpack<NP>(svv[j], sv);
+            qdelta = chain_step<NP, LPP>(q, qdelta, cv, L, P1pk, P2pk, first_lane, last_lane);
+#pragma unroll
+            for (int i = 0; i < NP; i++) { q[i] = L[i]; sv[i] = pk_add_sat(pk_add_sat(sv[i], L0[j][i]), L[i]); }
+            *reinterpret_cast<Vec*>(Sl + jj * WTA_ROWB) = Packer<NP>::go(sv);
+        }
+    }
+}
+
 // PH: 3 = both phases in one launch; 2 = phase 2 only (k_hscan has dropped the checkpoints before)
 template <int DPL, int PH>
 __global__ __launch_bounds__(256, 4) void k_hfused(ChainArgs a, uint32_t* __restrict__ ckpt)      // four waves per SIMD: the 128-VGPR budget
 {
     constexpr int NP = DPL / 2, LPP = 64 / DPL, PPW = DPL, K = 64 / PPW;
-    typedef typename VecT<DPL>::type Vec;
     __shared__ __attribute__((aligned(16))) unsigned char sS[4 * 64 * WTA_ROWB];
 
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
@@ -685,7 +739,6 @@ __global__ __launch_bounds__(256, 4) void k_hfused(ChainArgs a, uint32_t* __rest
     const int sub = lane / LPP, dl = lane % LPP;
     const int nblk = (W1 + K - 1) / K;
     const uint32_t P1pk = pk_bcast(a.P1), P2pk = pk_bcast(a.P2);
-    const bool first_lane = dl == 0, last_lane = dl == LPP - 1;
     unsigned char* myS = sS + wib * 64 * WTA_ROWB;
     // Ticketed form (a.persist): exactly the resident number of waves is launched and each draws (frame, row group) tickets
     // until none is left, instead of one wave per row group: no partly filled last "round" of the 4096 wave slots (34 frames
@@ -715,63 +768,35 @@ __global__ __launch_bounds__(256, 4) void k_hfused(ChainArgs a, uint32_t* __rest
 #pragma unroll
     for (int i = 0; i < NP; i++) q[i] = 0;
     uint32_t qdelta = P2pk;
-    for (int blk = nblk - 1; blk >= 0; blk--) {
+    const unsigned char* Cb = Crow + (size_t)(nblk - 1) * K * C_PXB;                     // the block's first pixel in both row streams
+    const int16_t* Sb = Srow + (size_t)(nblk - 1) * K * VOL_PX;
+    unsigned char* Sl = myS + sub * K * WTA_ROWB + dl * DPL * 2;
+    // WTA: lane = (row, pixel of the block).  The lanes of rows beyond the image's last repeat row c1 (as the chains above do):
+    // same record to the same address, so the store needs no row predicate
+    const int wsub = min(lane / K, c1 - c0), wj = lane % K, y = c0 + wsub;
+    const unsigned char* Wl = myS + (wsub * K + wj) * WTA_ROWB;
+    // (Round 2, 30 frames, same-box A/B, when the kernel waited on memory with its VALU 56 % busy: prefetching the next
+    //  block's C/S into a second register set (182 VGPRs: half the occupancy, 1.84 -> 2.07 ms per 8 frames), issuing the next
+    //  block's loads before this block's WTA tail, prefetching C one further block ahead (153 VGPRs), double- and
+    //  triple-buffering phase 1's C blocks (119-122 VGPRs) -- all on the same 4.91-4.95 ms or slower; forced to 128 VGPRs the
+    //  prefetching forms spill and take 6.6-7.1 ms.  Today's budget of the block, instruction by instruction: DESIGN.md section 4.)
+    auto block = [&](int blk, auto full) {
+        constexpr bool FULL = decltype(full)::value;
         const int x0 = blk * K;
-        // (prefetching the next block's C/S into a second register set was tried: 182 VGPRs halve the
-        //  occupancy and the kernel gets slower, 1.84 -> 2.07 ms per 8 frames; other waves cover the latency.
-        //  Round 2, 30 frames, same-box A/B: issuing the next block's loads before this block's WTA tail, folding the
-        //  recomputed left path into S at once (no L0 array), prefetching C one further block ahead (all 153 VGPRs, 3
-        //  waves per SIMD), double- and triple-buffering phase 1's C blocks (119-122 VGPRs) -- every one of them lands on
-        //  the same 4.91-4.95 ms as this form; forced to 128 VGPRs the prefetching forms spill and take 6.6-7.1 ms.
-        //  Experiment builds that drop work: no WTA tail 4.57 ms, no phase 1 3.29 ms, neither 2.69 ms (= 5.9 TB/s for
-        //  phase 2's C + S + checkpoints).  So phase 2 without the WTA streams at the box's read ceiling, phase 1 adds
-        //  its 8.2 GB at ~4.5 TB/s and the WTA tail 0.4-0.6 ms that no amount of load scheduling hides: the kernel is
-        //  bound by the memory system (24.5 GB at 5.0 TB/s, VALU 56 % busy), not by latency exposure or occupancy.)
-        typename HfC<DPL>::Raw craw[K]; Vec cvv[K], svv[K];
+        uint32_t p[NP];
+        const uint32_t* c = ck + (size_t)blk * NP * 64;         // block 0 restores the zero state phase 1 has put there: no branch
 #pragma unroll
-        for (int j = 0; j < K; j++) {
-            const int xj = min(x0 + j, W1 - 1);
-            craw[j] = HfC<DPL>::load(Crow, xj);
-            svv[j] = ld_stream(reinterpret_cast<const Vec*>(Srow + (size_t)xj * VOL_PX));
-        }
-        uint32_t p[NP], delta = P2pk;
-#pragma unroll
-        for (int i = 0; i < NP; i++) p[i] = 0;
-        if (blk > 0) {
-            const uint32_t* c = ck + (size_t)blk * NP * 64;
-#pragma unroll
-            for (int i = 0; i < NP; i++) p[i] = V3D_CK_NT ? __builtin_nontemporal_load(c + i * 64) : c[i * 64];
-            delta = chain_delta<NP, LPP>(p, P2pk);
-        }
-        uint32_t L0[K][NP];
-#pragma unroll
-        for (int j = 0; j < K; j++) {                          // forward recompute of the left path inside the block
-            uint32_t cv[NP];
-            cvv[j] = c_unpack(craw[j], dl, P2pk);              // unpacked once, as it arrives; the backward pass re-uses the int16 form
-            vec_unpack<NP>(cvv[j], cv);
-            delta = chain_step<NP, LPP>(p, delta, cv, L0[j], P1pk, P2pk, first_lane, last_lane);
-#pragma unroll
-            for (int i = 0; i < NP; i++) p[i] = L0[j][i];
-        }
-#pragma unroll
-        for (int jj = 0; jj < K; jj++) {                       // right path, backwards; x >= W1 only in the last block
-            const int j = K - 1 - jj;
-            if (x0 + j < W1) {                                  // uniform
-                uint32_t cv[NP], sv[NP], L[NP];
-                vec_unpack<NP>(cvv[j], cv);
-                vec_unpack<NP>(svv[j], sv);
-                qdelta = chain_step<NP, LPP>(q, qdelta, cv, L, P1pk, P2pk, first_lane, last_lane);
-#pragma unroll
-                for (int i = 0; i < NP; i++) { q[i] = L[i]; sv[i] = pk_add_sat(pk_add_sat(sv[i], L0[j][i]), L[i]); }
-                *reinterpret_cast<Vec*>(myS + (sub * K + jj) * WTA_ROWB + dl * DPL * 2) = Packer<NP>::go(sv);
-            }
-        }
-        {
-            const int wsub = lane / K, wj = lane % K;
-            const int x = x0 + K - 1 - wj, y = c0 + wsub;
-            wta_pixel(myS + lane * WTA_ROWB, (y <= c1) && (x < W1), x, y, frame, a);
-        }
-    }
+        for (int i = 0; i < NP; i++) p[i] = V3D_CK_NT ? __builtin_nontemporal_load(c + i * 64) : c[i * 64];
+        const uint32_t delta = chain_delta<NP, LPP>(p, P2pk);
+        hf_block<DPL, FULL>(Cb, Sb, FULL ? K : W1 - x0, p, delta, q, qdelta, Sl, dl, P1pk, P2pk);
+        const int x = x0 + K - 1 - wj;
+        wta_pixel(Wl, FULL || x < W1, x, y, frame, a);
+        Cb -= K * C_PXB; Sb -= K * VOL_PX;
+    };
+    // the row's last block is the only one that can cross W1: peeled off, so that the loop runs the branch-free form alone
+    int blk = nblk - 1;
+    if (W1 % K) block(blk--, std::false_type());
+    for (; blk >= 0; blk--) block(blk, std::true_type());
     }
     if (!a.persist) break;
     work = draw();
@@ -1544,6 +1569,7 @@ struct v3d_sgbm {
     v3d_sgbm_params prm;
     int device, maxW, maxH, maxB;
     int P1, P2, ftzero, uniq, d12;
+    uint32_t t1_mul; int t1_shift;               // v3d_t1_magic(100 - uniq)
     int dpl;                                    // disparities per lane in k_chain (4 or 8)
     uint4* rec;
     unsigned char* C;                           // cost volume, C_PXB bytes per pixel
@@ -1702,6 +1728,8 @@ extern "C" int v3d_sgbm_create(const v3d_sgbm_params* prm, int device, int maxW,
     h->P2 = prm->P2 > 0 ? prm->P2 : 5; if (h->P2 < h->P1 + 1) h->P2 = h->P1 + 1;
     h->ftzero = (prm->preFilterCap > 15 ? prm->preFilterCap : 15) | 1;
     h->uniq = prm->uniquenessRatio >= 0 ? prm->uniquenessRatio : 10;
+    h->t1_mul = 0; h->t1_shift = 0;
+    if (h->uniq < 100) v3d_t1_magic(100 - h->uniq, &h->t1_mul, &h->t1_shift);
     h->d12 = prm->disp12MaxDiff > 0 ? prm->disp12MaxDiff : 1;
     // int16 headroom of the packed recurrence: L <= C <= P2 + 25*(2*ftzero + 63) and delta = min L + P2
     // must stay below 32767 (OpenCV forms delta in int32; the reference's P2 = 2400 is far inside)
@@ -1857,6 +1885,7 @@ static int run_sgbm(v3d_sgbm* h, const uint8_t* left, const uint8_t* right, int 
 
     ChainArgs a;
     a.C = h->C; a.S = h->S; a.W1 = W1; a.H = H; a.W = W; a.nframes = n; a.P1 = h->P1; a.P2 = h->P2; a.uniq = h->uniq;
+    a.t1_mul = h->t1_mul; a.t1_shift = h->t1_shift;
     a.wta = h->wta; a.xcd = h->hf_xcd; a.persist = 0; a.ticket = h->hf_ticket;
     // direction order is free (sums commute; saturation of non-negative addends is order-independent)
     const bool use_vdd = vdd_usable(h) && H < 4095;
