@@ -23,6 +23,8 @@
  *                          correlation strength (align.py's VideoAligner.find_alignment)
  *   v3d_render_stereo_batch  readme.md:37 step 4 (handed to VisionDepth3D there): DIBR from the 4K frame and its 4K depth
  *                          to a side-by-side 3D frame (convert.py, the declared video-3d-convert step)
+ *   v3d_temporal_*, v3d_depth_minmax_batch, v3d_depth_to_u16_range_batch  no call site in the reference (it normalises every
+ *                          frame on its own, depth.py:397-406): opt-in temporal stabilisation of the depth sequence
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -242,6 +244,36 @@ int v3d_align_audio(const float* a1, int n1, const float* a2, int n2, double* re
 int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
                             size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
                             int convergence, int layout, uint8_t* out_bgr /* dense [n][H][outW][3] */, void* stream);
+
+/* Temporal depth stabilisation (v3d_temporal.hip): an opt-in stage between the disparity and the u16 normalisation.  A buffer
+   holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +
+   u*gray_stride bytes), rows dense.  Bit-exact contract, all integers: tests/temporal_ref.py.
+     d16_u(p) = (int)rint(16 D_u(p)) (half to even), valid iff >= 1; the caller keeps d16 <= 32767;
+     cut[u] = 1 iff sum_p |Y_u(p) - Y_{u-1}(p)| > c*W*H (u >= 1, 64-bit integers; cut[0] = 0); frame u may contribute to target t
+       iff |u - t| <= R, 0 <= u < T and no cut lies in (min(t,u), max(t,u)];
+     s_k(p) = 3x3 edge-replicated sum of |Y_{t+k} - Y_t|, rw_k = max(0, 256 - floor(256 s_k / (9 tau))), tw_k = R + 1 - |k|,
+       w_k = tw_k * rw_k * valid(d16_{t+k}(p)); out16 = floor((2 sum w d16 + sum w) / (2 sum w)), 0 if sum w = 0 or (fill = 0 and
+       d16_t(p) invalid); output depth = out16 / 16 (exact in float32).  int32 holds every sum for R <= 8.
+   Every entry enqueues on `stream`, never synchronises, never allocates, and takes device pointers only.
+   V3D_ERR_ARG: null pointer, T outside [1, 65535], W or H < 1, targets outside the buffer, R outside [0, 8], tau outside [1, 255],
+   c outside [0, 256], fill not 0/1, a stride below the frame size (T > 1). */
+/* cut_out u8 [T]; ws: device scratch of >= 8*T bytes, 8-byte aligned */
+int v3d_temporal_cuts(const uint8_t* gray, size_t gray_stride /* bytes */, int T, int W, int H, int c, void* ws,
+                      uint8_t* cut_out, void* stream);
+/* minmax_out f32 [T][2]: min and max of each frame, the exact values v3d_depth_to_u16_batch reduces */
+int v3d_depth_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride /* elements */, float* minmax_out,
+                           void* stream);
+/* lohi_out f32 [n][2] for targets t0 .. t0+n-1: min of the minima, max of the maxima over the frames that may contribute */
+int v3d_temporal_range(const float* minmax, const uint8_t* cut, int T, int t0, int n, int R, float* lohi_out, void* stream);
+/* out f32 dense [n][H][W]: the filtered depth of targets t0 .. t0+n-1, windows clipped to [0, T) */
+int v3d_temporal_filter_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
+                              size_t gray_stride /* bytes */, int T, int W, int H, int t0, int n, int R, int tau, int fill,
+                              const uint8_t* cut, float* out, void* stream);
+/* v3d_depth_to_u16_batch with frame f's (min, max) read from lohi[2f], lohi[2f+1] instead of reduced from the frame: same
+   float32 operations in the same order, hi == lo -> 0, the result clamped to [0, 65535] before the conversion.  With a frame's
+   own min and max it reproduces v3d_depth_to_u16_batch bit for bit.  out dense [n][frame_elems]; n <= 65535 */
+int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride /* elements */,
+                                 const float* lohi, uint16_t* out, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

@@ -1,0 +1,117 @@
+"""Temporal stabilisation stage on one GPU, 1080p, a 34-frame pass in steady state (2R carried frames + 34 new ones, 34 targets):
+time per frame of the filter kernel alone and of the whole stage (concat of the carry, cuts, min/max, range, filter,
+normalisation) from HIP events (warm-up, 20 timed launches), the filter's share of 8 TB/s on its algorithmic 9 B/px, and the
+device step of the one-pass pipeline (sbs_to_disparity + u16 samples) with the stage on and off, alternating in this one
+process.  Prints one JSON line.
+
+    python tools/temporal_rate.py [--kernel-only] [--radius 2 4]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "video-3d-pipeline_amd")]
+from video_3d_pipeline import _native as N  # noqa: E402
+
+W, H, NF, REPS, HBM = 1920, 1080, 34, 20, 8.0e12
+
+
+def clip(T, seed=0):
+    """static scene + per-frame noise: disparity with sub-pixel jitter and 5 % invalid pixels, luma with sigma-3 noise"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.linspace(4, 60, W, device="cuda")[None, None, :].expand(T, H, W)
+    d16 = torch.round((x + 0.1 * torch.randn((T, H, W), generator=g, device="cuda")) * 16)
+    d16[torch.rand((T, H, W), generator=g, device="cuda") < 0.05] = 0
+    base = torch.randint(0, 256, (1, H, W), generator=g, device="cuda").float()
+    gray = (base + 3 * torch.randn((T, H, W), generator=g, device="cuda")).clamp(0, 255).round().to(torch.uint8)
+    return (d16 / 16).float().contiguous(), gray.contiguous()
+
+
+def timed(fn, reps=REPS, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps            # us per call
+
+
+def stage_rates(radii):
+    from video_3d_pipeline.depth import HipStereoBackend
+    be = HipStereoBackend()
+    res = {}
+    for R in radii:
+        T = NF + 2 * R
+        depth, gray = clip(T, R)
+        cut = N.temporal_cuts(gray, 20)
+        out = torch.empty((NF, H, W), dtype=torch.float32, device="cuda")
+        us_f = timed(lambda: N.temporal_filter_batch(depth, gray, R, 12, cut, True, R, NF, out)) / NF
+        carry_d, carry_g, new_d, new_g = depth[:2 * R], gray[:2 * R], depth[2 * R:], gray[2 * R:]
+
+        def stage():
+            d, g = be.temporal_concat(carry_d, new_d), be.temporal_concat(carry_g, new_g)
+            return be.temporal_stabilize(d, g, R, NF, R, 12, 20, True)
+
+        us_s = timed(stage) / NF
+        nbytes = W * H * 9
+        res[f"R{R}"] = {"filter_us_per_frame": round(us_f, 2), "stage_us_per_frame": round(us_s, 2),
+                        "filter_algorithmic_bytes_per_frame": nbytes,
+                        "filter_fraction_of_8TBps": round(nbytes / (us_f * 1e-6) / HBM, 3),
+                        "filter_bytes_read_per_frame_walking_the_window": W * H * (5 * (2 * R + 1) + 4)}
+    return res
+
+
+def pipeline_step(R=2, rounds=5):
+    """sbs_to_disparity + the u16 samples of a 34-frame pass, stage off / on alternating; us per frame"""
+    from video_3d_pipeline import synthetic as syn
+    from video_3d_pipeline.pipeline import HipPipelineBackend
+    be = HipPipelineBackend()
+    frames = [syn.sbs_frame(W, H, i % 4) for i in range(NF)]
+    state = {}
+
+    def off():
+        return be.depth_to_u16_batch(be.sbs_to_disparity(frames, True))
+
+    def on():
+        depth = be.sbs_to_disparity(frames, True)
+        gray = be.left_gray(NF)
+        if "d" in state:
+            depth, gray = be.temporal_concat(state["d"], depth), be.temporal_concat(state["g"], gray)
+        else:
+            depth, gray = depth.clone(), gray.clone()
+        t0 = len(depth) - NF - R if len(depth) > NF else 0
+        out = be.temporal_stabilize(depth, gray, max(t0, 0), NF if len(depth) > NF else NF - R, R, 12, 20, True)
+        state["d"], state["g"] = depth[-2 * R:], gray[-2 * R:]
+        return out
+
+    off(), on(), on()
+    t_off, t_on = [], []
+    for _ in range(rounds):
+        t_off.append(timed(off, reps=2, warm=0) / NF)
+        t_on.append(timed(on, reps=2, warm=0) / NF)
+    return {"radius": R, "off_us_per_frame": [round(t, 1) for t in t_off], "on_us_per_frame": [round(t, 1) for t in t_on],
+            "off_median": round(float(np.median(t_off)), 1), "on_median": round(float(np.median(t_on)), 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--radius", type=int, nargs="+", default=[2, 4])
+    ap.add_argument("--kernel-only", action="store_true", help="skip the pipeline step (profiler runs)")
+    a = ap.parse_args()
+    res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "frames_per_pass": NF, "stage": stage_rates(a.radius)}
+    if not a.kernel_only:
+        res["pipeline_step"] = pipeline_step()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

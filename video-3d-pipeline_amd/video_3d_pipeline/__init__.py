@@ -16,6 +16,7 @@ _EXPORTS = {
     "SimpleDepthUpscaler": ("upscale", "SimpleDepthUpscaler"),
     "SbsTo4kDepthPipeline": ("pipeline", "SbsTo4kDepthPipeline"),
     "DepthTo3DConverter": ("convert", "DepthTo3DConverter"),
+    "TemporalStabilizer": ("temporal", "TemporalStabilizer"),
     "get_video_info": ("utils", "get_video_info"),
     "create_work_directory": ("utils", "create_work_directory"),
 }

@@ -28,6 +28,8 @@ EXPORTS = (
     "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
     "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
     "v3d_render_stereo_batch",
+    "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
+    "v3d_depth_to_u16_range_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -127,6 +129,11 @@ def lib():
         L.v3d_xcorr.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.v3d_align_audio.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.v3d_render_stereo_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]
+        L.v3d_temporal_cuts.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp]
+        L.v3d_depth_minmax_batch.argtypes = [vp, ci, sz, sz, vp, vp]
+        L.v3d_temporal_range.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+        L.v3d_temporal_filter_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.v3d_depth_to_u16_range_batch.argtypes = [vp, ci, sz, sz, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -586,6 +593,107 @@ def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, l
         _check(lib().v3d_render_stereo_batch(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
                                              H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout),
                                              _dev(out, torch.uint8, "out"), _stream()), "v3d_render_stereo_batch")
+    return out
+
+
+TEMPORAL_MAX_RADIUS = 8
+
+
+def _clip(t, dtype, what):
+    """a [T,H,W] device tensor whose frames are dense HxW images (only the frame stride may differ) -> (pointer, frame stride)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != 3:
+        raise NativeError(f"{what}: expected a {dtype} [T,H,W] device tensor")
+    T, H, W = t.shape
+    if T < 1 or H < 1 or W < 1:
+        raise NativeError(f"{what}: empty clip {tuple(t.shape)}")
+    if t.stride(2) != 1 or t.stride(1) != W or (T > 1 and t.stride(0) < H * W):
+        raise NativeError(f"{what}: frames must be dense HxW images (only the frame stride may differ)")
+    return C.c_void_p(t.data_ptr()), (t.stride(0) if T > 1 else H * W)
+
+
+def _temporal_window(T, t0, n, radius):
+    n = T - t0 if n is None else n
+    if not 0 <= radius <= TEMPORAL_MAX_RADIUS:
+        raise ValueError(f"temporal radius must be in [0, {TEMPORAL_MAX_RADIUS}], got {radius}")
+    if t0 < 0 or n < 1 or t0 + n > T:
+        raise ValueError(f"targets {t0}..{t0 + n - 1} outside a buffer of {T} frames")
+    return n
+
+
+def temporal_cuts(gray, cut_threshold=20):
+    """left gray u8 [T,H,W] -> u8 [T] scene-cut flags on the device (v3d_temporal_cuts): cut[u] = 1 iff the mean absolute
+    luma difference between frames u-1 and u exceeds cut_threshold levels"""
+    if not 0 <= cut_threshold <= 256:
+        raise ValueError(f"cut threshold must be in [0, 256], got {cut_threshold}")
+    g, gs = _clip(gray, torch.uint8, "gray")
+    T, H, W = gray.shape
+    ws = torch.empty(T, dtype=torch.int64, device=gray.device)
+    out = torch.empty(T, dtype=torch.uint8, device=gray.device)
+    with torch.cuda.device(gray.device):
+        _check(lib().v3d_temporal_cuts(g, gs, T, W, H, int(cut_threshold), _dev(ws, torch.int64, "ws"), _dev(out, torch.uint8, "cut"),
+                                       _stream()), "v3d_temporal_cuts")
+    return out
+
+
+def depth_minmax_batch(depth):
+    """float32 [T,H,W] -> float32 [T,2] on the device: each frame's min and max (v3d_depth_minmax_batch)"""
+    d, ds = _clip(depth, torch.float32, "depth")
+    T, H, W = depth.shape
+    out = torch.empty((T, 2), dtype=torch.float32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        _check(lib().v3d_depth_minmax_batch(d, T, H * W, ds, _dev(out, torch.float32, "minmax"), _stream()), "v3d_depth_minmax_batch")
+    return out
+
+
+def temporal_range(minmax, cut, radius, t0=0, n=None):
+    """per-frame (min, max) [T,2] + cut flags [T] -> the clip-stable (lo, hi) [n,2] of targets t0 .. t0+n-1 (v3d_temporal_range)"""
+    T = minmax.shape[0]
+    n = _temporal_window(T, t0, n, radius)
+    if tuple(minmax.shape) != (T, 2) or tuple(cut.shape) != (T,):
+        raise NativeError(f"temporal_range: minmax {tuple(minmax.shape)} / cut {tuple(cut.shape)} do not describe one clip")
+    out = torch.empty((n, 2), dtype=torch.float32, device=minmax.device)
+    with torch.cuda.device(minmax.device):
+        _check(lib().v3d_temporal_range(_dev(minmax, torch.float32, "minmax"), _dev(cut, torch.uint8, "cut"), T, t0, n, int(radius),
+                                        _dev(out, torch.float32, "lohi"), _stream()), "v3d_temporal_range")
+    return out
+
+
+def temporal_filter_batch(depth, gray, radius, tau, cut, fill=True, t0=0, n=None, out=None):
+    """the temporal filter (v3d_temporal_filter_batch): depth f32 [T,H,W] (<= 0 invalid), left gray u8 [T,H,W], cut u8 [T] ->
+    filtered depth f32 [n,H,W] of targets t0 .. t0+n-1.  Bit-exact contract: tests/temporal_ref.py."""
+    d, ds = _clip(depth, torch.float32, "depth")
+    g, gs = _clip(gray, torch.uint8, "gray")
+    T, H, W = depth.shape
+    if tuple(gray.shape) != (T, H, W) or tuple(cut.shape) != (T,):
+        raise NativeError(f"gray {tuple(gray.shape)} / cut {tuple(cut.shape)} do not match depth {tuple(depth.shape)}")
+    n = _temporal_window(T, t0, n, radius)
+    if not 1 <= tau <= 255:
+        raise ValueError(f"temporal tau must be in [1, 255], got {tau}")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.float32, device=depth.device)
+    if tuple(out.shape) != (n, H, W):
+        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    with torch.cuda.device(depth.device):
+        _check(lib().v3d_temporal_filter_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
+                                               _dev(cut, torch.uint8, "cut"), _dev(out, torch.float32, "out"), _stream()),
+               "v3d_temporal_filter_batch")
+    return out
+
+
+def depth_to_u16_range_batch(depth, lohi, out=None):
+    """float32 [n,H,W] + (lo, hi) float32 [n,2] on the device -> uint16 bit patterns in an int16 [n,H,W] tensor: depth_to_u16_batch
+    with the range given instead of reduced (v3d_depth_to_u16_range_batch)"""
+    d, ds = _clip(depth, torch.float32, "depth")
+    n, H, W = depth.shape
+    if tuple(lohi.shape) != (n, 2):
+        raise NativeError(f"lohi: expected shape {(n, 2)}, got {tuple(lohi.shape)}")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.int16, device=depth.device)
+    if tuple(out.shape) != (n, H, W):
+        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    with torch.cuda.device(depth.device):
+        _check(lib().v3d_depth_to_u16_range_batch(d, n, H * W, ds, _dev(lohi, torch.float32, "lohi"), _dev(out, torch.int16, "out"),
+                                                  _stream()), "v3d_depth_to_u16_range_batch")
     return out
 
 

@@ -192,6 +192,36 @@ class HipStereoBackend:
         d = depth if self.torch.is_tensor(depth) else nat.to_device(np.asarray(depth, np.float32), self.device)
         return nat.depth_to_u16(d.contiguous()).cpu().numpy().view(np.uint16)
 
+    # ---- temporal stabilisation (temporal.py; only called with --temporal-radius > 0) ----
+    def left_gray(self, n: int):
+        """the left gray [n,H,W] of the latest sbs_to_disparity pass: a view of its staging buffer, which the next pass
+        overwrites (temporal_concat copies it)"""
+        return self._bufs["lg"][:n]
+
+    def temporal_concat(self, held, new):
+        """frames carried from earlier passes (or None) + the frames of this pass -> one private device buffer"""
+        return new.clone() if held is None else self.torch.cat([held, new])
+
+    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill):
+        """buffer of T frames (device depth f32 and left gray u8 [T,H,W]) -> device u16 samples (int16-viewed) [n,H,W] of
+        targets t0 .. t0+n-1: cuts, per-frame min/max, clip-stable range, filter, normalisation -- nine launches on the
+        current stream, nothing comes back to the host"""
+        nat = self.native
+        cut = nat.temporal_cuts(gray, cut_threshold)
+        lohi = nat.temporal_range(nat.depth_minmax_batch(depth), cut, radius, t0, n)
+        filt = nat.temporal_filter_batch(depth, gray, radius, tau, cut, fill, t0, n)
+        return nat.depth_to_u16_range_batch(filt, lohi)
+
+    def to_host_u16(self, u16):
+        """device u16 [n,H,W] -> NumPy uint16 [n,H,W] through pinned memory.  The pinned block comes from torch's caching host
+        allocator and goes back to it once the writers drop the last frame of it: no allocation in the steady state, and no
+        buffer is overwritten while a writer thread still encodes from it."""
+        torch = self.torch
+        host = torch.empty(tuple(u16.shape), dtype=torch.int16, pin_memory=True)
+        host.copy_(u16, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host.numpy().view(np.uint16)
+
 
 class HybridStereoDepthExtractor:
     """ GPU-accelerated depth extraction from SBS video using hybrid stereo matching + neural guidance """
@@ -210,9 +240,17 @@ class HybridStereoDepthExtractor:
                  stereo_only: bool = False,
                  unsqueeze_sbs: bool = True,
                  backend=None,
-                 mono_provider=None):
+                 mono_provider=None,
+                 temporal_radius: int = 0,
+                 temporal_tau: int = 12,
+                 temporal_cut: int = 20,
+                 temporal_fill: bool = True):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
-        depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350 """
+        depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
+        temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
+        on its own, the reference's behaviour.  process_frame_batch / save_depth_map stay per-frame: a list of pairs is not a clip """
+        from .temporal import check_parameters
+        self.temporal = check_parameters(temporal_radius, temporal_tau, temporal_cut, temporal_fill)
 
         self.device = device
         self.work_dir = create_work_directory(work_dir)
@@ -296,8 +334,11 @@ class HybridStereoDepthExtractor:
         return None
 
     def get_cache_path(self, video_path: str, frame_start: int, frame_count: int) -> Path:
-        """ Generate cache path for depth maps (key format identical to depth.py:119-120) """
+        """ Generate cache path for depth maps (key format identical to depth.py:119-120; with temporal stabilisation on, the
+        key also carries its four parameters, so stabilised and per-frame maps never share a directory) """
+        from .temporal import cache_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
+        cache_key += cache_suffix(*self.temporal)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -408,6 +449,8 @@ class HybridStereoDepthExtractor:
 
         rank, world = sharding.rank_world()
         sharding.require_initialized(world)                  # WORLD_SIZE > 1 without a process group would race the cache dir
+        if self.temporal[0] > 0:
+            return self._process_video_temporal(video_path, start_frame, frame_count, video_info, cache_path, rank, world)
         processed_count = 0
         batch, batch_idx = [], []
         # frames per device pass: decoupled from batch_size (which the reference only uses to chunk its frame list,
@@ -458,6 +501,69 @@ class HybridStereoDepthExtractor:
         return cache_path
 
 
+    def _process_video_temporal(self, video_path, start_frame, frame_count, video_info, cache_path, rank, world) -> Path:
+        """ process_video_sbs with --temporal-radius: each rank owns a contiguous block of frames and also decodes and matches
+        a halo of `radius` frames on each side (sharding.temporal_block); the u16 samples come from the streaming stabiliser,
+        `radius` frames behind the matcher """
+        import json
+        from . import sharding
+        from .temporal import BlockStabilizer, manifest_entry
+        be = self.backend
+        radius = self.temporal[0]
+        first, count, hb, ha = sharding.temporal_block(frame_count, rank, world, radius)
+        ow = video_info['width'] if self.unsqueeze_sbs else video_info['width'] // 2
+        sizer = getattr(be, "compute_batch_size", None)
+        pass_frames = sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
+        self.last_pass_frames = pass_frames
+        provider = self._guidance_provider()
+        stab = BlockStabilizer(be, self.temporal, first, count, hb)
+        writers = self.writer_pool_factory()
+        processed_count = 0
+        batch = []
+
+        def write(idx, u16):
+            nonlocal processed_count
+            if not idx:
+                return
+            host = be.to_host_u16(u16)
+            for j, frame_idx in enumerate(idx):
+                writers.submit(cache_path / f"depth_{frame_idx:06d}.png", host[j])
+            processed_count += len(idx)
+            print(f"✓ Queued batch depth maps ({processed_count} on rank {rank})")
+
+        def flush():
+            if not batch:
+                return
+            if provider is not None:
+                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs, provider)
+            else:
+                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs)
+            write(*stab.push(depth, be.left_gray(len(batch))))
+            batch.clear()
+
+        decoded = 0
+        with writers:
+            if count:
+                for frame in iter_frames(video_path, start_frame + first - hb, hb + count + ha):
+                    decoded += 1
+                    batch.append(frame)
+                    if len(batch) == pass_frames:
+                        flush()
+                flush()
+                write(*stab.finish())
+        self.last_decoded_frames = decoded
+        if sharding.total(processed_count) == 0:
+            raise ValueError("No frames extracted from video")
+        if rank == 0:
+            (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal)))
+        sharding.barrier()
+
+        print(f"✓ Depth extraction complete: {cache_path}")
+        print(f"  Processed {processed_count} frames")
+        print(f"  Output directory: {cache_path}")
+        return cache_path
+
+
 # run_pipeline.py:12,63 and reference __init__.py:6 import this name (SURVEY.md fact 0.4)
 IGEVStereoDepthExtractor = HybridStereoDepthExtractor
 
@@ -476,6 +582,8 @@ def main(argv=None):
     parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
     parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
+    from .temporal import add_temporal_arguments, temporal_options
+    add_temporal_arguments(parser)
     args = parser.parse_args(argv)
 
     stereo_only = args.stereo_only or args.no_neural
@@ -488,7 +596,7 @@ def main(argv=None):
         extractor = HybridStereoDepthExtractor(
             model_checkpoint=args.model, work_dir=args.work_dir, cache_dir=args.work_dir, device=args.device,
             batch_size=args.batch_size, use_neural_guidance=use_neural_guidance, stereo_only=stereo_only,
-            unsqueeze_sbs=unsqueeze_sbs)
+            unsqueeze_sbs=unsqueeze_sbs, **temporal_options(args))
         output_path = extractor.process_video_sbs(video_path=args.video, start_frame=args.start_frame,
                                                   max_frames=args.max_frames, force_reprocess=args.force)
         print(f"\n✓ Success! Depth maps saved to: {output_path}")

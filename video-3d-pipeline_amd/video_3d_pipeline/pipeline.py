@@ -7,6 +7,7 @@ and through zlib twice before the 4K filter sees it.  Here the depth stays on th
 
     SBS frames -> HipStereoBackend.sbs_to_disparity (the depth CLI's own pass, neural guidance included)
                -> v3d_depth_to_u16_batch (per-frame min-max -> u16, the depth PNG's samples)
+                  [--temporal-radius R: the temporal stabiliser's u16 samples instead (temporal.py), R frames behind the matcher]
                -> [--keep-depth-maps: depth_%06d.png into the depth CLI's cache directory]
                -> v3d_guided_upscale_u16_batch against the matching 4K frames' luma -> u16 4K samples -> writer pool
 
@@ -16,8 +17,6 @@ byte-for-byte what the two CLIs write.  The two-step route stays the reference f
 """
 import argparse
 from pathlib import Path
-
-import numpy as np
 
 from .depth import HipStereoBackend, HybridStereoDepthExtractor
 from .upscale import GUIDED_EPS, GUIDED_RADIUS, encode_depth4k
@@ -36,15 +35,7 @@ class HipPipelineBackend(HipStereoBackend):
         """device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W]"""
         return self.native.depth_to_u16_batch(depth)
 
-    def to_host_u16(self, u16):
-        """device u16 [n,H,W] -> NumPy uint16 [n,H,W] through pinned memory.  The pinned block comes from torch's caching host
-        allocator and goes back to it once the writers drop the last frame of it: no allocation in the steady state, and no
-        buffer is overwritten while a writer thread still encodes from it."""
-        torch = self.torch
-        host = torch.empty(tuple(u16.shape), dtype=torch.int16, pin_memory=True)
-        host.copy_(u16, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return host.numpy().view(np.uint16)
+    # to_host_u16 (device u16 -> NumPy through pinned memory) is HipStereoBackend's: the depth CLI's temporal path uses it too
 
     def guide_luma(self, frames, height, width, capacity):
         """4K BGR frames (None = beyond the clip: flat 128) -> device luma [n,height,width].  The frames are gathered in one
@@ -105,8 +96,13 @@ class SbsTo4kDepthPipeline:
                  eps: float = GUIDED_EPS,
                  guide_batch: int = GUIDE_BATCH,
                  backend=None,
-                 mono_provider=None):
-        """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests)"""
+                 mono_provider=None,
+                 temporal_radius: int = 0,
+                 temporal_tau: int = 12,
+                 temporal_cut: int = 20,
+                 temporal_fill: bool = True):
+        """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
+        temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own)"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -116,7 +112,8 @@ class SbsTo4kDepthPipeline:
         self.extractor = HybridStereoDepthExtractor(
             model_checkpoint=model_checkpoint, work_dir=work_dir, cache_dir=work_dir, device=device, batch_size=batch_size,
             use_neural_guidance=use_neural_guidance, stereo_only=stereo_only, unsqueeze_sbs=unsqueeze_sbs, backend=backend,
-            mono_provider=mono_provider)
+            mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
+            temporal_fill=temporal_fill)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
 
@@ -171,9 +168,20 @@ class SbsTo4kDepthPipeline:
         provider = ex._guidance_provider()
         # frame i -> rank i mod world; each rank decodes only its own frames of BOTH clips (4K frame g0 + i guides SBS frame i)
         g0 = max(int(guide_start_frame), 0)
-        guides = iter_frames(video_4k, g0, frame_count, stride=world, offset=rank)
+        stab = None
+        if ex.temporal[0] > 0:
+            # temporal stabilisation: a contiguous block per rank plus a halo of `radius` SBS frames on each side that is
+            # decoded and matched but not written; the 4K guides are the block's own frames only
+            from .temporal import BlockStabilizer, manifest_entry
+            first, count, hb, ha = sharding.temporal_block(frame_count, rank, world, ex.temporal[0])
+            stab = BlockStabilizer(be, ex.temporal, first, count, hb)
+            guides = iter_frames(video_4k, g0 + first, count) if count else iter(())
+            sbs_frames = iter_frames(sbs_video, start_frame + first - hb, hb + count + ha) if count else iter(())
+        else:
+            guides = iter_frames(video_4k, g0, frame_count, stride=world, offset=rank)
+            sbs_frames = iter_frames(sbs_video, start_frame, frame_count, stride=world, offset=rank)
         guide_state = {"delivered": 0, "ended": False}
-        flat = 0
+        flat = written = 0
         batch, batch_idx = [], []
 
         def next_guide():
@@ -189,20 +197,31 @@ class SbsTo4kDepthPipeline:
             return f
 
         def flush(writers):
-            nonlocal flat
             if not batch:
                 return
             if provider is not None:
                 depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, provider)
             else:
                 depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs)
-            u16 = be.depth_to_u16_batch(depth)
+            if stab is None:
+                emit(writers, list(batch_idx), be.depth_to_u16_batch(depth))
+            else:
+                emit(writers, *stab.push(depth, be.left_gray(len(batch))))
+            batch.clear()
+            batch_idx.clear()
+
+        def emit(writers, out_idx, u16):
+            """the u16 depth samples of frames out_idx -> [depth PNGs,] guided filter, 4K PNGs [, stereo frames]"""
+            nonlocal flat, written
+            if not out_idx:
+                return
+            written += len(out_idx)
             if keep_depth_maps:
                 lo = be.to_host_u16(u16)
-                for j, i in enumerate(batch_idx):
+                for j, i in enumerate(out_idx):
                     writers.submit(cache_path / f"depth_{i:06d}.png", lo[j])
-            for j0 in range(0, len(batch), gb):
-                idx = batch_idx[j0:j0 + gb]
+            for j0 in range(0, len(out_idx), gb):
+                idx = out_idx[j0:j0 + gb]
                 frames = [next_guide() for _ in idx]
                 flat += sum(f is None for f in frames)
                 q_dev = be.guided_upscale_u16(u16[j0:j0 + len(idx)], be.guide_luma(frames, Hhi, Whi, gb), self.radius, self.eps)
@@ -215,28 +234,32 @@ class SbsTo4kDepthPipeline:
                         if frames[j] is not None:                   # no 4K frame: no stereo frame (its slot is stale)
                             writers.submit(stereo["dir"] / f"frame_{i:06d}.png", sbs3d[j], encode=png_rgb_from_bgr)
                             stereo["count"] += 1
-            print(f"✓ Queued {len(batch)} 4K depth maps (rank {rank})")
-            batch.clear()
-            batch_idx.clear()
+            print(f"✓ Queued {len(out_idx)} 4K depth maps (rank {rank})")
 
         decoded = 0
         with self.writer_pool_factory() as writers:
-            for k, frame in enumerate(iter_frames(sbs_video, start_frame, frame_count, stride=world, offset=rank)):
+            for k, frame in enumerate(sbs_frames):
                 decoded += 1
                 batch.append(frame)
                 batch_idx.append(rank + k * world)
                 if len(batch) == pass_frames:
                     flush(writers)
             flush(writers)
+            if stab is not None:
+                emit(writers, *stab.finish())
         self.last_decoded_frames = decoded
         self.last_flat_guides = flat
-        n = sharding.total(decoded)
+        n = sharding.total(written)
         if n == 0:
             raise ValueError("No frames extracted from video")
         n_stereo = sharding.total(stereo["count"]) if stereo is not None else 0
         sharding.barrier()
         if rank == 0:
-            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps)
+            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps,
+                           {"temporal": manifest_entry(*ex.temporal)} if stab is not None else None)
+            if stab is not None and keep_depth_maps:
+                import json
+                (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*ex.temporal)))
             if stereo is not None and n_stereo:
                 from .convert import finish_stereo_output, write_clip_info
                 write_clip_info(stereo["dir"], fps)
@@ -276,7 +299,9 @@ def main(argv=None):
     parser.add_argument('--stereo-output', default=None,
                         help='Also render side-by-side 3D to this path (what the convert CLI makes from the depth output)')
     from .convert import add_stereo_arguments, stereo_options
+    from .temporal import add_temporal_arguments, temporal_options
     add_stereo_arguments(parser)
+    add_temporal_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -292,7 +317,7 @@ def main(argv=None):
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
         pipe = SbsTo4kDepthPipeline(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device,
                                     batch_size=args.batch_size, use_neural_guidance=not stereo_only, stereo_only=stereo_only,
-                                    unsqueeze_sbs=not args.no_unsqueeze)
+                                    unsqueeze_sbs=not args.no_unsqueeze, **temporal_options(args))
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,

@@ -47,6 +47,21 @@ def my_frames(n_frames: int, rank: int, world: int):
     return list(range(rank, n_frames, world))
 
 
+def temporal_block(n_frames: int, rank: int, world: int, radius: int):
+    """(first, count, halo_before, halo_after) of rank's share when frames need their temporal neighbours (--temporal-radius):
+    round-robin frames have none, so each rank owns a contiguous block of ceil(n / world) frames and also decodes and matches
+    `radius` frames on each side that it does not write.  Cuts, weights and ranges all reach exactly `radius` frames, so the
+    halo makes every owned frame equal to a single process's.  A rank past the end of a short clip gets count 0."""
+    if n_frames < 0 or world < 1 or not 0 <= rank < world or radius < 0:
+        raise ValueError(f"bad block request: {n_frames} frames, rank {rank} of {world}, radius {radius}")
+    block = -(-n_frames // world)
+    first = min(rank * block, n_frames)
+    count = min(block, n_frames - first)
+    if count == 0:
+        return first, 0, 0, 0
+    return first, count, min(radius, first), min(radius, n_frames - first - count)
+
+
 def init_process_group(backend=None):
     """one process per GPU; backend 'nccl' is RCCL on ROCm, 'gloo' for CPU rehearsals.  Sets the current device to
     LOCAL_RANK so that every later "cuda" resolves to this rank's GPU (see _native.resolve_device)."""

@@ -88,3 +88,93 @@ def gray_pair(W, H, frame_idx=0):
                  + a[..., 0].astype(np.int32) * 3735 + (1 << 14)) >> 15).astype(np.uint8)
 
     return gray(left), gray(right)
+
+
+# ---- a temporally coherent clip (temporal stabilisation: tests, tools/temporal_rate.py) ----
+# The frames above draw a new texture per index, which is right for per-frame work and useless for anything that compares
+# neighbouring frames.  Here a scene (seed) fixes the background texture and its disparity ramp; a textured rectangle at
+# d = 40 moves `speed` pixels per frame over it; every frame and eye gets fresh N(0, sigma) sensor noise.
+
+TEMPORAL_OBJECT_DISPARITY = 40.0
+
+
+def _gray_texture(rng, h, w, sigma=1.5, gain=2.5):
+    t = _blur(rng.integers(0, 256, (h, w)), sigma)
+    return np.clip((t - 127.5) * gain + 127.5, 0, 255)
+
+
+def temporal_object_box(W, H, t, speed=6):
+    """(x0, y0, x1, y1) of the moving rectangle in the left view of frame t (half-open)"""
+    ow, oh = max(W * 3 // 20, 4), max(H * 2 // 5, 4)
+    x0, y0 = W * 3 // 10 + int(speed) * t, H * 3 // 10
+    return x0, y0, x0 + ow, y0 + oh
+
+
+def temporal_gt_disparity(W, H, t, scene_seed=0, speed=6):
+    """ground-truth disparity of the left view of frame t, float32 HxW: the scene's ramp, the rectangle at 40"""
+    a = 4.0 + 2.0 * (scene_seed % 3)
+    x = np.arange(W, dtype=np.float64)[None, :]
+    d = np.broadcast_to(a + 16.0 * x / max(W - 1, 1), (H, W)).astype(np.float32).copy()
+    x0, y0, x1, y1 = temporal_object_box(W, H, t, speed)
+    d[max(y0, 0):min(y1, H), max(x0, 0):min(x1, W)] = TEMPORAL_OBJECT_DISPARITY
+    return d
+
+
+def temporal_gray_pair(W, H, t, scene_seed=0, speed=6, sigma=3.0, noise_seed=0, margin=64):
+    """full-width gray left / right views (HxW u8) of frame t of scene `scene_seed`"""
+    rng = np.random.default_rng(777000 + scene_seed)
+    bg = _gray_texture(rng, H, W + 2 * margin)
+    x0, y0, x1, y1 = temporal_object_box(W, H, t, speed)
+    obj = _gray_texture(rng, y1 - y0, x1 - x0, sigma=1.0, gain=3.0)
+    left_full = bg.copy()                                            # the left view with its margins, object pasted in
+    ya, yb, xa, xb = max(y0, 0), min(y1, H), max(x0 + margin, 0), min(x1 + margin, W + 2 * margin)
+    if yb > ya and xb > xa:
+        left_full[ya:yb, xa:xb] = obj[ya - y0:yb - y0, xa - x0 - margin:xb - x0 - margin]
+    left = left_full[:, margin:margin + W]
+    # right view: pixel x shows the left view's x + d.  Background: x_l = x_r + a + s x_l  =>  x_l = (x_r + a) / (1 - s);
+    # the rectangle sits 40 px to the left of its left-view position and hides the background there
+    a, s = 4.0 + 2.0 * (scene_seed % 3), 16.0 / max(W - 1, 1)
+    xr = np.arange(W, dtype=np.float64)
+    r = np.arange(H)[:, None]
+
+    def sample(img, src):
+        src = np.clip(src + margin, 0, W + 2 * margin - 1.001)
+        i0 = np.floor(src).astype(np.int64)
+        w = src - i0
+        return img[r, i0] * (1 - w) + img[r, i0 + 1] * w
+
+    right = sample(bg, np.broadcast_to((xr + a) / (1.0 - s), (H, W)))          # the background alone, also where the left view hides it
+    ox = xr + TEMPORAL_OBJECT_DISPARITY
+    in_obj = np.zeros((H, W), bool)
+    in_obj[max(y0, 0):min(y1, H)] = ((ox >= x0) & (ox < x1))[None, :]
+    right = np.where(in_obj, sample(left_full, np.broadcast_to(ox, (H, W))), right)
+    nrng = np.random.default_rng([888000 + scene_seed, t, noise_seed])
+    left = left + nrng.normal(0.0, sigma, left.shape)
+    right = right + nrng.normal(0.0, sigma, right.shape)
+    return np.clip(np.rint(left), 0, 255).astype(np.uint8), np.clip(np.rint(right), 0, 255).astype(np.uint8)
+
+
+def temporal_clip(W, H, n_frames, scene_seed=0, speed=6, sigma=3.0, cut_at=None, noise_seed=0):
+    """n_frames of one scene, or, with cut_at, of scene `scene_seed` up to frame cut_at - 1 and of scene `scene_seed + 1` from
+    frame cut_at on (the object keeps moving) -> (left u8 [n,H,W], right u8 [n,H,W], ground-truth disparity f32 [n,H,W])"""
+    L, R, G = [], [], []
+    for t in range(n_frames):
+        seed = scene_seed + (1 if cut_at is not None and t >= cut_at else 0)
+        l, r = temporal_gray_pair(W, H, t, seed, speed, sigma, noise_seed)
+        L.append(l)
+        R.append(r)
+        G.append(temporal_gt_disparity(W, H, t, seed, speed))
+    return np.stack(L), np.stack(R), np.stack(G)
+
+
+def temporal_sbs_clip(W, H, n_frames, **kw):
+    """the same clip as side-by-side BGR frames [n,H,W,3] u8 (each eye squeezed to W/2, gray in all three channels)"""
+    assert W % 2 == 0
+    L, R, _ = temporal_clip(W, H, n_frames, **kw)
+
+    def squeeze(a):
+        a = a.astype(np.uint16)
+        return ((a[..., 0::2] + a[..., 1::2] + 1) >> 1).astype(np.uint8)
+
+    sbs = np.concatenate([squeeze(L), squeeze(R)], axis=2)
+    return np.ascontiguousarray(np.repeat(sbs[..., None], 3, axis=3))

@@ -1,0 +1,141 @@
+"""Temporal stabilisation of the depth sequence (opt-in: `--temporal-radius R`, R in 1..8).
+
+Per frame the matcher's disparity jitters and the u16 normalisation takes the frame's own min and max, so static background
+moves in the 3D video.  With a radius this stage sits on the device between `sbs_to_disparity` and the u16 samples:
+
+  * scene cuts from the left gray (mean absolute luma difference above `cut_threshold` levels): frames on two sides of a cut
+    never mix;
+  * a cross-bilateral filter over the 2R+1 frames around a target: triangular weight in time, a weight that falls with the
+    3x3 luma difference to the target (so moving objects are left alone), invalid pixels skipped (and, with `fill`, filled);
+  * the u16 samples against the min / max of the whole window instead of the frame's own.
+
+All of it is integer arithmetic with a bit-exact contract (include/v3d_hip.h; tests/temporal_ref.py restates it).
+
+`TemporalStabilizer` is the streaming driver: a clip arrives in passes of any size, the output lags the input by R frames
+and the last 2R frames of depth and gray stay on the device between passes.  The result does not depend on how the clip is
+cut into passes.  Frames before the first pushed frame and after the last one do not exist for the window.
+"""
+
+MAX_RADIUS = 8
+DEFAULT_TAU = 12
+DEFAULT_CUT = 20
+
+
+def check_parameters(radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True):
+    """validated (radius, tau, cut_threshold, fill) as plain ints / bool; radius 0 means the stage is off"""
+    vals = {"temporal radius": (radius, 0, MAX_RADIUS), "temporal tau": (tau, 1, 255), "temporal cut threshold": (cut_threshold, 0, 256)}
+    for name, (v, lo, hi) in vals.items():
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    return int(radius), int(tau), int(cut_threshold), bool(fill)
+
+
+def cache_suffix(radius: int, tau: int, cut_threshold: int, fill: bool) -> str:
+    """what the depth cache key gains when the stage is on ('' when off: the reference's key unchanged)"""
+    return f"_temporal_r{radius}_t{tau}_c{cut_threshold}_f{int(bool(fill))}" if radius > 0 else ""
+
+
+def manifest_entry(radius: int, tau: int, cut_threshold: int, fill: bool) -> dict:
+    return {"radius": radius, "tau": tau, "cut_threshold": cut_threshold, "fill": bool(fill)}
+
+
+class TemporalStabilizer:
+    """push(depth [n,H,W], gray [n,H,W]) -> stabilised u16 samples of every frame whose window is complete (possibly none:
+    then None); finish() -> the tail, with windows clipped at the end of the clip.  The arrays are whatever the backend's
+    `sbs_to_disparity` / `left_gray` return (device tensors for the HIP backend); the driver touches them only through
+    `backend.temporal_concat` and `backend.temporal_stabilize`."""
+
+    def __init__(self, backend, radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True):
+        self.radius, self.tau, self.cut_threshold, self.fill = check_parameters(radius, tau, cut_threshold, fill)
+        if self.radius < 1:
+            raise ValueError("TemporalStabilizer needs a radius of at least 1 (radius 0 is the per-frame path)")
+        self.backend = backend
+        self._depth = self._gray = None      # frames first .. first+len-1 of the clip
+        self._first = 0
+        self._next = 0                       # the next target to emit
+        self._finished = False
+
+    def _emit(self, upto: int):
+        """targets self._next .. upto-1 out of the held buffer"""
+        n = upto - self._next
+        if n <= 0:
+            return None
+        out = self.backend.temporal_stabilize(self._depth, self._gray, self._next - self._first, n, self.radius, self.tau,
+                                              self.cut_threshold, self.fill)
+        self._next = upto
+        return out
+
+    def push(self, depth, gray):
+        if self._finished:
+            raise RuntimeError("push() after finish()")
+        if len(depth) != len(gray):
+            raise ValueError(f"{len(depth)} depth frames and {len(gray)} gray frames")
+        if len(depth) == 0:
+            return None
+        be = self.backend
+        self._depth = be.temporal_concat(self._depth, depth)
+        self._gray = be.temporal_concat(self._gray, gray)
+        end = self._first + len(self._depth)
+        out = self._emit(end - self.radius)
+        keep = min(2 * self.radius, len(self._depth))          # the next target is end - R at the earliest; it reaches back R more
+        self._first = end - keep
+        self._depth, self._gray = self._depth[len(self._depth) - keep:], self._gray[len(self._gray) - keep:]
+        return out
+
+    def finish(self):
+        if self._finished:
+            raise RuntimeError("finish() called twice")
+        self._finished = True
+        out = None if self._depth is None else self._emit(self._first + len(self._depth))
+        self._depth = self._gray = None
+        return out
+
+    def pending(self) -> int:
+        """frames pushed but not yet returned"""
+        return 0 if self._depth is None else self._first + len(self._depth) - self._next
+
+
+class BlockStabilizer:
+    """TemporalStabilizer for one rank's share of a clip (sharding.temporal_block): the rank pushes frames
+    first - halo_before .. first + count + halo_after - 1 in order and gets back (frame indices, u16 samples) of the frames
+    it owns; the halo frames only feed the windows."""
+
+    def __init__(self, backend, params, first: int, count: int, halo_before: int):
+        self.stab = TemporalStabilizer(backend, *params)
+        self.first, self.count = first, count
+        self._at = first - halo_before           # clip index of the next frame the stabiliser returns
+
+    def _owned(self, out):
+        if out is None:
+            return [], None
+        a, b = self._at, self._at + len(out)
+        self._at = b
+        lo, hi = max(a, self.first), min(b, self.first + self.count)
+        if hi <= lo:
+            return [], None
+        return list(range(lo, hi)), out[lo - a:hi - a]
+
+    def push(self, depth, gray):
+        return self._owned(self.stab.push(depth, gray))
+
+    def finish(self):
+        return self._owned(self.stab.finish())
+
+
+def add_temporal_arguments(parser):
+    """the CLI surface shared by the depth CLI and the one-pass pipeline"""
+    parser.add_argument('--temporal-radius', type=int, default=0,
+                        help=f'Temporal depth stabilisation over 2R+1 frames, R in 1..{MAX_RADIUS} (default 0: off, every frame on '
+                             'its own).  Frames before --start-frame and after the last processed frame do not exist for the window')
+    parser.add_argument('--temporal-tau', type=int, default=DEFAULT_TAU,
+                        help=f'Luma difference (levels, 3x3 mean) at which a neighbouring frame stops contributing (default {DEFAULT_TAU})')
+    parser.add_argument('--temporal-cut', type=int, default=DEFAULT_CUT,
+                        help=f'Mean absolute luma difference (levels) between frames that counts as a scene cut (default {DEFAULT_CUT})')
+    parser.add_argument('--no-temporal-fill', action='store_true',
+                        help='Leave pixels that are invalid in a frame invalid instead of filling them from its neighbours')
+
+
+def temporal_options(args) -> dict:
+    """parsed arguments -> the constructors' keyword arguments"""
+    return dict(temporal_radius=args.temporal_radius, temporal_tau=args.temporal_tau, temporal_cut=args.temporal_cut,
+                temporal_fill=not args.no_temporal_fill)

@@ -24,9 +24,11 @@ GUIDED_RADIUS = 8       # at 4K; the reference specifies nothing (SURVEY.md Appe
 GUIDED_EPS = 1e-3       # on [0,1]-scaled guide
 
 
-def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, radius: int, eps: float):
+def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, radius: int, eps: float,
+                   extra: dict = None):
     """the last step of a 4K depth run, on one process: frames_dir/depth4k_%06d.png -> H.264 at output_path when an ffmpeg
-    binary exists and the output is an .mp4, else a JSON manifest of the PNG sequence at output_path"""
+    binary exists and the output is an .mp4, else a JSON manifest of the PNG sequence at output_path (`extra`: further
+    entries of the manifest, e.g. the temporal stabilisation parameters of the run)"""
     ffmpeg = shutil.which("ffmpeg")
     if ffmpeg and str(output_path).endswith(".mp4"):
         cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / "depth4k_%06d.png"),
@@ -40,7 +42,7 @@ def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height
         Path(output_path).write_text(json.dumps({
             "format": "png16-sequence", "frames_dir": str(frames_dir), "pattern": "depth4k_%06d.png",
             "count": count, "width": width, "height": height, "fps": fps,
-            "guided_radius": radius, "guided_eps": eps,
+            "guided_radius": radius, "guided_eps": eps, **(extra or {}),
             "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"}, indent=1))
 
 
