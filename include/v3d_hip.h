@@ -25,6 +25,7 @@
  *                          to a side-by-side 3D frame (convert.py, the declared video-3d-convert step)
  *   v3d_temporal_*, v3d_depth_minmax_batch, v3d_depth_to_u16_range_batch  no call site in the reference (it normalises every
  *                          frame on its own, depth.py:397-406): opt-in temporal stabilisation of the depth sequence
+ *   v3d_depth_robust_minmax_batch  no call site in the reference either: opt-in percentile white point of that normalisation
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -274,6 +275,22 @@ int v3d_temporal_filter_batch(const float* depth, size_t depth_stride /* element
    own min and max it reproduces v3d_depth_to_u16_batch bit for bit.  out dense [n][frame_elems]; n <= 65535 */
 int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride /* elements */,
                                  const float* lohi, uint16_t* out, void* stream);
+
+/* Robust depth range (v3d_range.hip): v3d_depth_minmax_batch with the max replaced by a percentile of the frame's valid
+   disparities, so a handful of mismatched pixels cannot set the white point.  Bit-exact contract, integers up to the last
+   conversion: tests/range_ref.py.  q = percentile in parts per 10000, in [5000, 10000]; per frame, with d16 as above:
+     hist[b] = #{p: d16(p) == b} for 1 <= b <= 2046, hist[2047] = #{p: d16(p) >= 2047}; n_valid = sum hist;
+     k = max(1, ceil(q * n_valid / 10000)) (64-bit); hi16 = the smallest b with hist[1] + .. + hist[b] >= k;
+     mn, mx = the frame's float min and max exactly as v3d_depth_minmax_batch gives them (the min includes the invalid zeros);
+     hi = mx if n_valid == 0 or hi16 == 2047, else max((float)hi16 / 16, mn).
+   minmax_out f32 [T][2] = (mn, hi): the layout v3d_temporal_range and v3d_depth_to_u16_range_batch read.  At most
+   n_valid - k valid pixels of a frame lie above its hi; on depths that are multiples of 1/16 below 2047/16, q = 10000 gives mx.
+   ws: device scratch of v3d_depth_robust_minmax_ws_bytes(T) bytes, 16-byte aligned.  Enqueues three launches on `stream`,
+   never synchronises, never allocates.  V3D_ERR_ARG: null pointer, T outside [1, 65535], frame_elems < 1, q outside
+   [5000, 10000], a stride below the frame size (T > 1), a misaligned ws; V3D_ERR_UNSUPPORTED: frame_elems >= 2^32. */
+size_t v3d_depth_robust_minmax_ws_bytes(int T);
+int v3d_depth_robust_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride /* elements */, int q,
+                                  void* ws, float* minmax_out, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

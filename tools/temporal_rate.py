@@ -4,7 +4,11 @@ normalisation) from HIP events (warm-up, 20 timed launches), the filter's share 
 device step of the one-pass pipeline (sbs_to_disparity + u16 samples) with the stage on and off, alternating in this one
 process.  Prints one JSON line.
 
-    python tools/temporal_rate.py [--kernel-only] [--radius 2 4]
+--range-percentile P adds the robust range (v3d_depth_robust_minmax_batch) against v3d_depth_minmax_batch on the same 34-frame
+buffers (the synthetic clip, the matcher's output on the synthetic SBS frames, a constant frame: the worst case for same-address
+LDS atomics), alternating, and the stage at R = 2 and the radius-0 u16 step with and without the option.
+
+    python tools/temporal_rate.py [--kernel-only] [--radius 2 4] [--range-percentile 98]
 """
 import argparse
 import json
@@ -17,6 +21,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-3d-pipeline_amd")]
 from video_3d_pipeline import _native as N  # noqa: E402
+import envopts  # noqa: E402
+
+envopts.select_variant_lib(N)               # V3D_HIP_LIB=path: an experiment build of the library (development only)
 
 W, H, NF, REPS, HBM = 1920, 1080, 34, 20, 8.0e12
 
@@ -102,13 +109,53 @@ def pipeline_step(R=2, rounds=5):
             "off_median": round(float(np.median(t_off)), 1), "on_median": round(float(np.median(t_on)), 1)}
 
 
+def range_rates(percentile, R=2, rounds=3, entry_only=False):
+    """us per 34-frame call, max entry / robust entry alternating; floor: one 4 B/px read of the buffer at 8 TB/s"""
+    from video_3d_pipeline import synthetic as syn
+    from video_3d_pipeline.pipeline import HipPipelineBackend
+    from video_3d_pipeline.temporal import check_range_percentile
+    q = check_range_percentile(percentile)
+    be = HipPipelineBackend()
+    depth, gray = clip(NF + 2 * R, 1)
+    matched = be.sbs_to_disparity([syn.sbs_frame(W, H, i % 4) for i in range(NF)], True).clone()
+    bufs = {"synthetic_clip": depth[:NF], "matcher_output": matched, "constant_frame": torch.full_like(matched, 7.25)}
+    floor_us = NF * W * H * 4 / HBM * 1e6
+    res = {"q": q, "floor_us_one_read_at_8TBps": round(floor_us, 1), "entry_us_per_call": {}}
+    for name, buf in bufs.items():
+        mx, rb = [], []
+        for _ in range(rounds):
+            mx.append(timed(lambda: N.depth_minmax_batch(buf)))
+            rb.append(timed(lambda: N.depth_robust_minmax_batch(buf, q)))
+        res["entry_us_per_call"][name] = {"minmax": [round(t, 1) for t in mx], "robust": [round(t, 1) for t in rb],
+                                          "minmax_median": round(float(np.median(mx)), 1), "robust_median": round(float(np.median(rb)), 1),
+                                          "robust_times_floor": round(float(np.median(rb)) / floor_us, 2),
+                                          "minmax_times_floor": round(float(np.median(mx)) / floor_us, 2)}
+    if entry_only:
+        return res
+    off, on, off0, on0 = [], [], [], []
+    for _ in range(rounds):
+        off.append(timed(lambda: be.temporal_stabilize(depth, gray, R, NF, R, 12, 20, True)) / NF)
+        on.append(timed(lambda: be.temporal_stabilize(depth, gray, R, NF, R, 12, 20, True, q)) / NF)
+        off0.append(timed(lambda: be.depth_to_u16_batch(matched)) / NF)
+        on0.append(timed(lambda: be.depth_to_u16_robust(matched, q)) / NF)
+    res["stage_R2_us_per_frame"] = {"max": round(float(np.median(off)), 2), "robust": round(float(np.median(on)), 2)}
+    res["u16_step_R0_us_per_frame"] = {"max": round(float(np.median(off0)), 2), "robust": round(float(np.median(on0)), 2)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--radius", type=int, nargs="+", default=[2, 4])
     ap.add_argument("--kernel-only", action="store_true", help="skip the pipeline step (profiler runs)")
+    ap.add_argument("--range-percentile", type=float, default=None, help="also time the robust range at this percentile")
+    ap.add_argument("--range-only", action="store_true", help="with --range-percentile: only the two min/max entries (profiler, A/B runs)")
     a = ap.parse_args()
-    res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "frames_per_pass": NF, "stage": stage_rates(a.radius)}
-    if not a.kernel_only:
+    res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "frames_per_pass": NF}
+    if a.range_percentile is not None:
+        res["robust_range"] = range_rates(a.range_percentile, entry_only=a.range_only)
+    if not a.range_only:
+        res["stage"] = stage_rates(a.radius)
+    if not a.kernel_only and not a.range_only:
         res["pipeline_step"] = pipeline_step()
     print(json.dumps(res))
 

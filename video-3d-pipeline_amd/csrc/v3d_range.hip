@@ -1,0 +1,162 @@
+// v3d_range.hip -- robust depth range for the u16 normalisation ("Robust range"; contract in
+// include/v3d_hip.h, NumPy restatement in tests/range_ref.py).  Per frame, one read of the depth gives the float min and max
+// (as v3d_depth_minmax_batch reduces them) and a histogram of the fixed-point disparities d16 = rint(16 D), valid iff >= 1:
+//   hist[b] = #{d16 == b} for 1 <= b <= 2046, hist[2047] = #{d16 >= 2047}, n_valid = sum hist
+//   k = max(1, ceil(q n_valid / 10000)), hi16 = the smallest b whose cumulative count reaches k
+//   hi = mx if n_valid == 0 or hi16 == 2047, else max(hi16 / 16, mn)                 -> (mn, hi) per frame
+// Every sum is an integer, so the order of the atomics cannot change a bit.  No entry synchronises or allocates.
+#include "v3d_common.h"
+
+#define RR_NB 2048
+#define RR_WAVES 4             // waves of a 256-lane workgroup
+
+__device__ __forceinline__ unsigned rr_f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float rr_ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+
+// the histogram bin of a depth: 0 = invalid (not counted), the last bin saturates; NaN compares false twice -> 0
+__device__ __forceinline__ int rr_bin(float d)
+{
+    const float v = rintf(__fmul_rn(d, 16.0f));
+    return v >= (float)(RR_NB - 1) ? RR_NB - 1 : v >= 1.f ? (int)v : 0;
+}
+
+__global__ void k_rr_init(unsigned* hist, unsigned* mm, int T)
+{
+    const size_t n = (size_t)T * RR_NB;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) hist[i] = 0u;
+    for (int f = blockIdx.x * 256 + threadIdx.x; f < T; f += gridDim.x * 256) { mm[2 * f] = 0xFFFFFFFFu; mm[2 * f + 1] = 0u; }
+}
+
+// A depth map is piecewise smooth, so the lanes of a wave, and the 4 pixels of a lane, mostly hit the same few bins: same-
+// address LDS atomics.  The remedy that won its A/B: a lane merges equal bins among its 4 pixels before it issues,
+// at most one atomic per distinct bin.  One sub-histogram per wave on top of it gained nothing and was removed.  Invalid
+// pixels (a fifth of a matcher's frame, one single value) issue nothing: they are not in the histogram, n_valid is its sum.
+__device__ __forceinline__ void rr_count4(unsigned* h, const float4 v)
+{
+    const int b0 = rr_bin(v.x), b1 = rr_bin(v.y), b2 = rr_bin(v.z), b3 = rr_bin(v.w);
+    if (b0) atomicAdd(h + b0, 1u + (b1 == b0) + (b2 == b0) + (b3 == b0));
+    if (b1 && b1 != b0) atomicAdd(h + b1, 1u + (b2 == b1) + (b3 == b1));
+    if (b2 && b2 != b0 && b2 != b1) atomicAdd(h + b2, 1u + (b3 == b2));
+    if (b3 && b3 != b0 && b3 != b1 && b3 != b2) atomicAdd(h + b3, 1u);
+}
+__device__ __forceinline__ void rr_minmax4(unsigned& lo, unsigned& hi, const float4 v)
+{
+    const unsigned a = rr_f2ord(v.x), b = rr_f2ord(v.y), c = rr_f2ord(v.z), d = rr_f2ord(v.w);
+    lo = min(min(lo, a), min(b, min(c, d)));
+    hi = max(max(hi, a), max(b, max(c, d)));
+}
+
+// grid (blocks, T).  VEC: the frame's base address and stride allow 16-byte loads, a lane owns 4 adjacent pixels and four loads
+// are in flight per step; the n & 3 last pixels, and everything in the other instantiation (unaligned views, odd strides), go
+// element by element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_rr_hist(const float* __restrict__ d, size_t n, size_t stride, unsigned* __restrict__ hist,
+                                                 unsigned* __restrict__ mm)
+{
+    __shared__ unsigned h[RR_NB];
+    d += blockIdx.y * stride; hist += (size_t)blockIdx.y * RR_NB; mm += 2 * blockIdx.y;
+    for (int i = threadIdx.x; i < RR_NB; i += 256) h[i] = 0u;
+    __syncthreads();
+    unsigned lo = 0xFFFFFFFFu, hi = 0u;
+    const size_t step = (size_t)gridDim.x * 256;
+    const size_t nvec = VEC ? n / 4 : 0;
+    if (VEC) {
+        const float4* d4 = reinterpret_cast<const float4*>(d);
+        size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+        for (; i + 3 * step < nvec; i += 4 * step) {                       // four 16-byte loads in flight per lane
+            const float4 a = d4[i], b = d4[i + step], c = d4[i + 2 * step], e = d4[i + 3 * step];
+            rr_minmax4(lo, hi, a); rr_minmax4(lo, hi, b); rr_minmax4(lo, hi, c); rr_minmax4(lo, hi, e);
+            rr_count4(h, a); rr_count4(h, b); rr_count4(h, c); rr_count4(h, e);
+        }
+        for (; i < nvec; i += step) {
+            const float4 a = d4[i];
+            rr_minmax4(lo, hi, a);
+            rr_count4(h, a);
+        }
+    }
+    for (size_t i = nvec * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
+        const float v = d[i];
+        const unsigned o = rr_f2ord(v);
+        lo = min(lo, o); hi = max(hi, o);
+        const int b = rr_bin(v);
+        if (b) atomicAdd(h + b, 1u);
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
+    if ((threadIdx.x & 63) == 0) { atomicMin(mm, lo); atomicMax(mm + 1, hi); }
+    __syncthreads();
+    for (int b = threadIdx.x; b < RR_NB; b += 256) {
+        const unsigned c = h[b];
+        if (c) atomicAdd(hist + b, c);
+    }
+}
+
+// one workgroup per frame: a lane owns 8 adjacent bins, block scan of the lanes' sums, the lane whose run crosses k walks its 8
+__global__ __launch_bounds__(256) void k_rr_select(const unsigned* __restrict__ hist, const unsigned* __restrict__ mm, int q,
+                                                   float* __restrict__ out)
+{
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint4* h4 = reinterpret_cast<const uint4*>(hist + (size_t)t * RR_NB) + 2 * tid;
+    const uint4 a = h4[0], b = h4[1];
+    const unsigned c[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+    const unsigned own = a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w;
+    unsigned inc = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = (unsigned)__shfl_up((int)inc, o);
+        if (lane >= o) inc += v;
+    }
+    __shared__ unsigned part[RR_WAVES];
+    if (lane == 63) part[wave] = inc;
+    __syncthreads();
+    unsigned before = inc - own, n_valid = 0;
+#pragma unroll
+    for (int w = 0; w < RR_WAVES; w++) { before += w < wave ? part[w] : 0u; n_valid += part[w]; }
+    const float mn = rr_ord2f(mm[2 * t]), mx = rr_ord2f(mm[2 * t + 1]);
+    if (tid == 0) { out[2 * t] = mn; if (n_valid == 0) out[2 * t + 1] = mx; }
+    if (n_valid == 0) return;
+    const unsigned long long kq = ((unsigned long long)q * n_valid + 9999ull) / 10000ull;
+    const unsigned k = kq < 1ull ? 1u : (unsigned)kq;                      // q <= 10000: k <= n_valid
+    if (before < k && k <= before + own) {                                 // exactly one lane
+        unsigned run = before;
+        int hi16 = -1;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            run += c[j];
+            if (hi16 < 0 && run >= k) hi16 = 8 * tid + j;
+        }
+        const float v = (float)hi16 * 0.0625f;
+        out[2 * t + 1] = hi16 == RR_NB - 1 ? mx : (v > mn ? v : mn);
+    }
+}
+
+extern "C" size_t v3d_depth_robust_minmax_ws_bytes(int T)
+{
+    return T < 1 ? 0 : (size_t)T * (RR_NB + 2) * sizeof(unsigned);
+}
+
+extern "C" int v3d_depth_robust_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride, int q, void* ws,
+                                             float* minmax_out, void* stream)
+{
+    if (!depth || !ws || !minmax_out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
+    if (T < 1 || T > 65535 || frame_elems < 1) { v3d_set_error("bad batch %d x %zu", T, frame_elems); return V3D_ERR_ARG; }
+    if (q < 5000 || q > 10000) { v3d_set_error("range quantile %d outside [5000, 10000]", q); return V3D_ERR_ARG; }
+    if (T > 1 && frame_stride < frame_elems) { v3d_set_error("frame stride %zu below the frame size %zu", frame_stride, frame_elems); return V3D_ERR_ARG; }
+    if (((uintptr_t)ws & 15) != 0) { v3d_set_error("workspace must be 16-byte aligned"); return V3D_ERR_ARG; }
+    if (frame_elems > 0xFFFFFFFFull) { v3d_set_error("frame of %zu elements: the bins are 32-bit counters", frame_elems); return V3D_ERR_UNSUPPORTED; }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* hist = reinterpret_cast<unsigned*>(ws);
+    unsigned* mm = hist + (size_t)T * RR_NB;
+    const bool vec = ((uintptr_t)depth & 15) == 0 && (T == 1 || (frame_stride & 3) == 0);
+    // one step of a block covers 4096 px.  All workgroups of a 34-frame pass are resident at once (4 per CU): a grid a little
+    // larger than the chip holds runs a second, nearly empty round that costs as much as the first
+    const size_t want = (frame_elems + 4095) / 4096;
+    const size_t per = (size_t)(1024 / T > 8 ? 1024 / T : 8);
+    const int bx = (int)(want < per ? want : per);
+    hipLaunchKernelGGL(k_rr_init, dim3(T < 128 ? 8 * T : 1024), dim3(256), 0, st, hist, mm, T);
+    if (vec) hipLaunchKernelGGL(k_rr_hist<true>, dim3(bx, T), dim3(256), 0, st, depth, frame_elems, frame_stride, hist, mm);
+    else hipLaunchKernelGGL(k_rr_hist<false>, dim3(bx, T), dim3(256), 0, st, depth, frame_elems, frame_stride, hist, mm);
+    hipLaunchKernelGGL(k_rr_select, dim3(T), dim3(256), 0, st, hist, mm, q, minmax_out);
+    V3D_LAUNCH_CHECK();
+    return V3D_OK;
+}

@@ -30,6 +30,7 @@ EXPORTS = (
     "v3d_render_stereo_batch",
     "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
     "v3d_depth_to_u16_range_batch",
+    "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -134,6 +135,9 @@ def lib():
         L.v3d_temporal_range.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
         L.v3d_temporal_filter_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
         L.v3d_depth_to_u16_range_batch.argtypes = [vp, ci, sz, sz, vp, vp, vp]
+        L.v3d_depth_robust_minmax_ws_bytes.argtypes = [ci]
+        L.v3d_depth_robust_minmax_ws_bytes.restype = sz
+        L.v3d_depth_robust_minmax_batch.argtypes = [vp, ci, sz, sz, ci, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -642,6 +646,25 @@ def depth_minmax_batch(depth):
     out = torch.empty((T, 2), dtype=torch.float32, device=depth.device)
     with torch.cuda.device(depth.device):
         _check(lib().v3d_depth_minmax_batch(d, T, H * W, ds, _dev(out, torch.float32, "minmax"), _stream()), "v3d_depth_minmax_batch")
+    return out
+
+
+RANGE_Q_MIN, RANGE_Q_OFF = 5000, 10000
+
+
+def depth_robust_minmax_batch(depth, q):
+    """float32 [T,H,W] -> float32 [T,2] on the device: each frame's min and its robust white point, the q/10000 quantile of the
+    valid fixed-point disparities (v3d_depth_robust_minmax_batch; contract: tests/range_ref.py).  The histogram workspace is
+    a torch allocation from the caching allocator: nothing is allocated in the steady state."""
+    if isinstance(q, bool) or int(q) != q or not RANGE_Q_MIN <= q <= RANGE_Q_OFF:
+        raise ValueError(f"range quantile must be an integer in [{RANGE_Q_MIN}, {RANGE_Q_OFF}], got {q!r}")
+    d, ds = _clip(depth, torch.float32, "depth")
+    T, H, W = depth.shape
+    ws = torch.empty(lib().v3d_depth_robust_minmax_ws_bytes(T), dtype=torch.uint8, device=depth.device)
+    out = torch.empty((T, 2), dtype=torch.float32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        _check(lib().v3d_depth_robust_minmax_batch(d, T, H * W, ds, int(q), _dev(ws, torch.uint8, "ws"),
+                                                   _dev(out, torch.float32, "minmax"), _stream()), "v3d_depth_robust_minmax_batch")
     return out
 
 

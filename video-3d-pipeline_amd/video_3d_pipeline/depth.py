@@ -202,15 +202,23 @@ class HipStereoBackend:
         """frames carried from earlier passes (or None) + the frames of this pass -> one private device buffer"""
         return new.clone() if held is None else self.torch.cat([held, new])
 
-    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill):
+    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill, range_quantile=10000):
         """buffer of T frames (device depth f32 and left gray u8 [T,H,W]) -> device u16 samples (int16-viewed) [n,H,W] of
         targets t0 .. t0+n-1: cuts, per-frame min/max, clip-stable range, filter, normalisation -- nine launches on the
-        current stream, nothing comes back to the host"""
+        current stream, nothing comes back to the host.  range_quantile < 10000: the per-frame max is the robust white point
+        (three launches in place of the min/max's three)"""
         nat = self.native
         cut = nat.temporal_cuts(gray, cut_threshold)
-        lohi = nat.temporal_range(nat.depth_minmax_batch(depth), cut, radius, t0, n)
+        mm = nat.depth_robust_minmax_batch(depth, range_quantile) if range_quantile < 10000 else nat.depth_minmax_batch(depth)
+        lohi = nat.temporal_range(mm, cut, radius, t0, n)
         filt = nat.temporal_filter_batch(depth, gray, radius, tau, cut, fill, t0, n)
         return nat.depth_to_u16_range_batch(filt, lohi)
+
+    def depth_to_u16_robust(self, depth, range_quantile):
+        """--range-percentile without a radius: device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W], every
+        frame against its own (min, robust white point)"""
+        nat = self.native
+        return nat.depth_to_u16_range_batch(depth, nat.depth_robust_minmax_batch(depth, range_quantile))
 
     def to_host_u16(self, u16):
         """device u16 [n,H,W] -> NumPy uint16 [n,H,W] through pinned memory.  The pinned block comes from torch's caching host
@@ -244,13 +252,17 @@ class HybridStereoDepthExtractor:
                  temporal_radius: int = 0,
                  temporal_tau: int = 12,
                  temporal_cut: int = 20,
-                 temporal_fill: bool = True):
+                 temporal_fill: bool = True,
+                 range_percentile: float = 100.0):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
-        on its own, the reference's behaviour.  process_frame_batch / save_depth_map stay per-frame: a list of pairs is not a clip """
-        from .temporal import check_parameters
+        on its own, the reference's behaviour.  process_frame_batch / save_depth_map stay per-frame: a list of pairs is not a clip.
+        range_percentile < 100 (process_video_sbs only): the white point of the 16-bit normalisation is that percentile of the
+        valid disparities instead of the maximum; 100 = the reference's min-max """
+        from .temporal import check_parameters, check_range_percentile
         self.temporal = check_parameters(temporal_radius, temporal_tau, temporal_cut, temporal_fill)
+        self.range_quantile = check_range_percentile(range_percentile)
 
         self.device = device
         self.work_dir = create_work_directory(work_dir)
@@ -334,11 +346,11 @@ class HybridStereoDepthExtractor:
         return None
 
     def get_cache_path(self, video_path: str, frame_start: int, frame_count: int) -> Path:
-        """ Generate cache path for depth maps (key format identical to depth.py:119-120; with temporal stabilisation on, the
-        key also carries its four parameters, so stabilised and per-frame maps never share a directory) """
+        """ Generate cache path for depth maps (key format identical to depth.py:119-120; with temporal stabilisation or the
+        robust range on, the key also carries their parameters, so such maps and the reference's never share a directory) """
         from .temporal import cache_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
-        cache_key += cache_suffix(*self.temporal)
+        cache_key += cache_suffix(*self.temporal, self.range_quantile)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -460,6 +472,7 @@ class HybridStereoDepthExtractor:
         pass_frames = sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
         self.last_pass_frames = pass_frames
         provider = self._guidance_provider()
+        robust = self.range_quantile < 10000                 # --range-percentile: the batch's u16 samples come from the device
         # PNG compression (zlib) costs ~20 ms per 1080p map on one core, the GPU path 0.5 ms: the maps of a batch go to
         # a bounded pool of writer threads and compress while the next batch is decoded and computed
         writers = self.writer_pool_factory()
@@ -472,8 +485,9 @@ class HybridStereoDepthExtractor:
                 depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs, provider)
             else:
                 depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs)
+            u16 = self.backend.to_host_u16(self.backend.depth_to_u16_robust(depth, self.range_quantile)) if robust else None
             for j, frame_idx in enumerate(batch_idx):
-                writers.submit(cache_path / f"depth_{frame_idx:06d}.png", self.backend.normalise_u16(depth[j]))
+                writers.submit(cache_path / f"depth_{frame_idx:06d}.png", u16[j] if robust else self.backend.normalise_u16(depth[j]))
                 processed_count += 1
             print(f"✓ Queued batch depth maps ({processed_count} on rank {rank})")
             batch.clear()
@@ -493,6 +507,10 @@ class HybridStereoDepthExtractor:
         self.last_decoded_frames = decoded
         if sharding.total(decoded) == 0:
             raise ValueError("No frames extracted from video")
+        if robust and rank == 0:
+            import json
+            from .temporal import manifest_entry
+            (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal, self.range_quantile)))
         sharding.barrier()
 
         print(f"✓ Depth extraction complete: {cache_path}")
@@ -516,7 +534,7 @@ class HybridStereoDepthExtractor:
         pass_frames = sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
         self.last_pass_frames = pass_frames
         provider = self._guidance_provider()
-        stab = BlockStabilizer(be, self.temporal, first, count, hb)
+        stab = BlockStabilizer(be, self.temporal, first, count, hb, self.range_quantile)
         writers = self.writer_pool_factory()
         processed_count = 0
         batch = []
@@ -555,7 +573,7 @@ class HybridStereoDepthExtractor:
         if sharding.total(processed_count) == 0:
             raise ValueError("No frames extracted from video")
         if rank == 0:
-            (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal)))
+            (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal, self.range_quantile)))
         sharding.barrier()
 
         print(f"✓ Depth extraction complete: {cache_path}")
@@ -582,8 +600,9 @@ def main(argv=None):
     parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
     parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
-    from .temporal import add_temporal_arguments, temporal_options
+    from .temporal import add_range_arguments, add_temporal_arguments, range_options, temporal_options
     add_temporal_arguments(parser)
+    add_range_arguments(parser)
     args = parser.parse_args(argv)
 
     stereo_only = args.stereo_only or args.no_neural
@@ -596,7 +615,7 @@ def main(argv=None):
         extractor = HybridStereoDepthExtractor(
             model_checkpoint=args.model, work_dir=args.work_dir, cache_dir=args.work_dir, device=args.device,
             batch_size=args.batch_size, use_neural_guidance=use_neural_guidance, stereo_only=stereo_only,
-            unsqueeze_sbs=unsqueeze_sbs, **temporal_options(args))
+            unsqueeze_sbs=unsqueeze_sbs, **temporal_options(args), **range_options(args))
         output_path = extractor.process_video_sbs(video_path=args.video, start_frame=args.start_frame,
                                                   max_frames=args.max_frames, force_reprocess=args.force)
         print(f"\n✓ Success! Depth maps saved to: {output_path}")

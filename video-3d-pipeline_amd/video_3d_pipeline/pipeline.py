@@ -8,6 +8,7 @@ and through zlib twice before the 4K filter sees it.  Here the depth stays on th
     SBS frames -> HipStereoBackend.sbs_to_disparity (the depth CLI's own pass, neural guidance included)
                -> v3d_depth_to_u16_batch (per-frame min-max -> u16, the depth PNG's samples)
                   [--temporal-radius R: the temporal stabiliser's u16 samples instead (temporal.py), R frames behind the matcher]
+                  [--range-percentile P: the white point of either is the P-th percentile of the valid disparities, not the maximum]
                -> [--keep-depth-maps: depth_%06d.png into the depth CLI's cache directory]
                -> v3d_guided_upscale_u16_batch against the matching 4K frames' luma -> u16 4K samples -> writer pool
 
@@ -100,9 +101,11 @@ class SbsTo4kDepthPipeline:
                  temporal_radius: int = 0,
                  temporal_tau: int = 12,
                  temporal_cut: int = 20,
-                 temporal_fill: bool = True):
+                 temporal_fill: bool = True,
+                 range_percentile: float = 100.0):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
-        temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own)"""
+        temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own);
+        range_percentile: the depth CLI's robust white point (100 = off: the maximum)"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -113,7 +116,7 @@ class SbsTo4kDepthPipeline:
             model_checkpoint=model_checkpoint, work_dir=work_dir, cache_dir=work_dir, device=device, batch_size=batch_size,
             use_neural_guidance=use_neural_guidance, stereo_only=stereo_only, unsqueeze_sbs=unsqueeze_sbs, backend=backend,
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
-            temporal_fill=temporal_fill)
+            temporal_fill=temporal_fill, range_percentile=range_percentile)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
 
@@ -169,12 +172,13 @@ class SbsTo4kDepthPipeline:
         # frame i -> rank i mod world; each rank decodes only its own frames of BOTH clips (4K frame g0 + i guides SBS frame i)
         g0 = max(int(guide_start_frame), 0)
         stab = None
+        robust = ex.range_quantile < 10000
         if ex.temporal[0] > 0:
             # temporal stabilisation: a contiguous block per rank plus a halo of `radius` SBS frames on each side that is
             # decoded and matched but not written; the 4K guides are the block's own frames only
-            from .temporal import BlockStabilizer, manifest_entry
+            from .temporal import BlockStabilizer
             first, count, hb, ha = sharding.temporal_block(frame_count, rank, world, ex.temporal[0])
-            stab = BlockStabilizer(be, ex.temporal, first, count, hb)
+            stab = BlockStabilizer(be, ex.temporal, first, count, hb, ex.range_quantile)
             guides = iter_frames(video_4k, g0 + first, count) if count else iter(())
             sbs_frames = iter_frames(sbs_video, start_frame + first - hb, hb + count + ha) if count else iter(())
         else:
@@ -203,7 +207,9 @@ class SbsTo4kDepthPipeline:
                 depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, provider)
             else:
                 depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs)
-            if stab is None:
+            if stab is None and robust:
+                emit(writers, list(batch_idx), be.depth_to_u16_robust(depth, ex.range_quantile))
+            elif stab is None:
                 emit(writers, list(batch_idx), be.depth_to_u16_batch(depth))
             else:
                 emit(writers, *stab.push(depth, be.left_gray(len(batch))))
@@ -255,11 +261,12 @@ class SbsTo4kDepthPipeline:
         n_stereo = sharding.total(stereo["count"]) if stereo is not None else 0
         sharding.barrier()
         if rank == 0:
-            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps,
-                           {"temporal": manifest_entry(*ex.temporal)} if stab is not None else None)
-            if stab is not None and keep_depth_maps:
+            from .temporal import manifest_entry
+            entry = manifest_entry(*ex.temporal, ex.range_quantile) if stab is not None or robust else None
+            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, {"temporal": entry} if entry else None)
+            if entry and keep_depth_maps:
                 import json
-                (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*ex.temporal)))
+                (cache_path / "temporal.json").write_text(json.dumps(entry))
             if stereo is not None and n_stereo:
                 from .convert import finish_stereo_output, write_clip_info
                 write_clip_info(stereo["dir"], fps)
@@ -299,9 +306,10 @@ def main(argv=None):
     parser.add_argument('--stereo-output', default=None,
                         help='Also render side-by-side 3D to this path (what the convert CLI makes from the depth output)')
     from .convert import add_stereo_arguments, stereo_options
-    from .temporal import add_temporal_arguments, temporal_options
+    from .temporal import add_range_arguments, add_temporal_arguments, range_options, temporal_options
     add_stereo_arguments(parser)
     add_temporal_arguments(parser)
+    add_range_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -317,7 +325,7 @@ def main(argv=None):
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
         pipe = SbsTo4kDepthPipeline(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device,
                                     batch_size=args.batch_size, use_neural_guidance=not stereo_only, stereo_only=stereo_only,
-                                    unsqueeze_sbs=not args.no_unsqueeze, **temporal_options(args))
+                                    unsqueeze_sbs=not args.no_unsqueeze, **temporal_options(args), **range_options(args))
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,

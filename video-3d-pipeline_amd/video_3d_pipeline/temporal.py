@@ -11,6 +11,10 @@ moves in the 3D video.  With a radius this stage sits on the device between `sbs
 
 All of it is integer arithmetic with a bit-exact contract (include/v3d_hip.h; tests/temporal_ref.py restates it).
 
+`--range-percentile P` (opt-in, with or without a radius) makes the white point of that normalisation robust: a frame's "max"
+becomes the P-th percentile of its valid disparities, so a few mismatched pixels no longer set the scale of every sample
+(contract: include/v3d_hip.h, tests/range_ref.py).  Everything after the per-frame (min, max) is unchanged.
+
 `TemporalStabilizer` is the streaming driver: a clip arrives in passes of any size, the output lags the input by R frames
 and the last 2R frames of depth and gray stay on the device between passes.  The result does not depend on how the clip is
 cut into passes.  Frames before the first pushed frame and after the last one do not exist for the window.
@@ -19,6 +23,7 @@ cut into passes.  Frames before the first pushed frame and after the last one do
 MAX_RADIUS = 8
 DEFAULT_TAU = 12
 DEFAULT_CUT = 20
+RANGE_Q_MIN, RANGE_Q_OFF = 5000, 10000      # the range percentile in parts per 10000; 10000 = the maximum = off
 
 
 def check_parameters(radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True):
@@ -30,13 +35,29 @@ def check_parameters(radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = D
     return int(radius), int(tau), int(cut_threshold), bool(fill)
 
 
-def cache_suffix(radius: int, tau: int, cut_threshold: int, fill: bool) -> str:
-    """what the depth cache key gains when the stage is on ('' when off: the reference's key unchanged)"""
-    return f"_temporal_r{radius}_t{tau}_c{cut_threshold}_f{int(bool(fill))}" if radius > 0 else ""
+def check_range_percentile(percentile) -> int:
+    """--range-percentile P, a number in [50, 100] with at most two decimals -> q = P in parts per 10000; 100 means off"""
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, float)):
+        raise ValueError(f"range percentile must be a number in [50, 100], got {percentile!r}")
+    if not 50 <= percentile <= 100:                          # NaN fails both comparisons
+        raise ValueError(f"range percentile must lie in [50, 100], got {percentile!r}")
+    q = round(percentile * 100)
+    if abs(percentile * 100 - q) > 1e-6:
+        raise ValueError(f"range percentile may have at most two decimals, got {percentile!r}")
+    return int(q)
 
 
-def manifest_entry(radius: int, tau: int, cut_threshold: int, fill: bool) -> dict:
-    return {"radius": radius, "tau": tau, "cut_threshold": cut_threshold, "fill": bool(fill)}
+def cache_suffix(radius: int, tau: int, cut_threshold: int, fill: bool, range_quantile: int = RANGE_Q_OFF) -> str:
+    """what the depth cache key gains when the stage or the robust range is on ('' when off: the reference's key unchanged)"""
+    s = f"_temporal_r{radius}_t{tau}_c{cut_threshold}_f{int(bool(fill))}" if radius > 0 else ""
+    return s + (f"_rangeq{range_quantile}" if range_quantile < RANGE_Q_OFF else "")
+
+
+def manifest_entry(radius: int, tau: int, cut_threshold: int, fill: bool, range_quantile: int = RANGE_Q_OFF) -> dict:
+    entry = {"radius": radius, "tau": tau, "cut_threshold": cut_threshold, "fill": bool(fill)}
+    if range_quantile < RANGE_Q_OFF:
+        entry["range_quantile"] = range_quantile
+    return entry
 
 
 class TemporalStabilizer:
@@ -45,8 +66,12 @@ class TemporalStabilizer:
     `sbs_to_disparity` / `left_gray` return (device tensors for the HIP backend); the driver touches them only through
     `backend.temporal_concat` and `backend.temporal_stabilize`."""
 
-    def __init__(self, backend, radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True):
+    def __init__(self, backend, radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True,
+                 range_quantile: int = RANGE_Q_OFF):
         self.radius, self.tau, self.cut_threshold, self.fill = check_parameters(radius, tau, cut_threshold, fill)
+        if isinstance(range_quantile, bool) or int(range_quantile) != range_quantile or not RANGE_Q_MIN <= range_quantile <= RANGE_Q_OFF:
+            raise ValueError(f"range quantile must be an integer in [{RANGE_Q_MIN}, {RANGE_Q_OFF}], got {range_quantile!r}")
+        self.range_quantile = int(range_quantile)
         if self.radius < 1:
             raise ValueError("TemporalStabilizer needs a radius of at least 1 (radius 0 is the per-frame path)")
         self.backend = backend
@@ -60,8 +85,10 @@ class TemporalStabilizer:
         n = upto - self._next
         if n <= 0:
             return None
-        out = self.backend.temporal_stabilize(self._depth, self._gray, self._next - self._first, n, self.radius, self.tau,
-                                              self.cut_threshold, self.fill)
+        args = (self._depth, self._gray, self._next - self._first, n, self.radius, self.tau, self.cut_threshold, self.fill)
+        if self.range_quantile < RANGE_Q_OFF:                # off: the call a backend without the robust range knows
+            args += (self.range_quantile,)
+        out = self.backend.temporal_stabilize(*args)
         self._next = upto
         return out
 
@@ -100,8 +127,8 @@ class BlockStabilizer:
     first - halo_before .. first + count + halo_after - 1 in order and gets back (frame indices, u16 samples) of the frames
     it owns; the halo frames only feed the windows."""
 
-    def __init__(self, backend, params, first: int, count: int, halo_before: int):
-        self.stab = TemporalStabilizer(backend, *params)
+    def __init__(self, backend, params, first: int, count: int, halo_before: int, range_quantile: int = RANGE_Q_OFF):
+        self.stab = TemporalStabilizer(backend, *params, range_quantile)
         self.first, self.count = first, count
         self._at = first - halo_before           # clip index of the next frame the stabiliser returns
 
@@ -133,6 +160,18 @@ def add_temporal_arguments(parser):
                         help=f'Mean absolute luma difference (levels) between frames that counts as a scene cut (default {DEFAULT_CUT})')
     parser.add_argument('--no-temporal-fill', action='store_true',
                         help='Leave pixels that are invalid in a frame invalid instead of filling them from its neighbours')
+
+
+def add_range_arguments(parser):
+    """--range-percentile, shared by the depth CLI and the one-pass pipeline"""
+    parser.add_argument('--range-percentile', type=float, default=100.0,
+                        help='White point of the 16-bit normalisation: this percentile of the valid disparities of a frame (of the '
+                             'window, with --temporal-radius) instead of the maximum; 50..100, at most two decimals (default 100: '
+                             'the maximum, off).  98 keeps a few mismatched pixels from setting the range')
+
+
+def range_options(args) -> dict:
+    return dict(range_percentile=args.range_percentile)
 
 
 def temporal_options(args) -> dict:
