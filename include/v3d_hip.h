@@ -31,6 +31,10 @@
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
  *    data_ptr()); nothing here allocates on the steady-state path: workspaces belong to the handle
  *    and are sized at create time;
+ *  - memory contract (tests/test_abi_guard_gpu.py holds every entry to it): a typed pointer needs only the natural alignment
+ *    of its element type and a `void* ws` 16 bytes, unless the entry's comment says otherwise, and an entry that needs more
+ *    refuses with V3D_ERR_ARG; rows are `pitch` bytes apart and only the payload of a row is read; workspaces and outputs may
+ *    hold anything on entry; nothing outside the stated extent of an output or a workspace is written, inputs included;
  *  - `stream` is a hipStream_t passed as void*; calls enqueue work and do NOT synchronise;
  *  - return 0 on success, negative on error; v3d_last_error() returns the thread-local message;
  *  - a handle is bound to one device and is not thread-safe.
@@ -82,7 +86,8 @@ size_t v3d_sgbm_workspace_bytes(const v3d_sgbm* h);
 /* one frame: left/right gray u8 [H][pitch], disp16 out int16 [H][W] (value x16, -16 invalid) */
 int v3d_sgbm_compute(v3d_sgbm* h, const uint8_t* left_gray, const uint8_t* right_gray,
                      int W, int H, int pitch, int16_t* disp16_out, void* stream);
-/* n frames: frame f at left_gray + f*frame_stride (bytes), output frame f at disp16_out + f*W*H */
+/* n frames: frame f at left_gray + f*frame_stride (bytes), output frame f at disp16_out + f*W*H.  Frames must not overlap:
+   frame_stride < H*pitch with n > 1 is V3D_ERR_ARG, as in the newer batch entries (n == 1 ignores the stride) */
 int v3d_sgbm_compute_batch(v3d_sgbm* h, const uint8_t* left_gray, const uint8_t* right_gray,
                            int n, int W, int H, int pitch, size_t frame_stride,
                            int16_t* disp16_out, void* stream);
@@ -147,7 +152,8 @@ int v3d_filter_speckles(int16_t* img, int W, int H, int newVal, int maxSpeckleSi
    unsqueeze != 0: outputs are W x H (Lanczos4 x2 horizontal); else (W/2) x H. W must be even. */
 int v3d_sbs_to_gray(const uint8_t* sbs_bgr, int W, int H, int pitch, int unsqueeze,
                     uint8_t* left_gray, uint8_t* right_gray, void* stream);
-/* n frames in one launch: frame f at sbs_bgr + f*frame_stride bytes; outputs packed [n][H][outW] */
+/* n frames in one launch: frame f at sbs_bgr + f*frame_stride bytes; outputs packed [n][H][outW].  frame_stride < H*pitch
+   with n > 1 is V3D_ERR_ARG (n == 1 ignores the stride) */
 int v3d_sbs_to_gray_batch(const uint8_t* sbs_bgr, int n, int W, int H, int pitch, size_t frame_stride,
                           int unsqueeze, uint8_t* left_gray, uint8_t* right_gray, void* stream);
 /* the BGR halves themselves (split_sbs_frame's return value), [H][outW][3] */
@@ -214,7 +220,8 @@ int v3d_bgr_to_gray(const uint8_t* bgr, size_t n_pixels, uint8_t* gray, void* st
 
 /* CREStereo-style local group correlation on the matrix cores.
    fl, fr: bf16 [h][w][C] (channel-last), flow: f32 [2][h][w], out: f32 [G*9][h][w];
-   C = 64*G; pattern 0 = 1x9, 1 = 3x3.  ws: scratch of v3d_corr_ws_bytes(C,h,w) bytes */
+   C = 64*G; pattern 0 = 1x9, 1 = 3x3.  ws: scratch of v3d_corr_ws_bytes(C,h,w) bytes.  fl_bf16, fr_bf16 and ws are accessed
+   eight channels at a time and must be 16-byte aligned (else V3D_ERR_ARG) */
 size_t v3d_corr_ws_bytes(int C, int h, int w);
 int v3d_corr_lookup(const uint16_t* fl_bf16, const uint16_t* fr_bf16, const float* flow,
                     int C, int h, int w, int G, int pattern, float* out, void* ws, void* stream);

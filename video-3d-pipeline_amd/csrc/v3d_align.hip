@@ -562,6 +562,7 @@ int prepare(const float* a1, int n1, const float* a2, int n2, void* ws, Layout& 
 {
     if (!a1 || !a2 || !ws) { v3d_set_error("%s: null pointer", what); return V3D_ERR_ARG; }
     if (n1 < 1 || n2 < 1) { v3d_set_error("%s: lengths %d, %d (need >= 1)", what, n1, n2); return V3D_ERR_ARG; }
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) { v3d_set_error("%s: workspace must be 16-byte aligned", what); return V3D_ERR_ARG; }
     if (!make_layout(n1, n2, L)) {
         v3d_set_error("%s: n1 + n2 - 1 = %lld exceeds the largest FFT (2^%d)", what, (long long)n1 + n2 - 1, XC_MAX_LOG);
         return V3D_ERR_UNSUPPORTED;

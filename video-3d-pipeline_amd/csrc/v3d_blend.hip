@@ -93,6 +93,7 @@ extern "C" int v3d_mono_blend_batch(const int16_t* disp16, int n, int W, int H, 
     if (!disp16 || !mono || !depth_out || !ws) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
     if (n < 1 || W < 1 || H < 1 || mw < 1 || mh < 1) { v3d_set_error("bad geometry"); return V3D_ERR_ARG; }
     if (n > 65535) { v3d_set_error("batch too large"); return V3D_ERR_ARG; }
+    if (((uintptr_t)ws & 15) != 0) { v3d_set_error("workspace must be 16-byte aligned"); return V3D_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
     unsigned* mm = reinterpret_cast<unsigned*>(ws);
     const double scx = 1.0 / ((double)W / mw), scy = 1.0 / ((double)H / mh);       // cv::resize: scale = 1 / inv_scale

@@ -346,6 +346,8 @@ extern "C" int v3d_corr_lookup(const uint16_t* fl, const uint16_t* fr, const flo
     if (G < 1 || C != 64 * G) { v3d_set_error("need C == 64*G channels (got C=%d, G=%d)", C, G); return V3D_ERR_UNSUPPORTED; }
     if (h < 1 || w < 1) { v3d_set_error("bad geometry"); return V3D_ERR_ARG; }
     if (pattern != 0 && pattern != 1) { v3d_set_error("pattern must be 0 (1x9) or 1 (3x3)"); return V3D_ERR_ARG; }
+    // the kernels read fl / fr and write ws eight bf16 channels (16 bytes) at a time
+    if ((((uintptr_t)fl | (uintptr_t)fr | (uintptr_t)ws) & 15) != 0) { v3d_set_error("fl, fr and ws must be 16-byte aligned"); return V3D_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
     const int nwaves = ((w + 15) / 16) * h;
     // measured (270x480x256, MI355X): gather-GEMM through LDS 37 us (1x9; round 2, the default); warp + GEMM 67 us (1x9) / 91 us

@@ -876,6 +876,7 @@ static int guided_upscale_batch(const TD* depth_lo, int Wlo, int Hlo, size_t dep
     if (Wlo < 1 || Hlo < 1 || W < 1 || H < 1) { v3d_set_error("bad geometry"); return V3D_ERR_ARG; }
     if (r < 1 || r > GF_RMAX) { v3d_set_error("radius %d outside [1, %d]", r, GF_RMAX); return V3D_ERR_UNSUPPORTED; }
     if (!(eps >= 0.f)) { v3d_set_error("eps must be >= 0"); return V3D_ERR_ARG; }
+    if (((uintptr_t)ws & 15) != 0) { v3d_set_error("workspace must be 16-byte aligned"); return V3D_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
     double* A = reinterpret_cast<double*>(ws);
     double* B = A + (size_t)W * H;

@@ -145,6 +145,7 @@ static int split_common(const uint8_t* sbs, int W, int H, int pitch, int unsquee
     if (!sbs || !L || !R) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
     if (W % 2 != 0) { v3d_set_error("SBS frame width must be even"); return V3D_ERR_ARG; }
     if (W < 2 || H < 1 || pitch < W * 3) { v3d_set_error("bad SBS geometry %dx%d pitch %d", W, H, pitch); return V3D_ERR_ARG; }
+    if (n > 1 && in_stride < (size_t)H * pitch) { v3d_set_error("frame stride %zu below the frame size %zu (H * pitch)", in_stride, (size_t)H * pitch); return V3D_ERR_ARG; }
     LanczosTaps taps;
     lanczos4_taps_host(0.75f, taps.t[0]);
     lanczos4_taps_host(0.25f, taps.t[1]);

@@ -1870,6 +1870,7 @@ static int run_sgbm(v3d_sgbm* h, const uint8_t* left, const uint8_t* right, int 
     int rc = check_geometry(h, n, W, H, pitch);
     if (rc) return rc;
     if (!left || !right || !out) { v3d_set_error("null image pointer"); return V3D_ERR_ARG; }
+    if (n > 1 && frame_stride < (size_t)H * pitch) { v3d_set_error("frame stride %zu below the frame size %zu (H * pitch)", frame_stride, (size_t)H * pitch); return V3D_ERR_ARG; }
     if ((rc = lockstep_state(h)) != V3D_OK) return rc;
     const int W1 = W - V3D_D;
     const int px = W * H;
