@@ -59,17 +59,21 @@ extern "C" {
 
 typedef struct v3d_sgbm v3d_sgbm;
 
-/* mirrors the keyword arguments of cv2.StereoSGBM_create (depth.py:315-325) */
+/* mirrors the keyword arguments of cv2.StereoSGBM_create (depth.py:315-325).  Values are normalised as OpenCV does;
+   what lies outside the accepted domain makes v3d_sgbm_create return V3D_ERR_UNSUPPORTED (nothing is clamped silently).
+   Headroom rule of the packed int16 recurrence, with ftzero = max(preFilterCap, 15) | 1 and P2 after normalisation:
+       2*P2 + 25*(2*ftzero + 63) < 32767   and   ftzero <= 31
+   i.e. P2 <= 15220 for preFilterCap <= 15, P2 <= 14820 for preFilterCap = 30 or 31; preFilterCap >= 32 is refused. */
 typedef struct {
     int minDisparity;       /* must be 0 */
     int numDisparities;     /* must be 64 in this build */
     int blockSize;          /* must be 5 in this build */
-    int P1, P2;
-    int disp12MaxDiff;
-    int preFilterCap;
-    int uniquenessRatio;
-    int speckleWindowSize;
-    int speckleRange;
+    int P1, P2;             /* P1 <= 0 -> 2; P2 <= 0 -> 5; P2 < P1 + 1 -> P1 + 1; then the headroom rule above */
+    int disp12MaxDiff;      /* <= 0 -> 1; any larger value (>= 63 switches the left-right check off in effect) */
+    int preFilterCap;       /* <= 31; ftzero = max(preFilterCap, 15) | 1, so 0..15 act as 15 and an even value as the next odd one */
+    int uniquenessRatio;    /* 0..100; < 0 -> 10; > 100 is refused (OpenCV's literal comparison with a negative factor is not reproduced) */
+    int speckleWindowSize;  /* <= 0: no speckle filter; any positive size, also beyond the pixel count (every component is removed) */
+    int speckleRange;       /* any; joins neighbours with |a - b| <= 16 * speckleRange, compared in 32 bits */
     int mode;               /* V3D_MODE_SGBM / V3D_MODE_HH */
 } v3d_sgbm_params;
 

@@ -1729,6 +1729,13 @@ extern "C" int v3d_sgbm_create(const v3d_sgbm_params* prm, int device, int maxW,
     h->ftzero = (prm->preFilterCap > 15 ? prm->preFilterCap : 15) | 1;
     h->uniq = prm->uniquenessRatio >= 0 ? prm->uniquenessRatio : 10;
     h->t1_mul = 0; h->t1_shift = 0;
+    // uniquenessRatio > 100 makes 100 - uniq negative: OpenCV then rejects a pixel with min S == 0 as soon as a far
+    // disparity has S > 0, which wta_pixel's threshold form (T1 = 0 there) cannot express.  Meaningless as a ratio: refused.
+    if (h->uniq > 100) {
+        const int uq = h->uniq; delete h;
+        v3d_set_error("uniquenessRatio=%d is outside the accepted range (need uniquenessRatio <= 100; negative means 10)", uq);
+        return V3D_ERR_UNSUPPORTED;
+    }
     if (h->uniq < 100) v3d_t1_magic(100 - h->uniq, &h->t1_mul, &h->t1_shift);
     h->d12 = prm->disp12MaxDiff > 0 ? prm->disp12MaxDiff : 1;
     // int16 headroom of the packed recurrence: L <= C <= P2 + 25*(2*ftzero + 63) and delta = min L + P2
