@@ -128,6 +128,34 @@ def test_off_returns_the_maximum_on_fixed_point_depths(native):
     assert np.array_equal(got.cpu().numpy(), TR.minmax(d))
 
 
+@pytest.mark.parametrize("shape,pad", [((3, 5, 67), 0), ((2, 33, 257), 5)])
+def test_mixed_sign_frames_one_range_and_one_sample_on_every_route(native, oracle, shape, pad):
+    """frames whose values change sign (multiples of 1/16 in [-40, 40], so the histogram's white point at q = 10000 IS the
+    maximum): the three reductions -- v3d_depth_minmax_batch, v3d_depth_robust_minmax_batch and the one inside
+    v3d_depth_to_u16_batch -- give NumPy's per-frame min and max, and the u16 samples are the same bits whichever supplies the
+    range.  Frame pad 5 makes the stride odd: the element-wise instantiation of the histogram kernel."""
+    rng = np.random.default_rng(shape[2])
+    d = (rng.integers(-640, 641, shape) / 16.0).astype(np.float32)
+    want_mm = np.stack([d.reshape(shape[0], -1).min(axis=1), d.reshape(shape[0], -1).max(axis=1)], axis=1)
+    assert (want_mm[:, 0] < 0).all() and (want_mm[:, 1] > 0).all()
+    dd = _view(d, pad)
+    assert dd.stride(0) == shape[1] * shape[2] + pad
+    mm, rmm = native.depth_minmax_batch(dd), native.depth_robust_minmax_batch(dd, 10000)
+    assert np.array_equal(mm.cpu().numpy(), want_mm)
+    assert np.array_equal(rmm.cpu().numpy(), want_mm)
+    want = np.stack([oracle.depth_to_u16(f) for f in d])                     # the oracle reduces its own min and max
+    out = torch.empty(shape, dtype=torch.int16, device="cuda")                # the C entry itself: the binding takes dense clips only
+    ws = torch.empty(2 * shape[0], dtype=torch.float32, device="cuda")
+    assert native.lib().v3d_depth_to_u16_batch(C.c_void_p(dd.data_ptr()), shape[0], C.c_size_t(shape[1] * shape[2]), C.c_size_t(dd.stride(0)),
+                                               C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_void_p(0)) == 0
+    own = _u16(out)
+    assert np.array_equal(own, _u16(native.depth_to_u16_batch(dd.contiguous())))
+    assert not mismatch_report(own, want, f"own range {shape}")
+    assert not mismatch_report(_u16(native.depth_to_u16_range_batch(dd, mm)), want, f"min/max entry's range {shape} pad {pad}")
+    assert not mismatch_report(_u16(native.depth_to_u16_range_batch(dd, rmm)), want, f"histogram entry's range {shape} pad {pad}")
+    assert np.array_equal(want, TR.to_u16_range(d, want_mm))
+
+
 def _matched_clip(native, W, H, T, **kw):
     """the synthetic clip through the GPU matcher -> (depth f32 [T,H,W], left gray u8 [T,H,W]) as NumPy"""
     from video_3d_pipeline import synthetic as syn

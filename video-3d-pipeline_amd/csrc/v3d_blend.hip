@@ -5,18 +5,15 @@
 //   :363      combined = 0.7 * disparity + 0.3 * mono_n  disparity = compute() / 16 (invalid = -1.0)
 //   :374      combined[combined <= 0] = 0
 // Two streaming launches per batch: (1) resize into the output buffer + per-frame min/max (wave shuffle reduction,
-// one atomic pair per wave, order-preserving uint encoding); (2) normalise + blend + clamp in place.
+// one atomic pair per wave, order-preserving uint encoding: mm_wave_fold, v3d_f2ord); (2) normalise + blend + clamp in place.
 // Every float operation is a single correctly rounded f32 op in the reference's order (no contraction), so the result is
 // bit-identical to the NumPy expression on the same resized map.  HBM-bound: 2 B + 4 B in, 4 B written twice per pixel.
 #include "v3d_common.h"
 
-__device__ __forceinline__ unsigned bl_f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float bl_ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
-
 __global__ void k_blend_mm_init(unsigned* mm, int n)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i < n) { mm[2 * i] = 0xFFFFFFFFu; mm[2 * i + 1] = 0u; }
+    if (i < n) mm_reset(mm + 2 * i);
 }
 
 #define BL_ROWS 8
@@ -56,20 +53,18 @@ __global__ __launch_bounds__(256) void k_mono_resize_minmax(const float* __restr
                 v = __fadd_rn(__fmul_rn(r0, b0), __fmul_rn(r1, b1));
             }
             dst[(size_t)y * W + x] = v;
-            const unsigned o = bl_f2ord(v);
+            const unsigned o = v3d_f2ord(v);
             lo = min(lo, o); hi = max(hi, o);
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
-    if ((threadIdx.x & 63) == 0 && lo <= hi) { atomicMin(mm + 2 * f, lo); atomicMax(mm + 2 * f + 1, hi); }
+    mm_wave_fold(mm + 2 * f, lo, hi, true);                    // a wave wholly right of the image has nothing to say
 }
 
 __global__ __launch_bounds__(256) void k_mono_blend(const int16_t* __restrict__ disp16, size_t npx, const unsigned* __restrict__ mm,
                                                     float ws, float wm, float* __restrict__ out)
 {
     const int f = blockIdx.y;
-    const float mn = bl_ord2f(mm[2 * f]), mx = bl_ord2f(mm[2 * f + 1]);
+    const float mn = v3d_ord2f(mm[2 * f]), mx = v3d_ord2f(mm[2 * f + 1]);
     const bool flat = !(mx > mn);
     const float range = __fsub_rn(mx, mn);
     const int16_t* d16 = disp16 + (size_t)f * npx;

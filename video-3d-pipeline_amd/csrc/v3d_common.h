@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/v3d_hip.h"
+#include "v3d_depth_math.h"   // V3D_HD, the ordered float codec, d16 and the u16 normalisations
 
 #define V3D_D 64              // numDisparities this build is specialised for (one wavefront of d)
 #define V3D_MAX_COST 32767
@@ -48,11 +49,6 @@ static inline int v3d_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- division-free integer arithmetic of the winner-take-all tail (plain C: host and device; tests/test_wta_arith_host.py
 // restates these lines in NumPy and checks them against exact division) ----
-#ifdef __HIPCC__
-#define V3D_HD __host__ __device__
-#else
-#define V3D_HD
-#endif
 // T1 = ceil(minS * 100 / uq) = (100 minS + uq - 1) / uq for uq = 100 - uniquenessRatio in [1, 100] and minS in [0, 32767], as
 // (n * mul) >> shift with mul = ceil(2^shift / uq), shift = 23 + ceil(log2 uq).  Exact: mul * uq = 2^shift + e with
 // 0 <= e < uq <= 2^(shift - 23), so n * mul / 2^shift = n / uq + n e / (uq 2^shift) and the excess n e / 2^shift < n / 2^23 < 1
@@ -110,6 +106,17 @@ __device__ __forceinline__ uint32_t pk_subu_sat(uint32_t a, uint32_t b) { return
 __device__ __forceinline__ uint32_t pk_minu(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_min(as_us(a), as_us(b))); }
 __device__ __forceinline__ uint32_t pk_shr_u(uint32_t a, int n) { return as_u((v3d_u16x2)(as_us(a) >> (unsigned short)n)); }
 __device__ __forceinline__ uint32_t pk_bcast(int v) { return ((uint32_t)v & 0xFFFFu) * 0x00010001u; }
+
+// ---- per-frame float min / max in a {min, max} slot of two ordered uints (v3d_f2ord): exact, so schedule-independent ----
+__device__ __forceinline__ void mm_reset(unsigned* slot) { slot[0] = 0xFFFFFFFFu; slot[1] = 0u; }
+// a lane's (lo, hi) folded over its wave by butterfly, then ONE atomic pair per wave.  skip_empty: a wave none of whose lanes
+// saw a value (lo > hi) issues nothing
+__device__ __forceinline__ void mm_wave_fold(unsigned* slot, unsigned lo, unsigned hi, bool skip_empty = false)
+{
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
+    if ((threadIdx.x & 63) == 0 && !(skip_empty && lo > hi)) { atomicMin(slot, lo); atomicMax(slot + 1, hi); }
+}
 
 // ({hi,lo} >> sh) & 0xffffffff  (v_alignbit_b32)
 __device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }

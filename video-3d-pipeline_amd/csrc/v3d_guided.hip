@@ -33,13 +33,12 @@ template <> __device__ __forceinline__ float gf_ld<int16_t>(const int16_t* p, si
 // or as the normalised 16-bit sample of the depth PNG (read_png16(...).astype(float32) on the device: the same float values)
 template <> __device__ __forceinline__ float gf_ld<uint16_t>(const uint16_t* p, size_t i) { return (float)p[i]; }
 
-// q leaves either as float32 or as the 16-bit sample of the 4K PNG: clamp(rint(q), 0, 65535), NaN -> 0, exactly k_round_u16
-// (v3d_pre.hip) applied to the float32 value the float instantiation stores
+// q leaves either as float32 or as the 16-bit sample of the 4K PNG: v3d_rint_u16 (clamp(rint(q), 0, 65535), NaN -> 0), exactly
+// what k_round_u16 (v3d_pre.hip) applies to the float32 value the float instantiation stores
 typedef unsigned short v3d_u16x2v __attribute__((ext_vector_type(2)));
 typedef unsigned short v3d_u16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint16_t gf_u16(float q) { const float v = rintf(q); return (uint16_t)(v >= 65535.f ? 65535.f : v > 0.f ? v : 0.f); }
 __device__ __forceinline__ void gf_st(float* p, float q) { *p = q; }
-__device__ __forceinline__ void gf_st(uint16_t* p, float q) { *p = gf_u16(q); }
+__device__ __forceinline__ void gf_st(uint16_t* p, float q) { *p = v3d_rint_u16(q); }
 
 #define GF_TX 64
 #define GF_RUN 8      // outputs per thread along x in the horizontal pass
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(256) void k_gf(const TD* __restrict__ depth_lo, int
                     const double I = (double)guide[(size_t)gy * W + gx] / 255.0;
                     const float q = (float)((s[0] / cnt) * I + (s[1] / cnt));
                     if constexpr (std::is_same<TO, float>::value) out[(size_t)gy * W + gx] = q;
-                    else out[(size_t)gy * W + gx] = gf_u16(q);
+                    else out[(size_t)gy * W + gx] = v3d_rint_u16(q);
                 }
             }
             if (j + 1 < GF_RUNY) {
@@ -370,7 +369,7 @@ __global__ __launch_bounds__(256) void k_gfm(const TD* __restrict__ depth_lo, in
                                     v3d_f32x2 vq = { qa, qb };
                                     __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x2*>(out + o));
                                 } else {
-                                    v3d_u16x2v vq = { gf_u16(qa), gf_u16(qb) };
+                                    v3d_u16x2v vq = { v3d_rint_u16(qa), v3d_rint_u16(qb) };
                                     __builtin_nontemporal_store(vq, reinterpret_cast<v3d_u16x2v*>(out + o));
                                 }
                             } else {
@@ -769,7 +768,7 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                                     const v3d_f32x4 vq = { q[0], q[1], q[2], q[3] };
                                     __builtin_nontemporal_store(vq, reinterpret_cast<v3d_f32x4*>(out + o));
                                 } else {
-                                    const v3d_u16x4 vq = { gf_u16(q[0]), gf_u16(q[1]), gf_u16(q[2]), gf_u16(q[3]) };
+                                    const v3d_u16x4 vq = { v3d_rint_u16(q[0]), v3d_rint_u16(q[1]), v3d_rint_u16(q[2]), v3d_rint_u16(q[3]) };
                                     __builtin_nontemporal_store(vq, reinterpret_cast<v3d_u16x4*>(out + o));
                                 }
                             } else {

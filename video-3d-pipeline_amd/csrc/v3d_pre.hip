@@ -1,7 +1,8 @@
 // v3d_pre.hip -- the per-frame steps either side of the matcher:
 //   depth.py:250-268 split_sbs_frame (cv2.resize INTER_LANCZOS4 horizontal x2 "unsqueeze"),
 //   depth.py:274-275 + 337-338 cvtColor (BGR->RGB->GRAY), depth.py:341/374 (/16, clamp),
-//   depth.py:397-406 save_depth_map (min-max -> uint16).
+//   and the rounding of the 4K depth to the PNG sink's 16-bit sample.
+// (depth.py:397-406 save_depth_map, min-max -> uint16, lives in v3d_range.hip with the other range entries.)
 // All pure streaming kernels: one read of the input, one write of the output.
 #include "v3d_common.h"
 #include <math.h>
@@ -202,78 +203,10 @@ extern "C" int v3d_disp_to_depth(const int16_t* disp16, size_t n, float* out, vo
     return V3D_OK;
 }
 
-// ---- save_depth_map normalisation: ((d - min) / (max - min) * 65535).astype(uint16) in float32 ----
-__device__ __forceinline__ unsigned f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
-
-// One launch set for n frames: blockIdx.y is the frame, each frame has its own {min, max} pair in mm[2f], mm[2f + 1].  Min and
-// max are exact and the normalisation is per element, so frame f's bits depend neither on n nor on the block count.
-__global__ void k_minmax_init(unsigned* mm, int n)
-{
-    for (int f = blockIdx.x * 256 + threadIdx.x; f < n; f += gridDim.x * 256) { mm[2 * f] = 0xFFFFFFFFu; mm[2 * f + 1] = 0u; }
-}
-__global__ __launch_bounds__(256) void k_minmax(const float* __restrict__ d, size_t n, size_t stride, unsigned* mm)
-{
-    d += blockIdx.y * stride; mm += 2 * blockIdx.y;
-    unsigned lo = 0xFFFFFFFFu, hi = 0u;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const unsigned o = f2ord(d[i]);
-        lo = min(lo, o); hi = max(hi, o);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(mm, lo); atomicMax(mm + 1, hi); }
-}
-__global__ __launch_bounds__(256) void k_norm_u16(const float* __restrict__ d, size_t n, size_t stride, const unsigned* __restrict__ mm,
-                                                  uint16_t* __restrict__ out)
-{
-    d += blockIdx.y * stride; mm += 2 * blockIdx.y; out += blockIdx.y * n;
-    const float mn = ord2f(mm[0]), mx = ord2f(mm[1]);
-    const bool flat = !(mx > mn);
-    const float range = mx - mn;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float v = 0.f;
-        if (!flat) {
-            v = __fsub_rn(d[i], mn);
-            v = __fdiv_rn(v, range);
-            v = __fmul_rn(v, 65535.0f);
-        }
-        out[i] = (uint16_t)v;
-    }
-}
-static int depth_to_u16(const float* depth, int n, size_t elems, size_t stride, uint16_t* out, float* ws, hipStream_t st)
-{
-    if (!depth || !out || !ws) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
-    if (n < 1 || n > 65535) { v3d_set_error("bad batch %d", n); return V3D_ERR_ARG; }
-    if (n > 1 && stride < elems) { v3d_set_error("frame stride %zu below the frame size %zu", stride, elems); return V3D_ERR_ARG; }
-    if (elems == 0) return V3D_OK;
-    unsigned* mm = reinterpret_cast<unsigned*>(ws);
-    // about 1024 blocks per launch whatever n is (at least 64 per frame): a 1080p frame is 8100 blocks of 256
-    const size_t per = (size_t)(1024 / n > 64 ? 1024 / n : 64);
-    const int bx = (int)((elems + 255) / 256 < per ? (elems + 255) / 256 : per);
-    hipLaunchKernelGGL(k_minmax_init, dim3(v3d_cdiv(n, 256)), dim3(256), 0, st, mm, n);
-    hipLaunchKernelGGL(k_minmax, dim3(bx, n), dim3(256), 0, st, depth, elems, stride, mm);
-    hipLaunchKernelGGL(k_norm_u16, dim3(bx, n), dim3(256), 0, st, depth, elems, stride, mm, out);
-    V3D_LAUNCH_CHECK();
-    return V3D_OK;
-}
-extern "C" int v3d_depth_to_u16(const float* depth, size_t n, uint16_t* out, float* ws, void* stream)
-{
-    return depth_to_u16(depth, 1, n, n, out, ws, (hipStream_t)stream);
-}
-extern "C" int v3d_depth_to_u16_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, uint16_t* out,
-                                      float* minmax_ws, void* stream)
-{
-    return depth_to_u16(depth, n, frame_elems, frame_stride, out, minmax_ws, (hipStream_t)stream);
-}
-
-// ---- 4K depth -> the 16-bit sample of the PNG sink: round to nearest even (numpy.rint / torch.round), clamp to [0, 65535] ----
+// ---- 4K depth -> the 16-bit sample of the PNG sink: v3d_rint_u16 (v3d_depth_math.h) ----
 __global__ __launch_bounds__(256) void k_round_u16(const float* __restrict__ d, size_t n, uint16_t* __restrict__ out)
 {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float v = rintf(d[i]);
-        out[i] = (uint16_t)(v >= 65535.f ? 65535.f : v > 0.f ? v : 0.f);        // NaN -> 0
-    }
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = v3d_rint_u16(d[i]);
 }
 extern "C" int v3d_round_to_u16(const float* depth, size_t n, uint16_t* out, void* stream)
 {

@@ -1,22 +1,116 @@
-// v3d_range.hip -- robust depth range for the u16 normalisation ("Robust range"; contract in
-// include/v3d_hip.h, NumPy restatement in tests/range_ref.py).  Per frame, one read of the depth gives the float min and max
-// (as v3d_depth_minmax_batch reduces them) and a histogram of the fixed-point disparities d16 = rint(16 D), valid iff >= 1:
-//   hist[b] = #{d16 == b} for 1 <= b <= 2046, hist[2047] = #{d16 >= 2047}, n_valid = sum hist
-//   k = max(1, ceil(q n_valid / 10000)), hi16 = the smallest b whose cumulative count reaches k
-//   hi = mx if n_valid == 0 or hi16 == 2047, else max(hi16 / 16, mn)                 -> (mn, hi) per frame
-// Every sum is an integer, so the order of the atomics cannot change a bit.  No entry synchronises or allocates.
+// v3d_range.hip -- float depth -> per-frame (min, max) -> u16 samples: every entry that reduces a depth range or normalises
+// against one (contracts in include/v3d_hip.h; the arithmetic itself is v3d_depth_math.h).
+//   v3d_depth_to_u16[_batch]        depth.py:397-406 save_depth_map: a frame against its own min and max
+//   v3d_depth_minmax_batch          the same reduction, handed out as floats (the temporal stage's window range starts here)
+//   v3d_depth_to_u16_range_batch    the same samples against a (lo, hi) the device supplies per frame
+//   v3d_depth_robust_minmax_batch   ("Robust range"; NumPy restatement in tests/range_ref.py): per frame, one
+//     read of the depth gives the float min and max and a histogram of the fixed-point disparities d16 = rint(16 D), valid iff >= 1:
+//       hist[b] = #{d16 == b} for 1 <= b <= 2046, hist[2047] = #{d16 >= 2047}, n_valid = sum hist
+//       k = max(1, ceil(q n_valid / 10000)), hi16 = the smallest b whose cumulative count reaches k
+//       hi = mx if n_valid == 0 or hi16 == 2047, else max(hi16 / 16, mn)                 -> (mn, hi) per frame
+// Min and max are exact, every sum is an integer and the normalisation is per element, so neither the order of the atomics nor
+// the batch or block count can change a bit.  No entry synchronises or allocates.
 #include "v3d_common.h"
 
 #define RR_NB 2048
 #define RR_WAVES 4             // waves of a 256-lane workgroup
 
-__device__ __forceinline__ unsigned rr_f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float rr_ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+static int check_frames(int n, size_t elems, size_t stride, size_t min_elems = 1)
+{
+    if (n < 1 || n > 65535 || elems < min_elems) { v3d_set_error("bad batch %d x %zu", n, elems); return V3D_ERR_ARG; }
+    if (n > 1 && stride < elems) { v3d_set_error("frame stride %zu below the frame size %zu", stride, elems); return V3D_ERR_ARG; }
+    return V3D_OK;
+}
+// blocks per frame of a (blocks, n) grid whose block covers px elements per step: about 1024 blocks per launch whatever n is, at
+// least `floor` per frame, never more than the frame fills (a 1080p frame is 8100 blocks of 256)
+static int frame_blocks(size_t elems, int n, int floor, size_t px = 256)
+{
+    const size_t want = (elems + px - 1) / px, per = (size_t)(1024 / n > floor ? 1024 / n : floor);
+    return (int)(want < per ? want : per);
+}
 
-// the histogram bin of a depth: 0 = invalid (not counted), the last bin saturates; NaN compares false twice -> 0
+// ---- per-frame min / max: blockIdx.y is the frame, frame f's {min, max} slot is mm[2f], mm[2f + 1] (ordered uints) ----
+__global__ void k_mm_init(unsigned* mm, int n)
+{
+    for (int f = blockIdx.x * 256 + threadIdx.x; f < n; f += gridDim.x * 256) mm_reset(mm + 2 * f);
+}
+__global__ __launch_bounds__(256) void k_minmax(const float* __restrict__ d, size_t n, size_t stride, unsigned* mm)
+{
+    d += blockIdx.y * stride; mm += 2 * blockIdx.y;
+    unsigned lo = 0xFFFFFFFFu, hi = 0u;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned o = v3d_f2ord(d[i]);
+        lo = min(lo, o); hi = max(hi, o);
+    }
+    mm_wave_fold(mm, lo, hi);
+}
+__global__ void k_mm_decode(unsigned* mm, int n)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += gridDim.x * 256) mm[i] = __float_as_uint(v3d_ord2f(mm[i]));
+}
+// ENCODED: the frame's (lo, hi) is a {min, max} slot as k_minmax leaves it; else two floats
+template <bool ENCODED>
+__global__ __launch_bounds__(256) void k_norm_u16(const float* __restrict__ d, size_t n, size_t stride, const unsigned* __restrict__ lohi,
+                                                  uint16_t* __restrict__ out)
+{
+    d += blockIdx.y * stride; lohi += 2 * blockIdx.y; out += blockIdx.y * n;
+    const float lo = ENCODED ? v3d_ord2f(lohi[0]) : __uint_as_float(lohi[0]), hi = ENCODED ? v3d_ord2f(lohi[1]) : __uint_as_float(lohi[1]);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = v3d_norm_u16(d[i], lo, hi);
+}
+
+static int depth_to_u16(const float* depth, int n, size_t elems, size_t stride, uint16_t* out, float* ws, hipStream_t st)
+{
+    if (!depth || !out || !ws) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
+    if (check_frames(n, elems, stride, 0) != V3D_OK) return V3D_ERR_ARG;
+    if (elems == 0) return V3D_OK;
+    unsigned* mm = reinterpret_cast<unsigned*>(ws);
+    const int bx = frame_blocks(elems, n, 64);
+    hipLaunchKernelGGL(k_mm_init, dim3(v3d_cdiv(n, 256)), dim3(256), 0, st, mm, n);
+    hipLaunchKernelGGL(k_minmax, dim3(bx, n), dim3(256), 0, st, depth, elems, stride, mm);
+    hipLaunchKernelGGL(k_norm_u16<true>, dim3(bx, n), dim3(256), 0, st, depth, elems, stride, mm, out);
+    V3D_LAUNCH_CHECK();
+    return V3D_OK;
+}
+extern "C" int v3d_depth_to_u16(const float* depth, size_t n, uint16_t* out, float* ws, void* stream)
+{
+    return depth_to_u16(depth, 1, n, n, out, ws, (hipStream_t)stream);
+}
+extern "C" int v3d_depth_to_u16_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, uint16_t* out,
+                                      float* minmax_ws, void* stream)
+{
+    return depth_to_u16(depth, n, frame_elems, frame_stride, out, minmax_ws, (hipStream_t)stream);
+}
+
+extern "C" int v3d_depth_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride, float* minmax_out,
+                                      void* stream)
+{
+    if (!depth || !minmax_out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
+    if (check_frames(T, frame_elems, frame_stride) != V3D_OK) return V3D_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* mm = reinterpret_cast<unsigned*>(minmax_out);
+    hipLaunchKernelGGL(k_mm_init, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, mm, T);
+    hipLaunchKernelGGL(k_minmax, dim3(frame_blocks(frame_elems, T, 64), T), dim3(256), 0, st, depth, frame_elems, frame_stride, mm);
+    hipLaunchKernelGGL(k_mm_decode, dim3(v3d_cdiv(2 * T, 256)), dim3(256), 0, st, mm, T);
+    V3D_LAUNCH_CHECK();
+    return V3D_OK;
+}
+
+extern "C" int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, const float* lohi,
+                                            uint16_t* out, void* stream)
+{
+    if (!depth || !lohi || !out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
+    if (check_frames(n, frame_elems, frame_stride) != V3D_OK) return V3D_ERR_ARG;
+    hipLaunchKernelGGL(k_norm_u16<false>, dim3(frame_blocks(frame_elems, n, 64), n), dim3(256), 0, (hipStream_t)stream, depth, frame_elems,
+                       frame_stride, reinterpret_cast<const unsigned*>(lohi), out);
+    V3D_LAUNCH_CHECK();
+    return V3D_OK;
+}
+
+// ---- the robust range: its own fused kernels (min/max and histogram off one read), one init launch ----
+// the histogram bin: 0 = invalid (not counted), the last bin saturates; NaN compares false twice -> 0
 __device__ __forceinline__ int rr_bin(float d)
 {
-    const float v = rintf(__fmul_rn(d, 16.0f));
+    const float v = v3d_d16(d);
     return v >= (float)(RR_NB - 1) ? RR_NB - 1 : v >= 1.f ? (int)v : 0;
 }
 
@@ -24,7 +118,7 @@ __global__ void k_rr_init(unsigned* hist, unsigned* mm, int T)
 {
     const size_t n = (size_t)T * RR_NB;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) hist[i] = 0u;
-    for (int f = blockIdx.x * 256 + threadIdx.x; f < T; f += gridDim.x * 256) { mm[2 * f] = 0xFFFFFFFFu; mm[2 * f + 1] = 0u; }
+    for (int f = blockIdx.x * 256 + threadIdx.x; f < T; f += gridDim.x * 256) mm_reset(mm + 2 * f);
 }
 
 // A depth map is piecewise smooth, so the lanes of a wave, and the 4 pixels of a lane, mostly hit the same few bins: same-
@@ -41,7 +135,7 @@ __device__ __forceinline__ void rr_count4(unsigned* h, const float4 v)
 }
 __device__ __forceinline__ void rr_minmax4(unsigned& lo, unsigned& hi, const float4 v)
 {
-    const unsigned a = rr_f2ord(v.x), b = rr_f2ord(v.y), c = rr_f2ord(v.z), d = rr_f2ord(v.w);
+    const unsigned a = v3d_f2ord(v.x), b = v3d_f2ord(v.y), c = v3d_f2ord(v.z), d = v3d_f2ord(v.w);
     lo = min(min(lo, a), min(b, min(c, d)));
     hi = max(max(hi, a), max(b, max(c, d)));
 }
@@ -76,14 +170,12 @@ __global__ __launch_bounds__(256) void k_rr_hist(const float* __restrict__ d, si
     }
     for (size_t i = nvec * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
         const float v = d[i];
-        const unsigned o = rr_f2ord(v);
+        const unsigned o = v3d_f2ord(v);
         lo = min(lo, o); hi = max(hi, o);
         const int b = rr_bin(v);
         if (b) atomicAdd(h + b, 1u);
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(mm, lo); atomicMax(mm + 1, hi); }
+    mm_wave_fold(mm, lo, hi);
     __syncthreads();
     for (int b = threadIdx.x; b < RR_NB; b += 256) {
         const unsigned c = h[b];
@@ -112,7 +204,7 @@ __global__ __launch_bounds__(256) void k_rr_select(const unsigned* __restrict__ 
     unsigned before = inc - own, n_valid = 0;
 #pragma unroll
     for (int w = 0; w < RR_WAVES; w++) { before += w < wave ? part[w] : 0u; n_valid += part[w]; }
-    const float mn = rr_ord2f(mm[2 * t]), mx = rr_ord2f(mm[2 * t + 1]);
+    const float mn = v3d_ord2f(mm[2 * t]), mx = v3d_ord2f(mm[2 * t + 1]);
     if (tid == 0) { out[2 * t] = mn; if (n_valid == 0) out[2 * t + 1] = mx; }
     if (n_valid == 0) return;
     const unsigned long long kq = ((unsigned long long)q * n_valid + 9999ull) / 10000ull;
@@ -139,9 +231,8 @@ extern "C" int v3d_depth_robust_minmax_batch(const float* depth, int T, size_t f
                                              float* minmax_out, void* stream)
 {
     if (!depth || !ws || !minmax_out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
-    if (T < 1 || T > 65535 || frame_elems < 1) { v3d_set_error("bad batch %d x %zu", T, frame_elems); return V3D_ERR_ARG; }
+    if (check_frames(T, frame_elems, frame_stride) != V3D_OK) return V3D_ERR_ARG;
     if (q < 5000 || q > 10000) { v3d_set_error("range quantile %d outside [5000, 10000]", q); return V3D_ERR_ARG; }
-    if (T > 1 && frame_stride < frame_elems) { v3d_set_error("frame stride %zu below the frame size %zu", frame_stride, frame_elems); return V3D_ERR_ARG; }
     if (((uintptr_t)ws & 15) != 0) { v3d_set_error("workspace must be 16-byte aligned"); return V3D_ERR_ARG; }
     if (frame_elems > 0xFFFFFFFFull) { v3d_set_error("frame of %zu elements: the bins are 32-bit counters", frame_elems); return V3D_ERR_UNSUPPORTED; }
     hipStream_t st = (hipStream_t)stream;
@@ -150,9 +241,7 @@ extern "C" int v3d_depth_robust_minmax_batch(const float* depth, int T, size_t f
     const bool vec = ((uintptr_t)depth & 15) == 0 && (T == 1 || (frame_stride & 3) == 0);
     // one step of a block covers 4096 px.  All workgroups of a 34-frame pass are resident at once (4 per CU): a grid a little
     // larger than the chip holds runs a second, nearly empty round that costs as much as the first
-    const size_t want = (frame_elems + 4095) / 4096;
-    const size_t per = (size_t)(1024 / T > 8 ? 1024 / T : 8);
-    const int bx = (int)(want < per ? want : per);
+    const int bx = frame_blocks(frame_elems, T, 8, 4096);
     hipLaunchKernelGGL(k_rr_init, dim3(T < 128 ? 8 * T : 1024), dim3(256), 0, st, hist, mm, T);
     if (vec) hipLaunchKernelGGL(k_rr_hist<true>, dim3(bx, T), dim3(256), 0, st, depth, frame_elems, frame_stride, hist, mm);
     else hipLaunchKernelGGL(k_rr_hist<false>, dim3(bx, T), dim3(256), 0, st, depth, frame_elems, frame_stride, hist, mm);

@@ -1067,7 +1067,20 @@ __global__ __launch_bounds__(256) void k_vdd_guard(const int* __restrict__ err, 
 // ------------------------------------------------------------------------------------------------
 // a-8: medianBlur(3) on int16 with replicated borders (the invalid value takes part like any other).
 // ------------------------------------------------------------------------------------------------
-#define V3D_SORT2(a, b) { const int _lo = min(a, b), _hi = max(a, b); a = _lo; b = _hi; }
+// The 19-exchange median-of-9 network: sort2(a, b) leaves (min, max) in (a, b); the median ends in p[4], which is returned.
+// Run on int (one pixel) and on two int16 pixels packed in a dword.
+struct sort2_int { __device__ __forceinline__ void operator()(int& a, int& b) const { const int lo = min(a, b), hi = max(a, b); a = lo; b = hi; } };
+struct sort2_pk { __device__ __forceinline__ void operator()(uint32_t& a, uint32_t& b) const { const uint32_t lo = pk_min(a, b), hi = pk_max(a, b); a = lo; b = hi; } };
+template <typename T, typename X>
+__device__ __forceinline__ T median9(T (&p)[9], X sort2)
+{
+    sort2(p[1], p[2]); sort2(p[4], p[5]); sort2(p[7], p[8]); sort2(p[0], p[1]);
+    sort2(p[3], p[4]); sort2(p[6], p[7]); sort2(p[1], p[2]); sort2(p[4], p[5]);
+    sort2(p[7], p[8]); sort2(p[0], p[3]); sort2(p[5], p[8]); sort2(p[4], p[7]);
+    sort2(p[3], p[6]); sort2(p[1], p[4]); sort2(p[2], p[5]); sort2(p[4], p[7]);
+    sort2(p[4], p[2]); sort2(p[6], p[4]); sort2(p[4], p[2]);
+    return p[4];
+}
 __global__ __launch_bounds__(256) void k_median3x3(const int16_t* __restrict__ src, int W, int H, int16_t* __restrict__ dst)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
@@ -1077,13 +1090,22 @@ __global__ __launch_bounds__(256) void k_median3x3(const int16_t* __restrict__ s
     const int16_t* r0 = s + (size_t)max(y - 1, 0) * W;
     const int16_t* r1 = s + (size_t)y * W;
     const int16_t* r2 = s + (size_t)min(y + 1, H - 1) * W;
-    int p0 = r0[xm], p1 = r0[x], p2 = r0[xp], p3 = r1[xm], p4 = r1[x], p5 = r1[xp], p6 = r2[xm], p7 = r2[x], p8 = r2[xp];
-    V3D_SORT2(p1, p2); V3D_SORT2(p4, p5); V3D_SORT2(p7, p8); V3D_SORT2(p0, p1);
-    V3D_SORT2(p3, p4); V3D_SORT2(p6, p7); V3D_SORT2(p1, p2); V3D_SORT2(p4, p5);
-    V3D_SORT2(p7, p8); V3D_SORT2(p0, p3); V3D_SORT2(p5, p8); V3D_SORT2(p4, p7);
-    V3D_SORT2(p3, p6); V3D_SORT2(p1, p4); V3D_SORT2(p2, p5); V3D_SORT2(p4, p7);
-    V3D_SORT2(p4, p2); V3D_SORT2(p6, p4); V3D_SORT2(p4, p2);
-    dst[(size_t)f * H * W + (size_t)y * W + x] = (int16_t)p4;
+    int p[9] = { r0[xm], r0[x], r0[xp], r1[xm], r1[x], r1[xp], r2[xm], r2[x], r2[xp] };
+    dst[(size_t)f * H * W + (size_t)y * W + x] = (int16_t)median9(p, sort2_int());
+}
+
+// the L-R check of a valid left-view disparity d1 (x16) at image column x against its row's right-view keys (min S << 6 | 63 - d,
+// 0xFFFFFFFF = no source): stereosgbm.cpp invalidates the pixel when BOTH roundings of the disparity find a right-view disparity
+// further than d12 away.  key(c) reads the key of image column c (a reader, not a pointer: an LDS array handed over as a pointer
+// reaches the compiler as a generic address); x - da, x - db lie in [x - 63, x]: always inside the row
+template <typename KEY>
+__device__ __forceinline__ int lr_check(int d1, int x, int d12, KEY key)
+{
+    const int da = d1 >> 4, db = (d1 + 15) >> 4;
+    const uint32_t ka = key(x - da), kb = key(x - db);
+    const bool bad = (ka != 0xFFFFFFFFu) && (abs(63 - (int)(ka & 63u) - da) > d12) &&
+                     (kb != 0xFFFFFFFFu) && (abs(63 - (int)(kb & 63u) - db) > d12);
+    return bad ? V3D_INVALID16 : d1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1145,13 +1167,7 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
             int d1 = V3D_INVALID16;
             if (x >= V3D_D) {
                 d1 = wta_d16(sW[ty][x - xbase]);
-                if (d1 != V3D_INVALID16) {
-                    const int da = d1 >> 4, db = (d1 + 15) >> 4;              // x - da, x - db lie in [x - 63, x]: always inside the row
-                    const uint32_t ka = sD2[ty][x - da - xbase], kb = sD2[ty][x - db - xbase];
-                    const bool bad = (ka != 0xFFFFFFFFu) && (abs(63 - (int)(ka & 63u) - da) > d12) &&
-                                     (kb != 0xFFFFFFFFu) && (abs(63 - (int)(kb & 63u) - db) > d12);
-                    if (bad) d1 = V3D_INVALID16;
-                }
+                if (d1 != V3D_INVALID16) d1 = lr_check(d1, x, d12, [&](int c) { return sD2[ty][c - xbase]; });
             }
             sT[ty][tx] = (short)d1;
         }
@@ -1165,14 +1181,9 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
         const int y = y0 + ty;
         if (y >= H) break;
         if (!MED) { out[fo + (size_t)y * W + x] = sT[ty + 1][tx + 1]; continue; }
-        int p0 = sT[ty][tx], p1 = sT[ty][tx + 1], p2 = sT[ty][tx + 2], p3 = sT[ty + 1][tx], p4 = sT[ty + 1][tx + 1],
-            p5 = sT[ty + 1][tx + 2], p6 = sT[ty + 2][tx], p7 = sT[ty + 2][tx + 1], p8 = sT[ty + 2][tx + 2];
-        V3D_SORT2(p1, p2); V3D_SORT2(p4, p5); V3D_SORT2(p7, p8); V3D_SORT2(p0, p1);
-        V3D_SORT2(p3, p4); V3D_SORT2(p6, p7); V3D_SORT2(p1, p2); V3D_SORT2(p4, p5);
-        V3D_SORT2(p7, p8); V3D_SORT2(p0, p3); V3D_SORT2(p5, p8); V3D_SORT2(p4, p7);
-        V3D_SORT2(p3, p6); V3D_SORT2(p1, p4); V3D_SORT2(p2, p5); V3D_SORT2(p4, p7);
-        V3D_SORT2(p4, p2); V3D_SORT2(p6, p4); V3D_SORT2(p4, p2);
-        out[fo + (size_t)y * W + x] = (int16_t)p4;
+        int p[9] = { sT[ty][tx], sT[ty][tx + 1], sT[ty][tx + 2], sT[ty + 1][tx], sT[ty + 1][tx + 1], sT[ty + 1][tx + 2],
+                     sT[ty + 2][tx], sT[ty + 2][tx + 1], sT[ty + 2][tx + 2] };
+        out[fo + (size_t)y * W + x] = (int16_t)median9(p, sort2_int());
     }
 }
 
@@ -1186,7 +1197,6 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
 // same key set, same median network (run on two adjacent outputs at once in packed int16): bit-identical to the tile form.
 // ------------------------------------------------------------------------------------------------
 #define LRR_BAND 15
-#define V3D_SORT2PK(a, b) { const uint32_t _lo = pk_min(a, b), _hi = pk_max(a, b); a = _lo; b = _hi; }
 template <bool MED, int NPP>      // NPP: pixel PAIRS per thread and row (columns 2t, 2t+1, 2t + 512, ...): 4 covers W <= 2048, 8 W <= 4096; W even
 __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __restrict__ wta, int W, int H, int d12, int16_t* __restrict__ out)
 {
@@ -1236,13 +1246,7 @@ __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __r
                     int d1 = V3D_INVALID16;
                     if (x >= V3D_D) {
                         d1 = wta_d16(rec[2 * i + n]);
-                        if (d1 != V3D_INVALID16) {
-                            const int da = d1 >> 4, db = (d1 + 15) >> 4;
-                            const uint32_t ka = sD2[x - da], kb = sD2[x - db];
-                            const bool bad = (ka != 0xFFFFFFFFu) && (abs(63 - (int)(ka & 63u) - da) > d12) &&
-                                             (kb != 0xFFFFFFFFu) && (abs(63 - (int)(kb & 63u) - db) > d12);
-                            if (bad) d1 = V3D_INVALID16;
-                        }
+                        if (d1 != V3D_INVALID16) d1 = lr_check(d1, x, d12, [sD2](int c) { return sD2[c]; });
                     }
                     dd[n] = d1;
                 }
@@ -1269,12 +1273,7 @@ __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __r
                         const uint32_t wr = xw + 1 < W2 ? rr[r][xw + 1] : (w0 >> 16);         // column W replicates column W-1
                         p[3 * r] = alignbit(w0, wl, 16); p[3 * r + 1] = w0; p[3 * r + 2] = alignbit(wr, w0, 16);   // (x-1, x), (x, x+1), (x+1, x+2)
                     }
-                    V3D_SORT2PK(p[1], p[2]); V3D_SORT2PK(p[4], p[5]); V3D_SORT2PK(p[7], p[8]); V3D_SORT2PK(p[0], p[1]);
-                    V3D_SORT2PK(p[3], p[4]); V3D_SORT2PK(p[6], p[7]); V3D_SORT2PK(p[1], p[2]); V3D_SORT2PK(p[4], p[5]);
-                    V3D_SORT2PK(p[7], p[8]); V3D_SORT2PK(p[0], p[3]); V3D_SORT2PK(p[5], p[8]); V3D_SORT2PK(p[4], p[7]);
-                    V3D_SORT2PK(p[3], p[6]); V3D_SORT2PK(p[1], p[4]); V3D_SORT2PK(p[2], p[5]); V3D_SORT2PK(p[4], p[7]);
-                    V3D_SORT2PK(p[4], p[2]); V3D_SORT2PK(p[6], p[4]); V3D_SORT2PK(p[4], p[2]);
-                    *reinterpret_cast<uint32_t*>(out + fo + (size_t)yo * W + 2 * xw) = p[4];
+                    *reinterpret_cast<uint32_t*>(out + fo + (size_t)yo * W + 2 * xw) = median9(p, sort2_pk());
                 }
             }
         }

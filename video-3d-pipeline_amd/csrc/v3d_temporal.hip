@@ -4,13 +4,12 @@
 //   d16_u = rint(16 D_u)  (valid iff >= 1)          s_k = 3x3 edge-replicated sum of |Y_u - Y_t|  (0..2295)
 //   w_k = (R + 1 - |k|) * max(0, 256 - floor(256 s_k / (9 tau))) * valid      out16 = floor((2 sum w d16 + sum w) / (2 sum w))
 // All integers, so the bits do not depend on any order of evaluation; 2 Dsum + Wsum < 2^31 for R <= 8 and d16 <= 32767.
-// Cut flags, per-frame min/max and the clip-stable ranges are produced and consumed on the device: no entry synchronises.
+// Cut flags and the clip-stable ranges are produced and consumed on the device: no entry synchronises.  This file holds the cuts,
+// the window range and the filter; the per-frame min/max they take (v3d_depth_minmax_batch) and the u16 samples against the
+// window range (v3d_depth_to_u16_range_batch) live in v3d_range.hip, d16 in v3d_depth_math.h.
 #include "v3d_common.h"
 
 #define TP_MAX_R 8
-
-__device__ __forceinline__ unsigned tp_f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float tp_ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 
 // frames [lo, hi] that may contribute to target t: |u - t| <= R, inside [0, T), no cut in (min(t,u), max(t,u)]
 __device__ __forceinline__ void tp_admissible(const uint8_t* __restrict__ cut, int T, int t, int R, int& lo, int& hi)
@@ -85,45 +84,6 @@ extern "C" int v3d_temporal_cuts(const uint8_t* gray, size_t gray_stride, int T,
         hipLaunchKernelGGL(k_tp_sad, dim3(bx, T - 1), dim3(256), 0, st, gray, gray_stride, npx, vec, sums);
     }
     hipLaunchKernelGGL(k_tp_cutflag, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, sums, T, (unsigned long long)c * npx, cut_out);
-    V3D_LAUNCH_CHECK();
-    return V3D_OK;
-}
-
-// ---- per-frame min / max of the unfiltered depth (the reduction of v3d_depth_to_u16_batch, as floats) ----
-__global__ void k_tp_mm_init(unsigned* mm, int n)
-{
-    for (int f = blockIdx.x * 256 + threadIdx.x; f < n; f += gridDim.x * 256) { mm[2 * f] = 0xFFFFFFFFu; mm[2 * f + 1] = 0u; }
-}
-__global__ __launch_bounds__(256) void k_tp_minmax(const float* __restrict__ d, size_t n, size_t stride, unsigned* mm)
-{
-    d += blockIdx.y * stride; mm += 2 * blockIdx.y;
-    unsigned lo = 0xFFFFFFFFu, hi = 0u;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const unsigned o = tp_f2ord(d[i]);
-        lo = min(lo, o); hi = max(hi, o);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, s)); hi = max(hi, (unsigned)__shfl_xor((int)hi, s)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(mm, lo); atomicMax(mm + 1, hi); }
-}
-__global__ void k_tp_mm_decode(unsigned* mm, int n)
-{
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += gridDim.x * 256) mm[i] = __float_as_uint(tp_ord2f(mm[i]));
-}
-
-extern "C" int v3d_depth_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride, float* minmax_out,
-                                      void* stream)
-{
-    if (!depth || !minmax_out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
-    if (T < 1 || T > 65535 || frame_elems < 1) { v3d_set_error("bad batch %d x %zu", T, frame_elems); return V3D_ERR_ARG; }
-    if (T > 1 && frame_stride < frame_elems) { v3d_set_error("frame stride %zu below the frame size %zu", frame_stride, frame_elems); return V3D_ERR_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    unsigned* mm = reinterpret_cast<unsigned*>(minmax_out);
-    const size_t per = (size_t)(1024 / T > 64 ? 1024 / T : 64);
-    const int bx = (int)((frame_elems + 255) / 256 < per ? (frame_elems + 255) / 256 : per);
-    hipLaunchKernelGGL(k_tp_mm_init, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, mm, T);
-    hipLaunchKernelGGL(k_tp_minmax, dim3(bx, T), dim3(256), 0, st, depth, frame_elems, frame_stride, mm);
-    hipLaunchKernelGGL(k_tp_mm_decode, dim3(v3d_cdiv(2 * T, 256)), dim3(256), 0, st, mm, T);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }
@@ -235,7 +195,7 @@ __global__ __launch_bounds__(256) void k_tp_filter(const float* __restrict__ dep
         const uint32_t tw = (uint32_t)(R + 1 - (k < 0 ? -k : k));
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int d16 = (int)rintf(__fmul_rn(d[i], 16.0f));
+            const int d16 = (int)v3d_d16(d[i]);
             const bool valid = d16 >= 1;
             if (u == t) centre[i] = valid;
             const uint32_t q = __umulhi(s[i] << 8, mul);
@@ -279,39 +239,6 @@ extern "C" int v3d_temporal_filter_batch(const float* depth, size_t depth_stride
                                 t0, R, mul, fill, cut, out);
     else hipLaunchKernelGGL(k_tp_filter<false>, grid, block, 0, (hipStream_t)stream, depth, depth_stride, gray, gray_stride, T, W, H,
                             t0, R, mul, fill, cut, out);
-    V3D_LAUNCH_CHECK();
-    return V3D_OK;
-}
-
-// ---- u16 samples against a given range: v3d_depth_to_u16's float32 steps with (lo, hi) from the device ----
-__global__ __launch_bounds__(256) void k_tp_norm_u16(const float* __restrict__ d, size_t n, size_t stride, const float* __restrict__ lohi,
-                                                     uint16_t* __restrict__ out)
-{
-    d += blockIdx.y * stride; out += blockIdx.y * n;
-    const float mn = lohi[2 * blockIdx.y], mx = lohi[2 * blockIdx.y + 1];
-    const bool flat = !(mx > mn);
-    const float range = __fsub_rn(mx, mn);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float v = 0.f;
-        if (!flat) {
-            v = __fsub_rn(d[i], mn);
-            v = __fdiv_rn(v, range);
-            v = __fmul_rn(v, 65535.0f);
-            v = v >= 65535.f ? 65535.f : v > 0.f ? v : 0.f;      // a filtered blend may round up to 1/32 outside the range; NaN -> 0
-        }
-        out[i] = (uint16_t)v;
-    }
-}
-
-extern "C" int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, const float* lohi,
-                                            uint16_t* out, void* stream)
-{
-    if (!depth || !lohi || !out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
-    if (n < 1 || n > 65535 || frame_elems < 1) { v3d_set_error("bad batch %d x %zu", n, frame_elems); return V3D_ERR_ARG; }
-    if (n > 1 && frame_stride < frame_elems) { v3d_set_error("frame stride %zu below the frame size %zu", frame_stride, frame_elems); return V3D_ERR_ARG; }
-    const size_t per = (size_t)(1024 / n > 64 ? 1024 / n : 64);
-    const int bx = (int)((frame_elems + 255) / 256 < per ? (frame_elems + 255) / 256 : per);
-    hipLaunchKernelGGL(k_tp_norm_u16, dim3(bx, n), dim3(256), 0, (hipStream_t)stream, depth, frame_elems, frame_stride, lohi, out);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }
