@@ -26,6 +26,8 @@
  *   v3d_temporal_*, v3d_depth_minmax_batch, v3d_depth_to_u16_range_batch  no call site in the reference (it normalises every
  *                          frame on its own, depth.py:397-406): opt-in temporal stabilisation of the depth sequence
  *   v3d_depth_robust_minmax_batch  no call site in the reference either: opt-in percentile white point of that normalisation
+ *   v3d_fill_holes_disp16_batch  no call site in the reference (depth.py:374 turns every invalid disparity into depth 0): opt-in
+ *                          filling of the matcher's invalid pixels from their scanline neighbours, before /16
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -302,6 +304,25 @@ int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, 
 size_t v3d_depth_robust_minmax_ws_bytes(int T);
 int v3d_depth_robust_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride /* elements */, int q,
                                   void* ws, float* minmax_out, void* stream);
+
+/* Disparity hole filling (v3d_fill.hip): an opt-in stage on the matcher's int16 disparity, directly after the matcher and before
+   /16, the hybrid blend, the temporal stage, the range and the normalisation.  Bit-exact contract, all integers:
+   tests/fill_ref.py.  Per frame d (int16 [H][W]) a pixel is a hole iff d < 0; a disparity of 0 is valid and stays.
+     1. rows: in a row with at least one non-hole pixel, a hole at x takes min(d[a], d[b]) of the nearest non-hole pixels a (left)
+        and b (right) of the INPUT row, or the only one if one side has none; non-hole pixels are copied unchanged;
+     2. empty rows: a row with no non-hole pixel becomes a copy of the step-1 output of the nearest non-empty row by |r - y|, ties
+        to the row above; a frame with no non-hole pixel at all is copied unchanged.
+   So the result has no negative value unless the whole frame was invalid, the stage is idempotent, and valid pixels keep their
+   bits.  Frame f at disp16 + f*disp_stride (elements; rows dense), out dense [n][H][W]; int16 pointers need 2-byte alignment
+   only (W may be odd, frames may start at odd element offsets).  out == disp16 (in place) is allowed iff n == 1 or
+   disp_stride == W*H; any other overlap of out with disp16 is not.  ws: device scratch of v3d_fill_holes_ws_bytes(n, H) bytes
+   (one non-empty flag per row), 16-byte aligned.  Enqueues two launches on `stream`, never synchronises, never allocates.
+   V3D_ERR_ARG: null pointer, n outside [1, 65535], W or H < 1, disp_stride < W*H with n > 1, a misaligned ws, out == disp16
+   with another stride; V3D_ERR_UNSUPPORTED: W > 8192 or H > 65535.  v3d_fill_holes_ws_bytes is 0 for arguments the entry
+   refuses. */
+size_t v3d_fill_holes_ws_bytes(int n, int H);
+int v3d_fill_holes_disp16_batch(const int16_t* disp16, size_t disp_stride /* elements */, int n, int W, int H,
+                                int16_t* out /* dense [n][H][W] */, void* ws, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

@@ -31,6 +31,7 @@ EXPORTS = (
     "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
     "v3d_depth_to_u16_range_batch",
     "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
+    "v3d_fill_holes_ws_bytes", "v3d_fill_holes_disp16_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -138,6 +139,9 @@ def lib():
         L.v3d_depth_robust_minmax_ws_bytes.argtypes = [ci]
         L.v3d_depth_robust_minmax_ws_bytes.restype = sz
         L.v3d_depth_robust_minmax_batch.argtypes = [vp, ci, sz, sz, ci, vp, vp, vp]
+        L.v3d_fill_holes_ws_bytes.argtypes = [ci, ci]
+        L.v3d_fill_holes_ws_bytes.restype = sz
+        L.v3d_fill_holes_disp16_batch.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -717,6 +721,32 @@ def depth_to_u16_range_batch(depth, lohi, out=None):
     with torch.cuda.device(depth.device):
         _check(lib().v3d_depth_to_u16_range_batch(d, n, H * W, ds, _dev(lohi, torch.float32, "lohi"), _dev(out, torch.int16, "out"),
                                                   _stream()), "v3d_depth_to_u16_range_batch")
+    return out
+
+
+FILL_MAX_WIDTH, FILL_MAX_HEIGHT = 8192, 65535
+
+
+def fill_holes_disp16_batch(disp, out=None, ws=None):
+    """int16 disparity [n,H,W] on the device (frames dense HxW, only the frame stride may differ; < 0 = hole) -> the filled
+    disparity, dense [n,H,W] (v3d_fill_holes_disp16_batch; bit-exact contract: tests/fill_ref.py).  out=None allocates the result;
+    out=disp fills in place (a single frame or a dense batch).  ws: a uint8 device tensor of at least v3d_fill_holes_ws_bytes(n, H)
+    bytes, 16-byte aligned (a caller's staging buffer); None takes one from the caching allocator."""
+    d, ds = _clip(disp, torch.int16, "disp")
+    n, H, W = disp.shape
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.int16, device=disp.device)
+    if tuple(out.shape) != (n, H, W):
+        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    need = lib().v3d_fill_holes_ws_bytes(n, H)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=disp.device)
+    elif need and ws.numel() < need:
+        raise NativeError(f"ws: {ws.numel()} bytes, the fill needs {need}")
+    o = C.c_void_p(out.data_ptr()) if out is disp else _dev(out, torch.int16, "out")
+    with torch.cuda.device(disp.device):
+        _check(lib().v3d_fill_holes_disp16_batch(d, ds, n, W, H, o, _dev(ws, torch.uint8, "ws"), _stream()),
+               "v3d_fill_holes_disp16_batch")
     return out
 
 

@@ -114,8 +114,17 @@ class HipStereoBackend:
                 nat.mono_blend(disp[i], m, 0.7, 0.3, out[i])
         return out
 
-    def pairs_to_disparity(self, pairs: List[Tuple[np.ndarray, np.ndarray]], monos=None) -> List[np.ndarray]:
-        """BGR (left, right) pairs -> float32 disparity maps (>= 0), depth.py:337-341 + 374 (+ 344-371 with `monos`)"""
+    def fill_holes(self, disp):
+        """--fill-holes: the int16 disparity [n,H,W] of a pass, filled in place (v3d_fill_holes_disp16_batch); the row flags
+        live in a staging buffer"""
+        nat = self.native
+        n, H, _ = disp.shape
+        ws = self._staging("fill_ws", (max(16, nat.lib().v3d_fill_holes_ws_bytes(n, H)),), self.torch.uint8, False)
+        return nat.fill_holes_disp16_batch(disp, out=disp, ws=ws)
+
+    def pairs_to_disparity(self, pairs: List[Tuple[np.ndarray, np.ndarray]], monos=None, fill_holes: bool = False) -> List[np.ndarray]:
+        """BGR (left, right) pairs -> float32 disparity maps (>= 0), depth.py:337-341 + 374 (+ 344-371 with `monos`);
+        fill_holes: the matcher's invalid pixels are filled first (per frame, so this surface has it too)"""
         torch, nat = self.torch, self.native
         n = len(pairs)
         H, W = pairs[0][0].shape[:2]
@@ -130,6 +139,8 @@ class HipStereoBackend:
             disp = matcher.compute(lg, rg)
             if matcher.sync_errors():
                 raise RuntimeError("SGM kernels report time-outs with the lock-step pass off: device fault")
+        if fill_holes:
+            disp = self.fill_holes(disp)
         depth = self._depth_from(disp, monos)
         out = depth.cpu().numpy()
         return [out[i] for i in range(n)]
@@ -144,10 +155,12 @@ class HipStereoBackend:
             bufs[key] = t
         return t
 
-    def sbs_to_disparity(self, frames: List[np.ndarray], unsqueeze: bool, mono_provider=None):
+    def sbs_to_disparity(self, frames: List[np.ndarray], unsqueeze: bool, mono_provider=None, fill_holes: bool = False):
         """fused path: SBS BGR frames -> device float32 disparity [n,H,W] (no BGR halves materialised).
         Frames are gathered into one pinned buffer and cross PCIe in a single asynchronous copy.
-        mono_provider (neural guidance on): called with the left views as RGB arrays, its maps are blended in."""
+        mono_provider (neural guidance on): called with the left views as RGB arrays, its maps are blended in.
+        fill_holes: the int16 disparity is filled in place after the matcher (and its lock-step recompute), before /16 and the
+        blend."""
         torch, nat = self.torch, self.native
         n = len(frames)
         H, W = frames[0].shape[:2]
@@ -167,6 +180,8 @@ class HipStereoBackend:
             disp = matcher.compute(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False))
             if matcher.sync_errors():
                 raise RuntimeError("SGM kernels report time-outs with the lock-step pass off: device fault")
+        if fill_holes:
+            disp = self.fill_holes(disp)
         monos = None
         out = self._staging("depth", (n, H, ow), torch.float32, False)
         if mono_provider is not None:
@@ -253,16 +268,22 @@ class HybridStereoDepthExtractor:
                  temporal_tau: int = 12,
                  temporal_cut: int = 20,
                  temporal_fill: bool = True,
-                 range_percentile: float = 100.0):
+                 range_percentile: float = 100.0,
+                 fill_holes: bool = False):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
         on its own, the reference's behaviour.  process_frame_batch / save_depth_map stay per-frame: a list of pairs is not a clip.
         range_percentile < 100 (process_video_sbs only): the white point of the 16-bit normalisation is that percentile of the
-        valid disparities instead of the maximum; 100 = the reference's min-max """
+        valid disparities instead of the maximum; 100 = the reference's min-max.
+        fill_holes (every surface, process_frame_batch included: it is per frame): the matcher's invalid pixels are filled from
+        their scanline neighbours on the int16 disparity, before /16 and everything after it; off = they stay depth 0 """
         from .temporal import check_parameters, check_range_percentile
         self.temporal = check_parameters(temporal_radius, temporal_tau, temporal_cut, temporal_fill)
         self.range_quantile = check_range_percentile(range_percentile)
+        if not isinstance(fill_holes, (bool, np.bool_)):
+            raise ValueError(f"fill_holes must be a bool, got {fill_holes!r}")
+        self.fill_holes = bool(fill_holes)
 
         self.device = device
         self.work_dir = create_work_directory(work_dir)
@@ -339,6 +360,15 @@ class HybridStereoDepthExtractor:
                 out.append(self.model(**inputs).predicted_depth[0].float())
         return out
 
+    def _stage_kw(self) -> dict:
+        """the keyword a disparity pass of the backend gains with --fill-holes; off: none, the call every backend knows"""
+        return {"fill_holes": True} if self.fill_holes else {}
+
+    def _write_fill_side_file(self, cache_path: Path):
+        if self.fill_holes:
+            import json
+            (cache_path / "fill.json").write_text(json.dumps({"fill_holes": True}))
+
     def _guidance_provider(self):
         """ the provider when neural guidance is active (depth.py:344-345), else None """
         if self.use_neural_guidance and not self.stereo_only and self.mono_provider is not None:
@@ -348,9 +378,9 @@ class HybridStereoDepthExtractor:
     def get_cache_path(self, video_path: str, frame_start: int, frame_count: int) -> Path:
         """ Generate cache path for depth maps (key format identical to depth.py:119-120; with temporal stabilisation or the
         robust range on, the key also carries their parameters, so such maps and the reference's never share a directory) """
-        from .temporal import cache_suffix
+        from .temporal import cache_suffix, fill_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
-        cache_key += cache_suffix(*self.temporal, self.range_quantile)
+        cache_key += cache_suffix(*self.temporal, self.range_quantile) + fill_suffix(self.fill_holes)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -425,8 +455,8 @@ class HybridStereoDepthExtractor:
                     monos = provider([np.ascontiguousarray(l[..., ::-1]) for l, _ in frame_pairs])     # left views as RGB (depth.py:274)
                 except Exception as e:                       # depth.py:367-369
                     print(f"    Warning: Neural guidance failed, using stereo only: {e}")
-            depth_maps = self.backend.pairs_to_disparity(frame_pairs, monos) if monos is not None \
-                else self.backend.pairs_to_disparity(frame_pairs)
+            depth_maps = self.backend.pairs_to_disparity(frame_pairs, monos, **self._stage_kw()) if monos is not None \
+                else self.backend.pairs_to_disparity(frame_pairs, **self._stage_kw())
         except Exception as e:
             print(f"Error processing frame batch: {e}")
             raise
@@ -482,9 +512,9 @@ class HybridStereoDepthExtractor:
             if not batch:
                 return
             if provider is not None:
-                depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs, provider)
+                depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs, provider, **self._stage_kw())
             else:
-                depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs)
+                depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs, **self._stage_kw())
             u16 = self.backend.to_host_u16(self.backend.depth_to_u16_robust(depth, self.range_quantile)) if robust else None
             for j, frame_idx in enumerate(batch_idx):
                 writers.submit(cache_path / f"depth_{frame_idx:06d}.png", u16[j] if robust else self.backend.normalise_u16(depth[j]))
@@ -511,6 +541,8 @@ class HybridStereoDepthExtractor:
             import json
             from .temporal import manifest_entry
             (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal, self.range_quantile)))
+        if rank == 0:
+            self._write_fill_side_file(cache_path)
         sharding.barrier()
 
         print(f"✓ Depth extraction complete: {cache_path}")
@@ -553,9 +585,9 @@ class HybridStereoDepthExtractor:
             if not batch:
                 return
             if provider is not None:
-                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs, provider)
+                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs, provider, **self._stage_kw())
             else:
-                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs)
+                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs, **self._stage_kw())
             write(*stab.push(depth, be.left_gray(len(batch))))
             batch.clear()
 
@@ -574,6 +606,8 @@ class HybridStereoDepthExtractor:
             raise ValueError("No frames extracted from video")
         if rank == 0:
             (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal, self.range_quantile)))
+        if rank == 0:
+            self._write_fill_side_file(cache_path)
         sharding.barrier()
 
         print(f"✓ Depth extraction complete: {cache_path}")
@@ -600,9 +634,11 @@ def main(argv=None):
     parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
     parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
-    from .temporal import add_range_arguments, add_temporal_arguments, range_options, temporal_options
+    from .temporal import (add_fill_arguments, add_range_arguments, add_temporal_arguments, fill_options, range_options,
+                           temporal_options)
     add_temporal_arguments(parser)
     add_range_arguments(parser)
+    add_fill_arguments(parser)
     args = parser.parse_args(argv)
 
     stereo_only = args.stereo_only or args.no_neural
@@ -615,7 +651,7 @@ def main(argv=None):
         extractor = HybridStereoDepthExtractor(
             model_checkpoint=args.model, work_dir=args.work_dir, cache_dir=args.work_dir, device=args.device,
             batch_size=args.batch_size, use_neural_guidance=use_neural_guidance, stereo_only=stereo_only,
-            unsqueeze_sbs=unsqueeze_sbs, **temporal_options(args), **range_options(args))
+            unsqueeze_sbs=unsqueeze_sbs, **temporal_options(args), **range_options(args), **fill_options(args))
         output_path = extractor.process_video_sbs(video_path=args.video, start_frame=args.start_frame,
                                                   max_frames=args.max_frames, force_reprocess=args.force)
         print(f"\n✓ Success! Depth maps saved to: {output_path}")

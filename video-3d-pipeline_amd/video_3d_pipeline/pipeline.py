@@ -9,6 +9,7 @@ and through zlib twice before the 4K filter sees it.  Here the depth stays on th
                -> v3d_depth_to_u16_batch (per-frame min-max -> u16, the depth PNG's samples)
                   [--temporal-radius R: the temporal stabiliser's u16 samples instead (temporal.py), R frames behind the matcher]
                   [--range-percentile P: the white point of either is the P-th percentile of the valid disparities, not the maximum]
+                  [--fill-holes: the matcher's invalid pixels are filled inside sbs_to_disparity, before any of the above]
                -> [--keep-depth-maps: depth_%06d.png into the depth CLI's cache directory]
                -> v3d_guided_upscale_u16_batch against the matching 4K frames' luma -> u16 4K samples -> writer pool
 
@@ -102,10 +103,12 @@ class SbsTo4kDepthPipeline:
                  temporal_tau: int = 12,
                  temporal_cut: int = 20,
                  temporal_fill: bool = True,
-                 range_percentile: float = 100.0):
+                 range_percentile: float = 100.0,
+                 fill_holes: bool = False):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own);
-        range_percentile: the depth CLI's robust white point (100 = off: the maximum)"""
+        range_percentile: the depth CLI's robust white point (100 = off: the maximum);
+        fill_holes: the depth CLI's hole filling of the int16 disparity (off: invalid pixels stay depth 0)"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -116,7 +119,7 @@ class SbsTo4kDepthPipeline:
             model_checkpoint=model_checkpoint, work_dir=work_dir, cache_dir=work_dir, device=device, batch_size=batch_size,
             use_neural_guidance=use_neural_guidance, stereo_only=stereo_only, unsqueeze_sbs=unsqueeze_sbs, backend=backend,
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
-            temporal_fill=temporal_fill, range_percentile=range_percentile)
+            temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
 
@@ -204,9 +207,9 @@ class SbsTo4kDepthPipeline:
             if not batch:
                 return
             if provider is not None:
-                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, provider)
+                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, provider, **ex._stage_kw())
             else:
-                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs)
+                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, **ex._stage_kw())
             if stab is None and robust:
                 emit(writers, list(batch_idx), be.depth_to_u16_robust(depth, ex.range_quantile))
             elif stab is None:
@@ -263,10 +266,15 @@ class SbsTo4kDepthPipeline:
         if rank == 0:
             from .temporal import manifest_entry
             entry = manifest_entry(*ex.temporal, ex.range_quantile) if stab is not None or robust else None
-            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, {"temporal": entry} if entry else None)
+            extra = {"temporal": entry} if entry else {}
+            if ex.fill_holes:
+                extra["fill_holes"] = True
+            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, extra or None)
             if entry and keep_depth_maps:
                 import json
                 (cache_path / "temporal.json").write_text(json.dumps(entry))
+            if keep_depth_maps:
+                ex._write_fill_side_file(cache_path)
             if stereo is not None and n_stereo:
                 from .convert import finish_stereo_output, write_clip_info
                 write_clip_info(stereo["dir"], fps)
@@ -306,10 +314,12 @@ def main(argv=None):
     parser.add_argument('--stereo-output', default=None,
                         help='Also render side-by-side 3D to this path (what the convert CLI makes from the depth output)')
     from .convert import add_stereo_arguments, stereo_options
-    from .temporal import add_range_arguments, add_temporal_arguments, range_options, temporal_options
+    from .temporal import (add_fill_arguments, add_range_arguments, add_temporal_arguments, fill_options, range_options,
+                           temporal_options)
     add_stereo_arguments(parser)
     add_temporal_arguments(parser)
     add_range_arguments(parser)
+    add_fill_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -325,7 +335,8 @@ def main(argv=None):
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
         pipe = SbsTo4kDepthPipeline(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device,
                                     batch_size=args.batch_size, use_neural_guidance=not stereo_only, stereo_only=stereo_only,
-                                    unsqueeze_sbs=not args.no_unsqueeze, **temporal_options(args), **range_options(args))
+                                    unsqueeze_sbs=not args.no_unsqueeze, **temporal_options(args), **range_options(args),
+                                    **fill_options(args))
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,

@@ -15,6 +15,9 @@ All of it is integer arithmetic with a bit-exact contract (include/v3d_hip.h; te
 becomes the P-th percentile of its valid disparities, so a few mismatched pixels no longer set the scale of every sample
 (contract: include/v3d_hip.h, tests/range_ref.py).  Everything after the per-frame (min, max) is unchanged.
 
+`--fill-holes` (opt-in, per frame, combines with both) fills the matcher's invalid pixels from their scanline neighbours on the
+int16 disparity, before anything above sees it (contract: include/v3d_hip.h, tests/fill_ref.py).
+
 `TemporalStabilizer` is the streaming driver: a clip arrives in passes of any size, the output lags the input by R frames
 and the last 2R frames of depth and gray stay on the device between passes.  The result does not depend on how the clip is
 cut into passes.  Frames before the first pushed frame and after the last one do not exist for the window.
@@ -168,6 +171,23 @@ def add_range_arguments(parser):
                         help='White point of the 16-bit normalisation: this percentile of the valid disparities of a frame (of the '
                              'window, with --temporal-radius) instead of the maximum; 50..100, at most two decimals (default 100: '
                              'the maximum, off).  98 keeps a few mismatched pixels from setting the range')
+
+
+def add_fill_arguments(parser):
+    """--fill-holes, shared by the depth CLI and the one-pass pipeline"""
+    parser.add_argument('--fill-holes', action='store_true',
+                        help="Fill the matcher's invalid pixels (the 64 leftmost columns, occlusions, rejected matches) from their "
+                             'scanline neighbours with the background value before the depth is normalised (default: off, they '
+                             'stay depth 0)')
+
+
+def fill_options(args) -> dict:
+    return dict(fill_holes=args.fill_holes)
+
+
+def fill_suffix(fill_holes: bool) -> str:
+    """what the depth cache key gains, after the temporal and range suffixes, with --fill-holes ('' when off)"""
+    return "_fill1" if fill_holes else ""
 
 
 def range_options(args) -> dict:
