@@ -38,6 +38,12 @@ class OracleStereoBackend:
     def normalise_u16(self, depth):
         return O.depth_to_u16(np.asarray(depth, np.float32))
 
+    def depth_to_u16_batch(self, depth):
+        return np.stack([O.depth_to_u16(np.asarray(d, np.float32)) for d in depth])
+
+    def to_host_u16(self, u16):
+        return np.array(u16, np.uint16)
+
 
 class _FakeTensor:
     def __init__(self, a):
@@ -505,3 +511,65 @@ def test_world_without_process_group_fails_loudly(tmp_path, clip, monkeypatch):
     up = SimpleDepthUpscaler(backend=OracleUpscaleBackend())
     with pytest.raises(RuntimeError, match="not initialised"):
         up.upscale_depth_maps_ffmpeg(str(tmp_path / "d"), 8, 8, str(tmp_path / "o.mp4"), video_4k_path=path)
+
+
+@pytest.mark.parametrize("world", [1, 2, 3])
+def test_iter_depth_u16_is_the_depth_clis_samples_on_every_rank(tmp_path, monkeypatch, world):
+    """the streaming driver itself, ranks simulated one after the other: per frame (round-robin) and with a radius (blocks plus
+    halos), passes of 2 over 7 frames; every yielded plane is the file the depth CLI writes for that index"""
+    from test_temporal_host import TemporalStereoBackend
+    from video_3d_pipeline import depth as depth_mod, sharding, synthetic as syn
+    from video_3d_pipeline.utils import read_png16
+    n = 7
+    path = str(tmp_path / "clip7.npy")
+    np.save(path, syn.temporal_sbs_clip(192, 48, n, cut_at=4, speed=4))
+
+    def extractor(tag, radius):
+        return depth_mod.HybridStereoDepthExtractor(work_dir=str(tmp_path / tag), cache_dir=str(tmp_path / tag), batch_size=2, stereo_only=True,
+                                                    backend=TemporalStereoBackend() if radius else OracleStereoBackend(), temporal_radius=radius)
+
+    for radius in (0, 2):
+        cli_dir = extractor(f"cli{radius}", radius).process_video_sbs(path)
+        want = [read_png16(cli_dir / f"depth_{i:06d}.png") for i in range(n)]
+        seen = []
+        for rank in range(world):
+            ex = extractor(f"r{radius}", radius)
+            info, count = ex._frame_count(path, 0, None)
+            mine = []
+            with monkeypatch.context() as mp:
+                mp.setattr(sharding, "rank_world", lambda: (rank, world))
+                for idx, u16 in ex.iter_depth_u16(path, 0, count, info, *sharding.rank_world()):
+                    assert len(idx) == len(u16) > 0
+                    for i, plane in zip(idx, ex.backend.to_host_u16(u16)):
+                        assert plane.dtype == np.uint16 and np.array_equal(plane, want[i]), (radius, rank, i)
+                    mine += idx
+            assert mine == sorted(mine)
+            (_, dcount, stride, offset), owned, _ = ex.frame_plan(count, rank, world)
+            assert ex.last_decoded_frames == len(range(offset, dcount, stride)) and ex.last_pass_frames == 2
+            assert mine == list(range(owned[0] + owned[3], owned[0] + owned[1], owned[2]))
+            seen += mine
+        assert sorted(seen) == list(range(n)), (radius, world)
+    # a rank whose block is empty (2 frames, 3 ranks) yields nothing and never opens the clip
+    ex = extractor("empty", 2)
+    assert ex.frame_plan(2, 2, 3) == ((2, 0, 1, 0), (2, 0, 1, 0), (2, 0, 0))
+    monkeypatch.setattr(depth_mod, "iter_frames", lambda *a, **k: pytest.fail("an empty block decoded frames"))
+    assert list(ex.iter_depth_u16(path, 0, 2, ex._frame_count(path, 0, 2)[0], 2, 3)) == [] and ex.last_decoded_frames == 0
+
+
+def test_backend_with_the_per_frame_surface_only_writes_the_same_files(tmp_path, clip):
+    """a backend that has sbs_to_disparity and normalise_u16 but neither depth_to_u16_batch nor to_host_u16 -- all the plain
+    path asked of one before the streaming driver -- is still served, per frame, with the same files"""
+    from video_3d_pipeline.depth import HybridStereoDepthExtractor
+
+    class PerFrameBackend:
+        sbs_to_disparity = OracleStereoBackend.sbs_to_disparity
+        normalise_u16 = OracleStereoBackend.normalise_u16
+
+    path, _ = clip
+    dirs = []
+    for tag, be in (("batch", OracleStereoBackend()), ("frame", PerFrameBackend())):
+        ex = HybridStereoDepthExtractor(work_dir=str(tmp_path / tag), cache_dir=str(tmp_path / tag), batch_size=2, stereo_only=True, backend=be)
+        dirs.append(ex.process_video_sbs(path))
+    files = [sorted(os.listdir(d)) for d in dirs]
+    assert files[0] == files[1] == [f"depth_{i:06d}.png" for i in range(5)]
+    assert all((dirs[0] / f).read_bytes() == (dirs[1] / f).read_bytes() for f in files[0])

@@ -63,6 +63,26 @@ def test_process_video_sbs_and_upscale_end_to_end(native, oracle, tmp_path, clip
     assert d4.shape == (144, 512) and np.abs(d4 - want).max() <= 1e-3 * max(1.0, np.abs(want).max())
 
 
+def test_per_pass_samples_equal_the_per_frame_route(native, oracle, tmp_path, clip):
+    """the streaming driver's samples come from one normalising launch set per pass: 5 frames in passes of 2, 2 and 1 (a partial
+    last pass, staging buffers re-shaped) give the files of the per-frame route -- normalise_u16 on each frame's own depth --
+    and of the oracle"""
+    from video_3d_pipeline.depth import HybridStereoDepthExtractor
+    from video_3d_pipeline.utils import read_png16
+    path, frames = clip
+    ex = HybridStereoDepthExtractor(work_dir=str(tmp_path / "w"), cache_dir=str(tmp_path / "w"), batch_size=8, stereo_only=True)
+    ex.backend.compute_batch_size = lambda W, H, req: 2
+    out = ex.process_video_sbs(path)
+    assert sorted(os.listdir(out)) == [f"depth_{i:06d}.png" for i in range(5)]
+    assert ex.last_pass_frames == 2 and ex.last_decoded_frames == 5
+    for i, f in enumerate(frames):
+        got = read_png16(out / f"depth_{i:06d}.png")
+        depth = ex.backend.sbs_to_disparity([f], True)
+        assert np.array_equal(got, ex.backend.normalise_u16(depth[0])), i
+        l, r = oracle.sbs_to_gray(f, True)
+        assert np.array_equal(got, oracle.depth_to_u16(oracle.disp_to_depth(oracle.sgbm_compute(l, r)))), i
+
+
 def test_cli_runs_on_gpu(native, tmp_path, clip, capsys):
     from video_3d_pipeline import depth, upscale
     path, _ = clip

@@ -19,12 +19,6 @@ class OraclePipelineBackend(OracleStereoBackend):
     def __init__(self):
         self.guided_batches = []
 
-    def depth_to_u16_batch(self, depth):
-        return np.stack([O.depth_to_u16(np.asarray(d, np.float32)) for d in depth])
-
-    def to_host_u16(self, u16):
-        return np.array(u16, np.uint16)
-
     def guide_luma(self, frames, height, width, capacity):
         assert len(frames) <= capacity
         return np.stack([np.full((height, width), 128, np.uint8) if f is None else (f if f.ndim == 2 else O.bgr_to_gray(f))

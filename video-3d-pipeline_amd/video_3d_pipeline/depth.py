@@ -20,6 +20,7 @@ falls back to stereo-only exactly like the reference does when loading fails (de
 import argparse
 import hashlib
 from collections import defaultdict
+from itertools import islice
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
@@ -68,6 +69,17 @@ class HipStereoBackend:
               "over-subscribed; recomputing this batch and continuing with one launch per direction")
         matcher.set_lockstep(False)
         return False
+
+    def _match(self, lg, rg, out=None):
+        """gray [n,H,W] pairs -> int16 disparity x16 [n,H,W]; a pass whose lock-step kernel timed out is computed again"""
+        n, H, W = lg.shape
+        matcher = self._get_matcher(W, H, n)
+        disp = matcher.compute(lg, rg, out)
+        if not self._lockstep_ok(matcher):
+            disp = matcher.compute(lg, rg, out)
+            if matcher.sync_errors():
+                raise RuntimeError("SGM kernels report time-outs with the lock-step pass off: device fault")
+        return disp
 
     def compute_batch_size(self, W: int, H: int, requested: int) -> int:
         """frames per device pass of the streaming path (process_video_sbs).  The caller's batch_size is list chunking
@@ -133,12 +145,7 @@ class HipStereoBackend:
         for i, (l, r) in enumerate(pairs):
             lg[i] = nat.bgr_to_gray(nat.to_device(l, self.device))
             rg[i] = nat.bgr_to_gray(nat.to_device(r, self.device))
-        matcher = self._get_matcher(W, H, n)
-        disp = matcher.compute(lg, rg)
-        if not self._lockstep_ok(matcher):
-            disp = matcher.compute(lg, rg)
-            if matcher.sync_errors():
-                raise RuntimeError("SGM kernels report time-outs with the lock-step pass off: device fault")
+        disp = self._match(lg, rg)
         if fill_holes:
             disp = self.fill_holes(disp)
         depth = self._depth_from(disp, monos)
@@ -174,12 +181,7 @@ class HipStereoBackend:
         lg = self._staging("lg", (n, H, ow), torch.uint8, False)
         rg = self._staging("rg", (n, H, ow), torch.uint8, False)
         nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
-        matcher = self._get_matcher(ow, H, n)
-        disp = matcher.compute(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False))
-        if not self._lockstep_ok(matcher):
-            disp = matcher.compute(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False))
-            if matcher.sync_errors():
-                raise RuntimeError("SGM kernels report time-outs with the lock-step pass off: device fault")
+        disp = self._match(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False))
         if fill_holes:
             disp = self.fill_holes(disp)
         monos = None
@@ -228,6 +230,11 @@ class HipStereoBackend:
         lohi = nat.temporal_range(mm, cut, radius, t0, n)
         filt = nat.temporal_filter_batch(depth, gray, radius, tau, cut, fill, t0, n)
         return nat.depth_to_u16_range_batch(filt, lohi)
+
+    def depth_to_u16_batch(self, depth):
+        """device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W], every frame against its own min and max:
+        frame f is what normalise_u16 gives for it alone"""
+        return self.native.depth_to_u16_batch(depth)
 
     def depth_to_u16_robust(self, depth, range_quantile):
         """--range-percentile without a radius: device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W], every
@@ -360,13 +367,32 @@ class HybridStereoDepthExtractor:
                 out.append(self.model(**inputs).predicted_depth[0].float())
         return out
 
-    def _stage_kw(self) -> dict:
-        """the keyword a disparity pass of the backend gains with --fill-holes; off: none, the call every backend knows"""
-        return {"fill_holes": True} if self.fill_holes else {}
+    def _disparity_pass(self, call, *args, guidance=None):
+        """the one way a disparity pass of the backend (sbs_to_disparity, pairs_to_disparity) is called: an option that is off
+        adds no argument -- no provider / monocular maps without guidance, no `fill_holes` keyword without --fill-holes -- so
+        it stays the call every backend knows"""
+        if guidance is not None:
+            args += (guidance,)
+        return call(*args, **({"fill_holes": True} if self.fill_holes else {}))
 
-    def _write_fill_side_file(self, cache_path: Path):
+    def manifest_extra(self) -> dict:
+        """what the options that are on add to the one-pass pipeline's manifest (none: nothing); write_side_files puts the
+        same entries next to the depth maps"""
+        from .temporal import manifest_entry
+        extra = {}
+        if self.temporal[0] > 0 or self.range_quantile < 10000:
+            extra["temporal"] = manifest_entry(*self.temporal, self.range_quantile)
         if self.fill_holes:
-            import json
+            extra["fill_holes"] = True
+        return extra
+
+    def write_side_files(self, cache_path: Path):
+        """temporal.json (a radius or the robust range is on) and fill.json (--fill-holes) of a depth map directory"""
+        import json
+        extra = self.manifest_extra()
+        if "temporal" in extra:
+            (cache_path / "temporal.json").write_text(json.dumps(extra["temporal"]))
+        if "fill_holes" in extra:
             (cache_path / "fill.json").write_text(json.dumps({"fill_holes": True}))
 
     def _guidance_provider(self):
@@ -455,8 +481,7 @@ class HybridStereoDepthExtractor:
                     monos = provider([np.ascontiguousarray(l[..., ::-1]) for l, _ in frame_pairs])     # left views as RGB (depth.py:274)
                 except Exception as e:                       # depth.py:367-369
                     print(f"    Warning: Neural guidance failed, using stereo only: {e}")
-            depth_maps = self.backend.pairs_to_disparity(frame_pairs, monos, **self._stage_kw()) if monos is not None \
-                else self.backend.pairs_to_disparity(frame_pairs, **self._stage_kw())
+            depth_maps = self._disparity_pass(self.backend.pairs_to_disparity, frame_pairs, guidance=monos)
         except Exception as e:
             print(f"Error processing frame batch: {e}")
             raise
@@ -491,167 +516,135 @@ class HybridStereoDepthExtractor:
 
         rank, world = sharding.rank_world()
         sharding.require_initialized(world)                  # WORLD_SIZE > 1 without a process group would race the cache dir
-        if self.temporal[0] > 0:
-            return self._process_video_temporal(video_path, start_frame, frame_count, video_info, cache_path, rank, world)
-        processed_count = 0
-        batch, batch_idx = [], []
-        # frames per device pass: decoupled from batch_size (which the reference only uses to chunk its frame list,
-        # depth.py:448-461) -- a pass fills one lock-step SGM launch whatever the caller's chunk size is
+        written = 0
+        # PNG compression (zlib) costs ~20 ms per 1080p map on one core, the GPU path 0.5 ms: the maps of a pass go to
+        # a bounded pool of writer threads and compress while the next pass is decoded and computed
+        with self.writer_pool_factory() as writers:
+            for idx, u16 in self.iter_depth_u16(video_path, start_frame, frame_count, video_info, rank, world):
+                self.submit_depth_maps(writers, cache_path, idx, u16)
+                written += len(idx)
+                print(f"✓ Queued batch depth maps ({written} on rank {rank})")
+        if sharding.total(written) == 0:
+            raise ValueError("No frames extracted from video")
+        if rank == 0:
+            self.write_side_files(cache_path)
+        sharding.barrier()
+
+        print(f"✓ Depth extraction complete: {cache_path}")
+        print(f"  Processed {written} frames")
+        print(f"  Output directory: {cache_path}")
+        return cache_path
+
+    def submit_depth_maps(self, writers, cache_path: Path, idx, u16):
+        """the u16 samples of frames idx -> depth_%06d.png through the writer pool.  Every map crosses in a pinned block of its
+        own, which goes back to the allocator once that map is written; a whole pass in one block stays pinned until its last
+        map is, and the next pass has to pin a second one (20 ms at 1080p)"""
+        to_host = getattr(self.backend, "to_host_u16", lambda planes: planes)     # per-frame surface only: they are NumPy already
+        for j, frame_idx in enumerate(idx):
+            writers.submit(cache_path / f"depth_{frame_idx:06d}.png", to_host(u16[j:j + 1])[0])
+
+    def pass_frames(self, video_info) -> int:
+        """frames per device pass: decoupled from batch_size (which the reference only uses to chunk its frame list,
+        depth.py:448-461) -- a pass fills one lock-step SGM launch whatever the caller's chunk size is"""
         ow = video_info['width'] if self.unsqueeze_sbs else video_info['width'] // 2
         sizer = getattr(self.backend, "compute_batch_size", None)
-        pass_frames = sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
-        self.last_pass_frames = pass_frames
-        provider = self._guidance_provider()
-        robust = self.range_quantile < 10000                 # --range-percentile: the batch's u16 samples come from the device
-        # PNG compression (zlib) costs ~20 ms per 1080p map on one core, the GPU path 0.5 ms: the maps of a batch go to
-        # a bounded pool of writer threads and compress while the next batch is decoded and computed
-        writers = self.writer_pool_factory()
+        return sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
 
-        def flush():
-            nonlocal processed_count
-            if not batch:
-                return
-            if provider is not None:
-                depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs, provider, **self._stage_kw())
-            else:
-                depth = self.backend.sbs_to_disparity(batch, self.unsqueeze_sbs, **self._stage_kw())
-            u16 = self.backend.to_host_u16(self.backend.depth_to_u16_robust(depth, self.range_quantile)) if robust else None
-            for j, frame_idx in enumerate(batch_idx):
-                writers.submit(cache_path / f"depth_{frame_idx:06d}.png", u16[j] if robust else self.backend.normalise_u16(depth[j]))
-                processed_count += 1
-            print(f"✓ Queued batch depth maps ({processed_count} on rank {rank})")
-            batch.clear()
-            batch_idx.clear()
-
-        # frame i -> rank i mod world (round-robin): every rank seeks to and decodes ONLY its own frames, so the decode
-        # (the scaling limiter once the kernels are fast) is divided by the world size, not replicated
-        decoded = 0
-        with writers:
-            for k, frame in enumerate(iter_frames(video_path, start_frame, frame_count, stride=world, offset=rank)):
-                decoded += 1
-                batch.append(frame)
-                batch_idx.append(rank + k * world)
-                if len(batch) == pass_frames:
-                    flush()
-            flush()
-        self.last_decoded_frames = decoded
-        if sharding.total(decoded) == 0:
-            raise ValueError("No frames extracted from video")
-        if robust and rank == 0:
-            import json
-            from .temporal import manifest_entry
-            (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal, self.range_quantile)))
-        if rank == 0:
-            self._write_fill_side_file(cache_path)
-        sharding.barrier()
-
-        print(f"✓ Depth extraction complete: {cache_path}")
-        print(f"  Processed {processed_count} frames")
-        print(f"  Output directory: {cache_path}")
-        return cache_path
-
-
-    def _process_video_temporal(self, video_path, start_frame, frame_count, video_info, cache_path, rank, world) -> Path:
-        """ process_video_sbs with --temporal-radius: each rank owns a contiguous block of frames and also decodes and matches
-        a halo of `radius` frames on each side (sharding.temporal_block); the u16 samples come from the streaming stabiliser,
-        `radius` frames behind the matcher """
-        import json
+    def frame_plan(self, frame_count: int, rank: int, world: int):
+        """(decoded, owned, block) of one rank: `decoded` is the iter_frames range (first, count, stride, offset), relative to
+        start_frame, that the rank decodes and matches, `owned` the range in the same form of the frames it writes.
+        Per frame, frame i goes to rank i mod world: every rank seeks to and decodes ONLY its own frames, so the decode (the
+        scaling limiter once the kernels are fast) is divided by the world size, not replicated; block is None.
+        With --temporal-radius round-robin frames have no neighbours: a rank owns a contiguous block and also decodes a halo of
+        `radius` frames on each side (sharding.temporal_block); block is BlockStabilizer's (first, count, halo_before)."""
         from . import sharding
-        from .temporal import BlockStabilizer, manifest_entry
+        if self.temporal[0] == 0:
+            share = (0, frame_count, world, rank)
+            return share, share, None
+        first, count, hb, ha = sharding.temporal_block(frame_count, rank, world, self.temporal[0])
+        return (first - hb, hb + count + ha, 1, 0), (first, count, 1, 0), (first, count, hb)
+
+    def iter_depth_u16(self, video_path, start_frame, frame_count, video_info, rank, world):
+        """The streaming driver of the depth CLI and the one-pass pipeline: decodes this rank's frames of the clip (frame_plan),
+        matches them a device pass at a time and yields (clip frame indices, the backend's u16 samples [n,H,W]) of the frames
+        the rank owns: per pass, or -- with --temporal-radius -- `radius` frames behind the matcher with the tail at the end."""
         be = self.backend
-        radius = self.temporal[0]
-        first, count, hb, ha = sharding.temporal_block(frame_count, rank, world, radius)
-        ow = video_info['width'] if self.unsqueeze_sbs else video_info['width'] // 2
-        sizer = getattr(be, "compute_batch_size", None)
-        pass_frames = sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
-        self.last_pass_frames = pass_frames
+        self.last_pass_frames = pass_frames = self.pass_frames(video_info)
+        (first, count, stride, offset), _, block = self.frame_plan(frame_count, rank, world)
+        stab = None
+        if block is not None:
+            from .temporal import BlockStabilizer
+            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile)
+        frames = iter_frames(video_path, start_frame + first, count, stride=stride, offset=offset) if count else iter(())
         provider = self._guidance_provider()
-        stab = BlockStabilizer(be, self.temporal, first, count, hb, self.range_quantile)
-        writers = self.writer_pool_factory()
-        processed_count = 0
-        batch = []
+        self.last_decoded_frames = 0
 
-        def write(idx, u16):
-            nonlocal processed_count
-            if not idx:
-                return
-            host = be.to_host_u16(u16)
-            for j, frame_idx in enumerate(idx):
-                writers.submit(cache_path / f"depth_{frame_idx:06d}.png", host[j])
-            processed_count += len(idx)
-            print(f"✓ Queued batch depth maps ({processed_count} on rank {rank})")
+        def staged():
+            """(indices, u16 samples) of what each pass completes; ([], None) when the stabiliser's window is not full yet"""
+            for batch in iter(lambda: list(islice(frames, pass_frames)), []):
+                k0 = self.last_decoded_frames
+                self.last_decoded_frames += len(batch)
+                depth = self._disparity_pass(be.sbs_to_disparity, batch, self.unsqueeze_sbs, guidance=provider)
+                if stab is not None:
+                    yield stab.push(depth, be.left_gray(len(batch)))
+                    continue
+                idx = [first + offset + k * stride for k in range(k0, k0 + len(batch))]
+                if self.range_quantile < 10000:          # --range-percentile: every frame against its own robust white point
+                    yield idx, be.depth_to_u16_robust(depth, self.range_quantile)
+                elif hasattr(be, "depth_to_u16_batch"):
+                    yield idx, be.depth_to_u16_batch(depth)
+                else:                                    # a backend with the per-frame surface only: the same samples, on the host
+                    yield idx, np.stack([be.normalise_u16(d) for d in depth])
+            if stab is not None:
+                yield stab.finish()
 
-        def flush():
-            if not batch:
-                return
-            if provider is not None:
-                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs, provider, **self._stage_kw())
-            else:
-                depth = be.sbs_to_disparity(batch, self.unsqueeze_sbs, **self._stage_kw())
-            write(*stab.push(depth, be.left_gray(len(batch))))
-            batch.clear()
-
-        decoded = 0
-        with writers:
-            if count:
-                for frame in iter_frames(video_path, start_frame + first - hb, hb + count + ha):
-                    decoded += 1
-                    batch.append(frame)
-                    if len(batch) == pass_frames:
-                        flush()
-                flush()
-                write(*stab.finish())
-        self.last_decoded_frames = decoded
-        if sharding.total(processed_count) == 0:
-            raise ValueError("No frames extracted from video")
-        if rank == 0:
-            (cache_path / "temporal.json").write_text(json.dumps(manifest_entry(*self.temporal, self.range_quantile)))
-        if rank == 0:
-            self._write_fill_side_file(cache_path)
-        sharding.barrier()
-
-        print(f"✓ Depth extraction complete: {cache_path}")
-        print(f"  Processed {processed_count} frames")
-        print(f"  Output directory: {cache_path}")
-        return cache_path
+        for idx, u16 in staged():
+            if idx:
+                yield idx, u16
 
 
 # run_pipeline.py:12,63 and reference __init__.py:6 import this name (SURVEY.md fact 0.4)
 IGEVStereoDepthExtractor = HybridStereoDepthExtractor
 
 
-def main(argv=None):
-    """ Command line interface for depth extraction """
-    parser = argparse.ArgumentParser(description='Extract depth maps from SBS stereoscopic video')
-    parser.add_argument('video', help='Path to SBS video file')
+def add_depth_arguments(parser, force_help: str):
+    """the options of the depth path, shared by the depth CLI and the one-pass pipeline (--force means something else in each)"""
+    from .temporal import add_fill_arguments, add_range_arguments, add_temporal_arguments
     parser.add_argument('--start-frame', type=int, default=0, help='Starting frame number (default: 0)')
     parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to process (default: all)')
     parser.add_argument('--batch-size', type=int, default=8, help='Batch size for GPU processing (default: 8)')
     parser.add_argument('--model', default="Intel/dpt-large", help='Neural model checkpoint (default: Intel/dpt-large)')
     parser.add_argument('--work-dir', default='temp_depth', help='Working directory for output (default: temp_depth)')
-    parser.add_argument('--force', action='store_true', help='Force reprocessing even if cached results exist')
+    parser.add_argument('--force', action='store_true', help=force_help)
     parser.add_argument('--device', default='cuda', help='Processing device (default: cuda)')
     parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
     parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
-    from .temporal import (add_fill_arguments, add_range_arguments, add_temporal_arguments, fill_options, range_options,
-                           temporal_options)
     add_temporal_arguments(parser)
     add_range_arguments(parser)
     add_fill_arguments(parser)
-    args = parser.parse_args(argv)
 
+
+def depth_options(args) -> dict:
+    """parsed add_depth_arguments -> the keyword arguments HybridStereoDepthExtractor and SbsTo4kDepthPipeline share"""
+    from .temporal import fill_options, range_options, temporal_options
     stereo_only = args.stereo_only or args.no_neural
-    use_neural_guidance = not stereo_only
-    unsqueeze_sbs = not args.no_unsqueeze
+    return dict(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device, batch_size=args.batch_size,
+                use_neural_guidance=not stereo_only, stereo_only=stereo_only, unsqueeze_sbs=not args.no_unsqueeze,
+                **temporal_options(args), **range_options(args), **fill_options(args))
+
+
+def main(argv=None):
+    """ Command line interface for depth extraction """
+    parser = argparse.ArgumentParser(description='Extract depth maps from SBS stereoscopic video')
+    parser.add_argument('video', help='Path to SBS video file')
+    add_depth_arguments(parser, 'Force reprocessing even if cached results exist')
+    args = parser.parse_args(argv)
 
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        extractor = HybridStereoDepthExtractor(
-            model_checkpoint=args.model, work_dir=args.work_dir, cache_dir=args.work_dir, device=args.device,
-            batch_size=args.batch_size, use_neural_guidance=use_neural_guidance, stereo_only=stereo_only,
-            unsqueeze_sbs=unsqueeze_sbs, **temporal_options(args), **range_options(args), **fill_options(args))
+        extractor = HybridStereoDepthExtractor(cache_dir=args.work_dir, **depth_options(args))
         output_path = extractor.process_video_sbs(video_path=args.video, start_frame=args.start_frame,
                                                   max_frames=args.max_frames, force_reprocess=args.force)
         print(f"\n✓ Success! Depth maps saved to: {output_path}")

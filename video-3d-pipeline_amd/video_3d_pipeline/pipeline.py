@@ -13,14 +13,15 @@ and through zlib twice before the 4K filter sees it.  Here the depth stays on th
                -> [--keep-depth-maps: depth_%06d.png into the depth CLI's cache directory]
                -> v3d_guided_upscale_u16_batch against the matching 4K frames' luma -> u16 4K samples -> writer pool
 
-The only lossy step between the two CLIs is the u16 quantisation of the normalised depth; it happens here on the device and
+Everything up to the u16 samples is the depth CLI's own driver (HybridStereoDepthExtractor.iter_depth_u16), so the depth maps
+of the two are the same by construction.  The only lossy step between the two CLIs is the u16 quantisation of the normalised depth; it happens here on the device and
 the filter reads the same u16 samples `read_png16(...).astype(float32)` gives the upscale CLI, so every output PNG is
 byte-for-byte what the two CLIs write.  The two-step route stays the reference for this one.
 """
 import argparse
 from pathlib import Path
 
-from .depth import HipStereoBackend, HybridStereoDepthExtractor
+from .depth import HipStereoBackend, HybridStereoDepthExtractor, add_depth_arguments, depth_options
 from .upscale import GUIDED_EPS, GUIDED_RADIUS, encode_depth4k
 from .utils import PngWriterPool, get_video_info, iter_frames
 
@@ -31,13 +32,8 @@ GUIDE_BATCH = 8
 
 
 class HipPipelineBackend(HipStereoBackend):
-    """HipStereoBackend plus the device steps after the disparity: normalisation, guide luma, guided filter, copies out."""
-
-    def depth_to_u16_batch(self, depth):
-        """device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W]"""
-        return self.native.depth_to_u16_batch(depth)
-
-    # to_host_u16 (device u16 -> NumPy through pinned memory) is HipStereoBackend's: the depth CLI's temporal path uses it too
+    """HipStereoBackend (which has the u16 samples and their copy to the host: the depth CLI needs them too) plus the device
+    steps after them: guide luma, guided filter, stereo rendering."""
 
     def guide_luma(self, frames, height, width, capacity):
         """4K BGR frames (None = beyond the clip: flat 128) -> device luma [n,height,width].  The frames are gathered in one
@@ -166,30 +162,14 @@ class SbsTo4kDepthPipeline:
         sharding.require_initialized(world)
         frames_dir = Path(str(output_path.with_suffix("")) + "_frames")
         frames_dir.mkdir(parents=True, exist_ok=True)
-        ow = video_info['width'] if ex.unsqueeze_sbs else video_info['width'] // 2
-        sizer = getattr(be, "compute_batch_size", None)
-        pass_frames = sizer(ow, video_info['height'], ex.batch_size) if sizer else ex.batch_size
-        self.last_pass_frames = pass_frames
-        gb = min(self.guide_batch, pass_frames)
-        provider = ex._guidance_provider()
-        # frame i -> rank i mod world; each rank decodes only its own frames of BOTH clips (4K frame g0 + i guides SBS frame i)
+        # the extractor's frame plan: frame i -> rank i mod world, or -- with temporal stabilisation -- a contiguous block per
+        # rank plus a halo of SBS frames that is decoded and matched but not written.  Each rank decodes only its own frames
+        # of BOTH clips: the 4K guides are the frames it owns (4K frame g0 + i guides SBS frame i)
         g0 = max(int(guide_start_frame), 0)
-        stab = None
-        robust = ex.range_quantile < 10000
-        if ex.temporal[0] > 0:
-            # temporal stabilisation: a contiguous block per rank plus a halo of `radius` SBS frames on each side that is
-            # decoded and matched but not written; the 4K guides are the block's own frames only
-            from .temporal import BlockStabilizer
-            first, count, hb, ha = sharding.temporal_block(frame_count, rank, world, ex.temporal[0])
-            stab = BlockStabilizer(be, ex.temporal, first, count, hb, ex.range_quantile)
-            guides = iter_frames(video_4k, g0 + first, count) if count else iter(())
-            sbs_frames = iter_frames(sbs_video, start_frame + first - hb, hb + count + ha) if count else iter(())
-        else:
-            guides = iter_frames(video_4k, g0, frame_count, stride=world, offset=rank)
-            sbs_frames = iter_frames(sbs_video, start_frame, frame_count, stride=world, offset=rank)
+        first, count, stride, offset = ex.frame_plan(frame_count, rank, world)[1]
+        guides = iter_frames(video_4k, g0 + first, count, stride=stride, offset=offset) if count else iter(())
         guide_state = {"delivered": 0, "ended": False}
         flat = written = 0
-        batch, batch_idx = [], []
 
         def next_guide():
             if guide_state["ended"]:
@@ -203,32 +183,13 @@ class SbsTo4kDepthPipeline:
             guide_state["delivered"] += 1
             return f
 
-        def flush(writers):
-            if not batch:
-                return
-            if provider is not None:
-                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, provider, **ex._stage_kw())
-            else:
-                depth = be.sbs_to_disparity(batch, ex.unsqueeze_sbs, **ex._stage_kw())
-            if stab is None and robust:
-                emit(writers, list(batch_idx), be.depth_to_u16_robust(depth, ex.range_quantile))
-            elif stab is None:
-                emit(writers, list(batch_idx), be.depth_to_u16_batch(depth))
-            else:
-                emit(writers, *stab.push(depth, be.left_gray(len(batch))))
-            batch.clear()
-            batch_idx.clear()
-
         def emit(writers, out_idx, u16):
             """the u16 depth samples of frames out_idx -> [depth PNGs,] guided filter, 4K PNGs [, stereo frames]"""
             nonlocal flat, written
-            if not out_idx:
-                return
             written += len(out_idx)
+            gb = min(self.guide_batch, ex.last_pass_frames)         # the driver has sized the pass before its first yield
             if keep_depth_maps:
-                lo = be.to_host_u16(u16)
-                for j, i in enumerate(out_idx):
-                    writers.submit(cache_path / f"depth_{i:06d}.png", lo[j])
+                ex.submit_depth_maps(writers, cache_path, out_idx, u16)
             for j0 in range(0, len(out_idx), gb):
                 idx = out_idx[j0:j0 + gb]
                 frames = [next_guide() for _ in idx]
@@ -245,18 +206,10 @@ class SbsTo4kDepthPipeline:
                             stereo["count"] += 1
             print(f"✓ Queued {len(out_idx)} 4K depth maps (rank {rank})")
 
-        decoded = 0
         with self.writer_pool_factory() as writers:
-            for k, frame in enumerate(sbs_frames):
-                decoded += 1
-                batch.append(frame)
-                batch_idx.append(rank + k * world)
-                if len(batch) == pass_frames:
-                    flush(writers)
-            flush(writers)
-            if stab is not None:
-                emit(writers, *stab.finish())
-        self.last_decoded_frames = decoded
+            for idx, u16 in ex.iter_depth_u16(sbs_video, start_frame, frame_count, video_info, rank, world):
+                emit(writers, idx, u16)
+        self.last_pass_frames, self.last_decoded_frames = ex.last_pass_frames, ex.last_decoded_frames
         self.last_flat_guides = flat
         n = sharding.total(written)
         if n == 0:
@@ -264,17 +217,9 @@ class SbsTo4kDepthPipeline:
         n_stereo = sharding.total(stereo["count"]) if stereo is not None else 0
         sharding.barrier()
         if rank == 0:
-            from .temporal import manifest_entry
-            entry = manifest_entry(*ex.temporal, ex.range_quantile) if stab is not None or robust else None
-            extra = {"temporal": entry} if entry else {}
-            if ex.fill_holes:
-                extra["fill_holes"] = True
-            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, extra or None)
-            if entry and keep_depth_maps:
-                import json
-                (cache_path / "temporal.json").write_text(json.dumps(entry))
+            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, ex.manifest_extra() or None)
             if keep_depth_maps:
-                ex._write_fill_side_file(cache_path)
+                ex.write_side_files(cache_path)
             if stereo is not None and n_stereo:
                 from .convert import finish_stereo_output, write_clip_info
                 write_clip_info(stereo["dir"], fps)
@@ -293,16 +238,7 @@ def main(argv=None):
     parser.add_argument('video', help='Path to SBS video file')
     parser.add_argument('video_4k', help='Path to 4K 2D video (dimensions and guide frames)')
     parser.add_argument('--output', help='Output path for 4K depth video')
-    parser.add_argument('--start-frame', type=int, default=0, help='Starting frame number (default: 0)')
-    parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to process (default: all)')
-    parser.add_argument('--batch-size', type=int, default=8, help='Batch size for GPU processing (default: 8)')
-    parser.add_argument('--model', default="Intel/dpt-large", help='Neural model checkpoint (default: Intel/dpt-large)')
-    parser.add_argument('--work-dir', default='temp_depth', help='Working directory for output (default: temp_depth)')
-    parser.add_argument('--force', action='store_true', help='Force reprocessing even if the output exists')
-    parser.add_argument('--device', default='cuda', help='Processing device (default: cuda)')
-    parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
-    parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
-    parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
+    add_depth_arguments(parser, 'Force reprocessing even if the output exists')
     guide = parser.add_mutually_exclusive_group()
     guide.add_argument('--guide-start-frame', type=int, default=0,
                        help='4K frame that matches the first SBS frame (alignment offset in frames; default 0)')
@@ -314,12 +250,7 @@ def main(argv=None):
     parser.add_argument('--stereo-output', default=None,
                         help='Also render side-by-side 3D to this path (what the convert CLI makes from the depth output)')
     from .convert import add_stereo_arguments, stereo_options
-    from .temporal import (add_fill_arguments, add_range_arguments, add_temporal_arguments, fill_options, range_options,
-                           temporal_options)
     add_stereo_arguments(parser)
-    add_temporal_arguments(parser)
-    add_range_arguments(parser)
-    add_fill_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -329,14 +260,10 @@ def main(argv=None):
             print(f"Error: {e}")
             return 1
         print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
-    stereo_only = args.stereo_only or args.no_neural
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        pipe = SbsTo4kDepthPipeline(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device,
-                                    batch_size=args.batch_size, use_neural_guidance=not stereo_only, stereo_only=stereo_only,
-                                    unsqueeze_sbs=not args.no_unsqueeze, **temporal_options(args), **range_options(args),
-                                    **fill_options(args))
+        pipe = SbsTo4kDepthPipeline(**depth_options(args))
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,
