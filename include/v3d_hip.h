@@ -28,6 +28,8 @@
  *   v3d_depth_robust_minmax_batch  no call site in the reference either: opt-in percentile white point of that normalisation
  *   v3d_fill_holes_disp16_batch  no call site in the reference (depth.py:374 turns every invalid disparity into depth 0): opt-in
  *                          filling of the matcher's invalid pixels from their scanline neighbours, before /16
+ *   v3d_png_*              depth.py:397-406 save_depth_map writes 16-bit PNGs through cv2.imwrite (zlib on the host): opt-in
+ *                          deflate of the final u16 / BGR frames on the device, the host only adds the PNG chunks
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -323,6 +325,38 @@ int v3d_depth_robust_minmax_batch(const float* depth, int T, size_t frame_elems,
 size_t v3d_fill_holes_ws_bytes(int n, int H);
 int v3d_fill_holes_disp16_batch(const int16_t* disp16, size_t disp_stride /* elements */, int n, int W, int H,
                                 int16_t* out /* dense [n][H][W] */, void* ws, void* stream);
+
+/* GPU PNG encoding (v3d_png.hip): an opt-in sink stage.  The device turns each final frame into a complete zlib stream
+   (RFC 1950 / 1951) whose payload is byte for byte the filtered image the host encoder hands to zlib -- per scanline the byte 1
+   (filter "sub") and the samples minus the sample one pixel to the left, gray16 big-endian, BGR8 in RGB order -- and the host
+   wraps signature, IHDR, one IDAT with its CRC-32 and IEND around it (utils.png_from_stream).  Bit-exact contract:
+   tests/png_ref.py.  Stream: 78 01; per scanline one deflate block (BFINAL = 0) and an empty stored block (000, zero bits to
+   the byte boundary, 00 00 FF FF), so every scanline is coded on its own and ends on a byte boundary; then 01 00 00 FF FF and
+   the Adler-32 of the payload, big-endian.  Tokens of a scanline of RL = 1 + bpp*W bytes: literals and matches at the single
+   distance bpp (2 or 3): with m[i] = i >= bpp && raw[i] == raw[i - bpp], a maximal run of L true positions is L / 258 matches of
+   258 and, for r = L % 258, one match if r >= 3, else r literals.  The block is coded with the cheapest (header + codes,
+   ties to the lowest index) of the constant code books of csrc/v3d_png_books.h (tools/make_png_books.py); book 0 is deflate's
+   fixed code, which spends at most 9 bits per payload byte, so a scanline takes at most ceil(9*RL/8) + 8 bytes and
+     v3d_png_stream_bound(fmt, W, H) = 2 + H * (ceil(9*RL/8) + 8) + 9,
+     v3d_png_out_bytes(fmt, n, W, H) = n * (that bound rounded up to 16).
+   img: frame f at (const char*)img + f*frame_stride (BYTES), rows dense; V3D_PNG_GRAY16: uint16 [H][W], 2-byte alignment;
+   V3D_PNG_BGR8: uint8 [H][W][3], any alignment.  out: frame f's stream starts at out[offsets[f]], offsets[0] = 0 and every offset
+   is a multiple of 16 (each stream's size rounded up); offsets[n] is the used size; EVERY byte of out up to v3d_png_out_bytes is
+   written: what lies between the streams and behind the last one is zero.  A stream's own size is not stored: it closes with
+   01 00 00 FF FF and four Adler bytes in front of zero padding, so it ends at the one position e in (offsets[f+1] - 16,
+   offsets[f+1]] with out[e-9 .. e-5] = 01 00 00 FF FF (utils.png_stream_end).  A frame's bytes do not depend on n, on its place
+   in the batch or on the stride.  offsets: uint64 [n+1], 8-byte aligned.  ws: device scratch of v3d_png_ws_bytes bytes (one
+   fixed slot per scanline, row sizes and Adler sums), 16-byte aligned.  Enqueues four launches on `stream`, never synchronises,
+   never allocates.  V3D_ERR_ARG: null pointer, n outside [1, 65535], W or H < 1, unknown fmt, frame_stride below a frame with
+   n > 1, a misaligned ws, offsets or gray16 image; V3D_ERR_UNSUPPORTED: W > 8192 or H > 65535.  The three size functions return
+   0 for arguments the entry refuses. */
+#define V3D_PNG_GRAY16 0
+#define V3D_PNG_BGR8   1
+size_t v3d_png_stream_bound(int fmt, int W, int H);
+size_t v3d_png_out_bytes(int fmt, int n, int W, int H);
+size_t v3d_png_ws_bytes(int fmt, int n, int W, int H);
+int v3d_png_deflate_batch(const void* img, size_t frame_stride /* bytes */, int fmt, int n, int W, int H,
+                          uint8_t* out, uint64_t* offsets /* [n+1] */, void* ws, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

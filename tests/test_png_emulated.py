@@ -1,0 +1,82 @@
+"""csrc/v3d_png.hip itself, without a GPU: the kernel source is compiled as plain C++ against tests/png_emu/v3d_common.h, where
+the 256 threads of a workgroup are fibers and barriers / wave shuffles are rendezvous, and v3d_png_deflate_batch is called on
+poisoned host buffers at the alignments the header grants.  `out` and `offsets` must equal tests/png_ref.py byte for byte --
+streams, zero gaps, zero tail --, nothing outside `out`, `offsets` and `ws` may change, and every 16-byte load must be aligned.
+This checks the kernels' arithmetic and indexing; what only the device can show (LDS atomics, real wave scheduling, speed) is
+left to tests/test_png_gpu.py and tests/test_png_guard_gpu.py."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import png_ref as P
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "video-3d-pipeline_amd", "csrc")
+EMU = os.path.join(ROOT, "tests", "png_emu")
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "a host C++ compiler is needed (the oracle's Makefile needs one as well)"
+    d = tmp_path_factory.mktemp("png_emu")
+    text = open(os.path.join(CSRC, "v3d_png.hip")).read()
+    decl = "extern __shared__ __attribute__((aligned(16))) uint8_t smem[];"
+    assert text.count(decl) == 1
+    (d / "v3d_png.cpp").write_text(text.replace(decl, "extern uint8_t smem[];"))       # the harness defines it, 16-byte aligned
+    for name, src in (("v3d_png_books.h", CSRC), ("v3d_common.h", EMU), ("harness.cpp", EMU)):
+        shutil.copy(os.path.join(src, name), d / name)
+    lib = d / "libpngemu.so"
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-o", str(lib),
+                           str(d / "v3d_png.cpp"), str(d / "harness.cpp")])
+    L = C.CDLL(str(lib))
+    L.v3d_png_out_bytes.restype = L.v3d_png_ws_bytes.restype = C.c_size_t
+    L.v3d_png_deflate_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_int] * 4 + [C.c_void_p] * 4
+    return L
+
+
+def _buf(nbytes, skew, poison):
+    """nbytes at 256 k + skew inside a poisoned block -> (block, view)"""
+    block = np.full(nbytes + 1024, poison, np.uint8)
+    off = (-block.ctypes.data) % 256 + 256 + skew
+    return block, block[off:off + nbytes]
+
+
+# fmt, W, H, n, frame padding (elements), skew of img / out (bytes), poison
+CASES = [(P.GRAY16, 1, 1, 3, 7, 2, 1, 0xA5), (P.GRAY16, 127, 5, 3, 7, 2, 1, 0xFF), (P.GRAY16, 129, 2, 2, 0, 0, 0, 0xA5),
+         (P.BGR8, 1, 2, 1, 0, 1, 3, 0xFF), (P.BGR8, 85, 4, 3, 7, 1, 1, 0xA5), (P.BGR8, 86, 4, 2, 16, 5, 7, 0xFF),
+         (P.GRAY16, 1001, 5, 2, 7, 6, 9, 0xA5), (P.BGR8, 2731, 2, 1, 0, 3, 1, 0xA5), (P.GRAY16, 8192, 2, 1, 0, 2, 1, 0xFF),
+         (P.GRAY16, 64, 300, 2, 3, 2, 5, 0xA5)]
+
+
+@pytest.mark.parametrize("fmt,W,H,n,pad,skew_img,skew_out,poison", CASES,
+                         ids=[f"{'g16' if c[0] == 0 else 'bgr'}-{c[1]}x{c[2]}x{c[3]}" for c in CASES])
+def test_kernel_source_equals_the_reference(emu, fmt, W, H, n, pad, skew_img, skew_out, poison):
+    frames = [P.content_image(fmt, W, H, 3 * W + f) for f in range(n)]
+    want, want_off, _ = P.batch(frames, fmt)
+    item = 2 if fmt == P.GRAY16 else 1
+    per = frames[0].size * item
+    stride = per + pad * item
+    bi, img = _buf(n * stride, skew_img, poison)
+    for f in range(n):
+        img[f * stride:f * stride + per] = frames[f].reshape(-1).view(np.uint8)
+    nout = emu.v3d_png_out_bytes(fmt, n, W, H)
+    assert nout == want.size
+    bo, out = _buf(nout, skew_out, poison)
+    bw, ws = _buf(emu.v3d_png_ws_bytes(fmt, n, W, H), 16, poison)
+    bf, off = _buf(8 * (n + 1), 8, poison)
+    before = [b.copy() for b in (bi, bo, bw, bf)]
+    loads = emu.emu_misaligned_loads()
+    assert emu.v3d_png_deflate_batch(img.ctypes.data, stride, fmt, n, W, H, out.ctypes.data, off.ctypes.data, ws.ctypes.data, None) == 0
+    assert emu.emu_misaligned_loads() == loads, "a 16-byte load off its alignment"
+    assert np.array_equal(off.view(np.uint64), want_off)
+    bad = np.flatnonzero(out != want)
+    assert bad.size == 0, f"{bad.size} bytes differ, first at {int(bad[0])}"
+    assert np.array_equal(bi, before[0]), "the input was written"
+    for block, snap, view in ((bo, before[1], out), (bw, before[2], ws), (bf, before[3], off)):
+        lo = view.ctypes.data - block.ctypes.data
+        assert np.array_equal(block[:lo], snap[:lo]) and np.array_equal(block[lo + view.size:], snap[lo + view.size:]), "a store outside its buffer"

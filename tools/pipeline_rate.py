@@ -62,6 +62,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=68)
     ap.add_argument("--work", default="/tmp/pipeline_rate")
+    ap.add_argument("--png-encoder", nargs="+", choices=["zlib", "gpu"], default=["zlib"],
+                    help="PNG sink once per listed encoder, alternating in this one process (the raw sink always uses zlib's path)")
     args = ap.parse_args()
     from video_3d_pipeline import synthetic as syn
     from video_3d_pipeline.depth import HybridStereoDepthExtractor
@@ -81,14 +83,15 @@ def main():
     del sbs, g
 
     out = {"frames": N, "sbs": f"{W}x{H}", "guide": f"{2 * W}x{2 * H}", "kernels": kernel_times(W, H)}
-    for sink_name, sink in (("raw", RawSink), ("png", PngWriterPool)):
+    sinks = [("raw", RawSink, "zlib")] + [("png" if e == "zlib" else "png_gpu", PngWriterPool, e) for e in args.png_encoder]
+    for sink_name, sink, enc in sinks:
         with contextlib.redirect_stdout(io.StringIO()):
             ex = HybridStereoDepthExtractor(work_dir=os.path.join(args.work, "w"), cache_dir=os.path.join(args.work, "w"),
-                                            stereo_only=True, batch_size=34)
+                                            stereo_only=True, batch_size=34, png_encoder=enc)
             ex.writer_pool_factory = sink
-            up = SimpleDepthUpscaler()
+            up = SimpleDepthUpscaler(png_encoder=enc)
             up.writer_pool_factory = sink
-            pipe = SbsTo4kDepthPipeline(work_dir=os.path.join(args.work, "w"), stereo_only=True, batch_size=34)
+            pipe = SbsTo4kDepthPipeline(work_dir=os.path.join(args.work, "w"), stereo_only=True, batch_size=34, png_encoder=enc)
             pipe.writer_pool_factory = sink
             times = {}
             for rep in ("warm", "timed"):

@@ -32,6 +32,7 @@ EXPORTS = (
     "v3d_depth_to_u16_range_batch",
     "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
     "v3d_fill_holes_ws_bytes", "v3d_fill_holes_disp16_batch",
+    "v3d_png_stream_bound", "v3d_png_out_bytes", "v3d_png_ws_bytes", "v3d_png_deflate_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -142,6 +143,13 @@ def lib():
         L.v3d_fill_holes_ws_bytes.argtypes = [ci, ci]
         L.v3d_fill_holes_ws_bytes.restype = sz
         L.v3d_fill_holes_disp16_batch.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp]
+        L.v3d_png_stream_bound.argtypes = [ci, ci, ci]
+        L.v3d_png_stream_bound.restype = sz
+        L.v3d_png_out_bytes.argtypes = [ci, ci, ci, ci]
+        L.v3d_png_out_bytes.restype = sz
+        L.v3d_png_ws_bytes.argtypes = [ci, ci, ci, ci]
+        L.v3d_png_ws_bytes.restype = sz
+        L.v3d_png_deflate_batch.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -748,6 +756,44 @@ def fill_holes_disp16_batch(disp, out=None, ws=None):
         _check(lib().v3d_fill_holes_disp16_batch(d, ds, n, W, H, o, _dev(ws, torch.uint8, "ws"), _stream()),
                "v3d_fill_holes_disp16_batch")
     return out
+
+
+PNG_GRAY16, PNG_BGR8 = 0, 1          # V3D_PNG_GRAY16 / V3D_PNG_BGR8
+PNG_MAX_WIDTH, PNG_MAX_HEIGHT = 8192, 65535
+
+
+def png_deflate_batch(frames, out=None, offsets=None, ws=None):
+    """final frames on the device -> one zlib stream per frame (v3d_png_deflate_batch; bit-exact contract: tests/png_ref.py).
+    frames: int16 [n,H,W] holding uint16 bit patterns (16-bit gray) or uint8 [n,H,W,3] in BGR order (written as RGB); frames dense,
+    only the frame stride may differ.  Returns (out uint8 [v3d_png_out_bytes], offsets int64 [n+1]) on the device: frame f's
+    stream starts at out[offsets[f]], offsets[n] is the used size (utils.png_stream_end finds a stream's last byte).  out / offsets
+    / ws: a caller's buffers of at least the sizes the library states; None takes them from the caching allocator."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise NativeError("frames: expected a device tensor")
+    if frames.dtype == torch.int16 and frames.dim() == 3:
+        fmt, item, (n, H, W) = PNG_GRAY16, 2, frames.shape
+        dense = frames.stride(2) == 1 and frames.stride(1) == W
+    elif frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3:
+        fmt, item, (n, H, W, _) = PNG_BGR8, 1, frames.shape
+        dense = frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) == 3 * W
+    else:
+        raise NativeError(f"frames: expected int16 [n,H,W] or uint8 [n,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+    if not dense or min(n, H, W) < 1:
+        raise NativeError("frames: frames must be dense, non-empty images (only the frame stride may differ)")
+    L = lib()
+    need_out, need_ws = L.v3d_png_out_bytes(fmt, n, W, H), L.v3d_png_ws_bytes(fmt, n, W, H)
+    if not need_out:
+        raise NativeError(f"png_deflate_batch: {n} frames of {W}x{H} are outside the encoder's range (W <= {PNG_MAX_WIDTH}, H and n <= {PNG_MAX_HEIGHT})")
+    dev = frames.device
+    out = torch.empty(need_out, dtype=torch.uint8, device=dev) if out is None else out
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets is None else offsets
+    ws = torch.empty(need_ws, dtype=torch.uint8, device=dev) if ws is None else ws
+    if out.numel() < need_out or ws.numel() < need_ws or offsets.numel() < n + 1:
+        raise NativeError(f"png_deflate_batch: out / ws / offsets of {out.numel()} / {ws.numel()} / {offsets.numel()}, need {need_out} / {need_ws} / {n + 1}")
+    with torch.cuda.device(dev):
+        _check(L.v3d_png_deflate_batch(C.c_void_p(frames.data_ptr()), frames.stride(0) * item, fmt, n, W, H, _dev(out, torch.uint8, "out"),
+                                       _dev(offsets, torch.int64, "offsets"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_png_deflate_batch")
+    return out, offsets
 
 
 def to_device(a, device="cuda"):

@@ -137,7 +137,7 @@ class HipRenderBackend:
             self._bufs[key] = t
         return t
 
-    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None):
+    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, png=False):
         """NumPy BGR frames [H,W,3] + u16 depth maps [H,W] -> NumPy u8 [n,H,outW,3].  The input staging holds `capacity`
         frames and is reused (the synchronise at the end of the previous call made that safe); the output block comes from
         torch's caching host allocator and returns to it once the writers drop the last frame of it."""
@@ -159,10 +159,19 @@ class HipRenderBackend:
             fd[:n].copy_(fh[:n], non_blocking=True)
             dd[:n].copy_(dh[:n], non_blocking=True)
             nat.render_stereo_batch(fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n])
+            if png:
+                return od[:n]
             host = torch.empty((n, H, oW, 3), dtype=torch.uint8, pin_memory=True)
             host.copy_(od[:n], non_blocking=True)
             torch.cuda.current_stream().synchronize()
         return host.numpy()
+
+    def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None):
+        """--png-encoder gpu: render_batch whose frames stay on the device and come back as the zlib streams of their PNGs"""
+        if getattr(self, "_png", None) is None:
+            from .png_gpu import DevicePngEncoder
+            self._png = DevicePngEncoder(self.torch, self.native, self.device)
+        return self._png.encode(self.render_batch(frames, depths, gain_left, gain_right, conv, layout, capacity, png=True))
 
 
 class DepthTo3DConverter:
@@ -172,8 +181,11 @@ class DepthTo3DConverter:
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
-                 batch_size: int = CONVERT_BATCH):
-        """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests)"""
+                 batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib"):
+        """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
+        png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads"""
+        from .png_gpu import check_png_encoder
+        self.png_encoder = check_png_encoder(png_encoder)
         self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout)
         self.params = dict(max_shift=max_shift, convergence=convergence, eye_split=eye_split, layout=layout)
         if backend is None:
@@ -195,6 +207,7 @@ class DepthTo3DConverter:
         """depth frame i pairs with 4K frame guide_start_frame + i (the offset the upscale CLI used).  Returns the output
         path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
         from . import sharding
+        from .png_gpu import rgb8_file
         print(f"4K + depth -> 3D ({self.params['layout']}): {video_4k_path} + {depth_path}")
         depth_files = depth_frame_files(depth_path)
         info = get_video_info(video_4k_path)
@@ -226,9 +239,14 @@ class DepthTo3DConverter:
             nonlocal rendered
             if not batch_f:
                 return
-            out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size)
+            if self.png_encoder == "gpu":                        # deflated on the device: only the streams cross PCIe
+                out = self.backend.render_batch_png(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size)
+                encode = rgb8_file(2 * W if self.layout_code == LAYOUTS["full-sbs"] else W, H)
+            else:
+                out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size)
+                encode = png_rgb_from_bgr
             for j, i in enumerate(batch_i):
-                writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=png_rgb_from_bgr)
+                writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)
             rendered += len(batch_i)
             batch_f.clear()
             batch_d.clear()
@@ -278,6 +296,8 @@ def main(argv=None, backend=None):
     parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to render (default: all)')
     parser.add_argument('--force', action='store_true', help='Force reprocessing even if the output exists')
     parser.add_argument('--device', default='cuda', help='Processing device (default: cuda)')
+    from .png_gpu import add_png_arguments, png_options
+    add_png_arguments(parser)
     guide = parser.add_mutually_exclusive_group()
     guide.add_argument('--guide-start-frame', type=int, default=0,
                        help='4K frame that matches depth frame 0 (the offset the upscale CLI used; default 0)')
@@ -296,7 +316,7 @@ def main(argv=None, backend=None):
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args))
+        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args))
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)

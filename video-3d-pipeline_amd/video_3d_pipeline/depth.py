@@ -252,6 +252,17 @@ class HipStereoBackend:
         torch.cuda.current_stream().synchronize()
         return host.numpy().view(np.uint16)
 
+    def png_streams_u16(self, u16):
+        """--png-encoder gpu: device u16 samples (int16-viewed) [n,H,W] -> the zlib streams of their 16-bit PNGs, deflated on
+        the device (png_gpu.DevicePngEncoder); only the streams cross PCIe"""
+        return self._png_encoder().encode(u16)
+
+    def _png_encoder(self):
+        if getattr(self, "_png", None) is None:
+            from .png_gpu import DevicePngEncoder
+            self._png = DevicePngEncoder(self.torch, self.native, self.device)
+        return self._png
+
 
 class HybridStereoDepthExtractor:
     """ GPU-accelerated depth extraction from SBS video using hybrid stereo matching + neural guidance """
@@ -276,7 +287,8 @@ class HybridStereoDepthExtractor:
                  temporal_cut: int = 20,
                  temporal_fill: bool = True,
                  range_percentile: float = 100.0,
-                 fill_holes: bool = False):
+                 fill_holes: bool = False,
+                 png_encoder: str = "zlib"):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
@@ -284,7 +296,11 @@ class HybridStereoDepthExtractor:
         range_percentile < 100 (process_video_sbs only): the white point of the 16-bit normalisation is that percentile of the
         valid disparities instead of the maximum; 100 = the reference's min-max.
         fill_holes (every surface, process_frame_batch included: it is per frame): the matcher's invalid pixels are filled from
-        their scanline neighbours on the int16 disparity, before /16 and everything after it; off = they stay depth 0 """
+        their scanline neighbours on the int16 disparity, before /16 and everything after it; off = they stay depth 0
+        png_encoder (process_video_sbs only): "gpu" deflates the 16-bit maps on the device (png_gpu.py); "zlib" = on the writer
+        threads, as ever """
+        from .png_gpu import check_png_encoder
+        self.png_encoder = check_png_encoder(png_encoder)
         from .temporal import check_parameters, check_range_percentile
         self.temporal = check_parameters(temporal_radius, temporal_tau, temporal_cut, temporal_fill)
         self.range_quantile = check_range_percentile(range_percentile)
@@ -539,6 +555,12 @@ class HybridStereoDepthExtractor:
         """the u16 samples of frames idx -> depth_%06d.png through the writer pool.  Every map crosses in a pinned block of its
         own, which goes back to the allocator once that map is written; a whole pass in one block stays pinned until its last
         map is, and the next pass has to pin a second one (20 ms at 1080p)"""
+        if self.png_encoder == "gpu":                 # the pass is deflated on the device; the writers wrap and write
+            from .png_gpu import gray16_file
+            wrap = gray16_file(u16.shape[2], u16.shape[1])
+            for frame_idx, stream in zip(idx, self.backend.png_streams_u16(u16)):
+                writers.submit(cache_path / f"depth_{frame_idx:06d}.png", stream, encode=wrap)
+            return
         to_host = getattr(self.backend, "to_host_u16", lambda planes: planes)     # per-frame surface only: they are NumPy already
         for j, frame_idx in enumerate(idx):
             writers.submit(cache_path / f"depth_{frame_idx:06d}.png", to_host(u16[j:j + 1])[0])
@@ -609,6 +631,7 @@ IGEVStereoDepthExtractor = HybridStereoDepthExtractor
 
 def add_depth_arguments(parser, force_help: str):
     """the options of the depth path, shared by the depth CLI and the one-pass pipeline (--force means something else in each)"""
+    from .png_gpu import add_png_arguments
     from .temporal import add_fill_arguments, add_range_arguments, add_temporal_arguments
     parser.add_argument('--start-frame', type=int, default=0, help='Starting frame number (default: 0)')
     parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to process (default: all)')
@@ -623,15 +646,17 @@ def add_depth_arguments(parser, force_help: str):
     add_temporal_arguments(parser)
     add_range_arguments(parser)
     add_fill_arguments(parser)
+    add_png_arguments(parser)
 
 
 def depth_options(args) -> dict:
     """parsed add_depth_arguments -> the keyword arguments HybridStereoDepthExtractor and SbsTo4kDepthPipeline share"""
+    from .png_gpu import png_options
     from .temporal import fill_options, range_options, temporal_options
     stereo_only = args.stereo_only or args.no_neural
     return dict(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device, batch_size=args.batch_size,
                 use_neural_guidance=not stereo_only, stereo_only=stereo_only, unsqueeze_sbs=not args.no_unsqueeze,
-                **temporal_options(args), **range_options(args), **fill_options(args))
+                **temporal_options(args), **range_options(args), **fill_options(args), **png_options(args))
 
 
 def main(argv=None):

@@ -65,16 +65,25 @@ class HipPipelineBackend(HipStereoBackend):
         """--stereo-output: the 4K BGR frames guide_luma left in its device staging + their u16 4K depth [n,Hhi,Whi] (device)
         -> NumPy side-by-side frames [n,Hhi,outW,3]: one launch, one D2H, no second H2D of the 4K frames.  Slots of frames
         that had no 4K frame hold stale data; the caller drops them."""
+        torch = self.torch
+        out = self._render_stereo_dev(u16_4k, gains, layout)
+        host = torch.empty(tuple(out.shape), dtype=torch.uint8, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host.numpy()
+
+    def _render_stereo_dev(self, u16_4k, gains, layout):
         torch, nat = self.torch, self.native
         n, H, W = u16_4k.shape
         dev = self._bufs["guide_dev"]
         oW = 2 * W if layout == 0 else W
         out = self._staging("stereo_dev", (dev.shape[0], H, oW, 3), torch.uint8, False)
         nat.render_stereo_batch(dev[:n], u16_4k.contiguous(), *gains, layout, out[:n])
-        host = torch.empty((n, H, oW, 3), dtype=torch.uint8, pin_memory=True)
-        host.copy_(out[:n], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return host.numpy()
+        return out[:n]
+
+    def render_stereo_png(self, u16_4k, gains, layout):
+        """--png-encoder gpu: render_stereo whose frames stay on the device and come back as the zlib streams of their PNGs"""
+        return self._png_encoder().encode(self._render_stereo_dev(u16_4k, gains, layout))
 
 
 class SbsTo4kDepthPipeline:
@@ -100,11 +109,13 @@ class SbsTo4kDepthPipeline:
                  temporal_cut: int = 20,
                  temporal_fill: bool = True,
                  range_percentile: float = 100.0,
-                 fill_holes: bool = False):
+                 fill_holes: bool = False,
+                 png_encoder: str = "zlib"):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own);
         range_percentile: the depth CLI's robust white point (100 = off: the maximum);
-        fill_holes: the depth CLI's hole filling of the int16 disparity (off: invalid pixels stay depth 0)"""
+        fill_holes: the depth CLI's hole filling of the int16 disparity (off: invalid pixels stay depth 0);
+        png_encoder: "gpu" deflates every PNG this run writes on the device (png_gpu.py); "zlib" = on the writer threads"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -115,7 +126,8 @@ class SbsTo4kDepthPipeline:
             model_checkpoint=model_checkpoint, work_dir=work_dir, cache_dir=work_dir, device=device, batch_size=batch_size,
             use_neural_guidance=use_neural_guidance, stereo_only=stereo_only, unsqueeze_sbs=unsqueeze_sbs, backend=backend,
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
-            temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes)
+            temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes,
+            png_encoder=png_encoder)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
 
@@ -128,7 +140,9 @@ class SbsTo4kDepthPipeline:
         depth (the files the convert CLI writes from this run's depth output); stereo_options: max_shift, convergence,
         eye_split, layout (convert.py's defaults)."""
         from . import sharding
+        from .png_gpu import gray16_file, rgb8_file
         ex, be = self.extractor, self.backend
+        gpu_png = ex.png_encoder == "gpu"
         stereo = None
         if stereo_output is not None:
             from .convert import png_rgb_from_bgr, sibling_frames_dir, stereo_settings
@@ -195,14 +209,22 @@ class SbsTo4kDepthPipeline:
                 frames = [next_guide() for _ in idx]
                 flat += sum(f is None for f in frames)
                 q_dev = be.guided_upscale_u16(u16[j0:j0 + len(idx)], be.guide_luma(frames, Hhi, Whi, gb), self.radius, self.eps)
-                q = be.to_host_u16(q_dev)
-                for j, i in enumerate(idx):
-                    writers.submit(frames_dir / f"depth4k_{i:06d}.png", q[j])
+                if gpu_png:                                        # deflated on the device: only the streams cross PCIe
+                    for i, s in zip(idx, be.png_streams_u16(q_dev)):
+                        writers.submit(frames_dir / f"depth4k_{i:06d}.png", s, encode=gray16_file(Whi, Hhi))
+                else:
+                    q = be.to_host_u16(q_dev)
+                    for j, i in enumerate(idx):
+                        writers.submit(frames_dir / f"depth4k_{i:06d}.png", q[j])
                 if stereo is not None and any(f is not None for f in frames):
-                    sbs3d = be.render_stereo(q_dev, stereo["gains"], stereo["layout"])
+                    if gpu_png:
+                        sbs3d = be.render_stereo_png(q_dev, stereo["gains"], stereo["layout"])
+                        encode = rgb8_file(2 * Whi if stereo["layout"] == 0 else Whi, Hhi)
+                    else:
+                        sbs3d, encode = be.render_stereo(q_dev, stereo["gains"], stereo["layout"]), png_rgb_from_bgr
                     for j, i in enumerate(idx):
                         if frames[j] is not None:                   # no 4K frame: no stereo frame (its slot is stale)
-                            writers.submit(stereo["dir"] / f"frame_{i:06d}.png", sbs3d[j], encode=png_rgb_from_bgr)
+                            writers.submit(stereo["dir"] / f"frame_{i:06d}.png", sbs3d[j], encode=encode)
                             stereo["count"] += 1
             print(f"✓ Queued {len(out_idx)} 4K depth maps (rank {rank})")
 

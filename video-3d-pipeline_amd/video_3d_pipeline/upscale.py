@@ -71,6 +71,14 @@ class HipUpscaleBackend:
         # v3d_round_to_u16: the uint16 bit pattern leaves the device as 2 bytes per pixel
         return self.native.round_to_u16(q.contiguous()).cpu().numpy().view(np.uint16)
 
+    def upscale_png(self, depth_lo, guide, r, eps):
+        """--png-encoder gpu: upscale_u16 whose samples stay on the device and come back as the zlib stream of their PNG"""
+        if getattr(self, "_png", None) is None:
+            from .png_gpu import DevicePngEncoder
+            self._png = DevicePngEncoder(self.torch, self.native, self.device)
+        q = self.upscale(depth_lo, guide, r, eps)
+        return self._png.encode(self.native.round_to_u16(q.contiguous())[None])[0]
+
     def flat_guide(self, h, w):
         return self.torch.full((h, w), 128, dtype=self.torch.uint8, device=self.device)
 
@@ -81,7 +89,10 @@ class SimpleDepthUpscaler:
     writer_pool_factory = PngWriterPool       # sink of the 4K 16-bit maps (see HybridStereoDepthExtractor.writer_pool_factory)
 
     def __init__(self, use_nvenc: bool = True, radius: int = GUIDED_RADIUS, eps: float = GUIDED_EPS,
-                 device: str = "cuda", backend=None):
+                 device: str = "cuda", backend=None, png_encoder: str = "zlib"):
+        """png_encoder: "gpu" deflates the 4K maps on the device (png_gpu.py); "zlib" = on the writer threads"""
+        from .png_gpu import check_png_encoder
+        self.png_encoder = check_png_encoder(png_encoder)
         self.use_nvenc = use_nvenc
         self.radius, self.eps = radius, eps
         self.backend = backend if backend is not None else HipUpscaleBackend(device)
@@ -99,6 +110,7 @@ class SimpleDepthUpscaler:
         guide_start_frame: index of the 4K frame that belongs to depth_000000 -- the alignment offset that
         run_pipeline.py:45-50 computes and then drops; round(offset_seconds * fps), clamped at 0. """
         from . import sharding
+        from .png_gpu import gray16_file
 
         print(f"Processing depth upscaling...")
         print(f"Input: {depth_dir}")
@@ -191,6 +203,10 @@ class SimpleDepthUpscaler:
                     flat += 1
                     guide = self.backend.flat_guide(target_height, target_width)    # beyond the 4K clip: flat guide == plain smoothing upsample
                 d16 = next(my_depth).astype(np.float32)
+                if self.png_encoder == "gpu":
+                    writers.submit(frames_dir / f"depth4k_{i:06d}.png", self.backend.upscale_png(d16, guide, self.radius, self.eps),
+                                   encode=gray16_file(target_width, target_height))
+                    continue
                 writers.submit(frames_dir / f"depth4k_{i:06d}.png", self.backend.upscale_u16(d16, guide, self.radius, self.eps))
         self.last_flat_guides = flat
         if rank == 0 and guides is not None and n_hint is not None and decoded[0] > n_hint:
@@ -235,8 +251,8 @@ class SimpleDepthUpscaler:
         return result
 
 
-def main(argv=None):
-    """ Command line interface for depth upscaling """
+def main(argv=None, backend=None):
+    """ Command line interface for depth upscaling (backend: a stand-in for host tests) """
     parser = argparse.ArgumentParser(description='Depth upscaling to the 4K frame (guided filter)')
     parser.add_argument('depth_dir', help='Directory containing depth maps')
     parser.add_argument('video_4k', help='Path to 4K 2D video (dimensions and guide frames)')
@@ -249,6 +265,8 @@ def main(argv=None):
     guide.add_argument('--alignment-file', default=None,
                        help='alignment_data.json of the audio aligner: --guide-start-frame = '
                             'round(time_offset_seconds * fps of the 4K clip)')
+    from .png_gpu import add_png_arguments, png_options
+    add_png_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -261,7 +279,7 @@ def main(argv=None):
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        upscaler = SimpleDepthUpscaler(use_nvenc=not args.no_nvenc)
+        upscaler = SimpleDepthUpscaler(use_nvenc=not args.no_nvenc, backend=backend, **png_options(args))
         output_path = upscaler.process_depth_upscaling(depth_dir=args.depth_dir, video_4k_path=args.video_4k,
                                                        output_path=args.output, force_reprocess=args.force,
                                                        guide_start_frame=args.guide_start_frame)

@@ -310,6 +310,31 @@ def encode_png8(img: np.ndarray, level: int = 1, bgr: bool = False) -> bytes:
             + chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + chunk(b"IEND", b""))
 
 
+def png_from_stream(stream, w: int, h: int, bit_depth: int, colour_type: int) -> bytes:
+    """the PNG file around a ready zlib stream of the filtered image (the device's, _native.png_deflate_batch): signature, IHDR,
+    one IDAT with its CRC-32, IEND.  zlib.crc32 releases the GIL on a buffer of this size, so the writer threads run it in
+    parallel; it costs a few ms per 4K frame where deflate cost 80."""
+    import struct
+    import zlib
+    body = memoryview(stream)
+    ihdr = b"IHDR" + struct.pack(">IIBBBBB", w, h, bit_depth, colour_type, 0, 0, 0)
+    crc = zlib.crc32(body, zlib.crc32(b"IDAT")) & 0xFFFFFFFF
+    return b"".join((b"\x89PNG\r\n\x1a\n", struct.pack(">I", 13), ihdr, struct.pack(">I", zlib.crc32(ihdr) & 0xFFFFFFFF),
+                     struct.pack(">I", len(body)), b"IDAT", body, struct.pack(">I", crc),
+                     b"\x00\x00\x00\x00IEND\xaeB`\x82"))
+
+
+def png_stream_end(buf, lo: int, hi: int) -> int:
+    """where the zlib stream that starts at buf[lo] ends, given the next stream's start `hi` (a multiple of 16 past lo, the
+    bytes between zero): v3d_png_deflate_batch stores no sizes, but a stream closes with 01 00 00 FF FF and four Adler bytes, and
+    of the 16 candidate ends only the true one has that marker 9 bytes before it (include/v3d_hip.h)."""
+    tail = bytes(buf[max(hi - 25, lo):hi])
+    for e in range(len(tail), max(len(tail) - 16, 8), -1):      # paddings of 0 .. 15 bytes; the marker needs e >= 9
+        if tail[e - 9:e - 4] == b"\x01\x00\x00\xff\xff":
+            return hi - len(tail) + e
+    raise ValueError("no zlib trailer in the last 16 bytes of the stream's slot")
+
+
 class PngWriterPool:
     """Bounded pool of PNG writer threads: submit() returns at once unless `max_pending` images are already queued
     (back-pressure keeps host memory flat), close() waits for all of them and re-raises the first failure.  The
