@@ -30,6 +30,8 @@
  *                          filling of the matcher's invalid pixels from their scanline neighbours, before /16
  *   v3d_png_*              depth.py:397-406 save_depth_map writes 16-bit PNGs through cv2.imwrite (zlib on the host): opt-in
  *                          deflate of the final u16 / BGR frames on the device, the host only adds the PNG chunks
+ *   v3d_frame_signature_batch, v3d_signature_scores  no call site in the reference (align.py rounds the audio offset to a frame and
+ *                          nothing checks the pairing): opt-in frame-accurate matching of SBS frames and 4K frames
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -357,6 +359,31 @@ size_t v3d_png_out_bytes(int fmt, int n, int W, int H);
 size_t v3d_png_ws_bytes(int fmt, int n, int W, int H);
 int v3d_png_deflate_batch(const void* img, size_t frame_stride /* bytes */, int fmt, int n, int W, int H,
                           uint8_t* out, uint64_t* offsets /* [n+1] */, void* ws, void* stream);
+
+/* Frame matching (v3d_framematch.hip): a compact signature per luma plane and the exact integer correlation of signatures, for
+   pairing SBS frames with 4K frames (framematch.py: the align CLI's --refine-video, the pipeline's --check-guide).  No call site
+   in the reference (it trusts the rounded audio offset, align.py).  Bit-exact contract, all integers: tests/framematch_ref.py.
+   Signature: frame f at gray + f*frame_stride (bytes), rows `pitch` bytes apart, only the W payload bytes of a row are read.
+   The plane is cut into a grid of 64 x 36 cells RELATIVE to its size, so planes of different sizes give comparable cells:
+     cell (cy, cx) = rows [floor(cy*H/36), floor((cy+1)*H/36)) x columns [floor(cx*W/64), floor((cx+1)*W/64));
+     sig[cy*64 + cx] = floor(256 * S / c), S the sum of the cell's bytes, c its pixel count (the mean in 8.8 fixed point).
+   Domain 64 <= W <= 8192, 36 <= H <= 8192 (else V3D_ERR_UNSUPPORTED): then 1 <= c <= 128 * 228, 256 * 255 * c < 2^31 and
+   sig <= 65280.  sig_out dense uint16 [n][2304].  V3D_ERR_ARG: null pointer, n outside [1, 65535], pitch < W, frame_stride <
+   H*pitch with n > 1.
+   Scores of na x nb signatures, with G = 2304 and 64-bit integer sums (every term <= 2304^2 * 65280^2 < 2.3e16 < 2^63):
+     num[i][j] = G * sum(a_i * b_j) - sum(a_i) * sum(b_j);   var_a[i] = G * sum(a_i^2) - (sum a_i)^2;   var_b likewise.
+   The host forms the zero-mean normalised correlation Z = num / sqrt((double)var_a * (double)var_b); a pair with a zero variance
+   (a flat frame) has none.  Z does not change under a gain or an offset of either plane.  V3D_ERR_ARG: null pointer, na or nb
+   outside [1, 4096].  Both entries enqueue one launch on `stream`, never synchronise, never allocate, take device pointers only
+   and write nothing outside their outputs. */
+#define V3D_SIG_GW 64
+#define V3D_SIG_GH 36
+#define V3D_SIG_CELLS 2304
+int v3d_frame_signature_batch(const uint8_t* gray, int n, int W, int H, int pitch, size_t frame_stride,
+                              uint16_t* sig_out /* dense [n][2304] */, void* stream);
+int v3d_signature_scores(const uint16_t* sig_a, int na, const uint16_t* sig_b, int nb,
+                         int64_t* num_out /* [na][nb] */, int64_t* var_a_out /* [na] */, int64_t* var_b_out /* [nb] */,
+                         void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

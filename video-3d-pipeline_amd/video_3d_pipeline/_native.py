@@ -33,6 +33,7 @@ EXPORTS = (
     "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
     "v3d_fill_holes_ws_bytes", "v3d_fill_holes_disp16_batch",
     "v3d_png_stream_bound", "v3d_png_out_bytes", "v3d_png_ws_bytes", "v3d_png_deflate_batch",
+    "v3d_frame_signature_batch", "v3d_signature_scores",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -150,6 +151,8 @@ def lib():
         L.v3d_png_ws_bytes.argtypes = [ci, ci, ci, ci]
         L.v3d_png_ws_bytes.restype = sz
         L.v3d_png_deflate_batch.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp, vp]
+        L.v3d_frame_signature_batch.argtypes = [vp, ci, ci, ci, ci, sz, vp, vp]
+        L.v3d_signature_scores.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -794,6 +797,45 @@ def png_deflate_batch(frames, out=None, offsets=None, ws=None):
         _check(L.v3d_png_deflate_batch(C.c_void_p(frames.data_ptr()), frames.stride(0) * item, fmt, n, W, H, _dev(out, torch.uint8, "out"),
                                        _dev(offsets, torch.int64, "offsets"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_png_deflate_batch")
     return out, offsets
+
+
+SIG_GW, SIG_GH, SIG_CELLS = 64, 36, 2304      # V3D_SIG_GW / V3D_SIG_GH / V3D_SIG_CELLS
+SIG_MIN_WIDTH, SIG_MIN_HEIGHT, SIG_MAX_SIDE, SIG_MAX_COUNT = 64, 36, 8192, 4096
+
+
+def frame_signature_batch(gray, out=None):
+    """luma planes u8 [n,H,W] on the device (frames dense HxW, only the frame stride may differ) -> their signatures, the
+    64 x 36 cell means in 8.8 fixed point as uint16 bit patterns in an int16 [n,2304] tensor (v3d_frame_signature_batch;
+    bit-exact contract: tests/framematch_ref.py).  out: a caller's [n,2304] int16 tensor (a slice of a resident table)."""
+    g, gs = _clip(gray, torch.uint8, "gray")
+    n, H, W = gray.shape
+    if out is None:
+        out = torch.empty((n, SIG_CELLS), dtype=torch.int16, device=gray.device)
+    if tuple(out.shape) != (n, SIG_CELLS):
+        raise NativeError(f"out: expected shape {(n, SIG_CELLS)}, got {tuple(out.shape)}")
+    with torch.cuda.device(gray.device):
+        _check(lib().v3d_frame_signature_batch(g, n, W, H, W, gs, _dev(out, torch.int16, "sig"), _stream()),
+               "v3d_frame_signature_batch")
+    return out
+
+
+def signature_scores(sig_a, sig_b):
+    """signatures [na,2304] and [nb,2304] (int16-viewed uint16, device) -> (num int64 [na,nb], var_a int64 [na], var_b int64
+    [nb]) on the device: the integer numerator and variances of the zero-mean normalised correlation (v3d_signature_scores);
+    framematch.zncc divides them on the host."""
+    for t, what in ((sig_a, "sig_a"), (sig_b, "sig_b")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != SIG_CELLS or t.shape[0] < 1:
+            raise NativeError(f"{what}: expected an int16 [n,{SIG_CELLS}] device tensor")
+    na, nb = sig_a.shape[0], sig_b.shape[0]
+    dev = sig_a.device
+    num = torch.empty((na, nb), dtype=torch.int64, device=dev)
+    va = torch.empty(na, dtype=torch.int64, device=dev)
+    vb = torch.empty(nb, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().v3d_signature_scores(_dev(sig_a, torch.int16, "sig_a"), na, _dev(sig_b, torch.int16, "sig_b"), nb,
+                                          _dev(num, torch.int64, "num"), _dev(va, torch.int64, "var_a"), _dev(vb, torch.int64, "var_b"),
+                                          _stream()), "v3d_signature_scores")
+    return num, va, vb
 
 
 def to_device(a, device="cuda"):

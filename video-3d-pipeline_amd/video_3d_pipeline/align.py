@@ -5,6 +5,10 @@ cross-correlation and the peak search run in libv3d_hip (v3d_align_audio).  Ever
 impossible -- a missing file, no audio track, no decoder, a silent track, differing sample rates -- is detected before
 the first GPU call and raised as a RuntimeError that names --skip-alignment.  No correlation plot is drawn (the
 reference's plot_audio_correlation needs matplotlib, which this package does not require).
+
+Optional second step, not in the reference: --refine-video matches frames of the two clips on the device around the rounded audio
+offset and --video-only does so without an audio step (framematch.py); alignment_data.json then also carries guide_start_frame,
+which guide_start_frame_from prefers.
 """
 import argparse
 import json
@@ -105,6 +109,45 @@ class VideoAligner:
         print(f"Alignment data saved to: {alignment_file}")
         return alignment_data
 
+    def video_only_data(self) -> Dict:
+        """--video-only: the reference's ten keys without an audio step; what only the audio gives is null"""
+        self.video1_info = self._info(self.video1_path)
+        self.video2_info = self._info(self.video2_path)
+        return {
+            'video1_path': str(self.video1_path),
+            'video2_path': str(self.video2_path),
+            'time_offset_seconds': None,
+            'offset_frames': None,
+            'correlation_strength': None,
+            'frame_duration': 1.0 / self.video1_info['fps'],
+            'video1_fps': self.video1_info['fps'],
+            'video2_fps': self.video2_info['fps'],
+            'sample_rate': None,
+            'audio_length_analyzed': None
+        }
+
+    def refine_video(self, alignment_data: Dict, seed: int, seed_audio: Optional[int], backend=None, **options) -> Dict:
+        """Match frames around the seed (framematch.refine: signatures and their correlation on the GPU), add the visual keys
+        to alignment_data and write alignment_data.json again.  The ten keys of the audio step stay as they are."""
+        from .framematch import alignment_keys, refine
+        print(f"Refining the guide start frame around {seed} by frame matching (GPU signatures)...")
+        res = refine(self.video1_path, self.video2_path, seed, backend=backend, **options)
+        alignment_data.update(alignment_keys(res, seed_audio))
+        score = "n/a" if res["score"] is None else f"{res['score']:.4f}"
+        margin = "n/a" if res["margin"] is None else f"{res['margin']:.4f}"
+        print(f"Video refinement: {res['status']}, shift {res['shift']:+d} frames (best {res['best_shift']:+d}, score {score}, "
+              f"margin {margin}, probe shifts {res['probe_shifts']}); guide start frame {alignment_data['guide_start_frame']}")
+        if res["status"] == "inconsistent":
+            print("Warning: the probes disagree (differing cuts or drift between the clips); the seed is kept")
+        elif res["status"] == "undetermined":
+            print("Warning: the frames do not decide the shift (static or flat scene, too few informative frames); the seed is kept")
+        self.work_dir = create_work_directory(str(self.work_dir))
+        alignment_file = self.work_dir / 'alignment_data.json'
+        with open(alignment_file, 'w') as f:
+            json.dump(alignment_data, f, indent=2)
+        print(f"Alignment data saved to: {alignment_file}")
+        return alignment_data
+
     def assess_alignment_quality(self, alignment_data: Dict, tolerance_frames: float = 2.0) -> str:
         """Assess alignment quality and provide recommendations."""
         return assess_alignment_quality(alignment_data, tolerance_frames)
@@ -170,24 +213,35 @@ def load_alignment_data(alignment_file: str) -> Dict:
 
 
 def guide_start_frame_from(alignment_file: str, video_4k: str) -> int:
-    """--alignment-file of the upscale / pipeline CLIs: the 4K frame that matches the first SBS frame,
+    """--alignment-file of the upscale / pipeline CLIs: the 4K frame that matches the first SBS frame: the file's
+    guide_start_frame when it has one (--refine-video / --video-only wrote it), else
     round(time_offset_seconds * fps of the 4K clip).  A negative offset (the 4K clip starts later) is not clamped:
     ValueError naming the SBS --start-frame that compensates, round(-offset * video1_fps)."""
     data = load_alignment_data(alignment_file)
+    if data.get('guide_start_frame') is not None:
+        g = int(data['guide_start_frame'])
+        if g < 0:
+            raise ValueError(_negative_start_advice(alignment_file, f"{-g} frames", -g))
+        return g
     offset = float(data['time_offset_seconds'])
     info = get_video_info(video_4k)
     if not info or not info.get("fps"):
         raise ValueError(f"could not read the frame rate of {video_4k}")
     if offset < 0:
         sbs_fps = float(data.get('video1_fps') or info['fps'])
-        raise ValueError(f"{alignment_file}: the 4K clip starts {-offset:.3f}s after the SBS clip (negative offset); "
-                         f"start the SBS side at --start-frame {int(round(-offset * sbs_fps))} and pass "
-                         f"--guide-start-frame 0 instead of --alignment-file")
+        raise ValueError(_negative_start_advice(alignment_file, f"{-offset:.3f}s", int(round(-offset * sbs_fps))))
     return int(round(offset * float(info['fps'])))
 
 
-def main(argv=None):
-    """Command line interface for fast audio-only alignment."""
+def _negative_start_advice(alignment_file, by: str, start_frame: int) -> str:
+    return (f"{alignment_file}: the 4K clip starts {by} after the SBS clip (negative offset); "
+            f"start the SBS side at --start-frame {start_frame} and pass "
+            f"--guide-start-frame 0 instead of --alignment-file")
+
+
+def main(argv=None, backend=None):
+    """Command line interface for fast audio-only alignment (+ optional frame matching on the GPU).  backend: a stand-in for
+    the refinement's HipPipelineBackend (host-logic tests)."""
     parser = argparse.ArgumentParser(description='Fast audio-only video alignment (GPU FFT cross-correlation)')
     parser.add_argument('video1', help='Path to first video (reference)')
     parser.add_argument('video2', help='Path to second video (to be aligned)')
@@ -195,10 +249,23 @@ def main(argv=None):
     parser.add_argument('--max-audio', type=float, default=300.0, help='Maximum audio length for analysis (seconds)')
     parser.add_argument('--tolerance', type=float, default=2.0, help='Alignment tolerance in frame intervals')
     parser.add_argument('--min-correlation', type=float, default=0.6, help='Minimum correlation to proceed')
+    from .framematch import add_refine_arguments, refine_options
+    add_refine_arguments(parser)
     args = parser.parse_args(argv)
     try:
         aligner = VideoAligner(args.video1, args.video2, args.work_dir)
+        if args.video_only:
+            data = aligner.refine_video(aligner.video_only_data(), args.guide_start_frame, None, backend, **refine_options(args))
+            print(f"\n✓ Video-only alignment: {data['visual_status']}, guide start frame {data['guide_start_frame']}")
+            return 0
         alignment_data = aligner.find_alignment(args.max_audio)
+        if args.refine_video:
+            offset = alignment_data['time_offset_seconds']
+            if offset < 0:
+                raise ValueError(_negative_start_advice("--refine-video", f"{-offset:.3f}s",
+                                                        int(round(-offset * float(alignment_data['video1_fps'])))))
+            seed = int(round(offset * float(alignment_data['video2_fps'])))
+            aligner.refine_video(alignment_data, seed, seed, backend, **refine_options(args))
         quality = aligner.assess_alignment_quality(alignment_data, args.tolerance)
         if alignment_data['correlation_strength'] < args.min_correlation:
             print(f"\nWarning: Correlation {alignment_data['correlation_strength']:.3f} below threshold {args.min_correlation}")

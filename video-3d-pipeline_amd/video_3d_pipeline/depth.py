@@ -197,6 +197,53 @@ class HipStereoBackend:
                 print(f"    Warning: Neural guidance failed, using stereo only: {e}")
         return self._depth_from(disp, None, out)
 
+    # ---- frame matching (framematch.py; only called by --check-guide and the align CLI's video refinement) ----
+    def frame_signatures(self, gray):
+        """device luma planes u8 [n,H,W] -> their signatures [n,2304] on the device (v3d_frame_signature_batch)"""
+        return self.native.frame_signature_batch(gray)
+
+    def sbs_left_signatures(self, frames: List[np.ndarray], unsqueeze: bool):
+        """SBS BGR frames -> the signatures of their left views: the staging and the gray split of sbs_to_disparity, no matcher"""
+        torch, nat = self.torch, self.native
+        n = len(frames)
+        H, W = frames[0].shape[:2]
+        ow = W if unsqueeze else W // 2
+        host = self._staging("sbs_host", (n, H, W, 3), torch.uint8, True)
+        hview = host.numpy()
+        for i, f in enumerate(frames):
+            hview[i] = f
+        dev = self._staging("sbs_dev", (n, H, W, 3), torch.uint8, False)
+        dev.copy_(host, non_blocking=True)
+        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
+        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
+        nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
+        return nat.frame_signature_batch(lg)
+
+    def signature_scores(self, sig_a, sig_b):
+        """signatures [na,2304] x [nb,2304] on the device -> a handle for read_scores: one v3d_signature_scores call, then the
+        three small integer arrays go to pinned memory without blocking; an event marks the end of the copies"""
+        torch = self.torch
+        host = []
+        for t in self.native.signature_scores(sig_a, sig_b):
+            h = torch.empty(tuple(t.shape), dtype=torch.int64, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            host.append(h)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev
+
+    def guide_scores(self, rows, luma):
+        """--check-guide: the kept signature rows of a batch's left views x the signatures of its 4K luma -> a read_scores handle"""
+        return self.signature_scores(self.torch.stack(list(rows)), self.native.frame_signature_batch(luma))
+
+    def read_scores(self, handle):
+        """-> (num [na,nb], var_a [na], var_b [nb]) int64 NumPy.  After the stream's next synchronise the event has fired and
+        nothing waits here"""
+        host, ev = handle
+        if not ev.query():
+            ev.synchronize()
+        return tuple(h.numpy().copy() for h in host)
+
     def depth_to_host(self, depth) -> np.ndarray:
         """device float32 [n,H,W] -> NumPy through a pinned buffer"""
         host = self._staging("depth_host", tuple(depth.shape), self.torch.float32, True)
@@ -333,6 +380,7 @@ class HybridStereoDepthExtractor:
         self.model = None
         self.processor = None
         self.mono_provider = mono_provider
+        self.guide_check = None                  # framematch.GuideChecker of the one-pass pipeline's --check-guide
         self.model_loaded = False
         self.max_vram_usage = 0.9
         self.memory_stats = defaultdict(float)
@@ -400,6 +448,8 @@ class HybridStereoDepthExtractor:
             extra["temporal"] = manifest_entry(*self.temporal, self.range_quantile)
         if self.fill_holes:
             extra["fill_holes"] = True
+        if self.guide_check is not None and self.guide_check.summary is not None:
+            extra["guide_match"] = self.guide_check.summary
         return extra
 
     def write_side_files(self, cache_path: Path):
@@ -607,6 +657,8 @@ class HybridStereoDepthExtractor:
                 k0 = self.last_decoded_frames
                 self.last_decoded_frames += len(batch)
                 depth = self._disparity_pass(be.sbs_to_disparity, batch, self.unsqueeze_sbs, guidance=provider)
+                if self.guide_check is not None:         # --check-guide: the pass's left gray planes are valid until the next pass
+                    self.guide_check.note_left([first + offset + k * stride for k in range(k0, k0 + len(batch))], be.left_gray(len(batch)))
                 if stab is not None:
                     yield stab.push(depth, be.left_gray(len(batch)))
                     continue

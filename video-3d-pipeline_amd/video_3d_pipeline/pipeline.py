@@ -57,6 +57,17 @@ class HipPipelineBackend(HipStereoBackend):
                 luma[i].fill_(128)                              # beyond the 4K clip: flat guide, as upscale.py does
         return luma[:n]
 
+    def guide_signatures(self, frames, height, width):
+        """4K BGR frames -> their luma signatures [n,2304] on the device (the align CLI's video refinement): guide_luma's staging,
+        GUIDE_BATCH frames at a time; the pinned buffer is free again once a chunk's copy has finished"""
+        torch = self.torch
+        out = torch.empty((len(frames), self.native.SIG_CELLS), dtype=torch.int16, device=self.device)
+        for j0 in range(0, len(frames), GUIDE_BATCH):
+            chunk = frames[j0:j0 + GUIDE_BATCH]
+            self.native.frame_signature_batch(self.guide_luma(chunk, height, width, GUIDE_BATCH), out[j0:j0 + len(chunk)])
+            torch.cuda.current_stream().synchronize()
+        return out
+
     def guided_upscale_u16(self, u16, luma, r, eps):
         """device u16 depth samples [n,H,W] + device luma [n,Hhi,Whi] -> device u16 4K samples [n,Hhi,Whi]"""
         return self.native.guided_upscale_u16_batch(u16, luma, r, eps)
@@ -110,12 +121,15 @@ class SbsTo4kDepthPipeline:
                  temporal_fill: bool = True,
                  range_percentile: float = 100.0,
                  fill_holes: bool = False,
-                 png_encoder: str = "zlib"):
+                 png_encoder: str = "zlib",
+                 check_guide: bool = False,
+                 check_guide_min: float = 0.5):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own);
         range_percentile: the depth CLI's robust white point (100 = off: the maximum);
         fill_holes: the depth CLI's hole filling of the int16 disparity (off: invalid pixels stay depth 0);
-        png_encoder: "gpu" deflates every PNG this run writes on the device (png_gpu.py); "zlib" = on the writer threads"""
+        png_encoder: "gpu" deflates every PNG this run writes on the device (png_gpu.py); "zlib" = on the writer threads;
+        check_guide: score every (left view, 4K frame) pair the run uses (framematch.GuideChecker); no output PNG changes"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -130,6 +144,7 @@ class SbsTo4kDepthPipeline:
             png_encoder=png_encoder)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
+        self.check_guide, self.check_guide_min = bool(check_guide), float(check_guide_min)
 
     def run(self, sbs_video: str, video_4k: str, output_path: str = None, start_frame: int = 0, max_frames: int = None,
             guide_start_frame: int = 0, force_reprocess: bool = False, keep_depth_maps: bool = False,
@@ -174,6 +189,11 @@ class SbsTo4kDepthPipeline:
 
         rank, world = sharding.rank_world()
         sharding.require_initialized(world)
+        check = ex.guide_check = None
+        if self.check_guide:
+            from .framematch import GuideChecker
+            # round-robin sharding leaves a rank every world-th frame: per-pair scores only, no in-batch shift
+            check = ex.guide_check = GuideChecker(be, self.check_guide_min, consecutive=world == 1 or ex.temporal[0] > 0)
         frames_dir = Path(str(output_path.with_suffix("")) + "_frames")
         frames_dir.mkdir(parents=True, exist_ok=True)
         # the extractor's frame plan: frame i -> rank i mod world, or -- with temporal stabilisation -- a contiguous block per
@@ -208,7 +228,9 @@ class SbsTo4kDepthPipeline:
                 idx = out_idx[j0:j0 + gb]
                 frames = [next_guide() for _ in idx]
                 flat += sum(f is None for f in frames)
-                q_dev = be.guided_upscale_u16(u16[j0:j0 + len(idx)], be.guide_luma(frames, Hhi, Whi, gb), self.radius, self.eps)
+                luma = be.guide_luma(frames, Hhi, Whi, gb)
+                q_dev = be.guided_upscale_u16(u16[j0:j0 + len(idx)], luma, self.radius, self.eps)
+                pending = check.emit(idx, frames, luma) if check is not None else None
                 if gpu_png:                                        # deflated on the device: only the streams cross PCIe
                     for i, s in zip(idx, be.png_streams_u16(q_dev)):
                         writers.submit(frames_dir / f"depth4k_{i:06d}.png", s, encode=gray16_file(Whi, Hhi))
@@ -216,6 +238,8 @@ class SbsTo4kDepthPipeline:
                     q = be.to_host_u16(q_dev)
                     for j, i in enumerate(idx):
                         writers.submit(frames_dir / f"depth4k_{i:06d}.png", q[j])
+                if pending is not None:                            # behind the batch's own synchronise: nothing waits here
+                    check.collect(pending)
                 if stereo is not None and any(f is not None for f in frames):
                     if gpu_png:
                         sbs3d = be.render_stereo_png(q_dev, stereo["gains"], stereo["layout"])
@@ -237,6 +261,10 @@ class SbsTo4kDepthPipeline:
         if n == 0:
             raise ValueError("No frames extracted from video")
         n_stereo = sharding.total(stereo["count"]) if stereo is not None else 0
+        if check is not None:
+            check.finish(sharding.total)
+            if rank == 0:
+                check.report()
         sharding.barrier()
         if rank == 0:
             encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, ex.manifest_extra() or None)
@@ -271,6 +299,10 @@ def main(argv=None):
                         help="Also write the 1080p depth_%%06d.png maps into the depth CLI's cache directory")
     parser.add_argument('--stereo-output', default=None,
                         help='Also render side-by-side 3D to this path (what the convert CLI makes from the depth output)')
+    parser.add_argument('--check-guide', action='store_true',
+                        help='Score every SBS frame against the 4K frame it is filtered with (frame signatures on the GPU) and '
+                             'warn when the guide looks misaligned; no output changes')
+    parser.add_argument('--check-guide-min', type=float, default=0.5, help='Score below which a pair counts as bad (default 0.5)')
     from .convert import add_stereo_arguments, stereo_options
     add_stereo_arguments(parser)
     args = parser.parse_args(argv)
@@ -285,7 +317,7 @@ def main(argv=None):
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        pipe = SbsTo4kDepthPipeline(**depth_options(args))
+        pipe = SbsTo4kDepthPipeline(check_guide=args.check_guide, check_guide_min=args.check_guide_min, **depth_options(args))
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,
