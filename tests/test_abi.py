@@ -59,13 +59,22 @@ def test_library_reads_no_environment():
     import ctypes as C
     v = C.c_int(-7)
     for key, good, bad in ((b"gf_band", 128, 3), (b"gf_cols", 512, 300), (b"gf_int1", 0, None), (b"gf_fused", 0, None),
-                           (b"corr_fused", 0, None), (b"gf_band1", 60, 1 << 20)):
+                           (b"corr_fused", 0, None), (b"gf_band1", 60, 1 << 20), (b"gf_tiled", 1, None),
+                           (b"corr_gather", 1, None), (b"gf_band2", 64, 7)):
         assert lib.v3d_get_option(key, C.byref(v)) == 0
         before = v.value
         assert lib.v3d_set_option(key, good) == 0 and lib.v3d_get_option(key, C.byref(v)) == 0 and v.value == good
         if bad is not None:
             assert lib.v3d_set_option(key, bad) == -1 and lib.v3d_get_option(key, C.byref(v)) == 0 and v.value == good
         assert lib.v3d_set_option(key, before) == 0
+    # 0 rows per workgroup means "choose per launch" for the fused kernel only
+    assert lib.v3d_get_option(b"gf_band", C.byref(v)) == 0
+    before = v.value
+    assert lib.v3d_set_option(b"gf_band", 0) == 0 and lib.v3d_get_option(b"gf_band", C.byref(v)) == 0 and v.value == 0
+    assert lib.v3d_set_option(b"gf_band", before) == 0
+    assert lib.v3d_get_option(b"gf_band1", C.byref(v)) == 0
+    before = v.value
+    assert lib.v3d_set_option(b"gf_band1", 0) == -1 and lib.v3d_get_option(b"gf_band1", C.byref(v)) == 0 and v.value == before
     assert lib.v3d_get_option(b"no_such_switch", C.byref(v)) == -1
 
 

@@ -367,6 +367,40 @@ def test_lockstep_timeout_is_never_silent(native, oracle):
     m.close()
 
 
+def test_handle_options_round_trip(native):
+    """every key of v3d_sgbm_set_option / _get_option: its default, a good value reads back, a bad one raises and leaves the
+    setting alone, the read-only keys refuse a set.  No compute call: a tiny handle, milliseconds."""
+    import torch
+    m = native.StereoSGBM(max_width=96, max_height=8, max_batch=1)
+    ncu = torch.cuda.get_device_properties(m.device).multi_processor_count
+    onoff = lambda default: (default, (1 - default, default), (2,))
+    table = {                                                 # key: (default, good values, bad values)
+        "lockstep": onoff(1), "hfused": onoff(1), "chain_dpl": (4, (8, 4), (6,)), "hsplit": onoff(0),
+        "vdd_dpl": (0, (4, 8, 0), (2,)), "cost_band": (90, (8, 65536, 90), (7, 65537)), "cost_xcd": onoff(1),
+        "vdd_xcd": onoff(0), "hf_xcd": onoff(0), "hf_persist": onoff(1), "lrm_tiles": onoff(0),
+        "reserve_cus": (0, (2, ncu, 0), (-1, ncu + 1)), "vdd_spin_limit": (0, (-1, 100, 0), (-2,)),
+        "vdd_launch_frames": (0, (3, 0), (-1,)),
+    }
+    for key, (default, _, _) in table.items():
+        assert m.get_option(key) == default, f"default of {key}"
+    for key, (default, good, bad) in table.items():
+        for g in good:                                        # the last good value is the default: reserve_cus is back at 0
+            m.set_option(key, g)                              # before "lockstep" could be read again
+            assert m.get_option(key) == g, f"{key} = {g} does not read back"
+            for b in bad:
+                with pytest.raises(native.NativeError, match=f"option {key}: value {b} out of range"):
+                    m.set_option(key, b)
+                assert m.get_option(key) == g, f"refused {key} = {b} changed the setting"
+        assert m.get_option(key) == default
+    for key in ("vdd_frames_per_launch_dpl4", "vdd_frames_per_launch_dpl8"):
+        assert m.get_option(key) >= 1
+        with pytest.raises(native.NativeError, match=f"unknown option {key}"):
+            m.set_option(key, 1)
+    with pytest.raises(native.NativeError, match="unknown option no_such_option"):
+        m.get_option("no_such_option")
+    m.close()
+
+
 def test_reserved_cus_shrink_the_lockstep_launch(native, oracle):
     """reserve_cus (CUs a concurrent collective keeps busy) lowers the frames per lock-step launch; a batch then takes
     several launches and still gives the oracle's bits"""

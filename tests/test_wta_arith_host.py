@@ -3,7 +3,7 @@ v3d_subpix_q) against exact integer division.  No GPU, no native library.
 
 The functions below RESTATE the helpers line by line in NumPy integer arithmetic (uint32 wrap-around and the 24-bit
 operand masks included); v3d_common.h and this file must stay the same few lines -- whoever changes one changes the
-other.  What they replace in wta_pixel (v3d_sgbm.hip), and what is the reference here:
+other.  What they replace in wta_pixel (v3d_sgbm_paths.hip), and what is the reference here:
 
     T1 = uq > 0 ? (minS * 100 + uq - 1) / uq : (minS * 100 > 0 ? 32768 : 0);  T1 = min(T1, 32768)     uq = 100 - uniquenessRatio
     den = max(sm + sp - 2 * minS, 1);  d16 += ((sm - sp) * 16 + den) / (den * 2)                         C division: truncates toward 0

@@ -13,16 +13,26 @@
 
 void v3d_set_error(const char* fmt, ...);
 
-// library-wide tuning switches (v3d_set_option); the library reads no environment variables
+// library-wide tuning switches (v3d_set_option / v3d_get_option); the library reads no environment variables.
+// X(key = field of g_v3d_opt, default, the values `value` may take, what is stored, what it does)
+// gf_band: 432 rows = 5 bands of a 4K frame: 34 frames (one lock-step launch upstream) are 5.98 rounds of the 512 resident
+// workgroups, where round 2's 270 rows were 9.56 (2.56 -> 2.43 ms).  A FIXED height, not the per-launch optimum (value 0):
+// the second stage's sliding sums round differently for a different band origin, and a frame's bits must not depend on how
+// many frames share its launch.
+#define V3D_LIB_OPTIONS(X) \
+    X(gf_band1, 90, value >= 8 && value <= 65536, value, "rows per workgroup of the first guided sweep (measured best on 30 x 4K frames)") \
+    X(gf_band2, 270, value >= 8 && value <= 65536, value, "rows per workgroup of the second guided sweep") \
+    X(gf_tiled, 0, true, value != 0, "1: force the LDS-tiled guided kernel for every radius") \
+    X(gf_fused, 1, true, value != 0, "1: single-launch guided filter (a/b rows handed from stage-1 to stage-2 waves through LDS), 0: two sweeps through HBM") \
+    X(gf_band, 432, value == 0 || (value >= 8 && value <= 65536), value, "rows per workgroup of the fused kernel; 0 = per launch: fewest rounds x (band + 4r)") \
+    X(gf_cols, 256, value == 256 || value == 512, value, "strip width of the fused kernel: 256 (8 waves) or 512 (16 waves, one workgroup per CU; int16 exact-2x route only)") \
+    X(gf_int1, 1, true, value != 0, "1: int16 disparity + exact 2x -> stage 1 of the fused kernel in exact integers (same bits)") \
+    X(corr_gather, 0, true, value != 0, "1: register-only gather-GEMM correlation (bit-identical, blends every position twice, slower)") \
+    X(corr_fused, 1, true, value != 0, "1: gather-GEMM through LDS for the 1x9 pattern (warped features never touch HBM), 0: warp kernel + GEMM kernel")
 struct v3d_lib_options {
-    int gf_band1, gf_band2;   // rows per workgroup of the guided sweeps (measured best on 30 x 4K frames)
-    int gf_tiled;             // 1: force the LDS-tiled guided kernel for every radius
-    int gf_fused;             // 1: single-launch guided filter (a/b rows handed from stage-1 to stage-2 waves through LDS), 0: two sweeps through HBM
-    int gf_band;              // rows per workgroup of the fused kernel (default 432); 0 = per launch: fewest rounds x (band + 4r)
-    int gf_cols;              // strip width of the fused kernel: 256 (8 waves) or 512 (16 waves, one workgroup per CU; int16 exact-2x route only)
-    int gf_int1;              // 1: int16 disparity + exact 2x -> stage 1 of the fused kernel in exact integers (same bits)
-    int corr_gather;          // 1: register-only gather-GEMM correlation (bit-identical, blends every position twice, slower)
-    int corr_fused;           // 1: gather-GEMM through LDS for the 1x9 pattern (warped features never touch HBM), 0: warp kernel + GEMM kernel
+#define X(name, def, ok, store, doc) int name = def;
+    V3D_LIB_OPTIONS(X)
+#undef X
 };
 extern v3d_lib_options g_v3d_opt;
 
@@ -141,47 +151,28 @@ __device__ __forceinline__ uint32_t dpp_xchg(uint32_t src)
 {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, CTRL, 0xF, 0xF, true);
 }
-// streaming accesses: once-read / once-written volume data bypasses cache retention (V3D_NT=0 at build time to disable)
-#ifndef V3D_NT
-#define V3D_NT 1
-#endif
+// streaming accesses: once-read / once-written volume data bypasses cache retention
 typedef uint32_t v3d_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t v3d_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint4 ld_stream(const uint4* p)
 {
-#if V3D_NT
     const v3d_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const v3d_u32x4*>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ uint2 ld_stream(const uint2* p)
 {
-#if V3D_NT
     const v3d_u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const v3d_u32x2*>(p));
     return make_uint2(v.x, v.y);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ void st_stream(uint4* p, uint4 v)
 {
-#if V3D_NT
     v3d_u32x4 t = { v.x, v.y, v.z, v.w };
     __builtin_nontemporal_store(t, reinterpret_cast<v3d_u32x4*>(p));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void st_stream(uint2* p, uint2 v)
 {
-#if V3D_NT
     v3d_u32x2 t = { v.x, v.y };
     __builtin_nontemporal_store(t, reinterpret_cast<v3d_u32x2*>(p));
-#else
-    *p = v;
-#endif
 }
 
 // ---- raw buffer access (range-checked: an offset with bit 31 set is out of range for every buffer this library
@@ -198,12 +189,12 @@ __device__ __forceinline__ uint32_t buf_load_u32(__amdgpu_buffer_rsrc_t r, uint3
 __device__ __forceinline__ void buf_store_stream(__amdgpu_buffer_rsrc_t r, uint32_t off, uint4 v)
 {
     v3d_u32x4 t = { v.x, v.y, v.z, v.w };
-    __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, V3D_NT ? 2 : 0);
+    __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, 2);      // aux bit 1: non-temporal
 }
 __device__ __forceinline__ void buf_store_stream(__amdgpu_buffer_rsrc_t r, uint32_t off, uint2 v)
 {
     v3d_u32x2 t = { v.x, v.y };
-    __builtin_amdgcn_raw_buffer_store_b64(t, r, off, 0, V3D_NT ? 2 : 0);
+    __builtin_amdgcn_raw_buffer_store_b64(t, r, off, 0, 2);
 }
 
 // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own 4 MB L2).  Map the linear
