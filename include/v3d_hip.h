@@ -32,6 +32,8 @@
  *                          deflate of the final u16 / BGR frames on the device, the host only adds the PNG chunks
  *   v3d_frame_signature_batch, v3d_signature_scores  no call site in the reference (align.py rounds the audio offset to a frame and
  *                          nothing checks the pairing): opt-in frame-accurate matching of SBS frames and 4K frames
+ *   v3d_quality_reproj_batch, v3d_quality_flicker_batch  no call site in the reference (its readme only names "quality assessment
+ *                          metrics"): opt-in, ground-truth-free measures of a run's own depth -- reprojection error and flicker
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -384,6 +386,43 @@ int v3d_frame_signature_batch(const uint8_t* gray, int n, int W, int H, int pitc
 int v3d_signature_scores(const uint16_t* sig_a, int na, const uint16_t* sig_b, int nb,
                          int64_t* num_out /* [na][nb] */, int64_t* var_a_out /* [na] */, int64_t* var_b_out /* [nb] */,
                          void* stream);
+
+/* Stereo quality report (v3d_quality.hip): two opt-in measures that need no ground truth, on planes a depth pass already holds
+   on the device (quality.py: --quality-report).  No call site in the reference.  Bit-exact contract, all integers:
+   tests/quality_ref.py.
+   Reprojection: frame f's grays at left_gray / right_gray + f*frame_stride (bytes), rows `pitch` bytes apart, only the W payload
+   bytes of a row are read; its disparity at disp16 + f*disp_stride (elements), rows dense, 2-byte alignment only.  Per pixel
+   (x, y) with d = disp16[y][x]:
+     valid iff d >= 1 (any other int16 is invalid; d up to 32767 is legal); u = 16 x - d; the pixel is COMPARED iff valid and u >= 0;
+     for a compared pixel i = u >> 4, f = u & 15, r16 = (16 - f) R[y][i] + f R[y][i+1] (d >= 1 gives i + 1 <= W - 1: no clamp);
+     e = |16 L[y][x] - r16| (0 <= e <= 4080);  e0 = 16 |L[y][x] - R[y][x]| (the same pixel at disparity 0).
+   Record of a frame, u64 [8]: 0 n_valid = #{d >= 1} over all pixels; then over the compared pixels 1 n_cmp = their number,
+   2 sad = sum e, 3 ssd = sum e^2, 4 n_bad = #{e > 16 bad_thr}, 5 sad0 = sum e0, 6 ssd0 = sum e0^2, 7 n_bad0 = #{e0 > 16 bad_thr}.
+   A frame's record does not depend on n, on its place in the batch or on the strides.  Headroom: e^2 <= 16 646 400, so a u32
+   holds the ssd of at most 258 pixels (a lane sums at most 128 before widening); over 8192 x 65535 pixels every field stays
+   below 2^53.  No floating point anywhere in this entry.
+   Flicker: the buffers the temporal entries take -- depth f32 (frame u at depth + u*depth_stride elements) and gray u8 (frame u
+   at gray + u*gray_stride bytes), rows dense, T >= 2.  d16 = v3d_d16(D) = rint(16 D), valid iff >= 1 (NaN and <= 0 are
+   invalid); the caller keeps d16 <= 32767, as in the temporal contract.  Record of pair u (frames u and u+1), u64 [4]:
+     0 luma_sad = sum_p |Y_{u+1} - Y_u| over all pixels (the sum v3d_temporal_cuts thresholds: the host applies the same cut rule);
+     1 n_still = #{p: |Y_{u+1} - Y_u| <= still and both d16 valid};  2 flicker = sum over those of |d16_{u+1} - d16_u|;
+     3 n_jump = #{those with |d16_{u+1} - d16_u| > jump16}.
+   ws: device scratch of the entry's _ws_bytes (one partial record per workgroup), 16-byte aligned; out: 8-byte aligned.  Both
+   entries enqueue two launches on `stream`, never synchronise, never allocate, use no atomics on global memory, and write nothing
+   outside out and ws, which may hold anything on entry.  V3D_ERR_ARG: null pointer, n outside [1, 65535], T outside [2, 65535],
+   W or H < 1, pitch < W, a stride below a frame with more than one frame, bad_thr or still outside [0, 255], jump16 outside
+   [0, 32767], ws not 16-byte aligned, out not 8-byte aligned; V3D_ERR_UNSUPPORTED: W > 8192 or H > 65535.  The _ws_bytes functions
+   return 0 for arguments the entry refuses. */
+#define V3D_QUALITY_REPROJ_FIELDS 8
+#define V3D_QUALITY_FLICKER_FIELDS 4
+size_t v3d_quality_reproj_ws_bytes(int n, int W, int H);
+int v3d_quality_reproj_batch(const uint8_t* left_gray, const uint8_t* right_gray, int n, int W, int H, int pitch,
+                             size_t frame_stride /* bytes */, const int16_t* disp16, size_t disp_stride /* elements */,
+                             int bad_thr, uint64_t* out /* [n][8] */, void* ws, void* stream);
+size_t v3d_quality_flicker_ws_bytes(int T, int W, int H);
+int v3d_quality_flicker_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
+                              size_t gray_stride /* bytes */, int T, int W, int H, int still, int jump16,
+                              uint64_t* out /* [T-1][4] */, void* ws, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

@@ -34,6 +34,7 @@ EXPORTS = (
     "v3d_fill_holes_ws_bytes", "v3d_fill_holes_disp16_batch",
     "v3d_png_stream_bound", "v3d_png_out_bytes", "v3d_png_ws_bytes", "v3d_png_deflate_batch",
     "v3d_frame_signature_batch", "v3d_signature_scores",
+    "v3d_quality_reproj_ws_bytes", "v3d_quality_reproj_batch", "v3d_quality_flicker_ws_bytes", "v3d_quality_flicker_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -153,6 +154,12 @@ def lib():
         L.v3d_png_deflate_batch.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp, vp]
         L.v3d_frame_signature_batch.argtypes = [vp, ci, ci, ci, ci, sz, vp, vp]
         L.v3d_signature_scores.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp]
+        L.v3d_quality_reproj_ws_bytes.argtypes = [ci, ci, ci]
+        L.v3d_quality_reproj_ws_bytes.restype = sz
+        L.v3d_quality_reproj_batch.argtypes = [vp, vp, ci, ci, ci, ci, sz, vp, sz, ci, vp, vp, vp]
+        L.v3d_quality_flicker_ws_bytes.argtypes = [ci, ci, ci]
+        L.v3d_quality_flicker_ws_bytes.restype = sz
+        L.v3d_quality_flicker_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -836,6 +843,63 @@ def signature_scores(sig_a, sig_b):
                                           _dev(num, torch.int64, "num"), _dev(va, torch.int64, "var_a"), _dev(vb, torch.int64, "var_b"),
                                           _stream()), "v3d_signature_scores")
     return num, va, vb
+
+
+QUALITY_REPROJ_FIELDS, QUALITY_FLICKER_FIELDS = 8, 4      # V3D_QUALITY_REPROJ_FIELDS / V3D_QUALITY_FLICKER_FIELDS
+QUALITY_MAX_WIDTH, QUALITY_MAX_HEIGHT = 8192, 65535
+
+
+def _quality_buffers(what, need, rows, fields, out, ws, device):
+    if not need:
+        raise NativeError(f"{what}: outside the entry's range (W <= {QUALITY_MAX_WIDTH}, H and the frame count <= {QUALITY_MAX_HEIGHT})")
+    if out is None:
+        out = torch.empty((rows, fields), dtype=torch.int64, device=device)
+    if tuple(out.shape) != (rows, fields):
+        raise NativeError(f"out: expected shape {(rows, fields)}, got {tuple(out.shape)}")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    elif ws.numel() < need:
+        raise NativeError(f"ws: {ws.numel()} bytes, {what} needs {need}")
+    return out, ws
+
+
+def quality_reproj_batch(lg, rg, disp16, bad_thr=16, out=None, ws=None):
+    """left / right gray u8 [n,H,W] and the int16 disparity [n,H,W] on the device (frames dense HxW, only the frame strides may
+    differ) -> the reprojection records, int64 [n,8]: n_valid, n_cmp, sad, ssd, n_bad, sad0, ssd0, n_bad0 in 1/16 gray levels
+    (v3d_quality_reproj_batch; bit-exact contract: tests/quality_ref.py).  out / ws: a caller's buffers; None takes them from the
+    caching allocator."""
+    l, ls = _clip(lg, torch.uint8, "left gray")
+    r, rs = _clip(rg, torch.uint8, "right gray")
+    d, ds = _clip(disp16, torch.int16, "disp16")
+    n, H, W = lg.shape
+    if tuple(rg.shape) != (n, H, W) or tuple(disp16.shape) != (n, H, W) or rs != ls:
+        raise NativeError(f"right gray {tuple(rg.shape)} / disp16 {tuple(disp16.shape)} do not match left gray {tuple(lg.shape)} (one frame stride for both grays)")
+    if isinstance(bad_thr, bool) or int(bad_thr) != bad_thr or not 0 <= bad_thr <= 255:
+        raise ValueError(f"bad threshold must be an integer in [0, 255], got {bad_thr!r}")
+    out, ws = _quality_buffers("quality_reproj_batch", lib().v3d_quality_reproj_ws_bytes(n, W, H), n, QUALITY_REPROJ_FIELDS, out, ws, lg.device)
+    with torch.cuda.device(lg.device):
+        _check(lib().v3d_quality_reproj_batch(l, r, n, W, H, W, ls, d, ds, int(bad_thr), _dev(out, torch.int64, "out"),
+                                              _dev(ws, torch.uint8, "ws"), _stream()), "v3d_quality_reproj_batch")
+    return out
+
+
+def quality_flicker_batch(depth, gray, still, jump16, out=None, ws=None):
+    """depth f32 [T,H,W] and left gray u8 [T,H,W] on the device (T >= 2; frames dense, only the frame strides may differ) -> the
+    flicker records of the T-1 pairs of consecutive frames, int64 [T-1,4]: luma_sad, n_still, flicker (in 1/16 px), n_jump
+    (v3d_quality_flicker_batch; bit-exact contract: tests/quality_ref.py)"""
+    d, ds = _clip(depth, torch.float32, "depth")
+    g, gs = _clip(gray, torch.uint8, "gray")
+    T, H, W = depth.shape
+    if tuple(gray.shape) != (T, H, W) or T < 2:
+        raise NativeError(f"gray {tuple(gray.shape)} does not match depth {tuple(depth.shape)}, or fewer than two frames")
+    for name, v, hi in (("still", still, 255), ("jump16", jump16, 32767)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
+    out, ws = _quality_buffers("quality_flicker_batch", lib().v3d_quality_flicker_ws_bytes(T, W, H), T - 1, QUALITY_FLICKER_FIELDS, out, ws, depth.device)
+    with torch.cuda.device(depth.device):
+        _check(lib().v3d_quality_flicker_batch(d, ds, g, gs, T, W, H, int(still), int(jump16), _dev(out, torch.int64, "out"),
+                                               _dev(ws, torch.uint8, "ws"), _stream()), "v3d_quality_flicker_batch")
+    return out
 
 
 def to_device(a, device="cuda"):

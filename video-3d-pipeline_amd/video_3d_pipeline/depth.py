@@ -244,6 +244,49 @@ class HipStereoBackend:
             ev.synchronize()
         return tuple(h.numpy().copy() for h in host)
 
+    # ---- quality report (quality.py; only called with --quality-report) ----
+    def right_gray(self, n: int):
+        """the right gray [n,H,W] of the latest sbs_to_disparity pass: a view of its staging buffer, like left_gray"""
+        return self._bufs["rg"][:n]
+
+    def last_disp16(self, n: int):
+        """the int16 disparity [n,H,W] of the latest sbs_to_disparity pass, after --fill-holes when that is on (it fills in
+        place): a view of the staging buffer the next pass overwrites"""
+        return self._bufs["disp"][:n]
+
+    def quality_reproj(self, n: int, bad_thr: int):
+        """reprojection records int64 [n,8] of the latest pass's planes, on the device (v3d_quality_reproj_batch); the partial
+        records live in a staging buffer"""
+        nat = self.native
+        lg = self.left_gray(n)
+        ws = self._staging("quality_reproj_ws", (max(16, nat.lib().v3d_quality_reproj_ws_bytes(n, lg.shape[2], lg.shape[1])),), self.torch.uint8, False)
+        return nat.quality_reproj_batch(lg, self.right_gray(n), self.last_disp16(n), bad_thr, ws=ws)
+
+    def quality_flicker(self, depth, gray, still: int, jump16: int):
+        """flicker records int64 [T-1,4] of the consecutive frames depth f32 / gray u8 [T,H,W], on the device
+        (v3d_quality_flicker_batch)"""
+        return self.native.quality_flicker_batch(depth, gray, still, jump16)
+
+    def quality_fetch(self, records):
+        """device records -> a handle for read_quality: the small integer array goes to pinned memory without blocking, an event
+        marks the end of the copy (as signature_scores does)"""
+        torch = self.torch
+        host = torch.empty(tuple(records.shape), dtype=torch.int64, pin_memory=True)
+        host.copy_(records, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev
+
+    def read_quality(self, handle, wait: bool = True):
+        """-> int64 NumPy records, or None when the copy has not finished and wait is False.  After the stream's next
+        synchronise the event has fired and nothing waits here"""
+        host, ev = handle
+        if not ev.query():
+            if not wait:
+                return None
+            ev.synchronize()
+        return host.numpy().copy()
+
     def depth_to_host(self, depth) -> np.ndarray:
         """device float32 [n,H,W] -> NumPy through a pinned buffer"""
         host = self._staging("depth_host", tuple(depth.shape), self.torch.float32, True)
@@ -266,16 +309,19 @@ class HipStereoBackend:
         """frames carried from earlier passes (or None) + the frames of this pass -> one private device buffer"""
         return new.clone() if held is None else self.torch.cat([held, new])
 
-    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill, range_quantile=10000):
+    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill, range_quantile=10000, observe=None):
         """buffer of T frames (device depth f32 and left gray u8 [T,H,W]) -> device u16 samples (int16-viewed) [n,H,W] of
         targets t0 .. t0+n-1: cuts, per-frame min/max, clip-stable range, filter, normalisation -- nine launches on the
         current stream, nothing comes back to the host.  range_quantile < 10000: the per-frame max is the robust white point
-        (three launches in place of the min/max's three)"""
+        (three launches in place of the min/max's three).  observe (--quality-report): called with the filtered depth and the
+        targets' gray before the normalisation"""
         nat = self.native
         cut = nat.temporal_cuts(gray, cut_threshold)
         mm = nat.depth_robust_minmax_batch(depth, range_quantile) if range_quantile < 10000 else nat.depth_minmax_batch(depth)
         lohi = nat.temporal_range(mm, cut, radius, t0, n)
         filt = nat.temporal_filter_batch(depth, gray, radius, tau, cut, fill, t0, n)
+        if observe is not None:
+            observe(filt, gray[t0:t0 + n])
         return nat.depth_to_u16_range_batch(filt, lohi)
 
     def depth_to_u16_batch(self, depth):
@@ -335,7 +381,11 @@ class HybridStereoDepthExtractor:
                  temporal_fill: bool = True,
                  range_percentile: float = 100.0,
                  fill_holes: bool = False,
-                 png_encoder: str = "zlib"):
+                 png_encoder: str = "zlib",
+                 quality_report=None,
+                 quality_bad_threshold: int = 16,
+                 quality_still: int = 4,
+                 quality_jump: float = 1.0):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
@@ -345,7 +395,10 @@ class HybridStereoDepthExtractor:
         fill_holes (every surface, process_frame_batch included: it is per frame): the matcher's invalid pixels are filled from
         their scanline neighbours on the int16 disparity, before /16 and everything after it; off = they stay depth 0
         png_encoder (process_video_sbs only): "gpu" deflates the 16-bit maps on the device (png_gpu.py); "zlib" = on the writer
-        threads, as ever """
+        threads, as ever
+        quality_report (process_video_sbs and the one-pass pipeline): True or a path measures the run's depth on the device without
+        ground truth (quality.py) and writes quality.json next to the depth maps or to the path; quality_*: its thresholds.  No
+        output and no cache key changes """
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
         from .temporal import check_parameters, check_range_percentile
@@ -354,6 +407,13 @@ class HybridStereoDepthExtractor:
         if not isinstance(fill_holes, (bool, np.bool_)):
             raise ValueError(f"fill_holes must be a bool, got {fill_holes!r}")
         self.fill_holes = bool(fill_holes)
+        from .quality import check_parameters as check_quality
+        if quality_report is not None and not isinstance(quality_report, (bool, np.bool_, str, Path)):
+            raise ValueError(f"quality_report must be None, a bool or a path, got {quality_report!r}")
+        self.quality_report = quality_report if quality_report else None
+        self.quality_params = check_quality(quality_bad_threshold, quality_still, quality_jump, self.temporal[2])
+        self.quality_jump = float(quality_jump)
+        self.quality = None                      # quality.QualityMonitor of the run in progress (--quality-report)
 
         self.device = device
         self.work_dir = create_work_directory(work_dir)
@@ -450,7 +510,40 @@ class HybridStereoDepthExtractor:
             extra["fill_holes"] = True
         if self.guide_check is not None and self.guide_check.summary is not None:
             extra["guide_match"] = self.guide_check.summary
+        if self.quality is not None and self.quality.summary is not None:
+            extra["quality"] = self.quality.summary
         return extra
+
+    def start_quality(self, world: int, owned=None):
+        """--quality-report: the monitor of one run, created by the driver (None when the flag is off)"""
+        self.quality = None
+        if self.quality_report is not None:
+            from .quality import QualityMonitor
+            stage = "matcher+fill" if self.fill_holes else "matcher"
+            bad, still, _, cut = self.quality_params
+            self.quality = QualityMonitor(self.backend, bad, still, self.quality_jump, cut, consecutive=world == 1, reproj_stage=stage,
+                                          flicker_stage="hybrid blend" if self._guidance_provider() is not None else stage, owned=owned)
+        return self.quality
+
+    def finish_quality(self, default_dir, rank: int = 0):
+        """after the last pass: totals over the ranks, the printed summary and quality.json (rank 0) in default_dir or at the
+        flag's path; the manifest entry is ready afterwards"""
+        from . import sharding
+        if self.quality is None:
+            return None
+        self.quality.finish(sharding.total)
+        if rank != 0:
+            return None
+        self.quality.report()
+        path = Path(default_dir) / "quality.json" if isinstance(self.quality_report, (bool, np.bool_)) else Path(self.quality_report)
+        print(f"✓ Quality report: {self.quality.write(path)}")
+        return path
+
+    def quality_skipped(self):
+        """a run that reuses existing output measures nothing: say so"""
+        if self.quality_report is not None:
+            from .quality import CACHED_NOTE
+            print(CACHED_NOTE)
 
     def write_side_files(self, cache_path: Path):
         """temporal.json (a radius or the robust range is on) and fill.json (--fill-holes) of a depth map directory"""
@@ -574,6 +667,7 @@ class HybridStereoDepthExtractor:
         cache_path = self.get_cache_path(video_path, start_frame, frame_count)
         if not force_reprocess and self.is_cached(cache_path, frame_count):
             print("✓ Using cached depth maps")
+            self.quality_skipped()
             return cache_path
         if video_info['width'] % 2 != 0:
             raise ValueError("SBS frame width must be even")
@@ -592,6 +686,7 @@ class HybridStereoDepthExtractor:
                 print(f"✓ Queued batch depth maps ({written} on rank {rank})")
         if sharding.total(written) == 0:
             raise ValueError("No frames extracted from video")
+        self.finish_quality(cache_path, rank)
         if rank == 0:
             self.write_side_files(cache_path)
         sharding.barrier()
@@ -643,10 +738,13 @@ class HybridStereoDepthExtractor:
         be = self.backend
         self.last_pass_frames = pass_frames = self.pass_frames(video_info)
         (first, count, stride, offset), _, block = self.frame_plan(frame_count, rank, world)
+        # --quality-report: a rank's halo frames are matched twice in a block-sharded run; only the owner's records count
+        quality = self.start_quality(world, None if block is None else range(block[0], block[0] + block[1]))
         stab = None
         if block is not None:
             from .temporal import BlockStabilizer
-            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile)
+            observe = {"observe": quality.note_stabilised} if quality is not None and world == 1 else {}
+            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile, **observe)
         frames = iter_frames(video_path, start_frame + first, count, stride=stride, offset=offset) if count else iter(())
         provider = self._guidance_provider()
         self.last_decoded_frames = 0
@@ -657,6 +755,8 @@ class HybridStereoDepthExtractor:
                 k0 = self.last_decoded_frames
                 self.last_decoded_frames += len(batch)
                 depth = self._disparity_pass(be.sbs_to_disparity, batch, self.unsqueeze_sbs, guidance=provider)
+                if quality is not None:                  # --quality-report: the pass's planes are valid until the next pass
+                    quality.note_pass([first + offset + k * stride for k in range(k0, k0 + len(batch))], len(batch), depth)
                 if self.guide_check is not None:         # --check-guide: the pass's left gray planes are valid until the next pass
                     self.guide_check.note_left([first + offset + k * stride for k in range(k0, k0 + len(batch))], be.left_gray(len(batch)))
                 if stab is not None:
@@ -684,6 +784,7 @@ IGEVStereoDepthExtractor = HybridStereoDepthExtractor
 def add_depth_arguments(parser, force_help: str):
     """the options of the depth path, shared by the depth CLI and the one-pass pipeline (--force means something else in each)"""
     from .png_gpu import add_png_arguments
+    from .quality import add_quality_arguments
     from .temporal import add_fill_arguments, add_range_arguments, add_temporal_arguments
     parser.add_argument('--start-frame', type=int, default=0, help='Starting frame number (default: 0)')
     parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to process (default: all)')
@@ -699,16 +800,19 @@ def add_depth_arguments(parser, force_help: str):
     add_range_arguments(parser)
     add_fill_arguments(parser)
     add_png_arguments(parser)
+    add_quality_arguments(parser)
 
 
 def depth_options(args) -> dict:
     """parsed add_depth_arguments -> the keyword arguments HybridStereoDepthExtractor and SbsTo4kDepthPipeline share"""
     from .png_gpu import png_options
+    from .quality import quality_options
     from .temporal import fill_options, range_options, temporal_options
     stereo_only = args.stereo_only or args.no_neural
     return dict(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device, batch_size=args.batch_size,
                 use_neural_guidance=not stereo_only, stereo_only=stereo_only, unsqueeze_sbs=not args.no_unsqueeze,
-                **temporal_options(args), **range_options(args), **fill_options(args), **png_options(args))
+                **temporal_options(args), **range_options(args), **fill_options(args), **png_options(args),
+                **quality_options(args))
 
 
 def main(argv=None):

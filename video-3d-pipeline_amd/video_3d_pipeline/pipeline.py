@@ -10,6 +10,7 @@ and through zlib twice before the 4K filter sees it.  Here the depth stays on th
                   [--temporal-radius R: the temporal stabiliser's u16 samples instead (temporal.py), R frames behind the matcher]
                   [--range-percentile P: the white point of either is the P-th percentile of the valid disparities, not the maximum]
                   [--fill-holes: the matcher's invalid pixels are filled inside sbs_to_disparity, before any of the above]
+                  [--quality-report: reprojection error and flicker of the pass's planes are measured on the side (quality.py); no byte changes]
                -> [--keep-depth-maps: depth_%06d.png into the depth CLI's cache directory]
                -> v3d_guided_upscale_u16_batch against the matching 4K frames' luma -> u16 4K samples -> writer pool
 
@@ -123,13 +124,19 @@ class SbsTo4kDepthPipeline:
                  fill_holes: bool = False,
                  png_encoder: str = "zlib",
                  check_guide: bool = False,
-                 check_guide_min: float = 0.5):
+                 check_guide_min: float = 0.5,
+                 quality_report=None,
+                 quality_bad_threshold: int = 16,
+                 quality_still: int = 4,
+                 quality_jump: float = 1.0):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own);
         range_percentile: the depth CLI's robust white point (100 = off: the maximum);
         fill_holes: the depth CLI's hole filling of the int16 disparity (off: invalid pixels stay depth 0);
         png_encoder: "gpu" deflates every PNG this run writes on the device (png_gpu.py); "zlib" = on the writer threads;
-        check_guide: score every (left view, 4K frame) pair the run uses (framematch.GuideChecker); no output PNG changes"""
+        check_guide: score every (left view, 4K frame) pair the run uses (framematch.GuideChecker); no output PNG changes;
+        quality_*: the depth CLI's --quality-report (quality.py): quality.json goes next to the kept depth maps, else next to the
+        4K frames, or to the given path; no output PNG changes"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -141,7 +148,8 @@ class SbsTo4kDepthPipeline:
             use_neural_guidance=use_neural_guidance, stereo_only=stereo_only, unsqueeze_sbs=unsqueeze_sbs, backend=backend,
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
             temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes,
-            png_encoder=png_encoder)
+            png_encoder=png_encoder, quality_report=quality_report, quality_bad_threshold=quality_bad_threshold,
+            quality_still=quality_still, quality_jump=quality_jump)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
         self.check_guide, self.check_guide_min = bool(check_guide), float(check_guide_min)
@@ -177,6 +185,7 @@ class SbsTo4kDepthPipeline:
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
             print(f"✓ Using existing depth video: {output_path}")
+            ex.quality_skipped()
             return str(output_path)
         if video_info['width'] % 2 != 0:
             raise ValueError("SBS frame width must be even")
@@ -265,6 +274,7 @@ class SbsTo4kDepthPipeline:
             check.finish(sharding.total)
             if rank == 0:
                 check.report()
+        ex.finish_quality(cache_path if keep_depth_maps else frames_dir, rank)
         sharding.barrier()
         if rank == 0:
             encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, ex.manifest_extra() or None)

@@ -70,7 +70,10 @@ class TemporalStabilizer:
     `backend.temporal_concat` and `backend.temporal_stabilize`."""
 
     def __init__(self, backend, radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True,
-                 range_quantile: int = RANGE_Q_OFF):
+                 range_quantile: int = RANGE_Q_OFF, observe=None):
+        """observe (--quality-report): a callable the backend's temporal_stabilize calls with the filtered depth and the targets'
+        gray; None (the default) adds no argument to that call"""
+        self.observe = observe
         self.radius, self.tau, self.cut_threshold, self.fill = check_parameters(radius, tau, cut_threshold, fill)
         if isinstance(range_quantile, bool) or int(range_quantile) != range_quantile or not RANGE_Q_MIN <= range_quantile <= RANGE_Q_OFF:
             raise ValueError(f"range quantile must be an integer in [{RANGE_Q_MIN}, {RANGE_Q_OFF}], got {range_quantile!r}")
@@ -91,7 +94,7 @@ class TemporalStabilizer:
         args = (self._depth, self._gray, self._next - self._first, n, self.radius, self.tau, self.cut_threshold, self.fill)
         if self.range_quantile < RANGE_Q_OFF:                # off: the call a backend without the robust range knows
             args += (self.range_quantile,)
-        out = self.backend.temporal_stabilize(*args)
+        out = self.backend.temporal_stabilize(*args, **({} if self.observe is None else {"observe": self.observe}))
         self._next = upto
         return out
 
@@ -130,8 +133,8 @@ class BlockStabilizer:
     first - halo_before .. first + count + halo_after - 1 in order and gets back (frame indices, u16 samples) of the frames
     it owns; the halo frames only feed the windows."""
 
-    def __init__(self, backend, params, first: int, count: int, halo_before: int, range_quantile: int = RANGE_Q_OFF):
-        self.stab = TemporalStabilizer(backend, *params, range_quantile)
+    def __init__(self, backend, params, first: int, count: int, halo_before: int, range_quantile: int = RANGE_Q_OFF, observe=None):
+        self.stab = TemporalStabilizer(backend, *params, range_quantile, observe)
         self.first, self.count = first, count
         self._at = first - halo_before           # clip index of the next frame the stabiliser returns
 
