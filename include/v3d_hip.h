@@ -125,7 +125,10 @@ int v3d_sgbm_stream_wait_lockstep(v3d_sgbm* h, void* stream);
 /* Tuning switches of a handle (defaults = the measured best; results never change): "lockstep" 0/1, "hfused" 0/1,
    "chain_dpl" 4/8, "hsplit" 0/1, "hf_persist" 0/1, "lrm_tiles" 0/1, "vdd_dpl" 0/4/8, "cost_band" >= 8, "cost_xcd" / "vdd_xcd" / "hf_xcd" 0/1, "reserve_cus" (CUs
    other streams keep busy during a lock-step pass), "vdd_spin_limit" (poll rounds per lane; 0 = derived from the row
-   count), "vdd_launch_frames" (frames per lock-step launch; 0 = sized from the occupancy query and the call's width).
+   count), "vdd_launch_frames" (frames per lock-step launch; 0 = sized from the occupancy query and the call's width; more than are
+   co-resident is safe and slow, and such a launch ignores "vdd_xcd": the XCD order is a speed switch and never costs forward
+   progress), "vdd_seq" 1..0xFFFFF (test hook: the 20-bit sequence number the next lock-step launch carries, so that the wrap and
+   its granule sweep can be reached without 2^20 launches; get returns the number the next launch will carry).
    get also knows the read-only "vdd_frames_per_launch_dpl4" / "_dpl8".  Unknown key or bad value: V3D_ERR_ARG.
    The library reads no environment variables. */
 int v3d_sgbm_set_option(v3d_sgbm* h, const char* key, int value);

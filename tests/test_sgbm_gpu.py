@@ -379,7 +379,7 @@ def test_handle_options_round_trip(native):
         "vdd_dpl": (0, (4, 8, 0), (2,)), "cost_band": (90, (8, 65536, 90), (7, 65537)), "cost_xcd": onoff(1),
         "vdd_xcd": onoff(0), "hf_xcd": onoff(0), "hf_persist": onoff(1), "lrm_tiles": onoff(0),
         "reserve_cus": (0, (2, ncu, 0), (-1, ncu + 1)), "vdd_spin_limit": (0, (-1, 100, 0), (-2,)),
-        "vdd_launch_frames": (0, (3, 0), (-1,)),
+        "vdd_launch_frames": (0, (3, 0), (-1,)), "vdd_seq": (1, (0xFFFFF, 1), (0, 0x100000)),
     }
     for key, (default, _, _) in table.items():
         assert m.get_option(key) == default, f"default of {key}"

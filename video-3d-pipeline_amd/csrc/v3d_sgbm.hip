@@ -40,13 +40,14 @@ static void vdd_size_launches(v3d_sgbm* h)
     X("vdd_dpl", vdd_dpl, value == 0 || value == 4 || value == 8, "k_vdd strip mapping (0 = choose per call from the batch size)") \
     X("cost_band", cost_band, value >= 8 && value <= 65536, "rows per k_cost workgroup") \
     X("cost_xcd", cost_xcd, value == 0 || value == 1, "XCD-contiguous workgroup order of k_cost") \
-    X("vdd_xcd", vdd_xcd, value == 0 || value == 1, "XCD-contiguous workgroup order of k_vdd") \
+    X("vdd_xcd", vdd_xcd, value == 0 || value == 1, "XCD-contiguous workgroup order of k_vdd; speed only, so a launch of more frames than are co-resident ignores it (forward progress there rests on dispatch order = strip order)") \
     X("hf_xcd", hf_xcd, value == 0 || value == 1, "XCD-contiguous workgroup order of k_hfused") \
     X("hf_persist", hf_persist, value == 0 || value == 1, "k_hfused as the resident number of waves drawing row groups from a ticket counter / 0: one wave per row group") \
     X("lrm_tiles", lrm_tiles, value == 0 || value == 1, "L-R check + median as a row march over full-width bands / 1: as 128 x 16 tiles (also the form for W > 4096)") \
     X("reserve_cus", reserve_cus, value >= 0 && value <= h->ncu, "CUs other streams keep busy while a lock-step pass runs (shrinks the frames per launch)") \
     X("vdd_spin_limit", vdd_spin_limit, value >= -1, "poll rounds a lane may wait in a lock-step pass (0 = 64 per row + 4096; -1 = test hook: every workgroup reports a time-out, which drives the guard / V3D_ERR_LOCKSTEP path deterministically)") \
-    X("vdd_launch_frames", vdd_launch_frames, value >= 0, "frames per lock-step launch (0 = from the occupancy query); larger than the chip holds is safe, slow")
+    X("vdd_launch_frames", vdd_launch_frames, value >= 0, "frames per lock-step launch (0 = from the occupancy query); larger than the chip holds is safe, slow: such a launch runs in plain blockIdx order whatever vdd_xcd says") \
+    X("vdd_seq", vdd_seq, value >= 1 && value <= 0xFFFFF, "test hook: the 20-bit sequence number the next lock-step launch carries (reaches the wrap and its granule sweep without 2^20 launches); reads back the number the next launch will carry")
 
 extern "C" int v3d_sgbm_set_option(v3d_sgbm* h, const char* key, int value)
 {
@@ -67,6 +68,7 @@ extern "C" int v3d_sgbm_get_option(const v3d_sgbm* h, const char* key, int* valu
 {
     if (!h || !key || !value) { v3d_set_error("null argument"); return V3D_ERR_ARG; }
     if (!strcmp(key, "lockstep")) { *value = vdd_usable(h) ? 1 : 0; return V3D_OK; }       // what a compute call will do, not the stored flag
+    if (!strcmp(key, "vdd_seq")) { const int s = (int)(h->vdd_seq & 0xFFFFFu); *value = s ? s : 1; return V3D_OK; }   // the counter runs on; 0 is skipped (launch_vdd)
 #define X(name, field, ok, doc) if (!strcmp(key, name)) { *value = h->field; return V3D_OK; }
     V3D_SGBM_OPTIONS(X)
 #undef X

@@ -90,7 +90,7 @@ struct v3d_sgbm {
     unsigned long long* gran = nullptr;         // k_vdd edge granules
     size_t gran_bytes = 0;
     int* vdd_err = nullptr;
-    uint32_t vdd_seq = 1;
+    uint32_t vdd_seq = 1;                       // running count of lock-step launches; a launch carries its low 20 bits, never 0 (launch_vdd)
     int vdd_mode = 1;                           // 1: lock-step pass (k_vdd), 0: three k_chain launches
     int vdd_dpl = 0;                            // forced k_vdd mapping (4 / 8), 0 = choose per call
     int cost_band = 90;                         // rows per k_cost workgroup

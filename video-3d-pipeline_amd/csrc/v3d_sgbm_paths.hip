@@ -494,7 +494,7 @@ struct VddArgs {
     int spin_limit;                     // poll rounds a lane may spend waiting over the whole pass
     unsigned long long* gran;           // [frame][strip][2 dirs][VDD_RING][VDD_GRAN]
     int* err;
-    int xcd;                            // 1: XCD-contiguous strip order.  Measured slower (3.48 -> 4.58 ms per 30 frames): off
+    int xcd;                            // 1: XCD-contiguous strip order, co-resident launches only (launch_vdd).  Measured slower (3.48 -> 4.58 ms per 30 frames): off
 };
 
 // wait for N data granules (+ the delta granule if want_d) of one row: all loads of a poll round go out together
@@ -749,7 +749,11 @@ static void launch_vdd(v3d_sgbm* h, int n, int W1, int H, bool rev, hipStream_t 
             (void)hipMemsetAsync(h->gran, 0, h->gran_bytes, st);
             v.seq = (h->vdd_seq++) & 0xFFFFFu;
         }
-        v.gran = h->gran; v.err = h->vdd_err; v.xcd = h->vdd_xcd;
+        v.gran = h->gran; v.err = h->vdd_err;
+        // the XCD order is a speed switch and must never cost forward progress: a launch beyond the co-residency bound relies on
+        // dispatch order = strip order (k_vdd), which the permutation breaks -- a frame across two XCDs' ranges would have some
+        // strips resident first and the others last, and the first would spin their budget away
+        v.xcd = h->vdd_xcd && nf <= (dpl == 8 ? mf8 : mf4);
         v.spin_limit = h->vdd_spin_limit != 0 ? h->vdd_spin_limit : VDD_SPIN_PER_ROW * H + VDD_SPIN_SLACK;
         const dim3 grid(v.nstrips * nf), block(1024);
         if (dpl == 8) { if (rev) hipLaunchKernelGGL((k_vdd<8, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_vdd<8, false>), grid, block, 0, st, v); }
