@@ -23,6 +23,7 @@
  *                          correlation strength (align.py's VideoAligner.find_alignment)
  *   v3d_render_stereo_batch  readme.md:37 step 4 (handed to VisionDepth3D there): DIBR from the 4K frame and its 4K depth
  *                          to a side-by-side 3D frame (convert.py, the declared video-3d-convert step)
+ *   v3d_render_stereo_subpixel_batch  the same step in 1/16 pixel with interpolated colours (convert.py --subpixel)
  *   v3d_temporal_*, v3d_depth_minmax_batch, v3d_depth_to_u16_range_batch  no call site in the reference (it normalises every
  *                          frame on its own, depth.py:397-406): opt-in temporal stabilisation of the depth sequence
  *   v3d_depth_robust_minmax_batch  no call site in the reference either: opt-in percentile white point of that normalisation
@@ -267,6 +268,25 @@ int v3d_align_audio(const float* a1, int n1, const float* a2, int n2, double* re
 int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
                             size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
                             int convergence, int layout, uint8_t* out_bgr /* dense [n][H][outW][3] */, void* stream);
+
+/* Sub-pixel DIBR (v3d_stereo.hip): the same inputs, strides, layouts, gains, convergence, refusals and memory contract as
+   v3d_render_stereo_batch (natural alignment only, rows and frames at any byte offset, nothing written outside out_bgr, no
+   allocation, no synchronisation, one launch), with positions in 1/16 px and colours interpolated along connected spans.
+   Per row and eye with gain g, all integers (every floor and >> the mathematical one):
+     p(x) = 16 x + floor((g * (D[x] - convergence) + 2^19) / 2^20) (may be negative);
+     span of source x: L' = p(x+1) - p(x).  Connected iff x + 1 < W and 0 < L' <= V3D_STEREO_TEAR16 (stretched to at most 2 px):
+       L = L', colours between F[x] and F[x+1]; otherwise (last column, fold, tear) a point: L = 16, colour F[x].  It covers the
+       integer targets t with p(x) <= 16 t < p(x) + L: the first is (p(x) + 15) >> 4, at most two, none for a compressed span;
+     Z[t] = max over the spans that cover t, 0 <= t < W, of the u32 key (D[x] << 16) | (x + 1); targets outside [0, W) are dropped;
+     a hit target, x = (Z[t] & 0xFFFF) - 1: F[x] for a point; for a connected span w = 16 t - p(x) and per channel
+       floor((2 ((L - w) F[x] + w F[x+1]) + L) / (2 L)) (round-half-up linear interpolation);
+     a hole (Z[t] = 0) takes the rendered colour of the target that holds the farther of its nearest left / right keys (ties left,
+       the only one if one side has none, black if the row has none);
+     full and half SBS as above.  Bit-exact contract: tests/stereo_sub_ref.py. */
+#define V3D_STEREO_TEAR16 32
+int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
+                                     size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
+                                     int convergence, int layout, uint8_t* out_bgr /* dense [n][H][outW][3] */, void* stream);
 
 /* Temporal depth stabilisation (v3d_temporal.hip): an opt-in stage between the disparity and the u16 normalisation.  A buffer
    holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +

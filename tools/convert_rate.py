@@ -1,8 +1,9 @@
 """DIBR step (v3d_render_stereo_batch) on one GPU: kernel time per 4K frame from HIP events (8 distinct frames per launch,
 warm-up, 20 timed launches, both layouts), the algorithmic bytes and their share of 8 TB/s, and the convert CLI's end-to-end
-frames/s on a synthetic .npy 4K clip.  Prints one JSON line.
+frames/s on a synthetic .npy 4K clip.  Prints one JSON line.  --subpixel measures v3d_render_stereo_subpixel_batch the same way
+after the integer entry (the yardstick, same process and inputs) and adds "kernel_subpixel" and the ratio of the two.
 
-    python tools/convert_rate.py [--frames 24] [--kernel-only]
+    python tools/convert_rate.py [--frames 24] [--kernel-only] [--subpixel]
 """
 import argparse
 import json
@@ -33,7 +34,7 @@ def inputs(n, seed=0):
     return frames, depth
 
 
-def kernel_rates():
+def kernel_rates(subpixel=False):
     frames, depth = inputs(NF)
     f = torch.from_numpy(frames).cuda()
     d = torch.from_numpy(depth.view(np.int16)).cuda()
@@ -42,12 +43,12 @@ def kernel_rates():
     for name, layout, out_px in (("full_sbs", N.STEREO_FULL_SBS, 6), ("half_sbs", N.STEREO_HALF_SBS, 3)):
         out = torch.empty((NF, H, W * (2 if layout == N.STEREO_FULL_SBS else 1), 3), dtype=torch.uint8, device="cuda")
         for _ in range(3):
-            N.render_stereo_batch(f, d, gl, gr, conv, layout, out)
+            N.render_stereo_batch(f, d, gl, gr, conv, layout, out, subpixel=subpixel)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(REPS):
-            N.render_stereo_batch(f, d, gl, gr, conv, layout, out)
+            N.render_stereo_batch(f, d, gl, gr, conv, layout, out, subpixel=subpixel)
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / (REPS * NF)
@@ -57,7 +58,7 @@ def kernel_rates():
     return res
 
 
-def cli_rate(n, encoders=("zlib",)):
+def cli_rate(n, encoders=("zlib",), subpixel=False):
     from video_3d_pipeline import convert, utils
     frames, depth = inputs(n, seed=1)
     with tempfile.TemporaryDirectory() as tmp:
@@ -69,7 +70,7 @@ def cli_rate(n, encoders=("zlib",)):
         del frames, depth
         res = {}
         for enc in encoders:                                   # alternating in this one process
-            conv = convert.DepthTo3DConverter(png_encoder=enc)
+            conv = convert.DepthTo3DConverter(png_encoder=enc, subpixel=subpixel)
             conv.process_conversion(os.path.join(tmp, "v4k.npy"), ddir, os.path.join(tmp, f"warm_{enc}.json"), max_frames=2)
             t0 = time.perf_counter()
             conv.process_conversion(os.path.join(tmp, "v4k.npy"), ddir, os.path.join(tmp, f"out_{enc}.json"))
@@ -84,10 +85,15 @@ def main():
     ap.add_argument("--kernel-only", action="store_true", help="skip the end-to-end CLI run (profiler runs)")
     ap.add_argument("--png-encoder", nargs="+", choices=["zlib", "gpu"], default=["zlib"],
                     help="the CLI run once per listed encoder, alternating in this one process")
+    ap.add_argument("--subpixel", action="store_true", help="also measure the sub-pixel entry, after the integer one; the CLI run uses it")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "kernel": kernel_rates()}
+    if a.subpixel:
+        res["kernel_subpixel"] = kernel_rates(subpixel=True)
+        res["subpixel_over_integer"] = {k: round(res["kernel_subpixel"][k]["us_per_frame"] / res["kernel"][k]["us_per_frame"], 3)
+                                        for k in res["kernel"]}
     if not a.kernel_only:
-        res["convert_cli_full_sbs"] = cli_rate(a.frames, a.png_encoder)
+        res["convert_cli_full_sbs"] = cli_rate(a.frames, a.png_encoder, a.subpixel)
     print(json.dumps(res))
 
 

@@ -11,6 +11,17 @@
 //   4. fill + gather: holes take the farther neighbour (background extends into disocclusions), colours come from sF,
 //      half SBS averages pairs in registers, and each thread writes its run with the widest aligned stores.
 // Contract: tests/stereo_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "DIBR stereo rendering".
+//
+// Sub-pixel DIBR (v3d_render_stereo_subpixel_batch, k_render_stereo<PPT, true>) is the same march with positions in 1/16 px:
+// p(x) = 16 x + floor((g (D[x] - conv) + 2^19) / 2^20).  Source x owns the span [p(x), p(x) + L): L = p(x+1) - p(x) when that
+// lies in (0, V3D_STEREO_TEAR16] (a connected span, colours interpolated between F[x] and F[x+1]), else 16 (a point: last
+// column, fold or tear, colour F[x]).  It differs from the integer kernel in three places:
+//   2. scatter: the span's integer targets (at most two, first (p + 15) >> 4) each take a ds_max_u32 of the same key;
+//   4. gather: a hit target rebuilds p, L and w = 16 t - p from its key (D[x] is in the key, D[x+1] and the two colours in
+//      LDS) and interpolates floor((2 ((L - w) F[x] + w F[x+1]) + L) / 2L) as a multiply by ceil(2^20 / 2L) and a shift;
+//      holes carry the COLOUR of the neighbouring hit target, not its key;
+//   ... and the nearest hit targets outside a thread's run are evaluated from their keys and the indices the scans yield.
+// Contract: tests/stereo_sub_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Sub-pixel DIBR".
 #include "v3d_common.h"
 
 #define ST_THREADS 256
@@ -66,6 +77,38 @@ __device__ __forceinline__ int st_shift(int g, int d, int conv)
     return (int)((num + (1 << 23)) >> 24);                     // arithmetic shift = floor
 }
 
+__device__ __forceinline__ int st_shift16(int g, int d, int conv)
+{
+    // floor((g dd + 2^19) / 2^20), dd = d - conv, the shift in 1/16 px, without the 64-bit product: with g = 2^12 gh + gl it is
+    // floor((dd gh + (dd gl + 2^19) / 2^12) / 2^8), and dd gh is an integer, so the inner quotient may be floored first.  |dd| < 2^16,
+    // |gh| <= 2^12, gl < 2^12: 24-bit operands (full-rate v_mul_i32_i24), sums below 2^30.  tests/test_stereo_sub_ref.py repeats it.
+    const int dd = d - conv;
+    return (__mul24(dd, g >> 12) + ((__mul24(dd, g & 4095) + (1 << 19)) >> 12)) >> 8;
+}
+
+// sub-pixel: the colour of hit target t of the eye with gain g, from its key k != 0.  A point span (fold, tear) has w = 0; the last
+// column reads itself as its right neighbour (L = 16, both colours equal): F[x] either way, without a branch.
+__device__ __forceinline__ uint32_t st_sub_colour(uint32_t k, int t, int g, int conv, int W, const uint16_t* drow,
+                                                  const unsigned char* frow, const uint32_t* sM)
+{
+    const int x = (int)(k & 0xFFFFu) - 1, x1 = min(x + 1, W - 1);
+    const int s0 = st_shift16(g, (int)(k >> 16), conv);
+    const int Lp = 16 + st_shift16(g, drow[x1], conv) - s0;
+    const bool conn = (unsigned)(Lp - 1) < (unsigned)V3D_STEREO_TEAR16;
+    // L <= 32 and w < L; the masks say so to the compiler, which then multiplies with the full-rate 24-bit instructions
+    const uint32_t L = (conn ? (uint32_t)Lp : 16u) & 63u, w = (conn ? (uint32_t)(16 * t - (16 * x + s0)) : 0u) & 31u;
+    const uint32_t m = sM[L] & 0xFFFFFu;
+    const unsigned char *pa = frow + 3 * x, *pb = frow + 3 * x1;
+    uint32_t c = 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {                           // (L - w) a + w b = L a + w (b - a); numerator <= 511 L < 2^14, m <= 2^19
+        const int fa = pa[ch], fb = pb[ch];
+        const uint32_t num = (uint32_t)(2 * ((int)L * fa + (int)w * (fb - fa))) + L;
+        c |= (((num & 0x3FFFu) * m) >> 20) << (8 * ch);
+    }
+    return c;
+}
+
 template <int PPT>
 struct StGeom {
     static constexpr int WP = PPT * ST_THREADS;                // padded key row per eye (targets >= W stay 0)
@@ -75,7 +118,8 @@ struct StGeom {
 
 }  // namespace
 
-template <int PPT>
+// one march for both entries; SUB selects the sub-pixel scatter and gather
+template <int PPT, bool SUB>
 __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __restrict__ frame, size_t frame_stride,
                                                               const uint16_t* __restrict__ depth, size_t depth_stride, int W, int H,
                                                               int gl, int gr, int conv, int half, uint8_t* __restrict__ out,
@@ -88,8 +132,12 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
     unsigned char* sD = smem + 8 * WP;                         // depth row chunks (sd_bytes)
     unsigned char* sF = sD + sd_bytes;                         // BGR row chunks
     __shared__ uint32_t sTot[2][2][ST_THREADS / 64];           // [eye][prefix | suffix][wave]
+    __shared__ uint32_t sM[SUB ? V3D_STEREO_TEAR16 + 1 : 1];   // sub-pixel: ceil(2^20 / 2L), read after the row's first barrier
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (SUB) {
+        if (tid >= 1 && tid <= V3D_STEREO_TEAR16) sM[tid] = ((1u << 20) + 2u * tid - 1u) / (2u * tid);
+    }
     const int f = blockIdx.y;
     const int y0 = blockIdx.x * ST_BAND, y1 = min(y0 + ST_BAND, H);
     const uint8_t* fr = frame + (size_t)f * frame_stride;
@@ -141,9 +189,21 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
             if (x < W) {
                 const int d = drow[x];
                 const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(x + 1);
-                const int tl = x + st_shift(gl, d, conv), tr = x + st_shift(gr, d, conv);
-                if ((unsigned)tl < (unsigned)W) atomicMax(sZ + tl, key);
-                if ((unsigned)tr < (unsigned)W) atomicMax(sZ + WP + tr, key);
+                if constexpr (SUB) {
+                    const int d1 = drow[min(x + 1, W - 1)];         // the last column: L' = 16, the point span's length
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int g = e ? gr : gl, s0 = st_shift16(g, d, conv), Lp = 16 + st_shift16(g, d1, conv) - s0;
+                        const int p = 16 * x + s0, end = p + ((unsigned)(Lp - 1) < (unsigned)V3D_STEREO_TEAR16 ? Lp : 16);
+                        const int t0 = (p + 15) >> 4;              // arithmetic shift = floor; L <= 32: at most two targets
+                        if (16 * t0 < end && (unsigned)t0 < (unsigned)W) atomicMax(sZ + e * WP + t0, key);
+                        if (16 * t0 + 16 < end && (unsigned)(t0 + 1) < (unsigned)W) atomicMax(sZ + e * WP + t0 + 1, key);
+                    }
+                } else {
+                    const int tl = x + st_shift(gl, d, conv), tr = x + st_shift(gr, d, conv);
+                    if ((unsigned)tl < (unsigned)W) atomicMax(sZ + tl, key);
+                    if ((unsigned)tr < (unsigned)W) atomicMax(sZ + WP + tr, key);
+                }
             }
         }
         __syncthreads();
@@ -195,7 +255,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
         uint8_t* orow = out + ((size_t)f * H + y) * (size_t)outW * 3;
         const unsigned char* frow = sF + foff;
         for (int e = 0; e < 2; ++e) {
-            uint32_t kk[PPT], rb[PPT];
+            uint32_t kk[PPT], col[PPT];
             const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
 #pragma unroll
             for (int q = 0; q < PPT / 4; ++q) {
@@ -204,17 +264,41 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
             }
             uint32_t nb = suf[e] ? sZ[e * WP + WP - suf[e]] : 0u;
             uint32_t na = pre[e] ? sZ[e * WP + pre[e] - 1] : 0u;
+            if constexpr (SUB) {
+                // hit targets get their colour; holes then carry the (key, colour) of the nearest hit target on either side,
+                // the key only for the depth comparison
+                const int g = e ? gr : gl;
+                uint32_t hit = 0, nbc = 0, nac = 0;
 #pragma unroll
-            for (int i = PPT - 1; i >= 0; --i) { rb[i] = nb; if (kk[i]) nb = kk[i]; }
-            uint32_t col[PPT];
+                for (int i = 0; i < PPT; ++i) {
+                    col[i] = 0;
+                    if (kk[i]) { hit |= 1u << i; col[i] = st_sub_colour(kk[i], x0 + i, g, conv, W, drow, frow, sM); }
+                }
+                if (nb) nbc = st_sub_colour(nb, WP - (int)suf[e], g, conv, W, drow, frow, sM);
+                if (na) nac = st_sub_colour(na, (int)pre[e] - 1, g, conv, W, drow, frow, sM);
 #pragma unroll
-            for (int i = 0; i < PPT; ++i) {
-                uint32_t k = kk[i];
-                if (k) na = k;
-                else k = st_fill(na, rb[i]);
-                const int s = k ? (int)(k & 0xFFFFu) - 1 : 0;
-                const unsigned char* px = frow + 3 * s;
-                col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
+                for (int i = PPT - 1; i >= 0; --i) {
+                    if ((hit >> i) & 1u) { nb = kk[i]; nbc = col[i]; }
+                    else { kk[i] = nb; col[i] = nbc; }
+                }
+#pragma unroll
+                for (int i = 0; i < PPT; ++i) {
+                    if ((hit >> i) & 1u) { na = kk[i]; nac = col[i]; }
+                    else if (na && (!kk[i] || (na >> 16) <= (kk[i] >> 16))) col[i] = nac;      // st_fill's choice
+                }
+            } else {
+                uint32_t rb[PPT];
+#pragma unroll
+                for (int i = PPT - 1; i >= 0; --i) { rb[i] = nb; if (kk[i]) nb = kk[i]; }
+#pragma unroll
+                for (int i = 0; i < PPT; ++i) {
+                    uint32_t k = kk[i];
+                    if (k) na = k;
+                    else k = st_fill(na, rb[i]);
+                    const int s = k ? (int)(k & 0xFFFFu) - 1 : 0;
+                    const unsigned char* px = frow + 3 * s;
+                    col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
+                }
             }
             if (nvalid > 0 && !half) {
                 constexpr int NW = PPT * 3 / 4;
@@ -249,47 +333,65 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
     }
 }
 
-template <int PPT>
+template <int PPT, bool SUB>
 static int launch_stereo(const uint8_t* frame, size_t frame_stride, const uint16_t* depth, size_t depth_stride, int n, int W,
                          int H, int gl, int gr, int conv, int half, uint8_t* out, hipStream_t stream)
 {
     using G = StGeom<PPT>;
     const int sd = st_chunks(2 * W, 14) * 16, sf = st_chunks(3 * W, 15) * 16;
     const int smem = 8 * G::WP + sd + sf;
+    auto* kernel = k_render_stereo<PPT, SUB>;
     static bool attr_set = false;                              // per instantiation; the attribute is a property of the function
     if (!attr_set) {
-        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)k_render_stereo<PPT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           8 * G::WP + st_chunks(2 * G::WP, 14) * 16 + st_chunks(3 * G::WP, 15) * 16));
         attr_set = true;
     }
-    hipLaunchKernelGGL(k_render_stereo<PPT>, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride,
+    hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride,
                        depth, depth_stride, W, H, gl, gr, conv, half, out, sd);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
+}
+
+template <bool SUB>
+static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
+                         int n, int W, int H, int gain_left, int gain_right, int convergence, int layout, uint8_t* out_bgr,
+                         void* stream)
+{
+    if (!frame_bgr || !depth || !out_bgr) { v3d_set_error("%s: null pointer", who); return V3D_ERR_ARG; }
+    if (n < 1 || n > 65535 || W < 1 || H < 1) { v3d_set_error("%s: bad geometry n=%d W=%d H=%d", who, n, W, H); return V3D_ERR_ARG; }
+    if (n > 1 && (frame_stride < (size_t)W * H * 3 || depth_stride < (size_t)W * H)) {
+        v3d_set_error("%s: frame stride %zu B / depth stride %zu elements smaller than a frame", who, frame_stride, depth_stride);
+        return V3D_ERR_ARG;
+    }
+    if (layout != V3D_STEREO_FULL_SBS && layout != V3D_STEREO_HALF_SBS) { v3d_set_error("%s: layout %d", who, layout); return V3D_ERR_ARG; }
+    if (layout == V3D_STEREO_HALF_SBS && (W & 1)) { v3d_set_error("%s: half SBS needs an even width (W=%d)", who, W); return V3D_ERR_ARG; }
+    const int gmax = 1 << 24;
+    if (gain_left <= -gmax || gain_left >= gmax || gain_right <= -gmax || gain_right >= gmax) {
+        v3d_set_error("%s: |gain| must be < 2^24 (%d, %d)", who, gain_left, gain_right);
+        return V3D_ERR_ARG;
+    }
+    if (convergence < 0 || convergence > 65535) { v3d_set_error("%s: convergence %d outside [0, 65535]", who, convergence); return V3D_ERR_ARG; }
+    if (W > ST_MAX_W) { v3d_set_error("%s: W=%d > %d", who, W, ST_MAX_W); return V3D_ERR_UNSUPPORTED; }
+    const int half = layout == V3D_STEREO_HALF_SBS;
+    hipStream_t s = (hipStream_t)stream;
+    if (W <= 8 * ST_THREADS) return launch_stereo<8, SUB>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+    if (W <= 16 * ST_THREADS) return launch_stereo<16, SUB>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+    return launch_stereo<32, SUB>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
 }
 
 extern "C" int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
                                        int n, int W, int H, int gain_left, int gain_right, int convergence, int layout,
                                        uint8_t* out_bgr, void* stream)
 {
-    if (!frame_bgr || !depth || !out_bgr) { v3d_set_error("v3d_render_stereo_batch: null pointer"); return V3D_ERR_ARG; }
-    if (n < 1 || n > 65535 || W < 1 || H < 1) { v3d_set_error("v3d_render_stereo_batch: bad geometry n=%d W=%d H=%d", n, W, H); return V3D_ERR_ARG; }
-    if (n > 1 && (frame_stride < (size_t)W * H * 3 || depth_stride < (size_t)W * H)) {
-        v3d_set_error("v3d_render_stereo_batch: frame stride %zu B / depth stride %zu elements smaller than a frame", frame_stride, depth_stride);
-        return V3D_ERR_ARG;
-    }
-    if (layout != V3D_STEREO_FULL_SBS && layout != V3D_STEREO_HALF_SBS) { v3d_set_error("v3d_render_stereo_batch: layout %d", layout); return V3D_ERR_ARG; }
-    if (layout == V3D_STEREO_HALF_SBS && (W & 1)) { v3d_set_error("v3d_render_stereo_batch: half SBS needs an even width (W=%d)", W); return V3D_ERR_ARG; }
-    const int gmax = 1 << 24;
-    if (gain_left <= -gmax || gain_left >= gmax || gain_right <= -gmax || gain_right >= gmax) {
-        v3d_set_error("v3d_render_stereo_batch: |gain| must be < 2^24 (%d, %d)", gain_left, gain_right);
-        return V3D_ERR_ARG;
-    }
-    if (convergence < 0 || convergence > 65535) { v3d_set_error("v3d_render_stereo_batch: convergence %d outside [0, 65535]", convergence); return V3D_ERR_ARG; }
-    if (W > ST_MAX_W) { v3d_set_error("v3d_render_stereo_batch: W=%d > %d", W, ST_MAX_W); return V3D_ERR_UNSUPPORTED; }
-    const int half = layout == V3D_STEREO_HALF_SBS;
-    hipStream_t s = (hipStream_t)stream;
-    if (W <= 8 * ST_THREADS) return launch_stereo<8>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
-    if (W <= 16 * ST_THREADS) return launch_stereo<16>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
-    return launch_stereo<32>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+    return render_stereo<false>("v3d_render_stereo_batch", frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right,
+                                convergence, layout, out_bgr, stream);
+}
+
+extern "C" int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth,
+                                                size_t depth_stride, int n, int W, int H, int gain_left, int gain_right,
+                                                int convergence, int layout, uint8_t* out_bgr, void* stream)
+{
+    return render_stereo<true>("v3d_render_stereo_subpixel_batch", frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left,
+                               gain_right, convergence, layout, out_bgr, stream);
 }

@@ -27,7 +27,7 @@ EXPORTS = (
     "v3d_sgbm_poll_errors", "v3d_sgbm_stream_wait_lockstep", "v3d_sgbm_set_option", "v3d_sgbm_get_option", "v3d_set_option", "v3d_get_option", "v3d_round_to_u16",
     "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
     "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
-    "v3d_render_stereo_batch",
+    "v3d_render_stereo_batch", "v3d_render_stereo_subpixel_batch",
     "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
     "v3d_depth_to_u16_range_batch",
     "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
@@ -134,6 +134,7 @@ def lib():
         L.v3d_xcorr.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.v3d_align_audio.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.v3d_render_stereo_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]
+        L.v3d_render_stereo_subpixel_batch.argtypes = L.v3d_render_stereo_batch.argtypes
         L.v3d_temporal_cuts.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp]
         L.v3d_depth_minmax_batch.argtypes = [vp, ci, sz, sz, vp, vp]
         L.v3d_temporal_range.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
@@ -597,10 +598,11 @@ def stereo_gains(max_shift=48.0, convergence=0.5, eye_split=0.5):
     return gl, gr, conv
 
 
-def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, layout=STEREO_FULL_SBS, out=None):
+def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, layout=STEREO_FULL_SBS, out=None, subpixel=False):
     """DIBR (v3d_render_stereo_batch): frames u8 [n,H,W,3] BGR on the device (frames may be strided: rows dense), depth_u16 the
     u16 depth samples as an int16-viewed contiguous [n,H,W] tensor -> u8 [n,H,2W,3] (full SBS, left eye first) or [n,H,W,3]
-    (half SBS).  Bit-exact contract: tests/stereo_ref.py."""
+    (half SBS).  Bit-exact contract: tests/stereo_ref.py.  subpixel: v3d_render_stereo_subpixel_batch instead, positions in
+    1/16 px and colours interpolated along connected spans (contract: tests/stereo_sub_ref.py)."""
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
         raise NativeError(f"frames: expected a uint8 [n,H,W,3] device tensor, got {frames.dtype} {tuple(frames.shape)}")
     n, H, W, _ = frames.shape
@@ -615,10 +617,11 @@ def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, l
         out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
     if tuple(out.shape) != shape:
         raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    entry = "v3d_render_stereo_subpixel_batch" if subpixel else "v3d_render_stereo_batch"
     with torch.cuda.device(frames.device):
-        _check(lib().v3d_render_stereo_batch(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
-                                             H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout),
-                                             _dev(out, torch.uint8, "out"), _stream()), "v3d_render_stereo_batch")
+        _check(getattr(lib(), entry)(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
+                                     H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout),
+                                     _dev(out, torch.uint8, "out"), _stream()), entry)
     return out
 
 

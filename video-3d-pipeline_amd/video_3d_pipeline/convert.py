@@ -4,7 +4,9 @@ The reference declares this step as the console script `video-3d-convert = "vide
 work to an outside tool (VisionDepth3D, "Optimized DIBR rendering").  Here it is depth-image-based rendering on the device,
 v3d_render_stereo_batch: every source pixel moves horizontally by g/256 * (D - conv)/65536 pixels per eye, the nearest
 source wins, disocclusions take the farther neighbour (background extension), and the two eyes are packed as full or half
-side-by-side.  The bit-exact contract is tests/stereo_ref.py; the parameters:
+side-by-side.  The bit-exact contract is tests/stereo_ref.py.  --subpixel renders with v3d_render_stereo_subpixel_batch instead:
+positions in 1/16 pixel and colours interpolated along the spans between neighbouring sources, so that a smooth depth surface
+no longer comes out as a staircase of duplicated and dropped pixels (contract: tests/stereo_sub_ref.py).  The parameters:
 
     max_shift    parallax in pixels between depth 65535 (nearest) and depth 0 (default 48 = 1.25 % of a 3840 frame)
     convergence  the depth at the screen plane, in [0, 1] (default 0.5): nearer moves right in the left eye, left in the right
@@ -34,7 +36,8 @@ png_rgb_from_bgr = functools.partial(encode_png8, bgr=True)     # the writer poo
 
 
 def add_stereo_arguments(parser):
-    """--layout / --max-shift / --convergence / --eye-split: shared by the convert CLI and the pipeline's --stereo-output"""
+    """--layout / --max-shift / --convergence / --eye-split / --subpixel: shared by the convert CLI and the pipeline's
+    --stereo-output"""
     parser.add_argument('--layout', choices=list(LAYOUTS), default='full-sbs',
                         help='full-sbs: two full-width eyes side by side (2W x H); half-sbs: each eye squeezed to W/2 (W x H)')
     parser.add_argument('--max-shift', type=float, default=DEFAULT_MAX_SHIFT,
@@ -45,15 +48,32 @@ def add_stereo_arguments(parser):
                         help=f"left eye's share of the shift, 0 .. 1; 0 keeps the 4K frame as the left eye (default {DEFAULT_EYE_SPLIT:g})")
 
 
+    parser.add_argument('--subpixel', action='store_true',
+                        help='sub-pixel DIBR: positions in 1/16 px, colours interpolated between neighbouring sources '
+                             '(smooth surfaces render without one-pixel tears; default: whole-pixel shifts)')
+
+
 def stereo_options(args):
-    return dict(max_shift=args.max_shift, convergence=args.convergence, eye_split=args.eye_split, layout=args.layout)
+    """the parsed stereo flags as keyword arguments; `subpixel` appears only when the flag is on"""
+    opts = dict(max_shift=args.max_shift, convergence=args.convergence, eye_split=args.eye_split, layout=args.layout)
+    if getattr(args, "subpixel", False):
+        opts["subpixel"] = True
+    return opts
 
 
-def stereo_settings(max_shift=DEFAULT_MAX_SHIFT, convergence=DEFAULT_CONVERGENCE, eye_split=DEFAULT_EYE_SPLIT, layout="full-sbs"):
+def subpixel_kwargs(subpixel):
+    """what a backend's render call gains: nothing with the flag off, so a backend that predates it is called as before"""
+    return {"subpixel": True} if subpixel else {}
+
+
+def stereo_settings(max_shift=DEFAULT_MAX_SHIFT, convergence=DEFAULT_CONVERGENCE, eye_split=DEFAULT_EYE_SPLIT, layout="full-sbs",
+                    subpixel=False):
     """validated user parameters -> (layout code, (gain_left, gain_right, conv)); ValueError for anything out of range"""
     from ._native import stereo_gains
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, got {layout!r}")
+    if not isinstance(subpixel, (bool, np.bool_)):
+        raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
     return LAYOUTS[layout], stereo_gains(max_shift, convergence, eye_split)
 
 
@@ -74,12 +94,15 @@ def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, 
             print(res.stderr.decode())
             raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
     else:
-        Path(output_path).write_text(json.dumps({
+        man = {
             "format": "png8-rgb-sequence", "frames_dir": str(frames_dir), "pattern": "frame_%06d.png",
             "count": count, "width": width, "height": height, "fps": fps, "layout": params["layout"],
             "max_shift": params["max_shift"], "convergence": params["convergence"], "eye_split": params["eye_split"],
             "gain_left": gains[0], "gain_right": gains[1], "conv": gains[2],
-            "note": "no ffmpeg binary on this host: side-by-side frames kept as 8-bit RGB PNGs"}, indent=1))
+            "note": "no ffmpeg binary on this host: side-by-side frames kept as 8-bit RGB PNGs"}
+        if params.get("subpixel"):
+            man["subpixel"] = True
+        Path(output_path).write_text(json.dumps(man, indent=1))
 
 
 def write_clip_info(frames_dir: Path, fps: float):
@@ -137,7 +160,7 @@ class HipRenderBackend:
             self._bufs[key] = t
         return t
 
-    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, png=False):
+    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, png=False, subpixel=False):
         """NumPy BGR frames [H,W,3] + u16 depth maps [H,W] -> NumPy u8 [n,H,outW,3].  The input staging holds `capacity`
         frames and is reused (the synchronise at the end of the previous call made that safe); the output block comes from
         torch's caching host allocator and returns to it once the writers drop the last frame of it."""
@@ -158,7 +181,7 @@ class HipRenderBackend:
         with torch.cuda.device(self.device):
             fd[:n].copy_(fh[:n], non_blocking=True)
             dd[:n].copy_(dh[:n], non_blocking=True)
-            nat.render_stereo_batch(fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n])
+            nat.render_stereo_batch(fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n], subpixel=subpixel)
             if png:
                 return od[:n]
             host = torch.empty((n, H, oW, 3), dtype=torch.uint8, pin_memory=True)
@@ -166,12 +189,13 @@ class HipRenderBackend:
             torch.cuda.current_stream().synchronize()
         return host.numpy()
 
-    def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None):
+    def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, subpixel=False):
         """--png-encoder gpu: render_batch whose frames stay on the device and come back as the zlib streams of their PNGs"""
         if getattr(self, "_png", None) is None:
             from .png_gpu import DevicePngEncoder
             self._png = DevicePngEncoder(self.torch, self.native, self.device)
-        return self._png.encode(self.render_batch(frames, depths, gain_left, gain_right, conv, layout, capacity, png=True))
+        return self._png.encode(self.render_batch(frames, depths, gain_left, gain_right, conv, layout, capacity, png=True,
+                                                  subpixel=subpixel))
 
 
 class DepthTo3DConverter:
@@ -181,13 +205,17 @@ class DepthTo3DConverter:
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
-                 batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib"):
+                 batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
-        png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads"""
+        png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
+        subpixel: sub-pixel DIBR (the backend's render calls then carry subpixel=True; with it off they are unchanged)"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
-        self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout)
+        self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout, subpixel)
+        self.subpixel = bool(subpixel)
         self.params = dict(max_shift=max_shift, convergence=convergence, eye_split=eye_split, layout=layout)
+        if self.subpixel:
+            self.params["subpixel"] = True
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -200,7 +228,8 @@ class DepthTo3DConverter:
         frame_bgr, depth_u16 = np.asarray(frame_bgr), np.asarray(depth_u16)
         if frame_bgr.shape[:2] != depth_u16.shape or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
             raise ValueError(f"frame {frame_bgr.shape} and depth {depth_u16.shape} disagree")
-        return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code)[0])
+        return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
+                                                  **subpixel_kwargs(self.subpixel))[0])
 
     def process_conversion(self, video_4k_path: str, depth_path: str, output_path: str = None, force_reprocess: bool = False,
                            guide_start_frame: int = 0, max_frames: int = None) -> str:
@@ -208,14 +237,15 @@ class DepthTo3DConverter:
         path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
         from . import sharding
         from .png_gpu import rgb8_file
-        print(f"4K + depth -> 3D ({self.params['layout']}): {video_4k_path} + {depth_path}")
+        print(f"4K + depth -> 3D ({self.params['layout']}{', sub-pixel' if self.subpixel else ''}): {video_4k_path} + {depth_path}")
         depth_files = depth_frame_files(depth_path)
         info = get_video_info(video_4k_path)
         if not info:
             raise ValueError(f"Could not read video info: {video_4k_path}")
         W, H, fps = info['width'], info['height'], info['fps']
         if output_path is None:
-            output_path = f"3d_{self.params['layout']}_{Path(depth_path).with_suffix('').name}.mp4"
+            # _subpx: a run with --subpixel never reuses a file rendered without it
+            output_path = f"3d_{self.params['layout']}{'_subpx' if self.subpixel else ''}_{Path(depth_path).with_suffix('').name}.mp4"
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
             print(f"✓ Using existing 3D video: {output_path}")
@@ -240,10 +270,12 @@ class DepthTo3DConverter:
             if not batch_f:
                 return
             if self.png_encoder == "gpu":                        # deflated on the device: only the streams cross PCIe
-                out = self.backend.render_batch_png(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size)
+                out = self.backend.render_batch_png(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
+                                                    **subpixel_kwargs(self.subpixel))
                 encode = rgb8_file(2 * W if self.layout_code == LAYOUTS["full-sbs"] else W, H)
             else:
-                out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size)
+                out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
+                                                **subpixel_kwargs(self.subpixel))
                 encode = png_rgb_from_bgr
             for j, i in enumerate(batch_i):
                 writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)

@@ -73,29 +73,29 @@ class HipPipelineBackend(HipStereoBackend):
         """device u16 depth samples [n,H,W] + device luma [n,Hhi,Whi] -> device u16 4K samples [n,Hhi,Whi]"""
         return self.native.guided_upscale_u16_batch(u16, luma, r, eps)
 
-    def render_stereo(self, u16_4k, gains, layout):
+    def render_stereo(self, u16_4k, gains, layout, subpixel=False):
         """--stereo-output: the 4K BGR frames guide_luma left in its device staging + their u16 4K depth [n,Hhi,Whi] (device)
         -> NumPy side-by-side frames [n,Hhi,outW,3]: one launch, one D2H, no second H2D of the 4K frames.  Slots of frames
-        that had no 4K frame hold stale data; the caller drops them."""
+        that had no 4K frame hold stale data; the caller drops them.  subpixel: the sub-pixel renderer (--subpixel)."""
         torch = self.torch
-        out = self._render_stereo_dev(u16_4k, gains, layout)
+        out = self._render_stereo_dev(u16_4k, gains, layout, subpixel)
         host = torch.empty(tuple(out.shape), dtype=torch.uint8, pin_memory=True)
         host.copy_(out, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return host.numpy()
 
-    def _render_stereo_dev(self, u16_4k, gains, layout):
+    def _render_stereo_dev(self, u16_4k, gains, layout, subpixel=False):
         torch, nat = self.torch, self.native
         n, H, W = u16_4k.shape
         dev = self._bufs["guide_dev"]
         oW = 2 * W if layout == 0 else W
         out = self._staging("stereo_dev", (dev.shape[0], H, oW, 3), torch.uint8, False)
-        nat.render_stereo_batch(dev[:n], u16_4k.contiguous(), *gains, layout, out[:n])
+        nat.render_stereo_batch(dev[:n], u16_4k.contiguous(), *gains, layout, out[:n], subpixel=subpixel)
         return out[:n]
 
-    def render_stereo_png(self, u16_4k, gains, layout):
+    def render_stereo_png(self, u16_4k, gains, layout, subpixel=False):
         """--png-encoder gpu: render_stereo whose frames stay on the device and come back as the zlib streams of their PNGs"""
-        return self._png_encoder().encode(self._render_stereo_dev(u16_4k, gains, layout))
+        return self._png_encoder().encode(self._render_stereo_dev(u16_4k, gains, layout, subpixel))
 
 
 class SbsTo4kDepthPipeline:
@@ -161,18 +161,21 @@ class SbsTo4kDepthPipeline:
         output path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence.
         stereo_output: also render every frame that has a 4K frame to side-by-side 3D from the device-resident 4K frame and
         depth (the files the convert CLI writes from this run's depth output); stereo_options: max_shift, convergence,
-        eye_split, layout (convert.py's defaults)."""
+        eye_split, layout, subpixel (convert.py's defaults)."""
         from . import sharding
         from .png_gpu import gray16_file, rgb8_file
         ex, be = self.extractor, self.backend
         gpu_png = ex.png_encoder == "gpu"
         stereo = None
         if stereo_output is not None:
-            from .convert import png_rgb_from_bgr, sibling_frames_dir, stereo_settings
+            from .convert import png_rgb_from_bgr, sibling_frames_dir, stereo_settings, subpixel_kwargs
             params = dict(max_shift=48.0, convergence=0.5, eye_split=0.5, layout="full-sbs")
             params.update(stereo_options or {})
             layout, gains = stereo_settings(**params)
-            stereo = dict(params=params, layout=layout, gains=gains, dir=sibling_frames_dir(stereo_output), count=0)
+            if not params.get("subpixel"):
+                params.pop("subpixel", None)                         # off: the manifest and the backend calls are unchanged
+            stereo = dict(params=params, layout=layout, gains=gains, dir=sibling_frames_dir(stereo_output), count=0,
+                          sub=subpixel_kwargs(params.get("subpixel")))
         print(f"SBS -> 4K depth: {sbs_video} + {video_4k}")
         video_info, frame_count = ex._frame_count(sbs_video, start_frame, max_frames)
         info4k = get_video_info(video_4k)
@@ -251,10 +254,10 @@ class SbsTo4kDepthPipeline:
                     check.collect(pending)
                 if stereo is not None and any(f is not None for f in frames):
                     if gpu_png:
-                        sbs3d = be.render_stereo_png(q_dev, stereo["gains"], stereo["layout"])
+                        sbs3d = be.render_stereo_png(q_dev, stereo["gains"], stereo["layout"], **stereo["sub"])
                         encode = rgb8_file(2 * Whi if stereo["layout"] == 0 else Whi, Hhi)
                     else:
-                        sbs3d, encode = be.render_stereo(q_dev, stereo["gains"], stereo["layout"]), png_rgb_from_bgr
+                        sbs3d, encode = be.render_stereo(q_dev, stereo["gains"], stereo["layout"], **stereo["sub"]), png_rgb_from_bgr
                     for j, i in enumerate(idx):
                         if frames[j] is not None:                   # no 4K frame: no stereo frame (its slot is stale)
                             writers.submit(stereo["dir"] / f"frame_{i:06d}.png", sbs3d[j], encode=encode)
