@@ -312,6 +312,31 @@ int v3d_temporal_range(const float* minmax, const uint8_t* cut, int T, int t0, i
 int v3d_temporal_filter_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
                               size_t gray_stride /* bytes */, int T, int W, int H, int t0, int n, int R, int tau, int fill,
                               const uint8_t* cut, float* out, void* stream);
+/* Motion compensation of the temporal window (v3d_temporal_mc.hip; `--temporal-motion S`, S in 1..32 pixels per frame step).
+   Bit-exact contract, all integers: tests/temporal_mc_ref.py.  Blocks are 16x16 luma pixels on a grid anchored at (0,0), edge
+   blocks clipped to the frame: BW = ceil(W/16), BH = ceil(H/16), n_b = a block's pixel count.
+     Fields: for every frame u of the buffer and v = u+1 (forward, F_u) or v = u-1 (backward, Bk_u), every block b and candidate
+       (dx,dy) in [-S,S]^2: sad = sum over b's pixels |Y_u(x,y) - Y_v(clamp(x+dx,0,W-1), clamp(y+dy,0,H-1))|,
+       cost = sad + max(n_b >> 2, 1) * (|dx|+|dy|), key = cost * 8192 + (dy+S)*(2S+1) + (dx+S); b's vector is the candidate with
+       the smallest key (cost <= 65280 + 64*64, so key < 2^30; ranks <= 4224 < 8192).  F_{T-1} = Bk_0 = 0.
+       Storage: int16 [T][BH][BW][2] as (dx,dy).
+     resid[u] = sum over blocks of the unpenalised sad of Bk_u's chosen candidates (u64; resid[0] = 0); cut[u] = resid[u] > c*W*H.
+       With motion on this rule takes the place of v3d_temporal_cuts'.
+     Chained vector of block b from target t to u = t+k: m = 0; for each step j = 0 .. |k|-1 toward u,
+       m += F_{t+j}[block containing clamp(c_b + m)] (Bk_{t-j} going backward), c_b = (min(16 bx + 8, W-1), min(16 by + 8, H-1)),
+       clamped per coordinate to the frame; |m| <= R*S <= 256 per coordinate.
+     Filter: v3d_temporal_filter_batch's arithmetic with frame u read at q = p + m, m the vector of p's block:
+       s_k = 3x3 sum over delta of |Y_u(clamp(q+delta)) - Y_t(clamp(p+delta))|, the depth tap is d16_u(q), and a tap whose q lies
+       outside the frame has weight 0.  With all-zero fields the output is v3d_temporal_filter_batch's, bit for bit.
+   Both entries enqueue on `stream`, never synchronise, never allocate, and take device pointers only.
+   V3D_ERR_ARG: as for the entries above, S outside [1, 32], resid not 8-byte aligned, a field not 2-byte aligned. */
+/* mv_fwd, mv_bwd int16 [T][BH][BW][2], resid u64 [T] (zeroed by the entry), cut_out u8 [T]: three launches */
+int v3d_temporal_motion(const uint8_t* gray, size_t gray_stride /* bytes */, int T, int W, int H, int S, int c, int16_t* mv_fwd,
+                        int16_t* mv_bwd, unsigned long long* resid, uint8_t* cut_out, void* stream);
+/* out f32 dense [n][H][W]: the compensated filter of targets t0 .. t0+n-1; mv_fwd, mv_bwd and cut as v3d_temporal_motion wrote them */
+int v3d_temporal_filter_mc_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
+                                 size_t gray_stride /* bytes */, int T, int W, int H, int t0, int n, int R, int tau, int fill,
+                                 const uint8_t* cut, const int16_t* mv_fwd, const int16_t* mv_bwd, float* out, void* stream);
 /* v3d_depth_to_u16_batch with frame f's (min, max) read from lohi[2f], lohi[2f+1] instead of reduced from the frame: same
    float32 operations in the same order, hi == lo -> 0, the result clamped to [0, 65535] before the conversion.  With a frame's
    own min and max it reproduces v3d_depth_to_u16_batch bit for bit.  out dense [n][frame_elems]; n <= 65535 */

@@ -8,7 +8,11 @@ process.  Prints one JSON line.
 buffers (the synthetic clip, the matcher's output on the synthetic SBS frames, a constant frame: the worst case for same-address
 LDS atomics), alternating, and the stage at R = 2 and the radius-0 u16 step with and without the option.
 
-    python tools/temporal_rate.py [--kernel-only] [--radius 2 4] [--range-percentile 98]
+--motion S [S ...] adds the motion-compensated window (--temporal-motion): the stage at R = 2 on one panning 34-frame pass with
+the option off (v3d_temporal_cuts + v3d_temporal_filter_batch: what the stage always was) and on at each S, alternating, and
+v3d_temporal_motion and v3d_temporal_filter_mc_batch alone.
+
+    python tools/temporal_rate.py [--kernel-only] [--radius 2 4] [--range-percentile 98] [--motion 8 16 32 [--motion-only]]
 """
 import argparse
 import json
@@ -143,14 +147,56 @@ def range_rates(percentile, R=2, rounds=3, entry_only=False):
     return res
 
 
+def pan_clip(T, pan=5, seed=0):
+    """clip()'s disparity over a texture that pans by `pan` pixels per frame, sigma-3 noise"""
+    depth, _ = clip(T, seed)
+    g = torch.Generator(device="cuda").manual_seed(seed + 100)
+    base = torch.randint(0, 256, (H, W + pan * T), generator=g, device="cuda").float()
+    base = (base + base.roll(1, 0) + base.roll(1, 1) + base.roll((1, 1), (0, 1))) / 4
+    gray = torch.stack([base[:, pan * t:pan * t + W] for t in range(T)])
+    gray = (gray + 3 * torch.randn((T, H, W), generator=g, device="cuda")).clamp(0, 255).round().to(torch.uint8)
+    return depth, gray.contiguous()
+
+
+def motion_rates(searches, R=2, rounds=3):
+    """us per frame of a 34-frame pass (34 targets, 2R carried frames): stage off / on alternating, then the two new entries alone"""
+    from video_3d_pipeline.depth import HipStereoBackend
+    be = HipStereoBackend()
+    T = NF + 2 * R
+    depth, gray = pan_clip(T)
+    out = torch.empty((NF, H, W), dtype=torch.float32, device="cuda")
+    res = {"radius": R, "pan_px_per_frame": 5, "uncompensated_cuts": int(N.temporal_cuts(gray, 20).sum())}
+    for S in searches:
+        off, on, search, filt = [], [], [], []
+        fwd, bwd, resid, cut = N.temporal_motion(gray, S, 20)
+        for _ in range(rounds):
+            off.append(timed(lambda: be.temporal_stabilize(depth, gray, R, NF, R, 12, 20, True)) / NF)
+            on.append(timed(lambda: be.temporal_stabilize(depth, gray, R, NF, R, 12, 20, True, motion_search=S)) / NF)
+            search.append(timed(lambda: N.temporal_motion(gray, S, 20)) / NF)
+            filt.append(timed(lambda: N.temporal_filter_mc_batch(depth, gray, R, 12, cut, fwd, bwd, True, R, NF, out)) / NF)
+        res[f"S{S}"] = {"stage_off_us_per_frame": [round(t, 2) for t in off], "stage_on_us_per_frame": [round(t, 2) for t in on],
+                        "stage_off_median": round(float(np.median(off)), 2), "stage_on_median": round(float(np.median(on)), 2),
+                        "motion_entry_us_per_frame": round(float(np.median(search)), 2),
+                        "filter_mc_us_per_frame": round(float(np.median(filt)), 2), "compensated_cuts": int(cut.sum()),
+                        "sad_lane_ops_per_frame": 2 * (2 * S + 1) ** 2 * W * H // 4}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--radius", type=int, nargs="+", default=[2, 4])
     ap.add_argument("--kernel-only", action="store_true", help="skip the pipeline step (profiler runs)")
     ap.add_argument("--range-percentile", type=float, default=None, help="also time the robust range at this percentile")
     ap.add_argument("--range-only", action="store_true", help="with --range-percentile: only the two min/max entries (profiler, A/B runs)")
+    ap.add_argument("--motion", type=int, nargs="+", default=None, help="also time the motion-compensated window at these search radii")
+    ap.add_argument("--motion-only", action="store_true", help="with --motion: only that leg")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "frames_per_pass": NF}
+    if a.motion is not None:
+        res["motion"] = motion_rates(a.motion)
+        if a.motion_only:
+            print(json.dumps(res))
+            return
     if a.range_percentile is not None:
         res["robust_range"] = range_rates(a.range_percentile, entry_only=a.range_only)
     if not a.range_only:

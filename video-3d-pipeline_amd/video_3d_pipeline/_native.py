@@ -29,7 +29,7 @@ EXPORTS = (
     "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
     "v3d_render_stereo_batch", "v3d_render_stereo_subpixel_batch",
     "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
-    "v3d_depth_to_u16_range_batch",
+    "v3d_depth_to_u16_range_batch", "v3d_temporal_motion", "v3d_temporal_filter_mc_batch",
     "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
     "v3d_fill_holes_ws_bytes", "v3d_fill_holes_disp16_batch",
     "v3d_png_stream_bound", "v3d_png_out_bytes", "v3d_png_ws_bytes", "v3d_png_deflate_batch",
@@ -140,6 +140,8 @@ def lib():
         L.v3d_temporal_range.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
         L.v3d_temporal_filter_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
         L.v3d_depth_to_u16_range_batch.argtypes = [vp, ci, sz, sz, vp, vp, vp]
+        L.v3d_temporal_motion.argtypes = [vp, sz, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+        L.v3d_temporal_filter_mc_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
         L.v3d_depth_robust_minmax_ws_bytes.argtypes = [ci]
         L.v3d_depth_robust_minmax_ws_bytes.restype = sz
         L.v3d_depth_robust_minmax_batch.argtypes = [vp, ci, sz, sz, ci, vp, vp, vp]
@@ -725,6 +727,57 @@ def temporal_filter_batch(depth, gray, radius, tau, cut, fill=True, t0=0, n=None
         _check(lib().v3d_temporal_filter_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
                                                _dev(cut, torch.uint8, "cut"), _dev(out, torch.float32, "out"), _stream()),
                "v3d_temporal_filter_batch")
+    return out
+
+
+TEMPORAL_MAX_SEARCH = 32
+
+
+def temporal_motion(gray, search, cut_threshold=20):
+    """left gray u8 [T,H,W] -> (forward fields, backward fields) int16 [T,BH,BW,2] as (dx,dy) per 16x16 block, the compensated
+    residual int64 [T] and the scene-cut flags u8 [T] it gives, all on the device (v3d_temporal_motion; `search` = S pixels per
+    frame step, 1..32).  Bit-exact contract: tests/temporal_mc_ref.py."""
+    if isinstance(search, bool) or int(search) != search or not 1 <= search <= TEMPORAL_MAX_SEARCH:
+        raise ValueError(f"motion search radius must be an integer in [1, {TEMPORAL_MAX_SEARCH}], got {search!r}")
+    if not 0 <= cut_threshold <= 256:
+        raise ValueError(f"cut threshold must be in [0, 256], got {cut_threshold}")
+    g, gs = _clip(gray, torch.uint8, "gray")
+    T, H, W = gray.shape
+    BH, BW = -(-H // 16), -(-W // 16)
+    fwd = torch.empty((T, BH, BW, 2), dtype=torch.int16, device=gray.device)
+    bwd = torch.empty((T, BH, BW, 2), dtype=torch.int16, device=gray.device)
+    resid = torch.empty(T, dtype=torch.int64, device=gray.device)
+    cut = torch.empty(T, dtype=torch.uint8, device=gray.device)
+    with torch.cuda.device(gray.device):
+        _check(lib().v3d_temporal_motion(g, gs, T, W, H, int(search), int(cut_threshold), _dev(fwd, torch.int16, "mv_fwd"),
+                                         _dev(bwd, torch.int16, "mv_bwd"), _dev(resid, torch.int64, "resid"),
+                                         _dev(cut, torch.uint8, "cut"), _stream()), "v3d_temporal_motion")
+    return fwd, bwd, resid, cut
+
+
+def temporal_filter_mc_batch(depth, gray, radius, tau, cut, mv_fwd, mv_bwd, fill=True, t0=0, n=None, out=None):
+    """temporal_filter_batch with every neighbouring frame read along the chained block vectors of temporal_motion's fields
+    (v3d_temporal_filter_mc_batch).  Bit-exact contract: tests/temporal_mc_ref.py."""
+    d, ds = _clip(depth, torch.float32, "depth")
+    g, gs = _clip(gray, torch.uint8, "gray")
+    T, H, W = depth.shape
+    if tuple(gray.shape) != (T, H, W) or tuple(cut.shape) != (T,):
+        raise NativeError(f"gray {tuple(gray.shape)} / cut {tuple(cut.shape)} do not match depth {tuple(depth.shape)}")
+    fshape = (T, -(-H // 16), -(-W // 16), 2)
+    if tuple(mv_fwd.shape) != fshape or tuple(mv_bwd.shape) != fshape:
+        raise NativeError(f"fields {tuple(mv_fwd.shape)} / {tuple(mv_bwd.shape)}: expected {fshape}")
+    n = _temporal_window(T, t0, n, radius)
+    if not 1 <= tau <= 255:
+        raise ValueError(f"temporal tau must be in [1, 255], got {tau}")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.float32, device=depth.device)
+    if tuple(out.shape) != (n, H, W):
+        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    with torch.cuda.device(depth.device):
+        _check(lib().v3d_temporal_filter_mc_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
+                                                  _dev(cut, torch.uint8, "cut"), _dev(mv_fwd, torch.int16, "mv_fwd"),
+                                                  _dev(mv_bwd, torch.int16, "mv_bwd"), _dev(out, torch.float32, "out"), _stream()),
+               "v3d_temporal_filter_mc_batch")
     return out
 
 

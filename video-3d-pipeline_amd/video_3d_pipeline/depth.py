@@ -309,17 +309,25 @@ class HipStereoBackend:
         """frames carried from earlier passes (or None) + the frames of this pass -> one private device buffer"""
         return new.clone() if held is None else self.torch.cat([held, new])
 
-    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill, range_quantile=10000, observe=None):
+    def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill, range_quantile=10000, observe=None,
+                           motion_search=0):
         """buffer of T frames (device depth f32 and left gray u8 [T,H,W]) -> device u16 samples (int16-viewed) [n,H,W] of
         targets t0 .. t0+n-1: cuts, per-frame min/max, clip-stable range, filter, normalisation -- nine launches on the
         current stream, nothing comes back to the host.  range_quantile < 10000: the per-frame max is the robust white point
         (three launches in place of the min/max's three).  observe (--quality-report): called with the filtered depth and the
-        targets' gray before the normalisation"""
+        targets' gray before the normalisation.  motion_search > 0 (--temporal-motion): the block matcher's fields and the cuts
+        of its residual (three launches in place of the cuts' three) and the compensated filter in place of the filter"""
         nat = self.native
-        cut = nat.temporal_cuts(gray, cut_threshold)
+        if motion_search > 0:
+            fwd, bwd, _, cut = nat.temporal_motion(gray, motion_search, cut_threshold)
+        else:
+            cut = nat.temporal_cuts(gray, cut_threshold)
         mm = nat.depth_robust_minmax_batch(depth, range_quantile) if range_quantile < 10000 else nat.depth_minmax_batch(depth)
         lohi = nat.temporal_range(mm, cut, radius, t0, n)
-        filt = nat.temporal_filter_batch(depth, gray, radius, tau, cut, fill, t0, n)
+        if motion_search > 0:
+            filt = nat.temporal_filter_mc_batch(depth, gray, radius, tau, cut, fwd, bwd, fill, t0, n)
+        else:
+            filt = nat.temporal_filter_batch(depth, gray, radius, tau, cut, fill, t0, n)
         if observe is not None:
             observe(filt, gray[t0:t0 + n])
         return nat.depth_to_u16_range_batch(filt, lohi)
@@ -385,11 +393,13 @@ class HybridStereoDepthExtractor:
                  quality_report=None,
                  quality_bad_threshold: int = 16,
                  quality_still: int = 4,
-                 quality_jump: float = 1.0):
+                 quality_jump: float = 1.0,
+                 temporal_motion: int = 0):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
-        on its own, the reference's behaviour.  process_frame_batch / save_depth_map stay per-frame: a list of pairs is not a clip.
+        on its own, the reference's behaviour.  temporal_motion > 0 (needs a radius): the window follows the motion a block
+        matcher finds, search radius in pixels per frame step.  process_frame_batch / save_depth_map stay per-frame: a list of pairs is not a clip.
         range_percentile < 100 (process_video_sbs only): the white point of the 16-bit normalisation is that percentile of the
         valid disparities instead of the maximum; 100 = the reference's min-max.
         fill_holes (every surface, process_frame_batch included: it is per frame): the matcher's invalid pixels are filled from
@@ -401,8 +411,9 @@ class HybridStereoDepthExtractor:
         output and no cache key changes """
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
-        from .temporal import check_parameters, check_range_percentile
+        from .temporal import check_motion_search, check_parameters, check_range_percentile
         self.temporal = check_parameters(temporal_radius, temporal_tau, temporal_cut, temporal_fill)
+        self.motion_search = check_motion_search(temporal_motion, self.temporal[0])
         self.range_quantile = check_range_percentile(range_percentile)
         if not isinstance(fill_holes, (bool, np.bool_)):
             raise ValueError(f"fill_holes must be a bool, got {fill_holes!r}")
@@ -505,7 +516,7 @@ class HybridStereoDepthExtractor:
         from .temporal import manifest_entry
         extra = {}
         if self.temporal[0] > 0 or self.range_quantile < 10000:
-            extra["temporal"] = manifest_entry(*self.temporal, self.range_quantile)
+            extra["temporal"] = manifest_entry(*self.temporal, self.range_quantile, self.motion_search)
         if self.fill_holes:
             extra["fill_holes"] = True
         if self.guide_check is not None and self.guide_check.summary is not None:
@@ -565,7 +576,7 @@ class HybridStereoDepthExtractor:
         robust range on, the key also carries their parameters, so such maps and the reference's never share a directory) """
         from .temporal import cache_suffix, fill_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
-        cache_key += cache_suffix(*self.temporal, self.range_quantile) + fill_suffix(self.fill_holes)
+        cache_key += cache_suffix(*self.temporal, self.range_quantile, self.motion_search) + fill_suffix(self.fill_holes)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -744,7 +755,8 @@ class HybridStereoDepthExtractor:
         if block is not None:
             from .temporal import BlockStabilizer
             observe = {"observe": quality.note_stabilised} if quality is not None and world == 1 else {}
-            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile, **observe)
+            motion = {"motion_search": self.motion_search} if self.motion_search > 0 else {}
+            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile, **observe, **motion)
         frames = iter_frames(video_path, start_frame + first, count, stride=stride, offset=offset) if count else iter(())
         provider = self._guidance_provider()
         self.last_decoded_frames = 0

@@ -128,9 +128,11 @@ class SbsTo4kDepthPipeline:
                  quality_report=None,
                  quality_bad_threshold: int = 16,
                  quality_still: int = 4,
-                 quality_jump: float = 1.0):
+                 quality_jump: float = 1.0,
+                 temporal_motion: int = 0):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
-        temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own);
+        temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own; temporal_motion > 0: the
+        window follows the block matcher's motion);
         range_percentile: the depth CLI's robust white point (100 = off: the maximum);
         fill_holes: the depth CLI's hole filling of the int16 disparity (off: invalid pixels stay depth 0);
         png_encoder: "gpu" deflates every PNG this run writes on the device (png_gpu.py); "zlib" = on the writer threads;
@@ -149,7 +151,7 @@ class SbsTo4kDepthPipeline:
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
             temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes,
             png_encoder=png_encoder, quality_report=quality_report, quality_bad_threshold=quality_bad_threshold,
-            quality_still=quality_still, quality_jump=quality_jump)
+            quality_still=quality_still, quality_jump=quality_jump, temporal_motion=temporal_motion)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
         self.check_guide, self.check_guide_min = bool(check_guide), float(check_guide_min)

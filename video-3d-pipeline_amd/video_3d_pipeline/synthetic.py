@@ -178,3 +178,30 @@ def temporal_sbs_clip(W, H, n_frames, **kw):
 
     sbs = np.concatenate([squeeze(L), squeeze(R)], axis=2)
     return np.ascontiguousarray(np.repeat(sbs[..., None], 3, axis=3))
+
+
+def temporal_pan_clip(W, H, n_frames, pan, **kw):
+    """temporal_clip under a camera pan of `pan` pixels per frame: the clip at width W + |pan| (n_frames - 1) with both eyes
+    and the ground truth cropped to W columns at offset pan * t (from the right end backward for a negative pan), so the whole
+    scene moves by -pan pixels per frame while its disparity stays what it was"""
+    pan, span = int(pan), abs(int(pan)) * (n_frames - 1)
+    L, R, G = temporal_clip(W + span, H, n_frames, **kw)
+    off = [pan * t if pan >= 0 else span + pan * t for t in range(n_frames)]
+
+    def crop(a):
+        return np.stack([a[t][:, off[t]:off[t] + W] for t in range(n_frames)])
+
+    return crop(L), crop(R), crop(G)
+
+
+def temporal_pan_sbs_clip(W, H, n_frames, pan, **kw):
+    """temporal_pan_clip as side-by-side BGR frames [n,H,W,3] u8, squeezed like temporal_sbs_clip"""
+    assert W % 2 == 0
+    L, R, _ = temporal_pan_clip(W, H, n_frames, pan, **kw)
+
+    def squeeze(a):
+        a = a.astype(np.uint16)
+        return ((a[..., 0::2] + a[..., 1::2] + 1) >> 1).astype(np.uint8)
+
+    sbs = np.concatenate([squeeze(L), squeeze(R)], axis=2)
+    return np.ascontiguousarray(np.repeat(sbs[..., None], 3, axis=3))

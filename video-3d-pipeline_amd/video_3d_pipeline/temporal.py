@@ -11,6 +11,12 @@ moves in the 3D video.  With a radius this stage sits on the device between `sbs
 
 All of it is integer arithmetic with a bit-exact contract (include/v3d_hip.h; tests/temporal_ref.py restates it).
 
+`--temporal-motion S` (opt-in, needs a radius; S in 1..32 pixels per frame step) compensates the window for motion: a block
+matcher finds one vector per 16x16 luma block between adjacent frames, forward and backward; a neighbouring frame is read where
+the target's block went (the vectors chained step by step), and a scene cut is what the matcher cannot explain (the compensated
+residual above `cut_threshold` levels per pixel) rather than what moved.  A pan or a moving object then keeps its neighbours
+(contract: include/v3d_hip.h, tests/temporal_mc_ref.py).
+
 `--range-percentile P` (opt-in, with or without a radius) makes the white point of that normalisation robust: a frame's "max"
 becomes the P-th percentile of its valid disparities, so a few mismatched pixels no longer set the scale of every sample
 (contract: include/v3d_hip.h, tests/range_ref.py).  Everything after the per-frame (min, max) is unchanged.
@@ -24,6 +30,7 @@ cut into passes.  Frames before the first pushed frame and after the last one do
 """
 
 MAX_RADIUS = 8
+MAX_MOTION_SEARCH = 32
 DEFAULT_TAU = 12
 DEFAULT_CUT = 20
 RANGE_Q_MIN, RANGE_Q_OFF = 5000, 10000      # the range percentile in parts per 10000; 10000 = the maximum = off
@@ -38,6 +45,15 @@ def check_parameters(radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = D
     return int(radius), int(tau), int(cut_threshold), bool(fill)
 
 
+def check_motion_search(motion_search, radius: int) -> int:
+    """--temporal-motion S: an integer in [0, 32], 0 = off; S > 0 needs a radius"""
+    if isinstance(motion_search, bool) or int(motion_search) != motion_search or not 0 <= motion_search <= MAX_MOTION_SEARCH:
+        raise ValueError(f"temporal motion search must be an integer in [0, {MAX_MOTION_SEARCH}], got {motion_search!r}")
+    if motion_search > 0 and radius < 1:
+        raise ValueError("--temporal-motion needs --temporal-radius of at least 1")
+    return int(motion_search)
+
+
 def check_range_percentile(percentile) -> int:
     """--range-percentile P, a number in [50, 100] with at most two decimals -> q = P in parts per 10000; 100 means off"""
     if isinstance(percentile, bool) or not isinstance(percentile, (int, float)):
@@ -50,14 +66,18 @@ def check_range_percentile(percentile) -> int:
     return int(q)
 
 
-def cache_suffix(radius: int, tau: int, cut_threshold: int, fill: bool, range_quantile: int = RANGE_Q_OFF) -> str:
+def cache_suffix(radius: int, tau: int, cut_threshold: int, fill: bool, range_quantile: int = RANGE_Q_OFF, motion_search: int = 0) -> str:
     """what the depth cache key gains when the stage or the robust range is on ('' when off: the reference's key unchanged)"""
     s = f"_temporal_r{radius}_t{tau}_c{cut_threshold}_f{int(bool(fill))}" if radius > 0 else ""
+    if radius > 0 and motion_search > 0:
+        s += f"_m{motion_search}"
     return s + (f"_rangeq{range_quantile}" if range_quantile < RANGE_Q_OFF else "")
 
 
-def manifest_entry(radius: int, tau: int, cut_threshold: int, fill: bool, range_quantile: int = RANGE_Q_OFF) -> dict:
+def manifest_entry(radius: int, tau: int, cut_threshold: int, fill: bool, range_quantile: int = RANGE_Q_OFF, motion_search: int = 0) -> dict:
     entry = {"radius": radius, "tau": tau, "cut_threshold": cut_threshold, "fill": bool(fill)}
+    if motion_search > 0:
+        entry["motion_search"] = motion_search
     if range_quantile < RANGE_Q_OFF:
         entry["range_quantile"] = range_quantile
     return entry
@@ -70,11 +90,13 @@ class TemporalStabilizer:
     `backend.temporal_concat` and `backend.temporal_stabilize`."""
 
     def __init__(self, backend, radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True,
-                 range_quantile: int = RANGE_Q_OFF, observe=None):
+                 range_quantile: int = RANGE_Q_OFF, observe=None, motion_search: int = 0):
         """observe (--quality-report): a callable the backend's temporal_stabilize calls with the filtered depth and the targets'
-        gray; None (the default) adds no argument to that call"""
+        gray; None (the default) adds no argument to that call.  motion_search (--temporal-motion): S > 0 adds the keyword
+        `motion_search=S` to that call; 0 (the default) adds nothing"""
         self.observe = observe
         self.radius, self.tau, self.cut_threshold, self.fill = check_parameters(radius, tau, cut_threshold, fill)
+        self.motion_search = check_motion_search(motion_search, self.radius)
         if isinstance(range_quantile, bool) or int(range_quantile) != range_quantile or not RANGE_Q_MIN <= range_quantile <= RANGE_Q_OFF:
             raise ValueError(f"range quantile must be an integer in [{RANGE_Q_MIN}, {RANGE_Q_OFF}], got {range_quantile!r}")
         self.range_quantile = int(range_quantile)
@@ -94,7 +116,10 @@ class TemporalStabilizer:
         args = (self._depth, self._gray, self._next - self._first, n, self.radius, self.tau, self.cut_threshold, self.fill)
         if self.range_quantile < RANGE_Q_OFF:                # off: the call a backend without the robust range knows
             args += (self.range_quantile,)
-        out = self.backend.temporal_stabilize(*args, **({} if self.observe is None else {"observe": self.observe}))
+        kw = {} if self.observe is None else {"observe": self.observe}
+        if self.motion_search > 0:                           # off: no keyword, the call every backend knows
+            kw["motion_search"] = self.motion_search
+        out = self.backend.temporal_stabilize(*args, **kw)
         self._next = upto
         return out
 
@@ -133,8 +158,9 @@ class BlockStabilizer:
     first - halo_before .. first + count + halo_after - 1 in order and gets back (frame indices, u16 samples) of the frames
     it owns; the halo frames only feed the windows."""
 
-    def __init__(self, backend, params, first: int, count: int, halo_before: int, range_quantile: int = RANGE_Q_OFF, observe=None):
-        self.stab = TemporalStabilizer(backend, *params, range_quantile, observe)
+    def __init__(self, backend, params, first: int, count: int, halo_before: int, range_quantile: int = RANGE_Q_OFF, observe=None,
+                 motion_search: int = 0):
+        self.stab = TemporalStabilizer(backend, *params, range_quantile, observe, motion_search)
         self.first, self.count = first, count
         self._at = first - halo_before           # clip index of the next frame the stabiliser returns
 
@@ -166,6 +192,10 @@ def add_temporal_arguments(parser):
                         help=f'Mean absolute luma difference (levels) between frames that counts as a scene cut (default {DEFAULT_CUT})')
     parser.add_argument('--no-temporal-fill', action='store_true',
                         help='Leave pixels that are invalid in a frame invalid instead of filling them from its neighbours')
+    parser.add_argument('--temporal-motion', type=int, default=0,
+                        help=f'Motion-compensate the temporal window: block-matching search radius in pixels per frame step, '
+                             f'1..{MAX_MOTION_SEARCH} (default 0: off, a neighbouring frame is read at the same coordinates).  Needs '
+                             '--temporal-radius; 16 covers a pan of 16 px per frame')
 
 
 def add_range_arguments(parser):
@@ -200,4 +230,4 @@ def range_options(args) -> dict:
 def temporal_options(args) -> dict:
     """parsed arguments -> the constructors' keyword arguments"""
     return dict(temporal_radius=args.temporal_radius, temporal_tau=args.temporal_tau, temporal_cut=args.temporal_cut,
-                temporal_fill=not args.no_temporal_fill)
+                temporal_fill=not args.no_temporal_fill, temporal_motion=getattr(args, "temporal_motion", 0))
