@@ -288,8 +288,8 @@ int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t frame_stri
                                      size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
                                      int convergence, int layout, uint8_t* out_bgr /* dense [n][H][outW][3] */, void* stream);
 
-/* Temporal depth stabilisation (v3d_temporal.hip): an opt-in stage between the disparity and the u16 normalisation.  A buffer
-   holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +
+/* Temporal depth stabilisation (v3d_temporal.hip, its integer arithmetic v3d_temporal_math.h): an opt-in stage between the
+   disparity and the u16 normalisation.  A buffer holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +
    u*gray_stride bytes), rows dense.  Bit-exact contract, all integers: tests/temporal_ref.py.
      d16_u(p) = (int)rint(16 D_u(p)) (half to even), valid iff >= 1; the caller keeps d16 <= 32767;
      cut[u] = 1 iff sum_p |Y_u(p) - Y_{u-1}(p)| > c*W*H (u >= 1, 64-bit integers; cut[0] = 0); frame u may contribute to target t
@@ -312,7 +312,8 @@ int v3d_temporal_range(const float* minmax, const uint8_t* cut, int T, int t0, i
 int v3d_temporal_filter_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
                               size_t gray_stride /* bytes */, int T, int W, int H, int t0, int n, int R, int tau, int fill,
                               const uint8_t* cut, float* out, void* stream);
-/* Motion compensation of the temporal window (v3d_temporal_mc.hip; `--temporal-motion S`, S in 1..32 pixels per frame step).
+/* Motion compensation of the temporal window (the block search in v3d_temporal_mc.hip, the filter in v3d_temporal.hip: one kernel
+   for both filter entries; `--temporal-motion S`, S in 1..32 pixels per frame step).
    Bit-exact contract, all integers: tests/temporal_mc_ref.py.  Blocks are 16x16 luma pixels on a grid anchored at (0,0), edge
    blocks clipped to the frame: BW = ceil(W/16), BH = ceil(H/16), n_b = a block's pixel count.
      Fields: for every frame u of the buffer and v = u+1 (forward, F_u) or v = u-1 (backward, Bk_u), every block b and candidate

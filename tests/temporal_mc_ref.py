@@ -1,5 +1,5 @@
-"""NumPy restatement of the motion-compensated temporal stabilisation contract (include/v3d_hip.h, v3d_temporal_mc.hip;
-`--temporal-motion S`).  Test infrastructure: the GPU entries and the streaming driver are compared with these functions bit for
+"""NumPy restatement of the motion-compensated temporal stabilisation contract (include/v3d_hip.h; the block search is
+v3d_temporal_mc.hip, the filter v3d_temporal.hip's one kernel; `--temporal-motion S`).  Test infrastructure: the GPU entries and the streaming driver are compared with these functions bit for
 bit.  All arithmetic is integer.  Everything the motion leaves alone (d16, the admissible window, the range weight, the
 clip-stable range, the normalisation) is tests/temporal_ref.py's.
 

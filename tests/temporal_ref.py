@@ -1,4 +1,5 @@
-"""NumPy restatement of the temporal depth stabilisation contract (include/v3d_hip.h, v3d_temporal.hip).  Test infrastructure:
+"""NumPy restatement of the temporal depth stabilisation contract (include/v3d_hip.h; the device side is v3d_temporal.hip with
+the closed forms of v3d_temporal_math.h).  Test infrastructure:
 the GPU entries and the streaming driver are compared with these functions bit for bit.  All arithmetic is integer (int64
 here; the device proves int32 enough) except the final range normalisation, which repeats v3d_depth_to_u16's float32 steps.
 

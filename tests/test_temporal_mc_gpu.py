@@ -219,6 +219,44 @@ def test_zero_fields_equal_the_uncompensated_entry(native):
         assert torch.equal(got, native.temporal_filter_batch(d, g, R, 12, c, fill)), (T, H, W, R)
 
 
+def test_both_filter_entries_refuse_the_same_arguments_alike(native):
+    """one table of bad arguments: v3d_temporal_filter_batch and v3d_temporal_filter_mc_batch return the same code, leave the
+    same v3d_last_error text and write nothing; the compensated entry also refuses null and odd-address fields"""
+    L, P = native.lib(), lambda t: t.data_ptr()
+    T, H, W = 2, 8, 8
+    depth = torch.ones((T, H, W), dtype=torch.float32, device="cuda")
+    gray = torch.zeros((T, H, W), dtype=torch.uint8, device="cuda")
+    cut = torch.zeros(T, dtype=torch.uint8, device="cuda")
+    mv = torch.zeros((T, 1, 1, 2), dtype=torch.int16, device="cuda")
+    out = torch.full((T, H, W), -7.5, dtype=torch.float32, device="cuda")
+    good = dict(depth=P(depth), ds=H * W, gray=P(gray), gs=H * W, T=T, W=W, H=H, t0=0, n=T, R=1, tau=12, fill=1, cut=P(cut), out=P(out))
+
+    def plain(a):
+        rc = L.v3d_temporal_filter_batch(a["depth"], a["ds"], a["gray"], a["gs"], a["T"], a["W"], a["H"], a["t0"], a["n"], a["R"],
+                                         a["tau"], a["fill"], a["cut"], a["out"], None)
+        return rc, L.v3d_last_error()
+
+    def comp(a, fwd=P(mv), bwd=P(mv)):
+        rc = L.v3d_temporal_filter_mc_batch(a["depth"], a["ds"], a["gray"], a["gs"], a["T"], a["W"], a["H"], a["t0"], a["n"], a["R"],
+                                            a["tau"], a["fill"], a["cut"], fwd, bwd, a["out"], None)
+        return rc, L.v3d_last_error()
+
+    table = [(dict(depth=None), b"null pointer"), (dict(gray=None), b"null pointer"), (dict(cut=None), b"null pointer"),
+             (dict(out=None), b"null pointer"), (dict(T=0), b"bad targets"), (dict(n=T + 1), b"bad targets"),
+             (dict(t0=1), b"bad targets"), (dict(R=9), b"radius 9"), (dict(tau=0), b"tau 0"), (dict(tau=256), b"tau 256"),
+             (dict(fill=2), b"fill must be 0 or 1"), (dict(ds=H * W - 1), b"frame stride"), (dict(gs=H * W - 1), b"frame stride")]
+    for bad, text in table:
+        a = dict(good, **bad)
+        got_plain, got_comp = plain(a), comp(a)
+        assert got_plain == got_comp and got_plain[0] == -1 and text in got_plain[1], (bad, got_plain, got_comp)
+    for kw, text in ((dict(fwd=None), b"null pointer"), (dict(bwd=None), b"null pointer"), (dict(fwd=P(mv) + 1), b"2-byte aligned"),
+                     (dict(bwd=P(mv) + 1), b"2-byte aligned")):
+        rc, err = comp(good, **kw)
+        assert rc == -1 and text in err, (kw, rc, err)
+    torch.cuda.synchronize()
+    assert (out == -7.5).all()
+
+
 def test_filter_on_the_panning_clip(native):
     p = _pan_clip()
     m = native.StereoSGBM(320, 120, 9)

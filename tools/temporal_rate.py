@@ -10,7 +10,8 @@ LDS atomics), alternating, and the stage at R = 2 and the radius-0 u16 step with
 
 --motion S [S ...] adds the motion-compensated window (--temporal-motion): the stage at R = 2 on one panning 34-frame pass with
 the option off (v3d_temporal_cuts + v3d_temporal_filter_batch: what the stage always was) and on at each S, alternating, and
-v3d_temporal_motion and v3d_temporal_filter_mc_batch alone.
+v3d_temporal_motion and v3d_temporal_filter_mc_batch alone, the filter with the clip's own cuts and with an all-zero cut array (full
+windows: on a pan the search may leave cuts that shorten them).
 
     python tools/temporal_rate.py [--kernel-only] [--radius 2 4] [--range-percentile 98] [--motion 8 16 32 [--motion-only]]
 """
@@ -167,17 +168,20 @@ def motion_rates(searches, R=2, rounds=3):
     out = torch.empty((NF, H, W), dtype=torch.float32, device="cuda")
     res = {"radius": R, "pan_px_per_frame": 5, "uncompensated_cuts": int(N.temporal_cuts(gray, 20).sum())}
     for S in searches:
-        off, on, search, filt = [], [], [], []
+        off, on, search, filt, full = [], [], [], [], []
         fwd, bwd, resid, cut = N.temporal_motion(gray, S, 20)
+        nocut = torch.zeros_like(cut)
         for _ in range(rounds):
             off.append(timed(lambda: be.temporal_stabilize(depth, gray, R, NF, R, 12, 20, True)) / NF)
             on.append(timed(lambda: be.temporal_stabilize(depth, gray, R, NF, R, 12, 20, True, motion_search=S)) / NF)
             search.append(timed(lambda: N.temporal_motion(gray, S, 20)) / NF)
             filt.append(timed(lambda: N.temporal_filter_mc_batch(depth, gray, R, 12, cut, fwd, bwd, True, R, NF, out)) / NF)
+            full.append(timed(lambda: N.temporal_filter_mc_batch(depth, gray, R, 12, nocut, fwd, bwd, True, R, NF, out)) / NF)
         res[f"S{S}"] = {"stage_off_us_per_frame": [round(t, 2) for t in off], "stage_on_us_per_frame": [round(t, 2) for t in on],
                         "stage_off_median": round(float(np.median(off)), 2), "stage_on_median": round(float(np.median(on)), 2),
                         "motion_entry_us_per_frame": round(float(np.median(search)), 2),
                         "filter_mc_us_per_frame": round(float(np.median(filt)), 2), "compensated_cuts": int(cut.sum()),
+                        "filter_mc_full_windows_us_per_frame": round(float(np.median(full)), 2),
                         "sad_lane_ops_per_frame": 2 * (2 * S + 1) ** 2 * W * H // 4}
     return res
 

@@ -1,24 +1,17 @@
 // v3d_temporal.hip -- temporal depth stabilisation between sbs_to_disparity and the u16 normalisation (DESIGN.md section 4,
-// "Temporal stabilisation"; contract in include/v3d_hip.h, NumPy restatement in tests/temporal_ref.py).  Per target frame t
-// and pixel p, over the frames u = t+k of the window that no scene cut separates from t:
-//   d16_u = rint(16 D_u)  (valid iff >= 1)          s_k = 3x3 edge-replicated sum of |Y_u - Y_t|  (0..2295)
+// "Temporal stabilisation" and "Motion-compensated window"; contract in include/v3d_hip.h, NumPy restatements in
+// tests/temporal_ref.py and tests/temporal_mc_ref.py).  Per target frame t and pixel p, over the frames u = t+k of the window
+// that no scene cut separates from t, frame u read at q = p (plain) or q = p + m (compensated, m the chained block vector):
+//   d16_u = rint(16 D_u(q))  (valid iff >= 1)       s_k = 3x3 edge-replicated sum of |Y_u(q + .) - Y_t(p + .)|  (0..2295)
 //   w_k = (R + 1 - |k|) * max(0, 256 - floor(256 s_k / (9 tau))) * valid      out16 = floor((2 sum w d16 + sum w) / (2 sum w))
-// All integers, so the bits do not depend on any order of evaluation; 2 Dsum + Wsum < 2^31 for R <= 8 and d16 <= 32767.
-// Cut flags and the clip-stable ranges are produced and consumed on the device: no entry synchronises.  This file holds the cuts,
-// the window range and the filter; the per-frame min/max they take (v3d_depth_minmax_batch) and the u16 samples against the
-// window range (v3d_depth_to_u16_range_batch) live in v3d_range.hip, d16 in v3d_depth_math.h.
-#include "v3d_common.h"
+// All integers, so the bits do not depend on any order of evaluation.  The closed forms are v3d_temporal_math.h's, d16 is
+// v3d_depth_math.h's.  Cut flags and the clip-stable ranges are produced and consumed on the device: no entry synchronises.
+// This file holds the cuts, the window range and the one filter kernel behind both filter entries; the block search that gives the
+// compensated window its fields and cuts is v3d_temporal_mc.hip, the per-frame min/max (v3d_depth_minmax_batch) and the u16
+// samples against the window range (v3d_depth_to_u16_range_batch) live in v3d_range.hip.
+#include "v3d_temporal_internal.h"
 
 #define TP_MAX_R 8
-
-// frames [lo, hi] that may contribute to target t: |u - t| <= R, inside [0, T), no cut in (min(t,u), max(t,u)]
-__device__ __forceinline__ void tp_admissible(const uint8_t* __restrict__ cut, int T, int t, int R, int& lo, int& hi)
-{
-    lo = hi = t;
-    const int a = max(0, t - R), b = min(T - 1, t + R);
-    while (lo - 1 >= a && !cut[lo]) lo--;
-    while (hi + 1 <= b && !cut[hi + 1]) hi++;
-}
 
 // ---- scene cuts: per-pair sum of absolute luma differences (64-bit integer, one atomic per workgroup), then the compare ----
 __global__ void k_tp_zero(unsigned long long* s, int n)
@@ -59,9 +52,17 @@ __global__ __launch_bounds__(256) void k_tp_sad(const uint8_t* __restrict__ gray
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(sums + u, part[0] + part[1] + part[2] + part[3]);
 }
-__global__ void k_tp_cutflag(const unsigned long long* __restrict__ sums, int T, unsigned long long thresh, uint8_t* __restrict__ cut)
+__global__ void k_tp_cutflag(const unsigned long long* __restrict__ sums, int T, int c, size_t npx, uint8_t* __restrict__ cut)
 {
-    for (int u = blockIdx.x * 256 + threadIdx.x; u < T; u += gridDim.x * 256) cut[u] = (u >= 1 && sums[u] > thresh) ? 1 : 0;
+    for (int u = blockIdx.x * 256 + threadIdx.x; u < T; u += gridDim.x * 256) cut[u] = (u >= 1 && v3d_tp_is_cut(sums[u], c, npx)) ? 1 : 0;
+}
+void v3d_tp_launch_zero(unsigned long long* sums, int T, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_tp_zero, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, sums, T);
+}
+void v3d_tp_launch_cutflag(const unsigned long long* sums, int T, int c, size_t npx, uint8_t* cut, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_tp_cutflag, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, sums, T, c, npx, cut);
 }
 
 extern "C" int v3d_temporal_cuts(const uint8_t* gray, size_t gray_stride, int T, int W, int H, int c, void* ws, uint8_t* cut_out,
@@ -75,7 +76,7 @@ extern "C" int v3d_temporal_cuts(const uint8_t* gray, size_t gray_stride, int T,
     if (((uintptr_t)ws & 7) != 0) { v3d_set_error("workspace must be 8-byte aligned"); return V3D_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* sums = reinterpret_cast<unsigned long long*>(ws);
-    hipLaunchKernelGGL(k_tp_zero, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, sums, T);
+    v3d_tp_launch_zero(sums, T, st);
     if (T > 1) {
         const int vec = (((uintptr_t)gray & 15) == 0 && (gray_stride & 15) == 0) ? 1 : 0;
         const size_t want = (npx + 4095) / 4096;                             // one 16-px step per lane fills a block with 4096 px
@@ -83,7 +84,7 @@ extern "C" int v3d_temporal_cuts(const uint8_t* gray, size_t gray_stride, int T,
         const int bx = (int)(want < per ? (want ? want : 1) : per);
         hipLaunchKernelGGL(k_tp_sad, dim3(bx, T - 1), dim3(256), 0, st, gray, gray_stride, npx, vec, sums);
     }
-    hipLaunchKernelGGL(k_tp_cutflag, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, sums, T, (unsigned long long)c * npx, cut_out);
+    v3d_tp_launch_cutflag(sums, T, c, npx, cut_out, st);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }
@@ -94,7 +95,7 @@ __global__ void k_tp_range(const float* __restrict__ mm, const uint8_t* __restri
 {
     for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
         int a, b;
-        tp_admissible(cut, T, t0 + j, R, a, b);
+        v3d_tp_admissible(cut, T, t0 + j, R, &a, &b);
         float lo = mm[2 * a], hi = mm[2 * a + 1];
         for (int u = a + 1; u <= b; u++) {
             const float l = mm[2 * u], h = mm[2 * u + 1];
@@ -121,41 +122,57 @@ extern "C" int v3d_temporal_range(const float* minmax, const uint8_t* cut, int T
     return V3D_OK;
 }
 
-// ---- the filter (the hot kernel) ----
-// One lane owns 4 horizontally adjacent pixels of one row of one target; a 64 x 4 workgroup covers 256 x 4 px.  A gray row
-// segment is the dword of the 4 pixels plus its left and right neighbours (edge-replicated) packed into 48 bits {hi, lo};
-// pixel i's three horizontal neighbours are the 24-bit window (hi:lo) >> 8i, and |Y_u - Y_t| over them is one v_sad_u8
-// on the masked windows (the fourth byte is zero on both sides).  Three rows accumulate into the 3x3 sum.
-// floor(256 s / (9 tau)) = (256 s * mul) >> 32 with mul = ceil(2^32 / (9 tau)): exact for s <= 2295 because the excess
-// 256 s e / (9 tau 2^32), e < 9 tau, stays below 2^20 / 2^32, far under the 1 / (9 tau) a quotient's fraction leaves
-// (tests/test_temporal_ref.py checks every s and tau).
+// ---- the filter (the hot kernel), plain (MC = false: frame u read at p, the fields unused) and compensated (MC = true) ----
+// One lane owns 4 horizontally adjacent pixels of one row of one target (one 16x16 block, so one vector m); a 64 x 4 workgroup
+// covers 256 x 4 px.  A gray row segment is the dword of the 4 pixels plus its left and right neighbours (edge-replicated) packed
+// into 48 bits {hi, lo}; pixel i's three horizontal neighbours are the 24-bit window (hi:lo) >> 8i, and |Y_u - Y_t| over them is
+// one v_sad_u8 on the masked windows (the fourth byte is zero on both sides).  Three rows accumulate into the 3x3 sum.
+// The window is walked as u = t, t+1 .. uhi, then t-1 .. ulo: the order in which a compensated lane chains m, one int16 pair per
+// step, forward from t and then backward from t (integer sums: the order of the taps does not matter).
 // VEC: W, both frame strides and all base addresses allow dword gray loads and 16-byte depth loads / stores; the other
-// instantiation loads and stores element by element (odd widths, unaligned views).
-template <bool VEC>
+// instantiation loads and stores element by element (odd widths, unaligned views).  A displaced segment starts at x + m.x, any
+// alignment: VEC lanes whose columns lie inside the row take one unaligned dword, or one 16-byte depth load, every other lane
+// goes column by column, gray clamped to the row, depth outside the row invalid (weight 0).
+struct __attribute__((packed, aligned(1))) tp_u32u { uint32_t v; };
+struct __attribute__((packed, aligned(4))) tp_f4u { float v[4]; };
+
+template <bool VEC, bool MC>
 __device__ __forceinline__ void tp_gray_row(const uint8_t* __restrict__ row, int x, int W, uint32_t& lo, uint32_t& hi)
 {
+    const int w1 = W - 1;
     uint32_t c;
-    if (VEC) c = *reinterpret_cast<const uint32_t*>(row + x);
-    else c = (uint32_t)row[x] | ((uint32_t)row[min(x + 1, W - 1)] << 8) | ((uint32_t)row[min(x + 2, W - 1)] << 16)
-             | ((uint32_t)row[min(x + 3, W - 1)] << 24);
-    const uint32_t L = row[max(x - 1, 0)], Rb = row[min(x + 4, W - 1)];
+    if (VEC && (!MC || (x >= 0 && x + 3 < W))) c = reinterpret_cast<const tp_u32u*>(row + x)->v;
+    else c = (uint32_t)row[min(max(x, 0), w1)] | ((uint32_t)row[min(max(x + 1, 0), w1)] << 8)
+             | ((uint32_t)row[min(max(x + 2, 0), w1)] << 16) | ((uint32_t)row[min(max(x + 3, 0), w1)] << 24);
+    const uint32_t L = row[min(max(x - 1, 0), w1)], Rb = row[min(max(x + 4, 0), w1)];
     lo = L | (c << 8);
     hi = (c >> 24) | (Rb << 8);
 }
 
-template <bool VEC>
+// one step of the chain: m += the field's vector of the block that holds clamp(c_b + m)
+__device__ __forceinline__ void tp_step(const int16_t* __restrict__ field, int BW, int W, int H, int cbx, int cby, int& mx, int& my)
+{
+    const int px = min(max(cbx + mx, 0), W - 1) >> 4, py = min(max(cby + my, 0), H - 1) >> 4;
+    const int16_t* f = field + ((size_t)py * BW + px) * 2;
+    mx += f[0];
+    my += f[1];
+}
+
+template <bool VEC, bool MC>
 __global__ __launch_bounds__(256) void k_tp_filter(const float* __restrict__ depth, size_t dstride, const uint8_t* __restrict__ gray,
                                                    size_t gstride, int T, int W, int H, int t0, int R, uint32_t mul, int fill,
-                                                   const uint8_t* __restrict__ cut, float* __restrict__ out)
+                                                   const uint8_t* __restrict__ cut, const int16_t* __restrict__ mv_fwd,
+                                                   const int16_t* __restrict__ mv_bwd, float* __restrict__ out)
 {
     const int t = t0 + blockIdx.z;
     const int x = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int y = blockIdx.y * 4 + threadIdx.y;
     if (x >= W || y >= H) return;
     int ulo, uhi;
-    tp_admissible(cut, T, t, R, ulo, uhi);
-    const size_t r0 = (size_t)max(y - 1, 0) * W, r1 = (size_t)y * W, r2 = (size_t)min(y + 1, H - 1) * W;
-    const size_t rows[3] = { r0, r1, r2 };
+    v3d_tp_admissible(cut, T, t, R, &ulo, &uhi);
+    const int BW = (W + 15) >> 4, BH = (H + 15) >> 4;
+    const size_t fsz = (size_t)BW * BH * 2;
+    const int cbx = min((x & ~15) + 8, W - 1), cby = min((y & ~15) + 8, H - 1);
 
     uint32_t ref[3][4];
     {
@@ -163,55 +180,57 @@ __global__ __launch_bounds__(256) void k_tp_filter(const float* __restrict__ dep
 #pragma unroll
         for (int r = 0; r < 3; r++) {
             uint32_t lo, hi;
-            tp_gray_row<VEC>(g + rows[r], x, W, lo, hi);
+            tp_gray_row<VEC, MC>(g + (size_t)min(max(y + r - 1, 0), H - 1) * W, x, W, lo, hi);
 #pragma unroll
             for (int i = 0; i < 4; i++) ref[r][i] = alignbit(hi, lo, 8 * i) & 0xFFFFFFu;
         }
     }
     uint32_t Wsum[4] = { 0, 0, 0, 0 }, Dsum[4] = { 0, 0, 0, 0 };
     bool centre[4] = { false, false, false, false };
-    for (int u = ulo; u <= uhi; u++) {
+    const int nf = uhi - t, nb = t - ulo;
+    int mx = 0, my = 0;                                     // stay 0 without MC
+    for (int j = 0; j <= nf + nb; j++) {                    // u = t, t+1 .. uhi, then t-1 .. ulo
+        const int u = j <= nf ? t + j : t - (j - nf);
+        if (MC) {
+            if (j == nf + 1) mx = my = 0;
+            if (j > nf) tp_step(mv_bwd + (size_t)(u + 1) * fsz, BW, W, H, cbx, cby, mx, my);
+            else if (j >= 1) tp_step(mv_fwd + (size_t)(u - 1) * fsz, BW, W, H, cbx, cby, mx, my);
+        }
+        const int qx = x + mx, qy = y + my;
+        if (MC && (qy < 0 || qy >= H || qx + 3 < 0 || qx >= W)) continue;   // every tap outside the frame: weight 0
         uint32_t s[4] = { 0, 0, 0, 0 };
         if (u != t) {
             const uint8_t* g = gray + (size_t)u * gstride;
 #pragma unroll
             for (int r = 0; r < 3; r++) {
                 uint32_t lo, hi;
-                tp_gray_row<VEC>(g + rows[r], x, W, lo, hi);
+                tp_gray_row<VEC, MC>(g + (size_t)min(max(qy + r - 1, 0), H - 1) * W, qx, W, lo, hi);
 #pragma unroll
                 for (int i = 0; i < 4; i++) s[i] = __builtin_amdgcn_sad_u8(alignbit(hi, lo, 8 * i) & 0xFFFFFFu, ref[r][i], s[i]);
             }
         }
-        const float* dp = depth + (size_t)u * dstride + r1 + x;
+        const float* dp = depth + (size_t)u * dstride + (size_t)qy * W;
         float d[4];
-        if (VEC) {
-            const float4 v = *reinterpret_cast<const float4*>(dp);
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        if (VEC && (!MC || (qx >= 0 && qx + 3 < W))) {
+            const tp_f4u v = *reinterpret_cast<const tp_f4u*>(dp + qx);
+            d[0] = v.v[0]; d[1] = v.v[1]; d[2] = v.v[2]; d[3] = v.v[3];
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; i++) d[i] = x + i < W ? dp[i] : 0.f;
+            for (int i = 0; i < 4; i++) d[i] = (qx + i >= 0 && qx + i < W) ? dp[qx + i] : 0.f;
         }
-        const int k = u - t;
-        const uint32_t tw = (uint32_t)(R + 1 - (k < 0 ? -k : k));
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int d16 = (int)v3d_d16(d[i]);
-            const bool valid = d16 >= 1;
-            if (u == t) centre[i] = valid;
-            const uint32_t q = __umulhi(s[i] << 8, mul);
-            const uint32_t w = valid ? tw * (q >= 256u ? 0u : 256u - q) : 0u;
+            if (u == t) centre[i] = d16 >= 1;
+            const uint32_t w = v3d_tp_weight(s[i], mul, R, u - t, d16);
             Wsum[i] += w;
-            Dsum[i] += w * (uint32_t)(valid ? d16 : 0);
+            Dsum[i] += w * (uint32_t)d16;                   // w = 0 where d16 is invalid
         }
     }
     float o[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        uint32_t q = Wsum[i] ? (2u * Dsum[i] + Wsum[i]) / (2u * Wsum[i]) : 0u;
-        if (!fill && !centre[i]) q = 0u;
-        o[i] = __fmul_rn((float)q, 0.0625f);
-    }
-    float* op = out + (size_t)blockIdx.z * W * H + r1 + x;
+    for (int i = 0; i < 4; i++) o[i] = __fmul_rn((float)v3d_tp_quotient(Wsum[i], Dsum[i], fill, centre[i]), 0.0625f);
+    float* op = out + (size_t)blockIdx.z * W * H + (size_t)y * W + x;
     if (VEC) *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
     else {
 #pragma unroll
@@ -219,26 +238,40 @@ __global__ __launch_bounds__(256) void k_tp_filter(const float* __restrict__ dep
     }
 }
 
-extern "C" int v3d_temporal_filter_batch(const float* depth, size_t depth_stride, const uint8_t* gray, size_t gray_stride, int T,
-                                         int W, int H, int t0, int n, int R, int tau, int fill, const uint8_t* cut, float* out,
-                                         void* stream)
+// both filter entries: the checks, the VEC decision and the launch; `mc` adds the two fields
+static int tp_filter(const float* depth, size_t depth_stride, const uint8_t* gray, size_t gray_stride, int T, int W, int H, int t0, int n,
+                     int R, int tau, int fill, const uint8_t* cut, bool mc, const int16_t* mv_fwd, const int16_t* mv_bwd, float* out,
+                     void* stream)
 {
-    if (!depth || !gray || !cut || !out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
+    if (!depth || !gray || !cut || !out || (mc && (!mv_fwd || !mv_bwd))) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
     if (W < 1 || H < 1) { v3d_set_error("bad geometry %dx%d", W, H); return V3D_ERR_ARG; }
     if (tp_check_window(T, t0, n, R) != V3D_OK) return V3D_ERR_ARG;
     if (tau < 1 || tau > 255) { v3d_set_error("tau %d outside [1, 255]", tau); return V3D_ERR_ARG; }
     if (fill != 0 && fill != 1) { v3d_set_error("fill must be 0 or 1"); return V3D_ERR_ARG; }
     const size_t npx = (size_t)W * H;
     if (T > 1 && (depth_stride < npx || gray_stride < npx)) { v3d_set_error("frame stride below the frame size %zu", npx); return V3D_ERR_ARG; }
+    if (mc && (((uintptr_t)mv_fwd | (uintptr_t)mv_bwd) & 1) != 0) { v3d_set_error("the fields must be 2-byte aligned"); return V3D_ERR_ARG; }
     if (v3d_cdiv(H, 4) > 65535) { v3d_set_error("height %d not supported", H); return V3D_ERR_UNSUPPORTED; }
-    const uint32_t mul = (uint32_t)((((uint64_t)1 << 32) + 9u * (uint32_t)tau - 1u) / (9u * (uint32_t)tau));
     const bool vec = (W & 3) == 0 && (depth_stride & 3) == 0 && (gray_stride & 3) == 0 && ((uintptr_t)depth & 15) == 0
                      && ((uintptr_t)gray & 3) == 0 && ((uintptr_t)out & 15) == 0;
-    const dim3 grid(v3d_cdiv(W, 256), v3d_cdiv(H, 4), n), block(64, 4);
-    if (vec) hipLaunchKernelGGL(k_tp_filter<true>, grid, block, 0, (hipStream_t)stream, depth, depth_stride, gray, gray_stride, T, W, H,
-                                t0, R, mul, fill, cut, out);
-    else hipLaunchKernelGGL(k_tp_filter<false>, grid, block, 0, (hipStream_t)stream, depth, depth_stride, gray, gray_stride, T, W, H,
-                            t0, R, mul, fill, cut, out);
+    const auto kernel = mc ? (vec ? k_tp_filter<true, true> : k_tp_filter<false, true>)
+                           : (vec ? k_tp_filter<true, false> : k_tp_filter<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(W, 256), v3d_cdiv(H, 4), n), dim3(64, 4), 0, (hipStream_t)stream, depth, depth_stride, gray,
+                       gray_stride, T, W, H, t0, R, v3d_tp_rw_magic(tau), fill, cut, mv_fwd, mv_bwd, out);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
+}
+
+extern "C" int v3d_temporal_filter_batch(const float* depth, size_t depth_stride, const uint8_t* gray, size_t gray_stride, int T,
+                                         int W, int H, int t0, int n, int R, int tau, int fill, const uint8_t* cut, float* out,
+                                         void* stream)
+{
+    return tp_filter(depth, depth_stride, gray, gray_stride, T, W, H, t0, n, R, tau, fill, cut, false, nullptr, nullptr, out, stream);
+}
+
+extern "C" int v3d_temporal_filter_mc_batch(const float* depth, size_t depth_stride, const uint8_t* gray, size_t gray_stride, int T,
+                                            int W, int H, int t0, int n, int R, int tau, int fill, const uint8_t* cut,
+                                            const int16_t* mv_fwd, const int16_t* mv_bwd, float* out, void* stream)
+{
+    return tp_filter(depth, depth_stride, gray, gray_stride, T, W, H, t0, n, R, tau, fill, cut, true, mv_fwd, mv_bwd, out, stream);
 }

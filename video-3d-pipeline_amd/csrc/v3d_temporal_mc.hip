@@ -1,36 +1,15 @@
-// v3d_temporal_mc.hip -- motion compensation for the temporal depth stabilisation (`--temporal-motion S`; DESIGN.md section 4,
-// "Motion-compensated window"; contract in include/v3d_hip.h, NumPy restatement in tests/temporal_mc_ref.py).
-//   v3d_temporal_motion           block-matching fields between adjacent frames of the buffer, the compensated residual and the
-//                                 scene cuts it gives;
-//   v3d_temporal_filter_mc_batch  v3d_temporal_filter_batch with frame u = t+k read at q = p + m, m the block's vector chained
-//                                 over the |k| steps from t to u.
+// v3d_temporal_mc.hip -- the block search behind the motion-compensated temporal window (`--temporal-motion S`; DESIGN.md
+// section 4, "Motion-compensated window"; contract in include/v3d_hip.h, NumPy restatement in tests/temporal_mc_ref.py).
+//   v3d_temporal_motion  block-matching fields between adjacent frames of the buffer, the compensated residual and the scene
+//                        cuts it gives (the zeroing of the residual and the cut flags are v3d_temporal.hip's kernels).
+// The filter that reads along the fields, v3d_temporal_filter_mc_batch, is k_tp_filter<VEC, true> in v3d_temporal.hip.
 // Blocks are 16x16 luma pixels anchored at (0,0), edge blocks clipped.  All integers: the bits do not depend on any order.
-#include "v3d_common.h"
-#include "v3d_depth_math.h"
+#include "v3d_temporal_internal.h"
 
-#define MC_MAX_R 8
 #define MC_MAX_S 32
 #define MC_NB 4                                            // horizontally adjacent blocks per workgroup: one wavefront each
 #define MC_WIN_ROWS (16 + 2 * MC_MAX_S)
 #define MC_WIN_PITCH (16 * MC_NB + 2 * MC_MAX_S + 4)       // bytes; + 4: the fifth dword a shifted 16-byte row read touches
-
-// frames [lo, hi] that may contribute to target t: |u - t| <= R, inside [0, T), no cut in (min(t,u), max(t,u)]
-__device__ __forceinline__ void mc_admissible(const uint8_t* __restrict__ cut, int T, int t, int R, int& lo, int& hi)
-{
-    lo = hi = t;
-    const int a = max(0, t - R), b = min(T - 1, t + R);
-    while (lo - 1 >= a && !cut[lo]) lo--;
-    while (hi + 1 <= b && !cut[hi + 1]) hi++;
-}
-
-__global__ void k_mc_zero(unsigned long long* s, int n)
-{
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) s[i] = 0ull;
-}
-__global__ void k_mc_cutflag(const unsigned long long* __restrict__ resid, int T, unsigned long long thresh, uint8_t* __restrict__ cut)
-{
-    for (int u = blockIdx.x * 256 + threadIdx.x; u < T; u += gridDim.x * 256) cut[u] = (u >= 1 && resid[u] > thresh) ? 1 : 0;
-}
 
 // ---- the search (the hot kernel) ----
 // A workgroup of four wavefronts owns four horizontally adjacent blocks of frame u in one direction (v = u + 1 or u - 1); grid
@@ -162,159 +141,10 @@ extern "C" int v3d_temporal_motion(const uint8_t* gray, size_t gray_stride, int 
     const int BW = v3d_cdiv(W, 16), BH = v3d_cdiv(H, 16);
     if (BH > 65535) { v3d_set_error("frame %dx%d not supported", W, H); return V3D_ERR_UNSUPPORTED; }
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mc_zero, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, resid, T);
+    v3d_tp_launch_zero(resid, T, st);
     hipLaunchKernelGGL(k_mc_search, dim3(2 * v3d_cdiv(BW, MC_NB), BH, T), dim3(256), 0, st, gray, gray_stride, T, W, H, S, BW, BH, mv_fwd,
                        mv_bwd, resid);
-    hipLaunchKernelGGL(k_mc_cutflag, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, resid, T, (unsigned long long)c * npx, cut_out);
-    V3D_LAUNCH_CHECK();
-    return V3D_OK;
-}
-
-// ---- the compensated filter ----
-// k_tp_filter's lane (4 horizontally adjacent pixels of one row of one target: one block, so one vector m) with frame u read at
-// q = p + m.  The lane chains m itself, one int16 pair per step, forward from t and then backward from t (integer sums: the order
-// of the taps does not matter).  A gray row segment of frame u starts at x + m.x, any alignment: VEC lanes whose six columns lie
-// inside the row take one unaligned dword and two bytes, every other lane clamps column by column.  The depth taps likewise: one
-// 16-byte load where the four columns lie inside the row, else element by element with the outside ones at weight 0.
-struct __attribute__((packed, aligned(1))) mc_u32u { uint32_t v; };
-struct __attribute__((packed, aligned(4))) mc_f4u { float v[4]; };
-
-template <bool VEC>
-__device__ __forceinline__ void mc_gray_row(const uint8_t* __restrict__ row, int x, int W, uint32_t& lo, uint32_t& hi)
-{
-    uint32_t c;
-    if (VEC && x >= 0 && x + 3 < W) c = reinterpret_cast<const mc_u32u*>(row + x)->v;
-    else {
-        const int w1 = W - 1;
-        c = (uint32_t)row[min(max(x, 0), w1)] | ((uint32_t)row[min(max(x + 1, 0), w1)] << 8)
-            | ((uint32_t)row[min(max(x + 2, 0), w1)] << 16) | ((uint32_t)row[min(max(x + 3, 0), w1)] << 24);
-    }
-    const uint32_t L = row[min(max(x - 1, 0), W - 1)], Rb = row[min(max(x + 4, 0), W - 1)];
-    lo = L | (c << 8);
-    hi = (c >> 24) | (Rb << 8);
-}
-
-__device__ __forceinline__ void mc_step(const int16_t* __restrict__ field, int BW, int BH, int W, int H, int cbx, int cby, int& mx, int& my)
-{
-    const int px = min(max(cbx + mx, 0), W - 1) >> 4, py = min(max(cby + my, 0), H - 1) >> 4;
-    const int16_t* f = field + ((size_t)py * BW + px) * 2;
-    mx += f[0];
-    my += f[1];
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_mc_filter(const float* __restrict__ depth, size_t dstride, const uint8_t* __restrict__ gray,
-                                                   size_t gstride, int T, int W, int H, int t0, int R, uint32_t mul, int fill,
-                                                   const uint8_t* __restrict__ cut, const int16_t* __restrict__ mv_fwd,
-                                                   const int16_t* __restrict__ mv_bwd, float* __restrict__ out)
-{
-    const int t = t0 + blockIdx.z;
-    const int x = (blockIdx.x * 64 + threadIdx.x) * 4;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= W || y >= H) return;
-    int ulo, uhi;
-    mc_admissible(cut, T, t, R, ulo, uhi);
-    const int BW = (W + 15) >> 4, BH = (H + 15) >> 4;
-    const size_t fsz = (size_t)BW * BH * 2;
-    const int cbx = min((x & ~15) + 8, W - 1), cby = min((y & ~15) + 8, H - 1);
-
-    uint32_t ref[3][4];
-    {
-        const uint8_t* g = gray + (size_t)t * gstride;
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            uint32_t lo, hi;
-            mc_gray_row<VEC>(g + (size_t)min(max(y + r - 1, 0), H - 1) * W, x, W, lo, hi);
-#pragma unroll
-            for (int i = 0; i < 4; i++) ref[r][i] = alignbit(hi, lo, 8 * i) & 0xFFFFFFu;
-        }
-    }
-    uint32_t Wsum[4] = { 0, 0, 0, 0 }, Dsum[4] = { 0, 0, 0, 0 };
-    bool centre[4] = { false, false, false, false };
-    const int nf = uhi - t, nb = t - ulo;
-    int mx = 0, my = 0;
-    for (int j = 0; j <= nf + nb; j++) {                    // u = t, t+1 .. uhi, then t-1 .. ulo
-        int u;
-        if (j <= nf) {
-            u = t + j;
-            if (j >= 1) mc_step(mv_fwd + (size_t)(u - 1) * fsz, BW, BH, W, H, cbx, cby, mx, my);
-        } else {
-            if (j == nf + 1) mx = my = 0;
-            u = t - (j - nf);
-            mc_step(mv_bwd + (size_t)(u + 1) * fsz, BW, BH, W, H, cbx, cby, mx, my);
-        }
-        const int qx = x + mx, qy = y + my;
-        if (qy < 0 || qy >= H || qx + 3 < 0 || qx >= W) continue;           // every tap outside the frame: weight 0
-        uint32_t s[4] = { 0, 0, 0, 0 };
-        if (u != t) {
-            const uint8_t* g = gray + (size_t)u * gstride;
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                uint32_t lo, hi;
-                mc_gray_row<VEC>(g + (size_t)min(max(qy + r - 1, 0), H - 1) * W, qx, W, lo, hi);
-#pragma unroll
-                for (int i = 0; i < 4; i++) s[i] = __builtin_amdgcn_sad_u8(alignbit(hi, lo, 8 * i) & 0xFFFFFFu, ref[r][i], s[i]);
-            }
-        }
-        const float* dp = depth + (size_t)u * dstride + (size_t)qy * W;
-        float d[4];
-        if (VEC && qx >= 0 && qx + 3 < W) {
-            const mc_f4u v = *reinterpret_cast<const mc_f4u*>(dp + qx);
-            d[0] = v.v[0]; d[1] = v.v[1]; d[2] = v.v[2]; d[3] = v.v[3];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) d[i] = (qx + i >= 0 && qx + i < W) ? dp[qx + i] : 0.f;      // outside: invalid, weight 0
-        }
-        const int k = u - t;
-        const uint32_t tw = (uint32_t)(R + 1 - (k < 0 ? -k : k));
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int d16 = (int)v3d_d16(d[i]);
-            const bool valid = d16 >= 1;
-            if (u == t) centre[i] = valid;
-            const uint32_t q = __umulhi(s[i] << 8, mul);
-            const uint32_t w = valid ? tw * (q >= 256u ? 0u : 256u - q) : 0u;
-            Wsum[i] += w;
-            Dsum[i] += w * (uint32_t)(valid ? d16 : 0);
-        }
-    }
-    float o[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        uint32_t q = Wsum[i] ? (2u * Dsum[i] + Wsum[i]) / (2u * Wsum[i]) : 0u;
-        if (!fill && !centre[i]) q = 0u;
-        o[i] = __fmul_rn((float)q, 0.0625f);
-    }
-    float* op = out + (size_t)blockIdx.z * W * H + (size_t)y * W + x;
-    if (VEC) *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
-    else {
-#pragma unroll
-        for (int i = 0; i < 4; i++) if (x + i < W) op[i] = o[i];
-    }
-}
-
-extern "C" int v3d_temporal_filter_mc_batch(const float* depth, size_t depth_stride, const uint8_t* gray, size_t gray_stride, int T,
-                                            int W, int H, int t0, int n, int R, int tau, int fill, const uint8_t* cut,
-                                            const int16_t* mv_fwd, const int16_t* mv_bwd, float* out, void* stream)
-{
-    if (!depth || !gray || !cut || !mv_fwd || !mv_bwd || !out) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
-    if (W < 1 || H < 1) { v3d_set_error("bad geometry %dx%d", W, H); return V3D_ERR_ARG; }
-    if (T < 1 || T > 65535 || t0 < 0 || n < 1 || n > T - t0) { v3d_set_error("bad targets: T=%d t0=%d n=%d", T, t0, n); return V3D_ERR_ARG; }
-    if (R < 0 || R > MC_MAX_R) { v3d_set_error("radius %d outside [0, %d]", R, MC_MAX_R); return V3D_ERR_ARG; }
-    if (tau < 1 || tau > 255) { v3d_set_error("tau %d outside [1, 255]", tau); return V3D_ERR_ARG; }
-    if (fill != 0 && fill != 1) { v3d_set_error("fill must be 0 or 1"); return V3D_ERR_ARG; }
-    const size_t npx = (size_t)W * H;
-    if (T > 1 && (depth_stride < npx || gray_stride < npx)) { v3d_set_error("frame stride below the frame size %zu", npx); return V3D_ERR_ARG; }
-    if ((((uintptr_t)mv_fwd | (uintptr_t)mv_bwd) & 1) != 0) { v3d_set_error("the fields must be 2-byte aligned"); return V3D_ERR_ARG; }
-    if (v3d_cdiv(H, 4) > 65535) { v3d_set_error("height %d not supported", H); return V3D_ERR_UNSUPPORTED; }
-    const uint32_t mul = (uint32_t)((((uint64_t)1 << 32) + 9u * (uint32_t)tau - 1u) / (9u * (uint32_t)tau));
-    const bool vec = (W & 3) == 0 && (depth_stride & 3) == 0 && (gray_stride & 3) == 0 && ((uintptr_t)depth & 15) == 0
-                     && ((uintptr_t)gray & 3) == 0 && ((uintptr_t)out & 15) == 0;
-    const dim3 grid(v3d_cdiv(W, 256), v3d_cdiv(H, 4), n), block(64, 4);
-    if (vec) hipLaunchKernelGGL(k_mc_filter<true>, grid, block, 0, (hipStream_t)stream, depth, depth_stride, gray, gray_stride, T, W, H,
-                                t0, R, mul, fill, cut, mv_fwd, mv_bwd, out);
-    else hipLaunchKernelGGL(k_mc_filter<false>, grid, block, 0, (hipStream_t)stream, depth, depth_stride, gray, gray_stride, T, W, H,
-                            t0, R, mul, fill, cut, mv_fwd, mv_bwd, out);
+    v3d_tp_launch_cutflag(resid, T, c, npx, cut_out, st);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }

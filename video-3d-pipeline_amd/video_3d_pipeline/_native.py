@@ -708,14 +708,17 @@ def temporal_range(minmax, cut, radius, t0=0, n=None):
     return out
 
 
-def temporal_filter_batch(depth, gray, radius, tau, cut, fill=True, t0=0, n=None, out=None):
-    """the temporal filter (v3d_temporal_filter_batch): depth f32 [T,H,W] (<= 0 invalid), left gray u8 [T,H,W], cut u8 [T] ->
-    filtered depth f32 [n,H,W] of targets t0 .. t0+n-1.  Bit-exact contract: tests/temporal_ref.py."""
+def _temporal_filter_args(depth, gray, radius, tau, cut, t0, n, out, fields=None):
+    """what both temporal filters check and prepare: the two clips, cut (and the two motion fields, if given) against them, the
+    window, tau and `out` -> ((depth pointer, stride, gray pointer, stride, T, W, H, n), out)"""
     d, ds = _clip(depth, torch.float32, "depth")
     g, gs = _clip(gray, torch.uint8, "gray")
     T, H, W = depth.shape
     if tuple(gray.shape) != (T, H, W) or tuple(cut.shape) != (T,):
         raise NativeError(f"gray {tuple(gray.shape)} / cut {tuple(cut.shape)} do not match depth {tuple(depth.shape)}")
+    fshape = (T, -(-H // 16), -(-W // 16), 2)
+    if fields is not None and any(tuple(f.shape) != fshape for f in fields):
+        raise NativeError(f"fields {tuple(fields[0].shape)} / {tuple(fields[1].shape)}: expected {fshape}")
     n = _temporal_window(T, t0, n, radius)
     if not 1 <= tau <= 255:
         raise ValueError(f"temporal tau must be in [1, 255], got {tau}")
@@ -723,6 +726,13 @@ def temporal_filter_batch(depth, gray, radius, tau, cut, fill=True, t0=0, n=None
         out = torch.empty((n, H, W), dtype=torch.float32, device=depth.device)
     if tuple(out.shape) != (n, H, W):
         raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    return (d, ds, g, gs, T, W, H, n), out
+
+
+def temporal_filter_batch(depth, gray, radius, tau, cut, fill=True, t0=0, n=None, out=None):
+    """the temporal filter (v3d_temporal_filter_batch): depth f32 [T,H,W] (<= 0 invalid), left gray u8 [T,H,W], cut u8 [T] ->
+    filtered depth f32 [n,H,W] of targets t0 .. t0+n-1.  Bit-exact contract: tests/temporal_ref.py."""
+    (d, ds, g, gs, T, W, H, n), out = _temporal_filter_args(depth, gray, radius, tau, cut, t0, n, out)
     with torch.cuda.device(depth.device):
         _check(lib().v3d_temporal_filter_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
                                                _dev(cut, torch.uint8, "cut"), _dev(out, torch.float32, "out"), _stream()),
@@ -758,21 +768,7 @@ def temporal_motion(gray, search, cut_threshold=20):
 def temporal_filter_mc_batch(depth, gray, radius, tau, cut, mv_fwd, mv_bwd, fill=True, t0=0, n=None, out=None):
     """temporal_filter_batch with every neighbouring frame read along the chained block vectors of temporal_motion's fields
     (v3d_temporal_filter_mc_batch).  Bit-exact contract: tests/temporal_mc_ref.py."""
-    d, ds = _clip(depth, torch.float32, "depth")
-    g, gs = _clip(gray, torch.uint8, "gray")
-    T, H, W = depth.shape
-    if tuple(gray.shape) != (T, H, W) or tuple(cut.shape) != (T,):
-        raise NativeError(f"gray {tuple(gray.shape)} / cut {tuple(cut.shape)} do not match depth {tuple(depth.shape)}")
-    fshape = (T, -(-H // 16), -(-W // 16), 2)
-    if tuple(mv_fwd.shape) != fshape or tuple(mv_bwd.shape) != fshape:
-        raise NativeError(f"fields {tuple(mv_fwd.shape)} / {tuple(mv_bwd.shape)}: expected {fshape}")
-    n = _temporal_window(T, t0, n, radius)
-    if not 1 <= tau <= 255:
-        raise ValueError(f"temporal tau must be in [1, 255], got {tau}")
-    if out is None:
-        out = torch.empty((n, H, W), dtype=torch.float32, device=depth.device)
-    if tuple(out.shape) != (n, H, W):
-        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    (d, ds, g, gs, T, W, H, n), out = _temporal_filter_args(depth, gray, radius, tau, cut, t0, n, out, (mv_fwd, mv_bwd))
     with torch.cuda.device(depth.device):
         _check(lib().v3d_temporal_filter_mc_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
                                                   _dev(cut, torch.uint8, "cut"), _dev(mv_fwd, torch.int16, "mv_fwd"),
