@@ -23,6 +23,18 @@ def stereo_gains(max_shift=48.0, convergence=0.5, eye_split=0.5):
     return gl, gr, math.floor(convergence * 65535 + 0.5)
 
 
+def far_key_scene():
+    """(F, D, gains) of a 2048 x 2 frame (8 targets per thread, 512 per wave) whose nearest key lies more than one wave's run
+    away or does not exist: the near half (65535) moves 600 px.  Row 0: a 600-target hole at [1024, 1624) in the left eye, a
+    600-target tail without a right neighbour in the right eye; row 1 mirrors it (a head without a left neighbour)."""
+    W, H = 2048, 2
+    F = np.random.default_rng(W).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    D = np.zeros((H, W), np.uint16)
+    D[0, 1024:] = 65535
+    D[1, :1024] = 65535
+    return F, D, stereo_gains(1200, 0.0, 0.5)
+
+
 def eye_keys(depth, gain, conv):
     """u16 depth [H,W] -> the filled key rows K [H,W] (int64 holding the u32 keys)"""
     D = np.asarray(depth).astype(np.int64)

@@ -1,6 +1,6 @@
-"""csrc/v3d_png.hip itself, without a GPU: the kernel source is compiled as plain C++ against tests/png_emu/v3d_common.h, where
-the 256 threads of a workgroup are fibers and barriers / wave shuffles are rendezvous, and v3d_png_deflate_batch is called on
-poisoned host buffers at the alignments the header grants.  `out` and `offsets` must equal tests/png_ref.py byte for byte --
+"""csrc/v3d_png.hip itself (with csrc/v3d_wave.h), without a GPU: the kernel source is compiled as plain C++ against
+tests/png_emu/v3d_common.h, where the 256 threads of a workgroup are fibers and barriers / wave shuffles are rendezvous, and
+v3d_png_deflate_batch is called on poisoned host buffers at the alignments the header grants.  `out` and `offsets` must equal tests/png_ref.py byte for byte --
 streams, zero gaps, zero tail --, nothing outside `out`, `offsets` and `ws` may change, and every 16-byte load must be aligned.
 This checks the kernels' arithmetic and indexing; what only the device can show (LDS atomics, real wave scheduling, speed) is
 left to tests/test_png_gpu.py and tests/test_png_guard_gpu.py."""
@@ -28,7 +28,7 @@ def emu(tmp_path_factory):
     decl = "extern __shared__ __attribute__((aligned(16))) uint8_t smem[];"
     assert text.count(decl) == 1
     (d / "v3d_png.cpp").write_text(text.replace(decl, "extern uint8_t smem[];"))       # the harness defines it, 16-byte aligned
-    for name, src in (("v3d_png_books.h", CSRC), ("v3d_common.h", EMU), ("harness.cpp", EMU)):
+    for name, src in (("v3d_png_books.h", CSRC), ("v3d_wave.h", CSRC), ("v3d_common.h", EMU), ("harness.cpp", EMU)):
         shutil.copy(os.path.join(src, name), d / name)
     lib = d / "libpngemu.so"
     subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-o", str(lib),

@@ -59,6 +59,13 @@ def test_small_sizes_bit_exact(native, W, H):
                        f"{W}x{H} {kind} g=({gl},{gr}) conv={conv} layout={layout}")
 
 
+def test_nearest_key_beyond_a_wave_or_absent(native):
+    """holes and row ends 600 targets wide at 8 targets per thread: the scan's answer comes from another wave or is 'none'"""
+    F, D, (gl, gr, conv) = R.far_key_scene()
+    for layout in (R.FULL_SBS, R.HALF_SBS):
+        _check(_gpu(native, F, D, gl, gr, conv, layout), R.render(F, D, gl, gr, conv, layout), f"far keys, layout {layout}")
+
+
 def _frame_4k():
     from video_3d_pipeline import synthetic as syn
     g = syn.guide_frame(1920, 1080, 0).astype(np.int32)                          # 3840 x 2160 luma of the left view

@@ -111,3 +111,18 @@ def test_half_sbs_rounds_half_up():
     assert out[0, :2].tolist() == [[2, 255, 1], [0, 8, 201]] and np.array_equal(out[0, 2:], out[0, :2])
     with pytest.raises(ValueError):
         R.render(_frame(1, 5), np.zeros((1, 5), np.uint16), 0, 0, 0, R.HALF_SBS)
+
+
+def test_far_key_scene_has_the_gaps_it_promises():
+    """the targets nothing lands on, per row and eye, straight from step 1 of the contract"""
+    F, D, (gl, gr, conv) = R.far_key_scene()
+    assert (gl, gr, conv) == (153600, -153600, 0) and D.shape == (2, 2048)
+    x = np.arange(2048)
+    def empty(y, g):
+        t = x + ((g * (D[y].astype(np.int64) - conv) + (1 << 23)) >> 24)
+        return np.setdiff1d(x, t[(t >= 0) & (t < 2048)]).tolist()
+    assert empty(0, gl) == list(range(1024, 1624)) and empty(0, gr) == list(range(1448, 2048))
+    assert empty(1, gl) == list(range(0, 600)) and empty(1, gr) == list(range(424, 1024))
+    left = R.eye_keys(D, gl, conv)
+    assert (left[0, 1024:1624] == left[0, 1023]).all()                   # between background 1023 and the block: the farther side
+    assert (left[1, :600] == left[1, 600]).all()                         # no left neighbour: the only one

@@ -42,6 +42,14 @@ def test_sizes_bit_exact(native, W, H):
                        f"{W}x{H} {kind} g=({gl},{gr}) conv={conv} layout={layout}")
 
 
+def test_nearest_key_beyond_a_wave_or_absent(native):
+    """holes and row ends 600 targets wide at 8 targets per thread: the scan's answer comes from another wave or is 'none'"""
+    from stereo_ref import far_key_scene
+    F, D, (gl, gr, conv) = far_key_scene()
+    for layout in (S.FULL_SBS, S.HALF_SBS):
+        _check(_gpu(native, F, D, gl, gr, conv, layout), S.render(F, D, gl, gr, conv, layout), f"far keys, layout {layout}")
+
+
 def test_half_sbs_at_odd_run_edges(native):
     """even widths next to the boundaries (half SBS needs them): 254, 2046, 2050, 4094, 4098"""
     for W in (254, 2046, 2050, 4094, 4098):

@@ -18,6 +18,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-3d-pipeline_amd")]
 from video_3d_pipeline import _native as N  # noqa: E402
+import envopts  # noqa: E402
+
+envopts.select_variant_lib(N)               # V3D_HIP_LIB=path: an experiment build of the library (development only)
 
 W, H, NF, REPS, HBM = 3840, 2160, 8, 20, 8.0e12
 

@@ -116,6 +116,9 @@ def main():
     res = {"books": P.K, "seeded": seeded_sizes()}
     if not a.cpu:
         import torch
+        import envopts
+        from video_3d_pipeline import _native as N
+        envopts.select_variant_lib(N)       # V3D_HIP_LIB=path: an experiment build of the library (development only)
         frames = product_frames()
         res.update(device=torch.cuda.get_device_name(0), product=device_sizes(frames), kernel=kernel_times(frames))
     line = json.dumps(res)

@@ -110,6 +110,9 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true", help="kernel times only")
     a = ap.parse_args()
     import torch
+    import envopts
+    from video_3d_pipeline import _native as N
+    envopts.select_variant_lib(N)           # V3D_HIP_LIB=path: an experiment build of the library (development only)
     res = {"device": torch.cuda.get_device_name(0), "kernel": kernel_times()}
     if not a.no_pipeline:
         res["pipeline_1080p_to_4k"] = pipeline_rate()

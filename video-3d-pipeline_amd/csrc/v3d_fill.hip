@@ -15,6 +15,7 @@
 // and every full chunk leaves as the widest store its address allows; the row's first and last chunk go element by element.
 // k_fill_empty_rows: second, small launch; reads only non-empty rows of `out` and writes only empty ones.
 #include "v3d_common.h"
+#include "v3d_wave.h"
 
 #define FH_THREADS 256
 #define FH_WAVES (FH_THREADS / 64)
@@ -97,27 +98,14 @@ __global__ __launch_bounds__(FH_THREADS) void k_fill_rows(const int16_t* in, siz
                 firstk = ((uint32_t)(WP - (p0 + i)) << 16) | d;
             }
         }
-        uint32_t p = lastk, s = firstk;                        // inclusive scans over the wave: p left to right, s right to left
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t pv = __shfl_up(p, o), sv = __shfl_down(s, o);
-            if (lane >= o) p = max(p, pv);
-            if (lane + o < 64) s = max(s, sv);
-        }
+        near2 nn = near2_incl(lastk, firstk, lane);
         uint32_t (*tot)[FH_WAVES] = sTot[y & 1];
-        if (lane == 63) tot[0][wave] = p;
-        if (lane == 0) tot[1][wave] = s;
-        const uint32_t pe = __shfl_up(p, 1), se = __shfl_down(s, 1);
-        uint32_t pre = lane > 0 ? pe : 0u, suf = lane < 63 ? se : 0u;
+        if (lane == 63) tot[0][wave] = nn.pre;
+        if (lane == 0) tot[1][wave] = nn.suf;
+        nn = near2_excl(nn, lane);
         __syncthreads();
-        uint32_t any = 0;
-#pragma unroll
-        for (int w = 0; w < FH_WAVES; ++w) {
-            const uint32_t tp = tot[0][w], ts = tot[1][w];
-            any |= tp;
-            if (w < wave) pre = max(pre, tp);
-            if (w > wave) suf = max(suf, ts);
-        }
+        const near2_any fo = near2_fold<FH_WAVES>(nn, wave, tot[0], tot[1]);
+        const uint32_t pre = fo.pre, suf = fo.suf, any = fo.any;
         if (tid == 0) frow_flags[y] = any ? 1 : 0;
 
         // select in registers: la = nearest valid at or left of i, rb[i] = nearest valid right of i

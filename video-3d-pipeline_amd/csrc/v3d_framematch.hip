@@ -5,6 +5,7 @@
 //   num[i][j] = G sum(a_i b_j) - sum(a_i) sum(b_j),   var[i] = G sum(a_i^2) - (sum a_i)^2,   G = 2304,
 // in 64-bit integers (every term < 2.3e16 < 2^63), so no bit depends on a schedule; the host divides.
 #include "v3d_common.h"
+#include "v3d_wave.h"
 
 #define FM_GW V3D_SIG_GW
 #define FM_GH V3D_SIG_GH
@@ -14,26 +15,13 @@
 // ---- signature: one workgroup per (cell row, frame).  A lane owns one 16-byte column group and every ny-th row of the cell
 // row; it keeps the 16 column sums as packed 16-bit pairs in 8 registers (a cell row has at most ceil(8192 / 36) = 228 rows:
 // 228 * 255 = 58140 < 2^16), then adds each run of columns that share a cell to the cell's sum in LDS (integer adds: the order
-// does not reach the result).  VEC: base, pitch and stride allow 16-byte loads of the groups that lie wholly inside the row;
-// the last, partial group and the whole of the other instantiation are read byte by byte, so nothing past a row's W payload
-// bytes is touched.
+// does not reach the result).  VEC: base, pitch and stride allow v3d_wave.h's row_load16 its aligned 16-byte loads.
 __device__ __forceinline__ void fm_acc(uint32_t (&acc)[8], const uint4 p)
 {
     acc[0] += p.x & 0x00FF00FFu; acc[1] += (p.x >> 8) & 0x00FF00FFu;
     acc[2] += p.y & 0x00FF00FFu; acc[3] += (p.y >> 8) & 0x00FF00FFu;
     acc[4] += p.z & 0x00FF00FFu; acc[5] += (p.z >> 8) & 0x00FF00FFu;
     acc[6] += p.w & 0x00FF00FFu; acc[7] += (p.w >> 8) & 0x00FF00FFu;
-}
-
-template <bool VEC>
-__device__ __forceinline__ uint4 fm_load(const uint8_t* __restrict__ row, int x0, int W)
-{
-    if (VEC && x0 + 16 <= W) return *reinterpret_cast<const uint4*>(row + x0);
-    uint32_t v[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        if (x0 + i < W) v[i >> 2] |= (uint32_t)row[x0 + i] << (8 * (i & 3));
-    return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
 template <bool VEC>
@@ -52,13 +40,13 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_signature(const uint8_t* __re
         uint32_t acc[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
         int r = r0 + ty;
         for (; r + 3 * ny < r1; r += 4 * ny) {                     // four rows in flight per lane
-            const uint4 a = fm_load<VEC>(base + (size_t)r * pitch, x0, W);
-            const uint4 b = fm_load<VEC>(base + (size_t)(r + ny) * pitch, x0, W);
-            const uint4 c = fm_load<VEC>(base + (size_t)(r + 2 * ny) * pitch, x0, W);
-            const uint4 d = fm_load<VEC>(base + (size_t)(r + 3 * ny) * pitch, x0, W);
+            const uint4 a = row_load16<VEC>(base + (size_t)r * pitch, x0, W);
+            const uint4 b = row_load16<VEC>(base + (size_t)(r + ny) * pitch, x0, W);
+            const uint4 c = row_load16<VEC>(base + (size_t)(r + 2 * ny) * pitch, x0, W);
+            const uint4 d = row_load16<VEC>(base + (size_t)(r + 3 * ny) * pitch, x0, W);
             fm_acc(acc, a); fm_acc(acc, b); fm_acc(acc, c); fm_acc(acc, d);
         }
-        for (; r < r1; r += ny) fm_acc(acc, fm_load<VEC>(base + (size_t)r * pitch, x0, W));
+        for (; r < r1; r += ny) fm_acc(acc, row_load16<VEC>(base + (size_t)r * pitch, x0, W));
         // column x belongs to cell (64 x + 63) / W: the largest cx with floor(cx W / 64) <= x
         int c = (64 * x0 + 63) / W, nb = ((c + 1) * W) >> 6;
         uint32_t run = 0u;
@@ -108,16 +96,6 @@ extern "C" int v3d_frame_signature_batch(const uint8_t* gray, int n, int W, int 
 }
 
 // ---- scores: one wavefront per pair (i, j), 36 cells per lane; the pair's sums fold by butterfly ----
-__device__ __forceinline__ unsigned long long fm_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, s), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), s);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(64) void k_fm_scores(const uint16_t* __restrict__ sa, const uint16_t* __restrict__ sb, int nb,
                                                   long long* __restrict__ num, long long* __restrict__ var_a,
                                                   long long* __restrict__ var_b)
@@ -134,10 +112,10 @@ __global__ __launch_bounds__(64) void k_fm_scores(const uint16_t* __restrict__ s
         aa += (unsigned long long)x * x;
         bb += (unsigned long long)y * y;
     }
-    ab = fm_wave_sum(ab);
-    const unsigned long long ta = fm_wave_sum(s_a), tb = fm_wave_sum(s_b);
-    if (j == 0) aa = fm_wave_sum(aa);
-    if (i == 0) bb = fm_wave_sum(bb);
+    ab = wave_sum_u64(ab);
+    const unsigned long long ta = wave_sum_u64(s_a), tb = wave_sum_u64(s_b);
+    if (j == 0) aa = wave_sum_u64(aa);
+    if (i == 0) bb = wave_sum_u64(bb);
     if (threadIdx.x == 0) {
         num[(size_t)i * nb + j] = (long long)(FM_G * ab) - (long long)(ta * tb);
         if (j == 0) var_a[i] = (long long)(FM_G * aa - ta * ta);

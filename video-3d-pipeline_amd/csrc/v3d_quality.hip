@@ -5,6 +5,7 @@
 // on a schedule.  Two launches per entry: workgroups over (row band, frame or pair) leave one partial record each in the
 // workspace (plain stores, no atomics, no flags), then one workgroup per frame or pair adds its partial records up.
 #include "v3d_common.h"
+#include "v3d_wave.h"
 
 #define Q_THREADS 256
 #define Q_WAVES (Q_THREADS / 64)
@@ -19,59 +20,19 @@
 static inline int q_band_rows(int W, int px) { const int g = v3d_cdiv(W, px); return Q_BAND_GROUPS / g > 1 ? Q_BAND_GROUPS / g : 1; }
 static inline int q_bands(int W, int H, int px) { return v3d_cdiv(H, q_band_rows(W, px)); }
 
-__device__ __forceinline__ unsigned long long q_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, s), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), s);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
-// a workgroup's lane partials -> its partial record: butterfly inside the wave, the waves' sums through LDS, one u64 store per field
-template <int F>
-__device__ __forceinline__ void q_block_store(const uint32_t (&acc)[F], unsigned long long* __restrict__ rec)
+// a workgroup's lane partials -> its record: butterfly inside the wave, the waves' sums through LDS, one u64 store per field
+template <int F, typename T>
+__device__ __forceinline__ void q_block_store(const T (&acc)[F], unsigned long long* __restrict__ rec)
 {
     __shared__ unsigned long long part[Q_WAVES][F];
     const int tid = threadIdx.x;
+    unsigned long long t[F];
 #pragma unroll
-    for (int k = 0; k < F; k++) {
-        const unsigned long long s = q_wave_sum(acc[k]);
-        if ((tid & 63) == 0) part[tid >> 6][k] = s;
-    }
-    __syncthreads();
-    if (tid < F) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < Q_WAVES; w++) s += part[w][tid];
-        rec[tid] = s;
-    }
+    for (int k = 0; k < F; k++) t[k] = wave_sum_u64(acc[k]);
+    const unsigned long long s = block_sum_u64<Q_WAVES, F>(t, tid & 63, tid >> 6, tid, part);
+    if (tid < F) rec[tid] = s;
 }
 
-// N payload bytes of a row from x0 on as N/4 words, zero beyond the row's W bytes.  VEC: base, pitch and strides allow one aligned
-// load of a group that lies wholly inside the row; the partial last group and unaligned planes are read byte by byte, so nothing
-// past a row's payload is touched.
-template <bool VEC>
-__device__ __forceinline__ uint4 q_load16(const uint8_t* __restrict__ row, int x0, int W)
-{
-    if (VEC && x0 + 16 <= W) return *reinterpret_cast<const uint4*>(row + x0);
-    uint32_t v[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        if (x0 + i < W) v[i >> 2] |= (uint32_t)row[x0 + i] << (8 * (i & 3));
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-template <bool VEC>
-__device__ __forceinline__ uint2 q_load8(const uint8_t* __restrict__ row, int x0, int W)
-{
-    if (VEC && x0 + 8 <= W) return *reinterpret_cast<const uint2*>(row + x0);
-    uint32_t v[2] = { 0u, 0u };
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (x0 + i < W) v[i >> 2] |= (uint32_t)row[x0 + i] << (8 * (i & 3));
-    return make_uint2(v[0], v[1]);
-}
 __device__ __forceinline__ int q_byte(const uint32_t* w, int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 0xFFu); }
 
 // ---- reprojection: integers only.  R's gather reads the right row straight from global memory: it is row-local (two
@@ -93,7 +54,7 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_reproj(const uint8_t* __restric
         const int ry = it / G, x0 = (it - ry * G) * Q_RPX, y = r0 + ry;
         const uint8_t* Rr = R + (size_t)y * pitch;
         const int16_t* Dr = D + (size_t)y * W;
-        const uint4 lv = q_load16<VEC>(L + (size_t)y * pitch, x0, W), rv = q_load16<VEC>(Rr, x0, W);
+        const uint4 lv = row_load16<VEC>(L + (size_t)y * pitch, x0, W), rv = row_load16<VEC>(Rr, x0, W);
         const uint32_t lw[4] = { lv.x, lv.y, lv.z, lv.w }, rw[4] = { rv.x, rv.y, rv.z, rv.w };
         uint32_t dw[8];
         if (VEC && x0 + Q_RPX <= W) {
@@ -164,7 +125,7 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_flicker(const float* __restrict
     for (int it = tid; it < rows * G; it += Q_THREADS) {
         const int ry = it / G, x0 = (it - ry * G) * Q_FPX;
         const size_t o = (size_t)(r0 + ry) * W;
-        const uint2 ya = q_load8<VEC>(Y0 + o, x0, W), yb = q_load8<VEC>(Y1 + o, x0, W);
+        const uint2 ya = row_load8<VEC>(Y0 + o, x0, W), yb = row_load8<VEC>(Y1 + o, x0, W);
         const uint32_t aw[2] = { ya.x, ya.y }, bw[2] = { yb.x, yb.y };
         int da[Q_FPX], db[Q_FPX];
         q_load_depth<VEC>(D0 + o, x0, W, da);
@@ -186,7 +147,6 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_flicker(const float* __restrict
 template <int F>
 __global__ __launch_bounds__(Q_THREADS) void k_q_sum(const unsigned long long* __restrict__ ws, int nb, unsigned long long* __restrict__ out)
 {
-    __shared__ unsigned long long part[Q_WAVES][F];
     const int f = blockIdx.x, tid = threadIdx.x;
     const unsigned long long* rec = ws + (size_t)f * nb * F;
     unsigned long long s[F];
@@ -195,18 +155,7 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_sum(const unsigned long long* _
     for (int b = tid; b < nb; b += Q_THREADS)
 #pragma unroll
         for (int k = 0; k < F; k++) s[k] += rec[(size_t)b * F + k];
-#pragma unroll
-    for (int k = 0; k < F; k++) {
-        const unsigned long long t = q_wave_sum(s[k]);
-        if ((tid & 63) == 0) part[tid >> 6][k] = t;
-    }
-    __syncthreads();
-    if (tid < F) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int w = 0; w < Q_WAVES; w++) t += part[w][tid];
-        out[(size_t)f * F + tid] = t;
-    }
+    q_block_store<F>(s, out + (size_t)f * F);
 }
 
 // what both entries refuse about the plane and the two pointers every call has; 0 = fine

@@ -11,6 +11,7 @@
 // Min and max are exact, every sum is an integer and the normalisation is per element, so neither the order of the atomics nor
 // the batch or block count can change a bit.  No entry synchronises or allocates.
 #include "v3d_common.h"
+#include "v3d_wave.h"
 
 #define RR_NB 2048
 #define RR_WAVES 4             // waves of a 256-lane workgroup
@@ -192,18 +193,9 @@ __global__ __launch_bounds__(256) void k_rr_select(const unsigned* __restrict__ 
     const uint4 a = h4[0], b = h4[1];
     const unsigned c[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
     const unsigned own = a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w;
-    unsigned inc = own;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)inc, o);
-        if (lane >= o) inc += v;
-    }
     __shared__ unsigned part[RR_WAVES];
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    unsigned before = inc - own, n_valid = 0;
-#pragma unroll
-    for (int w = 0; w < RR_WAVES; w++) { before += w < wave ? part[w] : 0u; n_valid += part[w]; }
+    const excl_total sc = block_excl_add_u32<RR_WAVES>(own, lane, wave, part);
+    const unsigned before = sc.excl, n_valid = sc.total;
     const float mn = v3d_ord2f(mm[2 * t]), mx = v3d_ord2f(mm[2 * t + 1]);
     if (tid == 0) { out[2 * t] = mn; if (n_valid == 0) out[2 * t + 1] = mx; }
     if (n_valid == 0) return;

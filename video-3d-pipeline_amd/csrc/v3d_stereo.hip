@@ -23,6 +23,7 @@
 //   ... and the nearest hit targets outside a thread's run are evaluated from their keys and the indices the scans yield.
 // Contract: tests/stereo_sub_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Sub-pixel DIBR".
 #include "v3d_common.h"
+#include "v3d_wave.h"
 
 #define ST_THREADS 256
 #define ST_BAND 4                 // rows per workgroup: a 4K frame is 540 workgroups, one round of the resident slots
@@ -227,24 +228,17 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
                     }
                 }
             }
-            uint32_t p = lastp, s = firstp;                    // inclusive scans over the wave: p left to right, s right to left
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t pv = __shfl_up(p, o), sv = __shfl_down(s, o);
-                if (lane >= o) p = max(p, pv);
-                if (lane + o < 64) s = max(s, sv);
-            }
-            if (lane == 63) sTot[e][0][wave] = p;
-            if (lane == 0) sTot[e][1][wave] = s;
-            const uint32_t pe = __shfl_up(p, 1), se = __shfl_down(s, 1);
-            pre[e] = lane > 0 ? pe : 0u;
-            suf[e] = lane < 63 ? se : 0u;
+            const near2 sc = near2_incl(lastp, firstp, lane);
+            if (lane == 63) sTot[e][0][wave] = sc.pre;
+            if (lane == 0) sTot[e][1][wave] = sc.suf;
+            const near2 ex = near2_excl(sc, lane);
+            pre[e] = ex.pre; suf[e] = ex.suf;
         }
         __syncthreads();
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
 #pragma unroll
-            for (int w = 0; w < ST_THREADS / 64; ++w) {
+            for (int w = 0; w < ST_THREADS / 64; ++w) {        // v3d_wave.h's near2_fold, kept here: its call costs half SBS 0.5 %
                 if (w < wave) pre[e] = max(pre[e], sTot[e][0][w]);
                 if (w > wave) suf[e] = max(suf[e], sTot[e][1][w]);
             }

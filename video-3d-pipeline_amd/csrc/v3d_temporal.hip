@@ -10,6 +10,7 @@
 // compensated window its fields and cuts is v3d_temporal_mc.hip, the per-frame min/max (v3d_depth_minmax_batch) and the u16
 // samples against the window range (v3d_depth_to_u16_range_batch) live in v3d_range.hip.
 #include "v3d_temporal_internal.h"
+#include "v3d_wave.h"
 
 #define TP_MAX_R 8
 
@@ -40,17 +41,10 @@ __global__ __launch_bounds__(256) void k_tp_sad(const uint8_t* __restrict__ gray
         const int d = (int)a[i] - (int)b[i];
         acc += (unsigned)(d < 0 ? -d : d);
     }
-    unsigned lo = (unsigned)acc, hi = (unsigned)(acc >> 32);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long o = ((unsigned long long)(unsigned)__shfl_xor((int)hi, s) << 32) | (unsigned)__shfl_xor((int)lo, s);
-        acc += o;
-        lo = (unsigned)acc; hi = (unsigned)(acc >> 32);
-    }
-    __shared__ unsigned long long part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(sums + u, part[0] + part[1] + part[2] + part[3]);
+    __shared__ unsigned long long part[4][1];
+    const unsigned long long t[1] = { wave_sum_u64(acc) };
+    const unsigned long long s = block_sum_u64<4, 1>(t, threadIdx.x & 63, threadIdx.x >> 6, threadIdx.x, part);
+    if (threadIdx.x == 0) atomicAdd(sums + u, s);
 }
 __global__ void k_tp_cutflag(const unsigned long long* __restrict__ sums, int T, int c, size_t npx, uint8_t* __restrict__ cut)
 {

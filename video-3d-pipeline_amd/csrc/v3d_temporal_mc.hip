@@ -5,6 +5,7 @@
 // The filter that reads along the fields, v3d_temporal_filter_mc_batch, is k_tp_filter<VEC, true> in v3d_temporal.hip.
 // Blocks are 16x16 luma pixels anchored at (0,0), edge blocks clipped.  All integers: the bits do not depend on any order.
 #include "v3d_temporal_internal.h"
+#include "v3d_wave.h"
 
 #define MC_MAX_S 32
 #define MC_NB 4                                            // horizontally adjacent blocks per workgroup: one wavefront each
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void k_mc_search(const uint8_t* __restrict__ g
 {
     __shared__ uint32_t win[MC_WIN_ROWS * MC_WIN_PITCH / 4];
     __shared__ uint32_t cur[MC_NB * 64];
-    __shared__ uint32_t part[MC_NB];
+    __shared__ uint32_t part[MC_NB][1];
     const int dir = blockIdx.x & 1, grp = blockIdx.x >> 1, by = blockIdx.y, u = blockIdx.z;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int bx = grp * MC_NB + wave;
@@ -105,11 +106,7 @@ __global__ __launch_bounds__(256) void k_mc_search(const uint8_t* __restrict__ g
             best = key < best ? key : best;
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)best, s);
-        best = o < best ? o : best;
-    }
+    best = wave_min_u32(best);
     uint32_t sad = 0;
     if (bx < BW) {
         const int cand = (int)(best & 8191u);
@@ -119,9 +116,9 @@ __global__ __launch_bounds__(256) void k_mc_search(const uint8_t* __restrict__ g
         if (lane == 0) { mv[2 * bx] = (int16_t)(cx - S); mv[2 * bx + 1] = (int16_t)(cy - S); }
     }
     if (dir) {                                              // resid[u]: the unpenalised SAD of Bk_u's choices, one atomic per workgroup
-        if (lane == 0) part[wave] = sad;
-        __syncthreads();
-        if (tid == 0) atomicAdd(resid + u, (unsigned long long)part[0] + part[1] + part[2] + part[3]);
+        const uint32_t t[1] = { sad };
+        const unsigned long long r = block_sum_u64<MC_NB, 1>(t, lane, wave, tid, part);
+        if (tid == 0) atomicAdd(resid + u, r);
     }
 }
 
