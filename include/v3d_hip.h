@@ -177,11 +177,37 @@ int v3d_split_sbs(const uint8_t* sbs_bgr, int W, int H, int pitch, int unsqueeze
                   uint8_t* left_bgr, uint8_t* right_bgr, void* stream);
 
 int v3d_disp_to_depth(const int16_t* disp16, size_t n, float* depth_out, void* stream);
+
+/* Non-finite input.  Every entry that takes float data states here what a NaN, +inf, -inf, -0.0, a denormal and a finite value
+   outside its range do ("Non-finite input"; pinned on the device by tests/test_nonfinite_gpu.py).  The rule:
+   where depth.py's NumPy expression defines the result, that result is the contract; where NumPy's answer is a platform accident
+   (any astype of a non-finite or out-of-range float), the contract is written out and no such conversion is ever performed.
+     Per-frame min / max (v3d_depth_minmax_batch, mn and hi of v3d_depth_robust_minmax_batch): a frame that holds any NaN, of
+       either sign and any payload, yields (NaN, NaN), as ndarray.min() / .max() do; +-inf are ordinary extrema; -0.0 sorts below
+       +0.0; denormals are ordinary values.
+     v3d_temporal_range: a NaN bound in any admissible frame gives (NaN, NaN) for that target, wherever the frame sits in the window.
+     v3d_depth_to_u16[_batch], v3d_depth_to_u16_range_batch: a range that is unordered, flat or holds a NaN gives a frame of 0; so
+       does an infinite bound (the finite samples give 0, an infinite one NaN -> 0); a NaN sample gives 0; every other sample is
+       clamped to [0, 65535] in float32 before it is converted.  So a frame with one NaN or one infinity is written as 0.
+     Fixed point d16 (temporal filters, robust histogram, flicker): a sample is valid iff 1 <= rint(16 D): NaN, -inf, -0.0, a
+       denormal and every D < 1/32 are invalid, in every entry, decided on the float before any conversion.  Robust histogram and flicker (v3d_depth_math.h's v3d_d16_tap,
+       decided on the float before any conversion): a valid sample above the range, D > 2047.9375 and +inf included, counts as
+       d16 = 32767 (the histogram keeps its own last bin, 2047).  The two temporal filters decide validity the same way, on the float, but do
+       not clamp the value (the clamp cost their kernel 3 to 4 %: DESIGN.md): their domain is D <= 2047.9375, and an output
+       pixel whose window holds a tap above it with a non-zero weight has an unspecified (finite) value; every other pixel is
+       exact, and nothing outside `out` is written.  tests/temporal_ref.py states the saturating rule; the tests mask those pixels.
+     v3d_mono_blend[_batch]: as the NumPy expression.  A NaN in the resized map makes max > min false: the frame is the stereo
+       disparity alone.  +inf in the resized map gives e = 0 at its finite pixels and NaN where the map is +inf; -inf makes every
+       pixel of the frame NaN.  The resize multiplies taps of weight 0 too: an infinity under one becomes a NaN of the resized map.
+     v3d_guided_upscale[_batch] (float input): domain finite, |v| <= 65535; a non-finite sample is read as 0 (an invalid depth).
+     v3d_quality_flicker_batch: d16 as above.
+     v3d_corr_lookup: a tap whose coordinate is not inside the plane contributes 0; a NaN, infinite or huge flow has no tap inside. */
 /* minmax_ws: device scratch of >= 2 floats */
 int v3d_depth_to_u16(const float* depth, size_t n, uint16_t* out, float* minmax_ws, void* stream);
 
 /* n frames in one fixed set of launches: frame f (frame_elems floats at depth + f*frame_stride) -> out + f*frame_elems with
-   its OWN min/max, bit-identical to v3d_depth_to_u16 on that frame alone (same order of operations, max == min -> 0).
+   its OWN min/max, bit-identical to v3d_depth_to_u16 on that frame alone (same order of operations, max == min -> 0; a frame that
+   holds a NaN or an infinity -> 0: "Non-finite input" above).
    minmax_ws: device scratch of >= 2n floats; n <= 65535 */
 int v3d_depth_to_u16_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride, uint16_t* out,
                            float* minmax_ws, void* stream);
@@ -194,7 +220,8 @@ int v3d_round_to_u16(const float* depth, size_t n, uint16_t* out, void* stream);
    arithmetic in the reference's order (bit-identical to the NumPy expression); max == min leaves the stereo disparity.
    mono: f32 [mh][mw] of any size (cv2.resize INTER_LINEAR semantics; same size = no resize).  depth.py uses 0.7 / 0.3.
    ws: device scratch of v3d_mono_blend_ws_bytes(n) bytes.  Batch: frame f at disp16 + f*W*H, mono + f*mono_stride (floats),
-   depth_out + f*W*H. */
+   depth_out + f*W*H.  A map with a NaN leaves the stereo disparity; one with an infinity puts NaN into depth_out ("Non-finite
+   input" above): what the NumPy expression gives. */
 size_t v3d_mono_blend_ws_bytes(int n);
 int v3d_mono_blend(const int16_t* disp16, int W, int H, const float* mono, int mw, int mh,
                    float w_stereo, float w_mono, float* depth_out, void* ws, void* stream);
@@ -202,6 +229,9 @@ int v3d_mono_blend_batch(const int16_t* disp16, int n, int W, int H, const float
                          float w_stereo, float w_mono, float* depth_out, void* ws, void* stream);
 
 /* guided-filter joint upsampling: depth_lo f32 [Hlo][Wlo], guide u8 luma [Hhi][Whi] -> out f32 [Hhi][Whi].
+   Domain of depth_lo: finite, |v| <= 65535 (the accuracy tests' range).  A NaN or an infinity is read as 0, an invalid depth like
+   depth.py:374's `<= 0 -> 0`, so the output is finite everywhere (the window sums slide: a NaN let in would stay for the rest of
+   its strip).  -0.0 and denormals are ordinary values.
    ws: device scratch of v3d_guided_upscale_ws_bytes(Whi, Hhi) bytes */
 size_t v3d_guided_upscale_ws_bytes(int Whi, int Hhi);
 int v3d_guided_upscale(const float* depth_lo, int Wlo, int Hlo, const uint8_t* guide, int Whi, int Hhi,
@@ -237,7 +267,9 @@ int v3d_bgr_to_gray(const uint8_t* bgr, size_t n_pixels, uint8_t* gray, void* st
 /* CREStereo-style local group correlation on the matrix cores.
    fl, fr: bf16 [h][w][C] (channel-last), flow: f32 [2][h][w], out: f32 [G*9][h][w];
    C = 64*G; pattern 0 = 1x9, 1 = 3x3.  ws: scratch of v3d_corr_ws_bytes(C,h,w) bytes.  fl_bf16, fr_bf16 and ws are accessed
-   eight channels at a time and must be 16-byte aligned (else V3D_ERR_ARG) */
+   eight channels at a time and must be 16-byte aligned (else V3D_ERR_ARG).  flow is data: any float is legal.  A tap whose
+   coordinate is not inside the plane contributes 0, so a pixel whose flow is NaN, +-inf or beyond any image (1e30, +-2^31) has a
+   warped feature of 0; the coordinate is clamped as a float before it becomes an index, and nothing outside fr is read */
 size_t v3d_corr_ws_bytes(int C, int h, int w);
 int v3d_corr_lookup(const uint16_t* fl_bf16, const uint16_t* fr_bf16, const float* flow,
                     int C, int h, int w, int G, int pattern, float* out, void* ws, void* stream);
@@ -291,22 +323,27 @@ int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t frame_stri
 /* Temporal depth stabilisation (v3d_temporal.hip, its integer arithmetic v3d_temporal_math.h): an opt-in stage between the
    disparity and the u16 normalisation.  A buffer holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +
    u*gray_stride bytes), rows dense.  Bit-exact contract, all integers: tests/temporal_ref.py.
-     d16_u(p) = (int)rint(16 D_u(p)) (half to even), valid iff >= 1; the caller keeps d16 <= 32767;
+     d16_u(p) = (int)rint(16 D_u(p)) (half to even), valid iff >= 1: NaN, -inf, -0.0 and denormals are invalid.  Domain:
+       D <= 2047.9375 (d16 <= 32767).  A target pixel whose window holds a tap above it (+inf included) with a non-zero weight
+       has an unspecified finite value; nothing else is affected;
      cut[u] = 1 iff sum_p |Y_u(p) - Y_{u-1}(p)| > c*W*H (u >= 1, 64-bit integers; cut[0] = 0); frame u may contribute to target t
        iff |u - t| <= R, 0 <= u < T and no cut lies in (min(t,u), max(t,u)];
      s_k(p) = 3x3 edge-replicated sum of |Y_{t+k} - Y_t|, rw_k = max(0, 256 - floor(256 s_k / (9 tau))), tw_k = R + 1 - |k|,
        w_k = tw_k * rw_k * valid(d16_{t+k}(p)); out16 = floor((2 sum w d16 + sum w) / (2 sum w)), 0 if sum w = 0 or (fill = 0 and
-       d16_t(p) invalid); output depth = out16 / 16 (exact in float32).  int32 holds every sum for R <= 8.
+       d16_t(p) invalid); output depth = out16 / 16 (exact in float32), finite whatever the input holds.
+       int32 holds every sum for R <= 8 and d16 <= 32767.
    Every entry enqueues on `stream`, never synchronises, never allocates, and takes device pointers only.
    V3D_ERR_ARG: null pointer, T outside [1, 65535], W or H < 1, targets outside the buffer, R outside [0, 8], tau outside [1, 255],
    c outside [0, 256], fill not 0/1, a stride below the frame size (T > 1). */
 /* cut_out u8 [T]; ws: device scratch of >= 8*T bytes, 8-byte aligned */
 int v3d_temporal_cuts(const uint8_t* gray, size_t gray_stride /* bytes */, int T, int W, int H, int c, void* ws,
                       uint8_t* cut_out, void* stream);
-/* minmax_out f32 [T][2]: min and max of each frame, the exact values v3d_depth_to_u16_batch reduces */
+/* minmax_out f32 [T][2]: min and max of each frame, the exact values v3d_depth_to_u16_batch reduces; (NaN, NaN) for a frame that
+   holds any NaN, +-inf as ordinary extrema, -0.0 below +0.0 */
 int v3d_depth_minmax_batch(const float* depth, int T, size_t frame_elems, size_t frame_stride /* elements */, float* minmax_out,
                            void* stream);
-/* lohi_out f32 [n][2] for targets t0 .. t0+n-1: min of the minima, max of the maxima over the frames that may contribute */
+/* lohi_out f32 [n][2] for targets t0 .. t0+n-1: min of the minima, max of the maxima over the frames that may contribute;
+   (NaN, NaN) if any bound of any of those frames is NaN, whatever the frame's position in the window */
 int v3d_temporal_range(const float* minmax, const uint8_t* cut, int T, int t0, int n, int R, float* lohi_out, void* stream);
 /* out f32 dense [n][H][W]: the filtered depth of targets t0 .. t0+n-1, windows clipped to [0, T) */
 int v3d_temporal_filter_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
@@ -340,7 +377,8 @@ int v3d_temporal_filter_mc_batch(const float* depth, size_t depth_stride /* elem
                                  const uint8_t* cut, const int16_t* mv_fwd, const int16_t* mv_bwd, float* out, void* stream);
 /* v3d_depth_to_u16_batch with frame f's (min, max) read from lohi[2f], lohi[2f+1] instead of reduced from the frame: same
    float32 operations in the same order, hi == lo -> 0, the result clamped to [0, 65535] before the conversion.  With a frame's
-   own min and max it reproduces v3d_depth_to_u16_batch bit for bit.  out dense [n][frame_elems]; n <= 65535 */
+   own min and max it reproduces v3d_depth_to_u16_batch bit for bit.  lohi = (-inf, inf), (NaN, x), (x, NaN), (inf, inf) or any
+   other range that is not finite and ordered gives a frame of 0; a NaN sample gives 0.  out dense [n][frame_elems]; n <= 65535 */
 int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, size_t frame_stride /* elements */,
                                  const float* lohi, uint16_t* out, void* stream);
 
@@ -350,7 +388,8 @@ int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t frame_elems, 
      hist[b] = #{p: d16(p) == b} for 1 <= b <= 2046, hist[2047] = #{p: d16(p) >= 2047}; n_valid = sum hist;
      k = max(1, ceil(q * n_valid / 10000)) (64-bit); hi16 = the smallest b with hist[1] + .. + hist[b] >= k;
      mn, mx = the frame's float min and max exactly as v3d_depth_minmax_batch gives them (the min includes the invalid zeros);
-     hi = mx if n_valid == 0 or hi16 == 2047, else max((float)hi16 / 16, mn).
+     hi = mx if n_valid == 0 or hi16 == 2047, else max((float)hi16 / 16, mn); a frame that holds a NaN gives (NaN, NaN); NaN and
+     -inf are invalid (not counted), +inf and every D >= 2047/16 land in hist[2047].
    minmax_out f32 [T][2] = (mn, hi): the layout v3d_temporal_range and v3d_depth_to_u16_range_batch read.  At most
    n_valid - k valid pixels of a frame lie above its hi; on depths that are multiples of 1/16 below 2047/16, q = 10000 gives mx.
    ws: device scratch of v3d_depth_robust_minmax_ws_bytes(T) bytes, 16-byte aligned.  Enqueues three launches on `stream`,
@@ -451,8 +490,8 @@ int v3d_signature_scores(const uint16_t* sig_a, int na, const uint16_t* sig_b, i
    holds the ssd of at most 258 pixels (a lane sums at most 128 before widening); over 8192 x 65535 pixels every field stays
    below 2^53.  No floating point anywhere in this entry.
    Flicker: the buffers the temporal entries take -- depth f32 (frame u at depth + u*depth_stride elements) and gray u8 (frame u
-   at gray + u*gray_stride bytes), rows dense, T >= 2.  d16 = v3d_d16(D) = rint(16 D), valid iff >= 1 (NaN and <= 0 are
-   invalid); the caller keeps d16 <= 32767, as in the temporal contract.  Record of pair u (frames u and u+1), u64 [4]:
+   at gray + u*gray_stride bytes), rows dense, T >= 2.  d16 = v3d_d16_tap(D): rint(16 D), valid iff >= 1 (NaN, -inf and <= 0 are
+   invalid), +inf and every value above 32767 count as 32767 (the temporal filters do not saturate: "Non-finite input" above).  Record of pair u (frames u and u+1), u64 [4]:
      0 luma_sad = sum_p |Y_{u+1} - Y_u| over all pixels (the sum v3d_temporal_cuts thresholds: the host applies the same cut rule);
      1 n_still = #{p: |Y_{u+1} - Y_u| <= still and both d16 valid};  2 flicker = sum over those of |d16_{u+1} - d16_u|;
      3 n_jump = #{those with |d16_{u+1} - d16_u| > jump16}.

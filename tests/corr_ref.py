@@ -106,8 +106,12 @@ def weights(flow):
     sx = np.arange(w, dtype=np.float32)[None, :] + flow[0]
     sy = np.arange(h, dtype=np.float32)[:, None] + flow[1]
     fx, fy = np.floor(sx), np.floor(sy)
-    wx, wy = sx - fx, sy - fy
-    ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+    with np.errstate(invalid="ignore"):                    # inf - inf: such a position has no tap inside the image anyway
+        wx, wy = sx - fx, sy - fy
+    # a tap whose coordinate is not inside the plane contributes 0, and a NaN, an infinity or a value no integer holds is not
+    # inside: decided on the floats, so that only coordinates near the image are ever converted ((-2, -2) has all taps outside)
+    near = (fx >= -1) & (fx <= w) & (fy >= -1) & (fy <= h)
+    ix, iy = np.where(near, fx, -2).astype(np.int64), np.where(near, fy, -2).astype(np.int64)
     wt = np.stack([(one - wx) * (one - wy), wx * (one - wy), (one - wx) * wy, wx * wy])
     for t in range(4):
         xx, yy = ix + (t & 1), iy + (t >> 1)

@@ -18,15 +18,17 @@ pixels; over the pixels with |dY| <= still and both d16 >= 1: n_still, flicker =
 (FLICKER_FIELDS)."""
 import numpy as np
 
+import temporal_ref as TR
+
 REPROJ_FIELDS = ("n_valid", "n_cmp", "sad", "ssd", "n_bad", "sad0", "ssd0", "n_bad0")
 FLICKER_FIELDS = ("luma_sad", "n_still", "flicker", "n_jump")
 E_MAX = 4080                        # 16 * 255
 
 
 def d16_of(depth):
-    """the temporal contract's fixed point: rint(16 D) in float32, half to even; NaN becomes invalid (0)"""
-    r = np.rint(np.asarray(depth, np.float32) * np.float32(16))
-    return np.where(r >= 1, r, 0).astype(np.int64)
+    """the temporal contract's fixed point (tests/temporal_ref.py d16_of): rint(16 D) in float32, half to even; NaN, -inf and
+    everything below 1 are invalid (0), +inf and everything above 32767 count as 32767; no non-finite value is converted"""
+    return TR.d16_of(depth)
 
 
 def reproj_frame(left, right, disp16, bad_thr=16):
@@ -99,9 +101,7 @@ def flicker_loops(depth, gray, still, jump16):
     T, H, W = depth.shape
     Y = np.asarray(gray).astype(int).tolist()
 
-    def d16(v):
-        r = np.rint(np.float32(v) * np.float32(16))
-        return int(r) if r >= 1 else 0
+    d16 = TR.d16_loop
     out = []
     for u in range(T - 1):
         rec = [0] * 4

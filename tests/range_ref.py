@@ -11,7 +11,8 @@ Q_MIN, Q_OFF = 5000, 10000
 
 
 def histogram(frame):
-    """hist[b] = #{d16 == b} for 1 <= b <= 2046, hist[2047] = #{d16 >= 2047}; hist[0] stays 0: invalid pixels are not counted"""
+    """hist[b] = #{d16 == b} for 1 <= b <= 2046, hist[2047] = #{d16 >= 2047}; hist[0] stays 0: invalid pixels are not counted
+    (NaN and -inf are invalid, +inf lands in the last bin: TR.d16_of)"""
     d16 = TR.d16_of(frame).reshape(-1)
     return np.bincount(np.minimum(d16[d16 >= 1], NB - 1), minlength=NB).astype(np.int64)
 
@@ -31,9 +32,11 @@ def select(hist, q):
 
 
 def white_point(frame, q):
-    """(mn, hi) of one frame as float32"""
+    """(mn, hi) of one frame as float32; a frame that holds a NaN gives (NaN, NaN) whatever its histogram says"""
     f = np.asarray(frame, np.float32)
-    mn, mx = f.min(), f.max()
+    mn, mx = TR.minmax(f.reshape(1, -1))[0]
+    if np.isnan(mn):
+        return mn, mx
     n_valid, _, hi16 = select(histogram(f), q)
     if n_valid == 0 or hi16 == NB - 1:
         return mn, mx
@@ -71,12 +74,16 @@ def white_point_loops(frame, q):
     f = np.asarray(frame, np.float32)
     hist = [0] * NB
     mn = mx = None
+    nan = False
     for v in f.reshape(-1):
-        mn = v if mn is None or v < mn else mn
-        mx = v if mx is None or v > mx else mx
-        d16 = int(np.rint(np.float32(v) * np.float32(16)))
+        nan = nan or v != v
+        mn = v if mn is None or v < mn or (v == mn and np.signbit(v)) else mn          # -0.0 sorts below +0.0
+        mx = v if mx is None or v > mx or (v == mx and not np.signbit(v)) else mx
+        d16 = TR.d16_loop(v)
         if d16 >= 1:
             hist[min(d16, NB - 1)] += 1
+    if nan:
+        return np.float32(np.nan), np.float32(np.nan)
     n_valid = sum(hist)
     if n_valid == 0:
         return np.float32(mn), np.float32(mx)

@@ -167,7 +167,7 @@ def filter_loops(depth, gray, R, tau, cut, F, Bk, fill):
     T, H, W = depth.shape
     BW, BH = blocks(W, H)
     out = np.zeros((T, H, W), np.float32)
-    d16 = [[[int(np.rint(np.float32(depth[t, y, x]) * np.float32(16))) for x in range(W)] for y in range(H)] for t in range(T)]
+    d16 = [[[TR.d16_loop(depth[t, y, x]) for x in range(W)] for y in range(H)] for t in range(T)]
     Y = np.asarray(gray).astype(int).tolist()
     clx, cly = (lambda v: min(max(v, 0), W - 1)), (lambda v: min(max(v, 0), H - 1))
     for t in range(T):

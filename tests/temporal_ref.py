@@ -11,9 +11,17 @@ MAX_RADIUS = 8
 S_MAX = 9 * 255                     # largest 3x3 sum of absolute luma differences
 
 
+D16_MAX = 32767                     # a valid tap above the range, +inf included, counts as this (v3d_depth_math.h's v3d_d16_tap)
+
+
 def d16_of(depth):
-    """step 1: fixed point x16, round half to even"""
-    return np.rint(np.asarray(depth, np.float32) * np.float32(16)).astype(np.int64)
+    """step 1: fixed point x16, round half to even -> int64, 0 = invalid, else 1 .. D16_MAX.  Validity is decided on the float,
+    before any conversion: valid iff 1 <= rint(16 D), which NaN, -inf, -0.0 and every D < 1/32 fail; a valid value above D16_MAX
+    saturates.  Only values an integer holds are ever converted (an astype of a NaN or an infinity is a platform accident)."""
+    with np.errstate(over="ignore", invalid="ignore"):    # 16 * FLT_MAX is +inf: saturates like every tap above the range; a signalling NaN
+        r = np.rint(np.asarray(depth, np.float32) * np.float32(16))
+    ok = r >= 1                                           # False for NaN
+    return np.where(ok, np.minimum(np.where(ok, r, 0), D16_MAX), 0).astype(np.int64)
 
 
 def cuts(gray, c):
@@ -83,31 +91,43 @@ def filter_clip(depth, gray, R, tau=12, cut=None, fill=1, t0=0, n=None):
 
 
 def minmax(depth):
-    """per-frame min and max of the unfiltered depth, float32 [T,2]"""
-    d = np.asarray(depth, np.float32).reshape(len(depth), -1)
-    return np.stack([d.min(axis=1), d.max(axis=1)], axis=1).astype(np.float32)
+    """per-frame min and max of the unfiltered depth, float32 [T,2]; a frame that holds a NaN gives (NaN, NaN) (ndarray.min / .max
+    propagate), -0.0 sorts below +0.0 on the device and compares equal here, +-inf are ordinary extrema"""
+    d = np.ascontiguousarray(depth, np.float32).reshape(len(depth), -1)
+    u = d.view(np.uint32)
+    o = np.where(u >> 31 == 1, ~u, u | np.uint32(0x80000000))                # the device's order-preserving code: -0.0 below +0.0
+    o = np.stack([o.min(axis=1), o.max(axis=1)], axis=1)
+    out = np.where(o >> 31 == 1, o & np.uint32(0x7FFFFFFF), ~o).astype(np.uint32).view(np.float32)
+    out[np.isnan(d).any(axis=1)] = np.nan
+    return out
 
 
 def ranges(mm, cut, R, t0=0, n=None):
-    """step 5: lo_t = min mn_u, hi_t = max mx_u over the admissible u -> float32 [n,2]"""
+    """step 5: lo_t = min mn_u, hi_t = max mx_u over the admissible u -> float32 [n,2]; a NaN bound in any admissible frame, at
+    any position of the window, makes both bounds of the target NaN (and to_u16_range then writes a frame of 0)"""
     T = len(mm)
     n = T - t0 if n is None else n
     out = np.zeros((n, 2), np.float32)
     for j in range(n):
         lo, hi = admissible(cut, T, t0 + j, R)
-        out[j] = mm[lo:hi + 1, 0].min(), mm[lo:hi + 1, 1].max()
+        win = np.asarray(mm[lo:hi + 1], np.float32)
+        out[j] = (np.nan, np.nan) if np.isnan(win).any() else (win[:, 0].min(), win[:, 1].max())
     return out
 
 
 def to_u16_range(depth, lohi):
-    """v3d_depth_to_u16's float32 expression with (lo, hi) given per frame; hi == lo -> 0; clamped to [0, 65535] in float32"""
+    """v3d_depth_to_u16's float32 expression with (lo, hi) given per frame; hi == lo -> 0; clamped to [0, 65535] in float32.
+    A range that is unordered or holds a NaN gives a frame of 0; so does an infinite bound (every quotient is 0, NaN or negative);
+    a NaN sample gives 0 (the device's clamp `v >= 65535 ? 65535 : v > 0 ? v : 0` lets no NaN through, and none is converted here)"""
     depth = np.asarray(depth, np.float32)
     out = np.zeros(depth.shape, np.uint16)
     for f in range(len(depth)):
         mn, mx = np.float32(lohi[f][0]), np.float32(lohi[f][1])
         if mx > mn:
-            v = (depth[f] - mn) / np.float32(mx - mn) * np.float32(65535.0)
-            out[f] = np.clip(v, np.float32(0), np.float32(65535)).astype(np.uint16)
+            with np.errstate(over="ignore", invalid="ignore"):          # inf - inf, inf / inf, FLT_MAX * 65535: all defined below
+                v = (depth[f] - mn) / np.float32(mx - mn) * np.float32(65535.0)
+            v = np.where(v >= np.float32(65535), np.float32(65535), np.where(v > 0, v, np.float32(0)))
+            out[f] = v.astype(np.uint16)
     return out
 
 
@@ -118,11 +138,20 @@ def stabilize(depth, gray, R, tau=12, c=20, fill=1, t0=0, n=None):
     return to_u16_range(filt, ranges(minmax(depth), cut, R, t0, n))
 
 
+def d16_loop(v):
+    """d16_of for one sample, as branches on the float: nothing that is not a finite value in range reaches int()"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = np.rint(np.float32(v) * np.float32(16))
+    if not r >= 1:                                        # NaN, -inf, zeros, negatives
+        return 0
+    return D16_MAX if r >= D16_MAX else int(r)
+
+
 def filter_loops(depth, gray, R, tau, cut, fill):
     """the contract as a literal per-pixel, per-tap loop (checks the vectorised form above on small clips)"""
     T, H, W = depth.shape
     out = np.zeros((T, H, W), np.float32)
-    d16 = [[[int(np.rint(np.float32(depth[t, y, x]) * np.float32(16))) for x in range(W)] for y in range(H)] for t in range(T)]
+    d16 = [[[d16_loop(depth[t, y, x]) for x in range(W)] for y in range(H)] for t in range(T)]
     Y = np.asarray(gray).astype(int).tolist()
     for t in range(T):
         for y in range(H):

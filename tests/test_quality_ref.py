@@ -78,3 +78,23 @@ def test_identical_frames_and_invalid_depth():
     nv = int((QR.d16_of(depth[0]) >= 1).sum())
     assert 0 < nv < 45 and QR.flicker(depth, gray, 0, 0).tolist() == [[0, nv, 0, 0]] * 2
     assert QR.d16_of(np.array([np.nan, -1.0, 0.03125, 0.09375, 0.1], np.float32)).tolist() == [0, 0, 0, 2, 2]
+
+
+def test_flicker_vectorised_equals_the_loop_on_specials():
+    """NaN of both signs, infinities and depths above the fixed point's range: NaN and -inf are invalid, +inf and the like
+    count as 32767 (tests/temporal_ref.py d16_of); no astype of a non-finite value (the NumPy warning is an error here)"""
+    import nonfinite as NF
+    rng = np.random.default_rng(9)
+    T, H, W = 4, 3, 17
+    depth = (rng.integers(-8, 1024, (T, H, W)) / 16).astype(np.float32)
+    gray = np.clip(rng.integers(0, 256, (1, H, W)) + rng.integers(-6, 7, (T, H, W)), 0, 255).astype(np.uint8)
+    with NF.cast_warnings_are_errors():
+        for label, where in NF.placements(H * W):
+            d = depth.copy()
+            d[1] = NF.put(d[1], where)
+            for still, jump in ((0, 0), (4, 16), (255, 32766)):
+                assert QR.flicker(d, gray, still, jump).tolist() == QR.flicker_loops(d, gray, still, jump), label
+        assert QR.d16_of(np.float32(list(NF.SPECIALS.values()))).tolist() == [0, 0, 32767, 0, 0, 0, 32767, 32767, 32767, 32767]
+        # +inf next to 1/16 on still luma: one still pixel that moves 32766
+        d = np.float32([1 / 16, np.inf, -np.inf, np.nan]).reshape(4, 1, 1)
+        assert QR.flicker(d, np.zeros((4, 1, 1), np.uint8), 0, 32765).tolist() == [[0, 1, 32766, 1], [0, 0, 0, 0], [0, 0, 0, 0]]

@@ -134,3 +134,40 @@ def test_stabilize_with_the_option_off_is_the_temporal_contract():
     assert (RR.stabilize(depth, gray, 2, q=9000) != TR.stabilize(depth, gray, 2)).any()
     with pytest.raises(ValueError):
         RR.robust_minmax(depth, 4999)
+
+
+# ---------------------------------------------------------------- NaN, infinities and depths above the fixed point's range
+
+@pytest.mark.parametrize("q", (5000, 9800, 10000))
+def test_vectorised_form_equals_the_loop_on_specials(q):
+    import nonfinite as NF
+    with NF.cast_warnings_are_errors():
+        for name, f in _frames().items():
+            for label, where in NF.placements(f.size):
+                g = NF.put(f, where)
+                got, want = RR.robust_minmax(g[None], q)[0], np.float32(RR.white_point_loops(g, q))
+                assert NF.same_floats(got, want), (name, label, q, got, want)
+                if np.isnan(g).any():
+                    assert np.isnan(got).all(), (name, label)
+                    assert not RR.to_u16(g[None], q).any()
+                hist = RR.histogram(g)
+                assert hist[0] == 0 and hist.sum() == (TR.d16_of(g) >= 1).sum()
+
+
+def test_specials_in_the_histogram_by_hand():
+    import nonfinite as NF
+    f = np.float32([[1.0, 2.0, 3.0, 4.0]])
+    with NF.cast_warnings_are_errors():
+        # NaN -> 0 (not counted), and the frame's range is (NaN, NaN) whatever the NaN's sign
+        for v in (NF.SPECIALS["nan+"], NF.SPECIALS["nan-"]):
+            g = NF.put(f, {2: v})
+            assert RR.histogram(g).sum() == 3 and np.isnan(RR.robust_minmax(g[None], 9800)).all()
+        # -inf, -0.0 and a denormal are invalid and ordinary minima; +inf and everything from 2047/16 up land in the last bin
+        for v, mn in ((-np.inf, -np.inf), (-0.0, 0.0), (1e-45, 1e-45)):
+            g = NF.put(f, {0: v})
+            assert RR.histogram(g).sum() == 3 and RR.robust_minmax(g[None], 10000)[0].tolist() == [np.float32(mn), 4.0]
+        for v in (np.inf, NF.FLT_MAX, 1e9, 2048.0, 2047.9375):
+            g = NF.put(f, {3: v})
+            assert RR.histogram(g)[RR.NB - 1] == 1
+            assert RR.robust_minmax(g[None], 10000)[0].tolist() == [1.0, np.float32(v)]          # hi16 == 2047 -> the float max
+            assert RR.robust_minmax(g[None], 5000)[0].tolist() == [1.0, 2.0]                     # below the outlier: the percentile

@@ -111,3 +111,27 @@ def test_chaining_on_a_field_built_by_hand():
     Fc = np.zeros((2, 1, 2, 2), np.int16)
     Fc[0, 0, 1] = (-4, 0)
     assert tuple(MR.chain(Fc, Fc, 0, 1, 20, 10)[0, 1]) == (-4, 0)
+
+
+def test_vectorised_filter_equals_the_loops_on_specials():
+    """NaN, infinities and depths above the fixed point's range, at the centre and carried in by displaced loads; no astype of a
+    non-finite value anywhere (the NumPy warning is an error here)"""
+    import nonfinite as NF
+    rng = np.random.default_rng(50)
+    T, H, W, S = 4, 18, 21, 2
+    d, g = _clip(rng, T, H, W)
+    F = rng.integers(-S, S + 1, (T,) + MR.blocks(W, H)[::-1] + (2,)).astype(np.int16)
+    Bk = rng.integers(-S, S + 1, F.shape).astype(np.int16)
+    z = np.zeros_like(F)
+    cut = np.zeros(T, np.uint8)
+    vals = list(NF.SPECIALS.values())
+    with NF.cast_warnings_are_errors():
+        for k, (label, where) in enumerate([(n, {int(rng.integers(H * W)): v, 0: v, H * W - 1: v}) for n, v in NF.SPECIALS.items()]
+                                           + [("all", {int(i): vals[j % len(vals)] for j, i in enumerate(rng.choice(H * W, 60, replace=False))})]):
+            dd = d.copy()
+            dd[1 + k % 2] = NF.put(dd[1 + k % 2], where)
+            R, fill = (1, 2, 8)[k % 3], k % 2
+            got = MR.filter_clip(dd, g, R, 12, cut, F, Bk, fill)
+            assert np.isfinite(got).all()
+            assert np.array_equal(got, MR.filter_loops(dd, g, R, 12, cut, F, Bk, fill)), label
+            assert np.array_equal(MR.filter_clip(dd, g, R, 12, cut, z, z, fill), TR.filter_clip(dd, g, R, 12, cut, fill)), label

@@ -55,7 +55,7 @@ def test_one_pixel_by_hand():
     g = np.array([0, 200, 0], np.uint8).reshape(3, 1, 1)
     assert TR.filter_clip(d, g, 1, 12)[1, 0, 0] == 0
     # rint is half to even: 0.03125 * 16 = 0.5 -> 0 (invalid), 0.09375 * 16 = 1.5 -> 2
-    assert list(TR.d16_of(np.array([0.03125, 0.09375, -1.0], np.float32))) == [0, 2, -16]
+    assert list(TR.d16_of(np.array([0.03125, 0.09375, -1.0], np.float32))) == [0, 2, 0]       # invalid is 0, whatever it rounds to
 
 
 def test_radius_zero_is_the_identity_and_the_per_frame_range():
@@ -151,3 +151,94 @@ def test_stabilised_blend_stays_within_a_thirty_second_of_the_range():
     f = TR.filter_clip(stereo, gray, 2, 255, cut)
     lohi = TR.ranges(TR.minmax(stereo), cut, 2)
     assert (f >= lohi[:, :1, None]).all() and (f <= lohi[:, 1:, None]).all()
+
+
+# ---------------------------------------------------------------- NaN, infinities and depths above the fixed point's range
+
+def _special_clips(rng, T, H, W, blend=False):
+    """(label, depth, gray): every placement of tests/nonfinite.py in the middle frame of a clip, and one in every frame"""
+    import nonfinite as NF
+    depth, gray = _clip(rng, T, H, W, blend=blend)
+    for label, where in NF.placements(H * W):
+        d = depth.copy()
+        d[T // 2] = NF.put(d[T // 2], where)
+        yield label, d, gray
+    d = depth.copy()
+    for t in range(T):
+        d[t] = NF.put(d[t], {(7 * t + 1) % (H * W): list(NF.SPECIALS.values())[t % len(NF.SPECIALS)]})
+    yield "one per frame", d, gray
+
+
+def test_vectorised_reference_equals_the_literal_loop_on_specials():
+    import nonfinite as NF
+    rng = np.random.default_rng(40)
+    i = 0
+    with NF.cast_warnings_are_errors():
+        for label, depth, gray in _special_clips(rng, 4, 2, 5):
+            R, tau, fill = (1, 2, 8)[i % 3], (1, 12, 255)[i % 3], (i // 3) % 2
+            i += 1
+            cut = np.zeros(4, np.uint8)
+            cut[3] = i % 4 == 0
+            got = TR.filter_clip(depth, gray, R, tau, cut, fill)
+            assert np.isfinite(got).all() and got.min() >= 0 and got.max() <= TR.D16_MAX / 16
+            assert np.array_equal(got, TR.filter_loops(depth, gray, R, tau, cut, fill)), label
+
+
+def test_d16_rule_by_hand():
+    """valid iff 1 <= rint(16 D), decided on the float; NaN, -inf, -0.0 and a denormal are invalid; above the range saturates"""
+    import nonfinite as NF
+    with NF.cast_warnings_are_errors():
+        got = TR.d16_of(np.float32(list(NF.SPECIALS.values())))
+        assert dict(zip(NF.NAMES, got.tolist())) == {"nan+": 0, "nan-": 0, "+inf": 32767, "-inf": 0, "-0.0": 0, "denormal": 0,
+                                                      "FLT_MAX": 32767, "2048": 32767, "2047.9375": 32767, "1e9": 32767}
+        assert [TR.d16_loop(v) for v in NF.SPECIALS.values()] == got.tolist()
+        # a +inf neighbour is an ordinary tap of 32767; a NaN or -inf neighbour has weight 0 and leaves the centre alone
+        g = np.zeros((3, 1, 1), np.uint8)
+        for v, want in ((np.inf, (2 * (256 * 32767 + 512 * 160 + 256 * 160) + 1024) // 2048), (np.nan, 160), (-np.inf, 160)):
+            d = np.float32([v, 10.0, 10.0]).reshape(3, 1, 1)
+            assert TR.filter_clip(d, g, 1, 12)[1, 0, 0] * 16 == want, v
+        # an invalid centre: filled from its neighbours, or 0 without fill
+        d = np.float32([10.0, np.nan, 12.0]).reshape(3, 1, 1)
+        assert TR.filter_clip(d, g, 1, 12)[1, 0, 0] == 11.0 and TR.filter_clip(d, g, 1, 12, fill=0)[1, 0, 0] == 0.0
+
+
+def test_a_nan_bound_makes_the_range_nan_wherever_it_sits_in_the_window():
+    import nonfinite as NF
+    T = 9
+    rng = np.random.default_rng(41)
+    base = np.sort(rng.uniform(0, 50, (T, 2)).astype(np.float32), axis=1)
+    for R in (0, 1, 2, 8):
+        for pos in range(T):
+            for cut_at in (None, max(pos - 1, 1), pos, min(pos + 1, T - 1)):
+                cut = np.zeros(T, np.uint8)
+                if cut_at:
+                    cut[cut_at] = 1
+                for col, v in ((0, NF.SPECIALS["nan-"]), (1, NF.SPECIALS["nan+"]), (0, NF.SPECIALS["nan+"])):
+                    mm = base.copy()
+                    mm[pos, col] = v
+                    got, clean = TR.ranges(mm, cut, R), TR.ranges(base, cut, R)
+                    for t in range(T):
+                        lo, hi = TR.admissible(cut, T, t, R)
+                        if lo <= pos <= hi:
+                            assert np.isnan(got[t]).all(), (R, pos, cut_at, t)
+                        else:
+                            assert np.array_equal(got[t], clean[t]), (R, pos, cut_at, t)
+    # infinities are ordinary extrema
+    mm = base.copy()
+    mm[4] = (-np.inf, np.inf)
+    assert np.array_equal(TR.ranges(mm, np.zeros(T, np.uint8), 1)[3:6], np.float32([[-np.inf, np.inf]] * 3))
+
+
+def test_normalisation_writes_zero_for_a_nan_or_infinite_range_and_a_nan_sample():
+    import nonfinite as NF
+    d = np.float32([[0.0, 1.0, 2.5, np.nan, np.inf, -np.inf, 3.4e38, -0.0]])
+    with NF.cast_warnings_are_errors():
+        for lohi in ((-np.inf, np.inf), (np.nan, 2.0), (0.0, np.nan), (np.inf, np.inf), (0.0, np.inf), (-np.inf, 3.0), (3.0, 1.0), (np.nan, np.nan)):
+            assert not TR.to_u16_range(d[None], np.float32([lohi])).any(), lohi
+        got = TR.to_u16_range(d[None], np.float32([[0.0, 2.5]]))[0, 0]
+        assert got.tolist() == [0, 26214, 65535, 0, 65535, 0, 65535, 0]
+        # a frame's own range: one NaN anywhere makes the frame 0, one infinity too (finite pixels 0, the infinite one NaN -> 0)
+        for v in (np.nan, np.inf, -np.inf):
+            f = np.float32([[1.0, 2.0, v, 4.0]])
+            assert not TR.to_u16_range(f[None], TR.minmax(f[None])).any(), v
+        assert np.isnan(TR.minmax(np.float32([[[1.0, np.nan]], [[1.0, 2.0]]]))[0]).all()

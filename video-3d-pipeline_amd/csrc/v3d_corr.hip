@@ -18,6 +18,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 
+// floor(s) of a sample coordinate, as the int the taps are indexed with.  The flow is data and may hold a NaN, an infinity or 1e30,
+// and (int) of such a float is undefined: gfx950 saturates it to INT_MAX, `x0 + 1` then wraps to INT_MIN, and the compiler, which
+// may assume that it does not, had reduced `x0 + 1 >= 0 && x0 + 1 < w` to a test the wrapped value passes -- a tap far outside the
+// image counted as inside and was read.  So the float is clamped before it is converted: every coordinate at or below -2 becomes
+// -2, every one beyond the largest float an int holds becomes that float (neither has a tap inside any image, and x0 + 1 cannot
+// overflow), and a NaN becomes -2 (fmaxf returns its other operand).  A tap whose coordinate is not inside the plane contributes 0.
+__device__ __forceinline__ int corr_floor_int(float floored) { return (int)fminf(fmaxf(floored, -2.0f), 2147483520.0f); }
+
 // one thread = one pixel x one 8-channel chunk
 __global__ __launch_bounds__(256) void k_corr_warp(const unsigned short* __restrict__ fr, const float* __restrict__ flow,
                                                    int C, int h, int w, unsigned short* __restrict__ out)
@@ -31,7 +39,7 @@ __global__ __launch_bounds__(256) void k_corr_warp(const unsigned short* __restr
     const float sx = x + flow[pix], sy = y + flow[(size_t)h * w + pix];
     const float x0f = floorf(sx), y0f = floorf(sy);
     const float wx = sx - x0f, wy = sy - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
+    const int x0 = corr_floor_int(x0f), y0 = corr_floor_int(y0f);
     float acc[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) acc[k] = 0.f;
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(256) void k_corr_gather(const unsigned short* __res
             const float sx = xb + flow[pix], sy = yy + flow[hw + pix];
             const float x0f = floorf(sx), y0f = floorf(sy);
             const float wx = sx - x0f, wy = sy - y0f;
-            const int ix = (int)x0f, iy = (int)y0f;
+            const int ix = corr_floor_int(x0f), iy = corr_floor_int(y0f);
 #pragma unroll
             for (int t = 0; t < 4; t++) {
                 const int xx = ix + (t & 1), yv = iy + (t >> 1);
@@ -254,7 +262,7 @@ __global__ __launch_bounds__(256) void k_corr_fused0(const unsigned short* __res
                     const int i = i3 + ii;
                     const float x0f = floorf(fx[i]), y0f = floorf(fy[i]);
                     const float wx = fx[i] - x0f, wy = fy[i] - y0f;
-                    const int ix = (int)x0f, iy = (int)y0f;
+                    const int ix = corr_floor_int(x0f), iy = corr_floor_int(y0f);
 #pragma unroll
                     for (int t = 0; t < 4; t++) {                // tap order of k_corr_warp: (y0,x0) (y0,x1) (y1,x0) (y1,x1)
                         const int xx = ix + (t & 1), yy = iy + (t >> 1);

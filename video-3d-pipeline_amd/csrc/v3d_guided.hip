@@ -28,7 +28,9 @@ __device__ __forceinline__ double gf_rcp(double x)
 // the low-resolution depth comes either as float32 (depth.py's frame-out surface, any provider) or straight as the matcher's
 // int16 disparity x16: then depth.py:341 `/16` and depth.py:374 `<= 0 -> 0` happen in the load (the float map never exists)
 template <typename TD> __device__ __forceinline__ float gf_ld(const TD* p, size_t i);
-template <> __device__ __forceinline__ float gf_ld<float>(const float* p, size_t i) { return p[i]; }
+// float route: a non-finite sample counts as invalid (0, like depth.py:374's `<= 0 -> 0`): the window sums slide, so a NaN or an
+// infinity let in would stay in `s += in - out` for the rest of its strip
+template <> __device__ __forceinline__ float gf_ld<float>(const float* p, size_t i) { const float v = p[i]; return fabsf(v) <= 3.402823466e38f ? v : 0.f; }
 template <> __device__ __forceinline__ float gf_ld<int16_t>(const int16_t* p, size_t i) { const int d = p[i]; return d > 0 ? (float)d * 0.0625f : 0.f; }
 // or as the normalised 16-bit sample of the depth PNG (read_png16(...).astype(float32) on the device: the same float values)
 template <> __device__ __forceinline__ float gf_ld<uint16_t>(const uint16_t* p, size_t i) { return (float)p[i]; }

@@ -89,12 +89,9 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_reproj(const uint8_t* __restric
     q_block_store<Q_RF>(acc, ws + ((size_t)f * gridDim.x + band) * Q_RF);
 }
 
-// ---- flicker: the only float step is v3d_d16 (the temporal stage's own fixed point); NaN fails `>= 1` and is never converted ----
-__device__ __forceinline__ int q_d16(float D)
-{
-    const float r = v3d_d16(D);
-    return r >= 1.0f ? (int)r : 0;
-}
+// ---- flicker: the only float step is v3d_d16_tap (the temporal stage's own fixed point): NaN and -inf are invalid, +inf and
+// every depth above the range count as 32767, nothing out of an int's range is ever converted ----
+__device__ __forceinline__ int q_d16(float D) { return v3d_d16_tap(D); }
 
 template <bool VEC>
 __device__ __forceinline__ void q_load_depth(const float* __restrict__ row, int x0, int W, int (&d)[Q_FPX])

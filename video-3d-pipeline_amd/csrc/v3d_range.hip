@@ -45,9 +45,21 @@ __global__ __launch_bounds__(256) void k_minmax(const float* __restrict__ d, siz
     }
     mm_wave_fold(mm, lo, hi);
 }
+// a reduced {min, max} slot as floats.  The codec sorts a NaN with the sign bit set below -inf and one with it clear above +inf,
+// so a frame that holds any NaN shows it in the slot's min or in its max: then both are NaN, as numpy's min() and max() give
+struct mm_pair { float lo, hi; };
+__device__ __forceinline__ mm_pair mm_decode(const unsigned* mm)
+{
+    const float lo = v3d_ord2f(mm[0]), hi = v3d_ord2f(mm[1]);
+    const bool nan = lo != lo || hi != hi;
+    return { nan ? __builtin_nanf("") : lo, nan ? __builtin_nanf("") : hi };
+}
 __global__ void k_mm_decode(unsigned* mm, int n)
 {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += gridDim.x * 256) mm[i] = __float_as_uint(v3d_ord2f(mm[i]));
+    for (int f = blockIdx.x * 256 + threadIdx.x; f < n; f += gridDim.x * 256) {
+        const mm_pair p = mm_decode(mm + 2 * f);
+        mm[2 * f] = __float_as_uint(p.lo); mm[2 * f + 1] = __float_as_uint(p.hi);
+    }
 }
 // ENCODED: the frame's (lo, hi) is a {min, max} slot as k_minmax leaves it; else two floats
 template <bool ENCODED>
@@ -91,7 +103,7 @@ extern "C" int v3d_depth_minmax_batch(const float* depth, int T, size_t frame_el
     unsigned* mm = reinterpret_cast<unsigned*>(minmax_out);
     hipLaunchKernelGGL(k_mm_init, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, mm, T);
     hipLaunchKernelGGL(k_minmax, dim3(frame_blocks(frame_elems, T, 64), T), dim3(256), 0, st, depth, frame_elems, frame_stride, mm);
-    hipLaunchKernelGGL(k_mm_decode, dim3(v3d_cdiv(2 * T, 256)), dim3(256), 0, st, mm, T);
+    hipLaunchKernelGGL(k_mm_decode, dim3(v3d_cdiv(T, 256)), dim3(256), 0, st, mm, T);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }
@@ -108,11 +120,11 @@ extern "C" int v3d_depth_to_u16_range_batch(const float* depth, int n, size_t fr
 }
 
 // ---- the robust range: its own fused kernels (min/max and histogram off one read), one init launch ----
-// the histogram bin: 0 = invalid (not counted), the last bin saturates; NaN compares false twice -> 0
+// the histogram bin: 0 = invalid (not counted; NaN and -inf are invalid), the last bin saturates (+inf lands there)
 __device__ __forceinline__ int rr_bin(float d)
 {
-    const float v = v3d_d16(d);
-    return v >= (float)(RR_NB - 1) ? RR_NB - 1 : v >= 1.f ? (int)v : 0;
+    const int v = v3d_d16_tap(d);
+    return v >= RR_NB - 1 ? RR_NB - 1 : v;
 }
 
 __global__ void k_rr_init(unsigned* hist, unsigned* mm, int T)
@@ -196,7 +208,8 @@ __global__ __launch_bounds__(256) void k_rr_select(const unsigned* __restrict__ 
     __shared__ unsigned part[RR_WAVES];
     const excl_total sc = block_excl_add_u32<RR_WAVES>(own, lane, wave, part);
     const unsigned before = sc.excl, n_valid = sc.total;
-    const float mn = v3d_ord2f(mm[2 * t]), mx = v3d_ord2f(mm[2 * t + 1]);
+    const mm_pair p = mm_decode(mm + 2 * t);                               // a frame with a NaN: (NaN, NaN), whatever the histogram holds
+    const float mn = p.lo, mx = p.hi;
     if (tid == 0) { out[2 * t] = mn; if (n_valid == 0) out[2 * t + 1] = mx; }
     if (n_valid == 0) return;
     const unsigned long long kq = ((unsigned long long)q * n_valid + 9999ull) / 10000ull;

@@ -91,12 +91,14 @@ __global__ void k_tp_range(const float* __restrict__ mm, const uint8_t* __restri
         int a, b;
         v3d_tp_admissible(cut, T, t0 + j, R, &a, &b);
         float lo = mm[2 * a], hi = mm[2 * a + 1];
-        for (int u = a + 1; u <= b; u++) {
+        bool nan = lo != lo || hi != hi;                    // ndarray.min() / .max(): a NaN bound in any frame of the window, at any
+        for (int u = a + 1; u <= b; u++) {                  // position, makes both bounds of the target NaN
             const float l = mm[2 * u], h = mm[2 * u + 1];
+            nan = nan || l != l || h != h;
             lo = l < lo ? l : lo;
             hi = h > hi ? h : hi;
         }
-        lohi[2 * j] = lo; lohi[2 * j + 1] = hi;
+        lohi[2 * j] = nan ? __builtin_nanf("") : lo; lohi[2 * j + 1] = nan ? __builtin_nanf("") : hi;
     }
 }
 
@@ -214,9 +216,15 @@ __global__ __launch_bounds__(256) void k_tp_filter(const float* __restrict__ dep
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int d16 = (int)v3d_d16(d[i]);
-            if (u == t) centre[i] = d16 >= 1;
-            const uint32_t w = v3d_tp_weight(s[i], mul, R, u - t, d16);
+            // validity is decided on the float, as v3d_d16_tap decides it: NaN, -inf and every rint(16 D) < 1 are invalid whatever
+            // the conversion makes of them, and an invalid tap's weight is 0.  Only the value keeps the bare conversion: v3d_d16_tap's
+            // clamp to 32767 cost 3 to 4 % of this kernel ("Non-finite input"), so a tap above the domain D <= 2047.9375
+            // (+inf included) is valid with a value that wraps: the header leaves such a pixel's value unspecified
+            const float r16 = v3d_d16(d[i]);
+            const bool valid = r16 >= 1.0f;
+            const int d16 = (int)r16;
+            if (u == t) centre[i] = valid;
+            const uint32_t w = v3d_tp_weight(s[i], mul, R, u - t, valid ? 1 : 0);
             Wsum[i] += w;
             Dsum[i] += w * (uint32_t)d16;                   // w = 0 where d16 is invalid
         }
