@@ -74,7 +74,12 @@ typedef struct v3d_sgbm v3d_sgbm;
        2*P2 + 25*(2*ftzero + 63) < 32767   and   ftzero <= 31
    i.e. P2 <= 15220 for preFilterCap <= 15, P2 <= 14820 for preFilterCap = 30 or 31; preFilterCap >= 32 is refused. */
 typedef struct {
-    int minDisparity;       /* must be 0 */
+    int minDisparity;       /* m in [-64, 0]; anything else is refused.  The search window is d = xL - xR in [m, m + 64): cost column
+                               x1 in [0, W - 64) compares the left image's column x1 + 64 + m with the right image's columns
+                               x1 + 64 - d', d' in [0, 64).  Output: disparity x16 (true value, so negative inside the window) at
+                               image column x1 + 64 + m; INVALID = 16 (m - 1) at rejected pixels and at every column outside
+                               [64 + m, W + m) (64 + m columns on the left, -m on the right); 3x3 median and speckle filter
+                               (newVal = 16 (m - 1)) after that.  0 = OpenCV's call in depth.py, bit for bit */
     int numDisparities;     /* must be 64 in this build */
     int blockSize;          /* must be 5 in this build */
     int P1, P2;             /* P1 <= 0 -> 2; P2 <= 0 -> 5; P2 < P1 + 1 -> P1 + 1; then the headroom rule above */
@@ -96,7 +101,7 @@ void v3d_sgbm_destroy(v3d_sgbm* h);
 /* bytes of device workspace the handle owns */
 size_t v3d_sgbm_workspace_bytes(const v3d_sgbm* h);
 
-/* one frame: left/right gray u8 [H][pitch], disp16 out int16 [H][W] (value x16, -16 invalid) */
+/* one frame: left/right gray u8 [H][pitch], disp16 out int16 [H][W] (value x16, 16 (minDisparity - 1) invalid: -16 at the default) */
 int v3d_sgbm_compute(v3d_sgbm* h, const uint8_t* left_gray, const uint8_t* right_gray,
                      int W, int H, int pitch, int16_t* disp16_out, void* stream);
 /* n frames: frame f at left_gray + f*frame_stride (bytes), output frame f at disp16_out + f*W*H.  Frames must not overlap:
@@ -108,7 +113,7 @@ int v3d_sgbm_compute_batch(v3d_sgbm* h, const uint8_t* left_gray, const uint8_t*
 /* Lock-step pass and an over-subscribed GPU.  The three top-down SGM paths run as ONE pass whose workgroups must all
    be resident together (sized from the occupancy query at create time).  If another process or stream holds CUs, a
    workgroup's bounded wait for its neighbour strip gives up.  The library then NEVER hands out those disparities:
-     - the last launch of the call sets every output pixel of the call to INVALID (-16) and raises a host-visible flag;
+     - the last launch of the call sets every output pixel of the call to INVALID (16 (minDisparity - 1)) and raises a host-visible flag;
      - every later v3d_sgbm_compute* on the handle returns V3D_ERR_LOCKSTEP until the host reacts;
      - v3d_sgbm_poll_errors (no synchronisation) / v3d_sgbm_sync_errors (device synchronise) return the number of
        workgroups that timed out since the state was last cleared (0 = healthy);
@@ -152,11 +157,11 @@ const char* v3d_sgbm_profile_stage_name(int stage);
 int v3d_sgbm_profile_read(v3d_sgbm* h, double* total_ms, int n);
 
 /* stage exports used by the parity tests (same inputs as v3d_sgbm_compute, one frame) */
-/* cost volume C[y][x-64][d] int16, P2 folded in */
+/* cost volume C[y][x1][d'] int16, P2 folded in (x1 = x - 64 - minDisparity, d' = d - minDisparity) */
 int v3d_sgbm_debug_cost_volume(v3d_sgbm* h, const uint8_t* left_gray, const uint8_t* right_gray,
                                int W, int H, int pitch, int16_t* C_out, void* stream);
 /* raw disparity before median/speckle (after WTA, uniqueness, sub-pixel, L-R check) and,
-   if S_out != NULL, the aggregated volume S[y][x-64][d] */
+   if S_out != NULL, the aggregated volume S[y][x1][d']; the image is placed as v3d_sgbm_params.minDisparity says */
 int v3d_sgbm_debug_raw(v3d_sgbm* h, const uint8_t* left_gray, const uint8_t* right_gray,
                        int W, int H, int pitch, int16_t* disp16_out, int16_t* S_out, void* stream);
 int v3d_median3x3_i16(const int16_t* src, int W, int H, int16_t* dst, void* stream);

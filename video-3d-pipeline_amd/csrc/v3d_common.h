@@ -9,7 +9,7 @@
 
 #define V3D_D 64              // numDisparities this build is specialised for (one wavefront of d)
 #define V3D_MAX_COST 32767
-#define V3D_INVALID16 (-16)   // (minDisparity - 1) * 16
+#define V3D_INVALID16 (-16)   // invalid in RELATIVE values (d - minDisparity) x16, what the kernels work in; the output holds (minDisparity - 1) * 16
 
 void v3d_set_error(const char* fmt, ...);
 

@@ -81,8 +81,10 @@ extern "C" int v3d_sgbm_get_option(const v3d_sgbm* h, const char* key, int* valu
 extern "C" int v3d_sgbm_create(const v3d_sgbm_params* prm, int device, int maxW, int maxH, int maxB, v3d_sgbm** out)
 {
     if (!prm || !out) { v3d_set_error("null argument"); return V3D_ERR_ARG; }
-    if (prm->minDisparity != 0 || prm->numDisparities != V3D_D || prm->blockSize != 5) {
-        v3d_set_error("this build supports minDisparity=0, numDisparities=64, blockSize=5 (got %d, %d, %d)",
+    // minDisparity m in [-64, 0]: the left record of cost column x1 is read at image column x1 + 64 + m, which must stay inside
+    // the image for every x1 in [0, W - 64); outside that range the cost region would have to shrink
+    if (prm->minDisparity < -V3D_D || prm->minDisparity > 0 || prm->numDisparities != V3D_D || prm->blockSize != 5) {
+        v3d_set_error("this build supports -64 <= minDisparity <= 0, numDisparities=64, blockSize=5 (got %d, %d, %d)",
                       prm->minDisparity, prm->numDisparities, prm->blockSize);
         return V3D_ERR_UNSUPPORTED;
     }

@@ -111,7 +111,7 @@ __device__ __forceinline__ uint32_t bt_pair(uint32_t U, uint32_t U0, uint32_t U1
 #endif
 template <int LPC>
 __global__ __launch_bounds__(512, V3D_COST_WAVES) void k_cost(const uint4* __restrict__ rec,
-                                              int W, int H, int W1, int band_h, int P2, unsigned char* __restrict__ C, int xcd_order)
+                                              int W, int H, int W1, int lofs, int band_h, int P2, unsigned char* __restrict__ C, int xcd_order)
 {
     typedef CostGeo<LPC> G;
     constexpr int EP = G::EP, NP = G::NP, COLS = G::COLS, OUT = G::OUT, NREC = G::NREC;
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(512, V3D_COST_WAVES) void k_cost(const uint4* __res
         const int k = NREC - 1 - ri;
         st_off = (k & 1) * RCOPY + 3 * half * RROW + (k >> 1);
     } else if (ld_left) {
-        ld_a = ld_b = 4 * (min(max(xr0 - 2 + lt, 0), W1 - 1) + V3D_D) + half;
+        ld_a = ld_b = 4 * (min(max(xr0 - 2 + lt, 0), W1 - 1) + lofs) + half;      // lofs = 64 + minDisparity: cost column x1 <-> left image column x1 + lofs
         st_off = lt * 6 + 3 * half;
     }
     const bool ld_any = ld_right || ld_left;
@@ -288,7 +288,7 @@ int sgbm_cost_volume(v3d_sgbm* h, const uint8_t* left, const uint8_t* right, int
     hipLaunchKernelGGL(k_prefilter, dim3(v3d_cdiv(W, 252), v3d_cdiv(H, PF_BAND), n), dim3(256), 0, st, left, right, W, H, pitch, frame_stride, h->ftzero, h->rec);
     prof_mark(h, ST_COST, st);
     constexpr int COST_OUT = CostGeo<V3D_COST_LPC>::OUT;
-    hipLaunchKernelGGL((k_cost<V3D_COST_LPC>), dim3(v3d_cdiv(W1, COST_OUT), v3d_cdiv(H, h->cost_band), n), dim3(512), 0, st, h->rec, W, H, W1, h->cost_band, h->P2, h->C, h->cost_xcd);
+    hipLaunchKernelGGL((k_cost<V3D_COST_LPC>), dim3(v3d_cdiv(W1, COST_OUT), v3d_cdiv(H, h->cost_band), n), dim3(512), 0, st, h->rec, W, H, W1, V3D_D + h->prm.minDisparity, h->cost_band, h->P2, h->C, h->cost_xcd);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }

@@ -688,12 +688,12 @@ __global__ __launch_bounds__(1024, 8) void k_vdd(VddArgs a)      // 8 waves/SIMD
 // INVALID and a flag lands in host-visible memory (the next API call on the handle then returns V3D_ERR_LOCKSTEP).
 // Healthy path: one dword load per workgroup.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_vdd_guard(const int* __restrict__ err, volatile int* err_host, int16_t* __restrict__ out, size_t n)
+__global__ __launch_bounds__(256) void k_vdd_guard(const int* __restrict__ err, volatile int* err_host, int16_t* __restrict__ out, size_t n, int invalid)
 {
     const int e = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (e == 0) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) { *err_host = e; __threadfence_system(); }
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = (int16_t)V3D_INVALID16;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = (int16_t)invalid;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -829,7 +829,7 @@ int sgbm_aggregate_wta(v3d_sgbm* h, int n, int W, int H, hipStream_t st, bool* l
 // time-outs of this call's (or an earlier, uncleared) lock-step pass: poison `out`, raise the host flag
 int sgbm_lockstep_guard(v3d_sgbm* h, int16_t* out, size_t npx, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_vdd_guard, dim3(256), dim3(256), 0, st, h->vdd_err, h->err_host, out, npx);
+    hipLaunchKernelGGL(k_vdd_guard, dim3(256), dim3(256), 0, st, h->vdd_err, h->err_host, out, npx, 16 * (h->prm.minDisparity - 1));
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }

@@ -64,7 +64,7 @@ __device__ __forceinline__ int lr_check(int d1, int x, int d12, KEY key)
 #define LRM_NS (LRM_TX + 2 * V3D_D)        // source columns per row  (256 = one per thread)
 #define LRM_NT (LRM_TX + V3D_D + 1)        // right-view targets per row
 template <bool MED>
-__global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restrict__ wta, int W, int H, int d12, int16_t* __restrict__ out)
+__global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restrict__ wta, int W, int H, int d12, int m, int16_t* __restrict__ out)
 {
     static_assert(LRM_NS == 256, "one source column per thread");
     constexpr int NR = LRM_TY + 2;
@@ -74,7 +74,10 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
     const int t = threadIdx.x, f = blockIdx.z;
     const int x0 = blockIdx.x * LRM_TX, y0 = blockIdx.y * LRM_TY;
     const size_t fo = (size_t)f * H * W;
-    const int xbase = x0 - V3D_D;                                            // image column of source / target index 0
+    // minDisparity m <= 0: the records, the keys and the check live in RELATIVE columns xr = x1 + 64 (what the WTA tail wrote);
+    // output column x shows relative column x - m, columns whose x - m falls outside [64, W) are invalid, and the value
+    // written last is relative + 16 m (invalid: -16 + 16 m = 16 (m - 1)); the median commutes with the constant
+    const int xbase = x0 - m - V3D_D;                                        // relative column of source / target index 0
     // ---- 1. this thread's source column, all rows in flight together (unconditional loads from clamped addresses;
     //         columns left of the cost region were never written: masked below) ----
     const int xs = xbase + t;
@@ -102,10 +105,11 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
         if (i < NR * (LRM_TX + 2)) {
             const int ty = i / (LRM_TX + 2), tx = i - ty * (LRM_TX + 2);
             const int x = min(max(x0 - 1 + tx, 0), W - 1);
+            const int xr = x - m;
             int d1 = V3D_INVALID16;
-            if (x >= V3D_D) {
-                d1 = wta_d16(sW[ty][x - xbase]);
-                if (d1 != V3D_INVALID16) d1 = lr_check(d1, x, d12, [&](int c) { return sD2[ty][c - xbase]; });
+            if (xr >= V3D_D && xr < W) {
+                d1 = wta_d16(sW[ty][xr - xbase]);
+                if (d1 != V3D_INVALID16) d1 = lr_check(d1, xr, d12, [&](int c) { return sD2[ty][c - xbase]; });
             }
             sT[ty][tx] = (short)d1;
         }
@@ -118,10 +122,10 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
     for (int ty = t >> 7; ty < LRM_TY; ty += 2) {
         const int y = y0 + ty;
         if (y >= H) break;
-        if (!MED) { out[fo + (size_t)y * W + x] = sT[ty + 1][tx + 1]; continue; }
+        if (!MED) { out[fo + (size_t)y * W + x] = (int16_t)(sT[ty + 1][tx + 1] + 16 * m); continue; }
         int p[9] = { sT[ty][tx], sT[ty][tx + 1], sT[ty][tx + 2], sT[ty + 1][tx], sT[ty + 1][tx + 1], sT[ty + 1][tx + 2],
                      sT[ty + 2][tx], sT[ty + 2][tx + 1], sT[ty + 2][tx + 2] };
-        out[fo + (size_t)y * W + x] = (int16_t)median9(p, sort2_int());
+        out[fo + (size_t)y * W + x] = (int16_t)(median9(p, sort2_int()) + 16 * m);
     }
 }
 
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(256) void k_lrcheck_median(const uint32_t* __restri
 // ------------------------------------------------------------------------------------------------
 #define LRR_BAND 15
 template <bool MED, int NPP>      // NPP: pixel PAIRS per thread and row (columns 2t, 2t+1, 2t + 512, ...): 4 covers W <= 2048, 8 W <= 4096; W even
-__global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __restrict__ wta, int W, int H, int d12, int16_t* __restrict__ out)
+__global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __restrict__ wta, int W, int H, int d12, int m, int16_t* __restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lrr_smem[];
     uint32_t* sD2 = reinterpret_cast<uint32_t*>(lrr_smem);                    // [W] right-view keys of the current row
@@ -172,6 +176,10 @@ __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __r
         }
         __syncthreads();
         // ---- L-R check (stereosgbm.cpp: both roundings of the disparity must disagree) ----
+        // minDisparity m <= 0 (see k_lrcheck_median): a thread checks its own RELATIVE columns xr and places the result at output
+        // column xr + m; the 64 relative columns left of the cost region carry no record and fill the output columns no
+        // relative column lands on, [0, 64 + m) and [W + m, W), with the invalid value.  64, W and an even m keep a pair (xr, xr + 1)
+        // a pair: one 32-bit write; an odd m splits it over two words: two 16-bit writes
         uint32_t* row = sT + (size_t)((y + 3) % 3) * W2;
 #pragma unroll
         for (int i = 0; i < NPP; i++) {
@@ -180,16 +188,23 @@ __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __r
                 int dd[2];
 #pragma unroll
                 for (int n = 0; n < 2; n++) {
-                    const int x = x0 + n;
+                    const int xr = x0 + n;
                     int d1 = V3D_INVALID16;
-                    if (x >= V3D_D) {
+                    if (xr >= V3D_D) {
                         d1 = wta_d16(rec[2 * i + n]);
-                        if (d1 != V3D_INVALID16) d1 = lr_check(d1, x, d12, [sD2](int c) { return sD2[c]; });
+                        if (d1 != V3D_INVALID16) d1 = lr_check(d1, xr, d12, [sD2](int c) { return sD2[c]; });
                     }
                     dd[n] = d1;
                 }
-                const uint32_t w = ((uint32_t)dd[0] & 0xFFFFu) | ((uint32_t)dd[1] << 16);
-                if (MED) row[x0 >> 1] = w; else *reinterpret_cast<uint32_t*>(out + fo + (size_t)y * W + x0) = w;
+                auto place = [&](int xr) { return xr >= V3D_D ? xr + m : (xr < V3D_D + m ? xr : xr - V3D_D + W); };   // output column of relative column xr
+                if (!MED) {
+                    out[fo + (size_t)y * W + place(x0)] = (int16_t)(dd[0] + 16 * m); out[fo + (size_t)y * W + place(x0 + 1)] = (int16_t)(dd[1] + 16 * m);
+                } else if ((m & 1) == 0) {                                    // uniform
+                    row[place(x0) >> 1] = ((uint32_t)dd[0] & 0xFFFFu) | ((uint32_t)dd[1] << 16);
+                } else {
+                    short* row16 = reinterpret_cast<short*>(row);
+                    row16[place(x0)] = (short)dd[0]; row16[place(x0 + 1)] = (short)dd[1];
+                }
             }
         }
         __syncthreads();
@@ -211,7 +226,7 @@ __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __r
                         const uint32_t wr = xw + 1 < W2 ? rr[r][xw + 1] : (w0 >> 16);         // column W replicates column W-1
                         p[3 * r] = alignbit(w0, wl, 16); p[3 * r + 1] = w0; p[3 * r + 2] = alignbit(wr, w0, 16);   // (x-1, x), (x, x+1), (x+1, x+2)
                     }
-                    *reinterpret_cast<uint32_t*>(out + fo + (size_t)yo * W + 2 * xw) = median9(p, sort2_pk());
+                    *reinterpret_cast<uint32_t*>(out + fo + (size_t)yo * W + 2 * xw) = pk_add(median9(p, sort2_pk()), pk_bcast(16 * m));    // relative -> true disparity at the last write
                 }
             }
         }
@@ -223,23 +238,23 @@ __global__ __launch_bounds__(256) void k_lrcheck_median_rows(const uint32_t* __r
 int sgbm_lrcheck_median(const v3d_sgbm* h, int n, int W, int H, int16_t* out, bool med, hipStream_t st)
 {
     const uint32_t* wta = h->wta;
-    const int d12 = h->d12;
+    const int d12 = h->d12, m = h->prm.minDisparity;
     // the row march reads record pairs and writes disparity pairs: even widths, 8-byte aligned buffers
     const bool rows_ok = !h->lrm_tiles && W <= 4096 && (W & 1) == 0 && (reinterpret_cast<uintptr_t>(wta) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
     if (rows_ok) {
         const dim3 grid(v3d_cdiv(H, LRR_BAND), 1, n);
         const size_t smem = (size_t)W * 4 + (size_t)3 * (W / 2) * 4;
         if (W <= 2048) {
-            if (med) hipLaunchKernelGGL((k_lrcheck_median_rows<true, 4>), grid, dim3(256), smem, st, wta, W, H, d12, out);
-            else hipLaunchKernelGGL((k_lrcheck_median_rows<false, 4>), grid, dim3(256), smem, st, wta, W, H, d12, out);
+            if (med) hipLaunchKernelGGL((k_lrcheck_median_rows<true, 4>), grid, dim3(256), smem, st, wta, W, H, d12, m, out);
+            else hipLaunchKernelGGL((k_lrcheck_median_rows<false, 4>), grid, dim3(256), smem, st, wta, W, H, d12, m, out);
         } else {
-            if (med) hipLaunchKernelGGL((k_lrcheck_median_rows<true, 8>), grid, dim3(256), smem, st, wta, W, H, d12, out);
-            else hipLaunchKernelGGL((k_lrcheck_median_rows<false, 8>), grid, dim3(256), smem, st, wta, W, H, d12, out);
+            if (med) hipLaunchKernelGGL((k_lrcheck_median_rows<true, 8>), grid, dim3(256), smem, st, wta, W, H, d12, m, out);
+            else hipLaunchKernelGGL((k_lrcheck_median_rows<false, 8>), grid, dim3(256), smem, st, wta, W, H, d12, m, out);
         }
     } else {
         const dim3 grid(v3d_cdiv(W, LRM_TX), v3d_cdiv(H, LRM_TY), n);
-        if (med) hipLaunchKernelGGL(k_lrcheck_median<true>, grid, dim3(256), 0, st, wta, W, H, d12, out);
-        else hipLaunchKernelGGL(k_lrcheck_median<false>, grid, dim3(256), 0, st, wta, W, H, d12, out);
+        if (med) hipLaunchKernelGGL(k_lrcheck_median<true>, grid, dim3(256), 0, st, wta, W, H, d12, m, out);
+        else hipLaunchKernelGGL(k_lrcheck_median<false>, grid, dim3(256), 0, st, wta, W, H, d12, m, out);
     }
     V3D_LAUNCH_CHECK();
     return V3D_OK;

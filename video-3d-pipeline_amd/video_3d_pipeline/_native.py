@@ -915,11 +915,15 @@ def _quality_buffers(what, need, rows, fields, out, ws, device):
     return out, ws
 
 
-def quality_reproj_batch(lg, rg, disp16, bad_thr=16, out=None, ws=None):
+def quality_reproj_batch(lg, rg, disp16, bad_thr=16, out=None, ws=None, right_shift=0):
     """left / right gray u8 [n,H,W] and the int16 disparity [n,H,W] on the device (frames dense HxW, only the frame strides may
     differ) -> the reprojection records, int64 [n,8]: n_valid, n_cmp, sad, ssd, n_bad, sad0, ssd0, n_bad0 in 1/16 gray levels
     (v3d_quality_reproj_batch; bit-exact contract: tests/quality_ref.py).  out / ws: a caller's buffers; None takes them from the
-    caching allocator."""
+    caching allocator.
+    right_shift k > 0 (a disparity rebiased by a search window [-k, 64 - k), depth.py --min-disparity): columns [0, W - k) of the left
+    gray and of the disparity (made dense) against the right gray advanced by k bytes, same pitch: R'[i] = R[i + k], so u = 16 x - d
+    addresses the true match and the record's "disparity 0" is the disparity -k."""
+    k = int(right_shift)
     l, ls = _clip(lg, torch.uint8, "left gray")
     r, rs = _clip(rg, torch.uint8, "right gray")
     d, ds = _clip(disp16, torch.int16, "disp16")
@@ -928,9 +932,15 @@ def quality_reproj_batch(lg, rg, disp16, bad_thr=16, out=None, ws=None):
         raise NativeError(f"right gray {tuple(rg.shape)} / disp16 {tuple(disp16.shape)} do not match left gray {tuple(lg.shape)} (one frame stride for both grays)")
     if isinstance(bad_thr, bool) or int(bad_thr) != bad_thr or not 0 <= bad_thr <= 255:
         raise ValueError(f"bad threshold must be an integer in [0, 255], got {bad_thr!r}")
-    out, ws = _quality_buffers("quality_reproj_batch", lib().v3d_quality_reproj_ws_bytes(n, W, H), n, QUALITY_REPROJ_FIELDS, out, ws, lg.device)
+    if not 0 <= k < W:
+        raise ValueError(f"right_shift must lie in [0, W), got {right_shift!r}")
+    if k:
+        r = C.c_void_p(rg.data_ptr() + k)
+        dense = disp16[:, :, :W - k].contiguous()          # held until the launch is enqueued (the allocator is stream-ordered)
+        d, ds = _clip(dense, torch.int16, "disp16")
+    out, ws = _quality_buffers("quality_reproj_batch", lib().v3d_quality_reproj_ws_bytes(n, W - k, H), n, QUALITY_REPROJ_FIELDS, out, ws, lg.device)
     with torch.cuda.device(lg.device):
-        _check(lib().v3d_quality_reproj_batch(l, r, n, W, H, W, ls, d, ds, int(bad_thr), _dev(out, torch.int64, "out"),
+        _check(lib().v3d_quality_reproj_batch(l, r, n, W - k, H, W, ls, d, ds, int(bad_thr), _dev(out, torch.int64, "out"),
                                               _dev(ws, torch.uint8, "ws"), _stream()), "v3d_quality_reproj_batch")
     return out
 

@@ -29,6 +29,53 @@ import numpy as np
 from .utils import PngWriterPool, create_work_directory, get_video_info, iter_frames, write_png16
 
 
+# --min-disparity: the matcher's search window is [m, m + 64), m in [-64, 0] ("minDisparity"); 0 = the reference's
+MIN_DISPARITY_CANDIDATES = (0, -16, -32, -48, -64)       # what `auto` tries
+MIN_DISPARITY_CALIBRATION_FRAMES = 8
+MIN_DISPARITY_BAD = 16                                   # the quality report's default bad threshold: auto scores with it
+
+
+def check_min_disparity(value, allow_auto: bool = True):
+    """validated --min-disparity: an integer in [-64, 0], or "auto" where a clip is at hand"""
+    if isinstance(value, str) and value == "auto":
+        if not allow_auto:
+            raise ValueError('min_disparity="auto" needs a clip to calibrate on: give an integer here')
+        return "auto"
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not -64 <= value <= 0:
+        raise ValueError(f'min_disparity must be an integer in [-64, 0] or "auto", got {value!r}')
+    return int(value)
+
+
+def min_disparity_argument(text: str):
+    """argparse type of --min-disparity"""
+    try:
+        return check_min_disparity(text if text == "auto" else int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def choose_min_disparity(scores: Dict[int, int]) -> int:
+    """the rule of --min-disparity auto: scores[m] = pixels of the calibration frames whose reprojection error stays within the
+    bad threshold.  The candidate nearest 0 within 2 % of the best wins (integers: 100 * score >= 98 * best), so the reference's
+    window stays where it is as good; 0 when nothing scored"""
+    best = max(scores.values())
+    if best <= 0:
+        return 0
+    return max(m for m, s in scores.items() if 100 * s >= 98 * best)
+
+
+def calibration_frames(start_frame: int, frame_count: int) -> List[int]:
+    """the clip frames `auto` calibrates on: K = min(8, N) of the N the run will process, spread evenly"""
+    k = min(MIN_DISPARITY_CALIBRATION_FRAMES, frame_count)
+    stride = max(frame_count // k, 1) if k else 1
+    return [start_frame + stride // 2 + j * stride for j in range(k)]
+
+
+def min_disparity_suffix(m: int) -> str:
+    """what the depth cache key gains, after the temporal, range and fill suffixes, with a window other than [0, 64)"""
+    return f"_mind{m}" if m != 0 else ""
+
+
 class HipStereoBackend:
     """The product compute backend: PyTorch-ROCm buffers + libv3d_hip.so kernels."""
 
@@ -47,14 +94,21 @@ class HipStereoBackend:
         self._matcher = None
         self._geom = None
 
-    def _get_matcher(self, W, H, n):
+    def _get_matcher(self, W, H, n, min_disparity=0):
         g = self._geom
-        if self._matcher is None or g[0] < W or g[1] < H or g[2] < n:
+        if self._matcher is None or g[0] < W or g[1] < H or g[2] < n or g[3] != min_disparity:
             if self._matcher is not None:
                 self._matcher.close()
-            self._matcher = self.native.StereoSGBM(W, H, n, device=self.device, **self.sgbm_params)
-            self._geom = (W, H, n)
+            window = {"minDisparity": min_disparity} if min_disparity else {}
+            self._matcher = self.native.StereoSGBM(W, H, n, device=self.device, **dict(self.sgbm_params, **window))
+            self._geom = (W, H, n, min_disparity)
         return self._matcher
+
+    def close_matcher(self):
+        """destroy the matcher and its workspace (the next pass creates one): --min-disparity auto's calibration"""
+        if self._matcher is not None:
+            self._matcher.close()
+        self._matcher = self._geom = None
 
     @staticmethod
     def _lockstep_ok(matcher) -> bool:
@@ -70,15 +124,19 @@ class HipStereoBackend:
         matcher.set_lockstep(False)
         return False
 
-    def _match(self, lg, rg, out=None):
-        """gray [n,H,W] pairs -> int16 disparity x16 [n,H,W]; a pass whose lock-step kernel timed out is computed again"""
+    def _match(self, lg, rg, out=None, min_disparity=0):
+        """gray [n,H,W] pairs -> int16 disparity x16 [n,H,W]; a pass whose lock-step kernel timed out is computed again.
+        min_disparity m != 0: the matcher searches [m, m + 64) and its output is rebiased in place by -16 m, so valid values lie
+        in [0, 1023] and invalid ones are -16 -- the form everything after the matcher reads"""
         n, H, W = lg.shape
-        matcher = self._get_matcher(W, H, n)
+        matcher = self._get_matcher(W, H, n, min_disparity)
         disp = matcher.compute(lg, rg, out)
         if not self._lockstep_ok(matcher):
             disp = matcher.compute(lg, rg, out)
             if matcher.sync_errors():
                 raise RuntimeError("SGM kernels report time-outs with the lock-step pass off: device fault")
+        if min_disparity:
+            disp.sub_(16 * min_disparity)
         return disp
 
     def compute_batch_size(self, W: int, H: int, requested: int) -> int:
@@ -134,7 +192,8 @@ class HipStereoBackend:
         ws = self._staging("fill_ws", (max(16, nat.lib().v3d_fill_holes_ws_bytes(n, H)),), self.torch.uint8, False)
         return nat.fill_holes_disp16_batch(disp, out=disp, ws=ws)
 
-    def pairs_to_disparity(self, pairs: List[Tuple[np.ndarray, np.ndarray]], monos=None, fill_holes: bool = False) -> List[np.ndarray]:
+    def pairs_to_disparity(self, pairs: List[Tuple[np.ndarray, np.ndarray]], monos=None, fill_holes: bool = False,
+                           min_disparity: int = 0) -> List[np.ndarray]:
         """BGR (left, right) pairs -> float32 disparity maps (>= 0), depth.py:337-341 + 374 (+ 344-371 with `monos`);
         fill_holes: the matcher's invalid pixels are filled first (per frame, so this surface has it too)"""
         torch, nat = self.torch, self.native
@@ -145,7 +204,7 @@ class HipStereoBackend:
         for i, (l, r) in enumerate(pairs):
             lg[i] = nat.bgr_to_gray(nat.to_device(l, self.device))
             rg[i] = nat.bgr_to_gray(nat.to_device(r, self.device))
-        disp = self._match(lg, rg)
+        disp = self._match(lg, rg, min_disparity=min_disparity)
         if fill_holes:
             disp = self.fill_holes(disp)
         depth = self._depth_from(disp, monos)
@@ -162,12 +221,14 @@ class HipStereoBackend:
             bufs[key] = t
         return t
 
-    def sbs_to_disparity(self, frames: List[np.ndarray], unsqueeze: bool, mono_provider=None, fill_holes: bool = False):
+    def sbs_to_disparity(self, frames: List[np.ndarray], unsqueeze: bool, mono_provider=None, fill_holes: bool = False,
+                         min_disparity: int = 0):
         """fused path: SBS BGR frames -> device float32 disparity [n,H,W] (no BGR halves materialised).
         Frames are gathered into one pinned buffer and cross PCIe in a single asynchronous copy.
         mono_provider (neural guidance on): called with the left views as RGB arrays, its maps are blended in.
         fill_holes: the int16 disparity is filled in place after the matcher (and its lock-step recompute), before /16 and the
-        blend."""
+        blend.
+        min_disparity: the matcher's window [m, m + 64); the disparity is rebiased to [0, 64) right after it (_match)."""
         torch, nat = self.torch, self.native
         n = len(frames)
         H, W = frames[0].shape[:2]
@@ -181,7 +242,7 @@ class HipStereoBackend:
         lg = self._staging("lg", (n, H, ow), torch.uint8, False)
         rg = self._staging("rg", (n, H, ow), torch.uint8, False)
         nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
-        disp = self._match(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False))
+        disp = self._match(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False), min_disparity)
         if fill_holes:
             disp = self.fill_holes(disp)
         monos = None
@@ -254,13 +315,24 @@ class HipStereoBackend:
         place): a view of the staging buffer the next pass overwrites"""
         return self._bufs["disp"][:n]
 
-    def quality_reproj(self, n: int, bad_thr: int):
+    def quality_reproj(self, n: int, bad_thr: int, min_disparity: int = 0):
         """reprojection records int64 [n,8] of the latest pass's planes, on the device (v3d_quality_reproj_batch); the partial
-        records live in a staging buffer"""
+        records live in a staging buffer.  min_disparity m != 0: the pass's disparity is rebiased, so the entry sees the columns
+        [0, W + m) of the left view against the right view moved by -m columns: the true match, and the baseline d = m"""
         nat = self.native
         lg = self.left_gray(n)
-        ws = self._staging("quality_reproj_ws", (max(16, nat.lib().v3d_quality_reproj_ws_bytes(n, lg.shape[2], lg.shape[1])),), self.torch.uint8, False)
-        return nat.quality_reproj_batch(lg, self.right_gray(n), self.last_disp16(n), bad_thr, ws=ws)
+        ws = self._staging("quality_reproj_ws", (max(16, nat.lib().v3d_quality_reproj_ws_bytes(n, lg.shape[2] + min_disparity, lg.shape[1])),), self.torch.uint8, False)
+        shift = {"right_shift": -min_disparity} if min_disparity else {}
+        return nat.quality_reproj_batch(lg, self.right_gray(n), self.last_disp16(n), bad_thr, ws=ws, **shift)
+
+    def min_disparity_score(self, frames: List[np.ndarray], unsqueeze: bool, min_disparity: int) -> int:
+        """--min-disparity auto: the calibration frames through a matcher of their own at window m -> the number of pixels whose
+        reprojection error stays within the report's default threshold, sum over frames of n_cmp - n_bad"""
+        self.close_matcher()
+        self.sbs_to_disparity(frames, unsqueeze, **({"min_disparity": min_disparity} if min_disparity else {}))
+        rec = self.quality_reproj(len(frames), MIN_DISPARITY_BAD, **({"min_disparity": min_disparity} if min_disparity else {})).cpu().numpy()
+        self.close_matcher()
+        return int((rec[:, 1] - rec[:, 4]).sum())
 
     def quality_flicker(self, depth, gray, still: int, jump16: int):
         """flicker records int64 [T-1,4] of the consecutive frames depth f32 / gray u8 [T,H,W], on the device
@@ -394,7 +466,8 @@ class HybridStereoDepthExtractor:
                  quality_bad_threshold: int = 16,
                  quality_still: int = 4,
                  quality_jump: float = 1.0,
-                 temporal_motion: int = 0):
+                 temporal_motion: int = 0,
+                 min_disparity=0):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
@@ -408,7 +481,13 @@ class HybridStereoDepthExtractor:
         threads, as ever
         quality_report (process_video_sbs and the one-pass pipeline): True or a path measures the run's depth on the device without
         ground truth (quality.py) and writes quality.json next to the depth maps or to the path; quality_*: its thresholds.  No
-        output and no cache key changes """
+        output and no cache key changes
+        min_disparity (every surface): m in [-64, 0], the matcher searches disparities [m, m + 64) -- content behind the screen
+        plane has d < 0 -- and the result is rebiased to [0, 64): larger still means nearer, and the far end of the window
+        (rel = 0) is dropped like d = 0 is at m = 0 (depth.py:374).  "auto" (process_video_sbs and the one-pass pipeline)
+        calibrates m on frames of the clip (resolve_min_disparity).  0 = the reference's window: no call, key or byte changes """
+        self.min_disparity = check_min_disparity(min_disparity)
+        self.min_disparity_scores = None         # {candidate: score} of an `auto` run, once resolved
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
         from .temporal import check_motion_search, check_parameters, check_range_percentile
@@ -508,7 +587,28 @@ class HybridStereoDepthExtractor:
         it stays the call every backend knows"""
         if guidance is not None:
             args += (guidance,)
-        return call(*args, **({"fill_holes": True} if self.fill_holes else {}))
+        window = {"min_disparity": self.min_disparity} if self.min_disparity != 0 else {}
+        return call(*args, **({"fill_holes": True} if self.fill_holes else {}), **window)
+
+    def resolve_min_disparity(self, video_path: str, start_frame: int, frame_count: int) -> int:
+        """--min-disparity auto -> its integer, before anything is keyed by it: every candidate window scores the calibration
+        frames by reprojection (backend.min_disparity_score), choose_min_disparity picks.  Under torchrun every rank decodes
+        the same frames and reaches the same integer: no collective"""
+        if self.min_disparity != "auto":
+            return self.min_disparity
+        if frame_count < 1:
+            self.min_disparity = 0
+            return 0
+        picks = calibration_frames(start_frame, frame_count)
+        stride = picks[1] - picks[0] if len(picks) > 1 else 1
+        frames = list(iter_frames(video_path, picks[0], (len(picks) - 1) * stride + 1, stride=stride))
+        scores = {m: int(self.backend.min_disparity_score(frames, self.unsqueeze_sbs, m)) for m in MIN_DISPARITY_CANDIDATES} if frames else \
+                 {m: 0 for m in MIN_DISPARITY_CANDIDATES}
+        self.min_disparity = choose_min_disparity(scores)
+        self.min_disparity_scores = {str(m): s for m, s in scores.items()}
+        print(f"--min-disparity auto: calibrated on frames {picks}")
+        print("  " + "  ".join(f"m={m}: {s}" for m, s in scores.items()) + f"  -> {self.min_disparity}")
+        return self.min_disparity
 
     def manifest_extra(self) -> dict:
         """what the options that are on add to the one-pass pipeline's manifest (none: nothing); write_side_files puts the
@@ -519,6 +619,10 @@ class HybridStereoDepthExtractor:
             extra["temporal"] = manifest_entry(*self.temporal, self.range_quantile, self.motion_search)
         if self.fill_holes:
             extra["fill_holes"] = True
+        if self.min_disparity != 0 or self.min_disparity_scores is not None:
+            extra["min_disparity"] = self.min_disparity
+        if self.min_disparity_scores is not None:
+            extra["min_disparity_scores"] = self.min_disparity_scores
         if self.guide_check is not None and self.guide_check.summary is not None:
             extra["guide_match"] = self.guide_check.summary
         if self.quality is not None and self.quality.summary is not None:
@@ -532,8 +636,10 @@ class HybridStereoDepthExtractor:
             from .quality import QualityMonitor
             stage = "matcher+fill" if self.fill_holes else "matcher"
             bad, still, _, cut = self.quality_params
+            window = {"min_disparity": self.min_disparity} if self.min_disparity != 0 else {}
             self.quality = QualityMonitor(self.backend, bad, still, self.quality_jump, cut, consecutive=world == 1, reproj_stage=stage,
-                                          flicker_stage="hybrid blend" if self._guidance_provider() is not None else stage, owned=owned)
+                                          flicker_stage="hybrid blend" if self._guidance_provider() is not None else stage, owned=owned,
+                                          **window)
         return self.quality
 
     def finish_quality(self, default_dir, rank: int = 0):
@@ -557,13 +663,16 @@ class HybridStereoDepthExtractor:
             print(CACHED_NOTE)
 
     def write_side_files(self, cache_path: Path):
-        """temporal.json (a radius or the robust range is on) and fill.json (--fill-holes) of a depth map directory"""
+        """temporal.json (a radius or the robust range is on), fill.json (--fill-holes) and min_disparity.json (--min-disparity)
+        of a depth map directory"""
         import json
         extra = self.manifest_extra()
         if "temporal" in extra:
             (cache_path / "temporal.json").write_text(json.dumps(extra["temporal"]))
         if "fill_holes" in extra:
             (cache_path / "fill.json").write_text(json.dumps({"fill_holes": True}))
+        if "min_disparity" in extra:
+            (cache_path / "min_disparity.json").write_text(json.dumps({k: extra[k] for k in ("min_disparity", "min_disparity_scores") if k in extra}))
 
     def _guidance_provider(self):
         """ the provider when neural guidance is active (depth.py:344-345), else None """
@@ -573,10 +682,14 @@ class HybridStereoDepthExtractor:
 
     def get_cache_path(self, video_path: str, frame_start: int, frame_count: int) -> Path:
         """ Generate cache path for depth maps (key format identical to depth.py:119-120; with temporal stabilisation or the
-        robust range on, the key also carries their parameters, so such maps and the reference's never share a directory) """
+        robust range on, the key also carries their parameters, so such maps and the reference's never share a directory; so
+        does a search window other than [0, 64): the resolved integer, which an `auto` run and an explicit one share) """
+        if self.min_disparity == "auto":
+            raise ValueError('min_disparity="auto" is resolved from the clip first (resolve_min_disparity)')
         from .temporal import cache_suffix, fill_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
         cache_key += cache_suffix(*self.temporal, self.range_quantile, self.motion_search) + fill_suffix(self.fill_holes)
+        cache_key += min_disparity_suffix(self.min_disparity)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -637,6 +750,7 @@ class HybridStereoDepthExtractor:
 
     def process_frame_batch(self, frame_pairs: List[Tuple[np.ndarray, np.ndarray]]) -> List[np.ndarray]:
         """ Process batch of BGR frame pairs -> list of HxW float32 disparity maps (>= 0) """
+        check_min_disparity(self.min_disparity, allow_auto=False)        # a list of pairs is not a clip
         if not self.model_loaded:
             self.load_model()
         batch_size = len(frame_pairs)
@@ -675,6 +789,7 @@ class HybridStereoDepthExtractor:
         print(f"Video info: {video_info['width']}x{video_info['height']} @ {video_info['fps']:.1f}fps")
         print(f"Processing {frame_count} frames starting from frame {start_frame}")
 
+        self.resolve_min_disparity(video_path, start_frame, frame_count)
         cache_path = self.get_cache_path(video_path, start_frame, frame_count)
         if not force_reprocess and self.is_cached(cache_path, frame_count):
             print("✓ Using cached depth maps")
@@ -811,6 +926,10 @@ def add_depth_arguments(parser, force_help: str):
     add_temporal_arguments(parser)
     add_range_arguments(parser)
     add_fill_arguments(parser)
+    parser.add_argument('--min-disparity', type=min_disparity_argument, default=0, metavar='M|auto',
+                        help='Search disparities [M, M + 64) instead of [0, 64), M in [-64, 0]: content behind the screen plane of '
+                             'a stereoscopic film has negative disparity.  The result is rebiased to [0, 64), so larger still means '
+                             'nearer.  auto: calibrate M on up to 8 frames of the clip by reprojection error (default: 0)')
     add_png_arguments(parser)
     add_quality_arguments(parser)
 
@@ -824,7 +943,7 @@ def depth_options(args) -> dict:
     return dict(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device, batch_size=args.batch_size,
                 use_neural_guidance=not stereo_only, stereo_only=stereo_only, unsqueeze_sbs=not args.no_unsqueeze,
                 **temporal_options(args), **range_options(args), **fill_options(args), **png_options(args),
-                **quality_options(args))
+                **quality_options(args), **({"min_disparity": args.min_disparity} if args.min_disparity != 0 else {}))
 
 
 def main(argv=None):

@@ -129,7 +129,8 @@ class SbsTo4kDepthPipeline:
                  quality_bad_threshold: int = 16,
                  quality_still: int = 4,
                  quality_jump: float = 1.0,
-                 temporal_motion: int = 0):
+                 temporal_motion: int = 0,
+                 min_disparity=0):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own; temporal_motion > 0: the
         window follows the block matcher's motion);
@@ -138,7 +139,8 @@ class SbsTo4kDepthPipeline:
         png_encoder: "gpu" deflates every PNG this run writes on the device (png_gpu.py); "zlib" = on the writer threads;
         check_guide: score every (left view, 4K frame) pair the run uses (framematch.GuideChecker); no output PNG changes;
         quality_*: the depth CLI's --quality-report (quality.py): quality.json goes next to the kept depth maps, else next to the
-        4K frames, or to the given path; no output PNG changes"""
+        4K frames, or to the given path; no output PNG changes;
+        min_disparity: the depth CLI's --min-disparity (an integer in [-64, 0] or "auto"; 0 = off: the window [0, 64))"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -151,7 +153,7 @@ class SbsTo4kDepthPipeline:
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
             temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes,
             png_encoder=png_encoder, quality_report=quality_report, quality_bad_threshold=quality_bad_threshold,
-            quality_still=quality_still, quality_jump=quality_jump, temporal_motion=temporal_motion)
+            quality_still=quality_still, quality_jump=quality_jump, temporal_motion=temporal_motion, min_disparity=min_disparity)
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
         self.check_guide, self.check_guide_min = bool(check_guide), float(check_guide_min)
@@ -184,7 +186,10 @@ class SbsTo4kDepthPipeline:
         if not info4k:
             raise ValueError(f"Could not read video info: {video_4k}")
         Whi, Hhi, fps = info4k['width'], info4k['height'], info4k['fps']
-        cache_path = ex.get_cache_path(sbs_video, start_frame, frame_count) if keep_depth_maps or output_path is None else None
+        reuse = output_path is not None and Path(output_path).exists() and not force_reprocess     # nothing will be computed
+        if not reuse:
+            ex.resolve_min_disparity(sbs_video, start_frame, frame_count)   # --min-disparity auto -> its integer, before anything is keyed by it
+        cache_path = ex.get_cache_path(sbs_video, start_frame, frame_count) if (keep_depth_maps or output_path is None) and ex.min_disparity != "auto" else None
         if output_path is None:
             output_path = f"depth_4k_{cache_path.name}.mp4"          # what the upscale CLI names its output for that directory
         output_path = Path(output_path)

@@ -98,9 +98,12 @@ class QualityMonitor:
 
     def __init__(self, backend, bad_threshold: int = DEFAULT_BAD, still: int = DEFAULT_STILL, jump: float = DEFAULT_JUMP,
                  cut_threshold: int = DEFAULT_CUT, consecutive: bool = True, reproj_stage: str = "matcher", flicker_stage: str = "matcher",
-                 owned: Optional[range] = None):
+                 owned: Optional[range] = None, min_disparity: int = 0):
         """consecutive: the frames arrive in clip order without gaps (one process); False switches flicker off (a sharded run).
-        owned: the clip frames whose reprojection records count (a rank's block without its halo); None = all"""
+        owned: the clip frames whose reprojection records count (a rank's block without its halo); None = all
+        min_disparity m != 0 (--min-disparity): the pass's disparity is rebiased by -16 m; the backend's quality_reproj is told, and
+        the "disparity 0" figures of the record are the hypothesis d = m (reported as baseline_disparity)"""
+        self.min_disparity = int(min_disparity)
         self.bad_threshold, self.still, self.jump16, self.cut_threshold = check_parameters(bad_threshold, still, jump, cut_threshold)
         self.backend, self.consecutive = backend, bool(consecutive)
         self.reproj_stage, self.flicker_stage, self.owned = reproj_stage, flicker_stage, owned
@@ -130,7 +133,8 @@ class QualityMonitor:
         self._drain(False)                   # earlier passes: their events fired with the consumer's own synchronise
         be = self.backend
         self.shape = tuple(int(v) for v in depth.shape[1:])
-        self._enqueue(be.quality_reproj(n, self.bad_threshold), self.frames, list(indices))
+        window = {"min_disparity": self.min_disparity} if self.min_disparity else {}
+        self._enqueue(be.quality_reproj(n, self.bad_threshold, **window), self.frames, list(indices))
         if self.consecutive:
             self.matched.push(indices[0], depth[:n], be.left_gray(n))
 
@@ -155,6 +159,8 @@ class QualityMonitor:
         params = dict(bad_threshold=self.bad_threshold, still=self.still, jump=self.jump16 / 16, jump16=self.jump16, cut_threshold=self.cut_threshold)
         reproj = dict(frames=n_frames, totals=tot, **reproj_summary(tot, n_frames * W * H))
         self.summary = dict(parameters=params, reproj_stage=self.reproj_stage, flicker_stage=self.flicker_stage, reproj=reproj)
+        if self.min_disparity:
+            self.summary["baseline_disparity"] = self.min_disparity
         data = dict(self.summary, width=W, height=H, units=dict(error="1/16 gray level", flicker="1/16 px"),
                     frames=[dict(frame=int(i), **{k: int(v) for k, v in zip(REPROJ_FIELDS, r)}) for i, r in frames])
         if not self.consecutive:
@@ -175,6 +181,9 @@ class QualityMonitor:
         pct = lambda v: "n/a" if v is None else f"{100 * v:.2f} %"
         num = lambda v: "n/a" if v is None else f"{v:.3f}"
         print(f"Quality report ({r['frames']} frames, disparity of the {s['reproj_stage']}):")
+        if self.min_disparity:
+            print(f"  search window [{self.min_disparity}, {self.min_disparity + 64}): \"disparity 0\" below reads disparity {self.min_disparity} "
+                  f"(baseline_disparity), compared over the {-self.min_disparity} columns narrower left view")
         print(f"  valid {pct(r['valid_share'])} of the pixels, compared {pct(r['compared_share'])}")
         print(f"  reprojection error: mean abs {num(r['mean_abs_error'])} levels (disparity 0: {num(r['mean_abs_error_d0'])}), "
               f"RMS {num(r['rms_error'])} (disparity 0: {num(r['rms_error_d0'])}), above {self.bad_threshold} levels {pct(r['bad_share'])} "
