@@ -282,14 +282,22 @@ int v3d_corr_lookup(const uint16_t* fl_bf16, const uint16_t* fr_bf16, const floa
 /* Audio cross-correlation (v3d_align.hip).  a1, a2: float32 tracks of n1, n2 samples; N = the smallest power of two
    >= n1 + n2 - 1 and >= 2^10; N > 2^26 (about 25 minutes per track at 22.05 kHz) -> V3D_ERR_UNSUPPORTED.
    ws: device scratch of v3d_xcorr_ws_bytes(n1, n2) bytes (0 = unsupported sizes), shared by both entries; each call
-   writes its own twiddle tables into it. */
+   writes its own twiddle tables into it.
+   Domain (what tests/test_align_edges_gpu.py pins): finite samples, |a| <= 1e15, and for v3d_align_audio a std of 0 (a
+   constant track) or >= 3e-19; outside it the result is unspecified, except for the following.
+   Non-finite input: a NaN, +inf or -inf anywhere in either track is legal.  Both entries return V3D_OK and write nothing
+   outside out / result / ws.  v3d_xcorr: every out[k] is NaN.  v3d_align_audio: lag = 0, c = 0 and strength = 0 exactly;
+   result[3] is the std of the finite track, NaN when neither track is finite. */
 size_t v3d_xcorr_ws_bytes(int n1, int n2);
 /* out[k], k in [0, n1+n2-1): scipy.signal.correlate(a2, a1, 'full') of the RAW inputs (no normalisation) */
 int v3d_xcorr(const float* a1, int n1, const float* a2, int n2, float* out, void* ws, void* stream);
 /* result (device, 4 doubles): lag in samples (a1[n] ~ a2[n+lag]), signed c(lag) of the normalised tracks,
    strength, min(std1, std2).  an = (a - mean) / (std + 1e-10) (f64 mean and population std, rounded to float32);
-   c(L) = sum_n a2n[n+L] a1n[n]; strength = |c(lag)| / sqrt(E1 E2), E = sum an^2.  The FFT only nominates candidate
-   lags; lag and c come from direct f64 sums over the overlap: the largest |c| wins, the smallest lag on a tie. */
+   c(L) = sum_n a2n[n+L] a1n[n]; strength = |c(lag)| / sqrt(E1 E2), E = sum an^2 (0 when E1 E2 = 0).  The FFT only
+   nominates candidate lags (one per block of 4096 lags, the 16 largest blocks, +-2 neighbours each); lag and c come from
+   direct f64 sums over the overlap.  A maximum of |c| that is unique among the valid lags -(n1-1) .. n2-1 wins.  Among
+   exactly tied lags the call returns one of them, with its exact c and strength: the smallest of those nominated, and
+   which are nominated depends on float32 rounding (an all-zero correlation returns some valid lag with c = 0). */
 int v3d_align_audio(const float* a1, int n1, const float* a2, int n2, double* result, void* ws, void* stream);
 
 /* DIBR stereo rendering (v3d_stereo.hip): 4K BGR frame + its u16 depth (larger = nearer) -> side-by-side 3D.  Per row and eye

@@ -7,55 +7,10 @@ import numpy as np
 import pytest
 import torch
 
+from align_ref import RATE, _direct, _norm64, _oracle_align, _ref_corr, _tracks, spectral_error, white
+from test_align_edges_gpu import K
+
 pytestmark = pytest.mark.gpu
-
-RATE = 22050
-
-
-def _ref_corr(a1, a2):
-    """float64 scipy.signal.correlate(a2, a1, 'full'): index k = lag + n1 - 1"""
-    a1 = np.asarray(a1, np.float64)
-    a2 = np.asarray(a2, np.float64)
-    n1, n2 = a1.size, a2.size
-    n = 1 << int(np.ceil(np.log2(n1 + n2 - 1)))
-    c = np.fft.irfft(np.conj(np.fft.rfft(a1, n)) * np.fft.rfft(a2, n), n)
-    return np.concatenate([c[n - (n1 - 1):], c[:n2]]) if n1 > 1 else c[:n2]
-
-
-def _direct(a1, a2, L):
-    """c(L) = sum_n a2[n + L] a1[n] in float64"""
-    a1 = np.asarray(a1, np.float64)
-    a2 = np.asarray(a2, np.float64)
-    lo, hi = max(0, -L), min(a1.size, a2.size - L)
-    return float(np.dot(a2[lo + L:hi + L], a1[lo:hi])) if hi > lo else 0.0
-
-
-def _norm64(a):
-    a = np.asarray(a, np.float64)
-    return (a - a.mean()) / (a.std() + 1e-10)
-
-
-def _band_noise(n, rng, lo=80.0, hi=5000.0):
-    """band-limited noise plus a few tones"""
-    spec = np.fft.rfft(rng.standard_normal(n))
-    f = np.fft.rfftfreq(n, 1.0 / RATE)
-    spec[(f < lo) | (f > hi)] = 0
-    x = np.fft.irfft(spec, n)
-    t = np.arange(n) / RATE
-    for fr, amp in ((220.0, 0.3), (997.0, 0.2), (3150.0, 0.1)):
-        x += amp * x.std() * np.sin(2 * np.pi * fr * t + rng.uniform(0, 6))
-    return x / np.abs(x).max()
-
-
-def _tracks(n1, n2, lag, seed, noise=0.2):
-    """a1[n] ~ a2[n + lag]: two recordings of one source, each with its own noise, float32"""
-    rng = np.random.default_rng(seed)
-    p1 = max(lag, 0) + 17
-    p2 = p1 - lag
-    s = _band_noise(max(p1 + n1, p2 + n2) + 1, rng)
-    a1 = s[p1:p1 + n1] + noise * rng.standard_normal(n1) * s.std()
-    a2 = 0.7 * s[p2:p2 + n2] + noise * rng.standard_normal(n2) * s.std() + 0.01
-    return a1.astype(np.float32), a2.astype(np.float32)
 
 
 def _dev(a):
@@ -88,6 +43,14 @@ def test_xcorr_every_fft_size(native, m):
         tol = 1e-5 * np.linalg.norm(a1.astype(np.float64)) * np.linalg.norm(a2.astype(np.float64))
         err = np.abs(got - want).max()
         assert err <= tol, (m, n1, n2, err, tol)
+    # a second, zero-mean white input held per spectrum bin (tests/align_ref.py; the bound above divides a one-bin error by N)
+    rng = np.random.default_rng(1000 + m)
+    for n1, n2 in _xcorr_cases(m)[:2]:
+        a1, a2 = white(n1, rng), white(n2, rng)
+        got = native.xcorr(_dev(a1), _dev(a2)).cpu().numpy().astype(np.float64)
+        units = spectral_error(got, a1, a2)
+        print(f"xcorr 2^{m} ({n1}, {n2}): {units:.3f} units of eps32 log2 N per bin")
+        assert units <= K, (m, n1, n2, units, K)
 
 
 @pytest.mark.timeout(900)
@@ -121,15 +84,6 @@ def test_xcorr_refuses_oversize(native):
 
 
 # ---------------------------------------------------------------- v3d_align_audio
-
-def _oracle_align(a1, a2):
-    """find_audio_offset in float64: (lag, signed c, strength, min std)"""
-    x1, x2 = _norm64(a1), _norm64(a2)
-    c = _ref_corr(x1, x2)
-    k = int(np.argmax(np.abs(c)))
-    strength = abs(c[k]) / np.sqrt(np.sum(x1 * x1) * np.sum(x2 * x2))
-    return k - (a1.size - 1), c[k], strength, min(np.std(a1.astype(np.float64)), np.std(a2.astype(np.float64)))
-
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("n1,n2,lag", [

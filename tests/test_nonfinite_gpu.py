@@ -4,7 +4,10 @@ DESIGN.md section 4) without ever converting a non-finite float: tests/temporal_
 quality_ref.py, corr_ref.py, the f64 oracle of the guided filter and a NumPy transcription of depth.py:344-374.
 
 Every batch has at least three frames and only the middle one carries a special: the neighbours' outputs must equal the clean
-run's, which checks slot and stride indexing.  Every input is a legal buffer of legal size."""
+run's, which checks slot and stride indexing.  Every input is a legal buffer of legal size.
+
+The two audio entries (v3d_xcorr, v3d_align_audio) take one pair of tracks per call: a NaN or an infinity at the first, a middle
+and the last sample of either track or both, inside guard arenas."""
 import contextlib
 import ctypes as C
 
@@ -610,3 +613,66 @@ def test_extractor_with_a_provider_that_returns_a_nan_and_an_inf(native, oracle,
             assert np.array_equal(want, oracle.depth_to_u16(oracle.disp_to_depth(d16))) and want.any()   # stereo only
         if i == 2:
             assert np.isnan(blend).any() and not want.any()                                               # an all-zero frame
+
+
+# ---------------------------------------------------------------- the audio entries inside a guard arena
+
+AUDIO_N1, AUDIO_N2 = 3000, 3500
+
+
+def _audio_arena(lib, out_dtype, out_n, poison):
+    a = Arena("cuda", poison)
+    b1 = a.buf("a1", "in", np.float32, (AUDIO_N1,))
+    b2 = a.buf("a2", "in", np.float32, (AUDIO_N2,))
+    bo = a.buf("out", "out", out_dtype, (out_n,), align=8)
+    ws = a.buf("ws", "ws", np.uint8, (int(lib.v3d_xcorr_ws_bytes(AUDIO_N1, AUDIO_N2)),), align=16)
+    return a, b1, b2, bo, ws
+
+
+def _audio_cases():
+    """(label, a1, a2, finite1, finite2): a NaN, +inf or -inf at the first, a middle and the last sample of a1, of a2, of both"""
+    rng = np.random.default_rng(21)
+    base = rng.standard_normal(AUDIO_N2 + 400).astype(np.float32)
+    c2 = base[:AUDIO_N2].copy()
+    c1 = (base[137:137 + AUDIO_N1] + 0.05 * rng.standard_normal(AUDIO_N1)).astype(np.float32)
+    yield "clean", c1, c2, True, True
+    for k, name in enumerate(("nan+", "nan-", "+inf", "-inf")):
+        for pos in ("first", "middle", "last"):
+            for in1, in2 in ((True, False), (False, True), (True, True)):
+                a1, a2 = c1.copy(), c2.copy()
+                for on, a in ((in1, a1), (in2, a2)):
+                    if on:
+                        a[{"first": 0, "middle": a.size // 2 + k, "last": a.size - 1}[pos]] = NF.SPECIALS[name]
+                yield f"{name} at the {pos} sample of {'a1' if in1 else ''}{' and ' if in1 and in2 else ''}{'a2' if in2 else ''}", a1, a2, not in1, not in2
+
+
+@pytest.mark.parametrize("poison", [0xA5, 0x00])
+def test_audio_entries_with_non_finite_samples(native, poison):
+    """v3d_xcorr and v3d_align_audio at (3000, 3500), tracks, out / result and ws inside guard arenas.  Both return V3D_OK and
+    write nothing outside out / result / ws.  v3d_xcorr: every output is NaN (a transform spreads a NaN over every bin, and an
+    infinity meets 0 * inf or inf - inf on the way).  v3d_align_audio: a NaN never wins the block maxima's `v > best`, so no lag is
+    nominated: lag = 0, c = 0 and strength = 0 exactly, and result[3] is the finite track's std, NaN when neither is finite."""
+    lib = native.lib()
+    P = lambda b: C.c_void_p(b.ptr)                                  # noqa: E731
+    st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    ax, x1, x2, xo, xw = _audio_arena(lib, np.float32, AUDIO_N1 + AUDIO_N2 - 1, poison)
+    aa, r1, r2, ro, rw = _audio_arena(lib, np.float64, 4, poison)
+    for label, a1, a2, fin1, fin2 in _audio_cases():
+        x1.set(a1), x2.set(a2), r1.set(a1), r2.set(a2)
+        ax.fill().snapshot()
+        assert lib.v3d_xcorr(P(x1), a1.size, P(x2), a2.size, P(xo), P(xw), st()) == 0, label
+        torch.cuda.synchronize()
+        ax.check()
+        aa.fill().snapshot()
+        assert lib.v3d_align_audio(P(r1), a1.size, P(r2), a2.size, P(ro), P(rw), st()) == 0, label
+        torch.cuda.synchronize()
+        aa.check()
+        out, res = xo.get(), ro.get()
+        sd = [float(np.std(a.astype(np.float64))) if fin else None for a, fin in ((a1, fin1), (a2, fin2))]
+        if fin1 and fin2:
+            assert np.isfinite(out).all() and res[0] == 137 and res[2] > 0.9 and abs(res[3] - min(sd)) <= 1e-9 * min(sd), label
+            continue
+        assert np.isnan(out).all(), (label, int((~np.isnan(out)).sum()), np.flatnonzero(~np.isnan(out))[:4].tolist())
+        assert res[0] == 0 and res[1] == 0 and res[2] == 0, (label, res.tolist())
+        want = sd[0] if fin1 else sd[1] if fin2 else None
+        assert np.isnan(res[3]) if want is None else abs(res[3] - want) <= 1e-9 * want, (label, res.tolist(), want)

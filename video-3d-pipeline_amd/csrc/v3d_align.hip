@@ -4,7 +4,8 @@
 //   1. f64 reductions: mean, population std, then an = (a - mean) / (std + 1e-10) rounded to float32, E = sum an^2.
 //   2. pack z[n] = s1 a1n[n] + i s2 a2n[n], zero-padded to N = 2^m (N >= n1 + n2 - 1, N >= 2^10, m <= 26).  s1, s2 are
 //      powers of two that bring both tracks to a norm near 1: the float32 error of the two-for-one FFT is of the order
-//      eps |z|^2, so unequal norms would put the larger track's error onto the smaller one's correlation.
+//      eps |z|^2, so unequal norms would put the larger track's error onto the smaller one's correlation.  The norm of
+//      an is sqrt(n) std / (std + 1e-10): a track with std far below 1e-10 is as far below sqrt(n).
 //   3. forward FFT of z in 1 to 3 in-place passes through HBM (see FftPlan): each pass runs LDS-resident radix-4/2
 //      sub-FFTs of R = 2^d points over a tile whose global rows hold 16 consecutive complex values (128 bytes), with the
 //      inter-pass twiddle fused into the pass.  The spectrum ends in digit-reversed order (storage position perm(k)).
@@ -13,7 +14,9 @@
 //   5. inverse FFT (the forward passes transposed, in reverse order: digit-reversed in, natural order out).  The real
 //      part is the circular correlation c[L mod N] = sum_n a2n[n + L] a1n[n].
 //   6. peak: per-block maxima of |c| over the valid lags, the TOPK largest, each with its +-NB neighbours, are
-//      re-evaluated by direct f64 sums over their overlap; the largest |c| wins (smallest lag on a tie).
+//      re-evaluated by direct f64 sums over their overlap; the largest |c| wins.  A maximum that is unique among the
+//      valid lags is found; of exactly tied lags the smallest NOMINATED one is returned, and which of them a block
+//      nominates (one lag per block, by the float32 value) depends on rounding.
 // Twiddles are computed in f64 (sincospi) and rounded to float32 into the caller's workspace by every call.  Every
 // reduction has a fixed order: a call's result does not depend on scheduling.
 #include "v3d_common.h"
@@ -188,7 +191,12 @@ __global__ __launch_bounds__(RED_THREADS) void k_xc_finish(const double* __restr
         if (threadIdx.x == 0) {
             const double n = t ? n2 : n1;
             if (MODE == RED_SUM) stats[t * 4] = s / n;
-            else if (MODE == RED_VAR) { stats[t * 4 + 1] = sqrt(s / n); stats[t * 4 + 3] = sqrt(n); }   // |an| ~ sqrt(n)
+            else if (MODE == RED_VAR) {
+                // |an| = sqrt(n) std / (std + 1e-10): sqrt(n) for ordinary audio, far below it for a track quieter than 1e-10
+                const double sd = sqrt(s / n);
+                stats[t * 4 + 1] = sd;
+                stats[t * 4 + 3] = sqrt(n) * (sd / (sd + 1e-10));
+            }
             else if (MODE == RED_SQ) stats[t * 4 + 3] = sqrt(s);
             else stats[t * 4 + 2] = s;
         }
@@ -471,7 +479,8 @@ __global__ __launch_bounds__(256) void k_xc_direct(const float* __restrict__ an1
     }
 }
 
-// result = {lag, c(lag), |c| / sqrt(E1 E2), min(std1, std2)}: the largest |c| among the valid candidates, smallest lag on a tie
+// result = {lag, c(lag), |c| / sqrt(E1 E2), min(std1, std2)}: the largest |c| among the valid candidates, the smallest of them on
+// a tie; no candidate (a NaN correlation nominates none): lag = c = strength = 0
 __global__ __launch_bounds__(128) void k_xc_pick(const int* __restrict__ cand, const double* __restrict__ dpart, int nchunk, int n1, int n2,
                                                  const double* __restrict__ stats, double* __restrict__ result)
 {
