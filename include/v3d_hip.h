@@ -42,7 +42,11 @@
  *    and are sized at create time;
  *  - memory contract (tests/test_abi_guard_gpu.py holds every entry to it): a typed pointer needs only the natural alignment
  *    of its element type and a `void* ws` 16 bytes, unless the entry's comment says otherwise, and an entry that needs more
- *    refuses with V3D_ERR_ARG; rows are `pitch` bytes apart and only the payload of a row is read; workspaces and outputs may
+ *    refuses with V3D_ERR_ARG; rows are `pitch` bytes apart and only the payload of a row is read, with one exception:
+ *    v3d_fill_holes_disp16_batch and v3d_render_stereo[_subpixel]_batch load the aligned 16-byte blocks that hold a row's payload,
+ *    so they touch up to 15 bytes on either side of a frame (never a block that holds no payload byte of the input, and no value
+ *    from outside the payload reaches a result): an input of theirs must be readable up to those block borders, as every device
+ *    allocation is (tests/test_stereo_emulated.py, tests/test_fill_emulated.py); workspaces and outputs may
  *    hold anything on entry; nothing outside the stated extent of an output or a workspace is written, inputs included;
  *  - `stream` is a hipStream_t passed as void*; calls enqueue work and do NOT synchronise;
  *  - return 0 on success, negative on error; v3d_last_error() returns the thread-local message;

@@ -1,9 +1,12 @@
 """csrc/v3d_png.hip itself (with csrc/v3d_wave.h), without a GPU: the kernel source is compiled as plain C++ against
-tests/png_emu/v3d_common.h, where the 256 threads of a workgroup are fibers and barriers / wave shuffles are rendezvous, and
+tests/emu/v3d_common.h, where the 256 threads of a workgroup are fibers and barriers / wave shuffles are rendezvous, and
 v3d_png_deflate_batch is called on poisoned host buffers at the alignments the header grants.  `out` and `offsets` must equal tests/png_ref.py byte for byte --
 streams, zero gaps, zero tail --, nothing outside `out`, `offsets` and `ws` may change, and every 16-byte load must be aligned.
 This checks the kernels' arithmetic and indexing; what only the device can show (LDS atomics, real wave scheduling, speed) is
-left to tests/test_png_gpu.py and tests/test_png_guard_gpu.py."""
+left to tests/test_png_gpu.py and tests/test_png_guard_gpu.py.
+The same cases then run through the stand-alone driver (tests/emu_case.py), plain and under AddressSanitizer and
+UndefinedBehaviorSanitizer: heap buffers that end on their payload's last byte, dynamic LDS of exactly the launch's size, both
+workgroup and thread orders, two LDS and two global poisons."""
 import ctypes as C
 import os
 import shutil
@@ -12,11 +15,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import emu_case as E
 import png_ref as P
+from emu_case import CSRC, EMU
 from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "video-3d-pipeline_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "png_emu")
 
 
 @pytest.fixture(scope="module")
@@ -24,15 +26,11 @@ def emu(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++")
     assert cxx, "a host C++ compiler is needed (the oracle's Makefile needs one as well)"
     d = tmp_path_factory.mktemp("png_emu")
-    text = open(os.path.join(CSRC, "v3d_png.hip")).read()
-    decl = "extern __shared__ __attribute__((aligned(16))) uint8_t smem[];"
-    assert text.count(decl) == 1
-    (d / "v3d_png.cpp").write_text(text.replace(decl, "extern uint8_t smem[];"))       # the harness defines it, 16-byte aligned
-    for name, src in (("v3d_png_books.h", CSRC), ("v3d_wave.h", CSRC), ("v3d_common.h", EMU), ("harness.cpp", EMU)):
-        shutil.copy(os.path.join(src, name), d / name)
+    assert open(os.path.join(CSRC, "v3d_png.hip")).read().count("extern __shared__") == 1
+    src, = E.stage(str(d), ["v3d_png.hip"])
     lib = d / "libpngemu.so"
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-o", str(lib),
-                           str(d / "v3d_png.cpp"), str(d / "harness.cpp")])
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-I", str(d), "-I", EMU, "-I", os.path.join(ROOT, "include"),
+                           "-o", str(lib), src, os.path.join(EMU, "harness.cpp")])
     L = C.CDLL(str(lib))
     L.v3d_png_out_bytes.restype = L.v3d_png_ws_bytes.restype = C.c_size_t
     L.v3d_png_deflate_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_int] * 4 + [C.c_void_p] * 4
@@ -80,3 +78,33 @@ def test_kernel_source_equals_the_reference(emu, fmt, W, H, n, pad, skew_img, sk
     for block, snap, view in ((bo, before[1], out), (bw, before[2], ws), (bf, before[3], off)):
         lo = view.ctypes.data - block.ctypes.data
         assert np.array_equal(block[:lo], snap[:lo]) and np.array_equal(block[lo + view.size:], snap[lo + view.size:]), "a store outside its buffer"
+
+
+# ---- the same source in the stand-alone driver, plain and sanitized ----
+driver = E.driver_fixture("png", ["v3d_png.hip"], ["v3d_png_deflate_batch", "v3d_png_out_bytes", "v3d_png_ws_bytes"])
+# + the second round of k_png_offsets and its carry (more than 256 frames)
+DRIVER_CASES = [c[:7] for c in CASES] + [(P.GRAY16, 3, 2, 300, 0, 0, 0)]
+
+
+@pytest.mark.parametrize("fmt,W,H,n,pad,skew_img,skew_out", DRIVER_CASES,
+                         ids=[f"{'g16' if c[0] == 0 else 'bgr'}-{c[1]}x{c[2]}x{c[3]}" for c in DRIVER_CASES])
+def test_driver_equals_the_reference(driver, tmp_path, fmt, W, H, n, pad, skew_img, skew_out):
+    frames = [P.content_image(fmt, W, H, 3 * W + f) for f in range(n)]
+    want, want_off, _ = P.batch(frames, fmt)
+    item = 2 if fmt == P.GRAY16 else 1
+    per = frames[0].size * item
+    stride = per + pad * item
+    nout = E.query(driver, "v3d_png_out_bytes", fmt, n, W, H)
+    assert nout == want.size
+    nws = E.query(driver, "v3d_png_ws_bytes", fmt, n, W, H)
+
+    def make(gp):
+        # the last frame's payload ends on the allocation's last byte: the padding belongs to the stride, not to the buffer
+        img = np.full((n - 1) * stride + per, gp, np.uint8)
+        for f in range(n):
+            img[f * stride:f * stride + per] = frames[f].reshape(-1).view(np.uint8)
+        return [E.exact("img", img, skew_img), stride, fmt, n, W, H,
+                E.exact("out", np.full(nout, gp, np.uint8), skew_out, expect=want),
+                E.exact("offsets", np.full(8 * (n + 1), gp, np.uint8), 8, expect=want_off.astype(np.uint64).view(np.uint8)),
+                E.exact("ws", np.full(nws, gp, np.uint8), 16, expect=None), 0]
+    E.run_configs(driver, tmp_path, "v3d_png_deflate_batch", make)

@@ -60,6 +60,21 @@ def test_streams_and_offsets_equal_the_reference(native, fmt, W, H):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("W,H,n", [(3, 2, 300), (64, 300, 2)], ids=["3x2x300", "64x300x2"])
+def test_many_frames_and_many_rows_byte_for_byte(native, W, H, n):
+    """more than 256 frames: the second round of k_png_offsets and its carry; more than 256 rows: the second round of k_png_frame"""
+    import torch
+    frames = [P.content_image(P.GRAY16, W, H, 3 * W + f) for f in range(n)]
+    want, want_off, _ = P.batch(frames, P.GRAY16)
+    out, off = native.png_deflate_batch(_on_device(frames, P.GRAY16, 3, 1))
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert got.size == want.size and np.array_equal(off.cpu().numpy().astype(np.uint64), want_off)
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, f"{bad.size} bytes differ, first at {int(bad[0])}"
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("fmt", [P.GRAY16, P.BGR8], ids=["g16", "bgr"])
 def test_product_size_frame_inflates_to_the_payload(native, fmt):
     """3840 x 2160, one frame: zlib.decompress == the host encoder's payload (no Python reference at this size)"""

@@ -8,7 +8,8 @@ from conftest import mismatch_report
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("W,H", [(64, 8), (322, 45), (1030, 9), (2050, 3), (960, 540), (1920, 1080)])
+# 1024 plain and 1032 unsqueezed: a staging block of the left eye ends exactly on the half row
+@pytest.mark.parametrize("W,H", [(64, 8), (322, 45), (1030, 9), (2050, 3), (960, 540), (1920, 1080), (1024, 9), (1032, 9)])
 @pytest.mark.parametrize("unsqueeze", [True, False])
 def test_sbs_to_gray_bit_exact(native, oracle, W, H, unsqueeze):
     rng = np.random.default_rng(W * 3 + H)
@@ -80,6 +81,26 @@ def test_sbs_from_an_unaligned_base_pointer(native, oracle, off, unsqueeze):
     buf[off:] = native.to_device(sbs).reshape(-1)
     view = buf[off:].view(H, W, 3)
     assert view.data_ptr() % 4 == off and view.is_contiguous()
+    gl, gr = native.sbs_to_gray(view, unsqueeze)
+    wl, wr = oracle.sbs_to_gray(sbs, unsqueeze)
+    assert np.array_equal(gl.cpu().numpy(), wl) and np.array_equal(gr.cpu().numpy(), wr)
+    bl, br = native.split_sbs(view, unsqueeze)
+    ol, orr = oracle.split_sbs(sbs, unsqueeze)
+    assert np.array_equal(bl.cpu().numpy(), ol) and np.array_equal(br.cpu().numpy(), orr)
+
+
+@pytest.mark.parametrize("off", [1, 2, 3])
+@pytest.mark.parametrize("unsqueeze", [True, False])
+def test_sbs_dword_plan_from_an_unaligned_base_pointer(native, oracle, off, unsqueeze):
+    """W = 1076: rows of 3228 bytes, a multiple of 4, so unlike the 538-wide frame above (pitch 1614: the byte plan only) the
+    interior blocks stage aligned dwords from a base that is not aligned, the case the kernel's comment describes"""
+    import torch
+    sbs = np.random.default_rng(1076 + off).integers(0, 256, (9, 1076, 3), dtype=np.uint8)
+    H, W, _ = sbs.shape
+    buf = torch.zeros(off + sbs.size, dtype=torch.uint8, device="cuda")
+    buf[off:] = native.to_device(sbs).reshape(-1)
+    view = buf[off:].view(H, W, 3)
+    assert view.data_ptr() % 4 == off and view.is_contiguous() and (W * 3) % 4 == 0
     gl, gr = native.sbs_to_gray(view, unsqueeze)
     wl, wr = oracle.sbs_to_gray(sbs, unsqueeze)
     assert np.array_equal(gl.cpu().numpy(), wl) and np.array_equal(gr.cpu().numpy(), wr)

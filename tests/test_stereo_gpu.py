@@ -59,6 +59,21 @@ def test_small_sizes_bit_exact(native, W, H):
                        f"{W}x{H} {kind} g=({gl},{gr}) conv={conv} layout={layout}")
 
 
+# both sides of every change of pixels per thread (8 up to 2048, 16 up to 4096, 32 above), and widths that end inside a thread's
+# run; a band of 4 rows plus a band of 1
+@pytest.mark.parametrize("W", [2047, 2048, 2049, 4090, 4096, 4097, 8190])
+def test_route_change_and_ragged_widths_bit_exact(native, W):
+    H = 5
+    F = np.random.default_rng(W).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    layouts = [R.FULL_SBS] + ([R.HALF_SBS] if W % 2 == 0 else [])
+    for i, (gl, gr, conv) in enumerate(_params(W)):
+        kind = ("noise", "planar")[i % 2]
+        D = _depth(kind, H, W, W + H + i)
+        for layout in layouts:
+            _check(_gpu(native, F, D, gl, gr, conv, layout), R.render(F, D, gl, gr, conv, layout),
+                   f"{W}x{H} {kind} g=({gl},{gr}) conv={conv} layout={layout}")
+
+
 def test_nearest_key_beyond_a_wave_or_absent(native):
     """holes and row ends 600 targets wide at 8 targets per thread: the scan's answer comes from another wave or is 'none'"""
     F, D, (gl, gr, conv) = R.far_key_scene()
