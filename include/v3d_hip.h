@@ -46,7 +46,10 @@
  *    v3d_fill_holes_disp16_batch and v3d_render_stereo[_subpixel]_batch load the aligned 16-byte blocks that hold a row's payload,
  *    so they touch up to 15 bytes on either side of a frame (never a block that holds no payload byte of the input, and no value
  *    from outside the payload reaches a result): an input of theirs must be readable up to those block borders, as every device
- *    allocation is (tests/test_stereo_emulated.py, tests/test_fill_emulated.py); workspaces and outputs may
+ *    allocation is (tests/test_stereo_emulated.py, tests/test_fill_emulated.py).  v3d_median3x3_i16, v3d_filter_speckles and
+ *    v3d_mono_blend[_batch] are held to "payload only" byte-exactly on the host as well, with every buffer ending on its last
+ *    payload byte (tests/test_speckle_emulated.py, tests/test_blend_emulated.py), and so is the matcher's L-R check + median on
+ *    its WTA records, whose never-written columns [0, 64) may hold anything (tests/test_sgbm_post_emulated.py); workspaces and outputs may
  *    hold anything on entry; nothing outside the stated extent of an output or a workspace is written, inputs included;
  *  - `stream` is a hipStream_t passed as void*; calls enqueue work and do NOT synchronise;
  *  - return 0 on success, negative on error; v3d_last_error() returns the thread-local message;

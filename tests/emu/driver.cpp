@@ -9,7 +9,8 @@
 //                                     red zone starts right behind it; the SKEW bytes in front hold GLOBAL_POISON.  CHUNK = 1
 //                                     registers [PAY_LO, PAY_HI) of the image as the payload of an input whose reader may load
 //                                     the 16-byte blocks around it (the streaming loads then check that a block holds payload)
-//   arg p NAME OFFSET | arg v INTEGER one argument of the entry, in order: a pointer into a buffer's image, or an integer
+//   arg p NAME OFFSET | arg v INTEGER one argument of the entry, in order: a pointer into a buffer's image, or an integer (for a
+//                                     float or double parameter: the bits of a float32)
 // After the call every block (SKEW bytes and image) is written to FILE.out, and "rc", "misaligned" and "nopayload" are printed.
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,6 +27,7 @@ typedef std::vector<unsigned long long> Args;
 template <class T> static T conv(unsigned long long v)
 {
     if constexpr (std::is_pointer<T>::value) return reinterpret_cast<T>((uintptr_t)v);
+    else if constexpr (std::is_floating_point<T>::value) { const uint32_t b = (uint32_t)v; float f; memcpy(&f, &b, 4); return (T)f; }   // a float32's bits
     else return static_cast<T>((long long)v);
 }
 template <class R, class... A, size_t... I> static long long call_idx(R (*fn)(A...), const Args& a, std::index_sequence<I...>)

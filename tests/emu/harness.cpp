@@ -34,6 +34,11 @@ void emu_check_block(const void* p, size_t bytes)
     for (const Extent& e : g_extents)
         if (b0 < e.a1 && b1 > e.a0 && !(b0 < e.p1 && b1 > e.p0)) ++g_nopayload;
 }
+void emu_fail(const char* fmt, ...)
+{
+    va_list ap; va_start(ap, fmt); fputs("emulator: ", stderr); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr);
+    abort();
+}
 void v3d_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 
 // The switch between two fibers.  On x86-64 it is the System V callee-saved registers and the stack pointer: swapcontext() costs

@@ -19,7 +19,8 @@ EMU = os.path.join(ROOT, "tests", "emu")
 SAN = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
 # workgroups descending, threads descending, LDS poison, global poison
 CONFIGS = [(0, 0, 0xCD, 0xA5), (1, 1, 0x32, 0xFF)]
-SMEM_DECL = re.compile(r"extern __shared__ [^;]*\bsmem\[\];")
+SMEM_DECL = re.compile(r"extern __shared__ [^;]*?\b(\w+)\[\];")      # the one dynamic LDS declaration of a file, whatever its name
+EXT_VECTOR = re.compile(r"typedef uint32_t (\w+) __attribute__\(\(ext_vector_type\((\d)\), aligned\(4\)\)\);")
 REPORT = re.compile(r"AddressSanitizer|runtime error|LeakSanitizer|emulator:")
 _built = {}
 
@@ -30,15 +31,22 @@ def _cxx():
     return cxx
 
 
-HEADERS = ["v3d_wave.h", "v3d_png_books.h", "v3d_depth_math.h", "v3d_temporal_math.h", "v3d_temporal_internal.h"]
-SMEM_TEXT = "unsigned char* const smem = g_lds;"               # the harness allocates it per workgroup
+HEADERS = ["v3d_wave.h", "v3d_png_books.h", "v3d_depth_math.h", "v3d_temporal_math.h", "v3d_temporal_internal.h", "v3d_sgbm_internal.h"]
+SMEM_TEXT = r"unsigned char* const \1 = g_lds;"                # the harness allocates it per workgroup
 
 
 def stage(d, kernels):
-    """copies the kernel sources (as .cpp) and the headers they are compiled with, unchanged, next to the stand-in for
-    v3d_common.h -> the .cpp paths.  An #include "v3d_common.h" then finds the stand-in"""
+    """copies the kernel sources (as .cpp) and the headers they are compiled with next to the stand-in for v3d_common.h -> the
+    .cpp paths.  An #include "v3d_common.h" then finds the stand-in.  The sources change in their dynamic LDS declaration only
+    (kernel_source), the headers in what the loop below says"""
     for h in HEADERS:
-        shutil.copy(os.path.join(CSRC, h), os.path.join(d, h))
+        text = open(os.path.join(CSRC, h)).read()
+        # clang's ext_vector_type does not exist in the host compiler: the typedefs that use it (v3d_sgbm_internal.h's two fetch types
+        # of the cost volume, which no emulated source touches) become structs of the same members.  Nothing else of a header changes
+        text = EXT_VECTOR.sub(lambda m: f"struct alignas(4) {m.group(1)} {{ uint32_t {', '.join('xyzw'[:int(m.group(2))])}; }};", text)
+        assert "ext_vector_type" not in text, f"{h}: an ext_vector_type declaration did not match"
+        with open(os.path.join(d, h), "w") as f:
+            f.write(text)
     shutil.copy(os.path.join(EMU, "v3d_common.h"), os.path.join(d, "v3d_common.h"))
     out = []
     for k in kernels:
@@ -48,7 +56,8 @@ def stage(d, kernels):
 
 
 def kernel_source(path, dst, smem_text):
-    """copies a kernel source as .cpp with its one `extern __shared__ ... smem[]` declaration (if it has one) replaced"""
+    """copies a kernel source as .cpp with its one `extern __shared__ ... NAME[]` declaration (if it has one) replaced; smem_text
+    is a replacement template, \\1 = NAME"""
     text = open(path).read()
     n = text.count("extern __shared__")
     assert n <= 1, f"{path}: {n} dynamic LDS declarations"

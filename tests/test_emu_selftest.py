@@ -1,6 +1,7 @@
 """The emulator's own test (tests/emu/, tests/emu_case.py), without a GPU and without the product's kernels: six toy kernels,
 each with one defect that leaves a device's output bits alone, must be rejected by the sanitized driver or by the comparison under
-two poisons and two orders, and the correct twin of each must pass.  Also: a launch outside a workgroup's limits is an error."""
+two poisons and two orders, and the correct twin of each must pass.  Also: a launch outside a workgroup's limits is an error, and
+each cross-lane shim of the stand-in (DPP row shifts and broadcasts, ballot, readlane, readfirstlane) gives its known answer."""
 import os
 
 import numpy as np
@@ -9,7 +10,8 @@ import pytest
 import emu_case as E
 
 TOYS = ["toy_lds_overrun", "toy_global_overread", "toy_misaligned_load", "toy_lds_unwritten", "toy_missing_barrier", "toy_workgroup_order", "toy_launch"]
-driver = E.driver_fixture("toys", [], TOYS, header="toys.h", extra=[os.path.join(E.EMU, "toys.cpp")])
+LANE_TOYS = ["toy_row_shr", "toy_row_bcast", "toy_wave_scan", "toy_ballot", "toy_readlane", "toy_wave_exit"]
+driver = E.driver_fixture("toys", [], TOYS + LANE_TOYS, header="toys.h", extra=[os.path.join(E.EMU, "toys.cpp")])
 
 IN32 = (np.arange(256, dtype=np.uint32) * 2654435761 + 12345).astype(np.uint32)
 IN8 = (np.arange(4096 + 16) * 37 % 251).astype(np.uint8)
@@ -65,3 +67,79 @@ def test_a_launch_outside_a_workgroups_limits_is_an_error(driver, tmp_path, lds,
     else:
         with pytest.raises(AssertionError, match="launch outside a workgroup's range"):
             E.run_configs(driver, tmp_path, "toy_launch", make)
+
+
+# ---- the cross-lane shims: lane l of wave w is thread 64 w + l; rows are 16 lanes ----
+LANE = np.arange(256) % 64
+WAVE0 = np.arange(256) // 64 * 64
+
+
+def _lane_case(toy, arg, want, threads=256):
+    def make(gp):
+        out = np.full(4 * want.size, gp, np.uint8)
+        return [E.exact("in", _words(IN32), 0), E.exact("out", out, 0, expect=_words(want)), arg, 0]
+    return make
+
+
+@pytest.mark.parametrize("n", [1, 2, 4, 8])
+def test_row_shr_keeps_old_at_row_starts(driver, tmp_path, n):
+    want = np.where(LANE % 16 >= n, np.roll(IN32, n), ~IN32)
+    assert np.all(want[::16] == ~IN32[::16])
+    E.run_configs(driver, tmp_path, "toy_row_shr", _lane_case("toy_row_shr", n, want))
+
+
+@pytest.mark.parametrize("which,rows,lane", [(15, (1, 3), None), (31, (2, 3), 31), (150, (1, 2, 3), None), (310, (2, 3), 31)])
+def test_row_bcast_under_a_row_mask(driver, tmp_path, which, rows, lane):
+    """row_bcast:15 gives lane 15 of a row to the next row, row_bcast:31 lane 31 to rows 2 and 3; rows masked off or without a
+    source keep `old`"""
+    src = WAVE0 + (LANE // 16 * 16 - 1 if lane is None else lane)
+    want = np.where(np.isin(LANE // 16, rows), IN32[src % 256], ~IN32)
+    E.run_configs(driver, tmp_path, "toy_row_bcast", _lane_case("toy_row_bcast", which, want))
+
+
+def test_another_dpp_control_is_an_emulator_error(driver, tmp_path):
+    with pytest.raises(AssertionError, match="DPP control 0x140 is not emulated"):
+        E.run_configs(driver, tmp_path, "toy_row_bcast", _lane_case("toy_row_bcast", 0x140, IN32))
+
+
+def test_the_wave_max_scan_equals_a_plain_loop_and_its_defective_twin_does_not(driver, tmp_path):
+    want = np.empty_like(IN32)
+    for t in range(256):
+        want[t] = IN32[t // 64 * 64:t + 1].max()
+    E.run_configs(driver, tmp_path, "toy_wave_scan", _lane_case("toy_wave_scan", 0, want))
+    with pytest.raises(AssertionError, match="bytes differ"):
+        E.run_configs(driver, tmp_path, "toy_wave_scan", _lane_case("toy_wave_scan", 1, want))
+
+
+@pytest.mark.parametrize("threads", [256, 100, 1])
+def test_ballot_with_a_partial_last_wave(driver, tmp_path, threads):
+    bits = (IN32[:threads] & 1).astype(np.uint64)
+    want = np.zeros(2 * threads, np.uint32)
+    for w in range((threads + 63) // 64):
+        b = bits[64 * w:64 * w + 64]
+        m = int((b << np.arange(b.size, dtype=np.uint64)).sum())
+        want[2 * 64 * w:2 * (64 * w + b.size):2] = m & 0xFFFFFFFF
+        want[2 * 64 * w + 1:2 * (64 * w + b.size):2] = m >> 32
+    assert threads != 100 or (want[2 * 64 + 1] >> 4 == 0 and want[1] != 0)      # lanes 36 .. 63 of the last wave do not vote
+    E.run_configs(driver, tmp_path, "toy_ballot", _lane_case("toy_ballot", threads, want))
+
+
+def test_readlane_63_and_readfirstlane(driver, tmp_path):
+    want = np.stack([IN32[WAVE0 + 63], IN32[WAVE0]], axis=1).reshape(-1)
+    E.run_configs(driver, tmp_path, "toy_readlane", _lane_case("toy_readlane", 63, want))
+    with pytest.raises(AssertionError, match="readlane of lane 64"):
+        E.run_configs(driver, tmp_path, "toy_readlane", _lane_case("toy_readlane", 64, want))
+
+
+@pytest.mark.parametrize("live", [4, 2, 1])
+def test_a_wave_that_returns_before_any_rendezvous(driver, tmp_path, live):
+    up = np.where(LANE > 0, np.roll(IN32, 1), IN32)
+    pop = np.array([int((IN32[w:w + 64] & 1).sum()) for w in WAVE0], np.uint32)
+    shr = np.where(LANE % 16 >= 1, np.roll(IN32, 1), 0)
+    want = (up ^ IN32[WAVE0 + 63] ^ pop ^ shr).astype(np.uint32)
+
+    def make(gp):
+        w = _words(want).copy()
+        w[4 * 64 * live:] = gp                                  # the waves that returned wrote nothing
+        return [E.exact("in", _words(IN32), 0), E.exact("out", np.full(1024, gp, np.uint8), 0, expect=w), live, 0]
+    E.run_configs(driver, tmp_path, "toy_wave_exit", make)

@@ -480,3 +480,26 @@ def test_lrcheck_median_row_march_equals_tiles_and_oracle(native, oracle, W, H):
         m.close()
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert not mismatch_report(outs[0][0].cpu().numpy(), want, f"{W}x{H}")
+
+
+@pytest.mark.parametrize("W,H", [(640, 48), (516, 35), (1920, 33)])
+def test_speckle_merge_shapes(native, oracle, W, H):
+    """the lock-free union-find where many roots merge at once (tests/speckle_shapes.py: combs, a spiral, a serpentine, a
+    staircase, components of exactly the threshold size spread over both merge levels, plateaus at the maxDiff edge, full run
+    lists): the emulated test runs these one fiber at a time, a race shows only here.  Every parameter set runs twice and both
+    outputs must be the oracle's.  No surface hands a given plane to a StereoSGBM handle's speckle stage (the handle takes
+    images), so the batched stage is run on these planes by tests/test_speckle_emulated.py alone"""
+    import torch
+    import speckle_shapes as SS
+    for max_size, max_diff in ((100, 512), (3, 1)):
+        planes = SS.shapes(W, H, max_size, max_diff)
+        assert {"comb-bottom", "comb-top", "spiral", "serpentine", "staircase", "plateaus", "full-lists"} <= set(planes)
+        assert ("exact" in planes) == (H >= 34 and max_size >= SS.EXACT_MIN)
+        for name, img in planes.items():
+            want = oracle.filter_speckles(img, -16, max_size, max_diff)
+            dev = _dev(native, img)
+            first = native.filter_speckles(dev, -16, max_size, max_diff)
+            second = native.filter_speckles(dev, -16, max_size, max_diff)
+            tag = f"{name} {W}x{H} size<={max_size} diff<={max_diff}"
+            assert torch.equal(first, second), tag + ": two runs differ"
+            assert not mismatch_report(first.cpu().numpy(), want, tag), mismatch_report(first.cpu().numpy(), want, tag)
