@@ -24,6 +24,8 @@
  *   v3d_render_stereo_batch  readme.md:37 step 4 (handed to VisionDepth3D there): DIBR from the 4K frame and its 4K depth
  *                          to a side-by-side 3D frame (convert.py, the declared video-3d-convert step)
  *   v3d_render_stereo_subpixel_batch  the same step in 1/16 pixel with interpolated colours (convert.py --subpixel)
+ *   v3d_render_stereo_packed_batch  the same step with the eyes packed top-bottom, row-interleaved or as a red-cyan anaglyph
+ *                          (convert.py --layout), the output formats VisionDepth3D offers there
  *   v3d_temporal_*, v3d_depth_minmax_batch, v3d_depth_to_u16_range_batch  no call site in the reference (it normalises every
  *                          frame on its own, depth.py:397-406): opt-in temporal stabilisation of the depth sequence
  *   v3d_depth_robust_minmax_batch  no call site in the reference either: opt-in percentile white point of that normalisation
@@ -43,7 +45,7 @@
  *  - memory contract (tests/test_abi_guard_gpu.py holds every entry to it): a typed pointer needs only the natural alignment
  *    of its element type and a `void* ws` 16 bytes, unless the entry's comment says otherwise, and an entry that needs more
  *    refuses with V3D_ERR_ARG; rows are `pitch` bytes apart and only the payload of a row is read, with one exception:
- *    v3d_fill_holes_disp16_batch and v3d_render_stereo[_subpixel]_batch load the aligned 16-byte blocks that hold a row's payload,
+ *    v3d_fill_holes_disp16_batch and v3d_render_stereo[_subpixel|_packed]_batch load the aligned 16-byte blocks that hold a row's payload,
  *    so they touch up to 15 bytes on either side of a frame (never a block that holds no payload byte of the input, and no value
  *    from outside the payload reaches a result): an input of theirs must be readable up to those block borders, as every device
  *    allocation is (tests/test_stereo_emulated.py, tests/test_fill_emulated.py).  v3d_median3x3_i16, v3d_filter_speckles and
@@ -339,6 +341,39 @@ int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride /* byt
 int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
                                      size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
                                      int convergence, int layout, uint8_t* out_bgr /* dense [n][H][outW][3] */, void* stream);
+
+/* Output packings (v3d_stereo.hip): the eye images EL, ER ([H][W][3] BGR) of v3d_render_stereo_batch (subpixel = 0) or of
+   v3d_render_stereo_subpixel_batch (subpixel = 1), packed for the display as `packing` says, in the same launch:
+     V3D_PACK_FULL_SBS, V3D_PACK_HALF_SBS   [H][2W][3] / [H][W][3] (W even): the layouts 0 / 1 of those entries, by their kernels;
+     V3D_PACK_FULL_TB           [2H][W][3]: rows 0 .. H-1 = EL, rows H .. 2H-1 = ER;
+     V3D_PACK_HALF_TB           [H][W][3], H even: eye row y' = (E[2y'] + E[2y'+1] + 1) >> 1 per channel, EL in rows 0 .. H/2-1, ER in
+                                rows H/2 .. H-1;
+     V3D_PACK_ROWS              [H][W][3]: row y = EL[y] for even y, ER[y] for odd y (row-interleaved, left eye first);
+     V3D_PACK_ANAGLYPH_COLOUR   [H][W][3]: B = ER.B, G = ER.G, R = EL.R (red-cyan);
+     V3D_PACK_ANAGLYPH_DUBOIS   [H][W][3]: Dubois' least-squares red-cyan matrices in 1/65536, with (Bl, Gl, Rl) = EL[y][x] and
+                                (Br, Gr, Rr) = ER[y][x], floor = the arithmetic >> 16 of the int32 sum, clamp255 to [0, 255]:
+       R' = clamp255(floor((29891 Rl + 32800 Gl + 11559 Bl -  2849 Rr -  5763 Gr -   102 Br + 32768) / 65536))
+       G' = clamp255(floor((-2627 Rl -  2479 Gl -  1033 Bl + 24804 Rr + 48080 Gr -  1209 Br + 32768) / 65536))
+       B' = clamp255(floor(( -997 Rl -  1350 Gl -   358 Bl -  4729 Rr -  7403 Gr + 80373 Br + 32768) / 65536))
+       (every row sums to 65536: a pixel that is the same grey in both eyes maps to itself).
+   Bit-exact contract: tests/stereo_pack_ref.py.  Inputs, strides, gains and convergence as for v3d_render_stereo_batch; out_bgr
+   dense [n][outH][outW][3].  The memory contract is that of the two entries above: natural alignment only; rows and frames at
+   any byte offset (the aligned 16-byte blocks that hold a row's payload are loaded, as there); nothing is written outside
+   out_bgr, and every byte of out_bgr is written; no allocation, no synchronisation, one launch.  V3D_ERR_ARG: everything
+   v3d_render_stereo_batch refuses (null pointer, n < 1, W or H < 1, strides smaller than a frame (n > 1), odd W for
+   V3D_PACK_HALF_SBS, |gain| >= 2^24, convergence outside [0, 65535]), subpixel not 0 / 1, packing outside 0 .. 6, odd H for
+   V3D_PACK_HALF_TB; V3D_ERR_UNSUPPORTED: W > 8192.  A refused call enqueues nothing. */
+#define V3D_PACK_FULL_SBS 0
+#define V3D_PACK_HALF_SBS 1
+#define V3D_PACK_FULL_TB 2
+#define V3D_PACK_HALF_TB 3
+#define V3D_PACK_ROWS 4
+#define V3D_PACK_ANAGLYPH_COLOUR 5
+#define V3D_PACK_ANAGLYPH_DUBOIS 6
+int v3d_render_stereo_packed_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
+                                   size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
+                                   int convergence, int subpixel /* 0 | 1 */, int packing /* V3D_PACK_* */,
+                                   uint8_t* out_bgr /* dense [n][outH][outW][3] */, void* stream);
 
 /* Temporal depth stabilisation (v3d_temporal.hip, its integer arithmetic v3d_temporal_math.h): an opt-in stage between the
    disparity and the u16 normalisation.  A buffer holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +

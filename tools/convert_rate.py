@@ -1,9 +1,10 @@
 """DIBR step (v3d_render_stereo_batch) on one GPU: kernel time per 4K frame from HIP events (8 distinct frames per launch,
 warm-up, 20 timed launches, both layouts), the algorithmic bytes and their share of 8 TB/s, and the convert CLI's end-to-end
 frames/s on a synthetic .npy 4K clip.  Prints one JSON line.  --subpixel measures v3d_render_stereo_subpixel_batch the same way
-after the integer entry (the yardstick, same process and inputs) and adds "kernel_subpixel" and the ratio of the two.
+after the integer entry (the yardstick, same process and inputs) and adds "kernel_subpixel" and the ratio of the two.  --packings
+adds the packings of v3d_render_stereo_packed_batch (top-bottom, row-interleaved, anaglyph) to each of those tables.
 
-    python tools/convert_rate.py [--frames 24] [--kernel-only] [--subpixel]
+    python tools/convert_rate.py [--frames 24] [--kernel-only] [--subpixel] [--packings]
 """
 import argparse
 import json
@@ -37,21 +38,32 @@ def inputs(n, seed=0):
     return frames, depth
 
 
-def kernel_rates(subpixel=False):
+# name, packing code, output bytes per source pixel; codes >= 2 are v3d_render_stereo_packed_batch (--packings)
+SBS = (("full_sbs", N.STEREO_FULL_SBS, 6), ("half_sbs", N.STEREO_HALF_SBS, 3))
+PACKED = (("full_tb", N.STEREO_PACK_FULL_TB, 6), ("half_tb", N.STEREO_PACK_HALF_TB, 3), ("interlaced", N.STEREO_PACK_ROWS, 3),
+          ("anaglyph_colour", N.STEREO_PACK_ANAGLYPH_COLOUR, 3), ("anaglyph_dubois", N.STEREO_PACK_ANAGLYPH_DUBOIS, 3))
+
+
+def kernel_rates(subpixel=False, layouts=SBS):
     frames, depth = inputs(NF)
     f = torch.from_numpy(frames).cuda()
     d = torch.from_numpy(depth.view(np.int16)).cuda()
     gl, gr, conv = N.stereo_gains()
     res = {}
-    for name, layout, out_px in (("full_sbs", N.STEREO_FULL_SBS, 6), ("half_sbs", N.STEREO_HALF_SBS, 3)):
-        out = torch.empty((NF, H, W * (2 if layout == N.STEREO_FULL_SBS else 1), 3), dtype=torch.uint8, device="cuda")
+    for name, layout, out_px in layouts:
+        oW, oH = N.stereo_output_size(layout, W, H)
+        out = torch.empty((NF, oH, oW, 3), dtype=torch.uint8, device="cuda")
+        if layout >= 2:
+            render = lambda: N.render_stereo_packed_batch(f, d, gl, gr, conv, layout, out, subpixel=subpixel)
+        else:
+            render = lambda: N.render_stereo_batch(f, d, gl, gr, conv, layout, out, subpixel=subpixel)
         for _ in range(3):
-            N.render_stereo_batch(f, d, gl, gr, conv, layout, out, subpixel=subpixel)
+            render()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(REPS):
-            N.render_stereo_batch(f, d, gl, gr, conv, layout, out, subpixel=subpixel)
+            render()
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / (REPS * NF)
@@ -89,10 +101,13 @@ def main():
     ap.add_argument("--png-encoder", nargs="+", choices=["zlib", "gpu"], default=["zlib"],
                     help="the CLI run once per listed encoder, alternating in this one process")
     ap.add_argument("--subpixel", action="store_true", help="also measure the sub-pixel entry, after the integer one; the CLI run uses it")
+    ap.add_argument("--packings", action="store_true",
+                    help="also measure the top-bottom, row-interleaved and anaglyph packings, after the two side-by-side layouts")
     a = ap.parse_args()
-    res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "kernel": kernel_rates()}
+    layouts = SBS + PACKED if a.packings else SBS
+    res = {"device": torch.cuda.get_device_name(0), "size": f"{W}x{H}", "kernel": kernel_rates(layouts=layouts)}
     if a.subpixel:
-        res["kernel_subpixel"] = kernel_rates(subpixel=True)
+        res["kernel_subpixel"] = kernel_rates(subpixel=True, layouts=layouts)
         res["subpixel_over_integer"] = {k: round(res["kernel_subpixel"][k]["us_per_frame"] / res["kernel"][k]["us_per_frame"], 3)
                                         for k in res["kernel"]}
     if not a.kernel_only:

@@ -22,6 +22,11 @@
 //      holes carry the COLOUR of the neighbouring hit target, not its key;
 //   ... and the nearest hit targets outside a thread's run are evaluated from their keys and the indices the scans yield.
 // Contract: tests/stereo_sub_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Sub-pixel DIBR".
+//
+// Output packings (v3d_render_stereo_packed_batch, k_render_packed<PPT, SUB, K>): the same march for either renderer with a fifth
+// step, which packs the eyes top-bottom, row-interleaved or as a red-cyan anaglyph before the store; colours that must wait for
+// the other eye or the next row wait in LDS words only their thread touches.
+// Contract: tests/stereo_pack_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Output packings".
 #include "v3d_common.h"
 #include "v3d_wave.h"
 
@@ -116,6 +121,51 @@ struct StGeom {
     static constexpr int ND = st_cdiv(st_chunks(2 * WP, 14), ST_THREADS);   // depth chunks per thread
     static constexpr int NF = st_cdiv(st_chunks(3 * WP, 15), ST_THREADS);   // BGR chunks per thread
 };
+
+// what the march does with the eye colours: the two side-by-side layouts (the mode argument says which), full top-bottom,
+// half top-bottom, row-interleaved, anaglyph (mode: Dubois)
+enum { ST_K_SBS, ST_K_TB, ST_K_HTB, ST_K_ROWS, ST_K_ANA };
+
+// LDS behind the BGR row in which a thread parks colours for itself, words [w][thread]: anaglyph the left eye's PPT colours until
+// the right eye's are there, half top-bottom both eyes' packed even row (PPT * 3 / 4 words each) until the odd row's is there
+template <int PPT>
+__host__ __device__ constexpr int st_park_bytes(int kind)
+{
+    return kind == ST_K_ANA ? 4 * PPT * ST_THREADS : kind == ST_K_HTB ? 2 * (PPT * 3 / 4) * 4 * ST_THREADS : 0;
+}
+
+// LDS of k_render_packed: both key rows, the widest depth and BGR rows at any phase, the parked words
+template <int PPT>
+__host__ __device__ constexpr int st_lds_bytes(int kind)
+{
+    return 8 * PPT * ST_THREADS + st_chunks(2 * PPT * ST_THREADS, 14) * 16 + st_chunks(3 * PPT * ST_THREADS, 15) * 16 + st_park_bytes<PPT>(kind);
+}
+
+// PPT colours (B | G << 8 | R << 16) -> the 3 PPT bytes of the run as words
+template <int PPT>
+__device__ __forceinline__ void st_pack3(const uint32_t (&col)[PPT], uint32_t (&wds)[PPT * 3 / 4])
+{
+#pragma unroll
+    for (int w = 0; w < PPT * 3 / 4; ++w) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v |= ((col[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
+        wds[w] = v;
+    }
+}
+
+// red-cyan anaglyph of one target from its left and right eye colours.  Colour: red from the left eye, green and blue from the
+// right.  Dubois: his least-squares matrices in 1/65536 (every row sums to 65536: equal greys map to themselves), floor, clamp
+__device__ __forceinline__ uint32_t st_anaglyph(uint32_t l, uint32_t r, int dubois)
+{
+    if (!dubois) return (r & 0x00FFFFu) | (l & 0xFF0000u);
+    const int bl = (int)(l & 255u), gl = (int)((l >> 8) & 255u), rl = (int)((l >> 16) & 255u);
+    const int br = (int)(r & 255u), gr = (int)((r >> 8) & 255u), rr = (int)((r >> 16) & 255u);
+    const int R = (29891 * rl + 32800 * gl + 11559 * bl - 2849 * rr - 5763 * gr - 102 * br + 32768) >> 16;
+    const int Gn = (-2627 * rl - 2479 * gl - 1033 * bl + 24804 * rr + 48080 * gr - 1209 * br + 32768) >> 16;
+    const int B = (-997 * rl - 1350 * gl - 358 * bl - 4729 * rr - 7403 * gr + 80373 * br + 32768) >> 16;
+    return (uint32_t)min(max(B, 0), 255) | ((uint32_t)min(max(Gn, 0), 255) << 8) | ((uint32_t)min(max(R, 0), 255) << 16);
+}
 
 }  // namespace
 
@@ -327,30 +377,274 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
     }
 }
 
-template <int PPT, bool SUB>
+// The march of k_render_stereo for the packings of v3d_render_stereo_packed_batch (k_render_packed): steps 1 to 3 and the fill and
+// gather of step 4 are the same statements; K says what becomes of the eye colours, and the row-interleaved frame skips the eye a
+// row does not show.  It is a second copy on purpose: k_render_stereo called through a shared inlined body compiles to other
+// machine code (measured: half SBS 0.3 % slower at 4K), and the six side-by-side instantiations are pinned (tools/kernel_digest.py;
+// DESIGN.md §4, "Output packings").  A change to one march belongs in the other.  mode: ST_K_ANA: Dubois.
+// Its LDS is static, sized for the widest row of PPT pixels per thread plus what K parks (st_park_bytes): 8 WP of it do not
+// depend on W anyway, and the file keeps its one dynamic declaration.
+template <int PPT, bool SUB, int K>
+__global__ __launch_bounds__(ST_THREADS) void k_render_packed(const uint8_t* __restrict__ frame, size_t frame_stride,
+                                                              const uint16_t* __restrict__ depth, size_t depth_stride, int W, int H,
+                                                              int gl, int gr, int conv, int mode, uint8_t* __restrict__ out,
+                                                              int sd_bytes)
+{
+    using G = StGeom<PPT>;
+    constexpr int WP = G::WP, ND = G::ND, NF = G::NF;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[st_lds_bytes<PPT>(K)];
+    uint32_t* sZ = reinterpret_cast<uint32_t*>(smem);          // [2][WP]
+    unsigned char* sD = smem + 8 * WP;                         // depth row chunks (sd_bytes)
+    unsigned char* sF = sD + sd_bytes;                         // BGR row chunks
+    __shared__ uint32_t sTot[2][2][ST_THREADS / 64];           // [eye][prefix | suffix][wave]
+    __shared__ uint32_t sM[SUB ? V3D_STEREO_TEAR16 + 1 : 1];   // sub-pixel: ceil(2^20 / 2L), read after the row's first barrier
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (SUB) {
+        if (tid >= 1 && tid <= V3D_STEREO_TEAR16) sM[tid] = ((1u << 20) + 2u * tid - 1u) / (2u * tid);
+    }
+    const int f = blockIdx.y;
+    const int y0 = blockIdx.x * ST_BAND, y1 = min(y0 + ST_BAND, H);
+    const uint8_t* fr = frame + (size_t)f * frame_stride;
+    const uint16_t* dp = depth + (size_t)f * depth_stride;
+    // this thread's parked words: st_park_bytes; nobody else reads or writes them, so they need no barrier
+    uint32_t* sP = reinterpret_cast<uint32_t*>(sF + st_chunks(3 * W, 15) * 16) + tid;
+    // row-interleaved keeps one eye per row (the left in even rows): the other is neither scattered, scanned nor filled
+    auto eye_on = [&](int e, int y) { return K != ST_K_ROWS || e == (y & 1); };
+
+    // a row's bytes as aligned 16-byte chunks: every load is unconditional (lanes past the last chunk re-read it), the
+    // chunks never leave the 16-byte blocks the row touches
+    uint4 rd[ND], rf[NF];
+    auto load_row = [&](int y) {
+        const uintptr_t ds = reinterpret_cast<uintptr_t>(dp + (size_t)y * W), fs = reinterpret_cast<uintptr_t>(fr + (size_t)y * W * 3);
+        const uint4* da = reinterpret_cast<const uint4*>(ds & ~(uintptr_t)15);
+        const uint4* fa = reinterpret_cast<const uint4*>(fs & ~(uintptr_t)15);
+        const int nd = (int)((ds + 2 * (uintptr_t)W - (ds & ~(uintptr_t)15) + 15) >> 4);
+        const int nf = (int)((fs + 3 * (uintptr_t)W - (fs & ~(uintptr_t)15) + 15) >> 4);
+#pragma unroll
+        for (int k = 0; k < ND; ++k) rd[k] = ld_stream(da + min(k * ST_THREADS + tid, nd - 1));
+#pragma unroll
+        for (int k = 0; k < NF; ++k) rf[k] = ld_stream(fa + min(k * ST_THREADS + tid, nf - 1));
+    };
+
+    load_row(y0);
+    for (int y = y0; y < y1; ++y) {
+        const uintptr_t ds = reinterpret_cast<uintptr_t>(dp + (size_t)y * W), fs = reinterpret_cast<uintptr_t>(fr + (size_t)y * W * 3);
+        const int doff = (int)(ds & 15), foff = (int)(fs & 15);
+        const int nd = (doff + 2 * W + 15) >> 4, nf = (foff + 3 * W + 15) >> 4;
+        __syncthreads();                                       // the previous row's LDS reads are done
+#pragma unroll
+        for (int k = 0; k < ND; ++k) {
+            const int c = k * ST_THREADS + tid;
+            if (c < nd) reinterpret_cast<uint4*>(sD)[c] = rd[k];
+        }
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const int c = k * ST_THREADS + tid;
+            if (c < nf) reinterpret_cast<uint4*>(sF)[c] = rf[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 2 * WP / 4 / ST_THREADS; ++k) reinterpret_cast<uint4*>(sZ)[k * ST_THREADS + tid] = make_uint4(0, 0, 0, 0);
+        if (y + 1 < y1) load_row(y + 1);                       // in flight while this row is rendered
+        __syncthreads();
+
+        // 2. scatter both eyes' keys
+        const uint16_t* drow = reinterpret_cast<const uint16_t*>(sD + doff);
+#pragma unroll 4
+        for (int j = 0; j < PPT; ++j) {
+            const int x = j * ST_THREADS + tid;
+            if (x < W) {
+                const int d = drow[x];
+                const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(x + 1);
+                if constexpr (SUB) {
+                    const int d1 = drow[min(x + 1, W - 1)];         // the last column: L' = 16, the point span's length
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        if (!eye_on(e, y)) continue;
+                        const int g = e ? gr : gl, s0 = st_shift16(g, d, conv), Lp = 16 + st_shift16(g, d1, conv) - s0;
+                        const int p = 16 * x + s0, end = p + ((unsigned)(Lp - 1) < (unsigned)V3D_STEREO_TEAR16 ? Lp : 16);
+                        const int t0 = (p + 15) >> 4;              // arithmetic shift = floor; L <= 32: at most two targets
+                        if (16 * t0 < end && (unsigned)t0 < (unsigned)W) atomicMax(sZ + e * WP + t0, key);
+                        if (16 * t0 + 16 < end && (unsigned)(t0 + 1) < (unsigned)W) atomicMax(sZ + e * WP + t0 + 1, key);
+                    }
+                } else {
+                    const int tl = x + st_shift(gl, d, conv), tr = x + st_shift(gr, d, conv);
+                    if (eye_on(0, y) && (unsigned)tl < (unsigned)W) atomicMax(sZ + tl, key);
+                    if (eye_on(1, y) && (unsigned)tr < (unsigned)W) atomicMax(sZ + WP + tr, key);
+                }
+            }
+        }
+        __syncthreads();
+
+        // 3. nearest keys outside my run: (last key index + 1) from the left, (WP - first key index) from the right
+        const int x0 = tid * PPT;
+        uint32_t pre[2], suf[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!eye_on(e, y)) continue;
+            const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
+            uint32_t lastp = 0, firstp = 0;
+#pragma unroll
+            for (int q = PPT / 4 - 1; q >= 0; --q) {
+                const uint4 v = zr[q];
+                const uint32_t k4[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+                for (int i = 3; i >= 0; --i) {
+                    if (k4[i]) {
+                        if (!lastp) lastp = (uint32_t)(x0 + 4 * q + i + 1);
+                        firstp = (uint32_t)(WP - (x0 + 4 * q + i));
+                    }
+                }
+            }
+            const near2 sc = near2_incl(lastp, firstp, lane);
+            if (lane == 63) sTot[e][0][wave] = sc.pre;
+            if (lane == 0) sTot[e][1][wave] = sc.suf;
+            const near2 ex = near2_excl(sc, lane);
+            pre[e] = ex.pre; suf[e] = ex.suf;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!eye_on(e, y)) continue;
+#pragma unroll
+            for (int w = 0; w < ST_THREADS / 64; ++w) {        // v3d_wave.h's near2_fold, kept here: its call costs half SBS 0.5 %
+                if (w < wave) pre[e] = max(pre[e], sTot[e][0][w]);
+                if (w > wave) suf[e] = max(suf[e], sTot[e][1][w]);
+            }
+        }
+
+        // 4. fill, gather, store
+        const int nvalid = min(PPT, W - x0);                   // <= 0: this thread's run lies beyond the row
+        const unsigned char* frow = sF + foff;
+        for (int e = 0; e < 2; ++e) {
+            if (!eye_on(e, y)) continue;
+            uint32_t kk[PPT], col[PPT];
+            const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
+#pragma unroll
+            for (int q = 0; q < PPT / 4; ++q) {
+                const uint4 v = zr[q];
+                kk[4 * q] = v.x; kk[4 * q + 1] = v.y; kk[4 * q + 2] = v.z; kk[4 * q + 3] = v.w;
+            }
+            uint32_t nb = suf[e] ? sZ[e * WP + WP - suf[e]] : 0u;
+            uint32_t na = pre[e] ? sZ[e * WP + pre[e] - 1] : 0u;
+            if constexpr (SUB) {
+                // hit targets get their colour; holes then carry the (key, colour) of the nearest hit target on either side,
+                // the key only for the depth comparison
+                const int g = e ? gr : gl;
+                uint32_t hit = 0, nbc = 0, nac = 0;
+#pragma unroll
+                for (int i = 0; i < PPT; ++i) {
+                    col[i] = 0;
+                    if (kk[i]) { hit |= 1u << i; col[i] = st_sub_colour(kk[i], x0 + i, g, conv, W, drow, frow, sM); }
+                }
+                if (nb) nbc = st_sub_colour(nb, WP - (int)suf[e], g, conv, W, drow, frow, sM);
+                if (na) nac = st_sub_colour(na, (int)pre[e] - 1, g, conv, W, drow, frow, sM);
+#pragma unroll
+                for (int i = PPT - 1; i >= 0; --i) {
+                    if ((hit >> i) & 1u) { nb = kk[i]; nbc = col[i]; }
+                    else { kk[i] = nb; col[i] = nbc; }
+                }
+#pragma unroll
+                for (int i = 0; i < PPT; ++i) {
+                    if ((hit >> i) & 1u) { na = kk[i]; nac = col[i]; }
+                    else if (na && (!kk[i] || (na >> 16) <= (kk[i] >> 16))) col[i] = nac;      // st_fill's choice
+                }
+            } else {
+                uint32_t rb[PPT];
+#pragma unroll
+                for (int i = PPT - 1; i >= 0; --i) { rb[i] = nb; if (kk[i]) nb = kk[i]; }
+#pragma unroll
+                for (int i = 0; i < PPT; ++i) {
+                    uint32_t k = kk[i];
+                    if (k) na = k;
+                    else k = st_fill(na, rb[i]);
+                    const int s = k ? (int)(k & 0xFFFFu) - 1 : 0;
+                    const unsigned char* px = frow + 3 * s;
+                    col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
+                }
+            }
+            {                                                  // 5. pack and store
+                constexpr int NW = PPT * 3 / 4;
+                if constexpr (K == ST_K_ANA) {               // both eyes' colours of my targets: the left eye's wait in LDS
+                    if (e == 0) {
+#pragma unroll
+                        for (int i = 0; i < PPT; ++i) sP[i * ST_THREADS] = col[i];
+                        continue;
+                    }
+#pragma unroll
+                    for (int i = 0; i < PPT; ++i) col[i] = st_anaglyph(sP[i * ST_THREADS], col[i], mode);
+                }
+                uint32_t wds[NW];
+                st_pack3<PPT>(col, wds);
+                if constexpr (K == ST_K_HTB) {                 // rows 2y' and 2y'+1 lie in one band: the even row's bytes wait in LDS
+                    uint32_t* pk = sP + e * NW * ST_THREADS;
+                    if (!(y & 1)) {
+#pragma unroll
+                        for (int w = 0; w < NW; ++w) pk[w * ST_THREADS] = wds[w];
+                        continue;
+                    }
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {             // per byte (a + b + 1) >> 1, as half SBS does
+                        const uint32_t a = pk[w * ST_THREADS], b = wds[w];
+                        wds[w] = (a | b) - (((a ^ b) & 0xFEFEFEFEu) >> 1);
+                    }
+                }
+                // the output row: full top-bottom stacks the eyes (2H rows), half top-bottom their halved rows, the others have row y
+                const size_t rows = K == ST_K_TB ? 2 * (size_t)H : (size_t)H;
+                const int row = K == ST_K_TB ? e * H + y : K == ST_K_HTB ? e * (H / 2) + (y >> 1) : y;
+                if (nvalid > 0) st_store_run(out + ((size_t)f * rows + row) * (size_t)W * 3 + x0 * 3, wds, nvalid * 3);
+            }
+        }
+    }
+}
+
+template <int PPT, bool SUB, int K>
 static int launch_stereo(const uint8_t* frame, size_t frame_stride, const uint16_t* depth, size_t depth_stride, int n, int W,
-                         int H, int gl, int gr, int conv, int half, uint8_t* out, hipStream_t stream)
+                         int H, int gl, int gr, int conv, int mode, uint8_t* out, hipStream_t stream)
 {
     using G = StGeom<PPT>;
     const int sd = st_chunks(2 * W, 14) * 16, sf = st_chunks(3 * W, 15) * 16;
-    const int smem = 8 * G::WP + sd + sf;
-    auto* kernel = k_render_stereo<PPT, SUB>;
-    static bool attr_set = false;                              // per instantiation; the attribute is a property of the function
-    if (!attr_set) {
-        V3D_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          8 * G::WP + st_chunks(2 * G::WP, 14) * 16 + st_chunks(3 * G::WP, 15) * 16));
-        attr_set = true;
+    if constexpr (K == ST_K_SBS) {
+        const int smem = 8 * G::WP + sd + sf;
+        auto* kernel = k_render_stereo<PPT, SUB>;
+        static bool attr_set = false;                          // per instantiation; the attribute is a property of the function
+        if (!attr_set) {
+            V3D_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              8 * G::WP + st_chunks(2 * G::WP, 14) * 16 + st_chunks(3 * G::WP, 15) * 16));
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride,
+                           depth, depth_stride, W, H, gl, gr, conv, mode, out, sd);
+    } else {                                                   // static LDS
+        hipLaunchKernelGGL((k_render_packed<PPT, SUB, K>), dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), 0, stream, frame,
+                           frame_stride, depth, depth_stride, W, H, gl, gr, conv, mode, out, sd);
     }
-    hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride,
-                       depth, depth_stride, W, H, gl, gr, conv, half, out, sd);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }
 
+template <int PPT, bool SUB>
+static int launch_packing(int packing, const uint8_t* frame, size_t frame_stride, const uint16_t* depth, size_t depth_stride, int n,
+                          int W, int H, int gl, int gr, int conv, uint8_t* out, hipStream_t s)
+{
+#define ST_LAUNCH(K, mode) launch_stereo<PPT, SUB, K>(frame, frame_stride, depth, depth_stride, n, W, H, gl, gr, conv, mode, out, s)
+    switch (packing) {
+    case V3D_PACK_FULL_SBS: return ST_LAUNCH(ST_K_SBS, 0);
+    case V3D_PACK_HALF_SBS: return ST_LAUNCH(ST_K_SBS, 1);
+    case V3D_PACK_FULL_TB: return ST_LAUNCH(ST_K_TB, 0);
+    case V3D_PACK_HALF_TB: return ST_LAUNCH(ST_K_HTB, 0);
+    case V3D_PACK_ROWS: return ST_LAUNCH(ST_K_ROWS, 0);
+    case V3D_PACK_ANAGLYPH_COLOUR: return ST_LAUNCH(ST_K_ANA, 0);
+    default: return ST_LAUNCH(ST_K_ANA, 1);                    // V3D_PACK_ANAGLYPH_DUBOIS
+    }
+#undef ST_LAUNCH
+}
+
+// every refusal, then the launch.  max_packing: the entry's last packing code (the layouts of the two older entries are codes 0, 1)
 template <bool SUB>
 static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
-                         int n, int W, int H, int gain_left, int gain_right, int convergence, int layout, uint8_t* out_bgr,
-                         void* stream)
+                         int n, int W, int H, int gain_left, int gain_right, int convergence, int packing, int max_packing,
+                         uint8_t* out_bgr, void* stream)
 {
     if (!frame_bgr || !depth || !out_bgr) { v3d_set_error("%s: null pointer", who); return V3D_ERR_ARG; }
     if (n < 1 || n > 65535 || W < 1 || H < 1) { v3d_set_error("%s: bad geometry n=%d W=%d H=%d", who, n, W, H); return V3D_ERR_ARG; }
@@ -358,8 +652,9 @@ static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame
         v3d_set_error("%s: frame stride %zu B / depth stride %zu elements smaller than a frame", who, frame_stride, depth_stride);
         return V3D_ERR_ARG;
     }
-    if (layout != V3D_STEREO_FULL_SBS && layout != V3D_STEREO_HALF_SBS) { v3d_set_error("%s: layout %d", who, layout); return V3D_ERR_ARG; }
-    if (layout == V3D_STEREO_HALF_SBS && (W & 1)) { v3d_set_error("%s: half SBS needs an even width (W=%d)", who, W); return V3D_ERR_ARG; }
+    if (packing < 0 || packing > max_packing) { v3d_set_error("%s: layout %d", who, packing); return V3D_ERR_ARG; }
+    if (packing == V3D_PACK_HALF_SBS && (W & 1)) { v3d_set_error("%s: half SBS needs an even width (W=%d)", who, W); return V3D_ERR_ARG; }
+    if (packing == V3D_PACK_HALF_TB && (H & 1)) { v3d_set_error("%s: half top-bottom needs an even height (H=%d)", who, H); return V3D_ERR_ARG; }
     const int gmax = 1 << 24;
     if (gain_left <= -gmax || gain_left >= gmax || gain_right <= -gmax || gain_right >= gmax) {
         v3d_set_error("%s: |gain| must be < 2^24 (%d, %d)", who, gain_left, gain_right);
@@ -367,11 +662,10 @@ static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame
     }
     if (convergence < 0 || convergence > 65535) { v3d_set_error("%s: convergence %d outside [0, 65535]", who, convergence); return V3D_ERR_ARG; }
     if (W > ST_MAX_W) { v3d_set_error("%s: W=%d > %d", who, W, ST_MAX_W); return V3D_ERR_UNSUPPORTED; }
-    const int half = layout == V3D_STEREO_HALF_SBS;
     hipStream_t s = (hipStream_t)stream;
-    if (W <= 8 * ST_THREADS) return launch_stereo<8, SUB>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
-    if (W <= 16 * ST_THREADS) return launch_stereo<16, SUB>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
-    return launch_stereo<32, SUB>(frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, half, out_bgr, s);
+    if (W <= 8 * ST_THREADS) return launch_packing<8, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s);
+    if (W <= 16 * ST_THREADS) return launch_packing<16, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s);
+    return launch_packing<32, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s);
 }
 
 extern "C" int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
@@ -379,7 +673,7 @@ extern "C" int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_st
                                        uint8_t* out_bgr, void* stream)
 {
     return render_stereo<false>("v3d_render_stereo_batch", frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right,
-                                convergence, layout, out_bgr, stream);
+                                convergence, layout, V3D_STEREO_HALF_SBS, out_bgr, stream);
 }
 
 extern "C" int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth,
@@ -387,5 +681,16 @@ extern "C" int v3d_render_stereo_subpixel_batch(const uint8_t* frame_bgr, size_t
                                                 int convergence, int layout, uint8_t* out_bgr, void* stream)
 {
     return render_stereo<true>("v3d_render_stereo_subpixel_batch", frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left,
-                               gain_right, convergence, layout, out_bgr, stream);
+                               gain_right, convergence, layout, V3D_STEREO_HALF_SBS, out_bgr, stream);
+}
+
+extern "C" int v3d_render_stereo_packed_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
+                                              int n, int W, int H, int gain_left, int gain_right, int convergence, int subpixel,
+                                              int packing, uint8_t* out_bgr, void* stream)
+{
+    const char* who = "v3d_render_stereo_packed_batch";
+    if (subpixel != 0 && subpixel != 1) { v3d_set_error("%s: subpixel %d is neither 0 nor 1", who, subpixel); return V3D_ERR_ARG; }
+    return (subpixel ? render_stereo<true> : render_stereo<false>)(who, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left,
+                                                                   gain_right, convergence, packing, V3D_PACK_ANAGLYPH_DUBOIS, out_bgr,
+                                                                   stream);
 }

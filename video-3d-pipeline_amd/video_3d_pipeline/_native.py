@@ -27,7 +27,7 @@ EXPORTS = (
     "v3d_sgbm_poll_errors", "v3d_sgbm_stream_wait_lockstep", "v3d_sgbm_set_option", "v3d_sgbm_get_option", "v3d_set_option", "v3d_get_option", "v3d_round_to_u16",
     "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
     "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
-    "v3d_render_stereo_batch", "v3d_render_stereo_subpixel_batch",
+    "v3d_render_stereo_batch", "v3d_render_stereo_subpixel_batch", "v3d_render_stereo_packed_batch",
     "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
     "v3d_depth_to_u16_range_batch", "v3d_temporal_motion", "v3d_temporal_filter_mc_batch",
     "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
@@ -40,6 +40,9 @@ EXPORTS = (
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
 STEREO_FULL_SBS, STEREO_HALF_SBS = 0, 1      # V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS
 STEREO_MAX_WIDTH = 8192
+# V3D_PACK_*: the packings of v3d_render_stereo_packed_batch (0 and 1 are the two layouts above)
+(STEREO_PACK_FULL_SBS, STEREO_PACK_HALF_SBS, STEREO_PACK_FULL_TB, STEREO_PACK_HALF_TB, STEREO_PACK_ROWS,
+ STEREO_PACK_ANAGLYPH_COLOUR, STEREO_PACK_ANAGLYPH_DUBOIS) = range(7)
 
 
 class NativeError(RuntimeError):
@@ -135,6 +138,7 @@ def lib():
         L.v3d_align_audio.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.v3d_render_stereo_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]
         L.v3d_render_stereo_subpixel_batch.argtypes = L.v3d_render_stereo_batch.argtypes
+        L.v3d_render_stereo_packed_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
         L.v3d_temporal_cuts.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp]
         L.v3d_depth_minmax_batch.argtypes = [vp, ci, sz, sz, vp, vp]
         L.v3d_temporal_range.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
@@ -624,6 +628,46 @@ def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, l
         _check(getattr(lib(), entry)(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
                                      H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout),
                                      _dev(out, torch.uint8, "out"), _stream()), entry)
+    return out
+
+
+def stereo_output_size(packing, W, H):
+    """(outW, outH) of a W x H frame rendered with packing code `packing` (STEREO_PACK_*): full SBS is twice as wide, full
+    top-bottom twice as high, every other packing W x H.  ValueError for an unknown code, an odd W for half SBS, an odd H for
+    half top-bottom."""
+    if isinstance(packing, bool) or not isinstance(packing, (int, np.integer)) or not 0 <= packing <= STEREO_PACK_ANAGLYPH_DUBOIS:
+        raise ValueError(f"packing must be one of 0 .. {STEREO_PACK_ANAGLYPH_DUBOIS} (STEREO_PACK_*), got {packing!r}")
+    if packing == STEREO_PACK_HALF_SBS and W % 2:
+        raise ValueError(f"half SBS needs an even width, got {W}")
+    if packing == STEREO_PACK_HALF_TB and H % 2:
+        raise ValueError(f"half top-bottom needs an even height, got {H}")
+    return (2 * W if packing == STEREO_PACK_FULL_SBS else W), (2 * H if packing == STEREO_PACK_FULL_TB else H)
+
+
+def render_stereo_packed_batch(frames, depth_u16, gain_left, gain_right, convergence, packing, out=None, subpixel=False):
+    """DIBR with the eyes packed for the display (v3d_render_stereo_packed_batch): the inputs of render_stereo_batch ->
+    u8 [n,outH,outW,3] (stereo_output_size): side by side, top-bottom, row-interleaved or a red-cyan anaglyph, in one launch.
+    Bit-exact contract: tests/stereo_pack_ref.py.  subpixel: the eyes of the sub-pixel renderer."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
+        raise NativeError(f"frames: expected a uint8 [n,H,W,3] device tensor, got {frames.dtype} {tuple(frames.shape)}")
+    n, H, W, _ = frames.shape
+    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W:
+        raise NativeError("frames: rows must be dense HxWx3 images (only the frame stride may differ)")
+    if tuple(depth_u16.shape) != (n, H, W):
+        raise NativeError(f"depth {tuple(depth_u16.shape)} does not match frames {tuple(frames.shape)}")
+    if not isinstance(subpixel, (bool, np.bool_)):
+        raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
+    oW, oH = stereo_output_size(packing, W, H)
+    shape = (n, oH, oW, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    if tuple(out.shape) != shape:
+        raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    with torch.cuda.device(frames.device):
+        _check(lib().v3d_render_stereo_packed_batch(C.c_void_p(frames.data_ptr()), frames.stride(0),
+                                                    _dev(depth_u16, torch.int16, "depth_u16"), H * W, n, W, H, int(gain_left),
+                                                    int(gain_right), int(convergence), int(bool(subpixel)), int(packing),
+                                                    _dev(out, torch.uint8, "out"), _stream()), "v3d_render_stereo_packed_batch")
     return out
 
 

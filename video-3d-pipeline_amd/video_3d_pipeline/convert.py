@@ -6,7 +6,9 @@ v3d_render_stereo_batch: every source pixel moves horizontally by g/256 * (D - c
 source wins, disocclusions take the farther neighbour (background extension), and the two eyes are packed as full or half
 side-by-side.  The bit-exact contract is tests/stereo_ref.py.  --subpixel renders with v3d_render_stereo_subpixel_batch instead:
 positions in 1/16 pixel and colours interpolated along the spans between neighbouring sources, so that a smooth depth surface
-no longer comes out as a staircase of duplicated and dropped pixels (contract: tests/stereo_sub_ref.py).  The parameters:
+no longer comes out as a staircase of duplicated and dropped pixels (contract: tests/stereo_sub_ref.py).  --layout packs the two
+eyes for the display: side by side, top-bottom, row-interleaved or as a red-cyan anaglyph; every layout but the two side-by-side
+ones is v3d_render_stereo_packed_batch, which packs in the launch that renders (contract: tests/stereo_pack_ref.py).  The parameters:
 
     max_shift    parallax in pixels between depth 65535 (nearest) and depth 0 (default 48 = 1.25 % of a 3840 frame)
     convergence  the depth at the screen plane, in [0, 1] (default 0.5): nearer moves right in the left eye, left in the right
@@ -27,7 +29,9 @@ import numpy as np
 
 from .utils import PngWriterPool, encode_png8, get_video_info, iter_frames, prefetch_map, read_png16
 
-LAYOUTS = {"full-sbs": 0, "half-sbs": 1}          # V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS
+# V3D_PACK_*: codes 0 / 1 are V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS of v3d_render_stereo[_subpixel]_batch, codes >= 2 go to
+# v3d_render_stereo_packed_batch
+LAYOUTS = {"full-sbs": 0, "half-sbs": 1, "full-tb": 2, "half-tb": 3, "interlaced": 4, "anaglyph-colour": 5, "anaglyph-dubois": 6}
 DEFAULT_MAX_SHIFT, DEFAULT_CONVERGENCE, DEFAULT_EYE_SPLIT = 48.0, 0.5, 0.5
 # frames per launch: 4 x (25 MB BGR + 17 MB depth) of pinned input staging and 4 x 50 MB of pinned output (full SBS at 4K)
 CONVERT_BATCH = 4
@@ -39,7 +43,12 @@ def add_stereo_arguments(parser):
     """--layout / --max-shift / --convergence / --eye-split / --subpixel: shared by the convert CLI and the pipeline's
     --stereo-output"""
     parser.add_argument('--layout', choices=list(LAYOUTS), default='full-sbs',
-                        help='full-sbs: two full-width eyes side by side (2W x H); half-sbs: each eye squeezed to W/2 (W x H)')
+                        help='full-sbs: two full-width eyes side by side (2W x H); half-sbs: each eye squeezed to W/2 (W x H); '
+                             'full-tb: the left eye above the right (W x 2H); half-tb: each eye squeezed to H/2, left on top '
+                             '(W x H, most 3D TVs and VR players); interlaced: left eye in even rows, right eye in odd rows '
+                             '(W x H, passive line-polarised displays); anaglyph-colour: red from the left eye, green and blue '
+                             'from the right (W x H, red-cyan glasses); anaglyph-dubois: red-cyan by the Dubois least-squares '
+                             'matrices (W x H, less ghosting and retinal rivalry)')
     parser.add_argument('--max-shift', type=float, default=DEFAULT_MAX_SHIFT,
                         help=f'parallax in pixels between the nearest and the farthest depth (default {DEFAULT_MAX_SHIFT:g})')
     parser.add_argument('--convergence', type=float, default=DEFAULT_CONVERGENCE,
@@ -75,6 +84,20 @@ def stereo_settings(max_shift=DEFAULT_MAX_SHIFT, convergence=DEFAULT_CONVERGENCE
     if not isinstance(subpixel, (bool, np.bool_)):
         raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
     return LAYOUTS[layout], stereo_gains(max_shift, convergence, eye_split)
+
+
+def output_size(layout, W, H):
+    """(outW, outH) of the packed frame of layout code `layout` (_native.stereo_output_size): ValueError for half-sbs on an odd
+    width and half-tb on an odd height"""
+    from ._native import stereo_output_size
+    return stereo_output_size(layout, W, H)
+
+
+def render_stereo(native, frames, depths, gain_left, gain_right, conv, layout, out, subpixel=False):
+    """the native call of a layout code: the two side-by-side layouts go where they always went, the others to the packed entry"""
+    if layout >= 2:
+        return native.render_stereo_packed_batch(frames, depths, gain_left, gain_right, conv, layout, out, subpixel=subpixel)
+    return native.render_stereo_batch(frames, depths, gain_left, gain_right, conv, layout, out, subpixel=subpixel)
 
 
 def sibling_frames_dir(output_path) -> Path:
@@ -168,7 +191,7 @@ class HipRenderBackend:
         n = len(frames)
         H, W = depths[0].shape
         cap = max(n, capacity or n)
-        oW = 2 * W if layout == LAYOUTS["full-sbs"] else W
+        oW, oH = nat.stereo_output_size(layout, W, H)
         fh = self._staging("frames_host", (cap, H, W, 3), torch.uint8, True)
         dh = self._staging("depth_host", (cap, H, W), torch.int16, True)
         fv, dv = fh.numpy(), dh.numpy()
@@ -177,14 +200,14 @@ class HipRenderBackend:
             dv[i] = np.asarray(d, np.uint16).view(np.int16)
         fd = self._staging("frames_dev", (cap, H, W, 3), torch.uint8, False)
         dd = self._staging("depth_dev", (cap, H, W), torch.int16, False)
-        od = self._staging("out_dev", (cap, H, oW, 3), torch.uint8, False)
+        od = self._staging("out_dev", (cap, oH, oW, 3), torch.uint8, False)
         with torch.cuda.device(self.device):
             fd[:n].copy_(fh[:n], non_blocking=True)
             dd[:n].copy_(dh[:n], non_blocking=True)
-            nat.render_stereo_batch(fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n], subpixel=subpixel)
+            render_stereo(nat, fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n], subpixel)
             if png:
                 return od[:n]
-            host = torch.empty((n, H, oW, 3), dtype=torch.uint8, pin_memory=True)
+            host = torch.empty((n, oH, oW, 3), dtype=torch.uint8, pin_memory=True)
             host.copy_(od[:n], non_blocking=True)
             torch.cuda.current_stream().synchronize()
         return host.numpy()
@@ -252,6 +275,9 @@ class DepthTo3DConverter:
             return str(output_path)
         if self.layout_code == LAYOUTS["half-sbs"] and W % 2:
             raise ValueError(f"half SBS needs an even frame width, the 4K clip is {W} wide")
+        if self.layout_code == LAYOUTS["half-tb"] and H % 2:
+            raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {H} high")
+        oW, oH = output_size(self.layout_code, W, H)
         n = len(depth_files) if max_frames is None else min(len(depth_files), max(int(max_frames), 0))
 
         rank, world = sharding.rank_world()
@@ -272,7 +298,7 @@ class DepthTo3DConverter:
             if self.png_encoder == "gpu":                        # deflated on the device: only the streams cross PCIe
                 out = self.backend.render_batch_png(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
                                                     **subpixel_kwargs(self.subpixel))
-                encode = rgb8_file(2 * W if self.layout_code == LAYOUTS["full-sbs"] else W, H)
+                encode = rgb8_file(oW, oH)
             else:
                 out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
                                                 **subpixel_kwargs(self.subpixel))
@@ -310,8 +336,7 @@ class DepthTo3DConverter:
         sharding.barrier()
         if rank == 0:
             write_clip_info(frames_dir, fps)
-            finish_stereo_output(frames_dir, output_path, total, 2 * W if self.layout_code == 0 else W, H, fps, self.params,
-                                 self.gains)
+            finish_stereo_output(frames_dir, output_path, total, oW, oH, fps, self.params, self.gains)
         sharding.barrier()
         print(f"✓ 3D video saved: {output_path}")
         return str(output_path)

@@ -75,7 +75,7 @@ class HipPipelineBackend(HipStereoBackend):
 
     def render_stereo(self, u16_4k, gains, layout, subpixel=False):
         """--stereo-output: the 4K BGR frames guide_luma left in its device staging + their u16 4K depth [n,Hhi,Whi] (device)
-        -> NumPy side-by-side frames [n,Hhi,outW,3]: one launch, one D2H, no second H2D of the 4K frames.  Slots of frames
+        -> NumPy packed frames [n,outH,outW,3] (convert.output_size): one launch, one D2H, no second H2D of the 4K frames.  Slots of frames
         that had no 4K frame hold stale data; the caller drops them.  subpixel: the sub-pixel renderer (--subpixel)."""
         torch = self.torch
         out = self._render_stereo_dev(u16_4k, gains, layout, subpixel)
@@ -88,9 +88,10 @@ class HipPipelineBackend(HipStereoBackend):
         torch, nat = self.torch, self.native
         n, H, W = u16_4k.shape
         dev = self._bufs["guide_dev"]
-        oW = 2 * W if layout == 0 else W
-        out = self._staging("stereo_dev", (dev.shape[0], H, oW, 3), torch.uint8, False)
-        nat.render_stereo_batch(dev[:n], u16_4k.contiguous(), *gains, layout, out[:n], subpixel=subpixel)
+        from .convert import render_stereo
+        oW, oH = nat.stereo_output_size(layout, W, H)
+        out = self._staging("stereo_dev", (dev.shape[0], oH, oW, 3), torch.uint8, False)
+        render_stereo(nat, dev[:n], u16_4k.contiguous(), *gains, layout, out[:n], subpixel)
         return out[:n]
 
     def render_stereo_png(self, u16_4k, gains, layout, subpixel=False):
@@ -172,7 +173,7 @@ class SbsTo4kDepthPipeline:
         gpu_png = ex.png_encoder == "gpu"
         stereo = None
         if stereo_output is not None:
-            from .convert import png_rgb_from_bgr, sibling_frames_dir, stereo_settings, subpixel_kwargs
+            from .convert import LAYOUTS, output_size, png_rgb_from_bgr, sibling_frames_dir, stereo_settings, subpixel_kwargs
             params = dict(max_shift=48.0, convergence=0.5, eye_split=0.5, layout="full-sbs")
             params.update(stereo_options or {})
             layout, gains = stereo_settings(**params)
@@ -202,6 +203,9 @@ class SbsTo4kDepthPipeline:
         if stereo is not None:
             if stereo["layout"] == 1 and Whi % 2:
                 raise ValueError(f"half SBS needs an even frame width, the 4K clip is {Whi} wide")
+            if stereo["layout"] == LAYOUTS["half-tb"] and Hhi % 2:
+                raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {Hhi} high")
+            stereo["size"] = output_size(stereo["layout"], Whi, Hhi)
             stereo["dir"].mkdir(parents=True, exist_ok=True)
         if not ex.model_loaded:
             ex.load_model()
@@ -262,7 +266,7 @@ class SbsTo4kDepthPipeline:
                 if stereo is not None and any(f is not None for f in frames):
                     if gpu_png:
                         sbs3d = be.render_stereo_png(q_dev, stereo["gains"], stereo["layout"], **stereo["sub"])
-                        encode = rgb8_file(2 * Whi if stereo["layout"] == 0 else Whi, Hhi)
+                        encode = rgb8_file(*stereo["size"])
                     else:
                         sbs3d, encode = be.render_stereo(q_dev, stereo["gains"], stereo["layout"], **stereo["sub"]), png_rgb_from_bgr
                     for j, i in enumerate(idx):
@@ -293,8 +297,7 @@ class SbsTo4kDepthPipeline:
             if stereo is not None and n_stereo:
                 from .convert import finish_stereo_output, write_clip_info
                 write_clip_info(stereo["dir"], fps)
-                finish_stereo_output(stereo["dir"], stereo_output, n_stereo, 2 * Whi if stereo["layout"] == 0 else Whi, Hhi, fps,
-                                     stereo["params"], stereo["gains"])
+                finish_stereo_output(stereo["dir"], stereo_output, n_stereo, *stereo["size"], fps, stereo["params"], stereo["gains"])
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
         if stereo is not None:
