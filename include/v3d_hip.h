@@ -37,6 +37,10 @@
  *                          nothing checks the pairing): opt-in frame-accurate matching of SBS frames and 4K frames
  *   v3d_quality_reproj_batch, v3d_quality_flicker_batch  no call site in the reference (its readme only names "quality assessment
  *                          metrics"): opt-in, ground-truth-free measures of a run's own depth -- reprojection error and flicker
+ *   v3d_plane_profiles_batch, v3d_profile_match_scores, v3d_warp_u16_batch  no call site in the reference (upscale.py:47-63 scales
+ *                          the depth to the 4K size and assumes both releases share one framing): opt-in spatial registration of
+ *                          the SBS eye to the 4K frame -- crop, letterbox, scale and shift per axis -- and the warp of the low-res
+ *                          depth into the 4K frame's framing (register.py: align --register-spatial)
  *
  * Conventions
  *  - every image/volume pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
@@ -566,6 +570,55 @@ size_t v3d_quality_flicker_ws_bytes(int T, int W, int H);
 int v3d_quality_flicker_batch(const float* depth, size_t depth_stride /* elements */, const uint8_t* gray,
                               size_t gray_stride /* bytes */, int T, int W, int H, int still, int jump16,
                               uint64_t* out /* [T-1][4] */, void* ws, void* stream);
+
+/* Spatial registration (v3d_register.hip): fit the left eye of the SBS clip to the 4K frame with one affine map per axis and
+   resample the low-res depth into the 4K frame's framing (register.py: the align CLI's --register-spatial, the upscale and
+   pipeline CLIs' spatial block).  No call site in the reference.  Bit-exact contract, all integers, no floating point in any of
+   the three entries: tests/register_ref.py.
+   Profiles: frame f at gray + f*frame_stride (bytes), rows `pitch` bytes apart, only the W payload bytes of a row are read;
+     col[f][x] = sum_y Y[y][x],  row[f][y] = sum_x Y[y][x]   (u32, dense [n][W] and [n][H]; 255 * 8192 < 2^21).
+   Domain 1 <= W, H <= 8192 (above: V3D_ERR_UNSUPPORTED).  Two launches: the column sums of row bands go to ws (device scratch of
+   v3d_plane_profiles_ws_bytes, 16-byte aligned, any content on entry), the second launch adds the bands; no atomics on global
+   memory.  A frame's profiles do not depend on n, on its place in the batch or on the strides.  V3D_ERR_ARG: null pointer, n
+   outside [1, 65535], W or H < 1, pitch < W, frame_stride < H*pitch with n > 1, ws not 16-byte aligned.
+   Match: prof_a u32 dense [K][na] (source: the eye), prof_b u32 dense [K][nb] (target: the 4K frame), cand int64 [C][2] = (a, b)
+   in Q16, out int64 [K][C][6].  Every floor and >> is the mathematical one, every number a 64-bit integer:
+     target bin edges  t_j = floor(j * nb * 65536 / bins), j = 0 .. bins;   source edges  s_j = ((a * t_j) >> 16) + b;
+     integral of a profile P of length n at p in [0, n * 65536]:  I(p) = pre[p >> 16] * 65536 + (p & 65535) * P[p >> 16],
+       pre[i] = sum of P[k] over k < i, P[n] read as 0;   mean over [lo, hi) = floor((I(hi) - I(lo)) / (hi - lo));
+     mb_j = mean of B over [t_j, t_j+1);  ma_j = mean of A over [s_j, s_j+1), valid iff 0 <= s_j and s_j+1 <= na * 65536;
+     for j = 0 .. bins - 2 the pair is valid iff the bins j and j + 1 are: da = ma_j+1 - ma_j, db = mb_j+1 - mb_j;
+     record = (n_pairs, sum da, sum db, sum da*db, sum da^2, sum db^2) over the valid pairs.
+   Headroom: profile samples below 2^21 (what the profiles entry writes) give |d| < 2^21, products < 2^42 and sums over at most
+   1023 pairs < 2^52; larger samples are legal memory-wise and wrap in the record.  The host forms the zero-mean normalised
+   correlation from the six sums; it has none if a variance is 0 or n_pairs < bins / 2.  Candidate domain 2^12 <= a <= 2^20,
+   |b| <= 2^29.  cand is device memory, which the entry cannot read without synchronising: a candidate outside the domain is
+   refused in band, its record is (-1, 0, 0, 0, 0, 0) and nothing is computed for it; the binding refuses a host-side
+   candidate list with ValueError before anything is enqueued.  ws: device scratch of v3d_profile_match_ws_bytes (the prefix
+   sums of every frame's profiles, built by the first of the two launches), 16-byte aligned; cand and out 8-byte aligned.
+   V3D_ERR_ARG: null pointer, K outside [1, 4096], C outside [1, 65535], na or nb < 1, bins outside [8, 1024], nb < bins, a
+   misaligned pointer; V3D_ERR_UNSUPPORTED: na or nb > 8192.
+   Warp: frame f at src + f*src_stride (elements), rows dense, 2-byte alignment only (odd widths and odd element offsets are
+   legal); out dense u16 [n][Ho][Wo].  Per output pixel (x, y): u = ax * x + bx, v = ay * y + by, Q16 source-index coordinates;
+     out = fill  if u is outside [0, (Ws - 1) * 65536] or v outside [0, (Hs - 1) * 65536];  else with
+     i0 = u >> 16, i1 = min(i0 + 1, Ws - 1), fx = (u >> 8) & 255, j0, j1, fy likewise from v,
+     out = ((256 - fy) * ((256 - fx) * s[j0][i0] + fx * s[j0][i1]) + fy * ((256 - fx) * s[j1][i0] + fx * s[j1][i1]) + 32768) >> 16
+   (at most 65535 * 65536 + 32768 < 2^32).  The identity (65536, 0, 65536, 0) with Wo = Ws, Ho = Hs is a bit copy.  One launch.
+   V3D_ERR_ARG: null pointer, n outside [1, 65535], a size < 1, src_stride < Ws*Hs with n > 1, ax or ay outside [2^12, 2^20],
+   |bx| or |by| > 2^40, out overlapping src; V3D_ERR_UNSUPPORTED: Ws or Wo > 8192, Hs or Ho > 65535.
+   All three entries enqueue on `stream`, never synchronise, never allocate, take device pointers only and write nothing outside
+   their outputs and workspaces; a refused call enqueues nothing; the _ws_bytes functions return 0 for arguments their entry
+   refuses. */
+#define V3D_MATCH_FIELDS 6
+size_t v3d_plane_profiles_ws_bytes(int n, int W, int H);
+int v3d_plane_profiles_batch(const uint8_t* gray, int n, int W, int H, int pitch, size_t frame_stride /* bytes */,
+                             uint32_t* col_out /* [n][W] */, uint32_t* row_out /* [n][H] */, void* ws, void* stream);
+size_t v3d_profile_match_ws_bytes(int K, int na, int nb);
+int v3d_profile_match_scores(const uint32_t* prof_a, int na, const uint32_t* prof_b, int nb, int K,
+                             const int64_t* cand /* [C][2] */, int C, int bins, int64_t* out /* [K][C][6] */, void* ws, void* stream);
+int v3d_warp_u16_batch(const uint16_t* src, int n, int Ws, int Hs, size_t src_stride /* elements */,
+                       int64_t ax, int64_t bx, int64_t ay, int64_t by, uint16_t fill,
+                       uint16_t* out /* [n][Ho][Wo] */, int Wo, int Ho, void* stream);
 
 const char* v3d_last_error(void);
 const char* v3d_version(void);

@@ -35,6 +35,7 @@ EXPORTS = (
     "v3d_png_stream_bound", "v3d_png_out_bytes", "v3d_png_ws_bytes", "v3d_png_deflate_batch",
     "v3d_frame_signature_batch", "v3d_signature_scores",
     "v3d_quality_reproj_ws_bytes", "v3d_quality_reproj_batch", "v3d_quality_flicker_ws_bytes", "v3d_quality_flicker_batch",
+    "v3d_plane_profiles_ws_bytes", "v3d_plane_profiles_batch", "v3d_profile_match_ws_bytes", "v3d_profile_match_scores", "v3d_warp_u16_batch",
 )
 
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
@@ -167,6 +168,13 @@ def lib():
         L.v3d_quality_flicker_ws_bytes.argtypes = [ci, ci, ci]
         L.v3d_quality_flicker_ws_bytes.restype = sz
         L.v3d_quality_flicker_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.v3d_plane_profiles_ws_bytes.argtypes = [ci, ci, ci]
+        L.v3d_plane_profiles_ws_bytes.restype = sz
+        L.v3d_plane_profiles_batch.argtypes = [vp, ci, ci, ci, ci, sz, vp, vp, vp, vp]
+        L.v3d_profile_match_ws_bytes.argtypes = [ci, ci, ci]
+        L.v3d_profile_match_ws_bytes.restype = sz
+        L.v3d_profile_match_scores.argtypes = [vp, ci, vp, ci, ci, vp, ci, ci, vp, vp, vp]
+        L.v3d_warp_u16_batch.argtypes = [vp, ci, ci, ci, sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint16, vp, ci, ci, vp]
         _lib = L
     return _lib
 
@@ -1005,6 +1013,84 @@ def quality_flicker_batch(depth, gray, still, jump16, out=None, ws=None):
     with torch.cuda.device(depth.device):
         _check(lib().v3d_quality_flicker_batch(d, ds, g, gs, T, W, H, int(still), int(jump16), _dev(out, torch.int64, "out"),
                                                _dev(ws, torch.uint8, "ws"), _stream()), "v3d_quality_flicker_batch")
+    return out
+
+
+MATCH_FIELDS = 6                                   # V3D_MATCH_FIELDS
+MATCH_A_MIN, MATCH_A_MAX, MATCH_B_MAX = 1 << 12, 1 << 20, 1 << 29
+MATCH_MAX_CANDIDATES = 65535
+WARP_B_MAX = 1 << 40
+
+
+def plane_profiles_batch(gray):
+    """luma planes u8 [n,H,W] on the device (frames dense HxW, only the frame stride may differ) -> (col int32 [n,W], row int32
+    [n,H]): the column and row sums as uint32 bit patterns (v3d_plane_profiles_batch; bit-exact contract: tests/register_ref.py)"""
+    g, gs = _clip(gray, torch.uint8, "gray")
+    n, H, W = gray.shape
+    need = lib().v3d_plane_profiles_ws_bytes(n, W, H)
+    if not need:
+        raise NativeError(f"plane_profiles_batch: {n} planes of {W}x{H} outside the entry's range (at most 65535 of 8192 x 8192)")
+    col = torch.empty((n, W), dtype=torch.int32, device=gray.device)
+    row = torch.empty((n, H), dtype=torch.int32, device=gray.device)
+    ws = torch.empty(need, dtype=torch.uint8, device=gray.device)
+    with torch.cuda.device(gray.device):
+        _check(lib().v3d_plane_profiles_batch(g, n, W, H, W, gs, _dev(col, torch.int32, "col"), _dev(row, torch.int32, "row"),
+                                              _dev(ws, torch.uint8, "ws"), _stream()), "v3d_plane_profiles_batch")
+    return col, row
+
+
+def check_match_candidates(cand):
+    """a host-side candidate list -> int64 [C,2]; ValueError outside the entry's domain (the device refuses those in band)"""
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.int64).reshape(-1, 2))
+    bad = (c[:, 0] < MATCH_A_MIN) | (c[:, 0] > MATCH_A_MAX) | (np.abs(c[:, 1]) > MATCH_B_MAX)
+    if not len(c) or bad.any():
+        raise ValueError("no candidates" if not len(c) else
+                         f"candidate {c[np.flatnonzero(bad)[0]].tolist()} outside 2^12 <= a <= 2^20, |b| <= 2^29")
+    return c
+
+
+def profile_match_scores(prof_a, prof_b, cand, bins):
+    """profiles int32-viewed uint32 [K,na] (source) and [K,nb] (target) on the device, cand (a, b) in Q16: a NumPy int64 [C,2]
+    (checked against the domain here, ValueError, then copied) or a device int64 [C,2] tensor -> the records int64 [K,C,6] on the
+    device: (n_pairs, sum da, sum db, sum da db, sum da^2, sum db^2) (v3d_profile_match_scores; tests/register_ref.py)"""
+    for t, what in ((prof_a, "prof_a"), (prof_b, "prof_b")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise NativeError(f"{what}: expected an int32 [K,n] device tensor")
+    (K, na), (Kb, nb) = prof_a.shape, prof_b.shape
+    if K != Kb:
+        raise NativeError(f"prof_a has {K} frames, prof_b {Kb}")
+    if not isinstance(cand, torch.Tensor):
+        cand = torch.from_numpy(check_match_candidates(cand)).to(prof_a.device)
+    if cand.dim() != 2 or cand.shape[1] != 2:
+        raise NativeError(f"cand: expected int64 [C,2], got {tuple(cand.shape)}")
+    Cn = cand.shape[0]
+    need = lib().v3d_profile_match_ws_bytes(K, na, nb)
+    if not need:
+        raise NativeError(f"profile_match_scores: {K} frames of {na} and {nb} samples outside the entry's range (4096 frames, 8192 samples)")
+    out = torch.empty((K, Cn, MATCH_FIELDS), dtype=torch.int64, device=prof_a.device)
+    ws = torch.empty(need, dtype=torch.uint8, device=prof_a.device)
+    with torch.cuda.device(prof_a.device):
+        _check(lib().v3d_profile_match_scores(_dev(prof_a, torch.int32, "prof_a"), na, _dev(prof_b, torch.int32, "prof_b"), nb, K,
+                                              _dev(cand, torch.int64, "cand"), Cn, int(bins), _dev(out, torch.int64, "out"),
+                                              _dev(ws, torch.uint8, "ws"), _stream()), "v3d_profile_match_scores")
+    return out
+
+
+def warp_u16_batch(src, ax, bx, ay, by, Wo, Ho, fill=0, out=None):
+    """u16 planes as int16 bit patterns [n,Hs,Ws] on the device (frames dense, only the frame stride may differ) resampled through
+    u = ax x + bx, v = ay y + by (Q16 source-index coordinates) -> int16-viewed u16 [n,Ho,Wo]; `fill` outside the source
+    (v3d_warp_u16_batch; bit-exact contract: tests/register_ref.py)"""
+    s, ss = _clip(src, torch.int16, "src")
+    n, Hs, Ws = src.shape
+    if out is None:
+        out = torch.empty((n, int(Ho), int(Wo)), dtype=torch.int16, device=src.device)
+    if tuple(out.shape) != (n, Ho, Wo):
+        raise NativeError(f"out: expected shape {(n, Ho, Wo)}, got {tuple(out.shape)}")
+    if not 0 <= int(fill) <= 65535:
+        raise ValueError(f"fill must lie in [0, 65535], got {fill!r}")
+    with torch.cuda.device(src.device):
+        _check(lib().v3d_warp_u16_batch(s, n, Ws, Hs, ss, int(ax), int(bx), int(ay), int(by), int(fill), _dev(out, torch.int16, "out"),
+                                        int(Wo), int(Ho), _stream()), "v3d_warp_u16_batch")
     return out
 
 

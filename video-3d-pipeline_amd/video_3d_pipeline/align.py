@@ -8,7 +8,8 @@ reference's plot_audio_correlation needs matplotlib, which this package does not
 
 Optional second step, not in the reference: --refine-video matches frames of the two clips on the device around the rounded audio
 offset and --video-only does so without an audio step (framematch.py); alignment_data.json then also carries guide_start_frame,
-which guide_start_frame_from prefers.
+which guide_start_frame_from prefers.  --register-spatial (register.py) then fits the left eye to the 4K frame's framing on the
+device and adds a "spatial" block, which the upscale and pipeline CLIs apply to the low-res depth.
 """
 import argparse
 import json
@@ -148,6 +149,26 @@ class VideoAligner:
         print(f"Alignment data saved to: {alignment_file}")
         return alignment_data
 
+    def register_spatial(self, alignment_data: Dict, guide_start_frame: int, backend=None, **options) -> Dict:
+        """Fit the left eye of video1 to the frames of video2 (register.estimate: profiles and their match on the GPU), add the
+        "spatial" block to alignment_data and write alignment_data.json again.  Every other key stays as it is."""
+        from .register import estimate, spatial_block
+        print(f"Registering the left eye to the 4K frame from guide start frame {guide_start_frame} (GPU profiles)...")
+        res = estimate(self.video1_path, self.video2_path, guide_start_frame, backend=backend, **options)
+        alignment_data["spatial"] = spatial_block(res)
+        score = "n/a" if res["score"] is None else ", ".join(f"{v:.4f}" for v in res["score"])
+        print(f"Spatial registration: {res['status']}, map (Ax, Bx, Ay, By) = {tuple(res['map'])}, scores {score}")
+        if res["status"] == "inconsistent":
+            print("Warning: the probe frames disagree (a film that switches aspect ratio?); the identity is kept")
+        elif res["status"] == "undetermined":
+            print("Warning: the frames do not decide the map (flat or dark probes, weak texture); the identity is kept")
+        self.work_dir = create_work_directory(str(self.work_dir))
+        alignment_file = self.work_dir / 'alignment_data.json'
+        with open(alignment_file, 'w') as f:
+            json.dump(alignment_data, f, indent=2)
+        print(f"Alignment data saved to: {alignment_file}")
+        return alignment_data
+
     def assess_alignment_quality(self, alignment_data: Dict, tolerance_frames: float = 2.0) -> str:
         """Assess alignment quality and provide recommendations."""
         return assess_alignment_quality(alignment_data, tolerance_frames)
@@ -251,11 +272,17 @@ def main(argv=None, backend=None):
     parser.add_argument('--min-correlation', type=float, default=0.6, help='Minimum correlation to proceed')
     from .framematch import add_refine_arguments, refine_options
     add_refine_arguments(parser)
+    from .register import add_register_arguments
+    add_register_arguments(parser)
     args = parser.parse_args(argv)
+    spatial = dict(start_frame=args.start_frame, probes=args.register_probes, unsqueeze=not args.no_unsqueeze,
+                   max_frames=args.max_frames, min_score=args.register_min_score, bins=args.register_bins)
     try:
         aligner = VideoAligner(args.video1, args.video2, args.work_dir)
         if args.video_only:
             data = aligner.refine_video(aligner.video_only_data(), args.guide_start_frame, None, backend, **refine_options(args))
+            if args.register_spatial:
+                aligner.register_spatial(data, data['guide_start_frame'], backend, **spatial)
             print(f"\n✓ Video-only alignment: {data['visual_status']}, guide start frame {data['guide_start_frame']}")
             return 0
         alignment_data = aligner.find_alignment(args.max_audio)
@@ -266,6 +293,15 @@ def main(argv=None, backend=None):
                                                         int(round(-offset * float(alignment_data['video1_fps'])))))
             seed = int(round(offset * float(alignment_data['video2_fps'])))
             aligner.refine_video(alignment_data, seed, seed, backend, **refine_options(args))
+        if args.register_spatial:
+            g0 = alignment_data.get('guide_start_frame')
+            if g0 is None:
+                offset = alignment_data['time_offset_seconds']
+                if offset < 0:
+                    raise ValueError(_negative_start_advice("--register-spatial", f"{-offset:.3f}s",
+                                                            int(round(-offset * float(alignment_data['video1_fps'])))))
+                g0 = int(round(offset * float(alignment_data['video2_fps'])))
+            aligner.register_spatial(alignment_data, int(g0), backend, **spatial)
         quality = aligner.assess_alignment_quality(alignment_data, args.tolerance)
         if alignment_data['correlation_strength'] < args.min_correlation:
             print(f"\nWarning: Correlation {alignment_data['correlation_strength']:.3f} below threshold {args.min_correlation}")

@@ -280,6 +280,29 @@ class HipStereoBackend:
         nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
         return nat.frame_signature_batch(lg)
 
+    def sbs_left_profiles(self, frames: List[np.ndarray], unsqueeze: bool):
+        """SBS BGR frames -> the column and row sums of their left views on the device (register.estimate): the staging and the
+        gray split of sbs_left_signatures, then v3d_plane_profiles_batch"""
+        torch, nat = self.torch, self.native
+        n = len(frames)
+        H, W = frames[0].shape[:2]
+        ow = W if unsqueeze else W // 2
+        host = self._staging("sbs_host", (n, H, W, 3), torch.uint8, True)
+        hview = host.numpy()
+        for i, f in enumerate(frames):
+            hview[i] = f
+        dev = self._staging("sbs_dev", (n, H, W, 3), torch.uint8, False)
+        dev.copy_(host, non_blocking=True)
+        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
+        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
+        nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
+        return nat.plane_profiles_batch(lg)
+
+    def match_scores(self, prof_a, prof_b, cand, bins):
+        """profiles [K,na] and [K,nb] on the device, a host-side candidate list int64 [C,2] -> the records int64 [K,C,6] as NumPy
+        (one v3d_profile_match_scores call; the copy back synchronises: the search picks its next candidates from them)"""
+        return self.native.profile_match_scores(prof_a, prof_b, cand, bins).cpu().numpy()
+
     def signature_scores(self, sig_a, sig_b):
         """signatures [na,2304] x [nb,2304] on the device -> a handle for read_scores: one v3d_signature_scores call, then the
         three small integer arrays go to pinned memory without blocking; an event marks the end of the copies"""

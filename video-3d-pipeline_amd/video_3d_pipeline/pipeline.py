@@ -69,6 +69,24 @@ class HipPipelineBackend(HipStereoBackend):
             torch.cuda.current_stream().synchronize()
         return out
 
+    def guide_profiles(self, frames, height, width):
+        """4K BGR frames -> the column and row sums of their luma on the device (register.estimate): guide_luma's staging,
+        GUIDE_BATCH frames at a time, as guide_signatures"""
+        torch = self.torch
+        cols, rows = [], []
+        for j0 in range(0, len(frames), GUIDE_BATCH):
+            chunk = frames[j0:j0 + GUIDE_BATCH]
+            c, r = self.native.plane_profiles_batch(self.guide_luma(chunk, height, width, GUIDE_BATCH))
+            torch.cuda.current_stream().synchronize()
+            cols.append(c)
+            rows.append(r)
+        return torch.cat(cols), torch.cat(rows)
+
+    def warp_u16(self, u16, q, size):
+        """device u16 depth samples [n,H,W] -> the same samples in the 4K frame's framing [n,size[1],size[0]] (v3d_warp_u16_batch
+        through the Q16 map q = (ax, bx, ay, by); outside the source: 0, the far plane)"""
+        return self.native.warp_u16_batch(u16, *q, size[0], size[1], 0)
+
     def guided_upscale_u16(self, u16, luma, r, eps):
         """device u16 depth samples [n,H,W] + device luma [n,Hhi,Whi] -> device u16 4K samples [n,Hhi,Whi]"""
         return self.native.guided_upscale_u16_batch(u16, luma, r, eps)
@@ -161,12 +179,13 @@ class SbsTo4kDepthPipeline:
 
     def run(self, sbs_video: str, video_4k: str, output_path: str = None, start_frame: int = 0, max_frames: int = None,
             guide_start_frame: int = 0, force_reprocess: bool = False, keep_depth_maps: bool = False,
-            stereo_output: str = None, stereo_options: dict = None) -> str:
+            stereo_output: str = None, stereo_options: dict = None, spatial: dict = None) -> str:
         """guide_start_frame: the 4K frame that belongs to SBS frame start_frame (as for the upscale CLI).  Returns the
         output path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence.
         stereo_output: also render every frame that has a 4K frame to side-by-side 3D from the device-resident 4K frame and
         depth (the files the convert CLI writes from this run's depth output); stereo_options: max_shift, convergence,
-        eye_split, layout, subpixel (convert.py's defaults)."""
+        eye_split, layout, subpixel (convert.py's defaults); spatial: register.resolve()'s result -- the low-res u16 depth is warped
+        into the 4K frame's framing right before the guided filter (None: nothing changes)."""
         from . import sharding
         from .png_gpu import gray16_file, rgb8_file
         ex, be = self.extractor, self.backend
@@ -207,6 +226,12 @@ class SbsTo4kDepthPipeline:
                 raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {Hhi} high")
             stereo["size"] = output_size(stereo["layout"], Whi, Hhi)
             stereo["dir"].mkdir(parents=True, exist_ok=True)
+        warp = None
+        if spatial is not None:                                      # every rank applies the same map: nothing to exchange
+            from .register import warp_q16
+            eye = (video_info['width'] if ex.unsqueeze_sbs else video_info['width'] // 2, video_info['height'])
+            warp = warp_q16(spatial["map"], eye, (Whi, Hhi))
+            print(f"Spatial map {tuple(spatial['map'])} from {spatial['source']}: depth warped to {warp['size'][0]}x{warp['size'][1]} before the guided filter")
         if not ex.model_loaded:
             ex.load_model()
 
@@ -252,7 +277,10 @@ class SbsTo4kDepthPipeline:
                 frames = [next_guide() for _ in idx]
                 flat += sum(f is None for f in frames)
                 luma = be.guide_luma(frames, Hhi, Whi, gb)
-                q_dev = be.guided_upscale_u16(u16[j0:j0 + len(idx)], luma, self.radius, self.eps)
+                lo = u16[j0:j0 + len(idx)]
+                if warp is not None:
+                    lo = be.warp_u16(lo, warp["q"], warp["size"])
+                q_dev = be.guided_upscale_u16(lo, luma, self.radius, self.eps)
                 pending = check.emit(idx, frames, luma) if check is not None else None
                 if gpu_png:                                        # deflated on the device: only the streams cross PCIe
                     for i, s in zip(idx, be.png_streams_u16(q_dev)):
@@ -291,7 +319,9 @@ class SbsTo4kDepthPipeline:
         ex.finish_quality(cache_path if keep_depth_maps else frames_dir, rank)
         sharding.barrier()
         if rank == 0:
-            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps, ex.manifest_extra() or None)
+            from .register import manifest_entries
+            encode_depth4k(frames_dir, output_path, n, Whi, Hhi, fps, self.radius, self.eps,
+                           {**(ex.manifest_extra() or {}), **manifest_entries(spatial)} or None)
             if keep_depth_maps:
                 ex.write_side_files(cache_path)
             if stereo is not None and n_stereo:
@@ -303,6 +333,23 @@ class SbsTo4kDepthPipeline:
         if stereo is not None:
             print(f"✓ 3D video saved: {stereo_output} ({n_stereo} frames)")
         return str(output_path)
+
+
+def _resolve_spatial(args, resolve):
+    """--alignment-file's spatial block / --spatial-map / --no-spatial -> what the run applies (None: nothing); the clips' sizes are
+    only read when there is something to compare them with"""
+    if args.no_spatial or (args.alignment_file is None and args.spatial_map is None):
+        return None
+    unsqueeze = not args.no_unsqueeze
+
+    def eye():
+        info = get_video_info(args.video)
+        return None if not info else [info["width"] if unsqueeze else info["width"] // 2, info["height"]]
+
+    def guide():
+        info = get_video_info(args.video_4k)
+        return None if not info else [info["width"], info["height"]]
+    return resolve(args.alignment_file, False, args.spatial_map, eye, guide, unsqueeze)
 
 
 def main(argv=None):
@@ -328,6 +375,8 @@ def main(argv=None):
     parser.add_argument('--check-guide-min', type=float, default=0.5, help='Score below which a pair counts as bad (default 0.5)')
     from .convert import add_stereo_arguments, stereo_options
     add_stereo_arguments(parser)
+    from .register import add_apply_arguments, resolve
+    add_apply_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -338,13 +387,14 @@ def main(argv=None):
             return 1
         print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
     try:
+        spatial = _resolve_spatial(args, resolve)
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
         pipe = SbsTo4kDepthPipeline(check_guide=args.check_guide, check_guide_min=args.check_guide_min, **depth_options(args))
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,
-                               stereo_output=args.stereo_output, stereo_options=stereo_options(args))
+                               stereo_output=args.stereo_output, stereo_options=stereo_options(args), spatial=spatial)
         print(f"\n✓ Success! 4K depth video: {output_path}")
     except Exception as e:
         print(f"Error: {e}")

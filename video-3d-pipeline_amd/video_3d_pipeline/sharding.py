@@ -5,6 +5,8 @@ independent, so the only parallelism the path needs is data parallelism over fra
 frame i -> rank i mod world, one process per GPU, no data-path collective for depth.  The single
 real exchange is the 4K guide: rank 0 decodes a round of `world` guide frames and broadcasts the
 round over RCCL/xGMI (root -> 7 peers uses all 7 links in parallel); each rank keeps its own frame.
+A spatial map (register.py) is one set of four numbers per run, read from the command line or the alignment file by every
+rank alike: each rank warps its own frames with it and nothing is exchanged.
 """
 import os
 from collections import deque

@@ -205,3 +205,44 @@ def temporal_pan_sbs_clip(W, H, n_frames, pan, **kw):
 
     sbs = np.concatenate([squeeze(L), squeeze(R)], axis=2)
     return np.ascontiguousarray(np.repeat(sbs[..., None], 3, axis=3))
+
+
+# ---- a left eye and a "4K" frame of one scene in different framings (spatial registration: register.py, its tests) ----
+# The scene is a piecewise-constant master over the eye's normalised coordinates sigma in [-1/2, 3/2] on both axes, REG_SUPER master
+# pixels per eye pixel.  Both planes are exact area averages of it in float64: eye pixel x covers sigma in [x, x + 1) / We, guide
+# pixel X covers xi in [X, X + 1) / Wg and with it sigma = A xi + B.  The guide is graded differently (gain, offset, noise).
+REG_SUPER = 4
+
+
+def _area_means(M, edges, axis):
+    """means of the piecewise-constant M between consecutive `edges` (master pixel units, float64) along `axis`"""
+    c = np.concatenate([np.zeros_like(np.take(M, [0], axis)), np.cumsum(M, axis=axis)], axis=axis)
+    i = np.clip(np.floor(edges).astype(np.int64), 0, M.shape[axis] - 1)
+    at = np.take(c, i, axis) + np.take(M, i, axis) * np.expand_dims(edges - i, tuple(k for k in range(M.ndim) if k != axis))
+    w = np.expand_dims(np.diff(edges), tuple(k for k in range(M.ndim) if k != axis))
+    return np.diff(at, axis=axis) / w
+
+
+def registered_pair(eye_size, guide_size, amap, index=0, bars=False):
+    """(left-eye gray u8 [He,We], guide gray u8 [Hg,Wg]) of scene `index`, related by amap = (Ax, Bx, Ay, By); bars: the eye is
+    black outside the picture the guide shows (a letterboxed or pillarboxed disc)"""
+    (We, He), (Wg, Hg), (Ax, Bx, Ay, By) = eye_size, guide_size, amap
+    rng = np.random.default_rng(4321 + index)
+    S = REG_SUPER
+    hm, wm = 2 * He * S, 2 * We * S
+    M = 0.55 * _gray_texture(rng, hm, wm, sigma=1.5 * S) + 0.45 * _gray_texture(rng, hm, wm, sigma=6.0 * S, gain=12.0)
+    M = M.astype(np.float64)
+
+    def plane(n_x, n_y, ax, bx, ay, by):
+        ex = ((ax * np.arange(n_x + 1) / n_x + bx) + 0.5) * We * S
+        ey = ((ay * np.arange(n_y + 1) / n_y + by) + 0.5) * He * S
+        return _area_means(_area_means(M, ey, 0), ex, 1)
+
+    eye = plane(We, He, 1.0, 0.0, 1.0, 0.0)
+    if bars:
+        sx, sy = (np.arange(We) + 0.5) / We, (np.arange(He) + 0.5) / He
+        eye[(sy < By) | (sy > Ay + By), :] = 0.0
+        eye[:, (sx < Bx) | (sx > Ax + Bx)] = 0.0
+    guide = plane(Wg, Hg, Ax, Bx, Ay, By) * 0.9 + 8.0 + rng.normal(0.0, 1.0, (Hg, Wg))
+    to_u8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
+    return to_u8(eye), to_u8(guide)

@@ -79,6 +79,13 @@ class HipUpscaleBackend:
         q = self.upscale(depth_lo, guide, r, eps)
         return self._png.encode(self.native.round_to_u16(q.contiguous())[None])[0]
 
+    def warp_u16(self, depth_u16: np.ndarray, q, size):
+        """the u16 samples of a depth PNG -> the same samples in the 4K frame's framing as device float32 [size[1],size[0]]
+        (v3d_warp_u16_batch through the Q16 map q = (ax, bx, ay, by); outside the source: 0, the far plane), what upscale() takes"""
+        d = self.native.to_device(np.ascontiguousarray(depth_u16, dtype=np.uint16).view(np.int16)[None], self.device)
+        w = self.native.warp_u16_batch(d, *q, size[0], size[1], 0)[0]
+        return (w.to(self.torch.int32) & 0xFFFF).to(self.torch.float32)
+
     def flat_guide(self, h, w):
         return self.torch.full((h, w), 128, dtype=self.torch.uint8, device=self.device)
 
@@ -89,8 +96,11 @@ class SimpleDepthUpscaler:
     writer_pool_factory = PngWriterPool       # sink of the 4K 16-bit maps (see HybridStereoDepthExtractor.writer_pool_factory)
 
     def __init__(self, use_nvenc: bool = True, radius: int = GUIDED_RADIUS, eps: float = GUIDED_EPS,
-                 device: str = "cuda", backend=None, png_encoder: str = "zlib"):
-        """png_encoder: "gpu" deflates the 4K maps on the device (png_gpu.py); "zlib" = on the writer threads"""
+                 device: str = "cuda", backend=None, png_encoder: str = "zlib", spatial: dict = None):
+        """png_encoder: "gpu" deflates the 4K maps on the device (png_gpu.py); "zlib" = on the writer threads;
+        spatial: register.resolve()'s result -- every low-res depth map is warped into the 4K frame's framing right before the
+        guided filter (None: nothing changes)"""
+        self.spatial = spatial
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
         self.use_nvenc = use_nvenc
@@ -182,7 +192,7 @@ class SimpleDepthUpscaler:
 
         # this rank's depth maps, decoded a few files ahead on reader threads (PNG inflate is the slowest host step)
         my_depth = prefetch_map(read_png16, [depth_files[i] for i in range(rank, n, world)])
-        flat = 0
+        flat, warp = 0, None                                          # warp: every rank applies the same map, nothing to exchange
         with self.writer_pool_factory() as writers:                  # 4K 16-bit PNGs: ~80 ms of zlib each, compressed off the main thread
             posted = post_round(0) if exchange is not None else False
             for base in range(0, n, world):
@@ -202,7 +212,15 @@ class SimpleDepthUpscaler:
                 if guide is None:
                     flat += 1
                     guide = self.backend.flat_guide(target_height, target_width)    # beyond the 4K clip: flat guide == plain smoothing upsample
-                d16 = next(my_depth).astype(np.float32)
+                d16 = next(my_depth)
+                if self.spatial is not None:
+                    if warp is None:
+                        from .register import check_block_size, warp_q16
+                        check_block_size(self.spatial, d16.shape[1], d16.shape[0])
+                        warp = warp_q16(self.spatial["map"], (d16.shape[1], d16.shape[0]), (target_width, target_height))
+                    d16 = self.backend.warp_u16(d16, warp["q"], warp["size"])
+                else:
+                    d16 = d16.astype(np.float32)
                 if self.png_encoder == "gpu":
                     writers.submit(frames_dir / f"depth4k_{i:06d}.png", self.backend.upscale_png(d16, guide, self.radius, self.eps),
                                    encode=gray16_file(target_width, target_height))
@@ -214,7 +232,9 @@ class SimpleDepthUpscaler:
         sharding.barrier()
 
         if rank == 0:
-            encode_depth4k(frames_dir, output_path, n, target_width, target_height, fps, self.radius, self.eps)
+            from .register import manifest_entries
+            encode_depth4k(frames_dir, output_path, n, target_width, target_height, fps, self.radius, self.eps,
+                           manifest_entries(self.spatial) or None)
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
         return output_path
@@ -267,6 +287,8 @@ def main(argv=None, backend=None):
                             'round(time_offset_seconds * fps of the 4K clip)')
     from .png_gpu import add_png_arguments, png_options
     add_png_arguments(parser)
+    from .register import add_apply_arguments, resolve
+    add_apply_arguments(parser)
     args = parser.parse_args(argv)
     if args.alignment_file is not None:
         from .align import guide_start_frame_from
@@ -277,9 +299,17 @@ def main(argv=None, backend=None):
             return 1
         print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
     try:
+        spatial = None
+        if not args.no_spatial and (args.alignment_file is not None or args.spatial_map is not None):
+            def guide_size():
+                info = get_video_info(args.video_4k)
+                return None if not info else [info["width"], info["height"]]
+            spatial = resolve(args.alignment_file, False, args.spatial_map, None, guide_size)
+            if spatial is not None:
+                print(f"Spatial map {spatial['map']} from {spatial['source']}: depth maps are warped before the guided filter")
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        upscaler = SimpleDepthUpscaler(use_nvenc=not args.no_nvenc, backend=backend, **png_options(args))
+        upscaler = SimpleDepthUpscaler(use_nvenc=not args.no_nvenc, backend=backend, spatial=spatial, **png_options(args))
         output_path = upscaler.process_depth_upscaling(depth_dir=args.depth_dir, video_4k_path=args.video_4k,
                                                        output_path=args.output, force_reprocess=args.force,
                                                        guide_start_frame=args.guide_start_frame)
