@@ -12,7 +12,7 @@
 //      half SBS averages pairs in registers, and each thread writes its run with the widest aligned stores.
 // Contract: tests/stereo_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "DIBR stereo rendering".
 //
-// Sub-pixel DIBR (v3d_render_stereo_subpixel_batch, k_render_stereo<PPT, true>) is the same march with positions in 1/16 px:
+// Sub-pixel DIBR (v3d_render_stereo_subpixel_batch, k_render_stereo<PPT, true, K>) is the same march with positions in 1/16 px:
 // p(x) = 16 x + floor((g (D[x] - conv) + 2^19) / 2^20).  Source x owns the span [p(x), p(x) + L): L = p(x+1) - p(x) when that
 // lies in (0, V3D_STEREO_TEAR16] (a connected span, colours interpolated between F[x] and F[x+1]), else 16 (a point: last
 // column, fold or tear, colour F[x]).  It differs from the integer kernel in three places:
@@ -23,9 +23,10 @@
 //   ... and the nearest hit targets outside a thread's run are evaluated from their keys and the indices the scans yield.
 // Contract: tests/stereo_sub_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Sub-pixel DIBR".
 //
-// Output packings (v3d_render_stereo_packed_batch, k_render_packed<PPT, SUB, K>): the same march for either renderer with a fifth
-// step, which packs the eyes top-bottom, row-interleaved or as a red-cyan anaglyph before the store; colours that must wait for
-// the other eye or the next row wait in LDS words only their thread touches.
+// Output packings (v3d_render_stereo_packed_batch): the march is written once, k_render_stereo<PPT, SUB, K>.  K = ST_K_SBS is the
+// two side-by-side layouts above, stored from step 4; every other K adds a fifth step to either renderer, which packs the eyes
+// top-bottom, row-interleaved or as a red-cyan anaglyph before the store; colours that must wait for the other eye or the next
+// row wait in LDS words only their thread touches.
 // Contract: tests/stereo_pack_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Output packings".
 #include "v3d_common.h"
 #include "v3d_wave.h"
@@ -134,7 +135,7 @@ __host__ __device__ constexpr int st_park_bytes(int kind)
     return kind == ST_K_ANA ? 4 * PPT * ST_THREADS : kind == ST_K_HTB ? 2 * (PPT * 3 / 4) * 4 * ST_THREADS : 0;
 }
 
-// LDS of k_render_packed: both key rows, the widest depth and BGR rows at any phase, the parked words
+// static LDS of a packing's march (st_smem): both key rows, the widest depth and BGR rows at any phase, the parked words
 template <int PPT>
 __host__ __device__ constexpr int st_lds_bytes(int kind)
 {
@@ -167,232 +168,37 @@ __device__ __forceinline__ uint32_t st_anaglyph(uint32_t l, uint32_t r, int dubo
     return (uint32_t)min(max(B, 0), 255) | ((uint32_t)min(max(Gn, 0), 255) << 8) | ((uint32_t)min(max(R, 0), 255) << 16);
 }
 
-}  // namespace
-
-// one march for both entries; SUB selects the sub-pixel scatter and gather
-template <int PPT, bool SUB>
-__global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __restrict__ frame, size_t frame_stride,
-                                                              const uint16_t* __restrict__ depth, size_t depth_stride, int W, int H,
-                                                              int gl, int gr, int conv, int half, uint8_t* __restrict__ out,
-                                                              int sd_bytes)
+// the march's LDS.  Side by side: dynamic, sized per launch for the row's W (launch_stereo), the file's one dynamic declaration,
+// which the host emulator rewrites.  The packings: static, sized for the widest row of PPT pixels per thread plus what K parks
+// (st_park_bytes); 8 WP of it do not depend on W anyway.
+template <int PPT, int K>
+__device__ __forceinline__ unsigned char* st_smem()
 {
-    using G = StGeom<PPT>;
-    constexpr int WP = G::WP, ND = G::ND, NF = G::NF;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t* sZ = reinterpret_cast<uint32_t*>(smem);          // [2][WP]
-    unsigned char* sD = smem + 8 * WP;                         // depth row chunks (sd_bytes)
-    unsigned char* sF = sD + sd_bytes;                         // BGR row chunks
-    __shared__ uint32_t sTot[2][2][ST_THREADS / 64];           // [eye][prefix | suffix][wave]
-    __shared__ uint32_t sM[SUB ? V3D_STEREO_TEAR16 + 1 : 1];   // sub-pixel: ceil(2^20 / 2L), read after the row's first barrier
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if constexpr (SUB) {
-        if (tid >= 1 && tid <= V3D_STEREO_TEAR16) sM[tid] = ((1u << 20) + 2u * tid - 1u) / (2u * tid);
-    }
-    const int f = blockIdx.y;
-    const int y0 = blockIdx.x * ST_BAND, y1 = min(y0 + ST_BAND, H);
-    const uint8_t* fr = frame + (size_t)f * frame_stride;
-    const uint16_t* dp = depth + (size_t)f * depth_stride;
-    const int outW = half ? W : 2 * W;
-    const int eye_bytes = half ? (W / 2) * 3 : W * 3;
-
-    // a row's bytes as aligned 16-byte chunks: every load is unconditional (lanes past the last chunk re-read it), the
-    // chunks never leave the 16-byte blocks the row touches
-    uint4 rd[ND], rf[NF];
-    auto load_row = [&](int y) {
-        const uintptr_t ds = reinterpret_cast<uintptr_t>(dp + (size_t)y * W), fs = reinterpret_cast<uintptr_t>(fr + (size_t)y * W * 3);
-        const uint4* da = reinterpret_cast<const uint4*>(ds & ~(uintptr_t)15);
-        const uint4* fa = reinterpret_cast<const uint4*>(fs & ~(uintptr_t)15);
-        const int nd = (int)((ds + 2 * (uintptr_t)W - (ds & ~(uintptr_t)15) + 15) >> 4);
-        const int nf = (int)((fs + 3 * (uintptr_t)W - (fs & ~(uintptr_t)15) + 15) >> 4);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) rd[k] = ld_stream(da + min(k * ST_THREADS + tid, nd - 1));
-#pragma unroll
-        for (int k = 0; k < NF; ++k) rf[k] = ld_stream(fa + min(k * ST_THREADS + tid, nf - 1));
-    };
-
-    load_row(y0);
-    for (int y = y0; y < y1; ++y) {
-        const uintptr_t ds = reinterpret_cast<uintptr_t>(dp + (size_t)y * W), fs = reinterpret_cast<uintptr_t>(fr + (size_t)y * W * 3);
-        const int doff = (int)(ds & 15), foff = (int)(fs & 15);
-        const int nd = (doff + 2 * W + 15) >> 4, nf = (foff + 3 * W + 15) >> 4;
-        __syncthreads();                                       // the previous row's LDS reads are done
-#pragma unroll
-        for (int k = 0; k < ND; ++k) {
-            const int c = k * ST_THREADS + tid;
-            if (c < nd) reinterpret_cast<uint4*>(sD)[c] = rd[k];
-        }
-#pragma unroll
-        for (int k = 0; k < NF; ++k) {
-            const int c = k * ST_THREADS + tid;
-            if (c < nf) reinterpret_cast<uint4*>(sF)[c] = rf[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 2 * WP / 4 / ST_THREADS; ++k) reinterpret_cast<uint4*>(sZ)[k * ST_THREADS + tid] = make_uint4(0, 0, 0, 0);
-        if (y + 1 < y1) load_row(y + 1);                       // in flight while this row is rendered
-        __syncthreads();
-
-        // 2. scatter both eyes' keys
-        const uint16_t* drow = reinterpret_cast<const uint16_t*>(sD + doff);
-#pragma unroll 4
-        for (int j = 0; j < PPT; ++j) {
-            const int x = j * ST_THREADS + tid;
-            if (x < W) {
-                const int d = drow[x];
-                const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(x + 1);
-                if constexpr (SUB) {
-                    const int d1 = drow[min(x + 1, W - 1)];         // the last column: L' = 16, the point span's length
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int g = e ? gr : gl, s0 = st_shift16(g, d, conv), Lp = 16 + st_shift16(g, d1, conv) - s0;
-                        const int p = 16 * x + s0, end = p + ((unsigned)(Lp - 1) < (unsigned)V3D_STEREO_TEAR16 ? Lp : 16);
-                        const int t0 = (p + 15) >> 4;              // arithmetic shift = floor; L <= 32: at most two targets
-                        if (16 * t0 < end && (unsigned)t0 < (unsigned)W) atomicMax(sZ + e * WP + t0, key);
-                        if (16 * t0 + 16 < end && (unsigned)(t0 + 1) < (unsigned)W) atomicMax(sZ + e * WP + t0 + 1, key);
-                    }
-                } else {
-                    const int tl = x + st_shift(gl, d, conv), tr = x + st_shift(gr, d, conv);
-                    if ((unsigned)tl < (unsigned)W) atomicMax(sZ + tl, key);
-                    if ((unsigned)tr < (unsigned)W) atomicMax(sZ + WP + tr, key);
-                }
-            }
-        }
-        __syncthreads();
-
-        // 3. nearest keys outside my run: (last key index + 1) from the left, (WP - first key index) from the right
-        const int x0 = tid * PPT;
-        uint32_t pre[2], suf[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
-            uint32_t lastp = 0, firstp = 0;
-#pragma unroll
-            for (int q = PPT / 4 - 1; q >= 0; --q) {
-                const uint4 v = zr[q];
-                const uint32_t k4[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-                for (int i = 3; i >= 0; --i) {
-                    if (k4[i]) {
-                        if (!lastp) lastp = (uint32_t)(x0 + 4 * q + i + 1);
-                        firstp = (uint32_t)(WP - (x0 + 4 * q + i));
-                    }
-                }
-            }
-            const near2 sc = near2_incl(lastp, firstp, lane);
-            if (lane == 63) sTot[e][0][wave] = sc.pre;
-            if (lane == 0) sTot[e][1][wave] = sc.suf;
-            const near2 ex = near2_excl(sc, lane);
-            pre[e] = ex.pre; suf[e] = ex.suf;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-#pragma unroll
-            for (int w = 0; w < ST_THREADS / 64; ++w) {        // v3d_wave.h's near2_fold, kept here: its call costs half SBS 0.5 %
-                if (w < wave) pre[e] = max(pre[e], sTot[e][0][w]);
-                if (w > wave) suf[e] = max(suf[e], sTot[e][1][w]);
-            }
-        }
-
-        // 4. fill, gather, store
-        const int nvalid = min(PPT, W - x0);                   // <= 0: this thread's run lies beyond the row
-        uint8_t* orow = out + ((size_t)f * H + y) * (size_t)outW * 3;
-        const unsigned char* frow = sF + foff;
-        for (int e = 0; e < 2; ++e) {
-            uint32_t kk[PPT], col[PPT];
-            const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
-#pragma unroll
-            for (int q = 0; q < PPT / 4; ++q) {
-                const uint4 v = zr[q];
-                kk[4 * q] = v.x; kk[4 * q + 1] = v.y; kk[4 * q + 2] = v.z; kk[4 * q + 3] = v.w;
-            }
-            uint32_t nb = suf[e] ? sZ[e * WP + WP - suf[e]] : 0u;
-            uint32_t na = pre[e] ? sZ[e * WP + pre[e] - 1] : 0u;
-            if constexpr (SUB) {
-                // hit targets get their colour; holes then carry the (key, colour) of the nearest hit target on either side,
-                // the key only for the depth comparison
-                const int g = e ? gr : gl;
-                uint32_t hit = 0, nbc = 0, nac = 0;
-#pragma unroll
-                for (int i = 0; i < PPT; ++i) {
-                    col[i] = 0;
-                    if (kk[i]) { hit |= 1u << i; col[i] = st_sub_colour(kk[i], x0 + i, g, conv, W, drow, frow, sM); }
-                }
-                if (nb) nbc = st_sub_colour(nb, WP - (int)suf[e], g, conv, W, drow, frow, sM);
-                if (na) nac = st_sub_colour(na, (int)pre[e] - 1, g, conv, W, drow, frow, sM);
-#pragma unroll
-                for (int i = PPT - 1; i >= 0; --i) {
-                    if ((hit >> i) & 1u) { nb = kk[i]; nbc = col[i]; }
-                    else { kk[i] = nb; col[i] = nbc; }
-                }
-#pragma unroll
-                for (int i = 0; i < PPT; ++i) {
-                    if ((hit >> i) & 1u) { na = kk[i]; nac = col[i]; }
-                    else if (na && (!kk[i] || (na >> 16) <= (kk[i] >> 16))) col[i] = nac;      // st_fill's choice
-                }
-            } else {
-                uint32_t rb[PPT];
-#pragma unroll
-                for (int i = PPT - 1; i >= 0; --i) { rb[i] = nb; if (kk[i]) nb = kk[i]; }
-#pragma unroll
-                for (int i = 0; i < PPT; ++i) {
-                    uint32_t k = kk[i];
-                    if (k) na = k;
-                    else k = st_fill(na, rb[i]);
-                    const int s = k ? (int)(k & 0xFFFFu) - 1 : 0;
-                    const unsigned char* px = frow + 3 * s;
-                    col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
-                }
-            }
-            if (nvalid > 0 && !half) {
-                constexpr int NW = PPT * 3 / 4;
-                uint32_t wds[NW];
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) v |= ((col[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
-                    wds[w] = v;
-                }
-                st_store_run(orow + e * eye_bytes + x0 * 3, wds, nvalid * 3);
-            } else if (nvalid > 0) {
-                constexpr int NH = PPT / 2, NW = NH * 3 / 4;
-                uint32_t hc[NH];
-#pragma unroll
-                for (int i = 0; i < NH; ++i) {                 // per byte (a + b + 1) >> 1 = (a | b) - ((a ^ b) >> 1)
-                    const uint32_t a = col[2 * i], b = col[2 * i + 1];
-                    hc[i] = (a | b) - (((a ^ b) & 0xFEFEFEFEu) >> 1);
-                }
-                uint32_t wds[NW];
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) v |= ((hc[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
-                    wds[w] = v;
-                }
-                st_store_run(orow + e * eye_bytes + (x0 / 2) * 3, wds, (nvalid / 2) * 3);
-            }
-        }
+    if constexpr (K == ST_K_SBS) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char st_dyn[];
+        return st_dyn;
+    } else {
+        __shared__ __attribute__((aligned(16))) unsigned char st_fix[st_lds_bytes<PPT>(K)];
+        return st_fix;
     }
 }
 
-// The march of k_render_stereo for the packings of v3d_render_stereo_packed_batch (k_render_packed): steps 1 to 3 and the fill and
-// gather of step 4 are the same statements; K says what becomes of the eye colours, and the row-interleaved frame skips the eye a
-// row does not show.  It is a second copy on purpose: k_render_stereo called through a shared inlined body compiles to other
-// machine code (measured: half SBS 0.3 % slower at 4K), and the six side-by-side instantiations are pinned (tools/kernel_digest.py;
-// DESIGN.md §4, "Output packings").  A change to one march belongs in the other.  mode: ST_K_ANA: Dubois.
-// Its LDS is static, sized for the widest row of PPT pixels per thread plus what K parks (st_park_bytes): 8 WP of it do not
-// depend on W anyway, and the file keeps its one dynamic declaration.
+}  // namespace
+
+// The march, once, for all three entries.  SUB selects the sub-pixel scatter and gather.  K says what becomes of the eye colours:
+// ST_K_SBS stores them side by side (mode: half SBS) from step 4, the other K go through step 5 (mode: ST_K_ANA: Dubois), and the
+// row-interleaved frame skips the eye a row does not show (eye_on; for every other K it folds away).  K selects by if constexpr,
+// so an instantiation is compiled from its own statements alone, and its machine code is pinned (tools/kernel_digest.py;
+// DESIGN.md §4, "Output packings", One march): a few declarations below stand where they do because moving them moves it.
 template <int PPT, bool SUB, int K>
-__global__ __launch_bounds__(ST_THREADS) void k_render_packed(const uint8_t* __restrict__ frame, size_t frame_stride,
+__global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __restrict__ frame, size_t frame_stride,
                                                               const uint16_t* __restrict__ depth, size_t depth_stride, int W, int H,
                                                               int gl, int gr, int conv, int mode, uint8_t* __restrict__ out,
                                                               int sd_bytes)
 {
     using G = StGeom<PPT>;
     constexpr int WP = G::WP, ND = G::ND, NF = G::NF;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[st_lds_bytes<PPT>(K)];
+    unsigned char* smem = st_smem<PPT, K>();
     uint32_t* sZ = reinterpret_cast<uint32_t*>(smem);          // [2][WP]
     unsigned char* sD = smem + 8 * WP;                         // depth row chunks (sd_bytes)
     unsigned char* sF = sD + sd_bytes;                         // BGR row chunks
@@ -407,6 +213,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_packed(const uint8_t* __r
     const int y0 = blockIdx.x * ST_BAND, y1 = min(y0 + ST_BAND, H);
     const uint8_t* fr = frame + (size_t)f * frame_stride;
     const uint16_t* dp = depth + (size_t)f * depth_stride;
+    // side by side: the output row's arithmetic, declared here and constant for every other K (either moves machine code otherwise)
+    [[maybe_unused]] const int outW = K != ST_K_SBS ? 0 : mode ? W : 2 * W;
+    [[maybe_unused]] const int eye_bytes = K != ST_K_SBS ? 0 : mode ? (W / 2) * 3 : W * 3;
     // this thread's parked words: st_park_bytes; nobody else reads or writes them, so they need no barrier
     uint32_t* sP = reinterpret_cast<uint32_t*>(sF + st_chunks(3 * W, 15) * 16) + tid;
     // row-interleaved keeps one eye per row (the left in even rows): the other is neither scattered, scanned nor filled
@@ -515,6 +324,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_packed(const uint8_t* __r
 
         // 4. fill, gather, store
         const int nvalid = min(PPT, W - x0);                   // <= 0: this thread's run lies beyond the row
+        [[maybe_unused]] uint8_t* orow = K != ST_K_SBS ? nullptr : out + ((size_t)f * H + y) * (size_t)outW * 3;
         const unsigned char* frow = sF + foff;
         for (int e = 0; e < 2; ++e) {
             if (!eye_on(e, y)) continue;
@@ -563,7 +373,37 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_packed(const uint8_t* __r
                     col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
                 }
             }
-            {                                                  // 5. pack and store
+            if constexpr (K == ST_K_SBS) {                     // side by side: store from here, statements kept as they were
+                if (nvalid > 0 && !mode) {
+                    constexpr int NW = PPT * 3 / 4;
+                    uint32_t wds[NW];
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        uint32_t v = 0;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) v |= ((col[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
+                        wds[w] = v;
+                    }
+                    st_store_run(orow + e * eye_bytes + x0 * 3, wds, nvalid * 3);
+                } else if (nvalid > 0) {
+                    constexpr int NH = PPT / 2, NW = NH * 3 / 4;
+                    uint32_t hc[NH];
+#pragma unroll
+                    for (int i = 0; i < NH; ++i) {             // per byte (a + b + 1) >> 1 = (a | b) - ((a ^ b) >> 1)
+                        const uint32_t a = col[2 * i], b = col[2 * i + 1];
+                        hc[i] = (a | b) - (((a ^ b) & 0xFEFEFEFEu) >> 1);
+                    }
+                    uint32_t wds[NW];
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        uint32_t v = 0;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) v |= ((hc[(4 * w + b) / 3] >> (8 * ((4 * w + b) % 3))) & 0xFFu) << (8 * b);
+                        wds[w] = v;
+                    }
+                    st_store_run(orow + e * eye_bytes + (x0 / 2) * 3, wds, (nvalid / 2) * 3);
+                }
+            } else {                                           // 5. pack and store
                 constexpr int NW = PPT * 3 / 4;
                 if constexpr (K == ST_K_ANA) {               // both eyes' colours of my targets: the left eye's wait in LDS
                     if (e == 0) {
@@ -604,21 +444,18 @@ static int launch_stereo(const uint8_t* frame, size_t frame_stride, const uint16
 {
     using G = StGeom<PPT>;
     const int sd = st_chunks(2 * W, 14) * 16, sf = st_chunks(3 * W, 15) * 16;
-    if constexpr (K == ST_K_SBS) {
-        const int smem = 8 * G::WP + sd + sf;
-        auto* kernel = k_render_stereo<PPT, SUB>;
+    auto* kernel = k_render_stereo<PPT, SUB, K>;
+    if constexpr (K == ST_K_SBS) {                             // dynamic LDS (st_smem); the packings' is static
         static bool attr_set = false;                          // per instantiation; the attribute is a property of the function
         if (!attr_set) {
             V3D_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                               8 * G::WP + st_chunks(2 * G::WP, 14) * 16 + st_chunks(3 * G::WP, 15) * 16));
             attr_set = true;
         }
-        hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride,
-                           depth, depth_stride, W, H, gl, gr, conv, mode, out, sd);
-    } else {                                                   // static LDS
-        hipLaunchKernelGGL((k_render_packed<PPT, SUB, K>), dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), 0, stream, frame,
-                           frame_stride, depth, depth_stride, W, H, gl, gr, conv, mode, out, sd);
     }
+    const int smem = K == ST_K_SBS ? 8 * G::WP + sd + sf : 0;
+    hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride, depth,
+                       depth_stride, W, H, gl, gr, conv, mode, out, sd);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }

@@ -612,11 +612,9 @@ def stereo_gains(max_shift=48.0, convergence=0.5, eye_split=0.5):
     return gl, gr, conv
 
 
-def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, layout=STEREO_FULL_SBS, out=None, subpixel=False):
-    """DIBR (v3d_render_stereo_batch): frames u8 [n,H,W,3] BGR on the device (frames may be strided: rows dense), depth_u16 the
-    u16 depth samples as an int16-viewed contiguous [n,H,W] tensor -> u8 [n,H,2W,3] (full SBS, left eye first) or [n,H,W,3]
-    (half SBS).  Bit-exact contract: tests/stereo_ref.py.  subpixel: v3d_render_stereo_subpixel_batch instead, positions in
-    1/16 px and colours interpolated along connected spans (contract: tests/stereo_sub_ref.py)."""
+def _stereo_io(frames, depth_u16, out, out_size):
+    """the checks both DIBR wrappers make -> (n, H, W, out).  out_size(W, H) -> (outW, outH) makes the wrapper's own argument
+    checks, after those of the inputs and before that of out (allocated here if None)."""
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
         raise NativeError(f"frames: expected a uint8 [n,H,W,3] device tensor, got {frames.dtype} {tuple(frames.shape)}")
     n, H, W, _ = frames.shape
@@ -624,13 +622,25 @@ def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, l
         raise NativeError("frames: rows must be dense HxWx3 images (only the frame stride may differ)")
     if tuple(depth_u16.shape) != (n, H, W):
         raise NativeError(f"depth {tuple(depth_u16.shape)} does not match frames {tuple(frames.shape)}")
-    if layout not in (STEREO_FULL_SBS, STEREO_HALF_SBS):
-        raise ValueError(f"layout must be {STEREO_FULL_SBS} (full SBS) or {STEREO_HALF_SBS} (half SBS), got {layout!r}")
-    shape = (n, H, 2 * W if layout == STEREO_FULL_SBS else W, 3)
+    oW, oH = out_size(W, H)
+    shape = (n, oH, oW, 3)
     if out is None:
         out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
     if tuple(out.shape) != shape:
         raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    return n, H, W, out
+
+
+def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, layout=STEREO_FULL_SBS, out=None, subpixel=False):
+    """DIBR (v3d_render_stereo_batch): frames u8 [n,H,W,3] BGR on the device (frames may be strided: rows dense), depth_u16 the
+    u16 depth samples as an int16-viewed contiguous [n,H,W] tensor -> u8 [n,H,2W,3] (full SBS, left eye first) or [n,H,W,3]
+    (half SBS).  Bit-exact contract: tests/stereo_ref.py.  subpixel: v3d_render_stereo_subpixel_batch instead, positions in
+    1/16 px and colours interpolated along connected spans (contract: tests/stereo_sub_ref.py)."""
+    def out_size(W, H):
+        if layout not in (STEREO_FULL_SBS, STEREO_HALF_SBS):
+            raise ValueError(f"layout must be {STEREO_FULL_SBS} (full SBS) or {STEREO_HALF_SBS} (half SBS), got {layout!r}")
+        return (2 * W if layout == STEREO_FULL_SBS else W), H
+    n, H, W, out = _stereo_io(frames, depth_u16, out, out_size)
     entry = "v3d_render_stereo_subpixel_batch" if subpixel else "v3d_render_stereo_batch"
     with torch.cuda.device(frames.device):
         _check(getattr(lib(), entry)(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
@@ -656,21 +666,11 @@ def render_stereo_packed_batch(frames, depth_u16, gain_left, gain_right, converg
     """DIBR with the eyes packed for the display (v3d_render_stereo_packed_batch): the inputs of render_stereo_batch ->
     u8 [n,outH,outW,3] (stereo_output_size): side by side, top-bottom, row-interleaved or a red-cyan anaglyph, in one launch.
     Bit-exact contract: tests/stereo_pack_ref.py.  subpixel: the eyes of the sub-pixel renderer."""
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
-        raise NativeError(f"frames: expected a uint8 [n,H,W,3] device tensor, got {frames.dtype} {tuple(frames.shape)}")
-    n, H, W, _ = frames.shape
-    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W:
-        raise NativeError("frames: rows must be dense HxWx3 images (only the frame stride may differ)")
-    if tuple(depth_u16.shape) != (n, H, W):
-        raise NativeError(f"depth {tuple(depth_u16.shape)} does not match frames {tuple(frames.shape)}")
-    if not isinstance(subpixel, (bool, np.bool_)):
-        raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
-    oW, oH = stereo_output_size(packing, W, H)
-    shape = (n, oH, oW, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    if tuple(out.shape) != shape:
-        raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    def out_size(W, H):
+        if not isinstance(subpixel, (bool, np.bool_)):
+            raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
+        return stereo_output_size(packing, W, H)
+    n, H, W, out = _stereo_io(frames, depth_u16, out, out_size)
     with torch.cuda.device(frames.device):
         _check(lib().v3d_render_stereo_packed_batch(C.c_void_p(frames.data_ptr()), frames.stride(0),
                                                     _dev(depth_u16, torch.int16, "depth_u16"), H * W, n, W, H, int(gain_left),
