@@ -25,6 +25,54 @@ def test_header_symbols_are_exported():
     assert sorted(_native.EXPORTS) == declared, "python binding list and header disagree"
 
 
+_C_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
+              "int64_t": ctypes.c_int64, "uint16_t": ctypes.c_uint16}
+_C_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+
+
+def _declarations():
+    """include/v3d_hip.h, comments stripped -> {symbol: (return type, [parameter types])}; a pointer of any kind is "*" """
+    text = open(os.path.join(ROOT, "include", "v3d_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    decls = {}
+    for ret, name, params in re.findall(r"\b(void|int|size_t|const\s+char\s*\*)\s*(v3d_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        if params in ([""], ["void"]):
+            params = []
+        kinds = ["*" if "*" in p else p.replace("const ", "").rsplit(" ", 1)[0] for p in params]
+        decls[name] = (re.sub(r"\s*\*", "*", " ".join(ret.split())), kinds)
+    return decls
+
+
+def _is_pointer(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def test_binding_signatures_equal_the_header():
+    """every declaration of the header against the loaded binding: as many argtypes as parameters and the same class at every
+    position (a pointer: a ctypes pointer, c_void_p or c_char_p; a scalar: its ctypes twin), and the declared restype.  A symbol
+    left without argtypes would take anything: that is a failure too."""
+    from video_3d_pipeline import _native
+    lib = _native.lib()
+    decls = _declarations()
+    assert sorted(decls) == _declared_symbols(), "a declaration the signature pattern does not parse"
+    bad = []
+    for name, (ret, kinds) in decls.items():
+        fn = getattr(lib, name)
+        if fn.argtypes is None:
+            bad.append(f"{name}: no argtypes")
+            continue
+        if len(fn.argtypes) != len(kinds):
+            bad.append(f"{name}: {len(fn.argtypes)} argtypes for {len(kinds)} parameters")
+            continue
+        for i, (kind, t) in enumerate(zip(kinds, fn.argtypes)):
+            if not (_is_pointer(t) if kind == "*" else t is _C_SCALARS[kind]):
+                bad.append(f"{name}: parameter {i} is `{kind}`, bound as {t.__name__}")
+        if fn.restype is not _C_RETURNS[ret]:
+            bad.append(f"{name}: returns `{ret}`, bound as {fn.restype}")
+    assert not bad, "\n".join(bad)
+
+
 def test_no_torch_types_in_the_abi():
     text = open(os.path.join(ROOT, "include", "v3d_hip.h")).read()
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # signatures only, comments stripped

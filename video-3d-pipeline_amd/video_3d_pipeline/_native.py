@@ -14,30 +14,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libv3d_hip.so")
 _lib = None
 
-# every symbol include/v3d_hip.h declares
-EXPORTS = (
-    "v3d_sgbm_default_params", "v3d_sgbm_create", "v3d_sgbm_destroy", "v3d_sgbm_workspace_bytes",
-    "v3d_sgbm_compute", "v3d_sgbm_compute_batch", "v3d_sgbm_debug_cost_volume", "v3d_sgbm_debug_raw",
-    "v3d_median3x3_i16", "v3d_filter_speckles", "v3d_sbs_to_gray", "v3d_split_sbs", "v3d_disp_to_depth",
-    "v3d_depth_to_u16", "v3d_guided_upscale_ws_bytes", "v3d_guided_upscale", "v3d_bgr_to_gray",
-    "v3d_corr_ws_bytes", "v3d_corr_lookup", "v3d_last_error", "v3d_version",
-    "v3d_sbs_to_gray_batch", "v3d_guided_upscale_batch", "v3d_guided_upscale_disp16_batch",
-    "v3d_sgbm_sync_errors", "v3d_sgbm_set_lockstep", "v3d_sgbm_profile", "v3d_sgbm_profile_stage_count", "v3d_sgbm_profile_stage_name", "v3d_sgbm_profile_read",
-    "v3d_mono_blend_ws_bytes", "v3d_mono_blend", "v3d_mono_blend_batch",
-    "v3d_sgbm_poll_errors", "v3d_sgbm_stream_wait_lockstep", "v3d_sgbm_set_option", "v3d_sgbm_get_option", "v3d_set_option", "v3d_get_option", "v3d_round_to_u16",
-    "v3d_depth_to_u16_batch", "v3d_guided_upscale_u16_batch",
-    "v3d_xcorr_ws_bytes", "v3d_xcorr", "v3d_align_audio",
-    "v3d_render_stereo_batch", "v3d_render_stereo_subpixel_batch", "v3d_render_stereo_packed_batch",
-    "v3d_temporal_cuts", "v3d_depth_minmax_batch", "v3d_temporal_range", "v3d_temporal_filter_batch",
-    "v3d_depth_to_u16_range_batch", "v3d_temporal_motion", "v3d_temporal_filter_mc_batch",
-    "v3d_depth_robust_minmax_ws_bytes", "v3d_depth_robust_minmax_batch",
-    "v3d_fill_holes_ws_bytes", "v3d_fill_holes_disp16_batch",
-    "v3d_png_stream_bound", "v3d_png_out_bytes", "v3d_png_ws_bytes", "v3d_png_deflate_batch",
-    "v3d_frame_signature_batch", "v3d_signature_scores",
-    "v3d_quality_reproj_ws_bytes", "v3d_quality_reproj_batch", "v3d_quality_flicker_ws_bytes", "v3d_quality_flicker_batch",
-    "v3d_plane_profiles_ws_bytes", "v3d_plane_profiles_batch", "v3d_profile_match_ws_bytes", "v3d_profile_match_scores", "v3d_warp_u16_batch",
-)
-
 ERR_LOCKSTEP = -4      # V3D_ERR_LOCKSTEP
 STEREO_FULL_SBS, STEREO_HALF_SBS = 0, 1      # V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS
 STEREO_MAX_WIDTH = 8192
@@ -62,6 +38,89 @@ class SgbmParams(C.Structure):
         "preFilterCap", "uniquenessRatio", "speckleWindowSize", "speckleRange", "mode")]
 
 
+vp, ci, sz, fl, cs, i64 = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_char_p, C.c_int64
+# every symbol include/v3d_hip.h declares, once: name -> (restype, argtypes).  lib() binds exactly these rows and
+# tests/test_abi.py holds each of them to the header's declaration
+SIGNATURES = {
+    "v3d_sgbm_default_params": (None, [C.POINTER(SgbmParams)]),
+    "v3d_sgbm_create": (ci, [C.POINTER(SgbmParams), ci, ci, ci, ci, C.POINTER(vp)]),
+    "v3d_sgbm_destroy": (None, [vp]),
+    "v3d_sgbm_workspace_bytes": (sz, [vp]),
+    "v3d_sgbm_compute": (ci, [vp, vp, vp, ci, ci, ci, vp, vp]),
+    "v3d_sgbm_compute_batch": (ci, [vp, vp, vp, ci, ci, ci, ci, sz, vp, vp]),
+    "v3d_sgbm_sync_errors": (ci, [vp]),
+    "v3d_sgbm_poll_errors": (ci, [vp]),
+    "v3d_sgbm_set_lockstep": (ci, [vp, ci]),
+    "v3d_sgbm_stream_wait_lockstep": (ci, [vp, vp]),
+    "v3d_sgbm_set_option": (ci, [vp, cs, ci]),
+    "v3d_sgbm_get_option": (ci, [vp, cs, C.POINTER(ci)]),
+    "v3d_set_option": (ci, [cs, ci]),
+    "v3d_get_option": (ci, [cs, C.POINTER(ci)]),
+    "v3d_sgbm_profile": (ci, [vp, ci]),
+    "v3d_sgbm_profile_stage_count": (ci, []),
+    "v3d_sgbm_profile_stage_name": (cs, [ci]),
+    "v3d_sgbm_profile_read": (ci, [vp, C.POINTER(C.c_double), ci]),
+    "v3d_sgbm_debug_cost_volume": (ci, [vp, vp, vp, ci, ci, ci, vp, vp]),
+    "v3d_sgbm_debug_raw": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
+    "v3d_median3x3_i16": (ci, [vp, ci, ci, vp, vp]),
+    "v3d_filter_speckles": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
+    "v3d_sbs_to_gray": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_sbs_to_gray_batch": (ci, [vp, ci, ci, ci, ci, sz, ci, vp, vp, vp]),
+    "v3d_split_sbs": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_disp_to_depth": (ci, [vp, sz, vp, vp]),
+    "v3d_depth_to_u16": (ci, [vp, sz, vp, vp, vp]),
+    "v3d_depth_to_u16_batch": (ci, [vp, ci, sz, sz, vp, vp, vp]),
+    "v3d_round_to_u16": (ci, [vp, sz, vp, vp]),
+    "v3d_mono_blend_ws_bytes": (sz, [ci]),
+    "v3d_mono_blend": (ci, [vp, ci, ci, vp, ci, ci, fl, fl, vp, vp, vp]),
+    "v3d_mono_blend_batch": (ci, [vp, ci, ci, ci, vp, ci, ci, sz, fl, fl, vp, vp, vp]),
+    "v3d_guided_upscale_ws_bytes": (sz, [ci, ci]),
+    "v3d_guided_upscale": (ci, [vp, ci, ci, vp, ci, ci, ci, fl, vp, vp, vp]),
+    "v3d_guided_upscale_batch": (ci, [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, fl, vp, vp, vp]),
+    "v3d_guided_upscale_disp16_batch": (ci, [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, fl, vp, vp, vp]),
+    "v3d_guided_upscale_u16_batch": (ci, [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, fl, vp, vp, vp]),
+    "v3d_bgr_to_gray": (ci, [vp, sz, vp, vp]),
+    "v3d_corr_ws_bytes": (sz, [ci, ci, ci]),
+    "v3d_corr_lookup": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_xcorr_ws_bytes": (sz, [ci, ci]),
+    "v3d_xcorr": (ci, [vp, ci, vp, ci, vp, vp, vp]),
+    "v3d_align_audio": (ci, [vp, ci, vp, ci, vp, vp, vp]),
+    "v3d_render_stereo_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "v3d_render_stereo_subpixel_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "v3d_render_stereo_packed_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "v3d_temporal_cuts": (ci, [vp, sz, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_depth_minmax_batch": (ci, [vp, ci, sz, sz, vp, vp]),
+    "v3d_temporal_range": (ci, [vp, vp, ci, ci, ci, ci, vp, vp]),
+    "v3d_temporal_filter_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_temporal_motion": (ci, [vp, sz, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "v3d_temporal_filter_mc_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "v3d_depth_to_u16_range_batch": (ci, [vp, ci, sz, sz, vp, vp, vp]),
+    "v3d_depth_robust_minmax_ws_bytes": (sz, [ci]),
+    "v3d_depth_robust_minmax_batch": (ci, [vp, ci, sz, sz, ci, vp, vp, vp]),
+    "v3d_fill_holes_ws_bytes": (sz, [ci, ci]),
+    "v3d_fill_holes_disp16_batch": (ci, [vp, sz, ci, ci, ci, vp, vp, vp]),
+    "v3d_png_stream_bound": (sz, [ci, ci, ci]),
+    "v3d_png_out_bytes": (sz, [ci, ci, ci, ci]),
+    "v3d_png_ws_bytes": (sz, [ci, ci, ci, ci]),
+    "v3d_png_deflate_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "v3d_frame_signature_batch": (ci, [vp, ci, ci, ci, ci, sz, vp, vp]),
+    "v3d_signature_scores": (ci, [vp, ci, vp, ci, vp, vp, vp, vp]),
+    "v3d_quality_reproj_ws_bytes": (sz, [ci, ci, ci]),
+    "v3d_quality_reproj_batch": (ci, [vp, vp, ci, ci, ci, ci, sz, vp, sz, ci, vp, vp, vp]),
+    "v3d_quality_flicker_ws_bytes": (sz, [ci, ci, ci]),
+    "v3d_quality_flicker_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_plane_profiles_ws_bytes": (sz, [ci, ci, ci]),
+    "v3d_plane_profiles_batch": (ci, [vp, ci, ci, ci, ci, sz, vp, vp, vp, vp]),
+    "v3d_profile_match_ws_bytes": (sz, [ci, ci, ci]),
+    "v3d_profile_match_scores": (ci, [vp, ci, vp, ci, ci, vp, ci, ci, vp, vp, vp]),
+    "v3d_warp_u16_batch": (ci, [vp, ci, ci, ci, sz, i64, i64, i64, i64, C.c_uint16, vp, ci, ci, vp]),
+    "v3d_last_error": (cs, []),
+    "v3d_version": (cs, []),
+}
+EXPORTS = tuple(SIGNATURES)
+del vp, ci, sz, fl, cs, i64
+
+
 def lib_path():
     return _LIB_PATH
 
@@ -84,97 +143,9 @@ def lib():
                 f"{_LIB_PATH} not found: build it with `make -C video-3d-pipeline_amd/csrc` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         L = C.CDLL(_LIB_PATH)
-        vp, ci, sz = C.c_void_p, C.c_int, C.c_size_t
-        L.v3d_last_error.restype = C.c_char_p
-        L.v3d_version.restype = C.c_char_p
-        L.v3d_sgbm_default_params.argtypes = [C.POINTER(SgbmParams)]
-        L.v3d_sgbm_default_params.restype = None
-        L.v3d_sgbm_create.argtypes = [C.POINTER(SgbmParams), ci, ci, ci, ci, C.POINTER(vp)]
-        L.v3d_sgbm_destroy.argtypes = [vp]
-        L.v3d_sgbm_destroy.restype = None
-        L.v3d_sgbm_workspace_bytes.argtypes = [vp]
-        L.v3d_sgbm_workspace_bytes.restype = sz
-        L.v3d_sgbm_compute.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
-        L.v3d_sgbm_profile.argtypes = [vp, ci]
-        L.v3d_sgbm_sync_errors.argtypes = [vp]
-        L.v3d_sgbm_set_lockstep.argtypes = [vp, C.c_int]
-        L.v3d_sgbm_poll_errors.argtypes = [vp]
-        L.v3d_sgbm_stream_wait_lockstep.argtypes = [vp, vp]
-        L.v3d_sgbm_set_option.argtypes = [vp, C.c_char_p, ci]
-        L.v3d_sgbm_get_option.argtypes = [vp, C.c_char_p, C.POINTER(ci)]
-        L.v3d_set_option.argtypes = [C.c_char_p, ci]
-        L.v3d_get_option.argtypes = [C.c_char_p, C.POINTER(ci)]
-        L.v3d_mono_blend_ws_bytes.argtypes = [ci]
-        L.v3d_mono_blend_ws_bytes.restype = sz
-        L.v3d_mono_blend.argtypes = [vp, ci, ci, vp, ci, ci, C.c_float, C.c_float, vp, vp, vp]
-        L.v3d_mono_blend_batch.argtypes = [vp, ci, ci, ci, vp, ci, ci, sz, C.c_float, C.c_float, vp, vp, vp]
-        L.v3d_sgbm_profile_stage_name.argtypes = [ci]
-        L.v3d_sgbm_profile_stage_name.restype = C.c_char_p
-        L.v3d_sgbm_profile_read.argtypes = [vp, C.POINTER(C.c_double), ci]
-        L.v3d_sgbm_compute_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, sz, vp, vp]
-        L.v3d_sgbm_debug_cost_volume.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
-        L.v3d_sgbm_debug_raw.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
-        L.v3d_median3x3_i16.argtypes = [vp, ci, ci, vp, vp]
-        L.v3d_filter_speckles.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp]
-        L.v3d_sbs_to_gray.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
-        L.v3d_split_sbs.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
-        L.v3d_sbs_to_gray_batch.argtypes = [vp, ci, ci, ci, ci, sz, ci, vp, vp, vp]
-        L.v3d_guided_upscale_batch.argtypes = [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, C.c_float, vp, vp, vp]
-        L.v3d_guided_upscale_disp16_batch.argtypes = [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, C.c_float, vp, vp, vp]
-        L.v3d_disp_to_depth.argtypes = [vp, sz, vp, vp]
-        L.v3d_depth_to_u16.argtypes = [vp, sz, vp, vp, vp]
-        L.v3d_depth_to_u16_batch.argtypes = [vp, ci, sz, sz, vp, vp, vp]
-        L.v3d_guided_upscale_u16_batch.argtypes = [vp, ci, ci, sz, vp, ci, ci, sz, ci, ci, C.c_float, vp, vp, vp]
-        L.v3d_round_to_u16.argtypes = [vp, sz, vp, vp]
-        L.v3d_guided_upscale_ws_bytes.argtypes = [ci, ci]
-        L.v3d_guided_upscale_ws_bytes.restype = sz
-        L.v3d_guided_upscale.argtypes = [vp, ci, ci, vp, ci, ci, ci, C.c_float, vp, vp, vp]
-        L.v3d_bgr_to_gray.argtypes = [vp, sz, vp, vp]
-        L.v3d_corr_ws_bytes.argtypes = [ci, ci, ci]
-        L.v3d_corr_ws_bytes.restype = sz
-        L.v3d_corr_lookup.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
-        L.v3d_xcorr_ws_bytes.argtypes = [ci, ci]
-        L.v3d_xcorr_ws_bytes.restype = sz
-        L.v3d_xcorr.argtypes = [vp, ci, vp, ci, vp, vp, vp]
-        L.v3d_align_audio.argtypes = [vp, ci, vp, ci, vp, vp, vp]
-        L.v3d_render_stereo_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.v3d_render_stereo_subpixel_batch.argtypes = L.v3d_render_stereo_batch.argtypes
-        L.v3d_render_stereo_packed_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.v3d_temporal_cuts.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp]
-        L.v3d_depth_minmax_batch.argtypes = [vp, ci, sz, sz, vp, vp]
-        L.v3d_temporal_range.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
-        L.v3d_temporal_filter_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
-        L.v3d_depth_to_u16_range_batch.argtypes = [vp, ci, sz, sz, vp, vp, vp]
-        L.v3d_temporal_motion.argtypes = [vp, sz, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
-        L.v3d_temporal_filter_mc_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
-        L.v3d_depth_robust_minmax_ws_bytes.argtypes = [ci]
-        L.v3d_depth_robust_minmax_ws_bytes.restype = sz
-        L.v3d_depth_robust_minmax_batch.argtypes = [vp, ci, sz, sz, ci, vp, vp, vp]
-        L.v3d_fill_holes_ws_bytes.argtypes = [ci, ci]
-        L.v3d_fill_holes_ws_bytes.restype = sz
-        L.v3d_fill_holes_disp16_batch.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp]
-        L.v3d_png_stream_bound.argtypes = [ci, ci, ci]
-        L.v3d_png_stream_bound.restype = sz
-        L.v3d_png_out_bytes.argtypes = [ci, ci, ci, ci]
-        L.v3d_png_out_bytes.restype = sz
-        L.v3d_png_ws_bytes.argtypes = [ci, ci, ci, ci]
-        L.v3d_png_ws_bytes.restype = sz
-        L.v3d_png_deflate_batch.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp, vp, vp]
-        L.v3d_frame_signature_batch.argtypes = [vp, ci, ci, ci, ci, sz, vp, vp]
-        L.v3d_signature_scores.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp]
-        L.v3d_quality_reproj_ws_bytes.argtypes = [ci, ci, ci]
-        L.v3d_quality_reproj_ws_bytes.restype = sz
-        L.v3d_quality_reproj_batch.argtypes = [vp, vp, ci, ci, ci, ci, sz, vp, sz, ci, vp, vp, vp]
-        L.v3d_quality_flicker_ws_bytes.argtypes = [ci, ci, ci]
-        L.v3d_quality_flicker_ws_bytes.restype = sz
-        L.v3d_quality_flicker_batch.argtypes = [vp, sz, vp, sz, ci, ci, ci, ci, ci, vp, vp, vp]
-        L.v3d_plane_profiles_ws_bytes.argtypes = [ci, ci, ci]
-        L.v3d_plane_profiles_ws_bytes.restype = sz
-        L.v3d_plane_profiles_batch.argtypes = [vp, ci, ci, ci, ci, sz, vp, vp, vp, vp]
-        L.v3d_profile_match_ws_bytes.argtypes = [ci, ci, ci]
-        L.v3d_profile_match_ws_bytes.restype = sz
-        L.v3d_profile_match_scores.argtypes = [vp, ci, vp, ci, ci, vp, ci, ci, vp, vp, vp]
-        L.v3d_warp_u16_batch.argtypes = [vp, ci, ci, ci, sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint16, vp, ci, ci, vp]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -199,6 +170,36 @@ def get_option(key):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _call(entry, device, *args):
+    """the one way an entry that takes a stream is launched: with `device` (the tensors' own) current, on that device's
+    current stream, and an error raised under the entry's own name.  args: ready ctypes values, every one but the stream"""
+    with torch.cuda.device(device):
+        rc = getattr(lib(), entry)(*args, _stream())
+    _check(rc, entry)
+
+
+def _out(out, shape, dtype, device):
+    """a caller's result tensor checked against `shape`, or a fresh one"""
+    shape = tuple(shape)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != shape:
+        raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    return out
+
+
+def _scratch(need, device, cache=None, key=None):
+    """uint8 device scratch of `need` bytes (a number, or a callable asked only when something is allocated), never fewer than
+    16.  With a cache, allocated once per (key, device) and kept; else from the caching allocator, nothing in the steady state"""
+    key = (key, device.index)
+    ws = cache.get(key) if cache is not None else None
+    if ws is None:
+        ws = torch.empty(max(int(need() if callable(need) else need), 16), dtype=torch.uint8, device=device)
+        if cache is not None:
+            cache[key] = ws
+    return ws
 
 
 def _dev(t, dtype, what):
@@ -289,10 +290,8 @@ class StereoSGBM:
         if out is None:
             out = torch.empty((n, H, W), dtype=torch.int16, device=l3.device)
         o3 = out if out.dim() == 3 else out[None]
-        with torch.cuda.device(self.device):
-            _check(lib().v3d_sgbm_compute_batch(self._h, _dev(l3, torch.uint8, "left"), _dev(r3, torch.uint8, "right"),
-                                                n, W, H, W, H * W, _dev(o3, torch.int16, "out"), _stream()),
-                   "v3d_sgbm_compute_batch")
+        _call("v3d_sgbm_compute_batch", self.device, self._h, _dev(l3, torch.uint8, "left"), _dev(r3, torch.uint8, "right"),
+              n, W, H, W, H * W, _dev(o3, torch.int16, "out"))
         return out if batched else o3[0]
 
     def sync_errors(self):
@@ -320,25 +319,23 @@ class StereoSGBM:
     def debug_cost_volume(self, left, right):
         H, W = left.shape
         out = torch.empty((H, W - 64, 64), dtype=torch.int16, device=left.device)
-        _check(lib().v3d_sgbm_debug_cost_volume(self._h, _dev(left, torch.uint8, "left"), _dev(right, torch.uint8, "right"),
-                                                W, H, W, _dev(out, torch.int16, "C"), _stream()), "v3d_sgbm_debug_cost_volume")
+        _call("v3d_sgbm_debug_cost_volume", self.device, self._h, _dev(left, torch.uint8, "left"), _dev(right, torch.uint8, "right"),
+              W, H, W, _dev(out, torch.int16, "C"))
         return out
 
     def debug_raw(self, left, right, want_S=False):
         H, W = left.shape
         out = torch.empty((H, W), dtype=torch.int16, device=left.device)
         S = torch.empty((H, W - 64, 64), dtype=torch.int16, device=left.device) if want_S else None
-        _check(lib().v3d_sgbm_debug_raw(self._h, _dev(left, torch.uint8, "left"), _dev(right, torch.uint8, "right"),
-                                        W, H, W, _dev(out, torch.int16, "disp"),
-                                        _dev(S, torch.int16, "S") if want_S else None, _stream()), "v3d_sgbm_debug_raw")
+        _call("v3d_sgbm_debug_raw", self.device, self._h, _dev(left, torch.uint8, "left"), _dev(right, torch.uint8, "right"),
+              W, H, W, _dev(out, torch.int16, "disp"), _dev(S, torch.int16, "S") if want_S else None)
         return (out, S) if want_S else out
 
 
 def median3x3(img):
     H, W = img.shape
     out = torch.empty_like(img)
-    _check(lib().v3d_median3x3_i16(_dev(img, torch.int16, "img"), W, H, _dev(out, torch.int16, "out"), _stream()),
-           "v3d_median3x3_i16")
+    _call("v3d_median3x3_i16", img.device, _dev(img, torch.int16, "img"), W, H, _dev(out, torch.int16, "out"))
     return out
 
 
@@ -346,8 +343,8 @@ def filter_speckles(img, new_val=-16, max_size=100, max_diff=512):
     H, W = img.shape
     out = img.clone()
     ws = torch.empty(3 * H * W, dtype=torch.int32, device=img.device)
-    _check(lib().v3d_filter_speckles(_dev(out, torch.int16, "img"), W, H, new_val, max_size, max_diff,
-                                     _dev(ws, torch.int32, "ws"), _stream()), "v3d_filter_speckles")
+    _call("v3d_filter_speckles", img.device, _dev(out, torch.int16, "img"), W, H, new_val, max_size, max_diff,
+          _dev(ws, torch.int32, "ws"))
     return out
 
 
@@ -361,8 +358,8 @@ def sbs_to_gray(sbs, unsqueeze=True):
     ow = W if unsqueeze else W // 2
     L = torch.empty((H, ow), dtype=torch.uint8, device=sbs.device)
     R = torch.empty_like(L)
-    _check(lib().v3d_sbs_to_gray(_dev(sbs, torch.uint8, "sbs"), W, H, W * 3, int(bool(unsqueeze)),
-                                 _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"), _stream()), "v3d_sbs_to_gray")
+    _call("v3d_sbs_to_gray", sbs.device, _dev(sbs, torch.uint8, "sbs"), W, H, W * 3, int(bool(unsqueeze)),
+          _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"))
     return L, R
 
 
@@ -374,8 +371,8 @@ def sbs_to_gray_batch(sbs, unsqueeze=True, out=None):
     ow = W if unsqueeze else W // 2
     if out is None:
         out = (torch.empty((n, H, ow), dtype=torch.uint8, device=sbs.device), torch.empty((n, H, ow), dtype=torch.uint8, device=sbs.device))
-    _check(lib().v3d_sbs_to_gray_batch(_dev(sbs, torch.uint8, "sbs"), n, W, H, W * 3, H * W * 3, int(bool(unsqueeze)),
-                                       _dev(out[0], torch.uint8, "L"), _dev(out[1], torch.uint8, "R"), _stream()), "v3d_sbs_to_gray_batch")
+    _call("v3d_sbs_to_gray_batch", sbs.device, _dev(sbs, torch.uint8, "sbs"), n, W, H, W * 3, H * W * 3, int(bool(unsqueeze)),
+          _dev(out[0], torch.uint8, "L"), _dev(out[1], torch.uint8, "R"))
     return out
 
 
@@ -386,8 +383,8 @@ def split_sbs(sbs, unsqueeze=True):
     ow = W if unsqueeze else W // 2
     L = torch.empty((H, ow, 3), dtype=torch.uint8, device=sbs.device)
     R = torch.empty_like(L)
-    _check(lib().v3d_split_sbs(_dev(sbs, torch.uint8, "sbs"), W, H, W * 3, int(bool(unsqueeze)),
-                               _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"), _stream()), "v3d_split_sbs")
+    _call("v3d_split_sbs", sbs.device, _dev(sbs, torch.uint8, "sbs"), W, H, W * 3, int(bool(unsqueeze)),
+          _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"))
     return L, R
 
 
@@ -396,16 +393,14 @@ def bgr_to_gray(bgr, out=None):
         out = torch.empty(bgr.shape[:-1], dtype=torch.uint8, device=bgr.device)
     if bgr.shape[-1] != 3 or tuple(out.shape) != tuple(bgr.shape[:-1]):
         raise NativeError(f"bgr_to_gray: shapes {tuple(bgr.shape)} -> {tuple(out.shape)}")
-    _check(lib().v3d_bgr_to_gray(_dev(bgr, torch.uint8, "bgr"), out.numel(), _dev(out, torch.uint8, "gray"), _stream()),
-           "v3d_bgr_to_gray")
+    _call("v3d_bgr_to_gray", bgr.device, _dev(bgr, torch.uint8, "bgr"), out.numel(), _dev(out, torch.uint8, "gray"))
     return out
 
 
 def disp_to_depth(disp16, out=None):
     if out is None:
         out = torch.empty(disp16.shape, dtype=torch.float32, device=disp16.device)
-    _check(lib().v3d_disp_to_depth(_dev(disp16, torch.int16, "disp16"), disp16.numel(), _dev(out, torch.float32, "out"),
-                                   _stream()), "v3d_disp_to_depth")
+    _call("v3d_disp_to_depth", disp16.device, _dev(disp16, torch.int16, "disp16"), disp16.numel(), _dev(out, torch.float32, "out"))
     return out
 
 
@@ -422,18 +417,17 @@ def mono_blend(disp16, mono, w_stereo=0.7, w_mono=0.3, out=None):
     if out is None:
         out = torch.empty(d3.shape, dtype=torch.float32, device=d3.device)
     o3 = out if out.dim() == 3 else out[None]
-    ws = torch.empty(max(int(lib().v3d_mono_blend_ws_bytes(n)), 16), dtype=torch.uint8, device=d3.device)
-    _check(lib().v3d_mono_blend_batch(_dev(d3, torch.int16, "disp16"), n, W, H, _dev(m3, torch.float32, "mono"), mw, mh, mh * mw,
-                                      float(w_stereo), float(w_mono), _dev(o3, torch.float32, "out"), _dev(ws, torch.uint8, "ws"),
-                                      _stream()), "v3d_mono_blend_batch")
+    ws = _scratch(lib().v3d_mono_blend_ws_bytes(n), d3.device)
+    _call("v3d_mono_blend_batch", d3.device, _dev(d3, torch.int16, "disp16"), n, W, H, _dev(m3, torch.float32, "mono"), mw, mh,
+          mh * mw, float(w_stereo), float(w_mono), _dev(o3, torch.float32, "out"), _dev(ws, torch.uint8, "ws"))
     return out if batched else o3[0]
 
 
 def depth_to_u16(depth):
     out = torch.empty(depth.shape, dtype=torch.int16, device=depth.device)   # torch has no uint16 math; raw bits
     ws = torch.empty(2, dtype=torch.float32, device=depth.device)
-    _check(lib().v3d_depth_to_u16(_dev(depth, torch.float32, "depth"), depth.numel(), _dev(out, torch.int16, "out"),
-                                  _dev(ws, torch.float32, "ws"), _stream()), "v3d_depth_to_u16")
+    _call("v3d_depth_to_u16", depth.device, _dev(depth, torch.float32, "depth"), depth.numel(), _dev(out, torch.int16, "out"),
+          _dev(ws, torch.float32, "ws"))
     return out
 
 
@@ -448,25 +442,26 @@ def depth_to_u16_batch(depth, out=None):
         out = torch.empty(depth.shape, dtype=torch.int16, device=depth.device)
     if depth.dim() != 3 or tuple(out.shape) != tuple(depth.shape):
         raise NativeError(f"depth_to_u16_batch: expected [n,H,W] in and out, got {tuple(depth.shape)} -> {tuple(out.shape)}")
-    key = (n, depth.device.index)
-    ws = _mm_ws.get(key)
-    if ws is None:
-        ws = _mm_ws[key] = torch.empty(2 * n, dtype=torch.float32, device=depth.device)
+    ws = _scratch(8 * n, depth.device, _mm_ws, n)                     # two floats per frame
     per = depth[0].numel() if n else 0
-    _check(lib().v3d_depth_to_u16_batch(_dev(depth, torch.float32, "depth"), n, per, per, _dev(out, torch.int16, "out"),
-                                        _dev(ws, torch.float32, "ws"), _stream()), "v3d_depth_to_u16_batch")
+    _call("v3d_depth_to_u16_batch", depth.device, _dev(depth, torch.float32, "depth"), n, per, per, _dev(out, torch.int16, "out"),
+          _dev(ws, torch.uint8, "ws"))
     return out
 
 
 def round_to_u16(depth):
     """float32 device tensor -> clamp(rint(x), 0, 65535) as uint16 bit patterns in an int16 tensor (torch has no uint16 math)"""
     out = torch.empty(depth.shape, dtype=torch.int16, device=depth.device)
-    _check(lib().v3d_round_to_u16(_dev(depth, torch.float32, "depth"), depth.numel(), _dev(out, torch.int16, "out"), _stream()),
-           "v3d_round_to_u16")
+    _call("v3d_round_to_u16", depth.device, _dev(depth, torch.float32, "depth"), depth.numel(), _dev(out, torch.int16, "out"))
     return out
 
 
 _gf_ws = {}
+
+
+def _gf_scratch(Whi, Hhi, n, device):
+    """the guided filter's workspace for n frames of Whi x Hhi, allocated once per geometry and device"""
+    return _scratch(lambda: int(lib().v3d_guided_upscale_ws_bytes(Whi, Hhi)) * n, device, _gf_ws, (Whi, Hhi, n))
 
 
 def guided_upscale(depth_lo, guide, r=8, eps=1e-3, out=None):
@@ -475,14 +470,9 @@ def guided_upscale(depth_lo, guide, r=8, eps=1e-3, out=None):
     Hhi, Whi = guide.shape
     if out is None:
         out = torch.empty((Hhi, Whi), dtype=torch.float32, device=guide.device)
-    key = (Whi, Hhi, guide.device.index)
-    ws = _gf_ws.get(key)
-    if ws is None:
-        ws = torch.empty(int(lib().v3d_guided_upscale_ws_bytes(Whi, Hhi)), dtype=torch.uint8, device=guide.device)
-        _gf_ws[key] = ws
-    _check(lib().v3d_guided_upscale(_dev(depth_lo, torch.float32, "depth_lo"), Wlo, Hlo, _dev(guide, torch.uint8, "guide"),
-                                    Whi, Hhi, int(r), float(eps), _dev(out, torch.float32, "out"),
-                                    _dev(ws, torch.uint8, "ws"), _stream()), "v3d_guided_upscale")
+    ws = _gf_scratch(Whi, Hhi, 1, guide.device)
+    _call("v3d_guided_upscale", guide.device, _dev(depth_lo, torch.float32, "depth_lo"), Wlo, Hlo, _dev(guide, torch.uint8, "guide"),
+          Whi, Hhi, int(r), float(eps), _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -499,24 +489,16 @@ def guided_upscale_batch(depth_lo, guide, r=8, eps=1e-3, out=None):
         raise NativeError("guide frames must be dense HxW images")
     if out is None:
         out = torch.empty((n, Hhi, Whi), dtype=torch.float32, device=guide.device)
-    ws = _gf_batch_ws(Whi, Hhi, n, guide.device)
+    ws = _gf_scratch(Whi, Hhi, n, guide.device)
     if guide.dtype != torch.uint8 or not guide.is_cuda:
         raise NativeError("guide: expected a uint8 device tensor")
     if depth_lo.dtype == torch.int16:
-        fn, name, src = lib().v3d_guided_upscale_disp16_batch, "v3d_guided_upscale_disp16_batch", _dev(depth_lo, torch.int16, "disp16")
+        entry, src = "v3d_guided_upscale_disp16_batch", _dev(depth_lo, torch.int16, "disp16")
     else:
-        fn, name, src = lib().v3d_guided_upscale_batch, "v3d_guided_upscale_batch", _dev(depth_lo, torch.float32, "depth_lo")
-    _check(fn(src, Wlo, Hlo, Hlo * Wlo, C.c_void_p(guide.data_ptr()), Whi, Hhi, guide.stride(0), n, int(r), float(eps),
-              _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"), _stream()), name)
+        entry, src = "v3d_guided_upscale_batch", _dev(depth_lo, torch.float32, "depth_lo")
+    _call(entry, guide.device, src, Wlo, Hlo, Hlo * Wlo, C.c_void_p(guide.data_ptr()), Whi, Hhi, guide.stride(0), n, int(r),
+          float(eps), _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"))
     return out
-
-
-def _gf_batch_ws(Whi, Hhi, n, device):
-    key = (Whi, Hhi, n, device.index)
-    ws = _gf_ws.get(key)
-    if ws is None:
-        ws = _gf_ws[key] = torch.empty(int(lib().v3d_guided_upscale_ws_bytes(Whi, Hhi)) * n, dtype=torch.uint8, device=device)
-    return ws
 
 
 def guided_upscale_u16_batch(depth_u16, guide, r=8, eps=1e-3, out=None):
@@ -531,15 +513,11 @@ def guided_upscale_u16_batch(depth_u16, guide, r=8, eps=1e-3, out=None):
         raise NativeError("guide: expected a uint8 device tensor")
     if guide.stride(2) != 1 or guide.stride(1) != Whi:
         raise NativeError("guide frames must be dense HxW images")
-    if out is None:
-        out = torch.empty((n, Hhi, Whi), dtype=torch.int16, device=guide.device)
-    if tuple(out.shape) != (n, Hhi, Whi):
-        raise NativeError(f"out: expected shape {(n, Hhi, Whi)}, got {tuple(out.shape)}")
-    ws = _gf_batch_ws(Whi, Hhi, n, guide.device)
-    _check(lib().v3d_guided_upscale_u16_batch(_dev(depth_u16, torch.int16, "depth_u16"), Wlo, Hlo, Hlo * Wlo,
-                                              C.c_void_p(guide.data_ptr()), Whi, Hhi, guide.stride(0), n, int(r), float(eps),
-                                              _dev(out, torch.int16, "out"), _dev(ws, torch.uint8, "ws"), _stream()),
-           "v3d_guided_upscale_u16_batch")
+    out = _out(out, (n, Hhi, Whi), torch.int16, guide.device)
+    ws = _gf_scratch(Whi, Hhi, n, guide.device)
+    _call("v3d_guided_upscale_u16_batch", guide.device, _dev(depth_u16, torch.int16, "depth_u16"), Wlo, Hlo, Hlo * Wlo,
+          C.c_void_p(guide.data_ptr()), Whi, Hhi, guide.stride(0), n, int(r), float(eps),
+          _dev(out, torch.int16, "out"), _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -547,10 +525,9 @@ def corr_lookup(fl, fr, flow, groups=4, pattern=0):
     """fl, fr: bf16 [h,w,C]; flow f32 [2,h,w] -> f32 [groups*9,h,w]"""
     h, w, Cc = fl.shape
     out = torch.empty((groups * 9, h, w), dtype=torch.float32, device=fl.device)
-    ws = torch.empty(max(int(lib().v3d_corr_ws_bytes(Cc, h, w)), 16), dtype=torch.uint8, device=fl.device)
-    _check(lib().v3d_corr_lookup(_dev(fl, torch.bfloat16, "fl"), _dev(fr, torch.bfloat16, "fr"),
-                                 _dev(flow, torch.float32, "flow"), Cc, h, w, groups, pattern,
-                                 _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_corr_lookup")
+    ws = _scratch(lib().v3d_corr_ws_bytes(Cc, h, w), fl.device)
+    _call("v3d_corr_lookup", fl.device, _dev(fl, torch.bfloat16, "fl"), _dev(fr, torch.bfloat16, "fr"),
+          _dev(flow, torch.float32, "flow"), Cc, h, w, groups, pattern, _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -563,7 +540,7 @@ def _xcorr_args(a1, a2, what):
     nbytes = int(lib().v3d_xcorr_ws_bytes(n1, n2)) if 1 <= n1 < 2 ** 31 and 1 <= n2 < 2 ** 31 else 0
     if nbytes == 0:
         raise NativeError(f"{what}: lengths {n1}, {n2} unsupported (need >= 1 and n1 + n2 - 1 <= 2^26)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=a1.device)
+    ws = _scratch(nbytes, a1.device)
     return (_dev(a1, torch.float32, "a1"), n1, _dev(a2, torch.float32, "a2"), n2), ws
 
 
@@ -572,8 +549,7 @@ def xcorr(a1, a2):
     tracks (index k = lag + n1 - 1), by FFT on the device (v3d_xcorr)"""
     args, ws = _xcorr_args(a1, a2, "xcorr")
     out = torch.empty(a1.numel() + a2.numel() - 1, dtype=torch.float32, device=a1.device)
-    with torch.cuda.device(a1.device):
-        _check(lib().v3d_xcorr(*args, _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_xcorr")
+    _call("v3d_xcorr", a1.device, *args, _dev(out, torch.float32, "out"), _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -582,9 +558,7 @@ def align_audio(a1, a2):
     (in samples, a1[n] ~ a2[n + lag]) that maximises |c| of find_audio_offset's normalised tracks (utils.py:137-165)"""
     args, ws = _xcorr_args(a1, a2, "align_audio")
     out = torch.empty(4, dtype=torch.float64, device=a1.device)
-    with torch.cuda.device(a1.device):
-        _check(lib().v3d_align_audio(*args, _dev(out, torch.float64, "result"), _dev(ws, torch.uint8, "ws"), _stream()),
-               "v3d_align_audio")
+    _call("v3d_align_audio", a1.device, *args, _dev(out, torch.float64, "result"), _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -623,12 +597,7 @@ def _stereo_io(frames, depth_u16, out, out_size):
     if tuple(depth_u16.shape) != (n, H, W):
         raise NativeError(f"depth {tuple(depth_u16.shape)} does not match frames {tuple(frames.shape)}")
     oW, oH = out_size(W, H)
-    shape = (n, oH, oW, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    if tuple(out.shape) != shape:
-        raise NativeError(f"out: expected shape {shape}, got {tuple(out.shape)}")
-    return n, H, W, out
+    return n, H, W, _out(out, (n, oH, oW, 3), torch.uint8, frames.device)
 
 
 def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, layout=STEREO_FULL_SBS, out=None, subpixel=False):
@@ -642,10 +611,8 @@ def render_stereo_batch(frames, depth_u16, gain_left, gain_right, convergence, l
         return (2 * W if layout == STEREO_FULL_SBS else W), H
     n, H, W, out = _stereo_io(frames, depth_u16, out, out_size)
     entry = "v3d_render_stereo_subpixel_batch" if subpixel else "v3d_render_stereo_batch"
-    with torch.cuda.device(frames.device):
-        _check(getattr(lib(), entry)(C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
-                                     H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout),
-                                     _dev(out, torch.uint8, "out"), _stream()), entry)
+    _call(entry, frames.device, C.c_void_p(frames.data_ptr()), frames.stride(0), _dev(depth_u16, torch.int16, "depth_u16"),
+          H * W, n, W, H, int(gain_left), int(gain_right), int(convergence), int(layout), _dev(out, torch.uint8, "out"))
     return out
 
 
@@ -671,11 +638,9 @@ def render_stereo_packed_batch(frames, depth_u16, gain_left, gain_right, converg
             raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
         return stereo_output_size(packing, W, H)
     n, H, W, out = _stereo_io(frames, depth_u16, out, out_size)
-    with torch.cuda.device(frames.device):
-        _check(lib().v3d_render_stereo_packed_batch(C.c_void_p(frames.data_ptr()), frames.stride(0),
-                                                    _dev(depth_u16, torch.int16, "depth_u16"), H * W, n, W, H, int(gain_left),
-                                                    int(gain_right), int(convergence), int(bool(subpixel)), int(packing),
-                                                    _dev(out, torch.uint8, "out"), _stream()), "v3d_render_stereo_packed_batch")
+    _call("v3d_render_stereo_packed_batch", frames.device, C.c_void_p(frames.data_ptr()), frames.stride(0),
+          _dev(depth_u16, torch.int16, "depth_u16"), H * W, n, W, H, int(gain_left), int(gain_right), int(convergence),
+          int(bool(subpixel)), int(packing), _dev(out, torch.uint8, "out"))
     return out
 
 
@@ -712,9 +677,7 @@ def temporal_cuts(gray, cut_threshold=20):
     T, H, W = gray.shape
     ws = torch.empty(T, dtype=torch.int64, device=gray.device)
     out = torch.empty(T, dtype=torch.uint8, device=gray.device)
-    with torch.cuda.device(gray.device):
-        _check(lib().v3d_temporal_cuts(g, gs, T, W, H, int(cut_threshold), _dev(ws, torch.int64, "ws"), _dev(out, torch.uint8, "cut"),
-                                       _stream()), "v3d_temporal_cuts")
+    _call("v3d_temporal_cuts", gray.device, g, gs, T, W, H, int(cut_threshold), _dev(ws, torch.int64, "ws"), _dev(out, torch.uint8, "cut"))
     return out
 
 
@@ -723,8 +686,7 @@ def depth_minmax_batch(depth):
     d, ds = _clip(depth, torch.float32, "depth")
     T, H, W = depth.shape
     out = torch.empty((T, 2), dtype=torch.float32, device=depth.device)
-    with torch.cuda.device(depth.device):
-        _check(lib().v3d_depth_minmax_batch(d, T, H * W, ds, _dev(out, torch.float32, "minmax"), _stream()), "v3d_depth_minmax_batch")
+    _call("v3d_depth_minmax_batch", depth.device, d, T, H * W, ds, _dev(out, torch.float32, "minmax"))
     return out
 
 
@@ -739,11 +701,10 @@ def depth_robust_minmax_batch(depth, q):
         raise ValueError(f"range quantile must be an integer in [{RANGE_Q_MIN}, {RANGE_Q_OFF}], got {q!r}")
     d, ds = _clip(depth, torch.float32, "depth")
     T, H, W = depth.shape
-    ws = torch.empty(lib().v3d_depth_robust_minmax_ws_bytes(T), dtype=torch.uint8, device=depth.device)
+    ws = _scratch(lib().v3d_depth_robust_minmax_ws_bytes(T), depth.device)
     out = torch.empty((T, 2), dtype=torch.float32, device=depth.device)
-    with torch.cuda.device(depth.device):
-        _check(lib().v3d_depth_robust_minmax_batch(d, T, H * W, ds, int(q), _dev(ws, torch.uint8, "ws"),
-                                                   _dev(out, torch.float32, "minmax"), _stream()), "v3d_depth_robust_minmax_batch")
+    _call("v3d_depth_robust_minmax_batch", depth.device, d, T, H * W, ds, int(q), _dev(ws, torch.uint8, "ws"),
+          _dev(out, torch.float32, "minmax"))
     return out
 
 
@@ -754,9 +715,8 @@ def temporal_range(minmax, cut, radius, t0=0, n=None):
     if tuple(minmax.shape) != (T, 2) or tuple(cut.shape) != (T,):
         raise NativeError(f"temporal_range: minmax {tuple(minmax.shape)} / cut {tuple(cut.shape)} do not describe one clip")
     out = torch.empty((n, 2), dtype=torch.float32, device=minmax.device)
-    with torch.cuda.device(minmax.device):
-        _check(lib().v3d_temporal_range(_dev(minmax, torch.float32, "minmax"), _dev(cut, torch.uint8, "cut"), T, t0, n, int(radius),
-                                        _dev(out, torch.float32, "lohi"), _stream()), "v3d_temporal_range")
+    _call("v3d_temporal_range", minmax.device, _dev(minmax, torch.float32, "minmax"), _dev(cut, torch.uint8, "cut"), T, t0, n,
+          int(radius), _dev(out, torch.float32, "lohi"))
     return out
 
 
@@ -774,21 +734,15 @@ def _temporal_filter_args(depth, gray, radius, tau, cut, t0, n, out, fields=None
     n = _temporal_window(T, t0, n, radius)
     if not 1 <= tau <= 255:
         raise ValueError(f"temporal tau must be in [1, 255], got {tau}")
-    if out is None:
-        out = torch.empty((n, H, W), dtype=torch.float32, device=depth.device)
-    if tuple(out.shape) != (n, H, W):
-        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
-    return (d, ds, g, gs, T, W, H, n), out
+    return (d, ds, g, gs, T, W, H, n), _out(out, (n, H, W), torch.float32, depth.device)
 
 
 def temporal_filter_batch(depth, gray, radius, tau, cut, fill=True, t0=0, n=None, out=None):
     """the temporal filter (v3d_temporal_filter_batch): depth f32 [T,H,W] (<= 0 invalid), left gray u8 [T,H,W], cut u8 [T] ->
     filtered depth f32 [n,H,W] of targets t0 .. t0+n-1.  Bit-exact contract: tests/temporal_ref.py."""
     (d, ds, g, gs, T, W, H, n), out = _temporal_filter_args(depth, gray, radius, tau, cut, t0, n, out)
-    with torch.cuda.device(depth.device):
-        _check(lib().v3d_temporal_filter_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
-                                               _dev(cut, torch.uint8, "cut"), _dev(out, torch.float32, "out"), _stream()),
-               "v3d_temporal_filter_batch")
+    _call("v3d_temporal_filter_batch", depth.device, d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
+          _dev(cut, torch.uint8, "cut"), _dev(out, torch.float32, "out"))
     return out
 
 
@@ -810,10 +764,8 @@ def temporal_motion(gray, search, cut_threshold=20):
     bwd = torch.empty((T, BH, BW, 2), dtype=torch.int16, device=gray.device)
     resid = torch.empty(T, dtype=torch.int64, device=gray.device)
     cut = torch.empty(T, dtype=torch.uint8, device=gray.device)
-    with torch.cuda.device(gray.device):
-        _check(lib().v3d_temporal_motion(g, gs, T, W, H, int(search), int(cut_threshold), _dev(fwd, torch.int16, "mv_fwd"),
-                                         _dev(bwd, torch.int16, "mv_bwd"), _dev(resid, torch.int64, "resid"),
-                                         _dev(cut, torch.uint8, "cut"), _stream()), "v3d_temporal_motion")
+    _call("v3d_temporal_motion", gray.device, g, gs, T, W, H, int(search), int(cut_threshold), _dev(fwd, torch.int16, "mv_fwd"),
+          _dev(bwd, torch.int16, "mv_bwd"), _dev(resid, torch.int64, "resid"), _dev(cut, torch.uint8, "cut"))
     return fwd, bwd, resid, cut
 
 
@@ -821,11 +773,9 @@ def temporal_filter_mc_batch(depth, gray, radius, tau, cut, mv_fwd, mv_bwd, fill
     """temporal_filter_batch with every neighbouring frame read along the chained block vectors of temporal_motion's fields
     (v3d_temporal_filter_mc_batch).  Bit-exact contract: tests/temporal_mc_ref.py."""
     (d, ds, g, gs, T, W, H, n), out = _temporal_filter_args(depth, gray, radius, tau, cut, t0, n, out, (mv_fwd, mv_bwd))
-    with torch.cuda.device(depth.device):
-        _check(lib().v3d_temporal_filter_mc_batch(d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
-                                                  _dev(cut, torch.uint8, "cut"), _dev(mv_fwd, torch.int16, "mv_fwd"),
-                                                  _dev(mv_bwd, torch.int16, "mv_bwd"), _dev(out, torch.float32, "out"), _stream()),
-               "v3d_temporal_filter_mc_batch")
+    _call("v3d_temporal_filter_mc_batch", depth.device, d, ds, g, gs, T, W, H, t0, n, int(radius), int(tau), int(bool(fill)),
+          _dev(cut, torch.uint8, "cut"), _dev(mv_fwd, torch.int16, "mv_fwd"), _dev(mv_bwd, torch.int16, "mv_bwd"),
+          _dev(out, torch.float32, "out"))
     return out
 
 
@@ -836,13 +786,8 @@ def depth_to_u16_range_batch(depth, lohi, out=None):
     n, H, W = depth.shape
     if tuple(lohi.shape) != (n, 2):
         raise NativeError(f"lohi: expected shape {(n, 2)}, got {tuple(lohi.shape)}")
-    if out is None:
-        out = torch.empty((n, H, W), dtype=torch.int16, device=depth.device)
-    if tuple(out.shape) != (n, H, W):
-        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
-    with torch.cuda.device(depth.device):
-        _check(lib().v3d_depth_to_u16_range_batch(d, n, H * W, ds, _dev(lohi, torch.float32, "lohi"), _dev(out, torch.int16, "out"),
-                                                  _stream()), "v3d_depth_to_u16_range_batch")
+    out = _out(out, (n, H, W), torch.int16, depth.device)
+    _call("v3d_depth_to_u16_range_batch", depth.device, d, n, H * W, ds, _dev(lohi, torch.float32, "lohi"), _dev(out, torch.int16, "out"))
     return out
 
 
@@ -856,19 +801,14 @@ def fill_holes_disp16_batch(disp, out=None, ws=None):
     bytes, 16-byte aligned (a caller's staging buffer); None takes one from the caching allocator."""
     d, ds = _clip(disp, torch.int16, "disp")
     n, H, W = disp.shape
-    if out is None:
-        out = torch.empty((n, H, W), dtype=torch.int16, device=disp.device)
-    if tuple(out.shape) != (n, H, W):
-        raise NativeError(f"out: expected shape {(n, H, W)}, got {tuple(out.shape)}")
+    out = _out(out, (n, H, W), torch.int16, disp.device)
     need = lib().v3d_fill_holes_ws_bytes(n, H)
     if ws is None:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=disp.device)
+        ws = _scratch(need, disp.device)
     elif need and ws.numel() < need:
         raise NativeError(f"ws: {ws.numel()} bytes, the fill needs {need}")
     o = C.c_void_p(out.data_ptr()) if out is disp else _dev(out, torch.int16, "out")
-    with torch.cuda.device(disp.device):
-        _check(lib().v3d_fill_holes_disp16_batch(d, ds, n, W, H, o, _dev(ws, torch.uint8, "ws"), _stream()),
-               "v3d_fill_holes_disp16_batch")
+    _call("v3d_fill_holes_disp16_batch", disp.device, d, ds, n, W, H, o, _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -901,12 +841,11 @@ def png_deflate_batch(frames, out=None, offsets=None, ws=None):
     dev = frames.device
     out = torch.empty(need_out, dtype=torch.uint8, device=dev) if out is None else out
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets is None else offsets
-    ws = torch.empty(need_ws, dtype=torch.uint8, device=dev) if ws is None else ws
+    ws = _scratch(need_ws, dev) if ws is None else ws
     if out.numel() < need_out or ws.numel() < need_ws or offsets.numel() < n + 1:
         raise NativeError(f"png_deflate_batch: out / ws / offsets of {out.numel()} / {ws.numel()} / {offsets.numel()}, need {need_out} / {need_ws} / {n + 1}")
-    with torch.cuda.device(dev):
-        _check(L.v3d_png_deflate_batch(C.c_void_p(frames.data_ptr()), frames.stride(0) * item, fmt, n, W, H, _dev(out, torch.uint8, "out"),
-                                       _dev(offsets, torch.int64, "offsets"), _dev(ws, torch.uint8, "ws"), _stream()), "v3d_png_deflate_batch")
+    _call("v3d_png_deflate_batch", dev, C.c_void_p(frames.data_ptr()), frames.stride(0) * item, fmt, n, W, H,
+          _dev(out, torch.uint8, "out"), _dev(offsets, torch.int64, "offsets"), _dev(ws, torch.uint8, "ws"))
     return out, offsets
 
 
@@ -920,13 +859,8 @@ def frame_signature_batch(gray, out=None):
     bit-exact contract: tests/framematch_ref.py).  out: a caller's [n,2304] int16 tensor (a slice of a resident table)."""
     g, gs = _clip(gray, torch.uint8, "gray")
     n, H, W = gray.shape
-    if out is None:
-        out = torch.empty((n, SIG_CELLS), dtype=torch.int16, device=gray.device)
-    if tuple(out.shape) != (n, SIG_CELLS):
-        raise NativeError(f"out: expected shape {(n, SIG_CELLS)}, got {tuple(out.shape)}")
-    with torch.cuda.device(gray.device):
-        _check(lib().v3d_frame_signature_batch(g, n, W, H, W, gs, _dev(out, torch.int16, "sig"), _stream()),
-               "v3d_frame_signature_batch")
+    out = _out(out, (n, SIG_CELLS), torch.int16, gray.device)
+    _call("v3d_frame_signature_batch", gray.device, g, n, W, H, W, gs, _dev(out, torch.int16, "sig"))
     return out
 
 
@@ -942,10 +876,8 @@ def signature_scores(sig_a, sig_b):
     num = torch.empty((na, nb), dtype=torch.int64, device=dev)
     va = torch.empty(na, dtype=torch.int64, device=dev)
     vb = torch.empty(nb, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().v3d_signature_scores(_dev(sig_a, torch.int16, "sig_a"), na, _dev(sig_b, torch.int16, "sig_b"), nb,
-                                          _dev(num, torch.int64, "num"), _dev(va, torch.int64, "var_a"), _dev(vb, torch.int64, "var_b"),
-                                          _stream()), "v3d_signature_scores")
+    _call("v3d_signature_scores", dev, _dev(sig_a, torch.int16, "sig_a"), na, _dev(sig_b, torch.int16, "sig_b"), nb,
+          _dev(num, torch.int64, "num"), _dev(va, torch.int64, "var_a"), _dev(vb, torch.int64, "var_b"))
     return num, va, vb
 
 
@@ -956,12 +888,9 @@ QUALITY_MAX_WIDTH, QUALITY_MAX_HEIGHT = 8192, 65535
 def _quality_buffers(what, need, rows, fields, out, ws, device):
     if not need:
         raise NativeError(f"{what}: outside the entry's range (W <= {QUALITY_MAX_WIDTH}, H and the frame count <= {QUALITY_MAX_HEIGHT})")
-    if out is None:
-        out = torch.empty((rows, fields), dtype=torch.int64, device=device)
-    if tuple(out.shape) != (rows, fields):
-        raise NativeError(f"out: expected shape {(rows, fields)}, got {tuple(out.shape)}")
+    out = _out(out, (rows, fields), torch.int64, device)
     if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        ws = _scratch(need, device)
     elif ws.numel() < need:
         raise NativeError(f"ws: {ws.numel()} bytes, {what} needs {need}")
     return out, ws
@@ -991,9 +920,8 @@ def quality_reproj_batch(lg, rg, disp16, bad_thr=16, out=None, ws=None, right_sh
         dense = disp16[:, :, :W - k].contiguous()          # held until the launch is enqueued (the allocator is stream-ordered)
         d, ds = _clip(dense, torch.int16, "disp16")
     out, ws = _quality_buffers("quality_reproj_batch", lib().v3d_quality_reproj_ws_bytes(n, W - k, H), n, QUALITY_REPROJ_FIELDS, out, ws, lg.device)
-    with torch.cuda.device(lg.device):
-        _check(lib().v3d_quality_reproj_batch(l, r, n, W - k, H, W, ls, d, ds, int(bad_thr), _dev(out, torch.int64, "out"),
-                                              _dev(ws, torch.uint8, "ws"), _stream()), "v3d_quality_reproj_batch")
+    _call("v3d_quality_reproj_batch", lg.device, l, r, n, W - k, H, W, ls, d, ds, int(bad_thr), _dev(out, torch.int64, "out"),
+          _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -1010,9 +938,8 @@ def quality_flicker_batch(depth, gray, still, jump16, out=None, ws=None):
         if isinstance(v, bool) or int(v) != v or not 0 <= v <= hi:
             raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
     out, ws = _quality_buffers("quality_flicker_batch", lib().v3d_quality_flicker_ws_bytes(T, W, H), T - 1, QUALITY_FLICKER_FIELDS, out, ws, depth.device)
-    with torch.cuda.device(depth.device):
-        _check(lib().v3d_quality_flicker_batch(d, ds, g, gs, T, W, H, int(still), int(jump16), _dev(out, torch.int64, "out"),
-                                               _dev(ws, torch.uint8, "ws"), _stream()), "v3d_quality_flicker_batch")
+    _call("v3d_quality_flicker_batch", depth.device, d, ds, g, gs, T, W, H, int(still), int(jump16), _dev(out, torch.int64, "out"),
+          _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -1032,10 +959,9 @@ def plane_profiles_batch(gray):
         raise NativeError(f"plane_profiles_batch: {n} planes of {W}x{H} outside the entry's range (at most 65535 of 8192 x 8192)")
     col = torch.empty((n, W), dtype=torch.int32, device=gray.device)
     row = torch.empty((n, H), dtype=torch.int32, device=gray.device)
-    ws = torch.empty(need, dtype=torch.uint8, device=gray.device)
-    with torch.cuda.device(gray.device):
-        _check(lib().v3d_plane_profiles_batch(g, n, W, H, W, gs, _dev(col, torch.int32, "col"), _dev(row, torch.int32, "row"),
-                                              _dev(ws, torch.uint8, "ws"), _stream()), "v3d_plane_profiles_batch")
+    ws = _scratch(need, gray.device)
+    _call("v3d_plane_profiles_batch", gray.device, g, n, W, H, W, gs, _dev(col, torch.int32, "col"), _dev(row, torch.int32, "row"),
+          _dev(ws, torch.uint8, "ws"))
     return col, row
 
 
@@ -1068,11 +994,9 @@ def profile_match_scores(prof_a, prof_b, cand, bins):
     if not need:
         raise NativeError(f"profile_match_scores: {K} frames of {na} and {nb} samples outside the entry's range (4096 frames, 8192 samples)")
     out = torch.empty((K, Cn, MATCH_FIELDS), dtype=torch.int64, device=prof_a.device)
-    ws = torch.empty(need, dtype=torch.uint8, device=prof_a.device)
-    with torch.cuda.device(prof_a.device):
-        _check(lib().v3d_profile_match_scores(_dev(prof_a, torch.int32, "prof_a"), na, _dev(prof_b, torch.int32, "prof_b"), nb, K,
-                                              _dev(cand, torch.int64, "cand"), Cn, int(bins), _dev(out, torch.int64, "out"),
-                                              _dev(ws, torch.uint8, "ws"), _stream()), "v3d_profile_match_scores")
+    ws = _scratch(need, prof_a.device)
+    _call("v3d_profile_match_scores", prof_a.device, _dev(prof_a, torch.int32, "prof_a"), na, _dev(prof_b, torch.int32, "prof_b"), nb,
+          K, _dev(cand, torch.int64, "cand"), Cn, int(bins), _dev(out, torch.int64, "out"), _dev(ws, torch.uint8, "ws"))
     return out
 
 
@@ -1082,15 +1006,11 @@ def warp_u16_batch(src, ax, bx, ay, by, Wo, Ho, fill=0, out=None):
     (v3d_warp_u16_batch; bit-exact contract: tests/register_ref.py)"""
     s, ss = _clip(src, torch.int16, "src")
     n, Hs, Ws = src.shape
-    if out is None:
-        out = torch.empty((n, int(Ho), int(Wo)), dtype=torch.int16, device=src.device)
-    if tuple(out.shape) != (n, Ho, Wo):
-        raise NativeError(f"out: expected shape {(n, Ho, Wo)}, got {tuple(out.shape)}")
+    out = _out(out, (n, int(Ho), int(Wo)), torch.int16, src.device)
     if not 0 <= int(fill) <= 65535:
         raise ValueError(f"fill must lie in [0, 65535], got {fill!r}")
-    with torch.cuda.device(src.device):
-        _check(lib().v3d_warp_u16_batch(s, n, Ws, Hs, ss, int(ax), int(bx), int(ay), int(by), int(fill), _dev(out, torch.int16, "out"),
-                                        int(Wo), int(Ho), _stream()), "v3d_warp_u16_batch")
+    _call("v3d_warp_u16_batch", src.device, s, n, Ws, Hs, ss, int(ax), int(bx), int(ay), int(by), int(fill),
+          _dev(out, torch.int16, "out"), int(Wo), int(Ho))
     return out
 
 

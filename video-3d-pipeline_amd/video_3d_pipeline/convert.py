@@ -27,6 +27,7 @@ from pathlib import Path
 
 import numpy as np
 
+from .backend import HipBackend
 from .utils import PngWriterPool, encode_png8, get_video_info, iter_frames, prefetch_map, read_png16
 
 # V3D_PACK_*: codes 0 / 1 are V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS of v3d_render_stereo[_subpixel]_batch, codes >= 2 go to
@@ -164,24 +165,8 @@ def depth_frame_files(depth_path):
     return files
 
 
-class HipRenderBackend:
+class HipRenderBackend(HipBackend):
     """the device side of the convert step: pinned staging, one H2D, one v3d_render_stereo_batch launch, one D2H per batch"""
-
-    def __init__(self, device: str = "cuda"):
-        import torch
-        from . import _native
-        if not torch.cuda.is_available():
-            raise RuntimeError("CUDA not available but requested")
-        _native.lib()
-        self.torch, self.native, self.device = torch, _native, _native.resolve_device(device)
-        self._bufs = {}
-
-    def _staging(self, key, shape, dtype, pinned):
-        t = self._bufs.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self.torch.empty(shape, dtype=dtype, pin_memory=True) if pinned else self.torch.empty(shape, dtype=dtype, device=self.device)
-            self._bufs[key] = t
-        return t
 
     def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, png=False, subpixel=False):
         """NumPy BGR frames [H,W,3] + u16 depth maps [H,W] -> NumPy u8 [n,H,outW,3].  The input staging holds `capacity`
@@ -192,33 +177,17 @@ class HipRenderBackend:
         H, W = depths[0].shape
         cap = max(n, capacity or n)
         oW, oH = nat.stereo_output_size(layout, W, H)
-        fh = self._staging("frames_host", (cap, H, W, 3), torch.uint8, True)
-        dh = self._staging("depth_host", (cap, H, W), torch.int16, True)
-        fv, dv = fh.numpy(), dh.numpy()
-        for i, (f, d) in enumerate(zip(frames, depths)):
-            fv[i] = f
-            dv[i] = np.asarray(d, np.uint16).view(np.int16)
-        fd = self._staging("frames_dev", (cap, H, W, 3), torch.uint8, False)
-        dd = self._staging("depth_dev", (cap, H, W), torch.int16, False)
         od = self._staging("out_dev", (cap, oH, oW, 3), torch.uint8, False)
         with torch.cuda.device(self.device):
-            fd[:n].copy_(fh[:n], non_blocking=True)
-            dd[:n].copy_(dh[:n], non_blocking=True)
-            render_stereo(nat, fd[:n], dd[:n], gain_left, gain_right, conv, layout, od[:n], subpixel)
-            if png:
-                return od[:n]
-            host = torch.empty((n, oH, oW, 3), dtype=torch.uint8, pin_memory=True)
-            host.copy_(od[:n], non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-        return host.numpy()
+            fd = self._upload("frames", frames, (H, W, 3), torch.uint8, cap)
+            dd = self._upload("depth", [np.asarray(d, np.uint16).view(np.int16) for d in depths[:n]], (H, W), torch.int16, cap)
+            render_stereo(nat, fd, dd, gain_left, gain_right, conv, layout, od[:n], subpixel)
+            return od[:n] if png else self._fetch(od[:n])
 
     def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, subpixel=False):
         """--png-encoder gpu: render_batch whose frames stay on the device and come back as the zlib streams of their PNGs"""
-        if getattr(self, "_png", None) is None:
-            from .png_gpu import DevicePngEncoder
-            self._png = DevicePngEncoder(self.torch, self.native, self.device)
-        return self._png.encode(self.render_batch(frames, depths, gain_left, gain_right, conv, layout, capacity, png=True,
-                                                  subpixel=subpixel))
+        return self._png_encoder().encode(self.render_batch(frames, depths, gain_left, gain_right, conv, layout, capacity, png=True,
+                                                            subpixel=subpixel))
 
 
 class DepthTo3DConverter:

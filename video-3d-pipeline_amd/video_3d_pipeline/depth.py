@@ -26,6 +26,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from .backend import HipBackend
 from .utils import PngWriterPool, create_work_directory, get_video_info, iter_frames, write_png16
 
 
@@ -76,20 +77,11 @@ def min_disparity_suffix(m: int) -> str:
     return f"_mind{m}" if m != 0 else ""
 
 
-class HipStereoBackend:
+class HipStereoBackend(HipBackend):
     """The product compute backend: PyTorch-ROCm buffers + libv3d_hip.so kernels."""
 
     def __init__(self, device: str = "cuda", sgbm_params: Optional[Dict] = None):
-        import torch
-        from . import _native
-        if not torch.cuda.is_available():
-            raise RuntimeError("CUDA not available but requested")
-        self.torch = torch
-        self.native = _native
-        _native.lib()                                  # fail now, loudly, if the HIP library is missing
-        # resolved ONCE: a bare "cuda" is the current device (what torch.cuda.set_device / LOCAL_RANK selected), and
-        # tensors, the matcher's workspace and its kernels all live on that same index
-        self.device = _native.resolve_device(device)
+        super().__init__(device)
         self.sgbm_params = dict(sgbm_params or {})
         self._matcher = None
         self._geom = None
@@ -211,42 +203,36 @@ class HipStereoBackend:
         out = depth.cpu().numpy()
         return [out[i] for i in range(n)]
 
-    def _staging(self, key, shape, dtype, pinned):
-        """reusable buffers: pinned host staging + device tensors (no allocation on the steady-state path)"""
+    def _sbs_to_gray(self, frames: List[np.ndarray], unsqueeze: bool):
+        """SBS BGR frames -> (device frames [n,H,W,3], left gray, right gray [n,H,ow]): the frames are gathered into one pinned
+        buffer and cross PCIe in a single asynchronous copy, then one v3d_sbs_to_gray_batch launch.  The grays stay in the
+        staging buffers `lg` / `rg` (left_gray, right_gray) until the next pass."""
         torch = self.torch
-        bufs = self.__dict__.setdefault("_bufs", {})
-        t = bufs.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.empty(shape, dtype=dtype, pin_memory=True) if pinned else torch.empty(shape, dtype=dtype, device=self.device)
-            bufs[key] = t
-        return t
+        n = len(frames)
+        H, W = frames[0].shape[:2]
+        ow = W if unsqueeze else W // 2
+        dev = self._upload("sbs", frames, (H, W, 3), torch.uint8)
+        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
+        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
+        self.native.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
+        return dev, lg, rg
 
     def sbs_to_disparity(self, frames: List[np.ndarray], unsqueeze: bool, mono_provider=None, fill_holes: bool = False,
                          min_disparity: int = 0):
         """fused path: SBS BGR frames -> device float32 disparity [n,H,W] (no BGR halves materialised).
-        Frames are gathered into one pinned buffer and cross PCIe in a single asynchronous copy.
+        Frames are gathered into one pinned buffer and cross PCIe in a single asynchronous copy (_sbs_to_gray).
         mono_provider (neural guidance on): called with the left views as RGB arrays, its maps are blended in.
         fill_holes: the int16 disparity is filled in place after the matcher (and its lock-step recompute), before /16 and the
         blend.
         min_disparity: the matcher's window [m, m + 64); the disparity is rebiased to [0, 64) right after it (_match)."""
         torch, nat = self.torch, self.native
         n = len(frames)
-        H, W = frames[0].shape[:2]
-        ow = W if unsqueeze else W // 2
-        host = self._staging("sbs_host", (n, H, W, 3), torch.uint8, True)
-        hview = host.numpy()
-        for i, f in enumerate(frames):
-            hview[i] = f
-        dev = self._staging("sbs_dev", (n, H, W, 3), torch.uint8, False)
-        dev.copy_(host, non_blocking=True)
-        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
-        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
-        nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
-        disp = self._match(lg, rg, self._staging("disp", (n, H, ow), torch.int16, False), min_disparity)
+        dev, lg, rg = self._sbs_to_gray(frames, unsqueeze)
+        disp = self._match(lg, rg, self._staging("disp", tuple(lg.shape), torch.int16, False), min_disparity)
         if fill_holes:
             disp = self.fill_holes(disp)
         monos = None
-        out = self._staging("depth", (n, H, ow), torch.float32, False)
+        out = self._staging("depth", tuple(lg.shape), torch.float32, False)
         if mono_provider is not None:
             # a failing provider (DPT forward out of memory, bad shape ...) must not abort the clip -- nor, in a sharded run,
             # leave the other ranks waiting in the final barrier: warn and continue stereo-only like depth.py:367-369
@@ -265,38 +251,12 @@ class HipStereoBackend:
 
     def sbs_left_signatures(self, frames: List[np.ndarray], unsqueeze: bool):
         """SBS BGR frames -> the signatures of their left views: the staging and the gray split of sbs_to_disparity, no matcher"""
-        torch, nat = self.torch, self.native
-        n = len(frames)
-        H, W = frames[0].shape[:2]
-        ow = W if unsqueeze else W // 2
-        host = self._staging("sbs_host", (n, H, W, 3), torch.uint8, True)
-        hview = host.numpy()
-        for i, f in enumerate(frames):
-            hview[i] = f
-        dev = self._staging("sbs_dev", (n, H, W, 3), torch.uint8, False)
-        dev.copy_(host, non_blocking=True)
-        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
-        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
-        nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
-        return nat.frame_signature_batch(lg)
+        return self.native.frame_signature_batch(self._sbs_to_gray(frames, unsqueeze)[1])
 
     def sbs_left_profiles(self, frames: List[np.ndarray], unsqueeze: bool):
         """SBS BGR frames -> the column and row sums of their left views on the device (register.estimate): the staging and the
         gray split of sbs_left_signatures, then v3d_plane_profiles_batch"""
-        torch, nat = self.torch, self.native
-        n = len(frames)
-        H, W = frames[0].shape[:2]
-        ow = W if unsqueeze else W // 2
-        host = self._staging("sbs_host", (n, H, W, 3), torch.uint8, True)
-        hview = host.numpy()
-        for i, f in enumerate(frames):
-            hview[i] = f
-        dev = self._staging("sbs_dev", (n, H, W, 3), torch.uint8, False)
-        dev.copy_(host, non_blocking=True)
-        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
-        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
-        nat.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
-        return nat.plane_profiles_batch(lg)
+        return self.native.plane_profiles_batch(self._sbs_to_gray(frames, unsqueeze)[1])
 
     def match_scores(self, prof_a, prof_b, cand, bins):
         """profiles [K,na] and [K,nb] on the device, a host-side candidate list int64 [C,2] -> the records int64 [K,C,6] as NumPy
@@ -306,15 +266,7 @@ class HipStereoBackend:
     def signature_scores(self, sig_a, sig_b):
         """signatures [na,2304] x [nb,2304] on the device -> a handle for read_scores: one v3d_signature_scores call, then the
         three small integer arrays go to pinned memory without blocking; an event marks the end of the copies"""
-        torch = self.torch
-        host = []
-        for t in self.native.signature_scores(sig_a, sig_b):
-            h = torch.empty(tuple(t.shape), dtype=torch.int64, pin_memory=True)
-            h.copy_(t, non_blocking=True)
-            host.append(h)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev
+        return self._fetch_async(self.native.signature_scores(sig_a, sig_b))
 
     def guide_scores(self, rows, luma):
         """--check-guide: the kept signature rows of a batch's left views x the signatures of its 4K luma -> a read_scores handle"""
@@ -323,10 +275,7 @@ class HipStereoBackend:
     def read_scores(self, handle):
         """-> (num [na,nb], var_a [na], var_b [nb]) int64 NumPy.  After the stream's next synchronise the event has fired and
         nothing waits here"""
-        host, ev = handle
-        if not ev.query():
-            ev.synchronize()
-        return tuple(h.numpy().copy() for h in host)
+        return tuple(self._read(handle))
 
     # ---- quality report (quality.py; only called with --quality-report) ----
     def right_gray(self, n: int):
@@ -365,29 +314,17 @@ class HipStereoBackend:
     def quality_fetch(self, records):
         """device records -> a handle for read_quality: the small integer array goes to pinned memory without blocking, an event
         marks the end of the copy (as signature_scores does)"""
-        torch = self.torch
-        host = torch.empty(tuple(records.shape), dtype=torch.int64, pin_memory=True)
-        host.copy_(records, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev
+        return self._fetch_async([records])
 
     def read_quality(self, handle, wait: bool = True):
         """-> int64 NumPy records, or None when the copy has not finished and wait is False.  After the stream's next
         synchronise the event has fired and nothing waits here"""
-        host, ev = handle
-        if not ev.query():
-            if not wait:
-                return None
-            ev.synchronize()
-        return host.numpy().copy()
+        got = self._read(handle, wait)
+        return None if got is None else got[0]
 
     def depth_to_host(self, depth) -> np.ndarray:
-        """device float32 [n,H,W] -> NumPy through a pinned buffer"""
-        host = self._staging("depth_host", tuple(depth.shape), self.torch.float32, True)
-        host.copy_(depth, non_blocking=True)
-        self.torch.cuda.current_stream().synchronize()
-        return host.numpy().copy()
+        """device float32 [n,H,W] -> NumPy through a pinned block of its own (_fetch)"""
+        return self._fetch(depth)
 
     def normalise_u16(self, depth) -> np.ndarray:
         nat = self.native
@@ -442,22 +379,12 @@ class HipStereoBackend:
         """device u16 [n,H,W] -> NumPy uint16 [n,H,W] through pinned memory.  The pinned block comes from torch's caching host
         allocator and goes back to it once the writers drop the last frame of it: no allocation in the steady state, and no
         buffer is overwritten while a writer thread still encodes from it."""
-        torch = self.torch
-        host = torch.empty(tuple(u16.shape), dtype=torch.int16, pin_memory=True)
-        host.copy_(u16, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return host.numpy().view(np.uint16)
+        return self._fetch(u16).view(np.uint16)
 
     def png_streams_u16(self, u16):
         """--png-encoder gpu: device u16 samples (int16-viewed) [n,H,W] -> the zlib streams of their 16-bit PNGs, deflated on
         the device (png_gpu.DevicePngEncoder); only the streams cross PCIe"""
         return self._png_encoder().encode(u16)
-
-    def _png_encoder(self):
-        if getattr(self, "_png", None) is None:
-            from .png_gpu import DevicePngEncoder
-            self._png = DevicePngEncoder(self.torch, self.native, self.device)
-        return self._png
 
 
 class HybridStereoDepthExtractor:

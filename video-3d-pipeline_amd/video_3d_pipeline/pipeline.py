@@ -40,19 +40,15 @@ class HipPipelineBackend(HipStereoBackend):
         """4K BGR frames (None = beyond the clip: flat 128) -> device luma [n,height,width].  The frames are gathered in one
         pinned buffer of `capacity` frames and cross PCIe in one copy; the buffer is reused by the next call, which
         to_host_u16's synchronise has made safe."""
-        torch, nat = self.torch, self.native
+        torch = self.torch
         n = len(frames)
-        host = self._staging("guide_host", (capacity, height, width, 3), torch.uint8, True)
-        dev = self._staging("guide_dev", (capacity, height, width, 3), torch.uint8, False)
-        luma = self._staging("guide_luma", (capacity, height, width), torch.uint8, False)
-        hv = host.numpy()
-        for i, f in enumerate(frames):
-            if f is not None:
-                if f.shape[:2] != (height, width):
-                    raise ValueError(f"4K frame of shape {f.shape}, expected {height}x{width}")
-                hv[i] = f if f.ndim == 3 else f[..., None]      # a luma frame: gray of (g, g, g) is g exactly
-        dev[:n].copy_(host[:n], non_blocking=True)
-        nat.bgr_to_gray(dev[:n], luma[:n])
+        for f in frames:
+            if f is not None and f.shape[:2] != (height, width):
+                raise ValueError(f"4K frame of shape {f.shape}, expected {height}x{width}")
+        bgr = [f if f is None or f.ndim == 3 else f[..., None] for f in frames]      # a luma frame: gray of (g, g, g) is g exactly
+        dev = self._upload("guide", bgr, (height, width, 3), torch.uint8, capacity)
+        luma = self._staging("guide_luma", (max(n, capacity), height, width), torch.uint8, False)
+        self.native.bgr_to_gray(dev, luma[:n])
         for i, f in enumerate(frames):
             if f is None:
                 luma[i].fill_(128)                              # beyond the 4K clip: flat guide, as upscale.py does
@@ -66,7 +62,7 @@ class HipPipelineBackend(HipStereoBackend):
         for j0 in range(0, len(frames), GUIDE_BATCH):
             chunk = frames[j0:j0 + GUIDE_BATCH]
             self.native.frame_signature_batch(self.guide_luma(chunk, height, width, GUIDE_BATCH), out[j0:j0 + len(chunk)])
-            torch.cuda.current_stream().synchronize()
+            self._synchronize()
         return out
 
     def guide_profiles(self, frames, height, width):
@@ -77,7 +73,7 @@ class HipPipelineBackend(HipStereoBackend):
         for j0 in range(0, len(frames), GUIDE_BATCH):
             chunk = frames[j0:j0 + GUIDE_BATCH]
             c, r = self.native.plane_profiles_batch(self.guide_luma(chunk, height, width, GUIDE_BATCH))
-            torch.cuda.current_stream().synchronize()
+            self._synchronize()
             cols.append(c)
             rows.append(r)
         return torch.cat(cols), torch.cat(rows)
@@ -95,12 +91,7 @@ class HipPipelineBackend(HipStereoBackend):
         """--stereo-output: the 4K BGR frames guide_luma left in its device staging + their u16 4K depth [n,Hhi,Whi] (device)
         -> NumPy packed frames [n,outH,outW,3] (convert.output_size): one launch, one D2H, no second H2D of the 4K frames.  Slots of frames
         that had no 4K frame hold stale data; the caller drops them.  subpixel: the sub-pixel renderer (--subpixel)."""
-        torch = self.torch
-        out = self._render_stereo_dev(u16_4k, gains, layout, subpixel)
-        host = torch.empty(tuple(out.shape), dtype=torch.uint8, pin_memory=True)
-        host.copy_(out, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return host.numpy()
+        return self._fetch(self._render_stereo_dev(u16_4k, gains, layout, subpixel))
 
     def _render_stereo_dev(self, u16_4k, gains, layout, subpixel=False):
         torch, nat = self.torch, self.native

@@ -18,6 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
+from .backend import HipBackend
 from .utils import PngWriterPool, get_video_info, iter_frames, prefetch_map, read_png16
 
 GUIDED_RADIUS = 8       # at 4K; the reference specifies nothing
@@ -46,15 +47,7 @@ def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height
             "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"}, indent=1))
 
 
-class HipUpscaleBackend:
-    def __init__(self, device: str = "cuda"):
-        import torch
-        from . import _native
-        if not torch.cuda.is_available():
-            raise RuntimeError("CUDA not available but requested")
-        _native.lib()
-        self.torch, self.native, self.device = torch, _native, _native.resolve_device(device)   # bare "cuda" = the current device
-
+class HipUpscaleBackend(HipBackend):
     def to_luma(self, frame_bgr):
         d = frame_bgr if self.torch.is_tensor(frame_bgr) else self.native.to_device(frame_bgr, self.device)
         return d if d.dim() == 2 else self.native.bgr_to_gray(d.contiguous())
@@ -73,11 +66,8 @@ class HipUpscaleBackend:
 
     def upscale_png(self, depth_lo, guide, r, eps):
         """--png-encoder gpu: upscale_u16 whose samples stay on the device and come back as the zlib stream of their PNG"""
-        if getattr(self, "_png", None) is None:
-            from .png_gpu import DevicePngEncoder
-            self._png = DevicePngEncoder(self.torch, self.native, self.device)
         q = self.upscale(depth_lo, guide, r, eps)
-        return self._png.encode(self.native.round_to_u16(q.contiguous())[None])[0]
+        return self._png_encoder().encode(self.native.round_to_u16(q.contiguous())[None])[0]
 
     def warp_u16(self, depth_u16: np.ndarray, q, size):
         """the u16 samples of a depth PNG -> the same samples in the 4K frame's framing as device float32 [size[1],size[0]]
