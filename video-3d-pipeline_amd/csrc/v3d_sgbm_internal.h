@@ -70,7 +70,11 @@ __device__ __forceinline__ uint32_t wta_word(int minS, int d16, int best) { retu
 __device__ __forceinline__ int wta_d16(uint32_t w) { return (int)((w >> 6) & 0x7FFu) - 16; }
 
 // k_vdd's edge granules: [frame][strip][2 directions][VDD_RING rows][VDD_GRAN] of 8 bytes
-#define VDD_RING 4
+// Ring depth.  A strip reads its neighbour's row r - 2 in its own row r (k_vdd, "row cycle").  Strip B writes row r only
+// after its poll of A's row r - 2 has returned; A published that row in its own iteration r - 2, after that iteration's poll
+// of B's row r - 4 had returned (poll and publish are the same wave's, in program order).  So when B overwrites a slot with
+// row r, A has finished with B's rows <= r - 4 and rows r - 3 .. r are live: 4 slots suffice.  8 is twice that.
+#define VDD_RING 8
 #define VDD_GRAN 34                      // granules per edge per row: 32 data dwords + delta (+1 pad)
 
 // ------------------------------------------------------------------------------------------------

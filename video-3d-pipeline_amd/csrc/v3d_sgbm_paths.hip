@@ -466,9 +466,25 @@ __global__ __launch_bounds__(256, 8) void k_hscan(ChainArgs a, uint32_t* __restr
 // workgroup (1024 threads = 16 waves, 16 lanes x 4 disparities per pixel) owns a strip of 64 columns of
 // one frame and marches down the rows in LOCK-STEP with its two neighbour strips:
 //   * inside the strip the previous row's (L1, L3) state is exchanged through LDS (one barrier per row);
-//   * across strips the edge columns' state travels through global memory as 8-byte {data, tag} granules
-//     (relaxed agent-scope atomic stores / loads: sc1, served by L2, no fences -- MI355X_MICROARCH
-//     "handoff-1to1"), tag = (call sequence << 12) | (row + 1), 4-row ring per strip edge (stays in L2).
+//   * across strips the state of the column NEXT TO each edge column travels through global memory as 8-byte
+//     {data, tag} granules (relaxed agent-scope atomic stores / loads: sc1, served by L2, no fences --
+//     MI355X_MICROARCH "handoff-1to1"), tag = (call sequence << 12) | (row + 1), 8-row ring per strip edge
+//     (VDD_RING; stays in L2).
+// Row cycle.  Strip A's first pixel (column xs) needs L1(xs-1, y-1), a column of its left neighbour B.  If B published
+// that column, A's row y would wait for B's row y-1 and B's row y for A's row y-1: one 2.7-us hop in every row's
+// dependency cycle.  Instead B publishes the column before it, L1 and delta of (xs-2, y), and A's edge lanes form
+//   L1(xs-1, y-1) = chain_step(L1(xs-2, y-2), delta1(xs-2, y-2), C(xs-1, y-1))
+// themselves: B's own inputs, so B's bits.  Mirrored for L3 at the right edge (B's pixel 1, after the ragged rule: a
+// last strip of one in-image column publishes (0, P2), the out-of-image state).  A's row y now waits for B's row y-2
+// and B's row y for A's row y-2: one hop per TWO rows, a strip may run two rows ahead of a neighbour, and the granule
+// an edge wave wants is a whole row period old.  That is what pays: the wave fetches it during the row BEFORE, one
+// granule per lane, right after its own publish, so the L2 round trip runs behind the vertical step and the barrier
+// and the row starts with a tag compare, not with a poll (measured: the rebuilt column with the poll still at the
+// start of the row is 3 % SLOWER than the one-row hand-off, 3.27 -> 3.37 ms per 34 frames; with the early fetch
+// 3.27-3.38 -> 3.16-3.21 ms.  Merging the rebuilt column into p1 / p3 in registers instead of through the LDS halo
+// slot: 64 VGPRs and back to 3.24-3.32 ms).  Rows 0 and 1 start from the out-of-image state and poll nothing; a
+// row is published only if a row y+2 exists.  Price: one more chain step per row on wave 0 / wave 15 and a 12-byte
+// (8 at 4 disparities per lane) C fetch per edge lane, queued one row ahead.
 // The coupling is bidirectional (strip k waits for k-1 AND k+1), so the strips of ONE FRAME must be co-resident;
 // frames are independent.  Workgroups are dispatched in blockIdx order (per XCD, each XCD taking every 8th), so the
 // resident set is always a prefix of the grid = whole frames plus at most one partial frame per XCD skew, and a
@@ -480,8 +496,8 @@ __global__ __launch_bounds__(256, 8) void k_hscan(ChainArgs a, uint32_t* __restr
 //  scatters neighbour strips over the XCDs and costs 3.38 -> 4.56 ms per 30 frames, like the XCD-contiguous order below;
 //  the hardware's own blockIdx -> XCD round-robin, neighbours on adjacent XCDs, is the fast placement.)
 // ------------------------------------------------------------------------------------------------
-// poll budget of one lane over the whole pass (every poll round is one L2 round trip, ~1 us): a healthy pass spends one
-// to three rounds per row, so 64 per row + slack is two orders of magnitude of headroom and still bounds a pass whose
+// poll budget of an edge wave over the whole pass (every poll round is one L2 round trip, ~1 us): a healthy pass spends
+// none to three rounds per row, so 64 per row + slack is two orders of magnitude of headroom and still bounds a pass whose
 // neighbours never become resident to ~0.1 s at 1080 rows (it was 2^20 rounds, i.e. seconds)
 #define VDD_SPIN_PER_ROW 64
 #define VDD_SPIN_SLACK 4096
@@ -497,29 +513,11 @@ struct VddArgs {
     int xcd;                            // 1: XCD-contiguous strip order, co-resident launches only (launch_vdd).  Measured slower (3.48 -> 4.58 ms per 30 frames): off
 };
 
-// wait for N data granules (+ the delta granule if want_d) of one row: all loads of a poll round go out together
-// (one L2 round trip per round, not one per granule); bounded by `budget`
-template <int N>
-__device__ __forceinline__ bool vdd_poll_n(const unsigned long long* g, const unsigned long long* gd, bool want_d,
-                                           uint32_t tag, uint32_t (&v)[N], uint32_t& vd, int& budget)
+// one {data, tag} granule.  An edge wave fetches a row's 33 granules one per lane: a single load instruction per poll
+// round (one L2 round trip), two registers to hold the row
+__device__ __forceinline__ unsigned long long vdd_get(const unsigned long long* g)
 {
-    for (;;) {
-        unsigned long long x[N], xd = (unsigned long long)tag << 32;
-#pragma unroll
-        for (int i = 0; i < N; i++) x[i] = __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (want_d) xd = __hip_atomic_load(gd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool ok = (uint32_t)(xd >> 32) == tag;
-#pragma unroll
-        for (int i = 0; i < N; i++) ok = ok && ((uint32_t)(x[i] >> 32) == tag);
-        if (ok) {
-#pragma unroll
-            for (int i = 0; i < N; i++) v[i] = (uint32_t)x[i];
-            if (want_d) vd = (uint32_t)xd;
-            return true;
-        }
-        if (--budget < 0) return false;
-        __builtin_amdgcn_s_sleep(1);
-    }
+    return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void vdd_put(unsigned long long* g, uint32_t v, uint32_t tag)
 {
@@ -596,6 +594,15 @@ __global__ __launch_bounds__(1024, 8) void k_vdd(VddArgs a)      // 8 waves/SIMD
     // branch tests.  Every wave still executes one barrier per row.
     auto rows = [&](auto edge_tag) {
     constexpr bool EDGE = decltype(edge_tag)::value;
+    // an edge wave is wave 0 or wave 15, never both, so one halo step per row serves either side
+    const bool halo_lane = edge_l ? lane_l : lane_r;               // the lanes that rebuild the neighbour's edge column
+    const bool pub_l = lane / LPP == 1, pub_r = lane / LPP == PPW - 2;   // pixel 1's L3 goes left, pixel PXS - 2's L1 goes right
+    const unsigned long long* gin = edge_l ? gleft : gright;
+    const ptrdiff_t halo_off = edge_l ? -(ptrdiff_t)C_PXB : (ptrdiff_t)C_PXB;   // column x0 - 1 / x0 + PXS, seen from the edge pixel
+    const bool gran_lane = lane <= 32;                             // a row's 32 data granules + delta, one per lane
+    typename CRaw<DPL>::type hq = {};                              // the halo column's C of the row before the current one
+    unsigned long long gq = 0;                                     // the neighbour's granule of the row before that
+    if constexpr (EDGE) if (halo_lane) hq = c_load<DPL, true>(Cp + c_row(rowy(0), W1) + halo_off);
     for (int y0 = 0; y0 < H; y0 += PF) {
 #pragma unroll
         for (int j = 0; j < PF; j++) {
@@ -603,8 +610,39 @@ __global__ __launch_bounds__(1024, 8) void k_vdd(VddArgs a)      // 8 waves/SIMD
             if (y < H) {                                           // uniform
                 const int prev = (y + 1) & 1, cur = y & 1;         // buffer holding row y-1 / receiving row y
                 __syncthreads();                                   // row y-1 of the whole strip is in buffer `prev`
-                // ---- 1. predecessors: strip neighbours from LDS; the two edge pixels take theirs from the neighbour
-                //         strips' granules, polled AFTER the barrier so the other 14 waves compute meanwhile ----
+                // ---- 0. edge waves: the neighbour's edge column of row y-1, rebuilt here from what the neighbour published of
+                //         row y-2 -- a whole row period old, so it was fetched during row y-1 -- and the halo column's C of
+                //         row y-1: one chain step, same inputs and so same bits as the neighbour's own.  After the barrier, so
+                //         the other 14 waves compute meanwhile.  The result goes into the strip's LDS halo slot (slot 0 / PXS + 1
+                //         of `prev`, which no other wave touches) and is read back below like any other predecessor: nothing
+                //         of this step is live when the three regular steps start ----
+                if constexpr (EDGE) if (y > 0) {
+                    uint32_t hp[NP], hd = P2pk, hv[NP], hL[NP];
+#pragma unroll
+                    for (int i = 0; i < NP; i++) hp[i] = 0u;       // rows 0 and -1 of every column: the out-of-image state
+                    if (y > 1) {
+                        // the row's 33 granules sit one per lane in `gq`, fetched during row y-1: only a wave that runs ahead
+                        // of its neighbour finds a stale tag and polls
+                        const uint32_t tag = (a.seq << 12) | (uint32_t)(y - 1);        // row y-2 carries tag (y-2)+1
+                        const unsigned long long* g = gin + ((y - 2) & (VDD_RING - 1)) * VDD_GRAN + lane;
+                        while (__builtin_amdgcn_ballot_w64(gran_lane && (uint32_t)(gq >> 32) != tag)) {      // wave-uniform
+                            if (--budget < 0) { failed = failed || lane == 0; budget = 0; break; }
+                            __builtin_amdgcn_s_sleep(1);
+                            if (gran_lane) gq = vdd_get(g);
+                        }
+#pragma unroll
+                        for (int i = 0; i < NP; i++) hp[i] = (uint32_t)__builtin_amdgcn_ds_bpermute((NP * dl + i) * 4, (int)(uint32_t)gq);
+                        hd = (uint32_t)__builtin_amdgcn_ds_bpermute(32 * 4, (int)(uint32_t)gq);
+                    }
+                    vec_unpack<NP>(c_unpack(hq, dl, P2pk), hv);
+                    if (halo_lane) hq = c_load<DPL, true>(Cp + c_row(rowy(y), W1) + halo_off);    // for row y+1
+                    const uint32_t hnd = chain_step<NP, LPP>(hp, hd, hv, hL, P1pk, P2pk, first_lane, last_lane);
+                    if (halo_lane) {
+                        if (edge_l) { sL1[prev][0][dl] = Packer<NP>::go(hL); if (dl == 0) sDl[prev][0].x = hnd; }
+                        else { sL3[prev][PXS + 1][dl] = Packer<NP>::go(hL); if (dl == 0) sDl[prev][PXS + 1].y = hnd; }
+                    }
+                }
+                // ---- 1. predecessors: row y-1 of the columns x-1 and x+1 from LDS ----
                 uint32_t cv[NP], p1[NP], p3[NP];
                 uint32_t sold[NP];
                 // (12-bit C: unpacking the NEXT row at the end of this one, off the path between the barrier and the recurrences
@@ -617,22 +655,6 @@ __global__ __launch_bounds__(1024, 8) void k_vdd(VddArgs a)      // 8 waves/SIMD
                 vec_unpack<NP>(sL1[prev][px][dl], p1);             // column x-1 (slot px holds pixel px-1)
                 vec_unpack<NP>(sL3[prev][px + 2][dl], p3);         // column x+1
                 uint32_t d1 = sDl[prev][px].x, d3 = sDl[prev][px + 2].y;
-                if constexpr (EDGE) if (y > 0) {
-                    const uint32_t tag = (a.seq << 12) | (uint32_t)y;          // row y-1 carries tag (y-1)+1
-                    const int slot = (y - 1) & (VDD_RING - 1);
-                    if (edge_l) if (lane_l) {                       // my pixel 0: column x0 - 1 lives in the left strip
-                        const unsigned long long* g = gleft + slot * VDD_GRAN;
-                        uint32_t vd = P2pk;
-                        if (!vdd_poll_n<NP>(g + NP * dl, g + 32, true, tag, p1, vd, budget)) { failed = true; budget = 0; }
-                        d1 = vd;
-                    }
-                    if (edge_r) if (lane_r) {                       // my last pixel: column x0 + PXS lives in the right strip
-                        const unsigned long long* g = gright + slot * VDD_GRAN;
-                        uint32_t vd = P2pk;
-                        if (!vdd_poll_n<NP>(g + NP * dl, g + 32, true, tag, p3, vd, budget)) { failed = true; budget = 0; }
-                        d3 = vd;
-                    }
-                }
                 // ---- 2. the two diagonal recurrences first: their edge values are what the neighbour strips wait for ----
                 uint32_t L1[NP], L2[NP], L3[NP];
                 uint32_t nd1 = chain_step<NP, LPP>(p1, d1, cv, L1, P1pk, P2pk, first_lane, last_lane);
@@ -643,16 +665,16 @@ __global__ __launch_bounds__(1024, 8) void k_vdd(VddArgs a)      // 8 waves/SIMD
                     nd1 = nd3 = P2pk;
                 }
                 // ---- 3. publish row y as early as possible: granules for the neighbours, LDS for the strip ----
-                if constexpr (EDGE) if (y + 1 < H) {
+                if constexpr (EDGE) if (y + 2 < H) {               // row y is read by the neighbours' row y + 2
                     const uint32_t tag = (a.seq << 12) | (uint32_t)(y + 1);
                     const int slot = y & (VDD_RING - 1);
-                    if (edge_r) if (lane_r) {                       // my last column's L1 goes right
+                    if (edge_r) if (pub_r) {                        // L1 of the column before my last goes right
                         unsigned long long* g = gme + (size_t)(1 * VDD_RING + slot) * VDD_GRAN;
 #pragma unroll
                         for (int i = 0; i < NP; i++) vdd_put(g + NP * dl + i, L1[i], tag);
                         if (dl == 0) vdd_put(g + 32, nd1, tag);
                     }
-                    if (edge_l) if (lane_l) {                       // my first column's L3 goes left
+                    if (edge_l) if (pub_l) {                        // L3 of the column after my first goes left
                         unsigned long long* g = gme + (size_t)(0 * VDD_RING + slot) * VDD_GRAN;
 #pragma unroll
                         for (int i = 0; i < NP; i++) vdd_put(g + NP * dl + i, L3[i], tag);
@@ -662,6 +684,9 @@ __global__ __launch_bounds__(1024, 8) void k_vdd(VddArgs a)      // 8 waves/SIMD
                 sL1[cur][px + 1][dl] = Packer<NP>::go(L1);
                 sL3[cur][px + 1][dl] = Packer<NP>::go(L3);
                 if (dl == 0) sDl[cur][px + 1] = make_uint2(nd1, nd3);
+                // the neighbour's row y-1, which row y+1 will want: published about one row period ago, fetched behind the
+                // vertical step and the barrier instead of after it
+                if constexpr (EDGE) if (y > 0 && y + 1 < H) if (gran_lane) gq = vdd_get(gin + ((y - 1) & (VDD_RING - 1)) * VDD_GRAN + lane);
                 // ---- 4. the vertical recurrence and the sum ----
                 const uint32_t nd2 = chain_step<NP, LPP>(p2, d2, cv, L2, P1pk, P2pk, first_lane, last_lane);
 #pragma unroll
