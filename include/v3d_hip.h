@@ -26,6 +26,8 @@
  *   v3d_render_stereo_subpixel_batch  the same step in 1/16 pixel with interpolated colours (convert.py --subpixel)
  *   v3d_render_stereo_packed_batch  the same step with the eyes packed top-bottom, row-interleaved or as a red-cyan anaglyph
  *                          (convert.py --layout), the output formats VisionDepth3D offers there
+ *   v3d_render_stereo_source_batch  no call site in the reference: the same step with the disocclusions taken from the stored eye
+ *                          of the SBS frame the depth was computed from (convert.py --fill-from-source)
  *   v3d_temporal_*, v3d_depth_minmax_batch, v3d_depth_to_u16_range_batch  no call site in the reference (it normalises every
  *                          frame on its own, depth.py:397-406): opt-in temporal stabilisation of the depth sequence
  *   v3d_depth_robust_minmax_batch  no call site in the reference either: opt-in percentile white point of that normalisation
@@ -49,7 +51,7 @@
  *  - memory contract (tests/test_abi_guard_gpu.py holds every entry to it): a typed pointer needs only the natural alignment
  *    of its element type and a `void* ws` 16 bytes, unless the entry's comment says otherwise, and an entry that needs more
  *    refuses with V3D_ERR_ARG; rows are `pitch` bytes apart and only the payload of a row is read, with one exception:
- *    v3d_fill_holes_disp16_batch and v3d_render_stereo[_subpixel|_packed]_batch load the aligned 16-byte blocks that hold a row's payload,
+ *    v3d_fill_holes_disp16_batch and v3d_render_stereo[_subpixel|_packed|_source]_batch load the aligned 16-byte blocks that hold a row's payload,
  *    so they touch up to 15 bytes on either side of a frame (never a block that holds no payload byte of the input, and no value
  *    from outside the payload reaches a result): an input of theirs must be readable up to those block borders, as every device
  *    allocation is (tests/test_stereo_emulated.py, tests/test_fill_emulated.py).  v3d_median3x3_i16, v3d_filter_speckles and
@@ -378,6 +380,33 @@ int v3d_render_stereo_packed_batch(const uint8_t* frame_bgr, size_t frame_stride
                                    size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
                                    int convergence, int subpixel /* 0 | 1 */, int packing /* V3D_PACK_* */,
                                    uint8_t* out_bgr /* dense [n][outH][outW][3] */, void* stream);
+
+/* Source fill (v3d_stereo.hip): v3d_render_stereo_packed_batch, except that a hole takes its colour from the stored eye of the SBS
+   frame the depth was computed from, not from the background.  Frame f's SBS image at sbs_bgr + f*sbs_stride (bytes), Hs rows
+   `pitch` bytes apart, Ws BGR pixels each; We = Ws / 2 and eye e's column i is SBS column e*We + i (S below: that eye's plane).
+   Eye plane P(e) at target (t, y), all integers, 64-bit coordinates:
+     u = clamp(ax t + bx, 0, (We - 1) << 16), v = clamp(ay y + by, 0, (Hs - 1) << 16);
+     i0 = u >> 16, i1 = min(i0 + 1, We - 1), fx = (u >> 8) & 255; j0, j1, fy from v in the same way; per channel
+     P = ((256 - fy) ((256 - fx) S[j0][i0] + fx S[j0][i1]) + fy ((256 - fx) S[j1][i0] + fx S[j1][i1]) + 32768) >> 16
+   (v3d_warp_u16_batch's arithmetic with the coordinates clamped to the eye in place of a fill value: no tap leaves its eye's half).
+   Render: the shift, the z-buffer and the sub-pixel span scatter are unchanged.  In an eye whose bit is set in fill_eyes (bit 0 the
+   left eye, bit 1 the right) a target with Z[t] == 0 takes P(eye)[y][t]; an eye whose bit is clear fills as before; the packings and
+   the anaglyph matrices apply to the eye colours afterwards.  fill_eyes = 0 is v3d_render_stereo_packed_batch bit for bit (its
+   kernels are launched) and sbs_bgr may then be null.  Bit-exact contract: tests/stereo_source_ref.py.
+   Memory contract: that of v3d_render_stereo_packed_batch for the frame, the depth and out_bgr.  The SBS frames are read byte by
+   byte, by hole targets only: nothing but the 3 Ws payload bytes of a row is touched, no 16-byte block around them, and sbs_bgr
+   needs no alignment.  No allocation, no synchronisation, one launch.
+   V3D_ERR_ARG: everything v3d_render_stereo_packed_batch refuses; a null sbs_bgr with fill_eyes != 0; Ws odd or < 2; Hs < 1;
+   pitch < 3 Ws; sbs_stride < Hs*pitch with n > 1; fill_eyes outside 0 .. 3; ax or ay outside [2^12, 2^20]; |bx| or |by| above 2^40.
+   V3D_ERR_UNSUPPORTED: W > 8192 or We > 8192, looked at after every V3D_ERR_ARG above (a call that is wrong in both ways returns
+   V3D_ERR_ARG).  Hs has no bound of its own: v, j0 and j1 are 64-bit in the kernel too, so (Hs - 1) << 16 may pass 2^31.
+   A refused call enqueues nothing. */
+int v3d_render_stereo_source_batch(const uint8_t* frame_bgr, size_t frame_stride /* bytes */, const uint16_t* depth,
+                                   size_t depth_stride /* elements */, int n, int W, int H, int gain_left, int gain_right,
+                                   int convergence, int subpixel /* 0 | 1 */, int packing /* V3D_PACK_* */,
+                                   const uint8_t* sbs_bgr, size_t sbs_stride /* bytes */, int Ws, int Hs, int pitch,
+                                   int fill_eyes /* bit 0: left eye, bit 1: right eye */, int64_t ax, int64_t bx, int64_t ay,
+                                   int64_t by, uint8_t* out_bgr /* dense [n][outH][outW][3] */, void* stream);
 
 /* Temporal depth stabilisation (v3d_temporal.hip, its integer arithmetic v3d_temporal_math.h): an opt-in stage between the
    disparity and the u16 normalisation.  A buffer holds T frames: depth f32 (frame u at depth + u*depth_stride elements; <= 0 invalid) and left gray u8 (frame u at gray +

@@ -28,6 +28,12 @@
 // top-bottom, row-interleaved or as a red-cyan anaglyph before the store; colours that must wait for the other eye or the next
 // row wait in LDS words only their thread touches.
 // Contract: tests/stereo_pack_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Output packings".
+//
+// Source fill (v3d_render_stereo_source_batch): the same march, entered with one more kernel argument (StSource).  A hole of an
+// eye whose fill bit is set takes the bilinear sample of the film's own stored eye at its target instead of the background: four
+// byte-wise global loads per channel, issued by the hole targets only (a few percent of a row); the eye plane is a few MB and
+// stays in L2, so it costs neither LDS nor a 4K plane through HBM.  The row's j0, j1, fy are workgroup-uniform.
+// Contract: tests/stereo_source_ref.py (bit-exact).  Resources and measured numbers: DESIGN.md §4, "Source-faithful 3D".
 #include "v3d_common.h"
 #include "v3d_wave.h"
 
@@ -168,6 +174,33 @@ __device__ __forceinline__ uint32_t st_anaglyph(uint32_t l, uint32_t r, int dubo
     return (uint32_t)min(max(B, 0), 255) | ((uint32_t)min(max(Gn, 0), 255) << 8) | ((uint32_t)min(max(R, 0), 255) << 16);
 }
 
+// source fill: the SBS frames whose stored eyes the holes are sampled from, and the Q16 map from a target to eye coordinates
+struct StSource {
+    const uint8_t* sbs;
+    size_t stride;                                             // bytes between frames
+    int We, Hs, pitch, fill;                                   // eye width (Ws / 2), rows, row pitch, bit e: eye e's holes
+    long long ax, bx, ay, by;
+};
+
+__device__ __forceinline__ const StSource& st_source(const StSource& s) { return s; }
+
+// eye plane P at target t, from the eye's rows j0 and j1 (r0, r1: their first byte of this eye) and the row's fy; the taps
+// stay inside the eye's We columns, 16-bit products and a sum below 2^24 + 2^15
+__device__ __forceinline__ uint32_t st_source_colour(const uint8_t* r0, const uint8_t* r1, int fy, int t, const StSource& S)
+{
+    const long long um = (long long)(S.We - 1) << 16, ul = S.ax * t + S.bx;
+    const int u = (int)(ul < 0 ? 0 : ul > um ? um : ul);
+    const int i0 = u >> 16, i1 = min(i0 + 1, S.We - 1), fx = (u >> 8) & 255;
+    uint32_t c = 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const uint32_t top = (uint32_t)((256 - fx) * r0[3 * i0 + ch] + fx * r0[3 * i1 + ch]);
+        const uint32_t bot = (uint32_t)((256 - fx) * r1[3 * i0 + ch] + fx * r1[3 * i1 + ch]);
+        c |= (((256 - fy) * top + fy * bot + 32768u) >> 16) << (8 * ch);
+    }
+    return c;
+}
+
 // the march's LDS.  Side by side: dynamic, sized per launch for the row's W (launch_stereo), the file's one dynamic declaration,
 // which the host emulator rewrites.  The packings: static, sized for the widest row of PPT pixels per thread plus what K parks
 // (st_park_bytes); 8 WP of it do not depend on W anyway.
@@ -185,16 +218,18 @@ __device__ __forceinline__ unsigned char* st_smem()
 
 }  // namespace
 
-// The march, once, for all three entries.  SUB selects the sub-pixel scatter and gather.  K says what becomes of the eye colours:
+// The march, once, for all four entries.  SUB selects the sub-pixel scatter and gather.  K says what becomes of the eye colours:
 // ST_K_SBS stores them side by side (mode: half SBS) from step 4, the other K go through step 5 (mode: ST_K_ANA: Dubois), and the
 // row-interleaved frame skips the eye a row does not show (eye_on; for every other K it folds away).  K selects by if constexpr,
 // so an instantiation is compiled from its own statements alone, and its machine code is pinned (tools/kernel_digest.py;
 // DESIGN.md §4, "Output packings", One march): a few declarations below stand where they do because moving them moves it.
-template <int PPT, bool SUB, int K>
+// SRC is empty, or StSource: the source fill's one more kernel argument.  Its statements stand under if constexpr (sizeof...(SRC)),
+// so the instantiations without it are compiled from what they had.
+template <int PPT, bool SUB, int K, class... SRC>
 __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __restrict__ frame, size_t frame_stride,
                                                               const uint16_t* __restrict__ depth, size_t depth_stride, int W, int H,
                                                               int gl, int gr, int conv, int mode, uint8_t* __restrict__ out,
-                                                              int sd_bytes)
+                                                              int sd_bytes, SRC... src)
 {
     using G = StGeom<PPT>;
     constexpr int WP = G::WP, ND = G::ND, NF = G::NF;
@@ -326,9 +361,21 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
         const int nvalid = min(PPT, W - x0);                   // <= 0: this thread's run lies beyond the row
         [[maybe_unused]] uint8_t* orow = K != ST_K_SBS ? nullptr : out + ((size_t)f * H + y) * (size_t)outW * 3;
         const unsigned char* frow = sF + foff;
+        [[maybe_unused]] const uint8_t *er0 = nullptr, *er1 = nullptr;     // source fill: the SBS rows j0, j1 of this output row
+        [[maybe_unused]] int efy = 0;
+        if constexpr (sizeof...(SRC) > 0) {
+            const StSource& S = st_source(src...);
+            // v stays 64 bits wide: Hs has no bound but int's, so (Hs - 1) << 16 may pass 2^31 (u may not: We <= ST_MAX_W)
+            const long long vm = (long long)(S.Hs - 1) << 16, vl = S.ay * y + S.by;
+            const long long v = vl < 0 ? 0 : vl > vm ? vm : vl;
+            const int j0 = (int)(v >> 16), j1 = min(j0 + 1, S.Hs - 1);
+            const uint8_t* eb = S.sbs + (size_t)f * S.stride;
+            er0 = eb + (size_t)j0 * S.pitch; er1 = eb + (size_t)j1 * S.pitch; efy = (int)(v >> 8) & 255;
+        }
         for (int e = 0; e < 2; ++e) {
             if (!eye_on(e, y)) continue;
             uint32_t kk[PPT], col[PPT];
+            [[maybe_unused]] uint32_t holes = 0;               // source fill: bit i: target x0 + i has no key
             const uint4* zr = reinterpret_cast<const uint4*>(sZ + e * WP + x0);
 #pragma unroll
             for (int q = 0; q < PPT / 4; ++q) {
@@ -359,6 +406,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
                     if ((hit >> i) & 1u) { na = kk[i]; nac = col[i]; }
                     else if (na && (!kk[i] || (na >> 16) <= (kk[i] >> 16))) col[i] = nac;      // st_fill's choice
                 }
+                if constexpr (sizeof...(SRC) > 0) holes = ~hit;
             } else {
                 uint32_t rb[PPT];
 #pragma unroll
@@ -371,6 +419,27 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
                     const int s = k ? (int)(k & 0xFFFFu) - 1 : 0;
                     const unsigned char* px = frow + 3 * s;
                     col[i] = k ? ((uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16)) : 0u;
+                    if constexpr (sizeof...(SRC) > 0) holes |= (kk[i] ? 0u : 1u) << i;
+                }
+            }
+            if constexpr (sizeof...(SRC) > 0) {                // holes of a filled eye: the stored eye's colour at the target
+                const StSource& S = st_source(src...);
+                if ((S.fill >> e) & 1) {
+                    // four targets per step of a loop that stays a loop: unrolled over the run, the loads of all PPT targets are
+                    // scheduled together and the widest instantiations spill.  col[] is indexed by selects, not by q
+                    const int eo = 3 * e * S.We;
+                    holes &= nvalid >= PPT ? ~0u : nvalid > 0 ? (1u << nvalid) - 1u : 0u;
+#pragma unroll 1
+                    for (int q = 0; q < PPT / 4; ++q) {
+                        const uint32_t h4 = (holes >> (4 * q)) & 15u;
+                        if (!h4) continue;
+                        uint32_t c4[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) c4[j] = st_source_colour(er0 + eo, er1 + eo, efy, x0 + 4 * q + j, S);
+#pragma unroll
+                        for (int i = 0; i < PPT; ++i)
+                            if ((i >> 2) == q && ((h4 >> (i & 3)) & 1u)) col[i] = c4[i & 3];
+                    }
                 }
             }
             if constexpr (K == ST_K_SBS) {                     // side by side: store from here, statements kept as they were
@@ -438,13 +507,13 @@ __global__ __launch_bounds__(ST_THREADS) void k_render_stereo(const uint8_t* __r
     }
 }
 
-template <int PPT, bool SUB, int K>
+template <int PPT, bool SUB, int K, class... SRC>
 static int launch_stereo(const uint8_t* frame, size_t frame_stride, const uint16_t* depth, size_t depth_stride, int n, int W,
-                         int H, int gl, int gr, int conv, int mode, uint8_t* out, hipStream_t stream)
+                         int H, int gl, int gr, int conv, int mode, uint8_t* out, hipStream_t stream, SRC... src)
 {
     using G = StGeom<PPT>;
     const int sd = st_chunks(2 * W, 14) * 16, sf = st_chunks(3 * W, 15) * 16;
-    auto* kernel = k_render_stereo<PPT, SUB, K>;
+    auto* kernel = k_render_stereo<PPT, SUB, K, SRC...>;
     if constexpr (K == ST_K_SBS) {                             // dynamic LDS (st_smem); the packings' is static
         static bool attr_set = false;                          // per instantiation; the attribute is a property of the function
         if (!attr_set) {
@@ -455,16 +524,16 @@ static int launch_stereo(const uint8_t* frame, size_t frame_stride, const uint16
     }
     const int smem = K == ST_K_SBS ? 8 * G::WP + sd + sf : 0;
     hipLaunchKernelGGL(kernel, dim3(v3d_cdiv(H, ST_BAND), n), dim3(ST_THREADS), smem, stream, frame, frame_stride, depth,
-                       depth_stride, W, H, gl, gr, conv, mode, out, sd);
+                       depth_stride, W, H, gl, gr, conv, mode, out, sd, src...);
     V3D_LAUNCH_CHECK();
     return V3D_OK;
 }
 
-template <int PPT, bool SUB>
+template <int PPT, bool SUB, class... SRC>
 static int launch_packing(int packing, const uint8_t* frame, size_t frame_stride, const uint16_t* depth, size_t depth_stride, int n,
-                          int W, int H, int gl, int gr, int conv, uint8_t* out, hipStream_t s)
+                          int W, int H, int gl, int gr, int conv, uint8_t* out, hipStream_t s, SRC... src)
 {
-#define ST_LAUNCH(K, mode) launch_stereo<PPT, SUB, K>(frame, frame_stride, depth, depth_stride, n, W, H, gl, gr, conv, mode, out, s)
+#define ST_LAUNCH(K, mode) launch_stereo<PPT, SUB, K>(frame, frame_stride, depth, depth_stride, n, W, H, gl, gr, conv, mode, out, s, src...)
     switch (packing) {
     case V3D_PACK_FULL_SBS: return ST_LAUNCH(ST_K_SBS, 0);
     case V3D_PACK_HALF_SBS: return ST_LAUNCH(ST_K_SBS, 1);
@@ -477,11 +546,11 @@ static int launch_packing(int packing, const uint8_t* frame, size_t frame_stride
 #undef ST_LAUNCH
 }
 
-// every refusal, then the launch.  max_packing: the entry's last packing code (the layouts of the two older entries are codes 0, 1)
-template <bool SUB>
-static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
-                         int n, int W, int H, int gain_left, int gain_right, int convergence, int packing, int max_packing,
-                         uint8_t* out_bgr, void* stream)
+// every refusal the render entries share: V3D_ERR_ARG first, then V3D_ERR_UNSUPPORTED.  max_packing: the entry's last packing code
+// (the layouts of the two older entries are codes 0, 1)
+static int stereo_refusal(const char* who, const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
+                          int n, int W, int H, int gain_left, int gain_right, int convergence, int packing, int max_packing,
+                          uint8_t* out_bgr)
 {
     if (!frame_bgr || !depth || !out_bgr) { v3d_set_error("%s: null pointer", who); return V3D_ERR_ARG; }
     if (n < 1 || n > 65535 || W < 1 || H < 1) { v3d_set_error("%s: bad geometry n=%d W=%d H=%d", who, n, W, H); return V3D_ERR_ARG; }
@@ -499,10 +568,22 @@ static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame
     }
     if (convergence < 0 || convergence > 65535) { v3d_set_error("%s: convergence %d outside [0, 65535]", who, convergence); return V3D_ERR_ARG; }
     if (W > ST_MAX_W) { v3d_set_error("%s: W=%d > %d", who, W, ST_MAX_W); return V3D_ERR_UNSUPPORTED; }
+    return V3D_OK;
+}
+
+// every refusal, then the launch
+template <bool SUB, class... SRC>
+static int render_stereo(const char* who, const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
+                         int n, int W, int H, int gain_left, int gain_right, int convergence, int packing, int max_packing,
+                         uint8_t* out_bgr, void* stream, SRC... src)
+{
+    const int rc = stereo_refusal(who, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, packing,
+                                  max_packing, out_bgr);
+    if (rc != V3D_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (W <= 8 * ST_THREADS) return launch_packing<8, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s);
-    if (W <= 16 * ST_THREADS) return launch_packing<16, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s);
-    return launch_packing<32, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s);
+    if (W <= 8 * ST_THREADS) return launch_packing<8, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s, src...);
+    if (W <= 16 * ST_THREADS) return launch_packing<16, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s, src...);
+    return launch_packing<32, SUB>(packing, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, out_bgr, s, src...);
 }
 
 extern "C" int v3d_render_stereo_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
@@ -530,4 +611,41 @@ extern "C" int v3d_render_stereo_packed_batch(const uint8_t* frame_bgr, size_t f
     return (subpixel ? render_stereo<true> : render_stereo<false>)(who, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left,
                                                                    gain_right, convergence, packing, V3D_PACK_ANAGLYPH_DUBOIS, out_bgr,
                                                                    stream);
+}
+
+extern "C" int v3d_render_stereo_source_batch(const uint8_t* frame_bgr, size_t frame_stride, const uint16_t* depth, size_t depth_stride,
+                                              int n, int W, int H, int gain_left, int gain_right, int convergence, int subpixel,
+                                              int packing, const uint8_t* sbs_bgr, size_t sbs_stride, int Ws, int Hs, int pitch,
+                                              int fill_eyes, int64_t ax, int64_t bx, int64_t ay, int64_t by, uint8_t* out_bgr,
+                                              void* stream)
+{
+    const char* who = "v3d_render_stereo_source_batch";
+    if (subpixel != 0 && subpixel != 1) { v3d_set_error("%s: subpixel %d is neither 0 nor 1", who, subpixel); return V3D_ERR_ARG; }
+    if (fill_eyes < 0 || fill_eyes > 3) { v3d_set_error("%s: fill_eyes %d outside 0 .. 3", who, fill_eyes); return V3D_ERR_ARG; }
+    if (fill_eyes && !sbs_bgr) { v3d_set_error("%s: null SBS pointer with fill_eyes %d", who, fill_eyes); return V3D_ERR_ARG; }
+    if (Ws < 2 || (Ws & 1) || Hs < 1) { v3d_set_error("%s: bad SBS geometry Ws=%d (even, >= 2) Hs=%d", who, Ws, Hs); return V3D_ERR_ARG; }
+    if ((int64_t)pitch < 3 * (int64_t)Ws) { v3d_set_error("%s: pitch %d < 3 Ws = %lld", who, pitch, 3LL * Ws); return V3D_ERR_ARG; }
+    if (n > 1 && sbs_stride < (size_t)Hs * (size_t)pitch) {
+        v3d_set_error("%s: SBS stride %zu B smaller than a frame", who, sbs_stride);
+        return V3D_ERR_ARG;
+    }
+    const int64_t amin = 1 << 12, amax = 1 << 20, bmax = (int64_t)1 << 40;
+    if (ax < amin || ax > amax || ay < amin || ay > amax || bx < -bmax || bx > bmax || by < -bmax || by > bmax) {
+        v3d_set_error("%s: map (%lld, %lld, %lld, %lld) outside scale [2^12, 2^20], |offset| <= 2^40", who, (long long)ax,
+                      (long long)bx, (long long)ay, (long long)by);
+        return V3D_ERR_ARG;
+    }
+    // every V3D_ERR_ARG of the packed entry comes before either V3D_ERR_UNSUPPORTED (W, then the eye width)
+    const int last = V3D_PACK_ANAGLYPH_DUBOIS;
+    const int rc = stereo_refusal(who, frame_bgr, frame_stride, depth, depth_stride, n, W, H, gain_left, gain_right, convergence, packing,
+                                  last, out_bgr);
+    if (rc != V3D_OK) return rc;
+    if (Ws / 2 > ST_MAX_W) { v3d_set_error("%s: eye width %d > %d", who, Ws / 2, ST_MAX_W); return V3D_ERR_UNSUPPORTED; }
+    if (!fill_eyes)                                            // no eye to fill: the packed entry's kernels, and so its bits and its time
+        return (subpixel ? render_stereo<true> : render_stereo<false>)(who, frame_bgr, frame_stride, depth, depth_stride, n, W, H,
+                                                                       gain_left, gain_right, convergence, packing, last, out_bgr, stream);
+    const StSource src = { sbs_bgr, sbs_stride, Ws / 2, Hs, pitch, fill_eyes, ax, bx, ay, by };
+    return (subpixel ? render_stereo<true, StSource> : render_stereo<false, StSource>)(who, frame_bgr, frame_stride, depth, depth_stride,
+                                                                                       n, W, H, gain_left, gain_right, convergence,
+                                                                                       packing, last, out_bgr, stream, src);
 }

@@ -88,6 +88,8 @@ SIGNATURES = {
     "v3d_render_stereo_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
     "v3d_render_stereo_subpixel_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
     "v3d_render_stereo_packed_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "v3d_render_stereo_source_batch": (ci, [vp, sz, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64,
+                                            vp, vp]),
     "v3d_temporal_cuts": (ci, [vp, sz, ci, ci, ci, ci, vp, vp, vp]),
     "v3d_depth_minmax_batch": (ci, [vp, ci, sz, sz, vp, vp]),
     "v3d_temporal_range": (ci, [vp, vp, ci, ci, ci, ci, vp, vp]),
@@ -641,6 +643,39 @@ def render_stereo_packed_batch(frames, depth_u16, gain_left, gain_right, converg
     _call("v3d_render_stereo_packed_batch", frames.device, C.c_void_p(frames.data_ptr()), frames.stride(0),
           _dev(depth_u16, torch.int16, "depth_u16"), H * W, n, W, H, int(gain_left), int(gain_right), int(convergence),
           int(bool(subpixel)), int(packing), _dev(out, torch.uint8, "out"))
+    return out
+
+
+def render_stereo_source_batch(frames, depth_u16, gain_left, gain_right, convergence, packing, sbs, fill_eyes, ax, bx, ay, by,
+                               out=None, subpixel=False):
+    """render_stereo_packed_batch with the holes of the eyes named by fill_eyes (bit 0 left, bit 1 right) sampled from the stored
+    eye of the SBS frames (v3d_render_stereo_source_batch): sbs u8 [n,Hs,Ws,3] BGR on the device (rows may be pitched, frames
+    strided; None only with fill_eyes = 0), target (t, y) reads eye coordinates (ax t + bx, ay y + by) in Q16, clamped to the eye.
+    Bit-exact contract: tests/stereo_source_ref.py."""
+    def out_size(W, H):
+        if not isinstance(subpixel, (bool, np.bool_)):
+            raise ValueError(f"subpixel must be True or False, got {subpixel!r}")
+        if isinstance(fill_eyes, bool) or not isinstance(fill_eyes, (int, np.integer)) or not 0 <= fill_eyes <= 3:
+            raise ValueError(f"fill_eyes must be 0 .. 3 (bit 0: left eye, bit 1: right eye), got {fill_eyes!r}")
+        return stereo_output_size(packing, W, H)
+    n, H, W, out = _stereo_io(frames, depth_u16, out, out_size)
+    if sbs is None:
+        if fill_eyes:
+            raise NativeError("sbs: fill_eyes != 0 needs the SBS frames")
+        sp, ss, Ws, Hs, pitch = C.c_void_p(None), 6, 2, 1, 6     # the smallest legal geometry: the entry checks it all the same
+    else:
+        if not isinstance(sbs, torch.Tensor) or not sbs.is_cuda or sbs.dtype != torch.uint8 or sbs.dim() != 4 or sbs.shape[3] != 3:
+            raise NativeError("sbs: expected a uint8 [n,Hs,Ws,3] device tensor")
+        if sbs.shape[0] != n:
+            raise NativeError(f"sbs holds {sbs.shape[0]} frames, frames {n}")
+        if sbs.stride(3) != 1 or sbs.stride(2) != 3:
+            raise NativeError("sbs: pixels must be dense BGR triples (only the row pitch and the frame stride may differ)")
+        _, Hs, Ws, _ = sbs.shape
+        sp, ss, pitch = C.c_void_p(sbs.data_ptr()), sbs.stride(0), sbs.stride(1) if Hs > 1 else 3 * Ws
+    _call("v3d_render_stereo_source_batch", frames.device, C.c_void_p(frames.data_ptr()), frames.stride(0),
+          _dev(depth_u16, torch.int16, "depth_u16"), H * W, n, W, H, int(gain_left), int(gain_right), int(convergence),
+          int(bool(subpixel)), int(packing), sp, ss, int(Ws), int(Hs), int(pitch), int(fill_eyes), int(ax), int(bx), int(ay), int(by),
+          _dev(out, torch.uint8, "out"))
     return out
 
 

@@ -14,6 +14,12 @@ ones is v3d_render_stereo_packed_batch, which packs in the launch that renders (
     convergence  the depth at the screen plane, in [0, 1] (default 0.5): nearer moves right in the left eye, left in the right
     eye_split    the left eye's share of the shift, in [0, 1] (default 0.5; 0 keeps the 4K frame itself as the left eye)
 
+--parallax source replaces the three invented parameters by the film's own parallax: a depth run made with --depth-range metric
+stores the matcher's disparity itself (64 s / 65535 pixels of its eye), and source_parallax() maps it back to 4K pixels, so the right
+eye's target of a pixel is x - round(K s d): the left eye is the 4K frame, the right eye sits where the SBS release had it.
+--fill-from-source SBS_CLIP then takes the disocclusions of that right eye from the SBS clip's stored right eye
+(v3d_render_stereo_source_batch; contract: tests/stereo_source_ref.py) instead of stretching the background into them.
+
 Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
 cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
 pool.  The output directory `<output without suffix>_frames` is itself a clip (frame_%06d.png + info.json).
@@ -34,6 +40,8 @@ from .utils import PngWriterPool, encode_png8, get_video_info, iter_frames, pref
 # v3d_render_stereo_packed_batch
 LAYOUTS = {"full-sbs": 0, "half-sbs": 1, "full-tb": 2, "half-tb": 3, "interlaced": 4, "anaglyph-colour": 5, "anaglyph-dubois": 6}
 DEFAULT_MAX_SHIFT, DEFAULT_CONVERGENCE, DEFAULT_EYE_SPLIT = 48.0, 0.5, 0.5
+PARALLAX = ("invented", "source")
+FILL_RIGHT_EYE = 2                  # --fill-from-source: fill_eyes of v3d_render_stereo_source_batch (the left eye has gain 0, no holes)
 # frames per launch: 4 x (25 MB BGR + 17 MB depth) of pinned input staging and 4 x 50 MB of pinned output (full SBS at 4K)
 CONVERT_BATCH = 4
 
@@ -50,25 +58,95 @@ def add_stereo_arguments(parser):
                              '(W x H, passive line-polarised displays); anaglyph-colour: red from the left eye, green and blue '
                              'from the right (W x H, red-cyan glasses); anaglyph-dubois: red-cyan by the Dubois least-squares '
                              'matrices (W x H, less ghosting and retinal rivalry)')
-    parser.add_argument('--max-shift', type=float, default=DEFAULT_MAX_SHIFT,
+    parser.add_argument('--max-shift', type=float, default=None,
                         help=f'parallax in pixels between the nearest and the farthest depth (default {DEFAULT_MAX_SHIFT:g})')
-    parser.add_argument('--convergence', type=float, default=DEFAULT_CONVERGENCE,
+    parser.add_argument('--convergence', type=float, default=None,
                         help=f'depth at the screen plane, 0 (far) .. 1 (near) (default {DEFAULT_CONVERGENCE:g})')
-    parser.add_argument('--eye-split', type=float, default=DEFAULT_EYE_SPLIT,
+    parser.add_argument('--eye-split', type=float, default=None,
                         help=f"left eye's share of the shift, 0 .. 1; 0 keeps the 4K frame as the left eye (default {DEFAULT_EYE_SPLIT:g})")
 
 
     parser.add_argument('--subpixel', action='store_true',
                         help='sub-pixel DIBR: positions in 1/16 px, colours interpolated between neighbouring sources '
                              '(smooth surfaces render without one-pixel tears; default: whole-pixel shifts)')
+    parser.add_argument('--parallax', choices=PARALLAX, default='invented',
+                        help="invented: --max-shift / --convergence / --eye-split map the depth to a parallax (default).  source: the "
+                             "film's own parallax, from a depth run made with --depth-range metric: the left eye is the 4K frame, the "
+                             "right eye sits where the SBS release had it; not with --max-shift, --convergence or --eye-split.  The depth "
+                             "must be the 16-bit PNG sequence with its JSON manifest: an H.264 depth file carries neither the metric "
+                             "samples nor the depth_range block")
+    parser.add_argument('--parallax-gain', type=float, default=None, metavar='K',
+                        help='with --parallax source: scale the film\'s parallax by K (default 1.0)')
 
 
 def stereo_options(args):
-    """the parsed stereo flags as keyword arguments; `subpixel` appears only when the flag is on"""
-    opts = dict(max_shift=args.max_shift, convergence=args.convergence, eye_split=args.eye_split, layout=args.layout)
+    """the parsed stereo flags as keyword arguments; `subpixel` and the parallax keys appear only when their flag is on"""
+    explicit = [f"--{k.replace('_', '-')}" for k in ("max_shift", "convergence", "eye_split") if getattr(args, k) is not None]
+    source = getattr(args, "parallax", "invented") == "source"
+    if source and explicit:
+        raise ValueError(f"--parallax source takes the film's parallax: it cannot be combined with {', '.join(explicit)}")
+    if not source and getattr(args, "parallax_gain", None) is not None:
+        raise ValueError("--parallax-gain needs --parallax source")
+    opts = dict(max_shift=DEFAULT_MAX_SHIFT if args.max_shift is None else args.max_shift,
+                convergence=DEFAULT_CONVERGENCE if args.convergence is None else args.convergence,
+                eye_split=DEFAULT_EYE_SPLIT if args.eye_split is None else args.eye_split, layout=args.layout)
     if getattr(args, "subpixel", False):
         opts["subpixel"] = True
+    if source:
+        opts.update(parallax="source", parallax_gain=1.0 if args.parallax_gain is None else args.parallax_gain)
     return opts
+
+
+def source_parallax(depth_range, Whi: int, spatial_map=None, gain: float = 1.0, flag: str = "--depth-range metric"):
+    """--parallax source: the `depth_range` block of a metric depth run + the 4K width -> dict(max_shift, convergence, eye_split,
+    scale, gain), the parameters stereo_settings turns into gains.  A u16 sample v is a rebiased disparity of 64 v / 65535 pixels
+    of the matcher's eye (W_eye wide); s = Whi / (Ax W_eye) 4K pixels per matcher pixel (Ax: the applied spatial map's x scale, or
+    1); with eye_split 0, max_shift = K s 64 65536 / 65535 and convergence = -m / 64 (m: the search window's first disparity) the
+    right eye's target is x - round(K s d), d the matcher's own disparity: the film's parallax at 4K."""
+    import math
+    if not isinstance(depth_range, dict) or depth_range.get("mode") != "metric":
+        raise ValueError(f"--parallax source needs a depth run made with {flag}, given as its JSON manifest of 16-bit PNGs (a manifest "
+                         f"with a depth_range block whose mode is metric; an .mp4 depth file carries none)")
+    W_eye, m, hi = depth_range.get("eye_width"), depth_range.get("min_disparity", 0), depth_range.get("hi", 64)
+    if not isinstance(W_eye, int) or W_eye < 1 or not isinstance(m, int) or not -hi <= m <= 0:
+        raise ValueError(f"--parallax source: the depth_range block {depth_range} lacks a usable eye_width / min_disparity")
+    if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or not math.isfinite(gain) or gain < 0:
+        raise ValueError(f"--parallax-gain must be a finite number >= 0, got {gain!r}")
+    Ax = float(spatial_map[0]) if spatial_map is not None else 1.0
+    if not Ax > 0:
+        raise ValueError(f"--parallax source: spatial map {spatial_map} has no positive x scale")
+    s = Whi / (Ax * W_eye)
+    max_shift = gain * s * hi * 65536 / 65535
+    if math.floor(max_shift * 256 + 0.5) >= 1 << 24:           # |gain_right| < 2^24 is what the render entries take
+        raise ValueError(f"--parallax source: scale {s:g} x gain {gain:g} gives a render gain beyond 2^24")
+    return dict(max_shift=max_shift, convergence=-m / hi, eye_split=0.0, scale=s, gain=float(gain))
+
+
+def fill_map_q16(spatial_map, eye_size, frame_size):
+    """--fill-from-source: the Q16 map (ax, bx, ay, by) from a 4K target to the stored eye's sample grid, for the applied spatial
+    map (normalised plane coordinates, so the stored half-width eye needs no special case) or the identity"""
+    from .register import map_to_q16
+    Ax, Bx, Ay, By = spatial_map if spatial_map is not None else (1, 0, 1, 0)
+    (We, Hs), (Whi, Hhi) = eye_size, frame_size
+    q = map_to_q16(Ax, Bx, We, Whi) + map_to_q16(Ay, By, Hs, Hhi)
+    if not (1 << 12 <= q[0] <= 1 << 20 and 1 << 12 <= q[2] <= 1 << 20 and abs(q[1]) <= 1 << 40 and abs(q[3]) <= 1 << 40):
+        raise ValueError(f"--fill-from-source: a {We}x{Hs} eye under a {Whi}x{Hhi} frame leaves the sampler's range (1/16 .. 16 samples per pixel)")
+    return q
+
+
+def depth_manifest(depth_path):
+    """the JSON manifest of a 4K depth run at depth_path, or {} (a directory, a video, anything else)"""
+    p = Path(depth_path)
+    if not p.is_file():
+        return {}
+    with open(p, "rb") as f:
+        if f.read(1) != b"{":
+            return {}
+    try:
+        man = json.loads(p.read_text())
+    except (UnicodeDecodeError, ValueError):
+        return {}
+    return man if isinstance(man, dict) else {}
 
 
 def subpixel_kwargs(subpixel):
@@ -126,6 +204,10 @@ def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, 
             "note": "no ffmpeg binary on this host: side-by-side frames kept as 8-bit RGB PNGs"}
         if params.get("subpixel"):
             man["subpixel"] = True
+        if params.get("parallax") == "source":
+            man.update(parallax="source", parallax_scale=params["parallax_scale"], parallax_gain=params["parallax_gain"])
+        if params.get("fill_from_source"):
+            man.update(fill_from_source=params["fill_from_source"], source_start_frame=params.get("source_start_frame", 0))
         Path(output_path).write_text(json.dumps(man, indent=1))
 
 
@@ -168,10 +250,12 @@ def depth_frame_files(depth_path):
 class HipRenderBackend(HipBackend):
     """the device side of the convert step: pinned staging, one H2D, one v3d_render_stereo_batch launch, one D2H per batch"""
 
-    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, png=False, subpixel=False):
+    def render_batch(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, png=False, subpixel=False, source=None):
         """NumPy BGR frames [H,W,3] + u16 depth maps [H,W] -> NumPy u8 [n,H,outW,3].  The input staging holds `capacity`
         frames and is reused (the synchronise at the end of the previous call made that safe); the output block comes from
-        torch's caching host allocator and returns to it once the writers drop the last frame of it."""
+        torch's caching host allocator and returns to it once the writers drop the last frame of it.
+        source (--fill-from-source): dict(frames: the SBS BGR frames [Hs,Ws,3] of this batch, fill_eyes, q: (ax, bx, ay, by)) -- the
+        render is v3d_render_stereo_source_batch, one launch all the same"""
         torch, nat = self.torch, self.native
         n = len(frames)
         H, W = depths[0].shape
@@ -181,13 +265,18 @@ class HipRenderBackend(HipBackend):
         with torch.cuda.device(self.device):
             fd = self._upload("frames", frames, (H, W, 3), torch.uint8, cap)
             dd = self._upload("depth", [np.asarray(d, np.uint16).view(np.int16) for d in depths[:n]], (H, W), torch.int16, cap)
-            render_stereo(nat, fd, dd, gain_left, gain_right, conv, layout, od[:n], subpixel)
+            if source is not None:
+                sd = self._upload("sbs", source["frames"], tuple(source["frames"][0].shape), torch.uint8, cap)
+                nat.render_stereo_source_batch(fd, dd, gain_left, gain_right, conv, layout, sd, source["fill_eyes"], *source["q"],
+                                               out=od[:n], subpixel=subpixel)
+            else:
+                render_stereo(nat, fd, dd, gain_left, gain_right, conv, layout, od[:n], subpixel)
             return od[:n] if png else self._fetch(od[:n])
 
-    def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, subpixel=False):
+    def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, subpixel=False, source=None):
         """--png-encoder gpu: render_batch whose frames stay on the device and come back as the zlib streams of their PNGs"""
         return self._png_encoder().encode(self.render_batch(frames, depths, gain_left, gain_right, conv, layout, capacity, png=True,
-                                                            subpixel=subpixel))
+                                                            subpixel=subpixel, **({} if source is None else {"source": source})))
 
 
 class DepthTo3DConverter:
@@ -197,17 +286,35 @@ class DepthTo3DConverter:
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
-                 batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False):
+                 batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False, parallax: str = "invented",
+                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
         png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
-        subpixel: sub-pixel DIBR (the backend's render calls then carry subpixel=True; with it off they are unchanged)"""
+        subpixel: sub-pixel DIBR (the backend's render calls then carry subpixel=True; with it off they are unchanged);
+        parallax: "source" takes the parallax from the depth run's depth_range block (set_source_parallax; process_conversion reads
+        it from the depth manifest) and ignores max_shift / convergence / eye_split, parallax_gain scales it;
+        fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
+        of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
+        if parallax not in PARALLAX:
+            raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
+        if fill_from_source is not None and parallax != "source":
+            raise ValueError("--fill-from-source needs --parallax source: the holes of an invented parallax do not line up with the real eye")
+        if isinstance(source_start_frame, bool) or not isinstance(source_start_frame, (int, np.integer)) or source_start_frame < 0:
+            raise ValueError(f"--source-start-frame must be an integer >= 0, got {source_start_frame!r}")
+        self.parallax, self.parallax_gain = parallax, parallax_gain
+        self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
         self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout, subpixel)
         self.subpixel = bool(subpixel)
         self.params = dict(max_shift=max_shift, convergence=convergence, eye_split=eye_split, layout=layout)
         if self.subpixel:
             self.params["subpixel"] = True
+        self.spatial_map = None                      # the spatial map the depth run applied (set_source_parallax)
+        if parallax == "source":
+            source_parallax({"mode": "metric", "eye_width": 1, "min_disparity": 0}, 1, None, parallax_gain)     # the gain's own checks, now
+            self.gains = None                        # until set_source_parallax, and so are the three parameters it derives
+            self.params.update(max_shift=None, convergence=None, eye_split=None)
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -215,13 +322,38 @@ class DepthTo3DConverter:
         self.backend = backend
         self.batch_size = max(1, int(batch_size))
 
-    def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray) -> np.ndarray:
-        """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous)"""
+    def set_source_parallax(self, depth_range, Whi: int, spatial_map=None):
+        """parallax="source": the depth run's depth_range block, the 4K width and the applied spatial map (or None) -> the gains"""
+        p = source_parallax(depth_range, Whi, spatial_map, self.parallax_gain)
+        _, self.gains = stereo_settings(p["max_shift"], p["convergence"], p["eye_split"], self.params["layout"], self.subpixel)
+        self.params.update(max_shift=p["max_shift"], convergence=p["convergence"], eye_split=p["eye_split"], parallax="source",
+                           parallax_scale=p["scale"], parallax_gain=p["gain"])
+        self.spatial_map = None if spatial_map is None else tuple(float(v) for v in spatial_map)
+        return self.gains
+
+    def source_kwargs(self, sbs_frames, frame_size):
+        """what a backend's render call gains with --fill-from-source: nothing without it"""
+        if sbs_frames is None:
+            return {}
+        Hs, Ws = sbs_frames[0].shape[:2]
+        if Ws % 2:
+            raise ValueError(f"the SBS frames of --fill-from-source are {Ws} wide: not two eyes side by side")
+        return {"source": dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE,
+                               q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))}
+
+    def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray, source: np.ndarray = None) -> np.ndarray:
+        """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous).  source: the SBS BGR
+        frame the depth was made from; the right eye's disocclusions are sampled from its stored right eye (parallax="source" only)"""
         frame_bgr, depth_u16 = np.asarray(frame_bgr), np.asarray(depth_u16)
         if frame_bgr.shape[:2] != depth_u16.shape or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
             raise ValueError(f"frame {frame_bgr.shape} and depth {depth_u16.shape} disagree")
+        if self.gains is None:
+            raise ValueError("parallax='source': call set_source_parallax(depth_range, frame width) first")
+        if source is not None and self.parallax != "source":
+            raise ValueError("source= needs parallax='source'")
+        src = self.source_kwargs(None if source is None else [np.asarray(source, np.uint8)], frame_bgr.shape[1::-1])
         return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
-                                                  **subpixel_kwargs(self.subpixel))[0])
+                                                  **subpixel_kwargs(self.subpixel), **src)[0])
 
     def process_conversion(self, video_4k_path: str, depth_path: str, output_path: str = None, force_reprocess: bool = False,
                            guide_start_frame: int = 0, max_frames: int = None) -> str:
@@ -229,7 +361,8 @@ class DepthTo3DConverter:
         path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
         from . import sharding
         from .png_gpu import rgb8_file
-        print(f"4K + depth -> 3D ({self.params['layout']}{', sub-pixel' if self.subpixel else ''}): {video_4k_path} + {depth_path}")
+        print(f"4K + depth -> 3D ({self.params['layout']}{', sub-pixel' if self.subpixel else ''}"
+              f"{', source parallax' if self.parallax == 'source' else ''}): {video_4k_path} + {depth_path}")
         depth_files = depth_frame_files(depth_path)
         info = get_video_info(video_4k_path)
         if not info:
@@ -237,7 +370,8 @@ class DepthTo3DConverter:
         W, H, fps = info['width'], info['height'], info['fps']
         if output_path is None:
             # _subpx: a run with --subpixel never reuses a file rendered without it
-            output_path = f"3d_{self.params['layout']}{'_subpx' if self.subpixel else ''}_{Path(depth_path).with_suffix('').name}.mp4"
+            tag = ("_subpx" if self.subpixel else "") + ("_srcpx" if self.parallax == "source" else "") + ("_srcfill" if self.fill_from_source else "")
+            output_path = f"3d_{self.params['layout']}{tag}_{Path(depth_path).with_suffix('').name}.mp4"
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
             print(f"✓ Using existing 3D video: {output_path}")
@@ -246,6 +380,15 @@ class DepthTo3DConverter:
             raise ValueError(f"half SBS needs an even frame width, the 4K clip is {W} wide")
         if self.layout_code == LAYOUTS["half-tb"] and H % 2:
             raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {H} high")
+        if self.parallax == "source":                           # the film's parallax: from the depth run's own record
+            man = depth_manifest(depth_path)
+            self.set_source_parallax(man.get("depth_range"), W, man.get("spatial_map"))
+            print(f"Source parallax: {self.params['parallax_scale']:g} 4K px per matcher px x gain {self.params['parallax_gain']:g} "
+                  f"-> gains {self.gains}")
+        if self.fill_from_source is not None:
+            if not get_video_info(self.fill_from_source):
+                raise ValueError(f"Could not read video info: {self.fill_from_source}")
+            self.params.update(fill_from_source=str(self.fill_from_source), source_start_frame=self.source_start_frame)
         oW, oH = output_size(self.layout_code, W, H)
         n = len(depth_files) if max_frames is None else min(len(depth_files), max(int(max_frames), 0))
 
@@ -257,20 +400,22 @@ class DepthTo3DConverter:
         mine = list(range(rank, n, world))                       # frame i -> rank i mod world; both inputs decoded per rank
         depths = prefetch_map(read_png16, [depth_files[i] for i in mine])
         frames4k = iter_frames(video_4k_path, g0, n, stride=world, offset=rank)
-        batch_f, batch_d, batch_i = [], [], []
+        sbs_frames = iter_frames(self.fill_from_source, self.source_start_frame, n, stride=world, offset=rank) if self.fill_from_source else None
+        batch_f, batch_d, batch_i, batch_s = [], [], [], []
         rendered = 0
 
         def flush(writers):
             nonlocal rendered
             if not batch_f:
                 return
+            src = self.source_kwargs(batch_s if sbs_frames is not None else None, (W, H))
             if self.png_encoder == "gpu":                        # deflated on the device: only the streams cross PCIe
                 out = self.backend.render_batch_png(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
-                                                    **subpixel_kwargs(self.subpixel))
+                                                    **subpixel_kwargs(self.subpixel), **src)
                 encode = rgb8_file(oW, oH)
             else:
                 out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
-                                                **subpixel_kwargs(self.subpixel))
+                                                **subpixel_kwargs(self.subpixel), **src)
                 encode = png_rgb_from_bgr
             for j, i in enumerate(batch_i):
                 writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)
@@ -278,6 +423,7 @@ class DepthTo3DConverter:
             batch_f.clear()
             batch_d.clear()
             batch_i.clear()
+            batch_s.clear()
 
         try:
             with self.writer_pool_factory() as writers:
@@ -286,6 +432,12 @@ class DepthTo3DConverter:
                     if f is None:
                         print(f"Warning: 4K video ended after {k} of this rank's frames; rendering stops at depth frame {i}")
                         break
+                    if sbs_frames is not None:
+                        s = next(sbs_frames, None)
+                        if s is None:
+                            print(f"Warning: the SBS clip ended after {k} of this rank's frames; rendering stops at depth frame {i}")
+                            break
+                        batch_s.append(s)
                     d = next(depths)
                     if d.shape != f.shape[:2] or f.ndim != 3:
                         raise ValueError(f"depth map {depth_files[i].name} is {d.shape[1]}x{d.shape[0]}, "
@@ -324,6 +476,11 @@ def main(argv=None, backend=None):
     parser.add_argument('--device', default='cuda', help='Processing device (default: cuda)')
     from .png_gpu import add_png_arguments, png_options
     add_png_arguments(parser)
+    parser.add_argument('--fill-from-source', default=None, metavar='SBS_CLIP',
+                        help="with --parallax source: take the right eye's disocclusions from the stored right eye of this SBS clip "
+                             '(the clip the depth was computed from) instead of stretching the background into them')
+    parser.add_argument('--source-start-frame', type=int, default=0, metavar='N',
+                        help='the SBS frame that depth frame 0 was made from (default 0)')
     guide = parser.add_mutually_exclusive_group()
     guide.add_argument('--guide-start-frame', type=int, default=0,
                        help='4K frame that matches depth frame 0 (the offset the upscale CLI used; default 0)')
@@ -342,7 +499,10 @@ def main(argv=None, backend=None):
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args))
+        source = {"fill_from_source": args.fill_from_source, "source_start_frame": args.source_start_frame} if args.fill_from_source else {}
+        if args.source_start_frame and not args.fill_from_source:
+            raise ValueError("--source-start-frame needs --fill-from-source")
+        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source)
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)

@@ -341,21 +341,39 @@ class HipStereoBackend(HipBackend):
         """frames carried from earlier passes (or None) + the frames of this pass -> one private device buffer"""
         return new.clone() if held is None else self.torch.cat([held, new])
 
+    def metric_lohi(self, n):
+        """--depth-range metric: the constant range (0, 64) of n frames, a [n,2] device tensor written once per n"""
+        from .temporal import METRIC_HI, METRIC_LO
+        bufs = self.__dict__.setdefault("_bufs", {})
+        lohi = bufs.get(("metric_lohi", n))
+        if lohi is None:
+            lohi = bufs[("metric_lohi", n)] = self.torch.tensor([[METRIC_LO, METRIC_HI]] * n, dtype=self.torch.float32, device=self.device)
+        return lohi
+
+    def depth_to_u16_metric(self, depth):
+        """--depth-range metric without a radius: device float32 depth [n,H,W] -> device u16 samples (int16-viewed) [n,H,W] against
+        the constant range (0, 64): one launch, no reduction"""
+        return self.native.depth_to_u16_range_batch(depth, self.metric_lohi(len(depth)))
+
     def temporal_stabilize(self, depth, gray, t0, n, radius, tau, cut_threshold, fill, range_quantile=10000, observe=None,
-                           motion_search=0):
+                           motion_search=0, metric=False):
         """buffer of T frames (device depth f32 and left gray u8 [T,H,W]) -> device u16 samples (int16-viewed) [n,H,W] of
         targets t0 .. t0+n-1: cuts, per-frame min/max, clip-stable range, filter, normalisation -- nine launches on the
         current stream, nothing comes back to the host.  range_quantile < 10000: the per-frame max is the robust white point
         (three launches in place of the min/max's three).  observe (--quality-report): called with the filtered depth and the
         targets' gray before the normalisation.  motion_search > 0 (--temporal-motion): the block matcher's fields and the cuts
-        of its residual (three launches in place of the cuts' three) and the compensated filter in place of the filter"""
+        of its residual (three launches in place of the cuts' three) and the compensated filter in place of the filter.  metric
+        (--depth-range metric): the constant range (0, 64) in place of the min/max and the window's range (four launches fewer)"""
         nat = self.native
         if motion_search > 0:
             fwd, bwd, _, cut = nat.temporal_motion(gray, motion_search, cut_threshold)
         else:
             cut = nat.temporal_cuts(gray, cut_threshold)
-        mm = nat.depth_robust_minmax_batch(depth, range_quantile) if range_quantile < 10000 else nat.depth_minmax_batch(depth)
-        lohi = nat.temporal_range(mm, cut, radius, t0, n)
+        if metric:
+            lohi = self.metric_lohi(n)
+        else:
+            mm = nat.depth_robust_minmax_batch(depth, range_quantile) if range_quantile < 10000 else nat.depth_minmax_batch(depth)
+            lohi = nat.temporal_range(mm, cut, radius, t0, n)
         if motion_search > 0:
             filt = nat.temporal_filter_mc_batch(depth, gray, radius, tau, cut, fwd, bwd, fill, t0, n)
         else:
@@ -417,7 +435,8 @@ class HybridStereoDepthExtractor:
                  quality_still: int = 4,
                  quality_jump: float = 1.0,
                  temporal_motion: int = 0,
-                 min_disparity=0):
+                 min_disparity=0,
+                 depth_range: str = "frame"):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
@@ -435,7 +454,10 @@ class HybridStereoDepthExtractor:
         min_disparity (every surface): m in [-64, 0], the matcher searches disparities [m, m + 64) -- content behind the screen
         plane has d < 0 -- and the result is rebiased to [0, 64): larger still means nearer, and the far end of the window
         (rel = 0) is dropped like d = 0 is at m = 0 (depth.py:374).  "auto" (process_video_sbs and the one-pass pipeline)
-        calibrates m on frames of the clip (resolve_min_disparity).  0 = the reference's window: no call, key or byte changes """
+        calibrates m on frames of the clip (resolve_min_disparity).  0 = the reference's window: no call, key or byte changes
+        depth_range (process_video_sbs and the one-pass pipeline): "metric" normalises every frame against the constant range
+        (0, 64) instead of its own (or its window's) minimum and maximum: a sample s is a rebiased disparity of 64 s / 65535 pixels
+        of the matcher's eye.  "frame" = the reference's min-max: no call, key or byte changes """
         self.min_disparity = check_min_disparity(min_disparity)
         self.min_disparity_scores = None         # {candidate: score} of an `auto` run, once resolved
         from .png_gpu import check_png_encoder
@@ -444,6 +466,11 @@ class HybridStereoDepthExtractor:
         self.temporal = check_parameters(temporal_radius, temporal_tau, temporal_cut, temporal_fill)
         self.motion_search = check_motion_search(temporal_motion, self.temporal[0])
         self.range_quantile = check_range_percentile(range_percentile)
+        from .temporal import check_depth_range
+        self.depth_range = check_depth_range(depth_range, self.range_quantile)
+        self.eye_width = None                    # the matcher's image width of the run in progress (--depth-range metric)
+        if self.depth_range == "metric" and not fill_holes:
+            print("Warning: --depth-range metric without --fill-holes: invalid pixels sit at the far end of the search window")
         if not isinstance(fill_holes, (bool, np.bool_)):
             raise ValueError(f"fill_holes must be a bool, got {fill_holes!r}")
         self.fill_holes = bool(fill_holes)
@@ -573,6 +600,10 @@ class HybridStereoDepthExtractor:
             extra["min_disparity"] = self.min_disparity
         if self.min_disparity_scores is not None:
             extra["min_disparity_scores"] = self.min_disparity_scores
+        if self.depth_range == "metric":
+            from .temporal import METRIC_HI, METRIC_LO
+            extra["depth_range"] = {"mode": "metric", "lo": METRIC_LO, "hi": METRIC_HI, "min_disparity": self.min_disparity,
+                                    "eye_width": self.eye_width}
         if self.guide_check is not None and self.guide_check.summary is not None:
             extra["guide_match"] = self.guide_check.summary
         if self.quality is not None and self.quality.summary is not None:
@@ -613,8 +644,8 @@ class HybridStereoDepthExtractor:
             print(CACHED_NOTE)
 
     def write_side_files(self, cache_path: Path):
-        """temporal.json (a radius or the robust range is on), fill.json (--fill-holes) and min_disparity.json (--min-disparity)
-        of a depth map directory"""
+        """temporal.json (a radius or the robust range is on), fill.json (--fill-holes), min_disparity.json (--min-disparity) and
+        depth_range.json (--depth-range metric) of a depth map directory"""
         import json
         extra = self.manifest_extra()
         if "temporal" in extra:
@@ -623,6 +654,8 @@ class HybridStereoDepthExtractor:
             (cache_path / "fill.json").write_text(json.dumps({"fill_holes": True}))
         if "min_disparity" in extra:
             (cache_path / "min_disparity.json").write_text(json.dumps({k: extra[k] for k in ("min_disparity", "min_disparity_scores") if k in extra}))
+        if "depth_range" in extra:
+            (cache_path / "depth_range.json").write_text(json.dumps(extra["depth_range"]))
 
     def _guidance_provider(self):
         """ the provider when neural guidance is active (depth.py:344-345), else None """
@@ -636,10 +669,10 @@ class HybridStereoDepthExtractor:
         does a search window other than [0, 64): the resolved integer, which an `auto` run and an explicit one share) """
         if self.min_disparity == "auto":
             raise ValueError('min_disparity="auto" is resolved from the clip first (resolve_min_disparity)')
-        from .temporal import cache_suffix, fill_suffix
+        from .temporal import cache_suffix, depth_range_suffix, fill_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
         cache_key += cache_suffix(*self.temporal, self.range_quantile, self.motion_search) + fill_suffix(self.fill_holes)
-        cache_key += min_disparity_suffix(self.min_disparity)
+        cache_key += min_disparity_suffix(self.min_disparity) + depth_range_suffix(self.depth_range)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -813,6 +846,8 @@ class HybridStereoDepthExtractor:
         the rank owns: per pass, or -- with --temporal-radius -- `radius` frames behind the matcher with the tail at the end."""
         be = self.backend
         self.last_pass_frames = pass_frames = self.pass_frames(video_info)
+        self.eye_width = video_info['width'] if self.unsqueeze_sbs else video_info['width'] // 2
+        metric = self.depth_range == "metric"
         (first, count, stride, offset), _, block = self.frame_plan(frame_count, rank, world)
         # --quality-report: a rank's halo frames are matched twice in a block-sharded run; only the owner's records count
         quality = self.start_quality(world, None if block is None else range(block[0], block[0] + block[1]))
@@ -821,7 +856,7 @@ class HybridStereoDepthExtractor:
             from .temporal import BlockStabilizer
             observe = {"observe": quality.note_stabilised} if quality is not None and world == 1 else {}
             motion = {"motion_search": self.motion_search} if self.motion_search > 0 else {}
-            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile, **observe, **motion)
+            stab = BlockStabilizer(be, self.temporal, *block, self.range_quantile, **observe, **motion, **({"metric": True} if metric else {}))
         frames = iter_frames(video_path, start_frame + first, count, stride=stride, offset=offset) if count else iter(())
         provider = self._guidance_provider()
         self.last_decoded_frames = 0
@@ -840,7 +875,9 @@ class HybridStereoDepthExtractor:
                     yield stab.push(depth, be.left_gray(len(batch)))
                     continue
                 idx = [first + offset + k * stride for k in range(k0, k0 + len(batch))]
-                if self.range_quantile < 10000:          # --range-percentile: every frame against its own robust white point
+                if metric:                               # --depth-range metric: the constant range, no reduction
+                    yield idx, be.depth_to_u16_metric(depth)
+                elif self.range_quantile < 10000:        # --range-percentile: every frame against its own robust white point
                     yield idx, be.depth_to_u16_robust(depth, self.range_quantile)
                 elif hasattr(be, "depth_to_u16_batch"):
                     yield idx, be.depth_to_u16_batch(depth)
@@ -862,7 +899,7 @@ def add_depth_arguments(parser, force_help: str):
     """the options of the depth path, shared by the depth CLI and the one-pass pipeline (--force means something else in each)"""
     from .png_gpu import add_png_arguments
     from .quality import add_quality_arguments
-    from .temporal import add_fill_arguments, add_range_arguments, add_temporal_arguments
+    from .temporal import add_depth_range_arguments, add_fill_arguments, add_range_arguments, add_temporal_arguments
     parser.add_argument('--start-frame', type=int, default=0, help='Starting frame number (default: 0)')
     parser.add_argument('--max-frames', type=int, default=None, help='Maximum number of frames to process (default: all)')
     parser.add_argument('--batch-size', type=int, default=8, help='Batch size for GPU processing (default: 8)')
@@ -875,6 +912,7 @@ def add_depth_arguments(parser, force_help: str):
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
     add_temporal_arguments(parser)
     add_range_arguments(parser)
+    add_depth_range_arguments(parser)
     add_fill_arguments(parser)
     parser.add_argument('--min-disparity', type=min_disparity_argument, default=0, metavar='M|auto',
                         help='Search disparities [M, M + 64) instead of [0, 64), M in [-64, 0]: content behind the screen plane of '
@@ -888,12 +926,13 @@ def depth_options(args) -> dict:
     """parsed add_depth_arguments -> the keyword arguments HybridStereoDepthExtractor and SbsTo4kDepthPipeline share"""
     from .png_gpu import png_options
     from .quality import quality_options
-    from .temporal import fill_options, range_options, temporal_options
+    from .temporal import depth_range_options, fill_options, range_options, temporal_options
     stereo_only = args.stereo_only or args.no_neural
     return dict(model_checkpoint=args.model, work_dir=args.work_dir, device=args.device, batch_size=args.batch_size,
                 use_neural_guidance=not stereo_only, stereo_only=stereo_only, unsqueeze_sbs=not args.no_unsqueeze,
                 **temporal_options(args), **range_options(args), **fill_options(args), **png_options(args),
-                **quality_options(args), **({"min_disparity": args.min_disparity} if args.min_disparity != 0 else {}))
+                **quality_options(args), **({"min_disparity": args.min_disparity} if args.min_disparity != 0 else {}),
+                **depth_range_options(args))
 
 
 def main(argv=None):

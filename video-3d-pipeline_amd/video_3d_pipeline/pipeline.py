@@ -140,7 +140,8 @@ class SbsTo4kDepthPipeline:
                  quality_still: int = 4,
                  quality_jump: float = 1.0,
                  temporal_motion: int = 0,
-                 min_disparity=0):
+                 min_disparity=0,
+                 depth_range: str = "frame"):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own; temporal_motion > 0: the
         window follows the block matcher's motion);
@@ -150,7 +151,8 @@ class SbsTo4kDepthPipeline:
         check_guide: score every (left view, 4K frame) pair the run uses (framematch.GuideChecker); no output PNG changes;
         quality_*: the depth CLI's --quality-report (quality.py): quality.json goes next to the kept depth maps, else next to the
         4K frames, or to the given path; no output PNG changes;
-        min_disparity: the depth CLI's --min-disparity (an integer in [-64, 0] or "auto"; 0 = off: the window [0, 64))"""
+        min_disparity: the depth CLI's --min-disparity (an integer in [-64, 0] or "auto"; 0 = off: the window [0, 64));
+        depth_range: the depth CLI's --depth-range ("metric": the constant range (0, 64); "frame" = off: per-frame min-max)"""
         if backend is None:
             if not str(device).startswith("cuda"):
                 raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
@@ -163,7 +165,8 @@ class SbsTo4kDepthPipeline:
             mono_provider=mono_provider, temporal_radius=temporal_radius, temporal_tau=temporal_tau, temporal_cut=temporal_cut,
             temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes,
             png_encoder=png_encoder, quality_report=quality_report, quality_bad_threshold=quality_bad_threshold,
-            quality_still=quality_still, quality_jump=quality_jump, temporal_motion=temporal_motion, min_disparity=min_disparity)
+            quality_still=quality_still, quality_jump=quality_jump, temporal_motion=temporal_motion, min_disparity=min_disparity,
+            **({"depth_range": depth_range} if depth_range != "frame" else {}))
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
         self.check_guide, self.check_guide_min = bool(check_guide), float(check_guide_min)
@@ -175,7 +178,8 @@ class SbsTo4kDepthPipeline:
         output path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence.
         stereo_output: also render every frame that has a 4K frame to side-by-side 3D from the device-resident 4K frame and
         depth (the files the convert CLI writes from this run's depth output); stereo_options: max_shift, convergence,
-        eye_split, layout, subpixel (convert.py's defaults); spatial: register.resolve()'s result -- the low-res u16 depth is warped
+        eye_split, layout, subpixel (convert.py's defaults), or parallax="source" [, parallax_gain] with depth_range="metric": the
+        film's own parallax (convert.source_parallax); spatial: register.resolve()'s result -- the low-res u16 depth is warped
         into the 4K frame's framing right before the guided filter (None: nothing changes)."""
         from . import sharding
         from .png_gpu import gray16_file, rgb8_file
@@ -186,11 +190,18 @@ class SbsTo4kDepthPipeline:
             from .convert import LAYOUTS, output_size, png_rgb_from_bgr, sibling_frames_dir, stereo_settings, subpixel_kwargs
             params = dict(max_shift=48.0, convergence=0.5, eye_split=0.5, layout="full-sbs")
             params.update(stereo_options or {})
+            source = {k: params.pop(k) for k in ("parallax", "parallax_gain") if k in params}
+            if source.get("parallax", "invented") not in ("invented", "source"):
+                raise ValueError(f"parallax must be 'invented' or 'source', got {source['parallax']!r}")
+            if source.get("parallax") != "source":
+                source = None
+            elif ex.depth_range != "metric":
+                raise ValueError("--parallax source needs --depth-range metric on the same command line: the depth must keep its scale")
             layout, gains = stereo_settings(**params)
             if not params.get("subpixel"):
                 params.pop("subpixel", None)                         # off: the manifest and the backend calls are unchanged
             stereo = dict(params=params, layout=layout, gains=gains, dir=sibling_frames_dir(stereo_output), count=0,
-                          sub=subpixel_kwargs(params.get("subpixel")))
+                          sub=subpixel_kwargs(params.get("subpixel")), source=source)
         print(f"SBS -> 4K depth: {sbs_video} + {video_4k}")
         video_info, frame_count = ex._frame_count(sbs_video, start_frame, max_frames)
         info4k = get_video_info(video_4k)
@@ -216,6 +227,15 @@ class SbsTo4kDepthPipeline:
             if stereo["layout"] == LAYOUTS["half-tb"] and Hhi % 2:
                 raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {Hhi} high")
             stereo["size"] = output_size(stereo["layout"], Whi, Hhi)
+            if stereo["source"] is not None:                         # the film's parallax: the window is resolved, the sizes are known
+                from .convert import source_parallax
+                eye_w = video_info['width'] if ex.unsqueeze_sbs else video_info['width'] // 2
+                p = source_parallax({"mode": "metric", "eye_width": eye_w, "min_disparity": ex.min_disparity}, Whi,
+                                    None if spatial is None else spatial["map"], stereo["source"].get("parallax_gain", 1.0))
+                stereo["params"].update(max_shift=p["max_shift"], convergence=p["convergence"], eye_split=p["eye_split"],
+                                        parallax="source", parallax_scale=p["scale"], parallax_gain=p["gain"])
+                stereo["gains"] = stereo_settings(p["max_shift"], p["convergence"], p["eye_split"], stereo["params"]["layout"])[1]
+                print(f"Source parallax: {p['scale']:g} 4K px per matcher px x gain {p['gain']:g} -> gains {stereo['gains']}")
             stereo["dir"].mkdir(parents=True, exist_ok=True)
         warp = None
         if spatial is not None:                                      # every rank applies the same map: nothing to exchange
@@ -378,6 +398,7 @@ def main(argv=None):
             return 1
         print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
     try:
+        stereo = stereo_options(args)            # refuses --parallax source beside an invented parallax before anything is opened
         spatial = _resolve_spatial(args, resolve)
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
@@ -385,7 +406,7 @@ def main(argv=None):
         output_path = pipe.run(args.video, args.video_4k, output_path=args.output, start_frame=args.start_frame,
                                max_frames=args.max_frames, guide_start_frame=args.guide_start_frame,
                                force_reprocess=args.force, keep_depth_maps=args.keep_depth_maps,
-                               stereo_output=args.stereo_output, stereo_options=stereo_options(args), spatial=spatial)
+                               stereo_output=args.stereo_output, stereo_options=stereo, spatial=spatial)
         print(f"\n✓ Success! 4K depth video: {output_path}")
     except Exception as e:
         print(f"Error: {e}")

@@ -90,11 +90,13 @@ class TemporalStabilizer:
     `backend.temporal_concat` and `backend.temporal_stabilize`."""
 
     def __init__(self, backend, radius: int, tau: int = DEFAULT_TAU, cut_threshold: int = DEFAULT_CUT, fill: bool = True,
-                 range_quantile: int = RANGE_Q_OFF, observe=None, motion_search: int = 0):
+                 range_quantile: int = RANGE_Q_OFF, observe=None, motion_search: int = 0, metric: bool = False):
         """observe (--quality-report): a callable the backend's temporal_stabilize calls with the filtered depth and the targets'
         gray; None (the default) adds no argument to that call.  motion_search (--temporal-motion): S > 0 adds the keyword
-        `motion_search=S` to that call; 0 (the default) adds nothing"""
+        `motion_search=S` to that call; 0 (the default) adds nothing.  metric (--depth-range metric): adds the keyword
+        `metric=True`, the constant range (0, 64) in place of the window's; off adds nothing"""
         self.observe = observe
+        self.metric = bool(metric)
         self.radius, self.tau, self.cut_threshold, self.fill = check_parameters(radius, tau, cut_threshold, fill)
         self.motion_search = check_motion_search(motion_search, self.radius)
         if isinstance(range_quantile, bool) or int(range_quantile) != range_quantile or not RANGE_Q_MIN <= range_quantile <= RANGE_Q_OFF:
@@ -119,6 +121,8 @@ class TemporalStabilizer:
         kw = {} if self.observe is None else {"observe": self.observe}
         if self.motion_search > 0:                           # off: no keyword, the call every backend knows
             kw["motion_search"] = self.motion_search
+        if self.metric:
+            kw["metric"] = True
         out = self.backend.temporal_stabilize(*args, **kw)
         self._next = upto
         return out
@@ -159,8 +163,8 @@ class BlockStabilizer:
     it owns; the halo frames only feed the windows."""
 
     def __init__(self, backend, params, first: int, count: int, halo_before: int, range_quantile: int = RANGE_Q_OFF, observe=None,
-                 motion_search: int = 0):
-        self.stab = TemporalStabilizer(backend, *params, range_quantile, observe, motion_search)
+                 motion_search: int = 0, metric: bool = False):
+        self.stab = TemporalStabilizer(backend, *params, range_quantile, observe, motion_search, **({"metric": True} if metric else {}))
         self.first, self.count = first, count
         self._at = first - halo_before           # clip index of the next frame the stabiliser returns
 
@@ -212,6 +216,37 @@ def add_fill_arguments(parser):
                         help="Fill the matcher's invalid pixels (the 64 leftmost columns, occlusions, rejected matches) from their "
                              'scanline neighbours with the background value before the depth is normalised (default: off, they '
                              'stay depth 0)')
+
+
+METRIC_LO, METRIC_HI = 0, 64                                   # --depth-range metric: the matcher's rebiased window, in pixels
+DEPTH_RANGES = ("frame", "metric")
+
+
+def add_depth_range_arguments(parser):
+    """--depth-range, shared by the depth CLI and the one-pass pipeline"""
+    parser.add_argument('--depth-range', choices=DEPTH_RANGES, default='frame',
+                        help=f"Range of the 16-bit normalisation.  frame: every frame (window, with --temporal-radius) against its own "
+                             f"minimum and maximum (default).  metric: the constant range [{METRIC_LO}, {METRIC_HI}], so a sample s is a "
+                             f"rebiased disparity of {METRIC_HI} s / 65535 pixels whatever else is in the frame (what convert's --parallax "
+                             f"source needs); use it with --fill-holes")
+
+
+def check_depth_range(mode, range_quantile: int = RANGE_Q_OFF) -> str:
+    if mode not in DEPTH_RANGES:
+        raise ValueError(f"depth_range must be one of {DEPTH_RANGES}, got {mode!r}")
+    if mode == "metric" and range_quantile < RANGE_Q_OFF:
+        raise ValueError("--depth-range metric fixes the range: it cannot be combined with --range-percentile below 100")
+    return mode
+
+
+def depth_range_options(args) -> dict:
+    """nothing at the default, so a constructor that predates the flag is called as before"""
+    return {"depth_range": args.depth_range} if getattr(args, "depth_range", "frame") != "frame" else {}
+
+
+def depth_range_suffix(mode: str) -> str:
+    """what the depth cache key gains, after every other suffix, with --depth-range metric ('' at the default)"""
+    return "_metric" if mode == "metric" else ""
 
 
 def fill_options(args) -> dict:

@@ -47,6 +47,19 @@ def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height
             "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"}, indent=1))
 
 
+def depth_range_entry(depth_dir) -> dict:
+    """the depth CLI's depth_range.json (--depth-range metric) as an entry of the 4K manifest: the guided filter keeps the samples'
+    scale, so what a sample means travels with them to the convert CLI ({} without the file)"""
+    side = Path(depth_dir) / "depth_range.json"
+    if not side.is_file():
+        return {}
+    try:
+        block = json.loads(side.read_text())
+    except ValueError:
+        return {}
+    return {"depth_range": block} if isinstance(block, dict) else {}
+
+
 class HipUpscaleBackend(HipBackend):
     def to_luma(self, frame_bgr):
         d = frame_bgr if self.torch.is_tensor(frame_bgr) else self.native.to_device(frame_bgr, self.device)
@@ -224,7 +237,7 @@ class SimpleDepthUpscaler:
         if rank == 0:
             from .register import manifest_entries
             encode_depth4k(frames_dir, output_path, n, target_width, target_height, fps, self.radius, self.eps,
-                           manifest_entries(self.spatial) or None)
+                           {**depth_range_entry(depth_dir), **manifest_entries(self.spatial)} or None)
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
         return output_path
