@@ -260,6 +260,29 @@ def _negative_start_advice(alignment_file, by: str, start_frame: int) -> str:
             f"--guide-start-frame 0 instead of --alignment-file")
 
 
+def add_guide_arguments(parser, frame0_help: str, offset_help: str = 'alignment offset in frames'):
+    """--guide-start-frame | --alignment-file of the upscale, pipeline and convert CLIs; frame0_help: what 4K frame N is paired with"""
+    guide = parser.add_mutually_exclusive_group()
+    guide.add_argument('--guide-start-frame', type=int, default=0,
+                       help=f'4K frame that matches {frame0_help} ({offset_help}; default 0)')
+    guide.add_argument('--alignment-file', default=None,
+                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
+                            'round(time_offset_seconds * fps of the 4K clip)')
+
+
+def resolve_guide_start(args) -> bool:
+    """--alignment-file -> args.guide_start_frame, announced; False, the error printed, when the file gives none (the CLI returns 1)"""
+    if args.alignment_file is None:
+        return True
+    try:
+        args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
+    except (OSError, ValueError, KeyError) as e:
+        print(f"Error: {e}")
+        return False
+    print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
+    return True
+
+
 def main(argv=None, backend=None):
     """Command line interface for fast audio-only alignment (+ optional frame matching on the GPU).  backend: a stand-in for
     the refinement's HipPipelineBackend (host-logic tests)."""

@@ -5,6 +5,12 @@ their own device steps."""
 import numpy as np
 
 
+def require_hip_device(device):
+    """what a driver checks before it builds its own backend (a given stand-in is never asked): there is no CPU path"""
+    if not str(device).startswith("cuda"):
+        raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
+
+
 class HipBackend:
     """PyTorch-ROCm buffers on one device + libv3d_hip.so.  Every method also works on a subclass whose __init__ set only
     torch / native / device (the host tests' stand-ins): nothing else is assumed to exist."""

@@ -27,14 +27,13 @@ pool.  The output directory `<output without suffix>_frames` is itself a clip (f
 import argparse
 import functools
 import json
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
 
-from .backend import HipBackend
-from .utils import PngWriterPool, encode_png8, get_video_info, iter_frames, prefetch_map, read_png16
+from .backend import HipBackend, require_hip_device
+from .utils import (PngWriterPool, encode_png8, finish_sequence, get_video_info, iter_frames, prefetch_map, read_png16,
+                    sibling_frames_dir)      # sibling_frames_dir is importable from here too
 
 # V3D_PACK_*: codes 0 / 1 are V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS of v3d_render_stereo[_subpixel]_batch, codes >= 2 go to
 # v3d_render_stereo_packed_batch
@@ -149,11 +148,6 @@ def depth_manifest(depth_path):
     return man if isinstance(man, dict) else {}
 
 
-def subpixel_kwargs(subpixel):
-    """what a backend's render call gains: nothing with the flag off, so a backend that predates it is called as before"""
-    return {"subpixel": True} if subpixel else {}
-
-
 def stereo_settings(max_shift=DEFAULT_MAX_SHIFT, convergence=DEFAULT_CONVERGENCE, eye_split=DEFAULT_EYE_SPLIT, layout="full-sbs",
                     subpixel=False):
     """validated user parameters -> (layout code, (gain_left, gain_right, conv)); ValueError for anything out of range"""
@@ -179,40 +173,21 @@ def render_stereo(native, frames, depths, gain_left, gain_right, conv, layout, o
     return native.render_stereo_batch(frames, depths, gain_left, gain_right, conv, layout, out, subpixel=subpixel)
 
 
-def sibling_frames_dir(output_path) -> Path:
-    return Path(str(Path(output_path).with_suffix("")) + "_frames")
-
-
 def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, params: dict, gains):
-    """one process, after every frame is written: H.264 at output_path when an ffmpeg binary exists and it ends in .mp4,
-    else a JSON manifest of the PNG sequence (as encode_depth4k does for the depth)"""
-    ffmpeg = shutil.which("ffmpeg")
-    if ffmpeg and str(output_path).endswith(".mp4"):
-        cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / "frame_%06d.png"),
-               "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-preset", "medium", "-r", str(fps), str(output_path)]
-        res = subprocess.run(cmd, capture_output=True)
-        if res.returncode != 0:
-            print("FFmpeg error:")
-            print(res.stderr.decode())
-            raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
-    else:
-        man = {
-            "format": "png8-rgb-sequence", "frames_dir": str(frames_dir), "pattern": "frame_%06d.png",
-            "count": count, "width": width, "height": height, "fps": fps, "layout": params["layout"],
-            "max_shift": params["max_shift"], "convergence": params["convergence"], "eye_split": params["eye_split"],
-            "gain_left": gains[0], "gain_right": gains[1], "conv": gains[2],
-            "note": "no ffmpeg binary on this host: side-by-side frames kept as 8-bit RGB PNGs"}
-        if params.get("subpixel"):
-            man["subpixel"] = True
-        if params.get("parallax") == "source":
-            man.update(parallax="source", parallax_scale=params["parallax_scale"], parallax_gain=params["parallax_gain"])
-        if params.get("fill_from_source"):
-            man.update(fill_from_source=params["fill_from_source"], source_start_frame=params.get("source_start_frame", 0))
-        Path(output_path).write_text(json.dumps(man, indent=1))
-
-
-def write_clip_info(frames_dir: Path, fps: float):
-    (frames_dir / "info.json").write_text(json.dumps({"fps": fps}))
+    """one process, after every frame is written: the manifest of the PNG sequence, through finish_sequence (as encode_depth4k)"""
+    man = {
+        "format": "png8-rgb-sequence", "frames_dir": str(frames_dir), "pattern": "frame_%06d.png",
+        "count": count, "width": width, "height": height, "fps": fps, "layout": params["layout"],
+        "max_shift": params["max_shift"], "convergence": params["convergence"], "eye_split": params["eye_split"],
+        "gain_left": gains[0], "gain_right": gains[1], "conv": gains[2],
+        "note": "no ffmpeg binary on this host: side-by-side frames kept as 8-bit RGB PNGs"}
+    if params.get("subpixel"):
+        man["subpixel"] = True
+    if params.get("parallax") == "source":
+        man.update(parallax="source", parallax_scale=params["parallax_scale"], parallax_gain=params["parallax_gain"])
+    if params.get("fill_from_source"):
+        man.update(fill_from_source=params["fill_from_source"], source_start_frame=params.get("source_start_frame", 0))
+    finish_sequence(frames_dir, "frame_%06d.png", output_path, fps, man)
 
 
 def depth_frame_files(depth_path):
@@ -228,18 +203,12 @@ def depth_frame_files(depth_path):
     if p.is_dir():
         files = listing(p)
     elif p.is_file():
-        with open(p, "rb") as f:
-            head = f.read(1)
-        if head == b"{":
-            try:
-                man = json.loads(p.read_text())
-            except (UnicodeDecodeError, ValueError):
-                man = None
-            if isinstance(man, dict) and "frames_dir" in man:
-                d = Path(man["frames_dir"])
-                if not d.is_dir() and not d.is_absolute():
-                    d = p.parent / d
-                files = listing(d)[:int(man.get("count", 1 << 62))]
+        man = depth_manifest(p)
+        if "frames_dir" in man:
+            d = Path(man["frames_dir"])
+            if not d.is_dir() and not d.is_absolute():
+                d = p.parent / d
+            files = listing(d)[:int(man.get("count", 1 << 62))]
         if not files:
             files = listing(sibling_frames_dir(p))
     if not files:
@@ -279,6 +248,87 @@ class HipRenderBackend(HipBackend):
                                                             subpixel=subpixel, **({} if source is None else {"source": source})))
 
 
+class StereoPlan:
+    """What stereo_options(args) (+ the fill-from-source keys) mean for a run, for the convert CLI and the pipeline's --stereo-output
+    alike: validated once, then the render calls' layout code, gains and optional keywords, the packed frame's size, the writers'
+    encoder and the files that finish the clip.
+    subpixel: sub-pixel DIBR (the backend's render calls then carry subpixel=True; with it off they are unchanged);
+    parallax: "source" takes the parallax from the depth run's depth_range block (resolve_source) and ignores max_shift /
+    convergence / eye_split, parallax_gain scales it;
+    fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
+    of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from"""
+
+    def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
+                 eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", subpixel: bool = False, parallax: str = "invented",
+                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0):
+        if parallax not in PARALLAX:
+            raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
+        if fill_from_source is not None and parallax != "source":
+            raise ValueError("--fill-from-source needs --parallax source: the holes of an invented parallax do not line up with the real eye")
+        if isinstance(source_start_frame, bool) or not isinstance(source_start_frame, (int, np.integer)) or source_start_frame < 0:
+            raise ValueError(f"--source-start-frame must be an integer >= 0, got {source_start_frame!r}")
+        self.parallax, self.parallax_gain = parallax, parallax_gain
+        self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
+        self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout, subpixel)
+        self.subpixel = bool(subpixel)
+        self.params = dict(max_shift=max_shift, convergence=convergence, eye_split=eye_split, layout=layout)   # the manifest's entries
+        if self.subpixel:
+            self.params["subpixel"] = True
+        self.spatial_map = None                      # the spatial map the depth run applied (resolve_source)
+        self.size = None                             # (outW, outH) of the packed frame (check_frame)
+        if parallax == "source":
+            source_parallax({"mode": "metric", "eye_width": 1, "min_disparity": 0}, 1, None, parallax_gain)     # the gain's own checks, now
+            self.gains = None                        # until resolve_source, and so are the three parameters it derives
+            self.params.update(max_shift=None, convergence=None, eye_split=None)
+
+    def check_frame(self, W: int, H: int):
+        """the 4K frame's size -> self.size = (outW, outH); ValueError for a half layout on an odd size"""
+        if self.layout_code == LAYOUTS["half-sbs"] and W % 2:
+            raise ValueError(f"half SBS needs an even frame width, the 4K clip is {W} wide")
+        if self.layout_code == LAYOUTS["half-tb"] and H % 2:
+            raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {H} high")
+        self.size = output_size(self.layout_code, W, H)
+
+    def resolve_source(self, depth_range, Whi: int, spatial_map=None, announce: bool = True):
+        """parallax="source": the depth run's depth_range block, the 4K width and the applied spatial map (or None) -> the gains"""
+        p = source_parallax(depth_range, Whi, spatial_map, self.parallax_gain)
+        _, self.gains = stereo_settings(p["max_shift"], p["convergence"], p["eye_split"], self.params["layout"], self.subpixel)
+        self.params.update(max_shift=p["max_shift"], convergence=p["convergence"], eye_split=p["eye_split"], parallax="source",
+                           parallax_scale=p["scale"], parallax_gain=p["gain"])
+        self.spatial_map = None if spatial_map is None else tuple(float(v) for v in spatial_map)
+        if announce:
+            print(f"Source parallax: {p['scale']:g} 4K px per matcher px x gain {p['gain']:g} -> gains {self.gains}")
+        return self.gains
+
+    def render_kwargs(self):
+        """what a backend's render call gains: nothing with --subpixel off, so a backend that predates it is called as before"""
+        return {"subpixel": True} if self.subpixel else {}
+
+    def source_kwargs(self, sbs_frames, frame_size):
+        """what a backend's render call gains with --fill-from-source: nothing without it"""
+        if sbs_frames is None:
+            return {}
+        Hs, Ws = sbs_frames[0].shape[:2]
+        if Ws % 2:
+            raise ValueError(f"the SBS frames of --fill-from-source are {Ws} wide: not two eyes side by side")
+        return {"source": dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE,
+                               q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))}
+
+    def encoder(self, gpu_png: bool):
+        """the writer pool's encoder of a rendered frame: the wrapper of a device-deflated stream, or zlib on the writer threads"""
+        from .png_gpu import rgb8_file
+        return rgb8_file(*self.size) if gpu_png else png_rgb_from_bgr
+
+    def finish(self, frames_dir: Path, output_path, count: int, fps: float):
+        """one process, after every frame is written: info.json makes frames_dir a clip, then the H.264 file or the manifest"""
+        (frames_dir / "info.json").write_text(json.dumps({"fps": fps}))
+        finish_stereo_output(frames_dir, output_path, count, *self.size, fps, self.params, self.gains)
+
+
+def _of_plan(name):
+    return property(lambda self: getattr(self.plan, name))
+
+
 class DepthTo3DConverter:
     """4K frames + 4K depth maps -> side-by-side 3D frames (DIBR on the GPU)"""
 
@@ -290,56 +340,28 @@ class DepthTo3DConverter:
                  parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
         png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
-        subpixel: sub-pixel DIBR (the backend's render calls then carry subpixel=True; with it off they are unchanged);
-        parallax: "source" takes the parallax from the depth run's depth_range block (set_source_parallax; process_conversion reads
-        it from the depth manifest) and ignores max_shift / convergence / eye_split, parallax_gain scales it;
-        fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
-        of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from"""
+        every other keyword is StereoPlan's (parallax="source": set_source_parallax, or process_conversion from the depth manifest)"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
-        if parallax not in PARALLAX:
-            raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
-        if fill_from_source is not None and parallax != "source":
-            raise ValueError("--fill-from-source needs --parallax source: the holes of an invented parallax do not line up with the real eye")
-        if isinstance(source_start_frame, bool) or not isinstance(source_start_frame, (int, np.integer)) or source_start_frame < 0:
-            raise ValueError(f"--source-start-frame must be an integer >= 0, got {source_start_frame!r}")
-        self.parallax, self.parallax_gain = parallax, parallax_gain
-        self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
-        self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout, subpixel)
-        self.subpixel = bool(subpixel)
-        self.params = dict(max_shift=max_shift, convergence=convergence, eye_split=eye_split, layout=layout)
-        if self.subpixel:
-            self.params["subpixel"] = True
-        self.spatial_map = None                      # the spatial map the depth run applied (set_source_parallax)
-        if parallax == "source":
-            source_parallax({"mode": "metric", "eye_width": 1, "min_disparity": 0}, 1, None, parallax_gain)     # the gain's own checks, now
-            self.gains = None                        # until set_source_parallax, and so are the three parameters it derives
-            self.params.update(max_shift=None, convergence=None, eye_split=None)
+        self.plan = StereoPlan(max_shift, convergence, eye_split, layout, subpixel, parallax, parallax_gain, fill_from_source,
+                               source_start_frame)
         if backend is None:
-            if not str(device).startswith("cuda"):
-                raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
+            require_hip_device(device)
             backend = HipRenderBackend(device)
         self.backend = backend
         self.batch_size = max(1, int(batch_size))
 
+    # the plan's state and steps under the converter's own names
+    params, gains, layout_code = _of_plan("params"), _of_plan("gains"), _of_plan("layout_code")
+    subpixel, parallax, parallax_gain = _of_plan("subpixel"), _of_plan("parallax"), _of_plan("parallax_gain")
+    spatial_map, fill_from_source, source_start_frame = _of_plan("spatial_map"), _of_plan("fill_from_source"), _of_plan("source_start_frame")
+
     def set_source_parallax(self, depth_range, Whi: int, spatial_map=None):
-        """parallax="source": the depth run's depth_range block, the 4K width and the applied spatial map (or None) -> the gains"""
-        p = source_parallax(depth_range, Whi, spatial_map, self.parallax_gain)
-        _, self.gains = stereo_settings(p["max_shift"], p["convergence"], p["eye_split"], self.params["layout"], self.subpixel)
-        self.params.update(max_shift=p["max_shift"], convergence=p["convergence"], eye_split=p["eye_split"], parallax="source",
-                           parallax_scale=p["scale"], parallax_gain=p["gain"])
-        self.spatial_map = None if spatial_map is None else tuple(float(v) for v in spatial_map)
-        return self.gains
+        """the plan's resolve_source, silently"""
+        return self.plan.resolve_source(depth_range, Whi, spatial_map, announce=False)
 
     def source_kwargs(self, sbs_frames, frame_size):
-        """what a backend's render call gains with --fill-from-source: nothing without it"""
-        if sbs_frames is None:
-            return {}
-        Hs, Ws = sbs_frames[0].shape[:2]
-        if Ws % 2:
-            raise ValueError(f"the SBS frames of --fill-from-source are {Ws} wide: not two eyes side by side")
-        return {"source": dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE,
-                               q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))}
+        return self.plan.source_kwargs(sbs_frames, frame_size)
 
     def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray, source: np.ndarray = None) -> np.ndarray:
         """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous).  source: the SBS BGR
@@ -353,14 +375,14 @@ class DepthTo3DConverter:
             raise ValueError("source= needs parallax='source'")
         src = self.source_kwargs(None if source is None else [np.asarray(source, np.uint8)], frame_bgr.shape[1::-1])
         return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
-                                                  **subpixel_kwargs(self.subpixel), **src)[0])
+                                                  **self.plan.render_kwargs(), **src)[0])
 
     def process_conversion(self, video_4k_path: str, depth_path: str, output_path: str = None, force_reprocess: bool = False,
                            guide_start_frame: int = 0, max_frames: int = None) -> str:
         """depth frame i pairs with 4K frame guide_start_frame + i (the offset the upscale CLI used).  Returns the output
         path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
         from . import sharding
-        from .png_gpu import rgb8_file
+        plan = self.plan
         print(f"4K + depth -> 3D ({self.params['layout']}{', sub-pixel' if self.subpixel else ''}"
               f"{', source parallax' if self.parallax == 'source' else ''}): {video_4k_path} + {depth_path}")
         depth_files = depth_frame_files(depth_path)
@@ -376,20 +398,14 @@ class DepthTo3DConverter:
         if output_path.exists() and not force_reprocess:
             print(f"✓ Using existing 3D video: {output_path}")
             return str(output_path)
-        if self.layout_code == LAYOUTS["half-sbs"] and W % 2:
-            raise ValueError(f"half SBS needs an even frame width, the 4K clip is {W} wide")
-        if self.layout_code == LAYOUTS["half-tb"] and H % 2:
-            raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {H} high")
+        plan.check_frame(W, H)
         if self.parallax == "source":                           # the film's parallax: from the depth run's own record
             man = depth_manifest(depth_path)
-            self.set_source_parallax(man.get("depth_range"), W, man.get("spatial_map"))
-            print(f"Source parallax: {self.params['parallax_scale']:g} 4K px per matcher px x gain {self.params['parallax_gain']:g} "
-                  f"-> gains {self.gains}")
+            plan.resolve_source(man.get("depth_range"), W, man.get("spatial_map"))
         if self.fill_from_source is not None:
             if not get_video_info(self.fill_from_source):
                 raise ValueError(f"Could not read video info: {self.fill_from_source}")
             self.params.update(fill_from_source=str(self.fill_from_source), source_start_frame=self.source_start_frame)
-        oW, oH = output_size(self.layout_code, W, H)
         n = len(depth_files) if max_frames is None else min(len(depth_files), max(int(max_frames), 0))
 
         rank, world = sharding.rank_world()
@@ -403,27 +419,22 @@ class DepthTo3DConverter:
         sbs_frames = iter_frames(self.fill_from_source, self.source_start_frame, n, stride=world, offset=rank) if self.fill_from_source else None
         batch_f, batch_d, batch_i, batch_s = [], [], [], []
         rendered = 0
+        gpu_png = self.png_encoder == "gpu"
+        encode = plan.encoder(gpu_png)
 
         def flush(writers):
             nonlocal rendered
             if not batch_f:
                 return
-            src = self.source_kwargs(batch_s if sbs_frames is not None else None, (W, H))
-            if self.png_encoder == "gpu":                        # deflated on the device: only the streams cross PCIe
-                out = self.backend.render_batch_png(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
-                                                    **subpixel_kwargs(self.subpixel), **src)
-                encode = rgb8_file(oW, oH)
-            else:
-                out = self.backend.render_batch(batch_f, batch_d, *self.gains, self.layout_code, capacity=self.batch_size,
-                                                **subpixel_kwargs(self.subpixel), **src)
-                encode = png_rgb_from_bgr
+            # --png-encoder gpu: deflated on the device, only the streams cross PCIe
+            render = self.backend.render_batch_png if gpu_png else self.backend.render_batch
+            out = render(batch_f, batch_d, *plan.gains, plan.layout_code, capacity=self.batch_size, **plan.render_kwargs(),
+                         **plan.source_kwargs(batch_s if sbs_frames is not None else None, (W, H)))
             for j, i in enumerate(batch_i):
                 writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)
             rendered += len(batch_i)
-            batch_f.clear()
-            batch_d.clear()
-            batch_i.clear()
-            batch_s.clear()
+            for b in (batch_f, batch_d, batch_i, batch_s):
+                b.clear()
 
         try:
             with self.writer_pool_factory() as writers:
@@ -456,8 +467,7 @@ class DepthTo3DConverter:
             raise ValueError("No frames rendered")
         sharding.barrier()
         if rank == 0:
-            write_clip_info(frames_dir, fps)
-            finish_stereo_output(frames_dir, output_path, total, oW, oH, fps, self.params, self.gains)
+            plan.finish(frames_dir, output_path, total, fps)
         sharding.barrier()
         print(f"✓ 3D video saved: {output_path}")
         return str(output_path)
@@ -481,21 +491,11 @@ def main(argv=None, backend=None):
                              '(the clip the depth was computed from) instead of stretching the background into them')
     parser.add_argument('--source-start-frame', type=int, default=0, metavar='N',
                         help='the SBS frame that depth frame 0 was made from (default 0)')
-    guide = parser.add_mutually_exclusive_group()
-    guide.add_argument('--guide-start-frame', type=int, default=0,
-                       help='4K frame that matches depth frame 0 (the offset the upscale CLI used; default 0)')
-    guide.add_argument('--alignment-file', default=None,
-                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
-                            'round(time_offset_seconds * fps of the 4K clip)')
+    from .align import add_guide_arguments, resolve_guide_start
+    add_guide_arguments(parser, 'depth frame 0', 'the offset the upscale CLI used')
     args = parser.parse_args(argv)
-    if args.alignment_file is not None:
-        from .align import guide_start_frame_from
-        try:
-            args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
-        except (OSError, ValueError, KeyError) as e:
-            print(f"Error: {e}")
-            return 1
-        print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
+    if not resolve_guide_start(args):
+        return 1
     try:
         from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)

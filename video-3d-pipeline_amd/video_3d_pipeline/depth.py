@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .backend import HipBackend
+from .backend import HipBackend, require_hip_device
 from .utils import PngWriterPool, create_work_directory, get_video_info, iter_frames, write_png16
 
 
@@ -405,6 +405,11 @@ class HipStereoBackend(HipBackend):
         return self._png_encoder().encode(u16)
 
 
+def sbs_eye_size(video_info, unsqueeze: bool) -> Tuple[int, int]:
+    """(width, height) of one eye as the matcher sees it (HybridStereoDepthExtractor.eye_size, for a caller without an extractor)"""
+    return video_info['width'] if unsqueeze else video_info['width'] // 2, video_info['height']
+
+
 class HybridStereoDepthExtractor:
     """ GPU-accelerated depth extraction from SBS video using hybrid stereo matching + neural guidance """
 
@@ -493,8 +498,7 @@ class HybridStereoDepthExtractor:
 
         # `backend` exists so host-logic tests can run without a GPU; the product always builds the HIP one
         if backend is None:
-            if not str(device).startswith("cuda"):
-                raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
+            require_hip_device(device)
             backend = HipStereoBackend(device)
         self.backend = backend
 
@@ -819,12 +823,15 @@ class HybridStereoDepthExtractor:
         for j, frame_idx in enumerate(idx):
             writers.submit(cache_path / f"depth_{frame_idx:06d}.png", to_host(u16[j:j + 1])[0])
 
+    def eye_size(self, video_info) -> Tuple[int, int]:
+        """(width, height) of the matcher's eye: the SBS frame's own width once the halves are unsqueezed, else half of it"""
+        return sbs_eye_size(video_info, self.unsqueeze_sbs)
+
     def pass_frames(self, video_info) -> int:
         """frames per device pass: decoupled from batch_size (which the reference only uses to chunk its frame list,
         depth.py:448-461) -- a pass fills one lock-step SGM launch whatever the caller's chunk size is"""
-        ow = video_info['width'] if self.unsqueeze_sbs else video_info['width'] // 2
         sizer = getattr(self.backend, "compute_batch_size", None)
-        return sizer(ow, video_info['height'], self.batch_size) if sizer else self.batch_size
+        return sizer(*self.eye_size(video_info), self.batch_size) if sizer else self.batch_size
 
     def frame_plan(self, frame_count: int, rank: int, world: int):
         """(decoded, owned, block) of one rank: `decoded` is the iter_frames range (first, count, stride, offset), relative to
@@ -846,7 +853,7 @@ class HybridStereoDepthExtractor:
         the rank owns: per pass, or -- with --temporal-radius -- `radius` frames behind the matcher with the tail at the end."""
         be = self.backend
         self.last_pass_frames = pass_frames = self.pass_frames(video_info)
-        self.eye_width = video_info['width'] if self.unsqueeze_sbs else video_info['width'] // 2
+        self.eye_width = self.eye_size(video_info)[0]
         metric = self.depth_range == "metric"
         (first, count, stride, offset), _, block = self.frame_plan(frame_count, rank, world)
         # --quality-report: a rank's halo frames are matched twice in a block-sharded run; only the owner's records count
@@ -866,15 +873,15 @@ class HybridStereoDepthExtractor:
             for batch in iter(lambda: list(islice(frames, pass_frames)), []):
                 k0 = self.last_decoded_frames
                 self.last_decoded_frames += len(batch)
+                idx = [first + offset + k * stride for k in range(k0, k0 + len(batch))]       # the pass's clip indices
                 depth = self._disparity_pass(be.sbs_to_disparity, batch, self.unsqueeze_sbs, guidance=provider)
                 if quality is not None:                  # --quality-report: the pass's planes are valid until the next pass
-                    quality.note_pass([first + offset + k * stride for k in range(k0, k0 + len(batch))], len(batch), depth)
+                    quality.note_pass(idx, len(batch), depth)
                 if self.guide_check is not None:         # --check-guide: the pass's left gray planes are valid until the next pass
-                    self.guide_check.note_left([first + offset + k * stride for k in range(k0, k0 + len(batch))], be.left_gray(len(batch)))
+                    self.guide_check.note_left(idx, be.left_gray(len(batch)))
                 if stab is not None:
                     yield stab.push(depth, be.left_gray(len(batch)))
                     continue
-                idx = [first + offset + k * stride for k in range(k0, k0 + len(batch))]
                 if metric:                               # --depth-range metric: the constant range, no reduction
                     yield idx, be.depth_to_u16_metric(depth)
                 elif self.range_quantile < 10000:        # --range-percentile: every frame against its own robust white point

@@ -22,9 +22,10 @@ byte-for-byte what the two CLIs write.  The two-step route stays the reference f
 import argparse
 from pathlib import Path
 
-from .depth import HipStereoBackend, HybridStereoDepthExtractor, add_depth_arguments, depth_options
+from .backend import require_hip_device
+from .depth import HipStereoBackend, HybridStereoDepthExtractor, add_depth_arguments, depth_options, sbs_eye_size
 from .upscale import GUIDED_EPS, GUIDED_RADIUS, encode_depth4k
-from .utils import PngWriterPool, get_video_info, iter_frames
+from .utils import PngWriterPool, get_video_info, iter_frames, sibling_frames_dir
 
 # 4K frames per guided launch.  A frame costs ~25 MB of pinned BGR staging + 25 MB of device BGR + 17 MB of u16 output on
 # each side, and the filter's workspace (used by its two-sweep routes) 133 MB of device memory: 8 frames keep the pinned
@@ -154,8 +155,7 @@ class SbsTo4kDepthPipeline:
         min_disparity: the depth CLI's --min-disparity (an integer in [-64, 0] or "auto"; 0 = off: the window [0, 64));
         depth_range: the depth CLI's --depth-range ("metric": the constant range (0, 64); "frame" = off: per-frame min-max)"""
         if backend is None:
-            if not str(device).startswith("cuda"):
-                raise RuntimeError(f"device {device!r} requested, but this build only has the MI355X (HIP) path")
+            require_hip_device(device)
             backend = HipPipelineBackend(device)
         self.backend = backend
         # the depth CLI's extractor supplies the model loading, the guidance provider, the cache path and the frame count
@@ -182,26 +182,16 @@ class SbsTo4kDepthPipeline:
         film's own parallax (convert.source_parallax); spatial: register.resolve()'s result -- the low-res u16 depth is warped
         into the 4K frame's framing right before the guided filter (None: nothing changes)."""
         from . import sharding
-        from .png_gpu import gray16_file, rgb8_file
+        from .png_gpu import gray16_file
         ex, be = self.extractor, self.backend
         gpu_png = ex.png_encoder == "gpu"
-        stereo = None
+        stereo, stereo_count = None, 0                               # convert.StereoPlan of --stereo-output, this rank's frames
         if stereo_output is not None:
-            from .convert import LAYOUTS, output_size, png_rgb_from_bgr, sibling_frames_dir, stereo_settings, subpixel_kwargs
-            params = dict(max_shift=48.0, convergence=0.5, eye_split=0.5, layout="full-sbs")
-            params.update(stereo_options or {})
-            source = {k: params.pop(k) for k in ("parallax", "parallax_gain") if k in params}
-            if source.get("parallax", "invented") not in ("invented", "source"):
-                raise ValueError(f"parallax must be 'invented' or 'source', got {source['parallax']!r}")
-            if source.get("parallax") != "source":
-                source = None
-            elif ex.depth_range != "metric":
+            from .convert import StereoPlan
+            if (stereo_options or {}).get("parallax") == "source" and ex.depth_range != "metric":
                 raise ValueError("--parallax source needs --depth-range metric on the same command line: the depth must keep its scale")
-            layout, gains = stereo_settings(**params)
-            if not params.get("subpixel"):
-                params.pop("subpixel", None)                         # off: the manifest and the backend calls are unchanged
-            stereo = dict(params=params, layout=layout, gains=gains, dir=sibling_frames_dir(stereo_output), count=0,
-                          sub=subpixel_kwargs(params.get("subpixel")), source=source)
+            stereo = StereoPlan(**(stereo_options or {}))
+            stereo_dir = sibling_frames_dir(stereo_output)
         print(f"SBS -> 4K depth: {sbs_video} + {video_4k}")
         video_info, frame_count = ex._frame_count(sbs_video, start_frame, max_frames)
         info4k = get_video_info(video_4k)
@@ -222,26 +212,16 @@ class SbsTo4kDepthPipeline:
         if video_info['width'] % 2 != 0:
             raise ValueError("SBS frame width must be even")
         if stereo is not None:
-            if stereo["layout"] == 1 and Whi % 2:
-                raise ValueError(f"half SBS needs an even frame width, the 4K clip is {Whi} wide")
-            if stereo["layout"] == LAYOUTS["half-tb"] and Hhi % 2:
-                raise ValueError(f"half top-bottom needs an even frame height, the 4K clip is {Hhi} high")
-            stereo["size"] = output_size(stereo["layout"], Whi, Hhi)
-            if stereo["source"] is not None:                         # the film's parallax: the window is resolved, the sizes are known
-                from .convert import source_parallax
-                eye_w = video_info['width'] if ex.unsqueeze_sbs else video_info['width'] // 2
-                p = source_parallax({"mode": "metric", "eye_width": eye_w, "min_disparity": ex.min_disparity}, Whi,
-                                    None if spatial is None else spatial["map"], stereo["source"].get("parallax_gain", 1.0))
-                stereo["params"].update(max_shift=p["max_shift"], convergence=p["convergence"], eye_split=p["eye_split"],
-                                        parallax="source", parallax_scale=p["scale"], parallax_gain=p["gain"])
-                stereo["gains"] = stereo_settings(p["max_shift"], p["convergence"], p["eye_split"], stereo["params"]["layout"])[1]
-                print(f"Source parallax: {p['scale']:g} 4K px per matcher px x gain {p['gain']:g} -> gains {stereo['gains']}")
-            stereo["dir"].mkdir(parents=True, exist_ok=True)
+            stereo.check_frame(Whi, Hhi)
+            if stereo.parallax == "source":                          # the film's parallax: the window is resolved, the sizes are known
+                stereo.resolve_source({"mode": "metric", "eye_width": ex.eye_size(video_info)[0], "min_disparity": ex.min_disparity}, Whi,
+                                      None if spatial is None else spatial["map"])
+            stereo_dir.mkdir(parents=True, exist_ok=True)
+            stereo_encode = stereo.encoder(gpu_png)
         warp = None
         if spatial is not None:                                      # every rank applies the same map: nothing to exchange
             from .register import warp_q16
-            eye = (video_info['width'] if ex.unsqueeze_sbs else video_info['width'] // 2, video_info['height'])
-            warp = warp_q16(spatial["map"], eye, (Whi, Hhi))
+            warp = warp_q16(spatial["map"], ex.eye_size(video_info), (Whi, Hhi))
             print(f"Spatial map {tuple(spatial['map'])} from {spatial['source']}: depth warped to {warp['size'][0]}x{warp['size'][1]} before the guided filter")
         if not ex.model_loaded:
             ex.load_model()
@@ -253,7 +233,7 @@ class SbsTo4kDepthPipeline:
             from .framematch import GuideChecker
             # round-robin sharding leaves a rank every world-th frame: per-pair scores only, no in-batch shift
             check = ex.guide_check = GuideChecker(be, self.check_guide_min, consecutive=world == 1 or ex.temporal[0] > 0)
-        frames_dir = Path(str(output_path.with_suffix("")) + "_frames")
+        frames_dir = sibling_frames_dir(output_path)
         frames_dir.mkdir(parents=True, exist_ok=True)
         # the extractor's frame plan: frame i -> rank i mod world, or -- with temporal stabilisation -- a contiguous block per
         # rank plus a halo of SBS frames that is decoded and matched but not written.  Each rank decodes only its own frames
@@ -278,7 +258,7 @@ class SbsTo4kDepthPipeline:
 
         def emit(writers, out_idx, u16):
             """the u16 depth samples of frames out_idx -> [depth PNGs,] guided filter, 4K PNGs [, stereo frames]"""
-            nonlocal flat, written
+            nonlocal flat, written, stereo_count
             written += len(out_idx)
             gb = min(self.guide_batch, ex.last_pass_frames)         # the driver has sized the pass before its first yield
             if keep_depth_maps:
@@ -303,15 +283,12 @@ class SbsTo4kDepthPipeline:
                 if pending is not None:                            # behind the batch's own synchronise: nothing waits here
                     check.collect(pending)
                 if stereo is not None and any(f is not None for f in frames):
-                    if gpu_png:
-                        sbs3d = be.render_stereo_png(q_dev, stereo["gains"], stereo["layout"], **stereo["sub"])
-                        encode = rgb8_file(*stereo["size"])
-                    else:
-                        sbs3d, encode = be.render_stereo(q_dev, stereo["gains"], stereo["layout"], **stereo["sub"]), png_rgb_from_bgr
+                    render = be.render_stereo_png if gpu_png else be.render_stereo
+                    sbs3d = render(q_dev, stereo.gains, stereo.layout_code, **stereo.render_kwargs())
                     for j, i in enumerate(idx):
                         if frames[j] is not None:                   # no 4K frame: no stereo frame (its slot is stale)
-                            writers.submit(stereo["dir"] / f"frame_{i:06d}.png", sbs3d[j], encode=encode)
-                            stereo["count"] += 1
+                            writers.submit(stereo_dir / f"frame_{i:06d}.png", sbs3d[j], encode=stereo_encode)
+                            stereo_count += 1
             print(f"✓ Queued {len(out_idx)} 4K depth maps (rank {rank})")
 
         with self.writer_pool_factory() as writers:
@@ -322,7 +299,7 @@ class SbsTo4kDepthPipeline:
         n = sharding.total(written)
         if n == 0:
             raise ValueError("No frames extracted from video")
-        n_stereo = sharding.total(stereo["count"]) if stereo is not None else 0
+        n_stereo = sharding.total(stereo_count) if stereo is not None else 0
         if check is not None:
             check.finish(sharding.total)
             if rank == 0:
@@ -336,9 +313,7 @@ class SbsTo4kDepthPipeline:
             if keep_depth_maps:
                 ex.write_side_files(cache_path)
             if stereo is not None and n_stereo:
-                from .convert import finish_stereo_output, write_clip_info
-                write_clip_info(stereo["dir"], fps)
-                finish_stereo_output(stereo["dir"], stereo_output, n_stereo, *stereo["size"], fps, stereo["params"], stereo["gains"])
+                stereo.finish(stereo_dir, stereo_output, n_stereo, fps)
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
         if stereo is not None:
@@ -355,7 +330,7 @@ def _resolve_spatial(args, resolve):
 
     def eye():
         info = get_video_info(args.video)
-        return None if not info else [info["width"] if unsqueeze else info["width"] // 2, info["height"]]
+        return None if not info else list(sbs_eye_size(info, unsqueeze))
 
     def guide():
         info = get_video_info(args.video_4k)
@@ -370,12 +345,8 @@ def main(argv=None):
     parser.add_argument('video_4k', help='Path to 4K 2D video (dimensions and guide frames)')
     parser.add_argument('--output', help='Output path for 4K depth video')
     add_depth_arguments(parser, 'Force reprocessing even if the output exists')
-    guide = parser.add_mutually_exclusive_group()
-    guide.add_argument('--guide-start-frame', type=int, default=0,
-                       help='4K frame that matches the first SBS frame (alignment offset in frames; default 0)')
-    guide.add_argument('--alignment-file', default=None,
-                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
-                            'round(time_offset_seconds * fps of the 4K clip)')
+    from .align import add_guide_arguments, resolve_guide_start
+    add_guide_arguments(parser, 'the first SBS frame')
     parser.add_argument('--keep-depth-maps', action='store_true',
                         help="Also write the 1080p depth_%%06d.png maps into the depth CLI's cache directory")
     parser.add_argument('--stereo-output', default=None,
@@ -389,14 +360,8 @@ def main(argv=None):
     from .register import add_apply_arguments, resolve
     add_apply_arguments(parser)
     args = parser.parse_args(argv)
-    if args.alignment_file is not None:
-        from .align import guide_start_frame_from
-        try:
-            args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
-        except (OSError, ValueError, KeyError) as e:
-            print(f"Error: {e}")
-            return 1
-        print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
+    if not resolve_guide_start(args):
+        return 1
     try:
         stereo = stereo_options(args)            # refuses --parallax source beside an invented parallax before anything is opened
         spatial = _resolve_spatial(args, resolve)

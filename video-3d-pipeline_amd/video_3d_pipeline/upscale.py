@@ -12,14 +12,12 @@ import argparse
 import glob
 import json
 import os
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
 
 from .backend import HipBackend
-from .utils import PngWriterPool, get_video_info, iter_frames, prefetch_map, read_png16
+from .utils import PngWriterPool, finish_sequence, get_video_info, iter_frames, prefetch_map, read_png16, sibling_frames_dir
 
 GUIDED_RADIUS = 8       # at 4K; the reference specifies nothing
 GUIDED_EPS = 1e-3       # on [0,1]-scaled guide
@@ -27,24 +25,13 @@ GUIDED_EPS = 1e-3       # on [0,1]-scaled guide
 
 def encode_depth4k(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, radius: int, eps: float,
                    extra: dict = None):
-    """the last step of a 4K depth run, on one process: frames_dir/depth4k_%06d.png -> H.264 at output_path when an ffmpeg
-    binary exists and the output is an .mp4, else a JSON manifest of the PNG sequence at output_path (`extra`: further
-    entries of the manifest, e.g. the temporal stabilisation parameters of the run)"""
-    ffmpeg = shutil.which("ffmpeg")
-    if ffmpeg and str(output_path).endswith(".mp4"):
-        cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / "depth4k_%06d.png"),
-               "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-preset", "medium", "-r", str(fps), str(output_path)]
-        res = subprocess.run(cmd, capture_output=True)
-        if res.returncode != 0:
-            print("FFmpeg error:")
-            print(res.stderr.decode())
-            raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
-    else:
-        Path(output_path).write_text(json.dumps({
-            "format": "png16-sequence", "frames_dir": str(frames_dir), "pattern": "depth4k_%06d.png",
-            "count": count, "width": width, "height": height, "fps": fps,
-            "guided_radius": radius, "guided_eps": eps, **(extra or {}),
-            "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"}, indent=1))
+    """the last step of a 4K depth run, on one process: the manifest of frames_dir/depth4k_%06d.png, through finish_sequence
+    (`extra`: further entries of the manifest, e.g. the temporal stabilisation parameters of the run)"""
+    finish_sequence(frames_dir, "depth4k_%06d.png", output_path, fps, {
+        "format": "png16-sequence", "frames_dir": str(frames_dir), "pattern": "depth4k_%06d.png",
+        "count": count, "width": width, "height": height, "fps": fps,
+        "guided_radius": radius, "guided_eps": eps, **(extra or {}),
+        "note": "no ffmpeg binary on this host: 4K depth frames kept as 16-bit PNGs"})
 
 
 def depth_range_entry(depth_dir) -> dict:
@@ -137,7 +124,7 @@ class SimpleDepthUpscaler:
 
         rank, world = sharding.rank_world()
         sharding.require_initialized(world)           # never a silent single-rank fallback under torchrun
-        frames_dir = Path(str(Path(output_path).with_suffix("")) + "_frames")
+        frames_dir = sibling_frames_dir(output_path)
         frames_dir.mkdir(parents=True, exist_ok=True)
         n = len(depth_files)
         g0 = max(int(guide_start_frame), 0)
@@ -282,25 +269,15 @@ def main(argv=None, backend=None):
     parser.add_argument('--output', help='Output path for 4K depth video')
     parser.add_argument('--no-nvenc', action='store_true', help='Disable NVENC, use CPU encoding')
     parser.add_argument('--force', action='store_true', help='Force reprocessing even if output exists')
-    guide = parser.add_mutually_exclusive_group()
-    guide.add_argument('--guide-start-frame', type=int, default=0,
-                       help='4K frame that matches depth_000000 (alignment offset in frames; default 0)')
-    guide.add_argument('--alignment-file', default=None,
-                       help='alignment_data.json of the audio aligner: --guide-start-frame = '
-                            'round(time_offset_seconds * fps of the 4K clip)')
+    from .align import add_guide_arguments, resolve_guide_start
+    add_guide_arguments(parser, 'depth_000000')
     from .png_gpu import add_png_arguments, png_options
     add_png_arguments(parser)
     from .register import add_apply_arguments, resolve
     add_apply_arguments(parser)
     args = parser.parse_args(argv)
-    if args.alignment_file is not None:
-        from .align import guide_start_frame_from
-        try:
-            args.guide_start_frame = guide_start_frame_from(args.alignment_file, args.video_4k)
-        except (OSError, ValueError, KeyError) as e:
-            print(f"Error: {e}")
-            return 1
-        print(f"Alignment file {args.alignment_file}: --guide-start-frame {args.guide_start_frame}")
+    if not resolve_guide_start(args):
+        return 1
     try:
         spatial = None
         if not args.no_spatial and (args.alignment_file is not None or args.spatial_map is not None):

@@ -26,6 +26,27 @@ def create_work_directory(base_path: str = "temp_pipeline") -> Path:
     return work_dir
 
 
+def sibling_frames_dir(output_path) -> Path:
+    """`<output without suffix>_frames`: where the upscale CLI, the convert CLI and the pipeline keep the PNGs of an output"""
+    return Path(str(Path(output_path).with_suffix("")) + "_frames")
+
+
+def finish_sequence(frames_dir: Path, pattern: str, output_path, fps: float, manifest: dict):
+    """the last step of a run that wrote frames_dir/<pattern>, on one process: H.264 at output_path when an ffmpeg binary exists
+    and the path ends in .mp4, else `manifest` (the caller's complete dict, in its key order) as JSON at output_path"""
+    ffmpeg = shutil.which("ffmpeg")
+    if ffmpeg and str(output_path).endswith(".mp4"):
+        cmd = [ffmpeg, "-y", "-v", "error", "-r", str(fps), "-f", "image2", "-i", str(frames_dir / pattern),
+               "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-preset", "medium", "-r", str(fps), str(output_path)]
+        res = subprocess.run(cmd, capture_output=True)
+        if res.returncode != 0:
+            print("FFmpeg error:")
+            print(res.stderr.decode())
+            raise RuntimeError(f"FFmpeg processing failed: rc={res.returncode}")
+    else:
+        Path(output_path).write_text(json.dumps(manifest, indent=1))
+
+
 def _parse_rate(s) -> float:
     # the reference eval()s ffprobe's "24000/1001" (utils.py:32); parse it instead
     try:
