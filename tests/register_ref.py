@@ -92,6 +92,41 @@ def match_scores(prof_a, prof_b, cand, bins: int):
     return out
 
 
+def match_scores_wrapping(prof_a, prof_b, cand, bins: int):
+    """match_scores for profile samples of any u32 value: the header's formula as a literal loop in Python integers, each of the
+    six sums reduced mod 2^64 and read as int64 (the record "wraps").  Below the headroom (samples < 2^21) nothing wraps and it
+    equals match_scores; it shares none of its code"""
+    pa, pb = np.atleast_2d(np.asarray(prof_a)), np.atleast_2d(np.asarray(prof_b))
+    (K, na), nb = pa.shape, pb.shape[1]
+    if not (8 <= bins <= 1024 and nb >= bins and pb.shape[0] == K):
+        raise ValueError("bins outside [8, 1024], nb < bins or unequal frame counts")
+    c = check_candidates(cand)
+    t = [(j * nb * Q) // bins for j in range(bins + 1)]
+    out = np.zeros((K, len(c), FIELDS), dtype=np.int64)
+
+    def means(P, e):
+        """floor means of the list P over [e_j, e_j+1), None where a bin leaves [0, len(P) 65536]"""
+        pre = [0]
+        for v in P:
+            pre.append(pre[-1] + v)
+        Pz = P + [0]
+        I = [pre[p >> 16] * Q + (p & 65535) * Pz[p >> 16] if 0 <= p <= len(P) * Q else None for p in e]
+        return [None if I[j] is None or I[j + 1] is None else (I[j + 1] - I[j]) // (e[j + 1] - e[j]) for j in range(len(e) - 1)]
+    for k in range(K):
+        A, B = [int(v) for v in pa[k]], [int(v) for v in pb[k]]
+        mb = means(B, t)
+        for ci, (a, b) in enumerate(c.tolist()):
+            ma = means(A, [((a * tj) >> 16) + b for tj in t])
+            rec = [0] * FIELDS
+            for j in range(bins - 1):
+                if ma[j] is None or ma[j + 1] is None:
+                    continue
+                da, db = ma[j + 1] - ma[j], mb[j + 1] - mb[j]
+                rec = [r + v for r, v in zip(rec, (1, da, db, da * db, da * da, db * db))]
+            out[k, ci] = [((r + (1 << 63)) % (1 << 64)) - (1 << 63) for r in rec]
+    return out
+
+
 def zncc(rec, bins: int):
     """the six sums -> Z float64 (same leading shape); NaN if a variance is 0 or n_pairs < bins / 2.  Python integers: the
     products n * sum(da db) reach 2^62 and the variances' product leaves int64"""

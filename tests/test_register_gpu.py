@@ -55,6 +55,74 @@ def test_profiles_padded_pitch_stride_and_odd_base(native):
     assert not rep, rep
 
 
+def profile_plan(n, W, H):
+    """v3d_register.hip's cut of n planes of W x H, restated: nseg segments of 1024 columns per row, ny row phases per workgroup,
+    L rows per lane, bands of R = L * ny rows"""
+    nseg = -(-W // 1024)
+    ny = 16 // nseg
+    L = min(max(-(-H * n // (ny * 1024)), 8), 256)
+    return dict(nseg=nseg, ny=ny, L=L, R=L * ny, bands=-(-H // (L * ny)))
+
+
+def _profiles_strided(native, g, pitch, stride, base):
+    """g u8 [n,H,W] laid out with rows `pitch` and frames `stride` bytes apart from byte `base` of an allocation, 255s in all the
+    slack, through the entry itself -> (col, row) u32"""
+    import torch
+    n, H, W = g.shape
+    buf = torch.full((base + n * stride,), 255, dtype=torch.uint8, device="cuda")
+    buf[base:].unflatten(0, (n, stride))[:, :H * pitch].unflatten(1, (H, pitch))[:, :, :W].copy_(native.to_device(g))
+    col = torch.empty((n, W), dtype=torch.int32, device="cuda")
+    row = torch.empty((n, H), dtype=torch.int32, device="cuda")
+    L = native.lib()
+    ws = torch.empty(L.v3d_plane_profiles_ws_bytes(n, W, H), dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    rc = L.v3d_plane_profiles_batch(P(buf.data_ptr() + base), n, W, H, pitch, stride, P(col.data_ptr()), P(row.data_ptr()), P(ws.data_ptr()),
+                                    native._stream())
+    assert rc == 0, L.v3d_last_error()
+    return _u32(col), _u32(row)
+
+
+# every segment count; the last segment holds one column, a partial 16-byte group, or is full.  H = R + 5 ny + 1: the first band
+# takes the four-row loop twice per phase, the second is ragged: the first phase has 4 + 2 rows, the others 4 + 1.  Each shape on the
+# vector route (aligned base, pitch and stride multiples of 16) and on the byte route (base + 1, pitch W + 3, stride padded)
+@pytest.mark.parametrize("nseg", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_profiles_every_segment_count(native, nseg):
+    L = native.lib()
+    ny, n = 16 // nseg, 2
+    H = 8 * ny + 5 * ny + 1
+    for W in (1024 * (nseg - 1) + 1, 1024 * nseg - 15, 1024 * nseg):
+        p = profile_plan(n, W, H)
+        assert (p["nseg"], p["ny"], p["L"], p["R"], p["bands"]) == (nseg, ny, 8, 8 * ny, 2)
+        assert H - p["R"] == 5 * ny + 1 and L.v3d_plane_profiles_ws_bytes(n, W, H) == 4 * n * p["bands"] * W
+        g = np.random.default_rng(W).integers(0, 256, (n, H, W), dtype=np.uint8)
+        g[1, :, W // 2:] = 255
+        wc, wr = RR.profiles(g)
+        pitch = (W + 15) // 16 * 16
+        for route, (pt, st, base) in (("vector", (pitch, H * pitch + 32, 0)), ("bytes", (W + 3, H * (W + 3) + 11, 1))):
+            col, row = _profiles_strided(native, g, pt, st, base)
+            rep = mismatch_report(col, wc, f"col {W}x{H} {route}") or mismatch_report(row, wr, f"row {W}x{H} {route}")
+            assert not rep, rep
+        if W % 16 == 0:                                             # the contiguous tensor of the binding is the vector route too
+            col, row = native.plane_profiles_batch(native.to_device(g))
+            assert np.array_equal(_u32(col), wc) and np.array_equal(_u32(row), wr)
+
+
+def test_profiles_more_than_eight_rows_per_lane(native):
+    """1025 x 8192, n = 9, random: two segments, eight phases, L = 9 rows per lane, 114 bands of 72 rows, the last with 56"""
+    import torch
+    n, W, H = 9, 1025, 8192
+    p = profile_plan(n, W, H)
+    assert (p["nseg"], p["ny"], p["L"], p["R"], p["bands"]) == (2, 8, 9, 72, 114) and H - 113 * 72 == 56
+    assert native.lib().v3d_plane_profiles_ws_bytes(n, W, H) == 4 * n * 114 * W
+    g = torch.randint(0, 256, (n, H, W), dtype=torch.uint8, device="cuda", generator=torch.Generator("cuda").manual_seed(9))
+    col, row = native.plane_profiles_batch(g)
+    col, row = _u32(col), _u32(row)
+    for f in range(n):                                              # per frame: the reference widens its input to int64
+        wc, wr = RR.profiles(g[f:f + 1].cpu().numpy())
+        rep = mismatch_report(col[f:f + 1], wc, f"col frame {f}") or mismatch_report(row[f:f + 1], wr, f"row frame {f}")
+        assert not rep, rep
+
+
 def test_profiles_headroom(native):
     """all-255 planes: 64 x 8192 reaches the largest column sum, 255 * 8192, through many bands; 512 planes of 1 x 8192 make a
     lane sum 256 rows, 255 * 256 = 65280, in a packed 16-bit field before it is widened"""
@@ -106,11 +174,13 @@ def test_profiles_refusals(native):
 
 # ---- match ----
 def _profiles(K, n, seed, kind):
-    if kind == "top":
-        return np.full((K, n), TOP, np.uint32)
-    if kind == "alt":
-        return np.tile(np.where(np.arange(n) % 2 == 0, 0, TOP).astype(np.uint32), (K, 1))
-    return np.random.default_rng(seed).integers(0, TOP + 1, (K, n)).astype(np.uint32)
+    """kind random / top / alt: samples up to TOP, inside the record's headroom; random32 / top32 / alt32: up to 2^32 - 1"""
+    top = 0xFFFFFFFF if kind.endswith("32") else TOP
+    if kind.startswith("top"):
+        return np.full((K, n), top, np.uint32)
+    if kind.startswith("alt"):
+        return np.tile(np.where(np.arange(n) % 2 == 0, 0, top).astype(np.uint32), (K, 1))
+    return np.random.default_rng(seed).integers(0, top + 1, (K, n)).astype(np.uint32)
 
 
 def _candidates(na, nb):
@@ -138,6 +208,17 @@ def test_match_bit_exact(native, na, nb, bins):
         n_pairs = want[0, :, 0]
         if kind == "random":
             assert n_pairs.max() == bins - 1 and n_pairs.min() == 0 and ((n_pairs > 0) & (n_pairs < bins - 1)).any()
+
+
+# samples of 2^21 and above "are legal memory-wise and wrap in the record": da and db reach +-(2^32 - 1), their products 2^64
+@pytest.mark.parametrize("na,nb,bins", [(23, 31, 8), (256, 512, 512)])
+def test_match_wraps_with_full_range_samples(native, na, nb, bins):
+    cand = _candidates(na, nb)
+    for kind, kind_b in (("random32", "random32"), ("top32", "top32"), ("top32", "random32"), ("alt32", "alt32"), ("alt32", "random32")):
+        a, b = _profiles(2, na, na + bins, kind), _profiles(2, nb, nb + 7 * bins, kind_b)
+        got = native.profile_match_scores(native.to_device(a.view(np.int32)), native.to_device(b.view(np.int32)), cand, bins).cpu().numpy()
+        want = RR.match_scores_wrapping(a, b, cand, bins)
+        assert np.array_equal(got, want), f"{kind} {na}->{nb} bins {bins}: records {np.argwhere((got != want).any(axis=2)).tolist()[:6]} differ"
 
 
 def test_match_refuses_candidates_outside_the_domain(native):
@@ -233,6 +314,32 @@ def test_warp_padded_stride_at_an_odd_element_offset(native):
     rep = mismatch_report(o[1:-1].reshape(n, Ho, Wo), RR.warp(s, *m, 7, Wo, Ho), "padded warp")
     assert not rep, rep
     assert o[0] == 0x5A5A and o[-1] == 0x5A5A
+
+
+# a workgroup holds a lead group of 0 .. 3 pixels and 255 (blockIdx.x > 0: 256) groups of four: 1020 is the widest row of one
+# workgroup at lead 0, 1021 .. 1023 are with a lead, 1024 and 1025 need the second workgroup at every lead, 2047 a third, 3840 is
+# the product's.  Dense: rows at 8-byte multiples where Wo is a multiple of 4; at element offset 1 the lead takes all of 0 .. 3 over
+# the rows of the odd widths
+@pytest.mark.parametrize("Wo", [1020, 1021, 1022, 1023, 1024, 1025, 2047, 3840])
+def test_warp_workgroup_seams(native, Wo):
+    import torch
+    Ho, n, Ws, Hs = 3, 2, (Wo + 1) // 2, 2
+    s = _planes(n, Hs, Ws, Wo)
+    d = native.to_device(s.view(np.int16))
+    L, maps = native.lib(), _maps(Ws, Hs, Wo, Ho)
+    for off in (4, 1):
+        out = torch.empty((off + n * Ho * Wo + 4,), dtype=torch.int16, device="cuda")
+        assert out.data_ptr() % 8 == 0
+        if off == 1 and Wo % 2:
+            assert {((out.data_ptr() + 2 * (off + r * Wo)) % 8) // 2 for r in range(n * Ho)} == {0, 1, 2, 3}
+        for name in ("fit", "half-pixel shift", "one past"):
+            out.fill_(0x5A5A)
+            rc = L.v3d_warp_u16_batch(P(d.data_ptr()), n, Ws, Hs, Ws * Hs, *maps[name], 4242, P(out.data_ptr() + 2 * off), Wo, Ho, native._stream())
+            assert rc == 0, L.v3d_last_error()
+            o = out.cpu().numpy().view(np.uint16)
+            rep = mismatch_report(o[off:-4].reshape(n, Ho, Wo), RR.warp(s, *maps[name], 4242, Wo, Ho), f"warp -> {Wo}x{Ho} {name} offset {off}")
+            assert not rep, rep
+            assert (o[:off] == 0x5A5A).all() and (o[-4:] == 0x5A5A).all()
 
 
 def test_warp_refusals(native):

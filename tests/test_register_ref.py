@@ -78,6 +78,23 @@ def test_match_record_against_a_loop():
         RR.match_scores(A, B, [(Q, RR.B_MAX + 1)], 8)
 
 
+def test_wrapping_match_is_the_record_below_the_headroom_and_wraps_above():
+    """match_scores_wrapping (Python integers, reduced mod 2^64 at the end) on the in-headroom inputs of tests/test_register_gpu.py,
+    and one record worked out by hand: alternating 0 / 2^32 - 1 under the identity has da = db = +-(2^32 - 1) in all 7 pairs, each
+    square is 2^64 - 2^33 + 1, each product of the two its negative"""
+    import test_register_gpu as G
+    for na, nb, bins in ((23, 31, 8), (256, 512, 8), (256, 512, 512)):
+        cand = G._candidates(na, nb)
+        for kind, kind_b in (("random", "random"), ("top", "top"), ("top", "random"), ("alt", "alt")):
+            a, b = G._profiles(2, na, na + bins, kind), G._profiles(2, nb, nb + 7 * bins, kind_b)
+            assert np.array_equal(RR.match_scores_wrapping(a, b, cand, bins), RR.match_scores(a, b, cand, bins)), (na, nb, bins, kind)
+    alt = G._profiles(1, 8, 0, "alt32")
+    assert alt.tolist() == [[0, 0xFFFFFFFF] * 4]
+    rec = RR.match_scores_wrapping(alt, alt, [(Q, 0)], 8)[0, 0].tolist()
+    assert rec == [7, (1 << 32) - 1, (1 << 32) - 1, 7 * (1 - (1 << 33)), 7 * (1 - (1 << 33)), 7 * (1 - (1 << 33))]
+    assert RR.match_scores_wrapping(alt, 0xFFFFFFFF - alt, [(Q, 0)], 8)[0, 0, 3] == -7 * (1 - (1 << 33))
+
+
 def test_zncc_from_the_six_sums():
     da, db = np.array([3, -4, 10, 0, 7]), np.array([6, -8, 21, 1, 13])
     rec = np.array([len(da), da.sum(), db.sum(), (da * db).sum(), (da * da).sum(), (db * db).sum()])

@@ -57,6 +57,18 @@ def test_widths_gains_and_packings(driver, tmp_path, W, H, sub):
         _call(driver, tmp_path, F, D, gl, gr, conv, sub, packing, (3 * i + W) % 16, 2 * ((i + W + H) % 8))
 
 
+# the row staging is sized to the byte for 8192 pixels whose BGR row starts at byte 15 of a 16-byte block (1537 chunks) and whose
+# depth row starts at byte 14 (1025 chunks), the parked words right behind: the dynamic LDS of the side-by-side march is a heap block
+# of the launch's size, the static LDS of the anaglyph march an array of st_lds_bytes, and AddressSanitizer has a red zone behind each
+@pytest.mark.parametrize("sub", [0, 1])
+@pytest.mark.parametrize("packing", [P.FULL_SBS, P.ANAGLYPH_DUBOIS])
+def test_widest_row_at_the_worst_alignment(driver, tmp_path, packing, sub):
+    W, H = 8192, 2
+    F = np.random.default_rng(15).integers(0, 256, (1, H, W, 3), dtype=np.uint8)
+    D = S.scene_depth("planar", H, W, 14 + sub)[None]
+    _call(driver, tmp_path, F, D, *R.stereo_gains(60, 0.5, 0.5), sub, packing, 15, 14)
+
+
 @pytest.mark.parametrize("sub", [0, 1])
 def test_nearest_key_beyond_a_wave_or_absent(driver, tmp_path, sub):
     F, D, (gl, gr, conv) = R.far_key_scene()

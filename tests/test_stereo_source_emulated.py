@@ -17,20 +17,21 @@ driver = E.driver_fixture("stereo_source", ["v3d_stereo.hip"], [ENTRY])
 MAPS = [(65536, 0, 65536, 0), (21845, -9000, 30000, 77), (200000, -3 << 16, 150000, 5 << 16), (4096, 1 << 30, 1 << 20, -(1 << 30))]
 
 
-def _call(driver, tmp, F, D, gains, sub, packing, sbs, fill, m, rowpad=0, framepad=0, rc=0):
-    """F u8 [n,H,W,3], D u16 [n,H,W], sbs u8 [n,Hs,Ws,3]; SBS rows rowpad bytes, frames framepad bytes apart beyond their size"""
+def _call(driver, tmp, F, D, gains, sub, packing, sbs, fill, m, rowpad=0, framepad=0, rc=0, fphase=5, dphase=6, want=None):
+    """F u8 [n,H,W,3], D u16 [n,H,W], sbs u8 [n,Hs,Ws,3]; SBS rows rowpad bytes, frames framepad bytes apart beyond their size; the
+    frame and the depth at bytes fphase and dphase of a 16-byte block; want: the expected frames where the caller has them"""
     n, H, W = D.shape
     Hs, Ws = sbs.shape[1:3]
     if rc:                                                     # a refused call: the poisoned output stays as it is
         ow, oh = P.output_size(packing, W, H)
         want = np.zeros((n, oh, ow, 3), np.uint8)
-    else:
+    elif want is None:
         want = np.stack([X.render(F[i], D[i], *gains, packing, bool(sub), sbs[i], fill, *m) for i in range(n)])
     pitch = 3 * Ws + rowpad
     ss = Hs * pitch + framepad
 
     def make(gp):
-        (fbuf, foff), (dbuf, doff) = E.chunked("frame", F.reshape(-1), 5, gp), E.chunked("depth", D.reshape(-1), 6, gp)
+        (fbuf, foff), (dbuf, doff) = E.chunked("frame", F.reshape(-1), fphase, gp), E.chunked("depth", D.reshape(-1), dphase, gp)
         sb = np.full((n - 1) * ss + (Hs - 1) * pitch + 3 * Ws, gp, np.uint8)     # ends on the last payload byte
         for i in range(n):
             for j in range(Hs):
@@ -57,6 +58,43 @@ def test_sizes_packings_and_fills(driver, tmp_path, W, H, sub):
         packing = packs[(fill + W + sub) % len(packs)]
         gains = [R.stereo_gains(24, 0.5, 0.5), R.stereo_gains(40, 0.5, 0.0), (W * 256 + 77, -(W * 256 + 77), 0)][(fill + H) % 3]
         _call(driver, tmp_path, F, D, gains, sub, packing, sbs, fill, MAPS[(fill + W) % len(MAPS)])
+
+
+# every instantiation with a source that is wider than 8 pixels per thread (16 up to 4096, 32 above), both renderers, all seven
+# packings, both eyes filled; H = 2: one row pair.  The 8-pixel ones run above
+WIDE_SIZES = [(2050, 2), (4100, 2)]
+
+
+def test_every_source_instantiation_is_launched():
+    """the 3 x 2 x 5 instantiations k_render_stereo<PPT, SUB, K, StSource> against the cases of test_every_packing"""
+    k_of = {P.FULL_SBS: "sbs", P.HALF_SBS: "sbs", P.FULL_TB: "tb", P.HALF_TB: "htb", P.ROWS: "rows", P.ANAGLYPH_COLOUR: "ana",
+            P.ANAGLYPH_DUBOIS: "ana"}
+    ppt = lambda W: 8 if W <= 2048 else 16 if W <= 4096 else 32
+    cases = {(ppt(W), sub, k_of[p]) for W, H in WIDE_SIZES + [(254, 6)] for sub in (0, 1) for p in P.PACKINGS if P.output_size(p, W, H)}
+    assert cases == {(n, sub, k) for n in (8, 16, 32) for sub in (0, 1) for k in ("sbs", "tb", "htb", "rows", "ana")} and len(cases) == 30
+
+
+@pytest.mark.parametrize("sub", [0, 1])
+@pytest.mark.parametrize("W,H", WIDE_SIZES + [(254, 6)])
+def test_every_packing(driver, tmp_path, W, H, sub):
+    F, D, sbs = _scene(1, W, H, 322, 45, W + 7 + sub, kinds=("planar",))
+    gains = R.stereo_gains(60, 0.5, 0.5)
+    EL, ER = X.eyes(F[0], D[0], *gains, bool(sub), sbs[0], 3, *MAPS[1])
+    plain = P.eyes(F[0], D[0], *gains, bool(sub))
+    assert (EL != plain[0]).any() and (ER != plain[1]).any()    # the fill does change both eyes
+    for packing in P.PACKINGS:
+        _call(driver, tmp_path, F, D, gains, sub, packing, sbs, 3, MAPS[1], want=P.pack(EL, ER, packing)[None])
+
+
+# the row staging is sized to the byte for 8192 pixels whose BGR row starts at byte 15 of a 16-byte block (1537 chunks) and whose
+# depth row starts at byte 14 (1025 chunks), the parked words right behind: under AddressSanitizer the dynamic LDS of the side-by-side
+# march is a heap block of the launch's size and the static LDS of the anaglyph march an array of st_lds_bytes, each with a red zone
+# right behind.  3 * 8192 and 2 * 8192 are multiples of 16: both rows have these offsets
+@pytest.mark.parametrize("sub", [0, 1])
+@pytest.mark.parametrize("packing", [P.FULL_SBS, P.ANAGLYPH_DUBOIS])
+def test_widest_row_at_the_worst_alignment(driver, tmp_path, packing, sub):
+    F, D, sbs = _scene(1, 8192, 2, 322, 45, 15 + sub, kinds=("planar",))
+    _call(driver, tmp_path, F, D, R.stereo_gains(60, 0.5, 0.5), sub, packing, sbs, 3, MAPS[1], fphase=15, dphase=14)
 
 
 @pytest.mark.parametrize("sub", [0, 1])

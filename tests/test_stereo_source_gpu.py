@@ -65,6 +65,78 @@ def test_every_packing(native, sub):
         T._check(_gpu(native, F, D, gains, packing, sub, sbs, 3, MAPS[0]), P.pack(EL, ER, packing), f"{P.NAMES[packing]} sub={sub}")
 
 
+# ---- every instantiation of the march with a source: pixels per thread (8 up to 2048, 16 up to 4096, 32 above) x renderer x what
+# becomes of the eye colours.  test_every_packing has the 8-pixel ones; the wide ones run at H = 6 (a band of four rows and a ragged
+# one holding one row pair), which allows every packing
+K_OF = {P.FULL_SBS: "sbs", P.HALF_SBS: "sbs", P.FULL_TB: "tb", P.HALF_TB: "htb", P.ROWS: "rows", P.ANAGLYPH_COLOUR: "ana",
+        P.ANAGLYPH_DUBOIS: "ana"}
+WIDE_SIZES = [(2050, 6), (4100, 6)]
+# (packing, fill_eyes): both eyes filled in all seven packings, one eye in two packings each
+WIDE_CASES = [(p, 3) for p in P.PACKINGS] + [(P.FULL_SBS, 1), (P.ANAGLYPH_COLOUR, 1), (P.HALF_TB, 2), (P.ROWS, 2)]
+
+
+def _ppt(W):
+    return 8 if W <= 2048 else 16 if W <= 4096 else 32
+
+
+def test_every_source_instantiation_is_launched():
+    """the 3 x 2 x 5 = 30 instantiations k_render_stereo<PPT, SUB, K, StSource> against the cases of test_every_packing (254 x 6,
+    all seven packings, both renderers) and of test_every_wide_instantiation"""
+    cases = {(_ppt(254), sub, K_OF[p]) for sub in (False, True) for p in P.PACKINGS}
+    cases |= {(_ppt(W), sub, K_OF[p]) for W, _ in WIDE_SIZES for sub in (False, True) for p, _ in WIDE_CASES}
+    assert cases == {(ppt, sub, k) for ppt in (8, 16, 32) for sub in (False, True) for k in ("sbs", "tb", "htb", "rows", "ana")}
+    assert len(cases) == 30
+    for W, H in WIDE_SIZES:                                        # every packing is legal at the wide sizes
+        for p, _ in WIDE_CASES:
+            P.output_size(p, W, H)
+
+
+@pytest.mark.parametrize("sub", [False, True])
+@pytest.mark.parametrize("W,H", WIDE_SIZES)
+def test_every_wide_instantiation(native, W, H, sub):
+    F = np.random.default_rng(W + H).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    D, sbs, gains = T._depth("planar", H, W, W + 9), _sbs(322, 45, 1), R.stereo_gains(60, 0.5, 0.5)
+    plain = P.eyes(F, D, *gains, sub)
+    eyes = {fill: X.eyes(F, D, *gains, sub, sbs, fill, *MAPS[0]) for fill in (1, 2, 3)}
+    for fill, (EL, ER) in eyes.items():                            # the fill changes the eyes it names, and only those
+        assert (EL != plain[0]).any() == bool(fill & 1) and (ER != plain[1]).any() == bool(fill & 2)
+    for packing, fill in WIDE_CASES:
+        T._check(_gpu(native, F, D, gains, packing, sub, sbs, fill, MAPS[0]), P.pack(*eyes[fill], packing),
+                 f"{W}x{H} {P.NAMES[packing]} sub={sub} fill={fill}")
+
+
+# ---- the widest row at the worst alignment: the row staging in LDS is sized to the byte for 8192 pixels whose BGR row starts at
+# byte 15 of a 16-byte block (1537 chunks) and whose depth row starts at byte 14 (1025 chunks), the parked words right behind.
+# 3 * 8192 and 2 * 8192 are multiples of 16: every row of every frame has these offsets
+@pytest.mark.parametrize("source", [False, True])
+@pytest.mark.parametrize("sub", [False, True])
+def test_widest_row_at_the_worst_alignment(native, sub, source):
+    W, n = 8192, 2
+    rng = np.random.default_rng(15 + sub)
+    sbs, gains = np.stack([_sbs(322, 45, 5 + i) for i in range(n)]), R.stereo_gains(60, 0.5, 0.5)
+    s = torch.from_numpy(sbs).cuda()
+    # FULL_SBS: dynamic LDS; HALF_SBS; HALF_TB at H = 6: parks packed rows; ANAGLYPH_DUBOIS: the largest static LDS
+    for packing, H in ((P.FULL_SBS, 5), (P.HALF_SBS, 5), (P.HALF_TB, 6), (P.ANAGLYPH_DUBOIS, 5)):
+        F = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+        D = np.stack([T._depth(("planar", "noise")[i], H, W, 100 + i + H) for i in range(n)])
+        per = H * W * 3
+        cap = torch.full((n + 1, per + 48), 7, dtype=torch.uint8, device="cuda")
+        frames = cap.flatten()[15:15 + n * (per + 48)].unflatten(0, (n, per + 48))[:, :per].unflatten(1, (H, W, 3))
+        frames.copy_(torch.from_numpy(F).cuda())
+        dcap = torch.zeros(n * H * W + 16, dtype=torch.int16, device="cuda")
+        depth = dcap[7:7 + n * H * W].unflatten(0, (n, H, W))
+        depth.copy_(torch.from_numpy(D.view(np.int16)).cuda())
+        assert cap.data_ptr() % 16 == 0 and frames.data_ptr() % 16 == 15 and frames.stride(0) == per + 48 and frames.stride(1) == 3 * W
+        assert dcap.data_ptr() % 16 == 0 and depth.data_ptr() % 16 == 14 and depth.is_contiguous()
+        if source:
+            got = native.render_stereo_source_batch(frames, depth, *gains, packing, s, 3, *MAPS[0], subpixel=sub).cpu().numpy()
+        else:
+            got = native.render_stereo_packed_batch(frames, depth, *gains, packing, subpixel=sub).cpu().numpy()
+        for i in range(n):
+            want = (X.render(F[i], D[i], *gains, packing, sub, sbs[i], 3, *MAPS[0]) if source else P.render(F[i], D[i], *gains, packing, sub))
+            T._check(got[i], want, f"8192x{H} {P.NAMES[packing]} sub={sub} source={source} frame {i}")
+
+
 @pytest.mark.parametrize("sub", [False, True])
 def test_holes_longer_than_a_waves_run(native, sub):
     F, D, gains = R.far_key_scene()

@@ -208,8 +208,9 @@ __global__ __launch_bounds__(64) void k_rg_match(const uint32_t* __restrict__ pr
         if (s0 < 0 || s2 > lim) continue;                           // s0 < s1 < s2: both bins lie inside the source
         const long long da = rg_mean(A, preA, na, s1, s2) - rg_mean(A, preA, na, s0, s1);
         const long long db = rg_mean(B, preB, nb, t1, t2) - rg_mean(B, preB, nb, t0, t1);
-        np += 1; sa += (unsigned long long)da; sb += (unsigned long long)db;
-        sab += (unsigned long long)(da * db); saa += (unsigned long long)(da * da); sbb += (unsigned long long)(db * db);
+        const unsigned long long ua = (unsigned long long)da, ub = (unsigned long long)db;     // unsigned products: samples of 2^21 and
+        np += 1; sa += ua; sb += ub;                                                           // above wrap, as the header says
+        sab += ua * ub; saa += ua * ua; sbb += ub * ub;
     }
     np = wave_sum_u64(np); sa = wave_sum_u64(sa); sb = wave_sum_u64(sb);
     sab = wave_sum_u64(sab); saa = wave_sum_u64(saa); sbb = wave_sum_u64(sbb);
