@@ -8,6 +8,7 @@
  *
  *   v3d_sbs_to_gray        depth.py:250-268 split_sbs_frame (cv2.resize INTER_LANCZOS4) +
  *                          depth.py:274-275, 337-338 cvtColor BGR->RGB->GRAY
+ *   v3d_tb_to_gray         the same two sites for a top-bottom (over-under) frame: the resize runs down the columns
  *   v3d_sgbm_create        depth.py:315-325 cv2.StereoSGBM_create(...)
  *   v3d_sgbm_compute[_batch]  depth.py:341 stereo.compute(left_gray, right_gray) -> int16 x16
  *   v3d_disp_to_depth      depth.py:341 .astype(float32)/16.0 and depth.py:374 clamp <=0 -> 0
@@ -195,6 +196,29 @@ int v3d_sbs_to_gray_batch(const uint8_t* sbs_bgr, int n, int W, int H, int pitch
 /* the BGR halves themselves (split_sbs_frame's return value), [H][outW][3] */
 int v3d_split_sbs(const uint8_t* sbs_bgr, int W, int H, int pitch, int unsqueeze,
                   uint8_t* left_bgr, uint8_t* right_bgr, void* stream);
+
+/* Top-bottom (over-under) input: the same three entries for a frame whose left eye is on top.  TB BGR u8 [H][pitch] (W*3 payload
+   bytes per row), H even, Hh = H / 2: eye e (0 = left = top) is rows e*Hh .. e*Hh + Hh - 1.
+   unsqueeze == 0: the eye's rows as they are, outputs W x Hh.
+   unsqueeze != 0: outputs W x H, cv2.resize(eye, (W, H), INTER_LANCZOS4) -- split_sbs_frame with the axes swapped.  Per channel of
+   eye plane S, t0 / t1 the 2^11-scaled int16 taps of the fractions 0.75 / 0.25 (the ones v3d_sbs_to_gray runs along the row):
+     acc(2m)     = sum k = 0 .. 7 of t0[k] S[clamp(m - 4 + k, 0, Hh - 1)][x]
+     acc(2m + 1) = sum k = 0 .. 7 of t1[k] S[clamp(m - 3 + k, 0, Hh - 1)][x],    v = clamp((acc + 1024) >> 11, 0, 255);
+   rows are clamped per eye: no tap of the top eye's last rows reads the bottom eye's first ones.  Gray is v3d_sbs_to_gray's luma of
+   the three clamped channels.  Bit-exact contract: tests/tb_ref.py.
+   Memory contract, that of the SBS entries: only the 3 W payload bytes of rows 0 .. H - 1 of each frame are read (no pitch padding,
+   nothing before or behind the buffer), tb_bgr needs no alignment, the outputs are written densely, exactly once, and nothing else
+   is written.  No allocation, no synchronisation, one launch.
+   V3D_ERR_ARG: a null pointer, n < 1, H odd or < 2, W < 1, pitch < 3 W, frame_stride < H*pitch with n > 1 (n == 1 ignores the
+   stride).  A refused call enqueues nothing. */
+int v3d_tb_to_gray(const uint8_t* tb_bgr, int W, int H, int pitch, int unsqueeze,
+                   uint8_t* left_gray, uint8_t* right_gray, void* stream);
+/* n frames in one launch: frame f at tb_bgr + f*frame_stride bytes; outputs packed [n][outH][W] */
+int v3d_tb_to_gray_batch(const uint8_t* tb_bgr, int n, int W, int H, int pitch, size_t frame_stride,
+                         int unsqueeze, uint8_t* left_gray, uint8_t* right_gray, void* stream);
+/* the BGR eyes themselves, [outH][W][3] */
+int v3d_split_tb(const uint8_t* tb_bgr, int W, int H, int pitch, int unsqueeze,
+                 uint8_t* left_bgr, uint8_t* right_bgr, void* stream);
 
 int v3d_disp_to_depth(const int16_t* disp16, size_t n, float* depth_out, void* stream);
 

@@ -1,5 +1,6 @@
 // v3d_pre.hip -- the per-frame steps either side of the matcher:
-//   depth.py:250-268 split_sbs_frame (cv2.resize INTER_LANCZOS4 horizontal x2 "unsqueeze"),
+//   depth.py:250-268 split_sbs_frame (cv2.resize INTER_LANCZOS4 horizontal x2 "unsqueeze"), and the same for a top-bottom frame
+//   (vertical x2, k_split_tb),
 //   depth.py:274-275 + 337-338 cvtColor (BGR->RGB->GRAY), depth.py:341/374 (/16, clamp),
 //   and the rounding of the 4K depth to the PNG sink's 16-bit sample.
 // (depth.py:397-406 save_depth_map, min-max -> uint16, lives in v3d_range.hip with the other range entries.)
@@ -169,6 +170,150 @@ extern "C" int v3d_split_sbs(const uint8_t* sbs, int W, int H, int pitch, int un
 extern "C" int v3d_sbs_to_gray_batch(const uint8_t* sbs, int n, int W, int H, int pitch, size_t frame_stride, int unsqueeze, uint8_t* L, uint8_t* R, void* stream)
 {
     return split_common(sbs, W, H, pitch, unsqueeze, L, R, true, n, frame_stride, (hipStream_t)stream);
+}
+
+// ---- top-bottom input: eye e is rows e*Hh .. e*Hh + Hh - 1 of the frame, Hh = H / 2 (left eye on top) ----
+// The unsqueeze is the same resize with the axes swapped: the 8 taps run DOWN a column, so they act on bytes independently --
+// no 3-byte stride, no LDS.  A thread owns 4 pixels (12 bytes, three dwords) of one eye and marches down a band of TB_BAND
+// source rows with the nine rows m-4 .. m+4 in registers: output rows 2m (frac 0.75, rows m-4 .. m+3) and 2m+1 (frac 0.25,
+// rows m-3 .. m+4) share seven of their eight input rows.  Rows are clamped to the eye: no tap of the top eye's last rows
+// reads the bottom eye's first ones.  A band re-reads 8 halo rows (13 % at 60); 540 = 9 * 60, so a 1080p eye has no ragged
+// band, and 2 eyes * 34 frames * 9 bands * 2 column blocks = 1224 workgroups fill 256 CUs at 4.8 waves per SIMD.
+#ifndef TB_BAND
+#define TB_BAND 60
+#endif
+template <bool GRAY>
+__global__ __launch_bounds__(256) void k_split_tb(const uint8_t* __restrict__ tb, int W, int H, int pitch, int unsqueeze,
+                                                  LanczosTaps taps, uint8_t* __restrict__ outL, uint8_t* __restrict__ outR,
+                                                  size_t in_stride)
+{
+    const int Hh = H >> 1, oh = unsqueeze ? H : Hh;
+    const int x = (blockIdx.x * 256 + threadIdx.x) * 4;             // first of this thread's pixels
+    if (x >= W) return;
+    const int np = min(4, W - x);                                   // < 4 in the last group of a row when W % 4 != 0
+    const int eye = blockIdx.z & 1, f = blockIdx.z >> 1;
+    const int ma = blockIdx.y * TB_BAND, mb = min(ma + TB_BAND, Hh);
+    const uint8_t* src = tb + (size_t)f * in_stride + (size_t)eye * Hh * pitch + (size_t)x * 3;   // this thread's bytes of eye row 0
+    uint8_t* out = (eye ? outR : outL) + (size_t)f * ((size_t)W * oh * (GRAY ? 1 : 3));
+    int tp0[8], tp1[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { tp0[k] = taps.t[0][k]; tp1[k] = taps.t[1][k]; }
+
+    // Load plan, the same for every row: three dwords when all four pixels exist and every row's copy of them is aligned (pitch a
+    // multiple of 4 and an aligned start; 12 bytes per thread keep the alignment along the row).  Otherwise twelve byte loads, the
+    // offsets clamped to the row's payload: nothing in front of the frame, in the pitch padding or behind the last row is read.
+    const bool fast = np == 4 && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0;
+    const int last = np * 3 - 1;
+    auto load_row = [&](int y, uint32_t* d) {
+        const uint8_t* row = src + (size_t)y * pitch;
+        if (fast) {
+            const uint32_t* p = reinterpret_cast<const uint32_t*>(row);
+            d[0] = p[0]; d[1] = p[1]; d[2] = p[2];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                d[k] = (uint32_t)row[min(4 * k, last)] | (uint32_t)row[min(4 * k + 1, last)] << 8 |
+                       (uint32_t)row[min(4 * k + 2, last)] << 16 | (uint32_t)row[min(4 * k + 3, last)] << 24;
+        }
+    };
+    // one output row of this thread: v = its 12 channel values (b, g, r of four pixels).  Dword stores when the group is whole
+    // and its first output byte is aligned (a dense output row of W or 3 W bytes may move the alignment from row to row)
+    auto emit = [&](int yo, const int* v) {
+        if (GRAY) {
+            uint8_t* o = out + (size_t)yo * W + x;
+            int g[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) g[j] = gray_of(v[3 * j], v[3 * j + 1], v[3 * j + 2]);
+            if (np == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0)
+                *reinterpret_cast<uint32_t*>(o) = (uint32_t)g[0] | (uint32_t)g[1] << 8 | (uint32_t)g[2] << 16 | (uint32_t)g[3] << 24;
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; j++) if (j < np) o[j] = (uint8_t)g[j];
+            }
+        } else {
+            uint8_t* o = out + ((size_t)yo * W + x) * 3;
+            if (np == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    reinterpret_cast<uint32_t*>(o)[k] = (uint32_t)v[4 * k] | (uint32_t)v[4 * k + 1] << 8 | (uint32_t)v[4 * k + 2] << 16 | (uint32_t)v[4 * k + 3] << 24;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 12; i++) if (i <= last) o[i] = (uint8_t)v[i];
+            }
+        }
+    };
+
+    uint32_t pre[3] = { 0u, 0u, 0u };
+    if (!unsqueeze) {                                               // the eye's rows as they are
+        load_row(ma, pre);
+        for (int m = ma; m < mb; m++) {
+            const uint32_t cur[3] = { pre[0], pre[1], pre[2] };
+            if (m + 1 < mb) load_row(m + 1, pre);                   // flies while this row is computed
+            int v[12];
+#pragma unroll
+            for (int i = 0; i < 12; i++) v[i] = (cur[i >> 2] >> (8 * (i & 3))) & 255;
+            emit(m, v);
+        }
+        return;
+    }
+    uint32_t r[9][3];                                               // rows m-4 .. m+4, clamped to the eye
+#pragma unroll
+    for (int k = 0; k < 9; k++) load_row(min(max(ma - 4 + k, 0), Hh - 1), r[k]);
+    for (int m = ma; m < mb; m++) {
+        // row m+5 is fetched before rows 2m and 2m+1 are computed, for k_split_sbs's reason: fetched where it is needed, every
+        // step waits for its bytes
+        if (m + 1 < mb) load_row(min(m + 5, Hh - 1), pre);
+        int v0[12], v1[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) {
+            int a0 = 0, a1 = 0;
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                const int s = (r[k][i >> 2] >> (8 * (i & 3))) & 255;
+                if (k < 8) a0 += s * tp0[k];
+                if (k > 0) a1 += s * tp1[k - 1];
+            }
+            // the horizontal pass is the identity tap (2048): (a * 2048 + 2^21) >> 22 == (a + 2^10) >> 11, as in k_split_sbs
+            v0[i] = min(max((a0 + 1024) >> 11, 0), 255);
+            v1[i] = min(max((a1 + 1024) >> 11, 0), 255);
+        }
+        emit(2 * m, v0);
+        emit(2 * m + 1, v1);
+#pragma unroll
+        for (int k = 0; k < 8; k++) { r[k][0] = r[k + 1][0]; r[k][1] = r[k + 1][1]; r[k][2] = r[k + 1][2]; }
+        r[8][0] = pre[0]; r[8][1] = pre[1]; r[8][2] = pre[2];
+    }
+}
+
+static int split_tb_common(const uint8_t* tb, int W, int H, int pitch, int unsqueeze, uint8_t* L, uint8_t* R, bool gray, int n, size_t in_stride, hipStream_t st)
+{
+    if (n < 1) { v3d_set_error("bad batch"); return V3D_ERR_ARG; }
+    if (!tb || !L || !R) { v3d_set_error("null pointer"); return V3D_ERR_ARG; }
+    if (H % 2 != 0) { v3d_set_error("top-bottom frame height must be even"); return V3D_ERR_ARG; }
+    if (W < 1 || H < 2 || pitch < W * 3) { v3d_set_error("bad top-bottom geometry %dx%d pitch %d", W, H, pitch); return V3D_ERR_ARG; }
+    if (n > 1 && in_stride < (size_t)H * pitch) { v3d_set_error("frame stride %zu below the frame size %zu (H * pitch)", in_stride, (size_t)H * pitch); return V3D_ERR_ARG; }
+    LanczosTaps taps;
+    lanczos4_taps_host(0.75f, taps.t[0]);
+    lanczos4_taps_host(0.25f, taps.t[1]);
+    const dim3 grid(v3d_cdiv(v3d_cdiv(W, 4), 256), v3d_cdiv(H / 2, TB_BAND), 2 * n);
+    if (gray) hipLaunchKernelGGL(k_split_tb<true>, grid, dim3(256), 0, st, tb, W, H, pitch, unsqueeze, taps, L, R, in_stride);
+    else hipLaunchKernelGGL(k_split_tb<false>, grid, dim3(256), 0, st, tb, W, H, pitch, unsqueeze, taps, L, R, in_stride);
+    V3D_LAUNCH_CHECK();
+    return V3D_OK;
+}
+
+extern "C" int v3d_tb_to_gray(const uint8_t* tb, int W, int H, int pitch, int unsqueeze, uint8_t* L, uint8_t* R, void* stream)
+{
+    return split_tb_common(tb, W, H, pitch, unsqueeze, L, R, true, 1, 0, (hipStream_t)stream);
+}
+extern "C" int v3d_split_tb(const uint8_t* tb, int W, int H, int pitch, int unsqueeze, uint8_t* L, uint8_t* R, void* stream)
+{
+    return split_tb_common(tb, W, H, pitch, unsqueeze, L, R, false, 1, 0, (hipStream_t)stream);
+}
+// n frames: frame f at tb + f*frame_stride (bytes); outputs packed [n][outH][W]
+extern "C" int v3d_tb_to_gray_batch(const uint8_t* tb, int n, int W, int H, int pitch, size_t frame_stride, int unsqueeze, uint8_t* L, uint8_t* R, void* stream)
+{
+    return split_tb_common(tb, W, H, pitch, unsqueeze, L, R, true, n, frame_stride, (hipStream_t)stream);
 }
 
 __global__ __launch_bounds__(256) void k_bgr_to_gray(const uint8_t* __restrict__ bgr, size_t n, uint8_t* __restrict__ gray)

@@ -67,6 +67,9 @@ SIGNATURES = {
     "v3d_sbs_to_gray": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
     "v3d_sbs_to_gray_batch": (ci, [vp, ci, ci, ci, ci, sz, ci, vp, vp, vp]),
     "v3d_split_sbs": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_tb_to_gray": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+    "v3d_tb_to_gray_batch": (ci, [vp, ci, ci, ci, ci, sz, ci, vp, vp, vp]),
+    "v3d_split_tb": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
     "v3d_disp_to_depth": (ci, [vp, sz, vp, vp]),
     "v3d_depth_to_u16": (ci, [vp, sz, vp, vp, vp]),
     "v3d_depth_to_u16_batch": (ci, [vp, ci, sz, sz, vp, vp, vp]),
@@ -386,6 +389,44 @@ def split_sbs(sbs, unsqueeze=True):
     L = torch.empty((H, ow, 3), dtype=torch.uint8, device=sbs.device)
     R = torch.empty_like(L)
     _call("v3d_split_sbs", sbs.device, _dev(sbs, torch.uint8, "sbs"), W, H, W * 3, int(bool(unsqueeze)),
+          _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"))
+    return L, R
+
+
+def _tb_out_height(H, unsqueeze):
+    if H % 2 or H < 2:
+        raise ValueError("top-bottom frame height must be even")
+    return H if unsqueeze else H // 2
+
+
+def tb_to_gray(tb, unsqueeze=True):
+    """tb: uint8 [H,W,3] BGR device tensor, left eye on top -> (left_gray, right_gray) uint8 [H or H/2, W]"""
+    H, W, ch = tb.shape
+    if ch != 3:
+        raise NativeError("expected HxWx3")
+    L = torch.empty((_tb_out_height(H, unsqueeze), W), dtype=torch.uint8, device=tb.device)
+    R = torch.empty_like(L)
+    _call("v3d_tb_to_gray", tb.device, _dev(tb, torch.uint8, "tb"), W, H, W * 3, int(bool(unsqueeze)),
+          _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"))
+    return L, R
+
+
+def tb_to_gray_batch(tb, unsqueeze=True, out=None):
+    """tb: uint8 [N,H,W,3] -> (left, right) uint8 [N,outH,W], one launch"""
+    n, H, W, ch = tb.shape
+    oh = _tb_out_height(H, unsqueeze)
+    if out is None:
+        out = (torch.empty((n, oh, W), dtype=torch.uint8, device=tb.device), torch.empty((n, oh, W), dtype=torch.uint8, device=tb.device))
+    _call("v3d_tb_to_gray_batch", tb.device, _dev(tb, torch.uint8, "tb"), n, W, H, W * 3, H * W * 3, int(bool(unsqueeze)),
+          _dev(out[0], torch.uint8, "L"), _dev(out[1], torch.uint8, "R"))
+    return out
+
+
+def split_tb(tb, unsqueeze=True):
+    H, W, ch = tb.shape
+    L = torch.empty((_tb_out_height(H, unsqueeze), W, 3), dtype=torch.uint8, device=tb.device)
+    R = torch.empty_like(L)
+    _call("v3d_split_tb", tb.device, _dev(tb, torch.uint8, "tb"), W, H, W * 3, int(bool(unsqueeze)),
           _dev(L, torch.uint8, "L"), _dev(R, torch.uint8, "R"))
     return L, R
 

@@ -298,8 +298,9 @@ def main(argv=None, backend=None):
     from .register import add_register_arguments
     add_register_arguments(parser)
     args = parser.parse_args(argv)
+    from .depth import input_layout_options
     spatial = dict(start_frame=args.start_frame, probes=args.register_probes, unsqueeze=not args.no_unsqueeze,
-                   max_frames=args.max_frames, min_score=args.register_min_score, bins=args.register_bins)
+                   max_frames=args.max_frames, min_score=args.register_min_score, bins=args.register_bins, **input_layout_options(args))
     try:
         aligner = VideoAligner(args.video1, args.video2, args.work_dir)
         if args.video_only:

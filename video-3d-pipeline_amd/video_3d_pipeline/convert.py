@@ -402,6 +402,11 @@ class DepthTo3DConverter:
         if self.parallax == "source":                           # the film's parallax: from the depth run's own record
             man = depth_manifest(depth_path)
             plan.resolve_source(man.get("depth_range"), W, man.get("spatial_map"))
+            if self.fill_from_source is not None and man.get("input_layout", "sbs") != "sbs":
+                raise ValueError(f"--fill-from-source cannot read a top-bottom source (the depth run's input_layout is "
+                                 f"{man['input_layout']}): the fill samples the stored right eye at column We + i of a side-by-side "
+                                 f"frame, and a top-bottom clip keeps that eye in rows, not columns.  --parallax source alone works "
+                                 f"for both layouts")
         if self.fill_from_source is not None:
             if not get_video_info(self.fill_from_source):
                 raise ValueError(f"Could not read video info: {self.fill_from_source}")

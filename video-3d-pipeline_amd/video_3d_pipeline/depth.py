@@ -3,7 +3,7 @@
 Mirror of reference src/video_3d_pipeline/depth.py (class, method names, argument meaning, error
 behaviour, CLI flags) with the per-frame arithmetic moved from OpenCV-on-CPU to libv3d_hip.so:
 
-    split_sbs_frame     depth.py:250-268  -> v3d_split_sbs / v3d_sbs_to_gray
+    split_sbs_frame     depth.py:250-268  -> v3d_split_sbs / v3d_sbs_to_gray (input_layout "tb": v3d_split_tb / v3d_tb_to_gray)
     process_frame_batch depth.py:297-395  -> v3d_bgr_to_gray + v3d_sgbm_compute_batch + v3d_disp_to_depth
     save_depth_map      depth.py:397-406  -> v3d_depth_to_u16 + 16-bit PNG (Pillow)
     process_video_sbs   depth.py:408-476  -> streaming decode -> fused SBS batch path -> PNG cache
@@ -70,6 +70,44 @@ def calibration_frames(start_frame: int, frame_count: int) -> List[int]:
     k = min(MIN_DISPARITY_CALIBRATION_FRAMES, frame_count)
     stride = max(frame_count // k, 1) if k else 1
     return [start_frame + stride // 2 + j * stride for j in range(k)]
+
+
+INPUT_LAYOUTS = ("sbs", "tb")                            # --input-layout: the eyes side by side, or the left eye on top
+
+
+def check_input_layout(value) -> str:
+    if value not in INPUT_LAYOUTS:
+        raise ValueError(f"input_layout must be one of {INPUT_LAYOUTS}, got {value!r}")
+    return value
+
+
+def add_input_layout_argument(parser):
+    """--input-layout, declared once for the depth, pipeline and align CLIs"""
+    parser.add_argument('--input-layout', choices=INPUT_LAYOUTS, default='sbs',
+                        help='How the stereoscopic clip packs its eyes: sbs = side by side, left eye first (default); tb = top-bottom '
+                             '(over-under), left eye on top.  Squeezed eyes are stretched back along the packed axis unless '
+                             '--no-unsqueeze says they are stored at full size')
+
+
+def input_layout_options(args) -> dict:
+    """the keyword only when the layout is not the default: an SBS run calls everything as before (and so does a caller whose
+    arguments predate the flag)"""
+    layout = getattr(args, "input_layout", "sbs")
+    return {"input_layout": layout} if layout != "sbs" else {}
+
+
+def input_layout_suffix(input_layout: str) -> str:
+    """what the depth cache key gains, last, for a top-bottom clip"""
+    return f"_{input_layout}" if input_layout != "sbs" else ""
+
+
+def check_frame_halves(width: int, height: int, input_layout: str = "sbs"):
+    """a frame of two eyes has an even width (side by side) or an even height (top-bottom)"""
+    if input_layout == "tb":
+        if height % 2 != 0:
+            raise ValueError("top-bottom frame height must be even")
+    elif width % 2 != 0:
+        raise ValueError("SBS frame width must be even")
 
 
 def min_disparity_suffix(m: int) -> str:
@@ -150,9 +188,9 @@ class HipStereoBackend(HipBackend):
             n = min((requested // fill) * fill or requested, fit)
         return max(1, n)
 
-    def split_sbs(self, sbs_frame: np.ndarray, unsqueeze: bool):
+    def split_sbs(self, sbs_frame: np.ndarray, unsqueeze: bool, input_layout: str = "sbs"):
         d = self.native.to_device(sbs_frame, self.device)
-        L, R = self.native.split_sbs(d, unsqueeze)
+        L, R = (self.native.split_tb if input_layout == "tb" else self.native.split_sbs)(d, unsqueeze)
         return L.cpu().numpy(), R.cpu().numpy()
 
     def _depth_from(self, disp, monos, out=None):
@@ -203,31 +241,35 @@ class HipStereoBackend(HipBackend):
         out = depth.cpu().numpy()
         return [out[i] for i in range(n)]
 
-    def _sbs_to_gray(self, frames: List[np.ndarray], unsqueeze: bool):
-        """SBS BGR frames -> (device frames [n,H,W,3], left gray, right gray [n,H,ow]): the frames are gathered into one pinned
-        buffer and cross PCIe in a single asynchronous copy, then one v3d_sbs_to_gray_batch launch.  The grays stay in the
-        staging buffers `lg` / `rg` (left_gray, right_gray) until the next pass."""
+    def _sbs_to_gray(self, frames: List[np.ndarray], unsqueeze: bool, input_layout: str = "sbs"):
+        """stereoscopic BGR frames -> (device frames [n,H,W,3], left gray, right gray [n,oh,ow]): the frames are gathered into one
+        pinned buffer and cross PCIe in a single asynchronous copy, then one v3d_sbs_to_gray_batch launch -- v3d_tb_to_gray_batch
+        for input_layout "tb", whose eyes are W x H unsqueezed and W x H/2 as stored.  The grays stay in the staging buffers
+        `lg` / `rg` (left_gray, right_gray) until the next pass."""
         torch = self.torch
         n = len(frames)
         H, W = frames[0].shape[:2]
-        ow = W if unsqueeze else W // 2
+        check_frame_halves(W, H, check_input_layout(input_layout))
+        ow, oh = sbs_eye_size({"width": W, "height": H}, unsqueeze, input_layout)
         dev = self._upload("sbs", frames, (H, W, 3), torch.uint8)
-        lg = self._staging("lg", (n, H, ow), torch.uint8, False)
-        rg = self._staging("rg", (n, H, ow), torch.uint8, False)
-        self.native.sbs_to_gray_batch(dev, unsqueeze, (lg, rg))
+        lg = self._staging("lg", (n, oh, ow), torch.uint8, False)
+        rg = self._staging("rg", (n, oh, ow), torch.uint8, False)
+        (self.native.tb_to_gray_batch if input_layout == "tb" else self.native.sbs_to_gray_batch)(dev, unsqueeze, (lg, rg))
         return dev, lg, rg
 
     def sbs_to_disparity(self, frames: List[np.ndarray], unsqueeze: bool, mono_provider=None, fill_holes: bool = False,
-                         min_disparity: int = 0):
+                         min_disparity: int = 0, input_layout: str = "sbs"):
         """fused path: SBS BGR frames -> device float32 disparity [n,H,W] (no BGR halves materialised).
         Frames are gathered into one pinned buffer and cross PCIe in a single asynchronous copy (_sbs_to_gray).
         mono_provider (neural guidance on): called with the left views as RGB arrays, its maps are blended in.
         fill_holes: the int16 disparity is filled in place after the matcher (and its lock-step recompute), before /16 and the
         blend.
-        min_disparity: the matcher's window [m, m + 64); the disparity is rebiased to [0, 64) right after it (_match)."""
+        min_disparity: the matcher's window [m, m + 64); the disparity is rebiased to [0, 64) right after it (_match).
+        input_layout: "tb" reads top-bottom frames (the left eye on top); everything after the gray split is the same."""
         torch, nat = self.torch, self.native
         n = len(frames)
-        dev, lg, rg = self._sbs_to_gray(frames, unsqueeze)
+        dev, lg, rg = self._sbs_to_gray(frames, unsqueeze, input_layout)
+        split = nat.split_tb if input_layout == "tb" else nat.split_sbs
         disp = self._match(lg, rg, self._staging("disp", tuple(lg.shape), torch.int16, False), min_disparity)
         if fill_holes:
             disp = self.fill_holes(disp)
@@ -237,7 +279,7 @@ class HipStereoBackend(HipBackend):
             # a failing provider (DPT forward out of memory, bad shape ...) must not abort the clip -- nor, in a sharded run,
             # leave the other ranks waiting in the final barrier: warn and continue stereo-only like depth.py:367-369
             try:
-                lefts = [nat.split_sbs(dev[i], unsqueeze)[0].flip(-1).cpu().numpy() for i in range(n)]     # left view, RGB (depth.py:274)
+                lefts = [split(dev[i], unsqueeze)[0].flip(-1).cpu().numpy() for i in range(n)]     # left view, RGB (depth.py:274)
                 monos = mono_provider(lefts)
                 return self._depth_from(disp, monos, out)
             except Exception as e:
@@ -249,14 +291,15 @@ class HipStereoBackend(HipBackend):
         """device luma planes u8 [n,H,W] -> their signatures [n,2304] on the device (v3d_frame_signature_batch)"""
         return self.native.frame_signature_batch(gray)
 
-    def sbs_left_signatures(self, frames: List[np.ndarray], unsqueeze: bool):
-        """SBS BGR frames -> the signatures of their left views: the staging and the gray split of sbs_to_disparity, no matcher"""
-        return self.native.frame_signature_batch(self._sbs_to_gray(frames, unsqueeze)[1])
+    def sbs_left_signatures(self, frames: List[np.ndarray], unsqueeze: bool, input_layout: str = "sbs"):
+        """SBS (or top-bottom) BGR frames -> the signatures of their left views: the staging and the gray split of sbs_to_disparity,
+        no matcher"""
+        return self.native.frame_signature_batch(self._sbs_to_gray(frames, unsqueeze, input_layout)[1])
 
-    def sbs_left_profiles(self, frames: List[np.ndarray], unsqueeze: bool):
-        """SBS BGR frames -> the column and row sums of their left views on the device (register.estimate): the staging and the
-        gray split of sbs_left_signatures, then v3d_plane_profiles_batch"""
-        return self.native.plane_profiles_batch(self._sbs_to_gray(frames, unsqueeze)[1])
+    def sbs_left_profiles(self, frames: List[np.ndarray], unsqueeze: bool, input_layout: str = "sbs"):
+        """SBS (or top-bottom) BGR frames -> the column and row sums of their left views on the device (register.estimate): the
+        staging and the gray split of sbs_left_signatures, then v3d_plane_profiles_batch"""
+        return self.native.plane_profiles_batch(self._sbs_to_gray(frames, unsqueeze, input_layout)[1])
 
     def match_scores(self, prof_a, prof_b, cand, bins):
         """profiles [K,na] and [K,nb] on the device, a host-side candidate list int64 [C,2] -> the records int64 [K,C,6] as NumPy
@@ -297,11 +340,12 @@ class HipStereoBackend(HipBackend):
         shift = {"right_shift": -min_disparity} if min_disparity else {}
         return nat.quality_reproj_batch(lg, self.right_gray(n), self.last_disp16(n), bad_thr, ws=ws, **shift)
 
-    def min_disparity_score(self, frames: List[np.ndarray], unsqueeze: bool, min_disparity: int) -> int:
+    def min_disparity_score(self, frames: List[np.ndarray], unsqueeze: bool, min_disparity: int, input_layout: str = "sbs") -> int:
         """--min-disparity auto: the calibration frames through a matcher of their own at window m -> the number of pixels whose
         reprojection error stays within the report's default threshold, sum over frames of n_cmp - n_bad"""
         self.close_matcher()
-        self.sbs_to_disparity(frames, unsqueeze, **({"min_disparity": min_disparity} if min_disparity else {}))
+        self.sbs_to_disparity(frames, unsqueeze, **({"min_disparity": min_disparity} if min_disparity else {}),
+                              **({"input_layout": input_layout} if input_layout != "sbs" else {}))
         rec = self.quality_reproj(len(frames), MIN_DISPARITY_BAD, **({"min_disparity": min_disparity} if min_disparity else {})).cpu().numpy()
         self.close_matcher()
         return int((rec[:, 1] - rec[:, 4]).sum())
@@ -405,8 +449,11 @@ class HipStereoBackend(HipBackend):
         return self._png_encoder().encode(u16)
 
 
-def sbs_eye_size(video_info, unsqueeze: bool) -> Tuple[int, int]:
-    """(width, height) of one eye as the matcher sees it (HybridStereoDepthExtractor.eye_size, for a caller without an extractor)"""
+def sbs_eye_size(video_info, unsqueeze: bool, input_layout: str = "sbs") -> Tuple[int, int]:
+    """(width, height) of one eye as the matcher sees it (HybridStereoDepthExtractor.eye_size, for a caller without an extractor):
+    the frame's own size once the eyes are unsqueezed, else half of it along the packed axis"""
+    if input_layout == "tb":
+        return video_info['width'], video_info['height'] if unsqueeze else video_info['height'] // 2
     return video_info['width'] if unsqueeze else video_info['width'] // 2, video_info['height']
 
 
@@ -441,7 +488,8 @@ class HybridStereoDepthExtractor:
                  quality_jump: float = 1.0,
                  temporal_motion: int = 0,
                  min_disparity=0,
-                 depth_range: str = "frame"):
+                 depth_range: str = "frame",
+                 input_layout: str = "sbs"):
         """ mono_provider: optional callable(list of HxWx3 uint8 RGB left views) -> list of 2-D float32 monocular
         depth maps (NumPy arrays or device tensors, any size); takes the place of the DPT forward of depth.py:348-350.
         temporal_radius > 0 (process_video_sbs only): temporal stabilisation over 2R+1 frames (temporal.py); 0 = every frame
@@ -462,7 +510,10 @@ class HybridStereoDepthExtractor:
         calibrates m on frames of the clip (resolve_min_disparity).  0 = the reference's window: no call, key or byte changes
         depth_range (process_video_sbs and the one-pass pipeline): "metric" normalises every frame against the constant range
         (0, 64) instead of its own (or its window's) minimum and maximum: a sample s is a rebiased disparity of 64 s / 65535 pixels
-        of the matcher's eye.  "frame" = the reference's min-max: no call, key or byte changes """
+        of the matcher's eye.  "frame" = the reference's min-max: no call, key or byte changes
+        input_layout (every surface that takes a packed frame): "tb" reads a top-bottom clip, the left eye on top; unsqueeze_sbs then
+        stretches the eyes vertically.  "sbs" = the reference's layout: no call, key or byte changes """
+        self.input_layout = check_input_layout(input_layout)
         self.min_disparity = check_min_disparity(min_disparity)
         self.min_disparity_scores = None         # {candidate: score} of an `auto` run, once resolved
         from .png_gpu import check_png_encoder
@@ -562,14 +613,19 @@ class HybridStereoDepthExtractor:
                 out.append(self.model(**inputs).predicted_depth[0].float())
         return out
 
-    def _disparity_pass(self, call, *args, guidance=None):
+    def _disparity_pass(self, call, *args, guidance=None, packed=False):
         """the one way a disparity pass of the backend (sbs_to_disparity, pairs_to_disparity) is called: an option that is off
         adds no argument -- no provider / monocular maps without guidance, no `fill_holes` keyword without --fill-holes -- so
-        it stays the call every backend knows"""
+        it stays the call every backend knows.  packed: the pass takes packed frames (sbs_to_disparity), so a top-bottom clip adds
+        its `input_layout`"""
         if guidance is not None:
             args += (guidance,)
         window = {"min_disparity": self.min_disparity} if self.min_disparity != 0 else {}
-        return call(*args, **({"fill_holes": True} if self.fill_holes else {}), **window)
+        return call(*args, **({"fill_holes": True} if self.fill_holes else {}), **window, **(self._layout_keyword() if packed else {}))
+
+    def _layout_keyword(self) -> dict:
+        """what a backend call that takes packed frames gains with a top-bottom clip: nothing with an SBS one"""
+        return {"input_layout": self.input_layout} if self.input_layout != "sbs" else {}
 
     def resolve_min_disparity(self, video_path: str, start_frame: int, frame_count: int) -> int:
         """--min-disparity auto -> its integer, before anything is keyed by it: every candidate window scores the calibration
@@ -583,7 +639,7 @@ class HybridStereoDepthExtractor:
         picks = calibration_frames(start_frame, frame_count)
         stride = picks[1] - picks[0] if len(picks) > 1 else 1
         frames = list(iter_frames(video_path, picks[0], (len(picks) - 1) * stride + 1, stride=stride))
-        scores = {m: int(self.backend.min_disparity_score(frames, self.unsqueeze_sbs, m)) for m in MIN_DISPARITY_CANDIDATES} if frames else \
+        scores = {m: int(self.backend.min_disparity_score(frames, self.unsqueeze_sbs, m, **self._layout_keyword())) for m in MIN_DISPARITY_CANDIDATES} if frames else \
                  {m: 0 for m in MIN_DISPARITY_CANDIDATES}
         self.min_disparity = choose_min_disparity(scores)
         self.min_disparity_scores = {str(m): s for m, s in scores.items()}
@@ -600,6 +656,8 @@ class HybridStereoDepthExtractor:
             extra["temporal"] = manifest_entry(*self.temporal, self.range_quantile, self.motion_search)
         if self.fill_holes:
             extra["fill_holes"] = True
+        if self.input_layout != "sbs":
+            extra["input_layout"] = self.input_layout
         if self.min_disparity != 0 or self.min_disparity_scores is not None:
             extra["min_disparity"] = self.min_disparity
         if self.min_disparity_scores is not None:
@@ -648,8 +706,8 @@ class HybridStereoDepthExtractor:
             print(CACHED_NOTE)
 
     def write_side_files(self, cache_path: Path):
-        """temporal.json (a radius or the robust range is on), fill.json (--fill-holes), min_disparity.json (--min-disparity) and
-        depth_range.json (--depth-range metric) of a depth map directory"""
+        """temporal.json (a radius or the robust range is on), fill.json (--fill-holes), min_disparity.json (--min-disparity),
+        depth_range.json (--depth-range metric) and input_layout.json (--input-layout tb) of a depth map directory"""
         import json
         extra = self.manifest_extra()
         if "temporal" in extra:
@@ -660,6 +718,8 @@ class HybridStereoDepthExtractor:
             (cache_path / "min_disparity.json").write_text(json.dumps({k: extra[k] for k in ("min_disparity", "min_disparity_scores") if k in extra}))
         if "depth_range" in extra:
             (cache_path / "depth_range.json").write_text(json.dumps(extra["depth_range"]))
+        if "input_layout" in extra:
+            (cache_path / "input_layout.json").write_text(json.dumps({"input_layout": extra["input_layout"]}))
 
     def _guidance_provider(self):
         """ the provider when neural guidance is active (depth.py:344-345), else None """
@@ -670,13 +730,14 @@ class HybridStereoDepthExtractor:
     def get_cache_path(self, video_path: str, frame_start: int, frame_count: int) -> Path:
         """ Generate cache path for depth maps (key format identical to depth.py:119-120; with temporal stabilisation or the
         robust range on, the key also carries their parameters, so such maps and the reference's never share a directory; so
-        does a search window other than [0, 64): the resolved integer, which an `auto` run and an explicit one share) """
+        does a search window other than [0, 64): the resolved integer, which an `auto` run and an explicit one share; a top-bottom
+        clip appends its layout last: the key of an SBS run is byte for byte what it was) """
         if self.min_disparity == "auto":
             raise ValueError('min_disparity="auto" is resolved from the clip first (resolve_min_disparity)')
         from .temporal import cache_suffix, depth_range_suffix, fill_suffix
         cache_key = f"{video_path}_{frame_start}_{frame_count}_{self.model_checkpoint}_{self.unsqueeze_sbs}"
         cache_key += cache_suffix(*self.temporal, self.range_quantile, self.motion_search) + fill_suffix(self.fill_holes)
-        cache_key += min_disparity_suffix(self.min_disparity) + depth_range_suffix(self.depth_range)
+        cache_key += min_disparity_suffix(self.min_disparity) + depth_range_suffix(self.depth_range) + input_layout_suffix(self.input_layout)
         cache_hash = hashlib.md5(cache_key.encode()).hexdigest()[:16]
         cache_subdir = self.cache_dir / f"depth_{cache_hash}"
         cache_subdir.mkdir(exist_ok=True)
@@ -721,11 +782,10 @@ class HybridStereoDepthExtractor:
     extract_frames_ffmpeg = extract_frames_opencv
 
     def split_sbs_frame(self, sbs_frame: np.ndarray, unsqueeze: bool = True) -> Tuple[np.ndarray, np.ndarray]:
-        """ Split side-by-side frame into left and right images """
+        """ Split side-by-side (input_layout "tb": top-bottom) frame into left and right images """
         height, width = sbs_frame.shape[:2]
-        if width % 2 != 0:
-            raise ValueError("SBS frame width must be even")
-        return self.backend.split_sbs(np.ascontiguousarray(sbs_frame), unsqueeze)
+        check_frame_halves(width, height, self.input_layout)
+        return self.backend.split_sbs(np.ascontiguousarray(sbs_frame), unsqueeze, **self._layout_keyword())
 
     def preprocess_frame_pair(self, left_frame: np.ndarray, right_frame: np.ndarray) -> Dict:
         """ Preprocess frame pair for depth estimation (BGR -> RGB views; the provider does its own input processing) """
@@ -782,8 +842,7 @@ class HybridStereoDepthExtractor:
             print("✓ Using cached depth maps")
             self.quality_skipped()
             return cache_path
-        if video_info['width'] % 2 != 0:
-            raise ValueError("SBS frame width must be even")
+        check_frame_halves(video_info['width'], video_info['height'], self.input_layout)
         if not self.model_loaded:
             self.load_model()
 
@@ -824,8 +883,9 @@ class HybridStereoDepthExtractor:
             writers.submit(cache_path / f"depth_{frame_idx:06d}.png", to_host(u16[j:j + 1])[0])
 
     def eye_size(self, video_info) -> Tuple[int, int]:
-        """(width, height) of the matcher's eye: the SBS frame's own width once the halves are unsqueezed, else half of it"""
-        return sbs_eye_size(video_info, self.unsqueeze_sbs)
+        """(width, height) of the matcher's eye: the packed frame's own size once the eyes are unsqueezed, else half of it along the
+        packed axis"""
+        return sbs_eye_size(video_info, self.unsqueeze_sbs, **self._layout_keyword())
 
     def pass_frames(self, video_info) -> int:
         """frames per device pass: decoupled from batch_size (which the reference only uses to chunk its frame list,
@@ -874,7 +934,7 @@ class HybridStereoDepthExtractor:
                 k0 = self.last_decoded_frames
                 self.last_decoded_frames += len(batch)
                 idx = [first + offset + k * stride for k in range(k0, k0 + len(batch))]       # the pass's clip indices
-                depth = self._disparity_pass(be.sbs_to_disparity, batch, self.unsqueeze_sbs, guidance=provider)
+                depth = self._disparity_pass(be.sbs_to_disparity, batch, self.unsqueeze_sbs, guidance=provider, packed=True)
                 if quality is not None:                  # --quality-report: the pass's planes are valid until the next pass
                     quality.note_pass(idx, len(batch), depth)
                 if self.guide_check is not None:         # --check-guide: the pass's left gray planes are valid until the next pass
@@ -917,6 +977,7 @@ def add_depth_arguments(parser, force_help: str):
     parser.add_argument('--stereo-only', action='store_true', help='Use stereo matching only (no neural guidance)')
     parser.add_argument('--no-neural', action='store_true', help='Disable neural guidance (same as --stereo-only)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Skip SBS unsqueezing (keep squeezed aspect ratio)')
+    add_input_layout_argument(parser)
     add_temporal_arguments(parser)
     add_range_arguments(parser)
     add_depth_range_arguments(parser)
@@ -939,7 +1000,7 @@ def depth_options(args) -> dict:
                 use_neural_guidance=not stereo_only, stereo_only=stereo_only, unsqueeze_sbs=not args.no_unsqueeze,
                 **temporal_options(args), **range_options(args), **fill_options(args), **png_options(args),
                 **quality_options(args), **({"min_disparity": args.min_disparity} if args.min_disparity != 0 else {}),
-                **depth_range_options(args))
+                **depth_range_options(args), **input_layout_options(args))
 
 
 def main(argv=None):

@@ -131,13 +131,15 @@ def _clip_frames(info, start_frame=0, max_frames=None) -> int:
 
 def refine(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame: int = 0, search: int = DEFAULT_SEARCH,
            window: int = DEFAULT_WINDOW, probes: int = DEFAULT_PROBES, unsqueeze: bool = True, max_frames: Optional[int] = None,
-           min_score: float = DEFAULT_MIN_SCORE, min_margin: float = DEFAULT_MIN_MARGIN, backend=None) -> Dict:
+           min_score: float = DEFAULT_MIN_SCORE, min_margin: float = DEFAULT_MIN_MARGIN, backend=None, input_layout: str = "sbs") -> Dict:
     """Refine the 4K frame that belongs to SBS frame start_frame, seeded with guide_start_frame (g0).  Decodes `probes` windows of
     `window` consecutive SBS frames spread over the clip (or over max_frames) and, per window starting at frame s, the 4K frames
     g0 + s - search .. g0 + s + window - 1 + search; the left eye (the backend's SBS staging and v3d_sbs_to_gray_batch) and the 4K
     luma (its guide staging and v3d_bgr_to_gray) give signatures on the device, one v3d_signature_scores call per probe gives the
     integers, decide() the answer.  Returns decide()'s result plus guide_start_frame (g0 + shift), guide_start_frame_seed, the
-    parameters and `ints`, the probes' integer scores.  ValueError: unreadable clips, unequal frame rates, bad parameters."""
+    parameters and `ints`, the probes' integer scores.  input_layout "tb": the left eye is the top half of the frame (the backend's
+    calls and the recorded parameters gain the keyword; an SBS run's are what they were).  ValueError: unreadable clips, unequal
+    frame rates, bad parameters."""
     search, window, probes, min_score, min_margin = check_parameters(search, window, probes, min_score, min_margin)
     info_s, info_g = get_video_info(sbs_video), get_video_info(video_4k)
     if not info_s or not info_g:
@@ -145,8 +147,9 @@ def refine(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame: i
     if abs(float(info_s["fps"]) - float(info_g["fps"])) > FPS_TOLERANCE:
         raise ValueError(f"video refinement refused: frame rates differ ({info_s['fps']:.3f} vs {info_g['fps']:.3f} fps); frames can "
                          f"only be matched one to one between clips of equal rate")
-    if info_s["width"] % 2:
-        raise ValueError("SBS frame width must be even")
+    from .depth import check_frame_halves, check_input_layout
+    layout = {"input_layout": check_input_layout(input_layout)} if input_layout != "sbs" else {}
+    check_frame_halves(info_s["width"], info_s["height"], input_layout)
     count, n4k = _clip_frames(info_s, start_frame, max_frames), _clip_frames(info_g)
     if count < 1:
         raise ValueError("No frames extracted from video")
@@ -164,7 +167,7 @@ def refine(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame: i
         guides = list(iter_frames(video_4k, lo, hi - lo))
         if not sbs or not guides:
             continue
-        sig_a = backend.sbs_left_signatures(sbs, unsqueeze)
+        sig_a = backend.sbs_left_signatures(sbs, unsqueeze, **layout)
         sig_b = backend.guide_signatures(guides, info_g["height"], info_g["width"])
         num, va, vb = backend.read_scores(backend.signature_scores(sig_a, sig_b))
         ints.append((num, va, vb))
@@ -173,7 +176,7 @@ def refine(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame: i
     out = decide(plist, search, min_score, min_margin)
     out.update(guide_start_frame_seed=g0, guide_start_frame=g0 + out["shift"], probe_starts=used, ints=ints,
                parameters=dict(search=search, window=w, probes=probes, min_score=min_score, min_margin=min_margin,
-                               unsqueeze=bool(unsqueeze), start_frame=int(start_frame), max_frames=max_frames))
+                               unsqueeze=bool(unsqueeze), start_frame=int(start_frame), max_frames=max_frames, **layout))
     return out
 
 
@@ -208,12 +211,15 @@ def add_refine_arguments(parser):
     parser.add_argument('--start-frame', type=int, default=0, help='First SBS frame of the refinement (default 0)')
     parser.add_argument('--max-frames', type=int, default=None, help='Spread the probes over this many SBS frames (default: the clip)')
     parser.add_argument('--no-unsqueeze', action='store_true', help='Match the squeezed left eye (as the depth CLI with --no-unsqueeze)')
+    from .depth import add_input_layout_argument
+    add_input_layout_argument(parser)
 
 
 def refine_options(args) -> Dict:
+    from .depth import input_layout_options
     return dict(start_frame=args.start_frame, search=args.refine_search, window=args.refine_window, probes=args.refine_probes,
                 unsqueeze=not args.no_unsqueeze, max_frames=args.max_frames, min_score=args.refine_min_score,
-                min_margin=args.refine_min_margin)
+                min_margin=args.refine_min_margin, **input_layout_options(args))
 
 
 class GuideChecker:

@@ -23,7 +23,7 @@ import argparse
 from pathlib import Path
 
 from .backend import require_hip_device
-from .depth import HipStereoBackend, HybridStereoDepthExtractor, add_depth_arguments, depth_options, sbs_eye_size
+from .depth import HipStereoBackend, HybridStereoDepthExtractor, add_depth_arguments, check_frame_halves, depth_options, input_layout_options, sbs_eye_size
 from .upscale import GUIDED_EPS, GUIDED_RADIUS, encode_depth4k
 from .utils import PngWriterPool, get_video_info, iter_frames, sibling_frames_dir
 
@@ -142,7 +142,8 @@ class SbsTo4kDepthPipeline:
                  quality_jump: float = 1.0,
                  temporal_motion: int = 0,
                  min_disparity=0,
-                 depth_range: str = "frame"):
+                 depth_range: str = "frame",
+                 input_layout: str = "sbs"):
         """backend: HipPipelineBackend (built when None) or a stand-in with its methods (host-logic tests);
         temporal_*: the depth CLI's temporal stabilisation (radius 0 = off: every frame on its own; temporal_motion > 0: the
         window follows the block matcher's motion);
@@ -153,7 +154,8 @@ class SbsTo4kDepthPipeline:
         quality_*: the depth CLI's --quality-report (quality.py): quality.json goes next to the kept depth maps, else next to the
         4K frames, or to the given path; no output PNG changes;
         min_disparity: the depth CLI's --min-disparity (an integer in [-64, 0] or "auto"; 0 = off: the window [0, 64));
-        depth_range: the depth CLI's --depth-range ("metric": the constant range (0, 64); "frame" = off: per-frame min-max)"""
+        depth_range: the depth CLI's --depth-range ("metric": the constant range (0, 64); "frame" = off: per-frame min-max);
+        input_layout: the depth CLI's --input-layout ("tb": a top-bottom clip, the left eye on top; "sbs" = side by side)"""
         if backend is None:
             require_hip_device(device)
             backend = HipPipelineBackend(device)
@@ -166,7 +168,8 @@ class SbsTo4kDepthPipeline:
             temporal_fill=temporal_fill, range_percentile=range_percentile, fill_holes=fill_holes,
             png_encoder=png_encoder, quality_report=quality_report, quality_bad_threshold=quality_bad_threshold,
             quality_still=quality_still, quality_jump=quality_jump, temporal_motion=temporal_motion, min_disparity=min_disparity,
-            **({"depth_range": depth_range} if depth_range != "frame" else {}))
+            **({"depth_range": depth_range} if depth_range != "frame" else {}),
+            **({"input_layout": input_layout} if input_layout != "sbs" else {}))
         self.radius, self.eps = radius, eps
         self.guide_batch = max(1, int(guide_batch))
         self.check_guide, self.check_guide_min = bool(check_guide), float(check_guide_min)
@@ -209,8 +212,7 @@ class SbsTo4kDepthPipeline:
             print(f"✓ Using existing depth video: {output_path}")
             ex.quality_skipped()
             return str(output_path)
-        if video_info['width'] % 2 != 0:
-            raise ValueError("SBS frame width must be even")
+        check_frame_halves(video_info['width'], video_info['height'], ex.input_layout)
         if stereo is not None:
             stereo.check_frame(Whi, Hhi)
             if stereo.parallax == "source":                          # the film's parallax: the window is resolved, the sizes are known
@@ -327,15 +329,16 @@ def _resolve_spatial(args, resolve):
     if args.no_spatial or (args.alignment_file is None and args.spatial_map is None):
         return None
     unsqueeze = not args.no_unsqueeze
+    layout = input_layout_options(args)
 
     def eye():
         info = get_video_info(args.video)
-        return None if not info else list(sbs_eye_size(info, unsqueeze))
+        return None if not info else list(sbs_eye_size(info, unsqueeze, **layout))
 
     def guide():
         info = get_video_info(args.video_4k)
         return None if not info else [info["width"], info["height"]]
-    return resolve(args.alignment_file, False, args.spatial_map, eye, guide, unsqueeze)
+    return resolve(args.alignment_file, False, args.spatial_map, eye, guide, unsqueeze, **layout)
 
 
 def main(argv=None):

@@ -189,21 +189,23 @@ def check_parameters(probes, min_score, bins):
 
 def estimate(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame: int = 0, probes: int = DEFAULT_PROBES,
              unsqueeze: bool = True, max_frames: Optional[int] = None, min_score: float = DEFAULT_MIN_SCORE, bins: int = DEFAULT_BINS,
-             backend=None) -> Dict:
+             backend=None, input_layout: str = "sbs") -> Dict:
     """Fit the left eye of the SBS clip to the 4K clip.  `probes` single frames spread over the clip (framematch.probe_starts), SBS
     frame start_frame + s against 4K frame guide_start_frame + s; the backend puts the left-eye gray (the plane the matcher sees:
     unsqueezed unless told otherwise) and the 4K luma on the device and returns their profiles (sbs_left_profiles,
     guide_profiles), match_scores(prof_a, prof_b, cand, bins) runs the device entry and returns the records.  Returns decide()'s
-    result plus the per-probe maps, both plane sizes and the parameters.  ValueError: unreadable clips, unequal frame rates, bad
-    parameters."""
+    result plus the per-probe maps, both plane sizes and the parameters.  input_layout "tb": the left eye is the top half of the
+    frame (the backend's call and the result gain the keyword; an SBS run's are what they were).  ValueError: unreadable clips,
+    unequal frame rates, bad parameters."""
     probes, min_score, bins = check_parameters(probes, min_score, bins)
     info_s, info_g = get_video_info(sbs_video), get_video_info(video_4k)
     if not info_s or not info_g:
         raise ValueError(f"Could not read video info: {sbs_video if not info_s else video_4k}")
     if abs(float(info_s["fps"]) - float(info_g["fps"])) > FPS_TOLERANCE:
         raise ValueError(f"spatial registration refused: frame rates differ ({info_s['fps']:.3f} vs {info_g['fps']:.3f} fps)")
-    if info_s["width"] % 2:
-        raise ValueError("SBS frame width must be even")
+    from .depth import check_frame_halves, check_input_layout, sbs_eye_size
+    layout = {"input_layout": check_input_layout(input_layout)} if input_layout != "sbs" else {}
+    check_frame_halves(info_s["width"], info_s["height"], input_layout)
     count, n4k = _clip_frames(info_s, start_frame, max_frames), _clip_frames(info_g)
     if count < 1:
         raise ValueError("No frames extracted from video")
@@ -218,12 +220,12 @@ def estimate(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame:
         f, g = list(iter_frames(sbs_video, start_frame + s, 1)), list(iter_frames(video_4k, g0 + s, 1))
         if f and g:
             used.append(int(s)); sbs.append(f[0]); guides.append(g[0])
-    We, He = (info_s["width"] if unsqueeze else info_s["width"] // 2), info_s["height"]
+    We, He = sbs_eye_size(info_s, unsqueeze, **layout)
     Wg, Hg = info_g["width"], info_g["height"]
     px: List[Optional[Dict]] = []
     py: List[Optional[Dict]] = []
     if used:
-        col_e, row_e = backend.sbs_left_profiles(sbs, unsqueeze)
+        col_e, row_e = backend.sbs_left_profiles(sbs, unsqueeze, **layout)
         col_g, row_g = backend.guide_profiles(guides, Hg, Wg)
         for p in range(len(used)):
             px.append(search_axis(lambda c, b: backend.match_scores(col_e[p:p + 1], col_g[p:p + 1], c, b)[0], We, Wg, bins))
@@ -231,7 +233,7 @@ def estimate(sbs_video: str, video_4k: str, guide_start_frame: int, start_frame:
     out = decide(px, py, (We, He), (Wg, Hg), min_score)
     out.update(probe_frames=used, probes_x=px, probes_y=py, eye_size=[We, He], guide_size=[Wg, Hg], unsqueeze=bool(unsqueeze),
                parameters=dict(probes=probes, min_score=min_score, bins=bins, start_frame=int(start_frame), max_frames=max_frames,
-                               guide_start_frame=g0))
+                               guide_start_frame=g0), **layout)
     return out
 
 
@@ -247,7 +249,8 @@ def spatial_block(res: Dict) -> Dict:
     return dict(status=res["status"], map=[float(v) for v in res["map"]], map_q16=res["map_q16"], score=res["score"],
                 probe_frames=res["probe_frames"], probes_x=[probe(p, We, Wg) for p in res["probes_x"]],
                 probes_y=[probe(p, He, Hg) for p in res["probes_y"]], eye_size=[We, He], guide_size=[Wg, Hg],
-                unsqueeze=res["unsqueeze"], parameters=res["parameters"])
+                unsqueeze=res["unsqueeze"], parameters=res["parameters"],
+                **({"input_layout": res["input_layout"]} if res.get("input_layout", "sbs") != "sbs" else {}))
 
 
 def parse_map(text: str) -> Tuple[float, float, float, float]:
@@ -262,11 +265,13 @@ def parse_map(text: str) -> Tuple[float, float, float, float]:
 
 
 def resolve(alignment_file: Optional[str], no_spatial: bool = False, spatial_map: Optional[str] = None,
-            eye_size: Optional[Sequence[int]] = None, guide_size: Optional[Sequence[int]] = None, unsqueeze: Optional[bool] = None) -> Optional[Dict]:
+            eye_size: Optional[Sequence[int]] = None, guide_size: Optional[Sequence[int]] = None, unsqueeze: Optional[bool] = None,
+            input_layout: Optional[str] = None) -> Optional[Dict]:
     """What a run applies: None (nothing: no block, --no-spatial, a block that is not `registered`, or the identity) or dict(map,
     source).  --spatial-map wins over the file.  A block estimated on other plane sizes (eye_size, guide_size: (W, H), or a
-    callable that returns it or None) or with another unsqueeze setting than the run's (each compared where the run knows it) is
-    refused: ValueError."""
+    callable that returns it or None), with another unsqueeze setting or with another input layout than the run's (each compared
+    where the run knows it; a CLI with --input-layout passes it only for "tb", and None here stands for "sbs" once the run knows its
+    unsqueeze setting) is refused: ValueError."""
     if no_spatial:
         return None
     if spatial_map is not None:
@@ -281,6 +286,11 @@ def resolve(alignment_file: Optional[str], no_spatial: bool = False, spatial_map
         if unsqueeze is not None and block.get("unsqueeze") is not None and bool(block["unsqueeze"]) != bool(unsqueeze):
             raise ValueError(f"{alignment_file}: the spatial map was estimated with unsqueeze={bool(block['unsqueeze'])}, this run has "
                              f"unsqueeze={bool(unsqueeze)}; estimate it again with `{ADVICE}` or pass --no-spatial")
+        if unsqueeze is not None or input_layout is not None:         # a run that splits the clip itself knows its layout
+            mine_layout, theirs_layout = input_layout or "sbs", block.get("input_layout") or "sbs"
+            if mine_layout != theirs_layout:
+                raise ValueError(f"{alignment_file}: the spatial map was estimated with input_layout={theirs_layout}, this run has "
+                                 f"input_layout={mine_layout}; estimate it again with `{ADVICE}` or pass --no-spatial")
         for name, mine, theirs in (("left-eye plane", eye_size, block.get("eye_size")), ("4K frame", guide_size, block.get("guide_size"))):
             mine = mine() if callable(mine) else mine                 # a CLI reads its clips' sizes only when there is a block to hold them to
             if mine is not None and theirs is not None and [int(v) for v in mine] != [int(v) for v in theirs]:

@@ -68,6 +68,19 @@ def sbs_frame(W, H, frame_idx=0):
     return np.ascontiguousarray(np.hstack([squeeze(left), squeeze(right)]))
 
 
+def tb_frame(W, H, frame_idx=0):
+    """top-bottom BGR frame HxWx3 u8, the left eye on top: each eye squeezed to H/2 by 2:1 area averaging of row pairs
+    (sbs_frame's counterpart for --input-layout tb)"""
+    assert H % 2 == 0
+    left, right = stereo_pair(W, H, frame_idx)
+
+    def squeeze(a):
+        a = a.astype(np.uint16)
+        return ((a[0::2] + a[1::2] + 1) >> 1).astype(np.uint8)
+
+    return np.ascontiguousarray(np.vstack([squeeze(left), squeeze(right)]))
+
+
 def guide_frame(W, H, frame_idx=0, scale=2):
     """2x 'original 4K' luma guide (scale*H x scale*W u8) of the left view, + N(0,2) noise"""
     left, _ = stereo_pair(W, H, frame_idx)

@@ -47,6 +47,19 @@ def depth_range_entry(depth_dir) -> dict:
     return {"depth_range": block} if isinstance(block, dict) else {}
 
 
+def input_layout_entry(depth_dir) -> dict:
+    """the depth CLI's input_layout.json (--input-layout tb) as an entry of the 4K manifest, where the convert CLI looks for it ({}
+    without the file: side by side)"""
+    side = Path(depth_dir) / "input_layout.json"
+    if not side.is_file():
+        return {}
+    try:
+        block = json.loads(side.read_text())
+    except ValueError:
+        return {}
+    return {"input_layout": block["input_layout"]} if isinstance(block, dict) and isinstance(block.get("input_layout"), str) else {}
+
+
 class HipUpscaleBackend(HipBackend):
     def to_luma(self, frame_bgr):
         d = frame_bgr if self.torch.is_tensor(frame_bgr) else self.native.to_device(frame_bgr, self.device)
@@ -224,7 +237,7 @@ class SimpleDepthUpscaler:
         if rank == 0:
             from .register import manifest_entries
             encode_depth4k(frames_dir, output_path, n, target_width, target_height, fps, self.radius, self.eps,
-                           {**depth_range_entry(depth_dir), **manifest_entries(self.spatial)} or None)
+                           {**depth_range_entry(depth_dir), **input_layout_entry(depth_dir), **manifest_entries(self.spatial)} or None)
         sharding.barrier()
         print(f"✓ Depth video saved: {output_path}")
         return output_path
