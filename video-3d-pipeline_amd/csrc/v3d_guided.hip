@@ -423,20 +423,40 @@ __device__ __forceinline__ int gf_swz2(int m) { return m ^ ((m >> 3) & 1) ^ ((m 
 __device__ __forceinline__ int gf_swz4(int m) { return m ^ ((m >> 4) & 3); }
 __device__ __forceinline__ int gf_c8(int c) { return 2 * gf_swz2(c >> 1) + (c & 1); }     // element of 8-byte column c
 
-// window sums of the four outputs c0 .. c0+3 of a swizzled f64 row (columns c0 - RR .. c0 + 3 + RR, r + 2 chunks)
+// A RUN'S ADDRESSES.  c0 and RR are multiples of 4, so a run's first chunk is even (f64 / int2 rows) or a multiple of 4 (int4
+// rows): its chunks come in aligned pairs (fours) that share the swizzle's XOR term, and chunk i of a group sits at
+// (first | term) ^ i.  The rows are GF_ROW_ALIGN-byte aligned in LDS, so the term is read off the BYTE ADDRESS itself (bits 7, 8
+// for gf_swz2, bits 8, 9 for gf_swz4) and a group costs one add, a shift or two and an OR, each further chunk one XOR -- against
+// an add, two shifts, an XOR and a shift-add per chunk when gf_swz2 / gf_swz4 are spelled out chunk by chunk.
+#define GF_ROW_ALIGN 1024
+typedef int gf_i32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const v3d_f64x2 gf_lds_f64x2;
+typedef __attribute__((address_space(3))) const gf_i32x4 gf_lds_i32x4;
+__device__ __forceinline__ uint32_t gf_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p; }
+// byte address of chunk 2 * jp of a run that starts at byte address w0 (chunk 2 * jp + 1: the same ^ 16)
+__device__ __forceinline__ uint32_t gf_pair_addr(uint32_t w0, int jp) { const uint32_t w = w0 + 32u * jp; return w | (((w >> 3) ^ (w >> 4)) & 16u); }
+// byte address of chunk 4 * jg (chunk 4 * jg + i: the same ^ 16 i)
+__device__ __forceinline__ uint32_t gf_quad_addr(uint32_t w0, int jg) { const uint32_t w = w0 + 64u * jg; return w | ((w >> 4) & 48u); }
+
+// window sums of the four outputs c0 .. c0+3 of a swizzled f64 row (columns c0 - RR .. c0 + 3 + RR, r + 2 chunks).  plane: byte
+// offset of a further plane with the same rows (a multiple of 512: the swizzle's bits stay, and the addresses of `row` serve
+// it at an immediate offset)
 template <int RR>
-__device__ __forceinline__ void gf_run4(const double* row, int c0, double s[4])
+__device__ __forceinline__ void gf_run4(const double* row, int c0, double s[4], uint32_t plane = 0u)
 {
-    const v3d_f64x2* d = reinterpret_cast<const v3d_f64x2*>(row);
-    const int m0 = (c0 - RR) >> 1;
+    static_assert(RR % 4 == 0, "aligned pairs of chunks, read as 4 + 4 + 2 (r = 8) or 4 + 2 (r = 4)");
+    const uint32_t w0 = gf_lds_addr(row) + 8u * (uint32_t)(c0 - RR);
     double c = 0.0, l0 = 0.0, l1 = 0.0, l2 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
 #pragma unroll
-    for (int k0 = 0; k0 < RR + 2; k0 += GF_CH) {
-        v3d_f64x2 w[GF_CH];
+    for (int k0 = 0; k0 < RR + 2; k0 += 4) {
+        v3d_f64x2 w[4];
 #pragma unroll
-        for (int i = 0; i < GF_CH; i++) if (k0 + i < RR + 2) w[i] = d[gf_swz2(m0 + k0 + i)];
+        for (int i = 0; i < 4; i += 2) if (k0 + i < RR + 2) {
+            const uint32_t a = gf_pair_addr(w0, (k0 + i) / 2);
+            w[i] = *(gf_lds_f64x2*)(uintptr_t)(a + plane); w[i + 1] = *(gf_lds_f64x2*)(uintptr_t)((a ^ 16u) + plane);
+        }
 #pragma unroll
-        for (int i = 0; i < GF_CH; i++) {
+        for (int i = 0; i < 4; i++) {
             const int k = k0 + i;
             if (k == 0) { l0 = w[i].x; l1 = w[i].y; c = w[i].x; c += w[i].y; }
             else if (k == 1) { l2 = w[i].x; c += w[i].x; c += w[i].y; }
@@ -453,16 +473,18 @@ __device__ __forceinline__ void gf_run4(const double* row, int c0, double s[4])
 template <int RR>
 __device__ __forceinline__ void gf_run4(const int2* row, int c0, int2 s[4])
 {
-    const int4* d = reinterpret_cast<const int4*>(row);
-    const int m0 = (c0 - RR) >> 1;
+    const uint32_t w0 = gf_lds_addr(row) + 8u * (uint32_t)(c0 - RR);
     int2 c = make_int2(0, 0), l0 = c, l1 = c, l2 = c, r1 = c, r2 = c, r3 = c;
 #pragma unroll
-    for (int k0 = 0; k0 < RR + 2; k0 += 3) {
-        int4 w[3];
+    for (int k0 = 0; k0 < RR + 2; k0 += 4) {
+        gf_i32x4 w[4];
 #pragma unroll
-        for (int i = 0; i < 3; i++) if (k0 + i < RR + 2) w[i] = d[gf_swz2(m0 + k0 + i)];
+        for (int i = 0; i < 4; i += 2) if (k0 + i < RR + 2) {
+            const uint32_t a = gf_pair_addr(w0, (k0 + i) / 2);
+            w[i] = *(gf_lds_i32x4*)(uintptr_t)a; w[i + 1] = *(gf_lds_i32x4*)(uintptr_t)(a ^ 16u);
+        }
 #pragma unroll
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < 4; i++) {
             const int k = k0 + i;
             const int2 a = make_int2(w[i].x, w[i].y), b = make_int2(w[i].z, w[i].w);
             if (k == 0) { l0 = a; l1 = b; c = make_int2(a.x + b.x, a.y + b.y); }
@@ -483,16 +505,18 @@ __device__ __forceinline__ void gf_run4(const int2* row, int c0, int2 s[4])
 template <int RR>
 __device__ __forceinline__ void gf_run4(const int4* row, int c0, int4 s[4])
 {
-    int4 c = make_int4(0, 0, 0, 0), l0 = c, l1 = c, l2 = c, r1 = c, r2 = c, r3 = c;
+    const uint32_t w0 = gf_lds_addr(row) + 16u * (uint32_t)(c0 - RR);
+    gf_i32x4 c = { 0, 0, 0, 0 }, l0 = c, l1 = c, l2 = c, r1 = c, r2 = c, r3 = c;
 #pragma unroll
-    for (int k0 = 0; k0 < 2 * RR + 4; k0 += 3) {
-        int4 u[3];
+    for (int k0 = 0; k0 < 2 * RR + 4; k0 += 4) {
+        const uint32_t a = gf_quad_addr(w0, k0 / 4);
+        gf_i32x4 u[4];
 #pragma unroll
-        for (int i = 0; i < 3; i++) if (k0 + i < 2 * RR + 4) u[i] = row[gf_swz4(c0 - RR + k0 + i)];
+        for (int i = 0; i < 4; i++) u[i] = *(gf_lds_i32x4*)(uintptr_t)(a ^ (16u * i));
 #pragma unroll
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < 4; i++) {
             const int k = k0 + i;
-            if (k < 2 * RR + 1) { c.x += u[i].x; c.y += u[i].y; c.z += u[i].z; c.w += u[i].w; }
+            if (k < 2 * RR + 1) c += u[i];
             if (k == 0) l0 = u[i];
             else if (k == 1) l1 = u[i];
             else if (k == 2) l2 = u[i];
@@ -500,14 +524,13 @@ __device__ __forceinline__ void gf_run4(const int4* row, int c0, int4 s[4])
             else if (k == 2 * RR + 2) r2 = u[i];
             else if (k == 2 * RR + 3) r3 = u[i];
         }
-        asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w) :: "memory");
+        asm volatile("" : "+v"(c) :: "memory");   // the group's adds cannot sink below the next group's reads
     }
     // the column leaving is subtracted BEFORE the entering one is added: no intermediate spans more than the 2r + 1 columns of a
     // window, so sum g*P stays below 2^31 on the whole documented domain (an 18-column partial sum passes it from d = 1721 on)
-    s[0] = c;
-    s[1] = make_int4(s[0].x - l0.x + r1.x, s[0].y - l0.y + r1.y, s[0].z - l0.z + r1.z, s[0].w - l0.w + r1.w);
-    s[2] = make_int4(s[1].x - l1.x + r2.x, s[1].y - l1.y + r2.y, s[1].z - l1.z + r2.z, s[1].w - l1.w + r2.w);
-    s[3] = make_int4(s[2].x - l2.x + r3.x, s[2].y - l2.y + r3.y, s[2].z - l2.z + r3.z, s[2].w - l2.w + r3.w);
+    const gf_i32x4 s1 = c - l0 + r1, s2 = s1 - l1 + r2, s3 = s2 - l2 + r3;
+    s[0] = make_int4(c.x, c.y, c.z, c.w); s[1] = make_int4(s1.x, s1.y, s1.z, s1.w);
+    s[2] = make_int4(s2.x, s2.y, s2.z, s2.w); s[3] = make_int4(s3.x, s3.y, s3.z, s3.w);
 }
 
 // a, b of the four pixels hgx .. hgx+3 of row y from their window sums {sum g, sum g*g} (exact ints), {sum p, sum g*p}
@@ -519,10 +542,10 @@ __device__ __forceinline__ void gf_solve4(const int sg[4], const int sgg[4], con
     int cx[4];
 #pragma unroll
     for (int n = 0; n < 4; n++) cx[n] = min(hgx + n + RR, W - 1) - max(hgx + n - RR, 0) + 1;
-    const double inv0 = gf_rcp((double)(cx[0] * cy));
+    const double inv0 = gf_rcp((double)(int)__umul24((uint32_t)cx[0], (uint32_t)cy));          // (counts <= 2r + 1: a 24-bit multiply is exact)
 #pragma unroll
     for (int n = 0; n < 4; n++) {
-        const double inv = (n == 0 || cx[n] == cx[0]) ? inv0 : gf_rcp((double)(cx[n] * cy));
+        const double inv = (n == 0 || cx[n] == cx[0]) ? inv0 : gf_rcp((double)(int)__umul24((uint32_t)cx[n], (uint32_t)cy));
         const double mI = (double)sg[n] * (inv * (1.0 / 255.0)), mp = sp[n] * inv;
         const double mII = (double)sgg[n] * (inv * (1.0 / 65025.0)), mIp = sgp[n] * (inv * (1.0 / 255.0));
         const double var = fma(-mI, mI, mII), cov = fma(-mI, mp, mIp);
@@ -549,12 +572,14 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
     // stage 1's column sums of the step's four rows: I1 one int4 {sum g, sum g*g, sum P, sum g*P}; general path {sum p, sum g*p}
     // f64 planes + {sum g, sum g*g} int2
     constexpr int S1D = 2 * 4 * 2 * COLS * 8, S1 = I1 ? 2 * 4 * COLS * 16 : S1D + 2 * 4 * COLS * 8;
-    __shared__ __attribute__((aligned(16))) unsigned char sS1[S1];
+    // (every row of these arrays starts on a multiple of 512 bytes, the int4 rows of 1024: gf_run4 reads the swizzle off the address)
+    static_assert((COLS * 8) % 512 == 0 && (COLS * 16) % GF_ROW_ALIGN == 0 && S1D % GF_ROW_ALIGN == 0, "row alignment of the swizzled LDS rows");
+    __shared__ __attribute__((aligned(GF_ROW_ALIGN))) unsigned char sS1[S1];
     double (*sV1)[4][2][COLS] = reinterpret_cast<double (*)[4][2][COLS]>(sS1);       // [buffer][row][sum p | sum g*p][column]
     int2 (*sVi)[4][COLS] = reinterpret_cast<int2 (*)[4][COLS]>(sS1 + (I1 ? 0 : S1D));  // [buffer][row][column] {sum g, sum g*g}
     int4 (*sVq)[4][COLS] = reinterpret_cast<int4 (*)[4][COLS]>(sS1);                  // I1: [buffer][row][column]
     (void)sV1; (void)sVi; (void)sVq;
-    __shared__ __attribute__((aligned(16))) double sAB[3][4][2][COLS];    // [ring slot][row][a | b, then sum a | sum b][column]
+    __shared__ __attribute__((aligned(GF_ROW_ALIGN))) double sAB[3][4][2][COLS];    // [ring slot][row][a | b, then sum a | sum b][column]
     {   // frame of the batch
         const size_t f = blockIdx.z, n4 = (size_t)W * H;
         depth_lo += f * depth_stride; guide += f * guide_stride; out += f * n4;
@@ -598,28 +623,69 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
             bxa = min(max((int)x0f, 0), Wlo - 1); bxb = min(max((int)x0f + 1, 0), Wlo - 1);
         }
         (void)wxa; (void)wxb; (void)bwx;
-        // inputs of the four rows a step consumes, fetched one step ahead; loads UNCONDITIONAL, from clamped addresses (see k_gfm)
-        struct RowIn { int g; typename std::conditional<I1, int, float>::type a0, a1, b0, b1; bool in; };
-        auto fetch_row = [&](int tt) -> RowIn {
-            RowIn q;
-            const int e = ya - 2 * RR + tt;                                      // input row entering the window
-            q.in = col_ok && e >= 0 && e < H && tt < nrows;
-            const int ec = min(max(e, 0), H - 1);
-            q.g = guide[(size_t)ec * W + gxc];
-            if constexpr (I1) {
-                const int ky = ec >> 1;
-                const TD* ra = depth_lo + (size_t)min(max((ec & 1) ? ky : ky - 1, 0), Hlo - 1) * Wlo;
-                const TD* rb = depth_lo + (size_t)min(max((ec & 1) ? ky + 1 : ky, 0), Hlo - 1) * Wlo;
-                q.a0 = max((int)ra[bxa], 0); q.a1 = max((int)ra[bxb], 0); q.b0 = max((int)rb[bxa], 0); q.b1 = max((int)rb[bxb], 0);   // depth.py:374: <= 0 -> 0
-            } else {
+        // GF_BRANCH NOTE (the one place that says it).  Three rare cases of this role are kept as BRANCHES by an empty
+        // `asm volatile("")` in their body: the image's last run when W % 4 != 0 (H1), a row outside the image or the band's input
+        // (V1), and the rotation of a band that starts on an odd row (V1), whose three copies are spelled as v_mov_b32 in asm.
+        // Why not plain C++: hipcc (ROCm 7) if-converts each of them into selects that EVERY step executes -- twelve v_cndmask_b32
+        // per run for the first, two per row for the second -- and, for the rotation, computes both row orders (twelve
+        // multiply-adds for four) or, given a branch, places the rotation's copies on the even path, the one every default band
+        // takes.  The asm carries no semantics of its own (the copies are %3 <- %2 <- %1 <- %0 on four distinct registers); a
+        // toolchain that branches here unaided makes the statements unnecessary, not wrong.  tools/isa.sh shows the step's
+        // stream; DESIGN.md section 4 has the counts.
+        // I1: the inputs of a STEP, fetched one step ahead.  The step's four consecutive 4K rows e0 .. e0+3 (e0 = ya - 2r + 4s,
+        // of ya's parity) touch the source rows sb .. sb+3 only, sb = (e0 >> 1) - 1 + (e0 & 1):
+        //   e0 even: rows (0,1) x (1,3), (1,2) x (3,1), (1,2) x (1,3), (2,3) x (3,1);  e0 odd: (0,1) x (3,1), (0,1) x (1,3),
+        //   (1,2) x (3,1), (1,2) x (1,3) -- the fourth is loaded and not used.
+        // So a step loads 4 source rows x {bxa, bxb} and four guide bytes.  Every load is a raw buffer load: the row (clamped on
+        // the scalar unit) is the scalar offset, the column a 32-bit lane constant -- no 64-bit address arithmetic per lane.  A
+        // lane whose column is outside the image carries V3D_BUF_OOB and reads 0 = "g = 0, P = 0"; rows outside the image or the
+        // band's input are zeroed when they enter the ring (uniform).  Loads stay unconditional.
+        // (the descriptors' sizes and the row offsets are 32-bit products: launch_gff takes this route only when the guide frame,
+        // W * H bytes, is below 2 GiB, and the depth frame is half of that)
+        struct StepIn { int16_t d[4][2]; uint8_t g[4]; };
+        const __amdgpu_buffer_rsrc_t rs_d = buf_rsrc(depth_lo, (uint32_t)Wlo * (uint32_t)Hlo * 2u), rs_g = buf_rsrc(guide, (uint32_t)W * (uint32_t)H);
+        const uint32_t og = col_ok ? (uint32_t)gxc : V3D_BUF_OOB;
+        const uint32_t oa = col_ok ? 2u * (uint32_t)bxa : V3D_BUF_OOB, ob = col_ok ? 2u * (uint32_t)bxb : V3D_BUF_OOB;
+        const int par = ya & 1;                                                  // uniform: parity of every step's first row
+        auto fetch_step = [&](int s) -> StepIn {
+            StepIn q;
+            const int e0 = ya - 2 * RR + 4 * s, sb = (e0 >> 1) - 1 + par;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t so = (uint32_t)min(max(sb + j, 0), Hlo - 1) * (2u * (uint32_t)Wlo);
+                q.d[j][0] = __builtin_amdgcn_raw_buffer_load_b16(rs_d, oa, so, 0);
+                q.d[j][1] = __builtin_amdgcn_raw_buffer_load_b16(rs_d, ob, so, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                q.g[i] = __builtin_amdgcn_raw_buffer_load_b8(rs_g, og, (uint32_t)min(max(e0 + i, 0), H - 1) * (uint32_t)W, 0);
+            return q;
+        };
+        (void)rs_d; (void)rs_g; (void)og; (void)oa; (void)ob; (void)par;
+        // general: inputs of the four rows a step consumes, fetched one step ahead; loads UNCONDITIONAL, from clamped addresses (see k_gfm)
+        struct RowIn { int g; float a0, a1, b0, b1; bool in; };
+        struct RowIn4 { RowIn r[4]; };
+        auto fetch_rows = [&](int t0) -> RowIn4 {
+            RowIn4 q4;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                RowIn& q = q4.r[k];
+                const int tt = t0 + k, e = ya - 2 * RR + tt;                     // input row entering the window
+                q.in = col_ok && e >= 0 && e < H && tt < nrows;
+                const int ec = min(max(e, 0), H - 1);
+                q.g = guide[(size_t)ec * W + gxc];
                 const double fy = (e + 0.5) * sy - 0.5, y0f = floor(fy);
                 const TD* ra = depth_lo + (size_t)min(max((int)y0f, 0), Hlo - 1) * Wlo;
                 const TD* rb = depth_lo + (size_t)min(max((int)y0f + 1, 0), Hlo - 1) * Wlo;
                 q.a0 = gf_ld(ra, bxa); q.a1 = gf_ld(ra, bxb); q.b0 = gf_ld(rb, bxa); q.b1 = gf_ld(rb, bxb);
             }
-            return q;
+            return q4;
         };
-        RowIn nx[4] = { fetch_row(0), fetch_row(1), fetch_row(2), fetch_row(3) };
+        (void)fetch_step; (void)fetch_rows;
+        // the inputs of the next step: one type per route, so neither route carries the other's state
+        typename std::conditional<I1, StepIn, RowIn4>::type nxt;
+        if constexpr (I1) nxt = fetch_step(0);
+        else nxt = fetch_rows(0);
         for (int p0 = 0; p0 < NP; p0 += R) {
 #pragma clang loop unroll(full)
             for (int sp = 0; sp < R; sp++) {
@@ -635,7 +701,8 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                         const int y = ya - 3 * RR + 4 * j + hrow;                // centre row of this window
                         double a[4] = { 0.0, 0.0, 0.0, 0.0 }, b[4] = { 0.0, 0.0, 0.0, 0.0 };
                         // a/b columns of the strip; hgx is a multiple of 4, so a run is left of the image or not at all
-                        if (c0 >= RR && c0 < COLS - RR && y >= 0 && y < H && hgx >= 0 && hgx < W) {
+                        // (one condition, one branch: as a chain of && the zeros above were written once per nested branch)
+                        if ((int)(c0 >= RR) & (int)(c0 < COLS - RR) & (int)(y >= 0) & (int)(y < H) & (int)(hgx >= 0) & (int)(hgx < W)) {
                             int sg[4], sgg[4]; double sp_[4], sgp[4];
                             if constexpr (I1) {
                                 int4 s[4];
@@ -649,13 +716,16 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                                 int2 si[4];
                                 gf_run4<RR>(&sVi[j & 1][hrow][0], c0, si);
                                 gf_run4<RR>(&sV1[j & 1][hrow][0][0], c0, sp_);
-                                gf_run4<RR>(&sV1[j & 1][hrow][1][0], c0, sgp);
+                                gf_run4<RR>(&sV1[j & 1][hrow][0][0], c0, sgp, COLS * 8u);
 #pragma unroll
                                 for (int n = 0; n < 4; n++) { sg[n] = si[n].x; sgg[n] = si[n].y; }
                             }
                             gf_solve4<RR>(sg, sgg, sp_, sgp, hgx, y, W, H, eps, a, b);
+                            if (hgx + 3 >= W) {                                  // the image's last run, W % 4 != 0 only (GF_BRANCH NOTE)
+                                asm volatile("");
 #pragma unroll
-                            for (int n = 0; n < 4; n++) if (hgx + n >= W) { a[n] = 0.0; b[n] = 0.0; }
+                                for (int n = 1; n < 4; n++) if (hgx + n >= W) { a[n] = 0.0; b[n] = 0.0; }
+                            }
                         }
                         // rows and columns outside the image (and the strip's halo) hand ZERO a/b to stage 2 (its windows count
                         // in-image pixels only); every column of the four rows is written
@@ -669,34 +739,53 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                     // ---- V1(p): four input rows enter the column's window ----
                     if (p < NS) {
                         const int tA = 4 * p;
-                        const RowIn cur[4] = { nx[0], nx[1], nx[2], nx[3] };
-#pragma unroll
-                        for (int k = 0; k < 4; k++) nx[k] = fetch_row(tA + 4 + k);
                         const bool emit = p >= RR / 2;                           // uniform (2r rows of warm-up: a multiple of 4)
+                        if constexpr (I1) {
+                            const StepIn cs = nxt;
+                            nxt = fetch_step(p + 1);
+                            // separable x2 bilinear: the horizontal term once per SOURCE row, then one multiply-add per 4K row.
+                            // All factors are below 2^24 (d <= 32767, h <= 4 d, P <= 16 d): 24-bit multiplies, the same integers
+                            uint32_t h[4], P4[4];                                // P4: 256 p of the step's four rows
 #pragma unroll
-                        for (int rr = 0; rr < 4; rr++) {
-                            const int slot = (4 * sp + rr) % R;                  // compile-time ring slot
-                            const int e = ya - 2 * RR + tA + rr;                 // (in the image when cur[rr].in)
-                            if constexpr (I1) {
-                                int gn = 0, Pn = 0;
-                                if (cur[rr].in) {
-                                    gn = cur[rr].g;
-                                    const int wya = (e & 1) ? 3 : 1;
-                                    Pn = wya * (wxa * cur[rr].a0 + wxb * cur[rr].a1) + (4 - wya) * (wxa * cur[rr].b0 + wxb * cur[rr].b1);   // 256 p
+                            for (int j = 0; j < 4; j++)                          // depth.py:374: <= 0 -> 0
+                                h[j] = __umul24((uint32_t)wxa, (uint32_t)max((int)cs.d[j][0], 0)) + __umul24((uint32_t)wxb, (uint32_t)max((int)cs.d[j][1], 0));
+                            P4[0] = __umul24(h[1], 3u) + h[0]; P4[1] = __umul24(h[1], 3u) + h[2];
+                            P4[2] = __umul24(h[2], 3u) + h[1]; P4[3] = __umul24(h[2], 3u) + h[3];
+                            // a band that starts on an odd row (GF_BRANCH NOTE above): the rows rotate IN PLACE, in asm
+                            if (par) {
+                                asm volatile("v_mov_b32 %3, %2\n\tv_mov_b32 %2, %1\n\tv_mov_b32 %1, %0"
+                                             : "+v"(P4[0]), "+v"(P4[1]), "+v"(P4[2]), "+v"(P4[3]));
+                                P4[0] = __umul24(h[0], 3u) + h[1];
+                            }
+#pragma unroll
+                            for (int rr = 0; rr < 4; rr++) {
+                                const int slot = (4 * sp + rr) % R;              // compile-time ring slot
+                                const int e = ya - 2 * RR + tA + rr;
+                                uint32_t gn = cs.g[rr], Pn = P4[rr];             // (a column outside the image read zeros)
+                                if (!(e >= 0 && e < H && tA + rr < nrows)) {     // uniform, rare (GF_BRANCH NOTE)
+                                    asm volatile("");
+                                    gn = 0u; Pn = 0u;
                                 }
-                                const int go = (int)(ring[slot] & 0xFFu), Po = (int)(ring[slot] >> 8);
-                                ring[slot] = ((uint32_t)Pn << 8) | (uint32_t)gn;
-                                vg += gn - go; vgg += gn * gn - go * go;
-                                vP += Pn - Po; vgP += gn * Pn - go * Po;
+                                const uint32_t go = ring[slot] & 0xFFu, Po = ring[slot] >> 8;
+                                ring[slot] = (Pn << 8) | gn;
+                                vg += (int)(gn - go); vgg += (int)(__umul24(gn, gn) - __umul24(go, go));
+                                vP += (int)(Pn - Po); vgP += (int)(__umul24(gn, Pn) - __umul24(go, Po));
                                 if (emit) sVq[p & 1][rr][gf_swz4(t)] = make_int4(vg, vgg, vP, vgP);
-                            } else {
+                            }
+                        } else {
+                            const RowIn4 cur = nxt;
+                            nxt = fetch_rows(tA + 4);
+#pragma unroll
+                            for (int rr = 0; rr < 4; rr++) {
+                                const int slot = (4 * sp + rr) % R;              // compile-time ring slot
+                                const int e = ya - 2 * RR + tA + rr;             // (in the image when cur.r[rr].in)
                                 int gn = 0; double pn = 0.0;
-                                if (cur[rr].in) {
-                                    gn = cur[rr].g;
+                                if (cur.r[rr].in) {
+                                    gn = cur.r[rr].g;
                                     const double fy = (e + 0.5) * sy - 0.5, wy = fy - floor(fy);
-                                    const double a0 = (double)cur[rr].a0, b0 = (double)cur[rr].b0;
-                                    const double top = fma(bwx, (double)cur[rr].a1 - a0, a0);
-                                    const double bot = fma(bwx, (double)cur[rr].b1 - b0, b0);
+                                    const double a0 = (double)cur.r[rr].a0, b0 = (double)cur.r[rr].b0;
+                                    const double top = fma(bwx, (double)cur.r[rr].a1 - a0, a0);
+                                    const double bot = fma(bwx, (double)cur.r[rr].b1 - b0, b0);
                                     pn = fma(wy, bot - top, top);
                                 }
                                 const int go = (int)((rgw[slot >> 2] >> (8 * (slot & 3))) & 0xFFu); const double po = r1[slot];
@@ -739,12 +828,12 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                         if (j >= RR && j < NS && c0 >= 2 * RR && c0 < COLS - 2 * RR && hgx < W && y < yb) {
                             double sa[4], sb[4];
                             gf_run4<RR>(&sAB[j % 3][hrow][0][0], c0, sa);
-                            gf_run4<RR>(&sAB[j % 3][hrow][1][0], c0, sb);
+                            gf_run4<RR>(&sAB[j % 3][hrow][0][0], c0, sb, COLS * 8u);
                             const int cy = min(y + RR, H - 1) - max(y - RR, 0) + 1;
                             int cx[4];
 #pragma unroll
                             for (int n = 0; n < 4; n++) cx[n] = min(hgx + n + RR, W - 1) - max(hgx + n - RR, 0) + 1;
-                            const double inv0 = gf_rcp((double)(cx[0] * cy));
+                            const double inv0 = gf_rcp((double)(int)__umul24((uint32_t)cx[0], (uint32_t)cy));
                             const size_t o = (size_t)y * W + hgx;
                             const bool all_in = hgx + 3 < W;
                             const bool vec_ok = all_in && (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(out + o) | reinterpret_cast<uintptr_t>(guide + o)) & 3) == 0
@@ -761,7 +850,7 @@ __global__ __launch_bounds__(2 * COLS, I1 ? 4 : 2) void k_gff(const TD* __restri
                             float q[4];
 #pragma unroll
                             for (int n = 0; n < 4; n++) {
-                                const double inv = (n == 0 || cx[n] == cx[0]) ? inv0 : gf_rcp((double)(cx[n] * cy));
+                                const double inv = (n == 0 || cx[n] == cx[0]) ? inv0 : gf_rcp((double)(int)__umul24((uint32_t)cx[n], (uint32_t)cy));
                                 const double I = (double)g[n] * (1.0 / 255.0);
                                 q[n] = (float)((sa[n] * inv) * I + (sb[n] * inv));
                             }
@@ -810,7 +899,8 @@ static void launch_gff(const TD* depth_lo, int Wlo, int Hlo, const uint8_t* guid
 {
     // int16 disparity, exact 2x: stage 1 in exact integers (80 KB of LDS: two workgroups per CU); the f64 route needs 96 KB (one)
     bool i1 = false;
-    if constexpr (std::is_same<TD, int16_t>::value) i1 = g_v3d_opt.gf_int1 && W == 2 * Wlo && H == 2 * Hlo;
+    // (its loads address a frame by 32-bit buffer offsets: a guide of 2 GiB or more takes the f64 route, same bits)
+    if constexpr (std::is_same<TD, int16_t>::value) i1 = g_v3d_opt.gf_int1 && W == 2 * Wlo && H == 2 * Hlo && (size_t)W * H < ((size_t)1 << 31);
     const int cols = g_v3d_opt.gf_cols == 512 && i1 ? 512 : 256;     // 512-column strips: I1 only (160 KB, one workgroup per CU)
     int band = g_v3d_opt.gf_band;
     if (band <= 0) {
