@@ -673,6 +673,41 @@ int v3d_warp_u16_batch(const uint16_t* src, int n, int Ws, int Hs, size_t src_st
                        int64_t ax, int64_t bx, int64_t ay, int64_t by, uint16_t fill,
                        uint16_t* out /* [n][Ho][Wo] */, int Wo, int Ho, void* stream);
 
+/* Colour matching (v3d_colour.hip): per-channel histogram transfer between two releases of a film (colour.py: the convert CLI's
+   --match-colour, which corrects the SBS clip's right eye before v3d_render_stereo_source_batch samples it).  No call site in the
+   reference.  Bit-exact contract, all integers, no floating point in any of the three entries: tests/colour_ref.py.
+   Images: frame f at base + f*frame_stride (bytes), rows `pitch` bytes apart, pixel x of a row in its bytes 3x .. 3x+2 (channel
+   c = byte 3x + c); the rectangle is the pixels [x0, x1) x [y0, y1).  No alignment is needed anywhere.
+   Histogram: hist[f][c][v] = the number of pixels of frame f's rectangle whose byte c equals v; u32 dense [n][3][256], OVERWRITTEN
+   (zeroing it is part of the entry: it may hold anything).  Two launches; sums of integers, so the order of the atomics cannot
+   change a bit, and a frame's histogram does not depend on n, on its place in the batch, on the pitch or on the strides.  Memory
+   contract: a row of the rectangle is read as the aligned 16-byte blocks that hold at least one of its bytes and nothing else is
+   touched; bytes of such a block outside the rectangle are not counted.  V3D_ERR_ARG: null pointer, n outside [1, 65535], W or H
+   outside [1, 65535] (an area stays below 2^32: no counter can wrap), pitch < 3W, frame_stride < H*pitch with n > 1, a rectangle
+   that is empty or leaves the image.
+   Table: table j is built from the frames [j*group, min(n, (j+1)*group)) of hist_src and hist_dst (both u32 [n][3][256], e.g. what
+   the entry above wrote), summed per bin in 64 bits.  Per channel, with Cs and Cf the inclusive prefix sums of the two sums and
+   Ns = Cs[255], Nf = Cf[255] the totals:
+     lut[j][c][v] = the smallest u with Cf[u] * Ns >= Cs[v] * Nf,   the identity v if Ns == 0 or Nf == 0.
+   The two products are compared exactly (totals reach 2^32 * 65535 < 2^48, products 2^96: 128-bit integers).  u exists
+   (u = 255 satisfies it) and, Cs being non-decreasing, the table is monotone: v <= v' gives lut[v] <= lut[v'].  A level below
+   the source's first occupied one has Cs = 0 and maps to 0.  lut u8 dense [ceil(n/group)][3][256].  One launch.  V3D_ERR_ARG: null
+   pointer, n outside [1, 65535], group outside [1, n].
+   Apply: for every pixel of the rectangle and channel c: dst = lut[f*lut_stride + 256 c + src]; lut_stride 0 = one table for all
+   frames, else >= 768 bytes from one frame's table to the next.  dst has the source's size, its own pitch and frame stride.  Only
+   the rectangle's bytes of src and of lut's tables are read, and no byte of dst outside the rectangle is written or read.  dst ==
+   src with dst_pitch == pitch and (n == 1 or dst_stride == src_stride) is the in-place case; any other overlap of the two images'
+   extents is refused.  One launch.  V3D_ERR_ARG: as the histogram's for both images, lut_stride in [1, 767], such an overlap.
+   All three entries enqueue on `stream`, never synchronise, never allocate, read no environment and take device pointers only; a
+   refused call enqueues nothing. */
+int v3d_bgr_hist_batch(const uint8_t* bgr, size_t frame_stride /* bytes */, int n, int W, int H, int pitch,
+                       int x0, int y0, int x1, int y1, uint32_t* hist /* [n][3][256] */, void* stream);
+int v3d_colour_lut_batch(const uint32_t* hist_src, const uint32_t* hist_dst, int n, int group,
+                         uint8_t* lut /* [ceil(n/group)][3][256] */, void* stream);
+int v3d_bgr_lut_batch(const uint8_t* src, size_t src_stride /* bytes */, int n, int W, int H, int pitch,
+                      int x0, int y0, int x1, int y1, const uint8_t* lut, int lut_stride /* bytes; 0: one table */,
+                      uint8_t* dst, size_t dst_stride /* bytes */, int dst_pitch, void* stream);
+
 const char* v3d_last_error(void);
 const char* v3d_version(void);
 

@@ -69,6 +69,26 @@ __device__ __forceinline__ excl_total block_excl_add_u32(uint32_t v, int lane, i
     return { base + inc - v, total };
 }
 
+// ---- workgroup inclusive add-scan of 64-bit values: the sum of v over the threads up to and including mine, and over all of them
+// (two 32-bit halves per shuffle step, as wave_sum_u64).  `tot` (WAVES double words of LDS) as above: busy until the workgroup's
+// next barrier after the call ----
+struct incl_total64 { unsigned long long incl, total; };
+template <int WAVES>
+__device__ __forceinline__ incl_total64 block_incl_add_u64(unsigned long long v, int lane, int wave, unsigned long long* tot)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t lo = __shfl_up((uint32_t)v, o), hi = __shfl_up((uint32_t)(v >> 32), o);
+        if (lane >= o) v += ((unsigned long long)hi << 32) | lo;
+    }
+    if (lane == 63) tot[wave] = v;
+    __syncthreads();
+    unsigned long long base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) { const unsigned long long t = tot[w]; total += t; if (w < wave) base += t; }
+    return { base + v, total };
+}
+
 // ---- two-sided nearest-neighbour scan.  Thread t holds p = a key of the last item of its run and s = a key of the first one, keys
 // that grow towards the side they are looked at from; 0 means the run has none.  The result is the max of p over the threads
 // before mine and the combination R of s over the threads after mine: the nearest item on either side.  R is the max (sentinel

@@ -119,6 +119,9 @@ SIGNATURES = {
     "v3d_profile_match_ws_bytes": (sz, [ci, ci, ci]),
     "v3d_profile_match_scores": (ci, [vp, ci, vp, ci, ci, vp, ci, ci, vp, vp, vp]),
     "v3d_warp_u16_batch": (ci, [vp, ci, ci, ci, sz, i64, i64, i64, i64, C.c_uint16, vp, ci, ci, vp]),
+    "v3d_bgr_hist_batch": (ci, [vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "v3d_colour_lut_batch": (ci, [vp, vp, ci, ci, vp, vp]),
+    "v3d_bgr_lut_batch": (ci, [vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, sz, ci, vp]),
     "v3d_last_error": (cs, []),
     "v3d_version": (cs, []),
 }
@@ -1087,6 +1090,67 @@ def warp_u16_batch(src, ax, bx, ay, by, Wo, Ho, fill=0, out=None):
         raise ValueError(f"fill must lie in [0, 65535], got {fill!r}")
     _call("v3d_warp_u16_batch", src.device, s, n, Ws, Hs, ss, int(ax), int(bx), int(ay), int(by), int(fill),
           _dev(out, torch.int16, "out"), int(Wo), int(Ho))
+    return out
+
+
+def _bgr_frames(t, what):
+    """a u8 [n,H,W,3] device tensor of dense BGR triples (the row pitch and the frame stride may differ) -> (pointer, frame stride,
+    n, W, H, pitch), strides in bytes"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+        raise NativeError(f"{what}: expected a uint8 [n,H,W,3] device tensor")
+    if t.stride(3) != 1 or t.stride(2) != 3:
+        raise NativeError(f"{what}: pixels must be dense BGR triples (only the row pitch and the frame stride may differ)")
+    n, H, W, _ = t.shape
+    pitch = t.stride(1) if H > 1 else 3 * W
+    return C.c_void_p(t.data_ptr()), (t.stride(0) if n > 1 else H * pitch), n, W, H, pitch
+
+
+def _rect(rect, W, H):
+    """(x0, y0, x1, y1) or None = the whole image, as four ints (the entry checks them)"""
+    return (0, 0, W, H) if rect is None else tuple(int(v) for v in rect)
+
+
+def bgr_hist_batch(bgr, rect=None, out=None):
+    """u8 [n,H,W,3] BGR frames on the device -> int32 [n,3,256] (the bits of uint32 counts): per frame and channel, how often each
+    level occurs among the pixels [x0, x1) x [y0, y1) of rect = (x0, y0, x1, y1), None = the whole image (v3d_bgr_hist_batch;
+    bit-exact contract: tests/colour_ref.py)"""
+    p, fs, n, W, H, pitch = _bgr_frames(bgr, "bgr")
+    out = _out(out, (n, 3, 256), torch.int32, bgr.device)
+    _call("v3d_bgr_hist_batch", bgr.device, p, fs, n, W, H, pitch, *_rect(rect, W, H), _dev(out, torch.int32, "out"))
+    return out
+
+
+def colour_lut_batch(hist_src, hist_dst, group=1, out=None):
+    """two int32 [n,3,256] histogram sets -> u8 [ceil(n/group),3,256]: table j maps the levels of the source frames [j group,
+    (j+1) group) onto the target's by histogram matching, exactly and monotonically (v3d_colour_lut_batch)"""
+    if not isinstance(hist_src, torch.Tensor) or hist_src.dim() != 3 or tuple(hist_src.shape[1:]) != (3, 256) or hist_src.shape != hist_dst.shape:
+        raise NativeError("hist_src / hist_dst: expected two int32 [n,3,256] device tensors of one shape")
+    n, group = hist_src.shape[0], int(group)
+    if not 1 <= group <= n:
+        raise ValueError(f"group must lie in [1, {n}], got {group!r}")
+    out = _out(out, ((n + group - 1) // group, 3, 256), torch.uint8, hist_src.device)
+    _call("v3d_colour_lut_batch", hist_src.device, _dev(hist_src, torch.int32, "hist_src"), _dev(hist_dst, torch.int32, "hist_dst"),
+          n, group, _dev(out, torch.uint8, "out"))
+    return out
+
+
+def bgr_lut_batch(src, lut, rect=None, out=None):
+    """out = lut[channel][src] on the pixels of rect (None = the whole image) of u8 [n,H,W,3] BGR frames on the device; lut u8
+    [3,256] or [1,3,256] (one table for all frames) or [n,3,256] (one per frame).  out=src works in place; out=None gives a new
+    tensor that equals src outside the rectangle (v3d_bgr_lut_batch)"""
+    p, fs, n, W, H, pitch = _bgr_frames(src, "src")
+    if not isinstance(lut, torch.Tensor) or tuple(lut.shape[-2:]) != (3, 256) or lut.dim() not in (2, 3) or \
+            (lut.dim() == 3 and lut.shape[0] not in (1, n)):
+        raise NativeError(f"lut: expected a uint8 [3,256] or [1 or {n},3,256] device tensor")
+    x0, y0, x1, y1 = _rect(rect, W, H)
+    if out is None:
+        whole = (x0, y0, x1, y1) == (0, 0, W, H)
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=src.device) if whole else src.clone(memory_format=torch.contiguous_format)
+    if tuple(out.shape) != tuple(src.shape):
+        raise NativeError(f"out: expected shape {tuple(src.shape)}, got {tuple(out.shape)}")
+    q, qs, _, _, _, qpitch = _bgr_frames(out, "out")
+    _call("v3d_bgr_lut_batch", src.device, p, fs, n, W, H, pitch, x0, y0, x1, y1, _dev(lut, torch.uint8, "lut"),
+          768 if lut.dim() == 3 and lut.shape[0] == n and n > 1 else 0, q, qs, qpitch)
     return out
 
 

@@ -19,6 +19,8 @@ stores the matcher's disparity itself (64 s / 65535 pixels of its eye), and sour
 eye's target of a pixel is x - round(K s d): the left eye is the 4K frame, the right eye sits where the SBS release had it.
 --fill-from-source SBS_CLIP then takes the disocclusions of that right eye from the SBS clip's stored right eye
 (v3d_render_stereo_source_batch; contract: tests/stereo_source_ref.py) instead of stretching the background into them.
+--match-colour clip|frame first fits that eye's colours to the 4K frame's (colour.py: the SBS clip is another release, with another
+grading; per-channel histogram matching left eye -> 4K frame, applied to the right eye on the device; contract: tests/colour_ref.py).
 
 Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
 cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
@@ -187,6 +189,8 @@ def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, 
         man.update(parallax="source", parallax_scale=params["parallax_scale"], parallax_gain=params["parallax_gain"])
     if params.get("fill_from_source"):
         man.update(fill_from_source=params["fill_from_source"], source_start_frame=params.get("source_start_frame", 0))
+    if params.get("match_colour"):
+        man.update({k: params[k] for k in ("match_colour", "colour_probe_frames", "colour_lut") if k in params})
     finish_sequence(frames_dir, "frame_%06d.png", output_path, fps, man)
 
 
@@ -224,7 +228,9 @@ class HipRenderBackend(HipBackend):
         frames and is reused (the synchronise at the end of the previous call made that safe); the output block comes from
         torch's caching host allocator and returns to it once the writers drop the last frame of it.
         source (--fill-from-source): dict(frames: the SBS BGR frames [Hs,Ws,3] of this batch, fill_eyes, q: (ax, bx, ay, by)) -- the
-        render is v3d_render_stereo_source_batch, one launch all the same"""
+        render is v3d_render_stereo_source_batch, one launch all the same.  With a `match` entry (--match-colour: ColourMatcher.
+        source_entry) the right-eye half of the uploaded SBS frames is colour-matched in place before that launch: with the clip's
+        table, or with one table per frame fitted to this batch (two histograms, the tables, the apply); nothing synchronises"""
         torch, nat = self.torch, self.native
         n = len(frames)
         H, W = depths[0].shape
@@ -236,11 +242,45 @@ class HipRenderBackend(HipBackend):
             dd = self._upload("depth", [np.asarray(d, np.uint16).view(np.int16) for d in depths[:n]], (H, W), torch.int16, cap)
             if source is not None:
                 sd = self._upload("sbs", source["frames"], tuple(source["frames"][0].shape), torch.uint8, cap)
+                if source.get("match") is not None:
+                    self._match_colour(sd, fd, source["match"])
                 nat.render_stereo_source_batch(fd, dd, gain_left, gain_right, conv, layout, sd, source["fill_eyes"], *source["q"],
                                                out=od[:n], subpixel=subpixel)
             else:
                 render_stereo(nat, fd, dd, gain_left, gain_right, conv, layout, od[:n], subpixel)
             return od[:n] if png else self._fetch(od[:n])
+
+    def _match_colour(self, sd, fd, match):
+        """the right eye of the staged SBS frames sd [n,Hs,Ws,3] through the clip's table, or through the tables of these frames'
+        own left eyes against the staged 4K frames fd"""
+        torch, nat = self.torch, self.native
+        _, Hs, Ws, _ = sd.shape
+        table = match["table"]
+        if match["mode"] == "frame":
+            table = nat.colour_lut_batch(nat.bgr_hist_batch(sd, match["eye_rect"]), nat.bgr_hist_batch(fd, match["frame_rect"]), 1)
+        elif not isinstance(table, torch.Tensor):              # the NumPy surface hands the table over as an array
+            table = torch.from_numpy(np.ascontiguousarray(table, np.uint8).reshape(3, 256)).to(self.device)
+        nat.bgr_lut_batch(sd, table, (Ws // 2, 0, Ws, Hs), out=sd)
+
+    def colour_probe(self, sbs_frames, frames, eye_rect, frame_rect):
+        """--match-colour clip, before the render loop: probe pairs -> (left-eye histograms, 4K histograms), int32 [n,3,256] each on
+        the device.  Uses the render loop's staging, so it waits for its launches before it returns"""
+        torch, nat = self.torch, self.native
+        with torch.cuda.device(self.device):
+            cap = max(len(frames), CONVERT_BATCH)              # the staging the render loop is about to use
+            sd = self._upload("sbs", sbs_frames, tuple(sbs_frames[0].shape), torch.uint8, cap)
+            fd = self._upload("frames", frames, tuple(frames[0].shape), torch.uint8, cap)
+            pair = nat.bgr_hist_batch(sd, eye_rect), nat.bgr_hist_batch(fd, frame_rect)
+            self._synchronize()
+        return pair
+
+    def colour_table(self, hists):
+        """the probe passes' histograms -> (the one table of all of them, u8 [1,3,256] on the device, its NumPy copy [3,256])"""
+        torch, nat = self.torch, self.native
+        with torch.cuda.device(self.device):
+            hs, hd = (torch.cat([h[k] for h in hists]) for k in (0, 1))
+            table = nat.colour_lut_batch(hs, hd, hs.shape[0])
+            return table, np.array(self._fetch(table)[0])
 
     def render_batch_png(self, frames, depths, gain_left, gain_right, conv, layout, capacity=None, subpixel=False, source=None):
         """--png-encoder gpu: render_batch whose frames stay on the device and come back as the zlib streams of their PNGs"""
@@ -256,17 +296,33 @@ class StereoPlan:
     parallax: "source" takes the parallax from the depth run's depth_range block (resolve_source) and ignores max_shift /
     convergence / eye_split, parallax_gain scales it;
     fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
-    of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from"""
+    of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from;
+    match_colour: "clip" or "frame" fits the SBS clip's colours to the 4K frame's before the fill (colour.py; needs
+    fill_from_source: it corrects the eye the fill samples, and nothing else reads it), match_probes: the clip mode's probe pairs"""
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", subpixel: bool = False, parallax: str = "invented",
-                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0):
+                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
+                 match_probes: int = None):
         if parallax not in PARALLAX:
             raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
         if fill_from_source is not None and parallax != "source":
             raise ValueError("--fill-from-source needs --parallax source: the holes of an invented parallax do not line up with the real eye")
         if isinstance(source_start_frame, bool) or not isinstance(source_start_frame, (int, np.integer)) or source_start_frame < 0:
             raise ValueError(f"--source-start-frame must be an integer >= 0, got {source_start_frame!r}")
+        if match_colour is None and match_probes is not None:
+            raise ValueError("--match-probes needs --match-colour clip: it counts the frame pairs the clip's one table is fitted to")
+        if match_colour is not None:
+            from .colour import DEFAULT_PROBES, check_parameters
+            if fill_from_source is None:
+                raise ValueError("--match-colour needs --fill-from-source: it corrects the colours of the SBS clip's right eye, which "
+                                 "only the source fill reads")
+            if match_colour != "clip" and match_probes is not None:
+                raise ValueError("--match-probes needs --match-colour clip: frame mode fits every batch to its own frames")
+            check_parameters(match_colour, DEFAULT_PROBES if match_probes is None else match_probes)
+            match_probes = DEFAULT_PROBES if match_probes is None else int(match_probes)
+        self.match_colour, self.match_probes = match_colour, match_probes
+        self.matcher = None                          # the ColourMatcher of a run (process_conversion)
         self.parallax, self.parallax_gain = parallax, parallax_gain
         self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
         self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout, subpixel)
@@ -311,8 +367,10 @@ class StereoPlan:
         Hs, Ws = sbs_frames[0].shape[:2]
         if Ws % 2:
             raise ValueError(f"the SBS frames of --fill-from-source are {Ws} wide: not two eyes side by side")
-        return {"source": dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE,
-                               q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))}
+        source = dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE, q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))
+        if self.matcher is not None:
+            source["match"] = self.matcher.source_entry()
+        return {"source": source}
 
     def encoder(self, gpu_png: bool):
         """the writer pool's encoder of a rendered frame: the wrapper of a device-deflated stream, or zlib on the writer threads"""
@@ -337,14 +395,15 @@ class DepthTo3DConverter:
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
                  batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False, parallax: str = "invented",
-                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0):
+                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
+                 match_probes: int = None):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
         png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
         every other keyword is StereoPlan's (parallax="source": set_source_parallax, or process_conversion from the depth manifest)"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
         self.plan = StereoPlan(max_shift, convergence, eye_split, layout, subpixel, parallax, parallax_gain, fill_from_source,
-                               source_start_frame)
+                               source_start_frame, match_colour, match_probes)
         if backend is None:
             require_hip_device(device)
             backend = HipRenderBackend(device)
@@ -363,9 +422,10 @@ class DepthTo3DConverter:
     def source_kwargs(self, sbs_frames, frame_size):
         return self.plan.source_kwargs(sbs_frames, frame_size)
 
-    def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray, source: np.ndarray = None) -> np.ndarray:
+    def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray, source: np.ndarray = None, colour_table: np.ndarray = None) -> np.ndarray:
         """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous).  source: the SBS BGR
-        frame the depth was made from; the right eye's disocclusions are sampled from its stored right eye (parallax="source" only)"""
+        frame the depth was made from; the right eye's disocclusions are sampled from its stored right eye (parallax="source" only);
+        colour_table: u8 [3,256] (BGR), applied to that eye first, as --match-colour clip applies its table"""
         frame_bgr, depth_u16 = np.asarray(frame_bgr), np.asarray(depth_u16)
         if frame_bgr.shape[:2] != depth_u16.shape or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
             raise ValueError(f"frame {frame_bgr.shape} and depth {depth_u16.shape} disagree")
@@ -373,7 +433,14 @@ class DepthTo3DConverter:
             raise ValueError("parallax='source': call set_source_parallax(depth_range, frame width) first")
         if source is not None and self.parallax != "source":
             raise ValueError("source= needs parallax='source'")
+        if colour_table is not None and source is None:
+            raise ValueError("colour_table= needs source=: it is applied to the SBS frame's right eye")
         src = self.source_kwargs(None if source is None else [np.asarray(source, np.uint8)], frame_bgr.shape[1::-1])
+        if colour_table is not None:
+            table = np.asarray(colour_table)
+            if table.dtype != np.uint8 or table.shape != (3, 256):
+                raise ValueError(f"colour_table must be uint8 [3,256], got {table.dtype} {table.shape}")
+            src["source"]["match"] = dict(mode="clip", table=table, eye_rect=None, frame_rect=None)
         return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
                                                   **self.plan.render_kwargs(), **src)[0])
 
@@ -392,7 +459,8 @@ class DepthTo3DConverter:
         W, H, fps = info['width'], info['height'], info['fps']
         if output_path is None:
             # _subpx: a run with --subpixel never reuses a file rendered without it
-            tag = ("_subpx" if self.subpixel else "") + ("_srcpx" if self.parallax == "source" else "") + ("_srcfill" if self.fill_from_source else "")
+            tag = ("_subpx" if self.subpixel else "") + ("_srcpx" if self.parallax == "source" else "") + ("_srcfill" if self.fill_from_source else "") + \
+                  {None: "", "clip": "_cm", "frame": "_cmf"}[plan.match_colour]
             output_path = f"3d_{self.params['layout']}{tag}_{Path(depth_path).with_suffix('').name}.mp4"
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
@@ -412,10 +480,20 @@ class DepthTo3DConverter:
                 raise ValueError(f"Could not read video info: {self.fill_from_source}")
             self.params.update(fill_from_source=str(self.fill_from_source), source_start_frame=self.source_start_frame)
         n = len(depth_files) if max_frames is None else min(len(depth_files), max(int(max_frames), 0))
+        frames_dir = sibling_frames_dir(output_path)
+        if plan.match_colour is not None:                       # every rank: the same probes, the same table
+            from .colour import ColourMatcher
+            src_info = get_video_info(self.fill_from_source)
+            plan.matcher = ColourMatcher(self.backend, plan.match_colour, plan.match_probes).prepare(
+                self.fill_from_source, self.source_start_frame, video_4k_path, max(int(guide_start_frame), 0), n,
+                (src_info['width'] // 2, src_info['height']), (W, H), plan.spatial_map)
+            self.params.update(plan.matcher.manifest_entries())
+            if plan.match_colour == "clip":
+                self.params["colour_lut"] = str(frames_dir / "colour_lut.json")
+                print(f"Colour match: one table from {len(plan.matcher.probe_frames)} frame pairs")
 
         rank, world = sharding.rank_world()
         sharding.require_initialized(world)
-        frames_dir = sibling_frames_dir(output_path)
         frames_dir.mkdir(parents=True, exist_ok=True)
         g0 = max(int(guide_start_frame), 0)
         mine = list(range(rank, n, world))                       # frame i -> rank i mod world; both inputs decoded per rank
@@ -472,6 +550,8 @@ class DepthTo3DConverter:
             raise ValueError("No frames rendered")
         sharding.barrier()
         if rank == 0:
+            if plan.matcher is not None and plan.matcher.lut_record() is not None:
+                (frames_dir / "colour_lut.json").write_text(json.dumps(plan.matcher.lut_record()))
             plan.finish(frames_dir, output_path, total, fps)
         sharding.barrier()
         print(f"✓ 3D video saved: {output_path}")
@@ -496,6 +576,15 @@ def main(argv=None, backend=None):
                              '(the clip the depth was computed from) instead of stretching the background into them')
     parser.add_argument('--source-start-frame', type=int, default=0, metavar='N',
                         help='the SBS frame that depth frame 0 was made from (default 0)')
+    parser.add_argument('--match-colour', choices=['clip', 'frame'], default=None,
+                        help="with --fill-from-source: fit the SBS clip's colours to the 4K frame's before its right eye fills the holes "
+                             "(the two are different releases: grading, tone mapping and black level differ, and an unmatched fill "
+                             "shows as a patch along every depth edge).  clip: one transfer curve per channel for the whole run, from "
+                             "--match-probes frame pairs; cannot flicker.  frame: every frame is fitted on its own, for clips whose "
+                             "difference changes from scene to scene; the filled regions can flicker.  Default: off")
+    parser.add_argument('--match-probes', type=int, default=None, metavar='P',
+                        help='with --match-colour clip: frame pairs, spread over the frames to render, that the table is fitted to '
+                             '(1 .. 64, default 16)')
     from .align import add_guide_arguments, resolve_guide_start
     add_guide_arguments(parser, 'depth frame 0', 'the offset the upscale CLI used')
     args = parser.parse_args(argv)
@@ -507,7 +596,8 @@ def main(argv=None, backend=None):
         source = {"fill_from_source": args.fill_from_source, "source_start_frame": args.source_start_frame} if args.fill_from_source else {}
         if args.source_start_frame and not args.fill_from_source:
             raise ValueError("--source-start-frame needs --fill-from-source")
-        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source)
+        match = {k: v for k, v in (("match_colour", args.match_colour), ("match_probes", args.match_probes)) if v is not None}
+        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source, **match)
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)
