@@ -34,8 +34,8 @@ static void lanczos4_taps_host(float x, short* taps)
 
 __device__ __forceinline__ int gray_of(int b, int g, int r) { return (r * 9798 + g * 19235 + b * 3735 + (1 << 14)) >> 15; }
 
-// one thread = one output pixel of one eye; a block covers 256 output pixels of one row.  The source span
-// (128 + 8 BGR pixels when unsqueezing, 256 otherwise) is staged through LDS with coalesced dword loads:
+// Without unsqueeze one thread = one output pixel of one eye; a block covers 256 output pixels of one row.  The source span
+// (256 + 8 BGR pixels when unsqueezing, 256 otherwise) is staged through LDS with coalesced dword loads:
 // per-tap byte loads at a 3-byte stride straight from HBM ran at 0.3 TB/s.
 // GRAY: write luma only; else write the BGR triple.
 #ifndef SBS_ROWS
@@ -43,8 +43,45 @@ __device__ __forceinline__ int gray_of(int b, int g, int r) { return (r * 9798 +
 #endif
 //    // rows per workgroup: the per-row work is tiny, one workgroup per row was bound by dispatch
 // Unsqueezing, a thread computes the output PAIR (2m, 2m+1): the two 8-tap windows (source pixels m-4..m+3 with the
-// frac-0.75 taps, m-3..m+4 with the frac-0.25 taps) overlap in 7 of 8 pixels, so 27 LDS bytes serve both instead of
-// 48; a block covers 512 output pixels of one eye row.  Without unsqueeze a thread copies one pixel (256 per block).
+// frac-0.75 taps, m-3..m+4 with the frac-0.25 taps) overlap in 7 of 8 pixels; a block covers 512 output pixels of one eye row.
+//  - The 27 bytes of the 9 pixels come out of LDS as the 8 aligned dwords that cover them, shifted into place with
+//    v_alignbit_b32 by the lane's byte phase.  The dwords reach at most 7 bytes past the staged span: inside sRow, and no
+//    selector below names those bytes.
+//  - One v_perm_b32 makes the int16 pair (pixel k, pixel k+1) of a channel; the 8-tap sum of an output is four
+//    v_dot2_i32_i16 of such pairs with the packed taps, the first accumulating onto the rounding constant.  Pixels are 0..255
+//    and the taps int16, so the i32 sum is exact: the same integer as eight multiply-adds.
+//  - The pair leaves as 16-bit words where the plane starts on an even address (W is even: then every row and every pair does).
+// (Two pairs per thread, 2m .. 2m+3 from 10 pixels, share the pairs (1,2) .. (7,8) between outputs 2m+1 and 2m+2 and store
+//  dwords: 73 instead of 86 vector instructions per pair, but a row then needs 128 lanes.  With the waves taking rows in
+//  turn it measured 2 % slower than one pair per thread -- DESIGN.md, "k_split_sbs: packed dot products".)
+
+// the bytes of {hi, lo} that sel names, as v_perm_b32 does for the selectors used here: 0..3 a byte of lo, 4..7 a byte of hi,
+// 0x0c the constant 0.  (The host definitions serve the builds of this file that have no device pass.)
+__device__ __forceinline__ uint32_t split_perm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t v = (uint64_t)hi << 32 | lo;
+    uint32_t r = 0;
+    for (int i = 0; i < 4; i++) {
+        const uint32_t b = (sel >> (8 * i)) & 255u;
+        if (b < 8) r |= ((uint32_t)(v >> (8 * b)) & 255u) << (8 * i);
+    }
+    return r;
+#endif
+}
+// acc + a.lo * b.lo + a.hi * b.hi on int16 halves, no saturation (v_dot2_i32_i16)
+__device__ __forceinline__ int split_dot2(uint32_t a, uint32_t b, int acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short split_s2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(split_s2, a), __builtin_bit_cast(split_s2, b), acc, false);
+#else
+    return acc + (int)(int16_t)(a & 0xFFFFu) * (int)(int16_t)(b & 0xFFFFu) + (int)(int16_t)(a >> 16) * (int)(int16_t)(b >> 16);
+#endif
+}
+
 template <bool GRAY>
 __global__ __launch_bounds__(256) void k_split_sbs(const uint8_t* __restrict__ sbs, int W, int H, int pitch, int unsqueeze,
                                                    LanczosTaps taps, uint8_t* __restrict__ outL, uint8_t* __restrict__ outR,
@@ -64,9 +101,16 @@ __global__ __launch_bounds__(256) void k_split_sbs(const uint8_t* __restrict__ s
     const int s0 = unsqueeze ? (xb >> 1) - 4 : xb;
     const int ns = unsqueeze ? 256 + 8 : 256;
     const bool interior = s0 >= 0 && (s0 + ns < hw || (eye == 0 && s0 + ns <= hw));
-    int tp0[8], tp1[8];
+    uint32_t tpk[2][4];                                             // taps (2i, 2i+1) of either phase as one int16 pair
 #pragma unroll
-    for (int k = 0; k < 8; k++) { tp0[k] = taps.t[0][k]; tp1[k] = taps.t[1][k]; }
+    for (int i = 0; i < 4; i++) {
+        tpk[0][i] = (uint32_t)(uint16_t)taps.t[0][2 * i] | (uint32_t)(uint16_t)taps.t[0][2 * i + 1] << 16;
+        tpk[1][i] = (uint32_t)(uint16_t)taps.t[1][2 * i] | (uint32_t)(uint16_t)taps.t[1][2 * i + 1] << 16;
+    }
+    // an unsqueezed pair leaves as 16-bit words when the plane starts on an even address and its rows are even: then every row
+    // starts on one, and every pair (x is even) with it; bytes otherwise
+    constexpr int CH = GRAY ? 1 : 3;
+    const bool wide = ((reinterpret_cast<uintptr_t>(out) | (uintptr_t)ow) & 1) == 0;
 
     // Staging plan of this thread, the same for every row of the band: interior blocks copy ONE aligned dword of the
     // span (the <= 3 bytes of over-read stay inside the image row); edge blocks copy up to four bytes from clamped
@@ -111,24 +155,47 @@ __global__ __launch_bounds__(256) void k_split_sbs(const uint8_t* __restrict__ s
             // source phase: fx = (x + 0.5) * 0.5 - 0.5 -> even x = 2m: sx = m - 1, frac 0.75; odd x = 2m + 1: sx = m, frac 0.25
             const int x = xb + 2 * t;                               // even member of the pair; m = x / 2 = s0 + 4 + t
             if (x >= ow) continue;
-            const uint8_t* p0 = sR + soff + t * 3;                  // pixel m - 4
-            int acc[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } };
+            constexpr int NW = 7;                                   // the window, pixels m-4 .. m+4, is 27 bytes: 7 dwords once shifted
+            const int b0 = soff + 3 * t;                            // byte of pixel m - 4, <= 768: the 8 dwords end at byte 799 or below
+            const uint32_t* dw = reinterpret_cast<const uint32_t*>(sR + (b0 & ~3));
+            const uint32_t sh = (uint32_t)(b0 & 3) * 8;
+            uint32_t d[NW + 1], w[NW];
 #pragma unroll
-            for (int k = 0; k < 9; k++) {
-                const int b = p0[3 * k], g = p0[3 * k + 1], r = p0[3 * k + 2];
-                if (k < 8) { acc[0][0] += b * tp0[k]; acc[0][1] += g * tp0[k]; acc[0][2] += r * tp0[k]; }
-                if (k > 0) { acc[1][0] += b * tp1[k - 1]; acc[1][1] += g * tp1[k - 1]; acc[1][2] += r * tp1[k - 1]; }
-            }
+            for (int i = 0; i <= NW; i++) d[i] = dw[i];
+#pragma unroll
+            for (int i = 0; i < NW; i++) w[i] = alignbit(d[i + 1], d[i], sh);
+            uint32_t pr[8][3];                                      // [k][c]: channel c of window pixels (k, k+1), bytes 3k+c and 3k+3+c
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const int j = 3 * k + c, a = j >> 2;            // a + 1 <= 6: byte 3k+3+c <= 26
+                    pr[k][c] = split_perm(w[a + 1], w[a], 0x0c000c00u | (uint32_t)(j - 4 * a) | (uint32_t)(j + 3 - 4 * a) << 16);
+                }
+            uint32_t ob[2 * CH];                                    // the pair's output bytes in order
 #pragma unroll
             for (int n = 0; n < 2; n++) {
-                if (x + n >= ow) break;
-                // vertical pass is the identity tap (2048): (a * 2048 + 2^21) >> 22 == (a + 2^10) >> 11 exactly (floor
-                // of the same rational), so the descale stays in 32 bits; saturate to u8
-                const int b = min(max((acc[n][0] + 1024) >> 11, 0), 255);
-                const int g = min(max((acc[n][1] + 1024) >> 11, 0), 255);
-                const int r = min(max((acc[n][2] + 1024) >> 11, 0), 255);
-                if (GRAY) out[(size_t)y * ow + x + n] = (uint8_t)gray_of(b, g, r);
-                else { uint8_t* o = out + ((size_t)y * ow + x + n) * 3; o[0] = (uint8_t)b; o[1] = (uint8_t)g; o[2] = (uint8_t)r; }
+                int v[3];
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    // vertical pass is the identity tap (2048): (a * 2048 + 2^21) >> 22 == (a + 2^10) >> 11 exactly (floor
+                    // of the same rational), so the descale stays in 32 bits; saturate to u8
+                    int acc = 1024;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) acc = split_dot2(pr[n + 2 * i][c], tpk[n][i], acc);
+                    v[c] = min(max(acc >> 11, 0), 255);
+                }
+#pragma unroll
+                for (int c = 0; c < CH; c++) ob[n * CH + c] = (uint32_t)(GRAY ? gray_of(v[0], v[1], v[2]) : v[c]);
+            }
+            uint8_t* o = out + ((size_t)y * ow + x) * CH;
+            if (wide) {                                             // uniform; ow and x are even: both outputs exist
+#pragma unroll
+                for (int u = 0; u < CH; u++) reinterpret_cast<uint16_t*>(o)[u] = (uint16_t)(ob[2 * u] | ob[2 * u + 1] << 8);
+            } else {
+                const int nb = min(2, ow - x) * CH;
+#pragma unroll
+                for (int i = 0; i < 2 * CH; i++) if (i < nb) o[i] = (uint8_t)ob[i];
             }
         } else {
             const int x = xb + t;
