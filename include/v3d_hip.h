@@ -708,6 +708,29 @@ int v3d_bgr_lut_batch(const uint8_t* src, size_t src_stride /* bytes */, int n, 
                       int x0, int y0, int x1, int y1, const uint8_t* lut, int lut_stride /* bytes; 0: one table */,
                       uint8_t* dst, size_t dst_stride /* bytes */, int dst_pitch, void* stream);
 
+/* Source-verified eye (v3d_verify.hip): a rendered eye checked, cell by cell and IN PLACE, against the stored eye of the SBS frame
+   (the convert CLI's --verify-source, right after v3d_render_stereo_source_batch).  No call site in the reference.  Bit-exact
+   contract, all integers: tests/verify_ref.py.
+   Frame f's eye image E at eye_bgr + f*eye_stride (bytes), H rows `eye_pitch` bytes apart, W BGR pixels each: the right eye of a
+   full-SBS output is base + 3W with pitch 6W, that of a full top-bottom output base + 3WH with pitch 3W.  The SBS frames, the map
+   and P = P(eye)[y][t] are those of v3d_render_stereo_source_batch above: the same u, v, clamps, fx, fy and rounding.
+   Cells: cx = (65536 + ax - 1) / ax by cy = (65536 + ay - 1) / ay targets (the targets one stored sample spans; 1 .. 16 each).
+   Cell (p, r) holds the targets [p cx, min((p+1) cx, W)) x [r cy, min((r+1) cy, H)), npix of them.  Per cell and channel c:
+     A_c = sum E, B_c = sum P over the cell;   m = |A_0 - B_0| + |A_1 - B_1| + |A_2 - B_2|;   replaced iff m > tau * npix.
+   Every target of a replaced cell takes P; every other byte of E stays.  replaced[f] = the number of replaced cells of frame f,
+   OVERWRITTEN (zeroing it is part of the entry: it may hold anything).  Sums are at most 255 * 256: int32 throughout.
+   Memory contract: E is read at its rows' payload bytes only (3W per row) and written at the bytes of replaced cells only; the
+   SBS rows are read at the payload bytes of the sampled eye's half only; neither needs any alignment.  No value outside a cell's
+   own targets reaches its decision.  Two launches, no allocation, no synchronisation.
+   V3D_ERR_ARG: null pointer; n, W or H < 1; eye_pitch < 3W; eye_stride < H*eye_pitch with n > 1; Ws odd or < 2; Hs < 1;
+   pitch < 3 Ws; sbs_stride < Hs*pitch with n > 1; eye not 0 or 1; ax or ay outside [2^12, 2^20]; |bx| or |by| above 2^40; tau
+   outside [0, 765] (765 = 3 * 255 can never be passed: nothing is replaced).  V3D_ERR_UNSUPPORTED: W > 8192 or Ws/2 > 8192, looked
+   at after every V3D_ERR_ARG.  A refused call enqueues nothing. */
+int v3d_verify_eye_source_batch(uint8_t* eye_bgr, size_t eye_stride /* bytes */, int eye_pitch /* bytes */, int n, int W, int H,
+                                const uint8_t* sbs_bgr, size_t sbs_stride /* bytes */, int Ws, int Hs, int pitch, int eye /* 0 | 1 */,
+                                int64_t ax, int64_t bx, int64_t ay, int64_t by, int tau,
+                                uint32_t* replaced /* [n], overwritten */, void* stream);
+
 const char* v3d_last_error(void);
 const char* v3d_version(void);
 

@@ -122,6 +122,7 @@ SIGNATURES = {
     "v3d_bgr_hist_batch": (ci, [vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
     "v3d_colour_lut_batch": (ci, [vp, vp, ci, ci, vp, vp]),
     "v3d_bgr_lut_batch": (ci, [vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, sz, ci, vp]),
+    "v3d_verify_eye_source_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64, ci, vp, vp]),
     "v3d_last_error": (cs, []),
     "v3d_version": (cs, []),
 }
@@ -1151,6 +1152,31 @@ def bgr_lut_batch(src, lut, rect=None, out=None):
     q, qs, _, _, _, qpitch = _bgr_frames(out, "out")
     _call("v3d_bgr_lut_batch", src.device, p, fs, n, W, H, pitch, x0, y0, x1, y1, _dev(lut, torch.uint8, "lut"),
           768 if lut.dim() == 3 and lut.shape[0] == n and n > 1 else 0, q, qs, qpitch)
+    return out
+
+
+def verify_cell(ax, ay):
+    """(cx, cy): the cell of targets that one stored-eye sample spans under the Q16 map scales ax, ay (ceil(65536 / a), 1 .. 16)"""
+    return (65536 + int(ax) - 1) // int(ax), (65536 + int(ay) - 1) // int(ay)
+
+
+def verify_eye_source_batch(eye_bgr, sbs, eye, ax, bx, ay, by, tau, out=None):
+    """a rendered eye checked IN PLACE against the stored eye `eye` (0 | 1) of the SBS frames (v3d_verify_eye_source_batch):
+    eye_bgr u8 [n,H,W,3] on the device, usually a view of a packed output (the right half of a full-SBS frame, the lower half of a
+    full top-bottom one: the row pitch and the frame stride may differ), sbs u8 [n,Hs,Ws,3] as for render_stereo_source_batch.  A
+    cell of verify_cell(ax, ay) targets whose channel sums differ from the sampled stored eye's by more than tau per pixel takes
+    the sample.  -> int32 [n] (the bits of uint32 counts): replaced cells per frame.  Bit-exact contract: tests/verify_ref.py."""
+    p, fs, n, W, H, pitch = _bgr_frames(eye_bgr, "eye_bgr")
+    sp, ss, ns, Ws, Hs, spitch = _bgr_frames(sbs, "sbs")
+    if ns != n:
+        raise NativeError(f"sbs holds {ns} frames, eye_bgr {n}")
+    if eye not in (0, 1) or isinstance(eye, bool):
+        raise ValueError(f"eye must be 0 (left) or 1 (right), got {eye!r}")
+    if isinstance(tau, bool) or not isinstance(tau, (int, np.integer)) or not 0 <= tau <= 765:
+        raise ValueError(f"tau must be an integer in [0, 765], got {tau!r}")
+    out = _out(out, (n,), torch.int32, eye_bgr.device)
+    _call("v3d_verify_eye_source_batch", eye_bgr.device, p, fs, pitch, n, W, H, sp, ss, Ws, Hs, spitch, int(eye), int(ax), int(bx),
+          int(ay), int(by), int(tau), _dev(out, torch.int32, "out"))
     return out
 
 

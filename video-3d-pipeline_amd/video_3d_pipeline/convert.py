@@ -21,6 +21,10 @@ eye's target of a pixel is x - round(K s d): the left eye is the 4K frame, the r
 (v3d_render_stereo_source_batch; contract: tests/stereo_source_ref.py) instead of stretching the background into them.
 --match-colour clip|frame first fits that eye's colours to the 4K frame's (colour.py: the SBS clip is another release, with another
 grading; per-channel histogram matching left eye -> 4K frame, applied to the right eye on the device; contract: tests/colour_ref.py).
+--verify-source [TAU] then checks the rendered right eye against that stored eye, cell by cell (a cell: the targets one stored sample
+spans), and replaces the cells whose mean colour is off by more than TAU with the stored eye's own samples: where the matcher's
+disparity was wrong the warp shows wrong picture content, and the film's right eye says so (v3d_verify_eye_source_batch; contract:
+tests/verify_ref.py).  Only for the layouts in which the right eye lies unpacked in the output: full-sbs and full-tb.
 
 Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
 cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
@@ -43,6 +47,11 @@ LAYOUTS = {"full-sbs": 0, "half-sbs": 1, "full-tb": 2, "half-tb": 3, "interlaced
 DEFAULT_MAX_SHIFT, DEFAULT_CONVERGENCE, DEFAULT_EYE_SPLIT = 48.0, 0.5, 0.5
 PARALLAX = ("invented", "source")
 FILL_RIGHT_EYE = 2                  # --fill-from-source: fill_eyes of v3d_render_stereo_source_batch (the left eye has gain 0, no holes)
+# --verify-source: the threshold's default and range (mean absolute difference of a cell's channel sums per pixel, the three channels
+# added: 0 .. 765).  48 is a convention exposed as a flag, like the matcher's min_score: not a film measurement
+DEFAULT_VERIFY_TAU, VERIFY_TAU_MAX = 48, 765
+VERIFY_LAYOUTS = ("full-sbs", "full-tb")       # the packings in which the right eye lies unpacked in the output
+VERIFY_WARN_SHARE = 0.25
 # frames per launch: 4 x (25 MB BGR + 17 MB depth) of pinned input staging and 4 x 50 MB of pinned output (full SBS at 4K)
 CONVERT_BATCH = 4
 
@@ -135,6 +144,27 @@ def fill_map_q16(spatial_map, eye_size, frame_size):
     return q
 
 
+def check_verify_source(tau, layout, fill_from_source, clip: bool = True):
+    """--verify-source TAU against the flags it depends on -> tau as an int; ValueError otherwise.  clip: a run over clips, which
+    needs the SBS clip's path (the NumPy surface is handed the SBS frame with every call, and fill_from_source is then its
+    parallax="source")"""
+    if isinstance(tau, bool) or not isinstance(tau, (int, np.integer)) or not 0 <= tau <= VERIFY_TAU_MAX:
+        raise ValueError(f"--verify-source takes an integer threshold in [0, {VERIFY_TAU_MAX}], got {tau!r}")
+    if not fill_from_source:
+        raise ValueError("--verify-source needs " + ("--fill-from-source" if clip else "parallax='source' (--parallax source "
+                         "--fill-from-source)") + ": it checks the rendered right eye against the SBS clip's stored right eye, which "
+                         "only the source fill uploads")
+    if layout not in VERIFY_LAYOUTS:
+        raise ValueError(f"--verify-source works on the layouts {', '.join(VERIFY_LAYOUTS)}, in which the right eye lies unpacked in "
+                         f"the output; {layout} squeezes, interleaves or mixes it")
+    return int(tau)
+
+
+def right_eye_view(out, layout, W, H):
+    """the right eye [n,H,W,3] of packed full-sbs / full-tb frames [n,outH,outW,3] as a view (NumPy array or tensor alike)"""
+    return out[:, :, W:] if layout == LAYOUTS["full-sbs"] else out[:, H:]
+
+
 def depth_manifest(depth_path):
     """the JSON manifest of a 4K depth run at depth_path, or {} (a directory, a video, anything else)"""
     p = Path(depth_path)
@@ -191,6 +221,8 @@ def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, 
         man.update(fill_from_source=params["fill_from_source"], source_start_frame=params.get("source_start_frame", 0))
     if params.get("match_colour"):
         man.update({k: params[k] for k in ("match_colour", "colour_probe_frames", "colour_lut") if k in params})
+    if params.get("verify_source"):
+        man["verify_source"] = params["verify_source"]
     finish_sequence(frames_dir, "frame_%06d.png", output_path, fps, man)
 
 
@@ -230,7 +262,10 @@ class HipRenderBackend(HipBackend):
         source (--fill-from-source): dict(frames: the SBS BGR frames [Hs,Ws,3] of this batch, fill_eyes, q: (ax, bx, ay, by)) -- the
         render is v3d_render_stereo_source_batch, one launch all the same.  With a `match` entry (--match-colour: ColourMatcher.
         source_entry) the right-eye half of the uploaded SBS frames is colour-matched in place before that launch: with the clip's
-        table, or with one table per frame fitted to this batch (two histograms, the tables, the apply); nothing synchronises"""
+        table, or with one table per frame fitted to this batch (two histograms, the tables, the apply); nothing synchronises.
+        With a `verify` entry (--verify-source: dict(tau)) the right eye of the staged output is checked in place against the
+        (colour-matched) stored right eye right after the render, v3d_verify_eye_source_batch with the render's own map; its
+        counters start their way to pinned memory before the frames' copy and are read after it (verify_counts)"""
         torch, nat = self.torch, self.native
         n = len(frames)
         H, W = depths[0].shape
@@ -246,9 +281,20 @@ class HipRenderBackend(HipBackend):
                     self._match_colour(sd, fd, source["match"])
                 nat.render_stereo_source_batch(fd, dd, gain_left, gain_right, conv, layout, sd, source["fill_eyes"], *source["q"],
                                                out=od[:n], subpixel=subpixel)
+                if source.get("verify") is not None:
+                    counts = self._staging("verify_dev", (cap,), torch.int32, False)
+                    nat.verify_eye_source_batch(right_eye_view(od[:n], layout, W, H), sd, 1, *source["q"], source["verify"]["tau"],
+                                                out=counts[:n])
+                    self._verify = self._fetch_async([counts[:n]])
             else:
                 render_stereo(nat, fd, dd, gain_left, gain_right, conv, layout, od[:n], subpixel)
             return od[:n] if png else self._fetch(od[:n])
+
+    def verify_counts(self):
+        """--verify-source: the replaced cells per frame of the last render_batch (uint32 [n]) once its frames are on the host, or
+        None when that call verified nothing.  The copy was enqueued before the frames' own, whose wait covered it"""
+        handle, self._verify = getattr(self, "_verify", None), None
+        return None if handle is None else self._read(handle)[0].view(np.uint32)
 
     def _match_colour(self, sd, fd, match):
         """the right eye of the staged SBS frames sd [n,Hs,Ws,3] through the clip's table, or through the tables of these frames'
@@ -298,12 +344,14 @@ class StereoPlan:
     fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
     of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from;
     match_colour: "clip" or "frame" fits the SBS clip's colours to the 4K frame's before the fill (colour.py; needs
-    fill_from_source: it corrects the eye the fill samples, and nothing else reads it), match_probes: the clip mode's probe pairs"""
+    fill_from_source: it corrects the eye the fill samples, and nothing else reads it), match_probes: the clip mode's probe pairs;
+    verify_source: the threshold tau of the source-verified right eye, or None (needs fill_from_source and a layout of
+    VERIFY_LAYOUTS): the render calls' source entry gains verify=dict(tau), and note_verify adds up what the backend counted"""
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", subpixel: bool = False, parallax: str = "invented",
                  parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
-                 match_probes: int = None):
+                 match_probes: int = None, verify_source: int = None):
         if parallax not in PARALLAX:
             raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
         if fill_from_source is not None and parallax != "source":
@@ -322,6 +370,8 @@ class StereoPlan:
             check_parameters(match_colour, DEFAULT_PROBES if match_probes is None else match_probes)
             match_probes = DEFAULT_PROBES if match_probes is None else int(match_probes)
         self.match_colour, self.match_probes = match_colour, match_probes
+        self.verify_source = None if verify_source is None else check_verify_source(verify_source, layout, parallax == "source", False)
+        self.verify_shares = []                      # replaced cells / cells of every verified frame this process rendered
         self.matcher = None                          # the ColourMatcher of a run (process_conversion)
         self.parallax, self.parallax_gain = parallax, parallax_gain
         self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
@@ -370,7 +420,27 @@ class StereoPlan:
         source = dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE, q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))
         if self.matcher is not None:
             source["match"] = self.matcher.source_entry()
+        if self.verify_source is not None:
+            source["verify"] = dict(tau=self.verify_source)
         return {"source": source}
+
+    def note_verify(self, backend, source, frame_size):
+        """after a render call with a verify entry: the backend's replaced cells per frame -> shares of the frame's cells"""
+        from ._native import verify_cell
+        counts = backend.verify_counts()
+        if counts is None:
+            raise RuntimeError("--verify-source: the backend rendered without verifying")
+        cx, cy = verify_cell(source["q"][0], source["q"][2])
+        cells = -(-frame_size[0] // cx) * -(-frame_size[1] // cy)
+        self.verify_cell = (cx, cy)
+        self.verify_shares += [int(c) / cells for c in counts]
+
+    def verify_record(self, world: int = 1):
+        """the manifest's verify_source block; the shares are this process's own, so null under torchrun"""
+        alone = world == 1 and bool(self.verify_shares)
+        return {"tau": self.verify_source, "cell": list(getattr(self, "verify_cell", (None, None))),
+                "replaced_share": float(np.mean(self.verify_shares)) if alone else None,
+                "replaced_share_max": float(np.max(self.verify_shares)) if alone else None}
 
     def encoder(self, gpu_png: bool):
         """the writer pool's encoder of a rendered frame: the wrapper of a device-deflated stream, or zlib on the writer threads"""
@@ -396,14 +466,14 @@ class DepthTo3DConverter:
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
                  batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False, parallax: str = "invented",
                  parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
-                 match_probes: int = None):
+                 match_probes: int = None, verify_source: int = None):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
         png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
         every other keyword is StereoPlan's (parallax="source": set_source_parallax, or process_conversion from the depth manifest)"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
         self.plan = StereoPlan(max_shift, convergence, eye_split, layout, subpixel, parallax, parallax_gain, fill_from_source,
-                               source_start_frame, match_colour, match_probes)
+                               source_start_frame, match_colour, match_probes, verify_source)
         if backend is None:
             require_hip_device(device)
             backend = HipRenderBackend(device)
@@ -425,7 +495,8 @@ class DepthTo3DConverter:
     def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray, source: np.ndarray = None, colour_table: np.ndarray = None) -> np.ndarray:
         """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous).  source: the SBS BGR
         frame the depth was made from; the right eye's disocclusions are sampled from its stored right eye (parallax="source" only);
-        colour_table: u8 [3,256] (BGR), applied to that eye first, as --match-colour clip applies its table"""
+        colour_table: u8 [3,256] (BGR), applied to that eye first, as --match-colour clip applies its table.  With verify_source
+        set and a source given, the right eye is verified against that stored eye as --verify-source does"""
         frame_bgr, depth_u16 = np.asarray(frame_bgr), np.asarray(depth_u16)
         if frame_bgr.shape[:2] != depth_u16.shape or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
             raise ValueError(f"frame {frame_bgr.shape} and depth {depth_u16.shape} disagree")
@@ -441,8 +512,11 @@ class DepthTo3DConverter:
             if table.dtype != np.uint8 or table.shape != (3, 256):
                 raise ValueError(f"colour_table must be uint8 [3,256], got {table.dtype} {table.shape}")
             src["source"]["match"] = dict(mode="clip", table=table, eye_rect=None, frame_rect=None)
-        return np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
-                                                  **self.plan.render_kwargs(), **src)[0])
+        out = np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
+                                                 **self.plan.render_kwargs(), **src)[0])
+        if src and "verify" in src["source"]:
+            self.plan.note_verify(self.backend, src["source"], frame_bgr.shape[1::-1])
+        return out
 
     def process_conversion(self, video_4k_path: str, depth_path: str, output_path: str = None, force_reprocess: bool = False,
                            guide_start_frame: int = 0, max_frames: int = None) -> str:
@@ -460,7 +534,7 @@ class DepthTo3DConverter:
         if output_path is None:
             # _subpx: a run with --subpixel never reuses a file rendered without it
             tag = ("_subpx" if self.subpixel else "") + ("_srcpx" if self.parallax == "source" else "") + ("_srcfill" if self.fill_from_source else "") + \
-                  {None: "", "clip": "_cm", "frame": "_cmf"}[plan.match_colour]
+                  {None: "", "clip": "_cm", "frame": "_cmf"}[plan.match_colour] + ("" if plan.verify_source is None else f"_vs{plan.verify_source}")
             output_path = f"3d_{self.params['layout']}{tag}_{Path(depth_path).with_suffix('').name}.mp4"
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
@@ -475,6 +549,8 @@ class DepthTo3DConverter:
                                  f"{man['input_layout']}): the fill samples the stored right eye at column We + i of a side-by-side "
                                  f"frame, and a top-bottom clip keeps that eye in rows, not columns.  --parallax source alone works "
                                  f"for both layouts")
+        if plan.verify_source is not None:
+            check_verify_source(plan.verify_source, self.params["layout"], self.fill_from_source)
         if self.fill_from_source is not None:
             if not get_video_info(self.fill_from_source):
                 raise ValueError(f"Could not read video info: {self.fill_from_source}")
@@ -511,8 +587,10 @@ class DepthTo3DConverter:
                 return
             # --png-encoder gpu: deflated on the device, only the streams cross PCIe
             render = self.backend.render_batch_png if gpu_png else self.backend.render_batch
-            out = render(batch_f, batch_d, *plan.gains, plan.layout_code, capacity=self.batch_size, **plan.render_kwargs(),
-                         **plan.source_kwargs(batch_s if sbs_frames is not None else None, (W, H)))
+            src = plan.source_kwargs(batch_s if sbs_frames is not None else None, (W, H))
+            out = render(batch_f, batch_d, *plan.gains, plan.layout_code, capacity=self.batch_size, **plan.render_kwargs(), **src)
+            if plan.verify_source is not None:
+                plan.note_verify(self.backend, src["source"], (W, H))
             for j, i in enumerate(batch_i):
                 writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)
             rendered += len(batch_i)
@@ -549,6 +627,15 @@ class DepthTo3DConverter:
         if total == 0:
             raise ValueError("No frames rendered")
         sharding.barrier()
+        if plan.verify_source is not None:
+            self.params["verify_source"] = rec = plan.verify_record(world)
+            if rec["replaced_share"] is not None:
+                print(f"Source verify: tau {rec['tau']}, cells of {rec['cell'][0]} x {rec['cell'][1]} pixels: "
+                      f"{rec['replaced_share']:.2%} of the right eye's cells replaced on average, {rec['replaced_share_max']:.2%} at most")
+                if rec["replaced_share"] > VERIFY_WARN_SHARE:
+                    print(f"Warning: --verify-source replaced {rec['replaced_share']:.0%} of the right eye: the SBS clip disagrees with "
+                          f"the render almost everywhere, as another grading or another framing makes it.  Try --match-colour, or a "
+                          f"depth run whose map came from `align --register-spatial`")
         if rank == 0:
             if plan.matcher is not None and plan.matcher.lut_record() is not None:
                 (frames_dir / "colour_lut.json").write_text(json.dumps(plan.matcher.lut_record()))
@@ -585,6 +672,12 @@ def main(argv=None, backend=None):
     parser.add_argument('--match-probes', type=int, default=None, metavar='P',
                         help='with --match-colour clip: frame pairs, spread over the frames to render, that the table is fitted to '
                              '(1 .. 64, default 16)')
+    parser.add_argument('--verify-source', type=int, nargs='?', const=DEFAULT_VERIFY_TAU, default=None, metavar='TAU',
+                        help="with --fill-from-source and --layout full-sbs or full-tb: check the rendered right eye against the SBS "
+                             "clip's stored right eye, cell by cell (the 4K pixels one stored sample spans), and take the stored eye's "
+                             "samples where a cell's mean colour differs by more than TAU (sum over the three channels, 0 .. "
+                             f"{VERIFY_TAU_MAX}; default {DEFAULT_VERIFY_TAU}): a wrong disparity warps wrong picture content into "
+                             "place, and the film's own right eye shows it.  Default: off")
     from .align import add_guide_arguments, resolve_guide_start
     add_guide_arguments(parser, 'depth frame 0', 'the offset the upscale CLI used')
     args = parser.parse_args(argv)
@@ -597,7 +690,9 @@ def main(argv=None, backend=None):
         if args.source_start_frame and not args.fill_from_source:
             raise ValueError("--source-start-frame needs --fill-from-source")
         match = {k: v for k, v in (("match_colour", args.match_colour), ("match_probes", args.match_probes)) if v is not None}
-        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source, **match)
+        verify = {} if args.verify_source is None else {"verify_source": check_verify_source(args.verify_source, args.layout, args.fill_from_source)}
+        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source, **match,
+                                  **verify)
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)
