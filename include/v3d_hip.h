@@ -731,6 +731,38 @@ int v3d_verify_eye_source_batch(uint8_t* eye_bgr, size_t eye_stride /* bytes */,
                                 int64_t ax, int64_t bx, int64_t ay, int64_t by, int tau,
                                 uint32_t* replaced /* [n], overwritten */, void* stream);
 
+/* Rendered-eye fidelity (v3d_fidelity.hip): a rendered eye MEASURED against the stored eye of the SBS frame (the convert CLI's
+   --fidelity-report).  No call site in the reference.  Bit-exact contract, all integers: tests/fidelity_ref.py.
+   The eye image E, the SBS frames, the map and P = P(eye)[y][t] are exactly those of v3d_verify_eye_source_batch above: the same
+   u, v, clamps, fx, fy and rounding, the same addressing of an eye inside a full-SBS or full top-bottom output.  Both images are
+   read only.
+   Cells as in the verify entry: cx = (65536 + ax - 1) / ax by cy = (65536 + ay - 1) / ay targets, ncx = ceil(W / cx) by
+   ncy = ceil(H / cy) of them, ragged last cells of npix targets.  Per cell and channel c (0 = B): A_c = sum E, B_c = sum P,
+     a_c = (2 A_c + npix) / (2 npix),  b_c = (2 B_c + npix) / (2 npix)        (the cell means, u8; / floors).
+   Colour record over all cells: n_cells = ncx ncy;  sad = sum_cells sum_c |a_c - b_c|;  ssd = sum sum (a_c - b_c)^2;
+     n_bad = #{cells: sum_c |a_c - b_c| > bad_thr}.
+   Luma of a cell: Ya = (9798 a_2 + 19235 a_1 + 3735 a_0 + 16384) >> 15, Yb likewise from b.
+   SSIM (the x264 / ffmpeg form) over windows of 8 x 8 cells at stride 4: window (i, j) covers the cells [4i, 4i+8) x [4j, 4j+8)
+   for every i, j with 4i + 8 <= ncx and 4j + 8 <= ncy (n_win of them, possibly 0).  Per window
+     s1 = sum Ya, s2 = sum Yb, ss = sum (Ya^2 + Yb^2), s12 = sum Ya Yb;  vars = 64 ss - s1^2 - s2^2;  covar = 64 s12 - s1 s2;
+     C1 = 416, C2 = 235963;  A = 2 s1 s2 + C1, B = s1^2 + s2^2 + C1, C = 2 covar + C2, D = vars + C2   (A <= B, |C| <= D, all
+     below 2^31);  q1 = floor(A 2^20 / B), q2 = floor(|C| 2^20 / D);  Q = sign(C) ((q1 q2) >> 20), in [-2^20, 2^20].
+   out row of frame f, int64 [V3D_FIDELITY_FIELDS]: n_cells, sad, ssd, n_bad, n_win, ssim_q20 = sum Q; OVERWRITTEN.  A frame's
+   record does not depend on n, on its place in the batch, on pitches or on strides.
+   Memory contract: E is read at its rows' payload bytes only (3W per row), the SBS rows at the payload bytes of the sampled eye's
+   half only; neither needs any alignment.  ws: device scratch of v3d_eye_fidelity_ws_bytes, 16-byte aligned, any content on
+   entry; out: 8-byte aligned.  Nothing outside out and ws is written.  At most three launches, no allocation, no synchronisation,
+   no atomics on global memory (per-workgroup partial sums in ws and a reducing launch).
+   V3D_ERR_ARG and V3D_ERR_UNSUPPORTED: exactly those of v3d_verify_eye_source_batch, with bad_thr in [0, 765] in place of tau;
+   also V3D_ERR_ARG for a null or misaligned ws or out.  _ws_bytes returns 0 for arguments the entry refuses.  A refused call
+   enqueues nothing. */
+#define V3D_FIDELITY_FIELDS 6
+size_t v3d_eye_fidelity_ws_bytes(int n, int W, int H, int64_t ax, int64_t ay);
+int v3d_eye_fidelity_batch(const uint8_t* eye_bgr, size_t eye_stride /* bytes */, int eye_pitch /* bytes */, int n, int W, int H,
+                           const uint8_t* sbs_bgr, size_t sbs_stride /* bytes */, int Ws, int Hs, int pitch, int eye /* 0 | 1 */,
+                           int64_t ax, int64_t bx, int64_t ay, int64_t by, int bad_thr,
+                           int64_t* out /* [n][V3D_FIDELITY_FIELDS] */, void* ws, void* stream);
+
 const char* v3d_last_error(void);
 const char* v3d_version(void);
 

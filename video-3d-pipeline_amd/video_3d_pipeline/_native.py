@@ -123,6 +123,8 @@ SIGNATURES = {
     "v3d_colour_lut_batch": (ci, [vp, vp, ci, ci, vp, vp]),
     "v3d_bgr_lut_batch": (ci, [vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, sz, ci, vp]),
     "v3d_verify_eye_source_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64, ci, vp, vp]),
+    "v3d_eye_fidelity_ws_bytes": (sz, [ci, ci, ci, i64, i64]),
+    "v3d_eye_fidelity_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64, ci, vp, vp, vp]),
     "v3d_last_error": (cs, []),
     "v3d_version": (cs, []),
 }
@@ -1177,6 +1179,48 @@ def verify_eye_source_batch(eye_bgr, sbs, eye, ax, bx, ay, by, tau, out=None):
     out = _out(out, (n,), torch.int32, eye_bgr.device)
     _call("v3d_verify_eye_source_batch", eye_bgr.device, p, fs, pitch, n, W, H, sp, ss, Ws, Hs, spitch, int(eye), int(ax), int(bx),
           int(ay), int(by), int(tau), _dev(out, torch.int32, "out"))
+    return out
+
+
+FIDELITY_FIELDS = 6                                # V3D_FIDELITY_FIELDS: n_cells, sad, ssd, n_bad, n_win, ssim_q20
+FIDELITY_BAD_MAX = 765
+
+
+def fidelity_grid(W, H, ax, ay):
+    """(ncx, ncy, n_win) of v3d_eye_fidelity_batch: the cells of verify_cell(ax, ay) targets over W x H, and the 8 x 8-cell windows
+    at stride 4 that fit into them"""
+    cx, cy = verify_cell(ax, ay)
+    ncx, ncy = -(-int(W) // cx), -(-int(H) // cy)
+    nwx, nwy = ((ncx - 8) // 4 + 1 if ncx >= 8 else 0), ((ncy - 8) // 4 + 1 if ncy >= 8 else 0)
+    return ncx, ncy, nwx * nwy
+
+
+def eye_fidelity_batch(eye_bgr, sbs, eye, ax, bx, ay, by, bad_thr, out=None, ws=None):
+    """a rendered eye measured against the stored eye `eye` (0 | 1) of the SBS frames (v3d_eye_fidelity_batch): eye_bgr u8
+    [n,H,W,3] on the device, usually a view of a packed output, and sbs u8 [n,Hs,Ws,3], both as for verify_eye_source_batch and
+    both read only -> int64 [n,6]: n_cells, sad, ssd, n_bad of the cell means (cells of verify_cell(ax, ay) targets; n_bad: those
+    whose three channel differences add up to more than bad_thr) and n_win, ssim_q20 of the cells' luma (8 x 8-cell windows at
+    stride 4, the sum of their SSIM in Q20).  out / ws: a caller's buffers; None takes them from the caching allocator.
+    Bit-exact contract: tests/fidelity_ref.py."""
+    p, fs, n, W, H, pitch = _bgr_frames(eye_bgr, "eye_bgr")
+    sp, ss, ns, Ws, Hs, spitch = _bgr_frames(sbs, "sbs")
+    if ns != n:
+        raise NativeError(f"sbs holds {ns} frames, eye_bgr {n}")
+    if eye not in (0, 1) or isinstance(eye, bool):
+        raise ValueError(f"eye must be 0 (left) or 1 (right), got {eye!r}")
+    if isinstance(bad_thr, bool) or not isinstance(bad_thr, (int, np.integer)) or not 0 <= bad_thr <= FIDELITY_BAD_MAX:
+        raise ValueError(f"bad_thr must be an integer in [0, {FIDELITY_BAD_MAX}], got {bad_thr!r}")
+    need = lib().v3d_eye_fidelity_ws_bytes(n, W, H, int(ax), int(ay))
+    if not need:
+        raise NativeError(f"eye_fidelity_batch: {n} eyes of {W}x{H} under the scales ({ax}, {ay}) outside the entry's range "
+                          f"(W <= 8192, scales in [2^12, 2^20])")
+    out = _out(out, (n, FIDELITY_FIELDS), torch.int64, eye_bgr.device)
+    if ws is None:
+        ws = _scratch(need, eye_bgr.device)
+    elif ws.numel() < need:
+        raise NativeError(f"ws: {ws.numel()} bytes, eye_fidelity_batch needs {need}")
+    _call("v3d_eye_fidelity_batch", eye_bgr.device, p, fs, pitch, n, W, H, sp, ss, Ws, Hs, spitch, int(eye), int(ax), int(bx),
+          int(ay), int(by), int(bad_thr), _dev(out, torch.int64, "out"), _dev(ws, torch.uint8, "ws"))
     return out
 
 

@@ -25,6 +25,9 @@ grading; per-channel histogram matching left eye -> 4K frame, applied to the rig
 spans), and replaces the cells whose mean colour is off by more than TAU with the stored eye's own samples: where the matcher's
 disparity was wrong the warp shows wrong picture content, and the film's right eye says so (v3d_verify_eye_source_batch; contract:
 tests/verify_ref.py).  Only for the layouts in which the right eye lies unpacked in the output: full-sbs and full-tb.
+--fidelity-report [PATH] measures what came of it (fidelity.py): per frame, error sums and SSIM of the right eye before the fill
+(rendered once more into scratch), of the right eye as written and of the left eye, each against the SBS frame's stored eye
+(v3d_eye_fidelity_batch; contract: tests/fidelity_ref.py).  No output byte and no cache key changes.
 
 Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
 cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
@@ -165,6 +168,11 @@ def right_eye_view(out, layout, W, H):
     return out[:, :, W:] if layout == LAYOUTS["full-sbs"] else out[:, H:]
 
 
+def left_eye_view(out, layout, W, H):
+    """the left eye of the same frames"""
+    return out[:, :, :W] if layout == LAYOUTS["full-sbs"] else out[:, :H]
+
+
 def depth_manifest(depth_path):
     """the JSON manifest of a 4K depth run at depth_path, or {} (a directory, a video, anything else)"""
     p = Path(depth_path)
@@ -223,6 +231,8 @@ def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, 
         man.update({k: params[k] for k in ("match_colour", "colour_probe_frames", "colour_lut") if k in params})
     if params.get("verify_source"):
         man["verify_source"] = params["verify_source"]
+    if params.get("fidelity_report"):
+        man["fidelity_report"] = params["fidelity_report"]
     finish_sequence(frames_dir, "frame_%06d.png", output_path, fps, man)
 
 
@@ -265,7 +275,12 @@ class HipRenderBackend(HipBackend):
         table, or with one table per frame fitted to this batch (two histograms, the tables, the apply); nothing synchronises.
         With a `verify` entry (--verify-source: dict(tau)) the right eye of the staged output is checked in place against the
         (colour-matched) stored right eye right after the render, v3d_verify_eye_source_batch with the render's own map; its
-        counters start their way to pinned memory before the frames' copy and are read after it (verify_counts)"""
+        counters start their way to pinned memory before the frames' copy and are read after it (verify_counts).
+        With a `fidelity` entry (--fidelity-report: dict(bad_thr, ceiling)) the frames are rendered once more with fill_eyes 0 into
+        a scratch output of this backend, and v3d_eye_fidelity_batch measures that right eye, the right eye of the staged output
+        and, with `ceiling`, its left eye against the stored eyes; the staged output is only read.  With `ceiling` and a `match`
+        entry the colour table goes over the whole SBS frame, after the histograms: the render and the verification read the
+        right half alone.  The records travel as the counters do (fidelity_handle)"""
         torch, nat = self.torch, self.native
         n = len(frames)
         H, W = depths[0].shape
@@ -277,8 +292,9 @@ class HipRenderBackend(HipBackend):
             dd = self._upload("depth", [np.asarray(d, np.uint16).view(np.int16) for d in depths[:n]], (H, W), torch.int16, cap)
             if source is not None:
                 sd = self._upload("sbs", source["frames"], tuple(source["frames"][0].shape), torch.uint8, cap)
+                fid = source.get("fidelity")
                 if source.get("match") is not None:
-                    self._match_colour(sd, fd, source["match"])
+                    self._match_colour(sd, fd, source["match"], whole=fid is not None and fid["ceiling"])
                 nat.render_stereo_source_batch(fd, dd, gain_left, gain_right, conv, layout, sd, source["fill_eyes"], *source["q"],
                                                out=od[:n], subpixel=subpixel)
                 if source.get("verify") is not None:
@@ -286,6 +302,9 @@ class HipRenderBackend(HipBackend):
                     nat.verify_eye_source_batch(right_eye_view(od[:n], layout, W, H), sd, 1, *source["q"], source["verify"]["tau"],
                                                 out=counts[:n])
                     self._verify = self._fetch_async([counts[:n]])
+                if fid is not None:
+                    self._fidelity = self._measure_fidelity(fd, dd, sd, od[:n], (gain_left, gain_right, conv), layout, subpixel,
+                                                            source["q"], fid, cap)
             else:
                 render_stereo(nat, fd, dd, gain_left, gain_right, conv, layout, od[:n], subpixel)
             return od[:n] if png else self._fetch(od[:n])
@@ -296,9 +315,33 @@ class HipRenderBackend(HipBackend):
         handle, self._verify = getattr(self, "_verify", None), None
         return None if handle is None else self._read(handle)[0].view(np.uint32)
 
-    def _match_colour(self, sd, fd, match):
+    def _measure_fidelity(self, fd, dd, sd, od, gains, layout, subpixel, q, fid, cap):
+        """--fidelity-report: the warp series from a render with fill_eyes 0 into the scratch output, the final series from the
+        right eye of od, the ceiling series from its left eye -> the handle of their records ([n,6] each) on the way to the host"""
+        torch, nat = self.torch, self.native
+        n, H, W = dd.shape
+        scratch = self._staging("fidelity_out_dev", (cap,) + tuple(od.shape[1:]), torch.uint8, False)
+        rec = self._staging("fidelity_dev", (3, cap, nat.FIDELITY_FIELDS), torch.int64, False)
+        nat.render_stereo_source_batch(fd, dd, *gains, layout, sd, 0, *q, out=scratch[:n], subpixel=subpixel)
+        nat.eye_fidelity_batch(right_eye_view(scratch[:n], layout, W, H), sd, 1, *q, fid["bad_thr"], out=rec[0, :n])
+        nat.eye_fidelity_batch(right_eye_view(od, layout, W, H), sd, 1, *q, fid["bad_thr"], out=rec[1, :n])
+        if fid["ceiling"]:
+            nat.eye_fidelity_batch(left_eye_view(od, layout, W, H), sd, 0, *q, fid["bad_thr"], out=rec[2, :n])
+        return self._fetch_async([rec[k, :n] for k in range(3 if fid["ceiling"] else 2)])
+
+    def fidelity_handle(self):
+        """--fidelity-report: the records of the last render_batch as a handle for read_fidelity, or None when that call measured
+        nothing.  Their copies were enqueued before the frames' own"""
+        handle, self._fidelity = getattr(self, "_fidelity", None), None
+        return handle
+
+    def read_fidelity(self, handle, wait: bool = True):
+        """-> [warp, final(, ceiling)] int64 [n,6] each, or None while the copies run and wait is False"""
+        return self._read(handle, wait)
+
+    def _match_colour(self, sd, fd, match, whole=False):
         """the right eye of the staged SBS frames sd [n,Hs,Ws,3] through the clip's table, or through the tables of these frames'
-        own left eyes against the staged 4K frames fd"""
+        own left eyes against the staged 4K frames fd.  whole: the table goes over both eyes (after the histograms were taken)"""
         torch, nat = self.torch, self.native
         _, Hs, Ws, _ = sd.shape
         table = match["table"]
@@ -306,7 +349,7 @@ class HipRenderBackend(HipBackend):
             table = nat.colour_lut_batch(nat.bgr_hist_batch(sd, match["eye_rect"]), nat.bgr_hist_batch(fd, match["frame_rect"]), 1)
         elif not isinstance(table, torch.Tensor):              # the NumPy surface hands the table over as an array
             table = torch.from_numpy(np.ascontiguousarray(table, np.uint8).reshape(3, 256)).to(self.device)
-        nat.bgr_lut_batch(sd, table, (Ws // 2, 0, Ws, Hs), out=sd)
+        nat.bgr_lut_batch(sd, table, (0 if whole else Ws // 2, 0, Ws, Hs), out=sd)
 
     def colour_probe(self, sbs_frames, frames, eye_rect, frame_rect):
         """--match-colour clip, before the render loop: probe pairs -> (left-eye histograms, 4K histograms), int32 [n,3,256] each on
@@ -346,12 +389,14 @@ class StereoPlan:
     match_colour: "clip" or "frame" fits the SBS clip's colours to the 4K frame's before the fill (colour.py; needs
     fill_from_source: it corrects the eye the fill samples, and nothing else reads it), match_probes: the clip mode's probe pairs;
     verify_source: the threshold tau of the source-verified right eye, or None (needs fill_from_source and a layout of
-    VERIFY_LAYOUTS): the render calls' source entry gains verify=dict(tau), and note_verify adds up what the backend counted"""
+    VERIFY_LAYOUTS): the render calls' source entry gains verify=dict(tau), and note_verify adds up what the backend counted;
+    fidelity_report: None, True (the report goes next to the manifest) or its path (fidelity.py; the same needs): process_conversion
+    sets up a FidelityMonitor as self.fidelity, and the render calls' source entry gains its request"""
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", subpixel: bool = False, parallax: str = "invented",
                  parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
-                 match_probes: int = None, verify_source: int = None):
+                 match_probes: int = None, verify_source: int = None, fidelity_report=None):
         if parallax not in PARALLAX:
             raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
         if fill_from_source is not None and parallax != "source":
@@ -372,6 +417,11 @@ class StereoPlan:
         self.match_colour, self.match_probes = match_colour, match_probes
         self.verify_source = None if verify_source is None else check_verify_source(verify_source, layout, parallax == "source", False)
         self.verify_shares = []                      # replaced cells / cells of every verified frame this process rendered
+        if fidelity_report is not None and fidelity_report is not False:
+            from .fidelity import check_fidelity_report
+            check_fidelity_report(layout, parallax == "source", False)
+        self.fidelity_report = None if fidelity_report is None or fidelity_report is False else fidelity_report
+        self.fidelity = None                         # the FidelityMonitor of a run (process_conversion)
         self.matcher = None                          # the ColourMatcher of a run (process_conversion)
         self.parallax, self.parallax_gain = parallax, parallax_gain
         self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
@@ -422,6 +472,8 @@ class StereoPlan:
             source["match"] = self.matcher.source_entry()
         if self.verify_source is not None:
             source["verify"] = dict(tau=self.verify_source)
+        if self.fidelity is not None:
+            source["fidelity"] = self.fidelity.request()
         return {"source": source}
 
     def note_verify(self, backend, source, frame_size):
@@ -466,14 +518,14 @@ class DepthTo3DConverter:
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
                  batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False, parallax: str = "invented",
                  parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
-                 match_probes: int = None, verify_source: int = None):
+                 match_probes: int = None, verify_source: int = None, fidelity_report=None):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
         png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
         every other keyword is StereoPlan's (parallax="source": set_source_parallax, or process_conversion from the depth manifest)"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
         self.plan = StereoPlan(max_shift, convergence, eye_split, layout, subpixel, parallax, parallax_gain, fill_from_source,
-                               source_start_frame, match_colour, match_probes, verify_source)
+                               source_start_frame, match_colour, match_probes, verify_source, fidelity_report)
         if backend is None:
             require_hip_device(device)
             backend = HipRenderBackend(device)
@@ -539,6 +591,9 @@ class DepthTo3DConverter:
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
             print(f"✓ Using existing 3D video: {output_path}")
+            if plan.fidelity_report is not None:
+                from .fidelity import CACHED_NOTE
+                print(CACHED_NOTE)
             return str(output_path)
         plan.check_frame(W, H)
         if self.parallax == "source":                           # the film's parallax: from the depth run's own record
@@ -551,6 +606,10 @@ class DepthTo3DConverter:
                                  f"for both layouts")
         if plan.verify_source is not None:
             check_verify_source(plan.verify_source, self.params["layout"], self.fill_from_source)
+        if plan.fidelity_report is not None:
+            from .fidelity import FidelityMonitor, check_fidelity_report
+            check_fidelity_report(self.params["layout"], self.fill_from_source)
+            plan.fidelity = FidelityMonitor(self.backend, ceiling=plan.gains[0] == 0)
         if self.fill_from_source is not None:
             if not get_video_info(self.fill_from_source):
                 raise ValueError(f"Could not read video info: {self.fill_from_source}")
@@ -591,6 +650,8 @@ class DepthTo3DConverter:
             out = render(batch_f, batch_d, *plan.gains, plan.layout_code, capacity=self.batch_size, **plan.render_kwargs(), **src)
             if plan.verify_source is not None:
                 plan.note_verify(self.backend, src["source"], (W, H))
+            if plan.fidelity is not None:
+                plan.fidelity.note(batch_i, (W, H), src["source"]["q"])
             for j, i in enumerate(batch_i):
                 writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)
             rendered += len(batch_i)
@@ -636,6 +697,13 @@ class DepthTo3DConverter:
                     print(f"Warning: --verify-source replaced {rec['replaced_share']:.0%} of the right eye: the SBS clip disagrees with "
                           f"the render almost everywhere, as another grading or another framing makes it.  Try --match-colour, or a "
                           f"depth run whose map came from `align --register-spatial`")
+        if plan.fidelity is not None:
+            fid_path = output_path.with_name(output_path.with_suffix("").name + "_fidelity.json") if plan.fidelity_report is True \
+                else Path(plan.fidelity_report)
+            self.params["fidelity_report"] = plan.fidelity.finish(fid_path, world)
+            plan.fidelity.report()
+            if rank == 0 and plan.fidelity.data is not None:
+                plan.fidelity.write(fid_path)
         if rank == 0:
             if plan.matcher is not None and plan.matcher.lut_record() is not None:
                 (frames_dir / "colour_lut.json").write_text(json.dumps(plan.matcher.lut_record()))
@@ -678,6 +746,11 @@ def main(argv=None, backend=None):
                              "samples where a cell's mean colour differs by more than TAU (sum over the three channels, 0 .. "
                              f"{VERIFY_TAU_MAX}; default {DEFAULT_VERIFY_TAU}): a wrong disparity warps wrong picture content into "
                              "place, and the film's own right eye shows it.  Default: off")
+    parser.add_argument('--fidelity-report', nargs='?', const=True, default=None, metavar='PATH',
+                        help="with --fill-from-source and --layout full-sbs or full-tb: measure the rendered eyes against the SBS clip's "
+                             "stored eyes on the GPU -- error sums and SSIM of the right eye before the fill (depth + DIBR alone), of the "
+                             "right eye as written, and of the left eye (how far the two releases differ) -- print a summary and write "
+                             "<output>_fidelity.json next to the manifest (or to PATH).  No output changes")
     from .align import add_guide_arguments, resolve_guide_start
     add_guide_arguments(parser, 'depth frame 0', 'the offset the upscale CLI used')
     args = parser.parse_args(argv)
@@ -691,8 +764,13 @@ def main(argv=None, backend=None):
             raise ValueError("--source-start-frame needs --fill-from-source")
         match = {k: v for k, v in (("match_colour", args.match_colour), ("match_probes", args.match_probes)) if v is not None}
         verify = {} if args.verify_source is None else {"verify_source": check_verify_source(args.verify_source, args.layout, args.fill_from_source)}
+        fidelity = {}
+        if args.fidelity_report is not None:
+            from .fidelity import check_fidelity_report
+            check_fidelity_report(args.layout, args.fill_from_source)
+            fidelity = {"fidelity_report": args.fidelity_report}
         conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source, **match,
-                                  **verify)
+                                  **verify, **fidelity)
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)
