@@ -7,6 +7,7 @@ import contextlib
 import json
 import math
 import types
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -195,11 +196,11 @@ def test_a_rendered_left_eye_has_no_ceiling(run, capsys):
     """left gain != 0 cannot come from --parallax source today; the monitor is told so directly"""
     from video_3d_pipeline.fidelity import CEILING_REASON, FidelityMonitor
     be = FidelityRenderBackend()
-    m = FidelityMonitor(be, ceiling=False)
+    m = FidelityMonitor(ceiling=False)
     assert m.request() == {"bad_thr": BAD, "ceiling": False}
     be._handle = [np.array([[64, 1, 1, 0, 1, 1 << 19]], np.int64), np.array([[64, 0, 0, 0, 1, 1 << 20]], np.int64)]
-    m.note([3], (16, 16), (32768, 0, 32768, 0))
-    entry = m.finish("x.json")
+    m.note(be, [3], (16, 16), (32768, 0, 32768, 0))
+    entry = m.finish(Path("x.json"), None, 1)[0]["fidelity_report"]
     assert entry["summary"]["ceiling"] is None and entry["ceiling_reason"] == CEILING_REASON and m.data["series"]["ceiling"] is None
     assert m.data["frames"] == [{"frame": 3, "warp": dict(n_cells=64, sad=1, ssd=1, n_bad=0, n_win=1, ssim_q20=1 << 19, mean_abs=1 / 192,
                                                           psnr=pytest.approx(10 * math.log10(65025 * 192)), bad_share=0.0, ssim=0.5),
@@ -208,7 +209,7 @@ def test_a_rendered_left_eye_has_no_ceiling(run, capsys):
     m.report()
     assert "ceiling: not measured" in capsys.readouterr().out
     with pytest.raises(RuntimeError, match="without measuring"):
-        m.note([4], (16, 16), (32768, 0, 32768, 0))
+        m.note(be, [4], (16, 16), (32768, 0, 32768, 0))
 
 
 def test_no_cache_suffix_and_nothing_changes_without_the_flag(run, monkeypatch):
@@ -228,10 +229,10 @@ def test_no_cache_suffix_and_nothing_changes_without_the_flag(run, monkeypatch):
 def test_a_sharded_run_has_a_null_summary(capsys):
     from video_3d_pipeline.fidelity import SHARDED_REASON, FidelityMonitor
     be = FidelityRenderBackend()
-    m = FidelityMonitor(be)
+    m = FidelityMonitor()
     be._handle = [np.zeros((1, 6), np.int64)] * 3
-    m.note([0], (16, 16), (32768, 0, 32768, 0))
-    assert m.finish("x.json", world=2) == {"path": None, "summary": None, "reason": SHARDED_REASON} and m.data is None
+    m.note(be, [0], (16, 16), (32768, 0, 32768, 0))
+    assert m.finish(Path("x.json"), None, 2) == ({"fidelity_report": {"path": None, "summary": None, "reason": SHARDED_REASON}}, {}) and m.data is None
     m.report()
     assert "not made" in capsys.readouterr().out
 

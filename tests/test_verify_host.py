@@ -175,7 +175,7 @@ def test_numpy_surface(run):
         want, n = V.verify(ER, sbs_frames[0], 1, *_q(), 40)
         assert np.array_equal(got, P.pack(EL, want, code)) and n > 0 and be.verified == [{"tau": 40}]
         cx, cy = V.cell(_q()[0], _q()[2])
-        assert conv.plan.verify_shares == [n / (-(-W4 // cx) * -(-H4 // cy))]
+        assert conv.plan.steps[0].shares == [n / (-(-W4 // cx) * -(-H4 // cy))]
         # without a source frame there is nothing to verify against: the plain render, no verify entry, nothing counted
         assert np.array_equal(conv.render_frame(frames4k[0], d), P.render(frames4k[0], d, *conv.gains, code))
         assert be.verified == [{"tau": 40}, None] and be.asked == 1

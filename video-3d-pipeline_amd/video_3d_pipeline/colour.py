@@ -11,9 +11,12 @@ no depth and no render.  Bit-exact contract: tests/colour_ref.py.
     frame  every render batch fits one table per frame to its own frames: for clips whose grading difference changes from scene to
            scene; neighbouring frames get slightly different tables, which can show as flicker in the filled regions
 """
+import json
 from fractions import Fraction
 
 import numpy as np
+
+from .verify import SourceStep
 
 MODES = ("clip", "frame")
 DEFAULT_PROBES = 16
@@ -57,24 +60,25 @@ def common_rects(spatial_map, eye_size, frame_size):
     return eye, frame
 
 
-class ColourMatcher:
-    """backend: a render backend with colour_probe(sbs_frames, frames, eye_rect, frame_rect) -> histograms and
-    colour_table(list of them) -> (the table where the render wants it, its NumPy copy u8 [3,256])"""
+class ColourMatcher(SourceStep):
+    """--match-colour of the convert CLI.  The backend supplies colour_probe(sbs_frames, frames, eye_rect, frame_rect) -> histograms
+    and colour_table(list of them) -> (the table where the render wants it, its NumPy copy u8 [3,256])"""
+    key = "match"
 
-    def __init__(self, backend, mode: str, probes: int = DEFAULT_PROBES):
+    def __init__(self, mode: str, probes: int = DEFAULT_PROBES):
         check_parameters(mode, probes)
-        self.backend, self.mode, self.probes = backend, mode, int(probes)
+        self.mode, self.probes, self.output_tag = mode, int(probes), {"clip": "_cm", "frame": "_cmf"}[mode]
         self.eye_rect = self.frame_rect = self.table = self.table_np = None
         self.probe_frames = []
 
-    def prepare(self, sbs_path, source_start: int, video_path, guide_start: int, count: int, eye_size, frame_size, spatial_map=None):
-        """before the render loop: the two rectangles; in clip mode the probe pass and the table.  Depth frame i pairs SBS frame
-        source_start + i with 4K frame guide_start + i, and `count` frames will be rendered"""
+    def prepare(self, backend, plan, video_path, guide_start, count, frame_size):
+        """the two rectangles; in clip mode the probe pass and the table (depth frame i: SBS frame source_start_frame + i, 4K frame guide_start + i)"""
         from .framematch import probe_starts
-        from .utils import iter_frames
-        self.eye_rect, self.frame_rect = common_rects(spatial_map, eye_size, frame_size)
+        from .utils import get_video_info, iter_frames
+        sbs_path, source_start, src_info = plan.fill_from_source, plan.source_start_frame, get_video_info(plan.fill_from_source)
+        self.eye_rect, self.frame_rect = common_rects(plan.spatial_map, (src_info['width'] // 2, src_info['height']), frame_size)
         if self.mode != "clip":
-            return self
+            return
         self.probe_frames, _ = probe_starts(int(count), 1, self.probes)
         hists = []
         for k in range(0, len(self.probe_frames), PROBE_BATCH):
@@ -83,23 +87,22 @@ class ColourMatcher:
             v4k = [next(iter_frames(video_path, guide_start + i, 1), None) for i in idx]
             if any(f is None for f in sbs + v4k):
                 raise ValueError(f"--match-colour: a probe frame among {idx} could not be read from {sbs_path} / {video_path}")
-            hists.append(self.backend.colour_probe(sbs, v4k, self.eye_rect, self.frame_rect))
-        self.table, self.table_np = self.backend.colour_table(hists)
-        return self
+            hists.append(backend.colour_probe(sbs, v4k, self.eye_rect, self.frame_rect))
+        self.table, self.table_np = backend.colour_table(hists)
+        print(f"Colour match: one table from {len(self.probe_frames)} frame pairs")
 
-    def source_entry(self):
-        """what the render call's source dict carries: the mode, the clip table (None in frame mode) and the two rectangles"""
+    def request(self):
+        """the mode, the clip table (None in frame mode) and the two rectangles"""
         return dict(mode=self.mode, table=self.table, eye_rect=self.eye_rect, frame_rect=self.frame_rect)
 
-    def manifest_entries(self):
-        man = {"match_colour": self.mode}
-        if self.mode == "clip":
-            man["colour_probe_frames"] = [int(i) for i in self.probe_frames]
-        return man
+    def note(self, backend, indices, frame_size, q):
+        """the render applied the table: nothing comes back"""
 
-    def lut_record(self):
-        """the content of colour_lut.json (clip mode), or None"""
-        if self.table_np is None:
-            return None
-        return {"channels": "BGR", "eye_rect": list(self.eye_rect), "frame_rect": list(self.frame_rect),
-                "probe_frames": [int(i) for i in self.probe_frames], "lut": np.asarray(self.table_np).reshape(3, 256).astype(int).tolist()}
+    def finish(self, output_path, frames_dir, world):
+        """clip mode: the probe frames and colour_lut.json"""
+        if self.mode != "clip":
+            return {"match_colour": self.mode}, {}
+        probes, path = [int(i) for i in self.probe_frames], frames_dir / "colour_lut.json"
+        lut = {"channels": "BGR", "eye_rect": list(self.eye_rect), "frame_rect": list(self.frame_rect), "probe_frames": probes,
+               "lut": np.asarray(self.table_np).reshape(3, 256).astype(int).tolist()}
+        return {"match_colour": self.mode, "colour_probe_frames": probes, "colour_lut": str(path)}, {path: json.dumps(lut)}

@@ -19,15 +19,11 @@ stores the matcher's disparity itself (64 s / 65535 pixels of its eye), and sour
 eye's target of a pixel is x - round(K s d): the left eye is the 4K frame, the right eye sits where the SBS release had it.
 --fill-from-source SBS_CLIP then takes the disocclusions of that right eye from the SBS clip's stored right eye
 (v3d_render_stereo_source_batch; contract: tests/stereo_source_ref.py) instead of stretching the background into them.
---match-colour clip|frame first fits that eye's colours to the 4K frame's (colour.py: the SBS clip is another release, with another
-grading; per-channel histogram matching left eye -> 4K frame, applied to the right eye on the device; contract: tests/colour_ref.py).
---verify-source [TAU] then checks the rendered right eye against that stored eye, cell by cell (a cell: the targets one stored sample
-spans), and replaces the cells whose mean colour is off by more than TAU with the stored eye's own samples: where the matcher's
-disparity was wrong the warp shows wrong picture content, and the film's right eye says so (v3d_verify_eye_source_batch; contract:
-tests/verify_ref.py).  Only for the layouts in which the right eye lies unpacked in the output: full-sbs and full-tb.
---fidelity-report [PATH] measures what came of it (fidelity.py): per frame, error sums and SSIM of the right eye before the fill
-(rendered once more into scratch), of the right eye as written and of the left eye, each against the SBS frame's stored eye
-(v3d_eye_fidelity_batch; contract: tests/fidelity_ref.py).  No output byte and no cache key changes.
+--match-colour clip|frame first fits that eye's colours to the 4K frame's (colour.py: the SBS clip is another release, another grading);
+--verify-source [TAU] then checks the rendered right eye against that stored eye, cell by cell, and replaces the cells whose mean
+colour is off by more than TAU with the stored eye's own samples (verify.py; only where the right eye lies unpacked in the output:
+full-sbs and full-tb); --fidelity-report [PATH] measures what came of it against the SBS frame's stored eyes (fidelity.py), and changes
+no output byte and no cache key.  These three are the plan's steps (verify.SourceStep): the conversion only iterates them.
 
 Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
 cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
@@ -40,9 +36,13 @@ from pathlib import Path
 
 import numpy as np
 
+from . import sharding
 from .backend import HipBackend, require_hip_device
+from .colour import DEFAULT_PROBES, ColourMatcher
+from .fidelity import FidelityMonitor, check_fidelity_report
 from .utils import (PngWriterPool, encode_png8, finish_sequence, get_video_info, iter_frames, prefetch_map, read_png16,
                     sibling_frames_dir)      # sibling_frames_dir is importable from here too
+from .verify import DEFAULT_VERIFY_TAU, VERIFY_LAYOUTS, VERIFY_TAU_MAX, SourceVerifier, check_source_rules, check_verify_source  # noqa: F401
 
 # V3D_PACK_*: codes 0 / 1 are V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS of v3d_render_stereo[_subpixel]_batch, codes >= 2 go to
 # v3d_render_stereo_packed_batch
@@ -50,11 +50,6 @@ LAYOUTS = {"full-sbs": 0, "half-sbs": 1, "full-tb": 2, "half-tb": 3, "interlaced
 DEFAULT_MAX_SHIFT, DEFAULT_CONVERGENCE, DEFAULT_EYE_SPLIT = 48.0, 0.5, 0.5
 PARALLAX = ("invented", "source")
 FILL_RIGHT_EYE = 2                  # --fill-from-source: fill_eyes of v3d_render_stereo_source_batch (the left eye has gain 0, no holes)
-# --verify-source: the threshold's default and range (mean absolute difference of a cell's channel sums per pixel, the three channels
-# added: 0 .. 765).  48 is a convention exposed as a flag, like the matcher's min_score: not a film measurement
-DEFAULT_VERIFY_TAU, VERIFY_TAU_MAX = 48, 765
-VERIFY_LAYOUTS = ("full-sbs", "full-tb")       # the packings in which the right eye lies unpacked in the output
-VERIFY_WARN_SHARE = 0.25
 # frames per launch: 4 x (25 MB BGR + 17 MB depth) of pinned input staging and 4 x 50 MB of pinned output (full SBS at 4K)
 CONVERT_BATCH = 4
 
@@ -77,8 +72,6 @@ def add_stereo_arguments(parser):
                         help=f'depth at the screen plane, 0 (far) .. 1 (near) (default {DEFAULT_CONVERGENCE:g})')
     parser.add_argument('--eye-split', type=float, default=None,
                         help=f"left eye's share of the shift, 0 .. 1; 0 keeps the 4K frame as the left eye (default {DEFAULT_EYE_SPLIT:g})")
-
-
     parser.add_argument('--subpixel', action='store_true',
                         help='sub-pixel DIBR: positions in 1/16 px, colours interpolated between neighbouring sources '
                              '(smooth surfaces render without one-pixel tears; default: whole-pixel shifts)')
@@ -147,22 +140,6 @@ def fill_map_q16(spatial_map, eye_size, frame_size):
     return q
 
 
-def check_verify_source(tau, layout, fill_from_source, clip: bool = True):
-    """--verify-source TAU against the flags it depends on -> tau as an int; ValueError otherwise.  clip: a run over clips, which
-    needs the SBS clip's path (the NumPy surface is handed the SBS frame with every call, and fill_from_source is then its
-    parallax="source")"""
-    if isinstance(tau, bool) or not isinstance(tau, (int, np.integer)) or not 0 <= tau <= VERIFY_TAU_MAX:
-        raise ValueError(f"--verify-source takes an integer threshold in [0, {VERIFY_TAU_MAX}], got {tau!r}")
-    if not fill_from_source:
-        raise ValueError("--verify-source needs " + ("--fill-from-source" if clip else "parallax='source' (--parallax source "
-                         "--fill-from-source)") + ": it checks the rendered right eye against the SBS clip's stored right eye, which "
-                         "only the source fill uploads")
-    if layout not in VERIFY_LAYOUTS:
-        raise ValueError(f"--verify-source works on the layouts {', '.join(VERIFY_LAYOUTS)}, in which the right eye lies unpacked in "
-                         f"the output; {layout} squeezes, interleaves or mixes it")
-    return int(tau)
-
-
 def right_eye_view(out, layout, W, H):
     """the right eye [n,H,W,3] of packed full-sbs / full-tb frames [n,outH,outW,3] as a view (NumPy array or tensor alike)"""
     return out[:, :, W:] if layout == LAYOUTS["full-sbs"] else out[:, H:]
@@ -213,8 +190,9 @@ def render_stereo(native, frames, depths, gain_left, gain_right, conv, layout, o
     return native.render_stereo_batch(frames, depths, gain_left, gain_right, conv, layout, out, subpixel=subpixel)
 
 
-def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, params: dict, gains):
-    """one process, after every frame is written: the manifest of the PNG sequence, through finish_sequence (as encode_depth4k)"""
+def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, height: int, fps: float, params: dict, gains, entries=()):
+    """one process, after every frame is written: the manifest of the PNG sequence (entries: what the plan's steps add to it), through
+    finish_sequence (as encode_depth4k)"""
     man = {
         "format": "png8-rgb-sequence", "frames_dir": str(frames_dir), "pattern": "frame_%06d.png",
         "count": count, "width": width, "height": height, "fps": fps, "layout": params["layout"],
@@ -227,12 +205,7 @@ def finish_stereo_output(frames_dir: Path, output_path, count: int, width: int, 
         man.update(parallax="source", parallax_scale=params["parallax_scale"], parallax_gain=params["parallax_gain"])
     if params.get("fill_from_source"):
         man.update(fill_from_source=params["fill_from_source"], source_start_frame=params.get("source_start_frame", 0))
-    if params.get("match_colour"):
-        man.update({k: params[k] for k in ("match_colour", "colour_probe_frames", "colour_lut") if k in params})
-    if params.get("verify_source"):
-        man["verify_source"] = params["verify_source"]
-    if params.get("fidelity_report"):
-        man["fidelity_report"] = params["fidelity_report"]
+    man.update(entries)
     finish_sequence(frames_dir, "frame_%06d.png", output_path, fps, man)
 
 
@@ -271,7 +244,7 @@ class HipRenderBackend(HipBackend):
         torch's caching host allocator and returns to it once the writers drop the last frame of it.
         source (--fill-from-source): dict(frames: the SBS BGR frames [Hs,Ws,3] of this batch, fill_eyes, q: (ax, bx, ay, by)) -- the
         render is v3d_render_stereo_source_batch, one launch all the same.  With a `match` entry (--match-colour: ColourMatcher.
-        source_entry) the right-eye half of the uploaded SBS frames is colour-matched in place before that launch: with the clip's
+        request) the right-eye half of the uploaded SBS frames is colour-matched in place before that launch: with the clip's
         table, or with one table per frame fitted to this batch (two histograms, the tables, the apply); nothing synchronises.
         With a `verify` entry (--verify-source: dict(tau)) the right eye of the staged output is checked in place against the
         (colour-matched) stored right eye right after the render, v3d_verify_eye_source_batch with the render's own map; its
@@ -386,12 +359,8 @@ class StereoPlan:
     convergence / eye_split, parallax_gain scales it;
     fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
     of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from;
-    match_colour: "clip" or "frame" fits the SBS clip's colours to the 4K frame's before the fill (colour.py; needs
-    fill_from_source: it corrects the eye the fill samples, and nothing else reads it), match_probes: the clip mode's probe pairs;
-    verify_source: the threshold tau of the source-verified right eye, or None (needs fill_from_source and a layout of
-    VERIFY_LAYOUTS): the render calls' source entry gains verify=dict(tau), and note_verify adds up what the backend counted;
-    fidelity_report: None, True (the report goes next to the manifest) or its path (fidelity.py; the same needs): process_conversion
-    sets up a FidelityMonitor as self.fidelity, and the render calls' source entry gains its request"""
+    match_colour and match_probes, verify_source (the threshold), fidelity_report (True: next to the manifest, or its path): the
+    source-eye options, which make self.steps (verify.SourceStep) in the order of their entries in the render calls' source dict"""
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", subpixel: bool = False, parallax: str = "invented",
@@ -399,30 +368,22 @@ class StereoPlan:
                  match_probes: int = None, verify_source: int = None, fidelity_report=None):
         if parallax not in PARALLAX:
             raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
-        if fill_from_source is not None and parallax != "source":
-            raise ValueError("--fill-from-source needs --parallax source: the holes of an invented parallax do not line up with the real eye")
+        check_source_rules(fill_from_source, parallax=parallax)
         if isinstance(source_start_frame, bool) or not isinstance(source_start_frame, (int, np.integer)) or source_start_frame < 0:
             raise ValueError(f"--source-start-frame must be an integer >= 0, got {source_start_frame!r}")
-        if match_colour is None and match_probes is not None:
-            raise ValueError("--match-probes needs --match-colour clip: it counts the frame pairs the clip's one table is fitted to")
+        check_source_rules(fill_from_source, match_colour=match_colour, match_probes=match_probes)
+        self.steps = []
         if match_colour is not None:
-            from .colour import DEFAULT_PROBES, check_parameters
-            if fill_from_source is None:
-                raise ValueError("--match-colour needs --fill-from-source: it corrects the colours of the SBS clip's right eye, which "
-                                 "only the source fill reads")
-            if match_colour != "clip" and match_probes is not None:
-                raise ValueError("--match-probes needs --match-colour clip: frame mode fits every batch to its own frames")
-            check_parameters(match_colour, DEFAULT_PROBES if match_probes is None else match_probes)
-            match_probes = DEFAULT_PROBES if match_probes is None else int(match_probes)
+            self.steps.append(ColourMatcher(match_colour, DEFAULT_PROBES if match_probes is None else match_probes))   # checks both values
+            match_probes = self.steps[-1].probes
         self.match_colour, self.match_probes = match_colour, match_probes
         self.verify_source = None if verify_source is None else check_verify_source(verify_source, layout, parallax == "source", False)
-        self.verify_shares = []                      # replaced cells / cells of every verified frame this process rendered
-        if fidelity_report is not None and fidelity_report is not False:
-            from .fidelity import check_fidelity_report
-            check_fidelity_report(layout, parallax == "source", False)
+        if self.verify_source is not None:
+            self.steps.append(SourceVerifier(self.verify_source))
         self.fidelity_report = None if fidelity_report is None or fidelity_report is False else fidelity_report
-        self.fidelity = None                         # the FidelityMonitor of a run (process_conversion)
-        self.matcher = None                          # the ColourMatcher of a run (process_conversion)
+        if self.fidelity_report is not None:
+            check_fidelity_report(layout, parallax == "source", False)
+            self.steps.append(FidelityMonitor(path=self.fidelity_report))
         self.parallax, self.parallax_gain = parallax, parallax_gain
         self.fill_from_source, self.source_start_frame = fill_from_source, int(source_start_frame)
         self.layout_code, self.gains = stereo_settings(max_shift, convergence, eye_split, layout, subpixel)
@@ -460,49 +421,32 @@ class StereoPlan:
         """what a backend's render call gains: nothing with --subpixel off, so a backend that predates it is called as before"""
         return {"subpixel": True} if self.subpixel else {}
 
-    def source_kwargs(self, sbs_frames, frame_size):
-        """what a backend's render call gains with --fill-from-source: nothing without it"""
+    def source_kwargs(self, sbs_frames, frame_size, surface: bool = False):
+        """what a backend's render call gains with --fill-from-source: nothing without it (surface: on the NumPy surface, which prepares no step)"""
         if sbs_frames is None:
             return {}
         Hs, Ws = sbs_frames[0].shape[:2]
         if Ws % 2:
             raise ValueError(f"the SBS frames of --fill-from-source are {Ws} wide: not two eyes side by side")
         source = dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE, q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))
-        if self.matcher is not None:
-            source["match"] = self.matcher.source_entry()
-        if self.verify_source is not None:
-            source["verify"] = dict(tau=self.verify_source)
-        if self.fidelity is not None:
-            source["fidelity"] = self.fidelity.request()
+        source.update((step.key, step.request()) for step in self.steps if step.on_surface or not surface)
         return {"source": source}
 
-    def note_verify(self, backend, source, frame_size):
-        """after a render call with a verify entry: the backend's replaced cells per frame -> shares of the frame's cells"""
-        from ._native import verify_cell
-        counts = backend.verify_counts()
-        if counts is None:
-            raise RuntimeError("--verify-source: the backend rendered without verifying")
-        cx, cy = verify_cell(source["q"][0], source["q"][2])
-        cells = -(-frame_size[0] // cx) * -(-frame_size[1] // cy)
-        self.verify_cell = (cx, cy)
-        self.verify_shares += [int(c) / cells for c in counts]
-
-    def verify_record(self, world: int = 1):
-        """the manifest's verify_source block; the shares are this process's own, so null under torchrun"""
-        alone = world == 1 and bool(self.verify_shares)
-        return {"tau": self.verify_source, "cell": list(getattr(self, "verify_cell", (None, None))),
-                "replaced_share": float(np.mean(self.verify_shares)) if alone else None,
-                "replaced_share_max": float(np.max(self.verify_shares)) if alone else None}
+    def note(self, backend, src, indices, frame_size):
+        """after a render call that carried source_kwargs' src: every step whose request was in it takes note"""
+        for step in self.steps:
+            if step.key in src.get("source", ()):
+                step.note(backend, indices, frame_size, src["source"]["q"])
 
     def encoder(self, gpu_png: bool):
         """the writer pool's encoder of a rendered frame: the wrapper of a device-deflated stream, or zlib on the writer threads"""
         from .png_gpu import rgb8_file
         return rgb8_file(*self.size) if gpu_png else png_rgb_from_bgr
 
-    def finish(self, frames_dir: Path, output_path, count: int, fps: float):
+    def finish(self, frames_dir: Path, output_path, count: int, fps: float, entries=()):
         """one process, after every frame is written: info.json makes frames_dir a clip, then the H.264 file or the manifest"""
         (frames_dir / "info.json").write_text(json.dumps({"fps": fps}))
-        finish_stereo_output(frames_dir, output_path, count, *self.size, fps, self.params, self.gains)
+        finish_stereo_output(frames_dir, output_path, count, *self.size, fps, self.params, self.gains, entries)
 
 
 def _of_plan(name):
@@ -514,18 +458,13 @@ class DepthTo3DConverter:
 
     writer_pool_factory = PngWriterPool       # sink of the 8-bit RGB frames (the CLIs' hook)
 
-    def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
-                 eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", device: str = "cuda", backend=None,
-                 batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", subpixel: bool = False, parallax: str = "invented",
-                 parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
-                 match_probes: int = None, verify_source: int = None, fidelity_report=None):
+    def __init__(self, device: str = "cuda", backend=None, batch_size: int = CONVERT_BATCH, png_encoder: str = "zlib", **stereo):
         """backend: HipRenderBackend (built when None) or a stand-in with its render_batch (host-logic tests);
         png_encoder: "gpu" deflates the rendered frames on the device (png_gpu.py); "zlib" = on the writer threads;
         every other keyword is StereoPlan's (parallax="source": set_source_parallax, or process_conversion from the depth manifest)"""
         from .png_gpu import check_png_encoder
         self.png_encoder = check_png_encoder(png_encoder)
-        self.plan = StereoPlan(max_shift, convergence, eye_split, layout, subpixel, parallax, parallax_gain, fill_from_source,
-                               source_start_frame, match_colour, match_probes, verify_source, fidelity_report)
+        self.plan = StereoPlan(**stereo)
         if backend is None:
             require_hip_device(device)
             backend = HipRenderBackend(device)
@@ -541,9 +480,6 @@ class DepthTo3DConverter:
         """the plan's resolve_source, silently"""
         return self.plan.resolve_source(depth_range, Whi, spatial_map, announce=False)
 
-    def source_kwargs(self, sbs_frames, frame_size):
-        return self.plan.source_kwargs(sbs_frames, frame_size)
-
     def render_frame(self, frame_bgr: np.ndarray, depth_u16: np.ndarray, source: np.ndarray = None, colour_table: np.ndarray = None) -> np.ndarray:
         """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous).  source: the SBS BGR
         frame the depth was made from; the right eye's disocclusions are sampled from its stored right eye (parallax="source" only);
@@ -558,7 +494,7 @@ class DepthTo3DConverter:
             raise ValueError("source= needs parallax='source'")
         if colour_table is not None and source is None:
             raise ValueError("colour_table= needs source=: it is applied to the SBS frame's right eye")
-        src = self.source_kwargs(None if source is None else [np.asarray(source, np.uint8)], frame_bgr.shape[1::-1])
+        src = self.plan.source_kwargs(None if source is None else [np.asarray(source, np.uint8)], frame_bgr.shape[1::-1], surface=True)
         if colour_table is not None:
             table = np.asarray(colour_table)
             if table.dtype != np.uint8 or table.shape != (3, 256):
@@ -566,15 +502,13 @@ class DepthTo3DConverter:
             src["source"]["match"] = dict(mode="clip", table=table, eye_rect=None, frame_rect=None)
         out = np.array(self.backend.render_batch([frame_bgr], [depth_u16], *self.gains, self.layout_code,
                                                  **self.plan.render_kwargs(), **src)[0])
-        if src and "verify" in src["source"]:
-            self.plan.note_verify(self.backend, src["source"], frame_bgr.shape[1::-1])
+        self.plan.note(self.backend, src, [0], frame_bgr.shape[1::-1])
         return out
 
     def process_conversion(self, video_4k_path: str, depth_path: str, output_path: str = None, force_reprocess: bool = False,
                            guide_start_frame: int = 0, max_frames: int = None) -> str:
         """depth frame i pairs with 4K frame guide_start_frame + i (the offset the upscale CLI used).  Returns the output
         path: an H.264 file when ffmpeg exists and it ends in .mp4, else a JSON manifest of the PNG sequence."""
-        from . import sharding
         plan = self.plan
         print(f"4K + depth -> 3D ({self.params['layout']}{', sub-pixel' if self.subpixel else ''}"
               f"{', source parallax' if self.parallax == 'source' else ''}): {video_4k_path} + {depth_path}")
@@ -582,18 +516,17 @@ class DepthTo3DConverter:
         info = get_video_info(video_4k_path)
         if not info:
             raise ValueError(f"Could not read video info: {video_4k_path}")
-        W, H, fps = info['width'], info['height'], info['fps']
+        W, H = info['width'], info['height']
         if output_path is None:
             # _subpx: a run with --subpixel never reuses a file rendered without it
-            tag = ("_subpx" if self.subpixel else "") + ("_srcpx" if self.parallax == "source" else "") + ("_srcfill" if self.fill_from_source else "") + \
-                  {None: "", "clip": "_cm", "frame": "_cmf"}[plan.match_colour] + ("" if plan.verify_source is None else f"_vs{plan.verify_source}")
+            tag = ("_subpx" if self.subpixel else "") + ("_srcpx" if self.parallax == "source" else "") + \
+                  ("_srcfill" if self.fill_from_source else "") + "".join(step.output_tag for step in plan.steps)
             output_path = f"3d_{self.params['layout']}{tag}_{Path(depth_path).with_suffix('').name}.mp4"
         output_path = Path(output_path)
         if output_path.exists() and not force_reprocess:
             print(f"✓ Using existing 3D video: {output_path}")
-            if plan.fidelity_report is not None:
-                from .fidelity import CACHED_NOTE
-                print(CACHED_NOTE)
+            for note in filter(None, (step.cached_note for step in plan.steps)):
+                print(note)
             return str(output_path)
         plan.check_frame(W, H)
         if self.parallax == "source":                           # the film's parallax: from the depth run's own record
@@ -604,33 +537,25 @@ class DepthTo3DConverter:
                                  f"{man['input_layout']}): the fill samples the stored right eye at column We + i of a side-by-side "
                                  f"frame, and a top-bottom clip keeps that eye in rows, not columns.  --parallax source alone works "
                                  f"for both layouts")
-        if plan.verify_source is not None:
-            check_verify_source(plan.verify_source, self.params["layout"], self.fill_from_source)
-        if plan.fidelity_report is not None:
-            from .fidelity import FidelityMonitor, check_fidelity_report
-            check_fidelity_report(self.params["layout"], self.fill_from_source)
-            plan.fidelity = FidelityMonitor(self.backend, ceiling=plan.gains[0] == 0)
         if self.fill_from_source is not None:
             if not get_video_info(self.fill_from_source):
                 raise ValueError(f"Could not read video info: {self.fill_from_source}")
             self.params.update(fill_from_source=str(self.fill_from_source), source_start_frame=self.source_start_frame)
         n = len(depth_files) if max_frames is None else min(len(depth_files), max(int(max_frames), 0))
-        frames_dir = sibling_frames_dir(output_path)
-        if plan.match_colour is not None:                       # every rank: the same probes, the same table
-            from .colour import ColourMatcher
-            src_info = get_video_info(self.fill_from_source)
-            plan.matcher = ColourMatcher(self.backend, plan.match_colour, plan.match_probes).prepare(
-                self.fill_from_source, self.source_start_frame, video_4k_path, max(int(guide_start_frame), 0), n,
-                (src_info['width'] // 2, src_info['height']), (W, H), plan.spatial_map)
-            self.params.update(plan.matcher.manifest_entries())
-            if plan.match_colour == "clip":
-                self.params["colour_lut"] = str(frames_dir / "colour_lut.json")
-                print(f"Colour match: one table from {len(plan.matcher.probe_frames)} frame pairs")
+        g0, frames_dir = max(int(guide_start_frame), 0), sibling_frames_dir(output_path)
+        for step in plan.steps:                                 # on every rank, before the ranks part: all prepare the same
+            step.prepare(self.backend, plan, video_4k_path, g0, n, (W, H))
+        self._render(video_4k_path, g0, n, depth_files, frames_dir, (W, H))
+        self._finish(output_path, frames_dir, info['fps'])
+        print(f"✓ 3D video saved: {output_path}")
+        return str(output_path)
 
+    def _render(self, video_4k_path, g0, n, depth_files, frames_dir, size):
+        """the streaming loop: this rank's frames, batch_size at a time, through the backend and on to the writers"""
+        plan = self.plan
         rank, world = sharding.rank_world()
         sharding.require_initialized(world)
         frames_dir.mkdir(parents=True, exist_ok=True)
-        g0 = max(int(guide_start_frame), 0)
         mine = list(range(rank, n, world))                       # frame i -> rank i mod world; both inputs decoded per rank
         depths = prefetch_map(read_png16, [depth_files[i] for i in mine])
         frames4k = iter_frames(video_4k_path, g0, n, stride=world, offset=rank)
@@ -646,12 +571,9 @@ class DepthTo3DConverter:
                 return
             # --png-encoder gpu: deflated on the device, only the streams cross PCIe
             render = self.backend.render_batch_png if gpu_png else self.backend.render_batch
-            src = plan.source_kwargs(batch_s if sbs_frames is not None else None, (W, H))
+            src = plan.source_kwargs(batch_s if sbs_frames is not None else None, size)
             out = render(batch_f, batch_d, *plan.gains, plan.layout_code, capacity=self.batch_size, **plan.render_kwargs(), **src)
-            if plan.verify_source is not None:
-                plan.note_verify(self.backend, src["source"], (W, H))
-            if plan.fidelity is not None:
-                plan.fidelity.note(batch_i, (W, H), src["source"]["q"])
+            plan.note(self.backend, src, batch_i, size)
             for j, i in enumerate(batch_i):
                 writers.submit(frames_dir / f"frame_{i:06d}.png", out[j], encode=encode)
             rendered += len(batch_i)
@@ -684,33 +606,24 @@ class DepthTo3DConverter:
         finally:
             depths.close()
         self.last_rendered_frames = rendered
-        total = sharding.total(rendered)
+
+    def _finish(self, output_path, frames_dir, fps):
+        """every rank: the steps' summaries; rank 0: their side files and the clip's manifest"""
+        rank, world = sharding.rank_world()
+        total = sharding.total(self.last_rendered_frames)
         if total == 0:
             raise ValueError("No frames rendered")
         sharding.barrier()
-        if plan.verify_source is not None:
-            self.params["verify_source"] = rec = plan.verify_record(world)
-            if rec["replaced_share"] is not None:
-                print(f"Source verify: tau {rec['tau']}, cells of {rec['cell'][0]} x {rec['cell'][1]} pixels: "
-                      f"{rec['replaced_share']:.2%} of the right eye's cells replaced on average, {rec['replaced_share_max']:.2%} at most")
-                if rec["replaced_share"] > VERIFY_WARN_SHARE:
-                    print(f"Warning: --verify-source replaced {rec['replaced_share']:.0%} of the right eye: the SBS clip disagrees with "
-                          f"the render almost everywhere, as another grading or another framing makes it.  Try --match-colour, or a "
-                          f"depth run whose map came from `align --register-spatial`")
-        if plan.fidelity is not None:
-            fid_path = output_path.with_name(output_path.with_suffix("").name + "_fidelity.json") if plan.fidelity_report is True \
-                else Path(plan.fidelity_report)
-            self.params["fidelity_report"] = plan.fidelity.finish(fid_path, world)
-            plan.fidelity.report()
-            if rank == 0 and plan.fidelity.data is not None:
-                plan.fidelity.write(fid_path)
+        entries, files = {}, {}
+        for step in self.plan.steps:
+            more, named = step.finish(output_path, frames_dir, world)
+            entries, files = {**entries, **more}, {**named, **files}     # the files in the order they were always written: the last step's first
         if rank == 0:
-            if plan.matcher is not None and plan.matcher.lut_record() is not None:
-                (frames_dir / "colour_lut.json").write_text(json.dumps(plan.matcher.lut_record()))
-            plan.finish(frames_dir, output_path, total, fps)
+            for path, text in files.items():
+                path.parent.mkdir(parents=True, exist_ok=True)
+                path.write_text(text)
+            self.plan.finish(frames_dir, output_path, total, fps, entries)
         sharding.barrier()
-        print(f"✓ 3D video saved: {output_path}")
-        return str(output_path)
 
 
 def main(argv=None, backend=None):
@@ -757,20 +670,14 @@ def main(argv=None, backend=None):
     if not resolve_guide_start(args):
         return 1
     try:
-        from . import sharding
         sharding.init_process_group()            # no-op for one process; under torchrun: one rank per GPU (sets the device)
-        source = {"fill_from_source": args.fill_from_source, "source_start_frame": args.source_start_frame} if args.fill_from_source else {}
-        if args.source_start_frame and not args.fill_from_source:
-            raise ValueError("--source-start-frame needs --fill-from-source")
-        match = {k: v for k, v in (("match_colour", args.match_colour), ("match_probes", args.match_probes)) if v is not None}
-        verify = {} if args.verify_source is None else {"verify_source": check_verify_source(args.verify_source, args.layout, args.fill_from_source)}
-        fidelity = {}
-        if args.fidelity_report is not None:
-            from .fidelity import check_fidelity_report
-            check_fidelity_report(args.layout, args.fill_from_source)
-            fidelity = {"fidelity_report": args.fidelity_report}
-        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args), **source, **match,
-                                  **verify, **fidelity)
+        check_source_rules(args.fill_from_source, source_start_frame=args.source_start_frame)
+        if args.verify_source is not None:
+            check_verify_source(args.verify_source, args.layout, args.fill_from_source)
+        check_source_rules(args.fill_from_source, layout=args.layout, fidelity_report=args.fidelity_report)
+        conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args),
+                                  **{k: getattr(args, k) for k in ("fill_from_source", "source_start_frame", "match_colour", "match_probes",
+                                                                     "verify_source", "fidelity_report")})
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)

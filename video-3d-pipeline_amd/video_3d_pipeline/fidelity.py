@@ -25,12 +25,13 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from .verify import VERIFY_LAYOUTS as LAYOUTS, SourceStep, check_source_rules
+
 FIELDS = ("n_cells", "sad", "ssd", "n_bad", "n_win", "ssim_q20")
 SERIES = ("warp", "final", "ceiling")
 DEFAULT_BAD, BAD_MAX = 48, 765               # a convention (--verify-source's default threshold), not a measurement: levels, B + G + R
 SSIM_ONE = 1 << 20
 WORST_FRAMES = 10
-LAYOUTS = ("full-sbs", "full-tb")            # the packings in which an eye lies unpacked in the output (convert.VERIFY_LAYOUTS)
 SHARDED_REASON = "the records are a rank's own; a sharded run (world > 1) gives no rank the whole clip"
 CEILING_REASON = "the left eye is rendered (left gain != 0): it is not the 4K frame, so it says nothing about the two releases"
 CACHED_NOTE = "Fidelity report: none was made, the existing output was used; --force recomputes"
@@ -45,14 +46,8 @@ def check_parameters(bad_threshold=DEFAULT_BAD):
 
 
 def check_fidelity_report(layout, fill_from_source, clip: bool = True):
-    """--fidelity-report against the flags it depends on (the wording of --verify-source's check); ValueError otherwise"""
-    if not fill_from_source:
-        raise ValueError("--fidelity-report needs " + ("--fill-from-source" if clip else "parallax='source' (--parallax source "
-                         "--fill-from-source)") + ": it measures the rendered right eye against the SBS clip's stored right eye, which "
-                         "only the source fill uploads")
-    if layout not in LAYOUTS:
-        raise ValueError(f"--fidelity-report works on the layouts {', '.join(LAYOUTS)}, in which the right eye lies unpacked in "
-                         f"the output; {layout} squeezes, interleaves or mixes it")
+    """--fidelity-report against the flags it depends on; ValueError otherwise"""
+    check_source_rules(fill_from_source, layout=layout, fidelity_report=True, clip=clip)
 
 
 def figures(t: Dict[str, int]) -> Dict:
@@ -101,49 +96,53 @@ def _jsonable(v):
     return "inf" if isinstance(v, float) and math.isinf(v) else v
 
 
-class FidelityMonitor:
-    """--fidelity-report of the convert CLI.  The converter puts request() into the render call's source entry and calls note()
-    right after the call; nothing here waits for the device before finish().  The backend supplies fidelity_handle() (the records
-    of its last render_batch, on their way to pinned memory) and read_fidelity(handle, wait)."""
+class FidelityMonitor(SourceStep):
+    """--fidelity-report of the convert CLI.  Nothing here waits for the device before finish().  The backend supplies
+    fidelity_handle() (the records of its last render_batch, on their way to pinned memory) and read_fidelity(handle, wait)."""
+    key, cached_note = "fidelity", CACHED_NOTE
 
-    def __init__(self, backend, bad_threshold: int = DEFAULT_BAD, ceiling: bool = True):
-        self.backend, self.bad_threshold, self.ceiling = backend, check_parameters(bad_threshold), bool(ceiling)
-        self.records = {name: [] for name in SERIES if name != "ceiling" or self.ceiling}
-        self._pending = deque()
-        self.shape = self.cell = None
-        self.data = self.entry = None
+    def __init__(self, bad_threshold: int = DEFAULT_BAD, ceiling: bool = True, path=True):
+        self.bad_threshold, self.ceiling, self.path = check_parameters(bad_threshold), bool(ceiling), path
+        self.records, self._pending = {}, deque()        # {series: [(frame, int64 [6])]}, the ceiling's only when it is measured
+        self.shape = self.cell = self.data = None
+
+    def prepare(self, backend, plan, video_4k_path, guide_start, count, frame_size):
+        check_fidelity_report(plan.params["layout"], plan.fill_from_source)      # a run over clips: now the SBS clip has to be there
+        # a run's own records; the ceiling series only when the left eye is the 4K frame itself, known once the gains are
+        self.ceiling, self.records, self._pending = plan.gains[0] == 0, {}, deque()
 
     def request(self) -> Dict:
         """the `fidelity` entry of a render call's source dict"""
         return dict(bad_thr=self.bad_threshold, ceiling=self.ceiling)
 
-    def note(self, indices, frame_size, q):
+    def note(self, backend, indices, frame_size, q):
         """after a render call that carried request(): indices = the clip frames of the batch"""
         from ._native import verify_cell
         self._drain(False)                   # earlier batches: their events fired with the batch's own copy back
-        handle = self.backend.fidelity_handle()
+        handle = backend.fidelity_handle()
         if handle is None:
             raise RuntimeError("--fidelity-report: the backend rendered without measuring")
         self.shape, self.cell = tuple(int(v) for v in frame_size), verify_cell(q[0], q[2])
-        self._pending.append((handle, list(indices)))
+        self._pending.append((backend, handle, list(indices)))
 
     def _drain(self, wait):
         while self._pending:
-            handle, indices = self._pending[0]
-            rec = self.backend.read_fidelity(handle, wait)
+            backend, handle, indices = self._pending[0]
+            rec = backend.read_fidelity(handle, wait)
             if rec is None:
                 return
             self._pending.popleft()
-            for name, r in zip(self.records, rec):
-                self.records[name].extend((i, np.asarray(row, np.int64)) for i, row in zip(indices, r))
+            for name, r in zip(SERIES, rec):
+                self.records.setdefault(name, []).extend((i, np.asarray(row, np.int64)) for i, row in zip(indices, r))
 
-    def finish(self, path, world: int = 1) -> Dict:
-        """-> the manifest's fidelity_report entry (also kept in .entry; .data holds the whole fidelity.json, None when sharded)"""
+    def finish(self, output_path, frames_dir, world):
+        """-> the manifest's fidelity_report entry, the report next to the manifest or at its path (.data: its content, None when sharded)"""
         self._drain(True)
         if world != 1:
-            self.entry = dict(path=None, summary=None, reason=SHARDED_REASON)
-            return self.entry
-        s = summary(dict(self.records, **({} if self.ceiling else {"ceiling": None})))
+            self.report()
+            return {"fidelity_report": dict(path=None, summary=None, reason=SHARDED_REASON)}, {}
+        path = output_path.with_name(output_path.with_suffix("").name + "_fidelity.json") if self.path is True else Path(self.path)
+        s = summary(self.records)
         W, H = self.shape if self.shape else (0, 0)
         params = dict(bad_threshold=self.bad_threshold, cell=list(self.cell or (None, None)), window="8 x 8 cells at stride 4",
                       reference="the stored eyes of the SBS clip, sampled through the render's own map")
@@ -152,10 +151,10 @@ class FidelityMonitor:
             head["ceiling_reason"] = CEILING_REASON
         self.data = dict(head, units=dict(mean_abs="levels per channel", psnr="dB over the cell means", ssim="mean over the windows"),
                          frames=s["frames"])
-        self.entry = _jsonable(dict(path=str(path), **{k: v for k, v in head.items() if k != "series"},
-                                    summary={k: (None if v is None else {a: b for a, b in v.items() if a != "worst_frames"})
-                                             for k, v in s["series"].items()}))
-        return self.entry
+        self.report()
+        entry = dict(path=str(path), **{k: v for k, v in head.items() if k != "series"},
+                     summary={k: (None if v is None else {a: b for a, b in v.items() if a != "worst_frames"}) for k, v in s["series"].items()})
+        return {"fidelity_report": _jsonable(entry)}, {path: json.dumps(_jsonable(self.data), indent=1)}
 
     def report(self):
         if self.data is None:
@@ -171,9 +170,3 @@ class FidelityMonitor:
                 continue
             print(f"  {name} ({notes[name]}): SSIM {num(s['ssim'])}, PSNR {num(s['psnr'], '{:.2f}')} dB, mean abs {num(s['mean_abs'], '{:.2f}')} levels, "
                   f"cells above {self.bad_threshold}: {num(None if s['bad_share'] is None else 100 * s['bad_share'], '{:.2f}')} %")
-
-    def write(self, path) -> Path:
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        path.write_text(json.dumps(_jsonable(self.data), indent=1))
-        return path
