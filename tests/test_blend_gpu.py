@@ -19,8 +19,10 @@ def _d16(rng, H, W):
 
 
 @pytest.mark.parametrize("W,H,mw,mh", [(192, 108, 384, 384), (192, 108, 48, 48), (320, 180, 320, 180), (203, 77, 97, 333),
-                                       (1920, 1080, 384, 384), (70, 1, 5, 3), (257, 33, 1, 1), (64, 64, 128, 128)])
+                                       (1920, 1080, 384, 384), (70, 1, 5, 3), (257, 33, 1, 1), (64, 64, 128, 128), (515, 510, 97, 33)])
 def test_blend_bit_exact(native, oracle, W, H, mw, mh):
+    """k_mono_blend has at most 1024 workgroups a frame (tests/launch_plan.py): 1920 x 1080 walks eight passes, the last partial;
+    515 x 510 is 506 pixels past one pass, so two of the 1024 workgroups alone walk on"""
     rng = np.random.default_rng(W * 7 + H + mw)
     d16 = _d16(rng, H, W)
     mono = (rng.random((mh, mw)).astype(np.float32) * 30 - 4)

@@ -11,7 +11,9 @@ Which shape reaches which route of csrc/v3d_colour.hip:
   k_colour_lut the cases of tests/test_colour_ref.py, among them the one a 64-bit compare gets wrong.
   k_bgr_lut<true>  (aligned 16-byte loads): in place at every phase, and out of place with both images at the same byte of a block;
   k_bgr_lut<false> (byte loads): out of place at different phases; both with whole blocks (one 16-byte store) and row ends (byte
-               stores), one shared table and one per frame."""
+               stores), one shared table and one per frame.
+  col_band     rows per workgroup from the lanes' fill: every case above; from the frame count (8 workgroups a frame, the floor):
+               130 frames of 171 x 210, both kernels (tests/test_launch_plan_host.py holds it against tests/launch_plan.py)."""
 import ctypes as C
 
 import numpy as np
@@ -182,6 +184,25 @@ def test_apply_out_of_place_both_routes(native):
     assert np.array_equal(native.bgr_lut_batch(src, torch.from_numpy(T[2]).cuda()).cpu().numpy(), CR.apply(F, T[2]))
     assert np.array_equal(native.bgr_lut_batch(src, torch.from_numpy(T[2]).cuda(), (5, 0, 900, 1)).cpu().numpy(), CR.apply(F, T[2], (5, 0, 900, 1)))
     assert np.array_equal(src.cpu().numpy(), F)
+
+
+def test_bands_decided_by_the_frame_count(native):
+    """col_band gives a workgroup as many rows as fill its 256 lanes once, or ceil(rows / max(1024 / n, 8)) where that is more
+    (tests/launch_plan.py).  Every case above has the former; LP.COLOUR_BAND_CASE, 130 frames of 171 x 210, has the latter in
+    k_bgr_hist (27 rows for 24) and k_bgr_lut (27 for 8): 8 workgroups a frame, the last with 21 rows.  Five distinct frames
+    repeated in order"""
+    import launch_plan as LP
+    n, W, H = LP.COLOUR_BAND_CASE
+    rng = np.random.default_rng(130)
+    base = rng.integers(0, 256, (5, H, W, 3), dtype=np.uint8)
+    base[1] = base[1] // 64 * 64
+    F = base[np.arange(n) % 5]
+    _hist(native, F, (0, 0, W, H), base=1, rowpad=2, framepad=5)
+    _hist(native, F, (3, 0, W - 2, H), base=0)
+    T = rng.integers(0, 256, (n, 3, 256), dtype=np.uint8)
+    _apply(native, F, T, (0, 0, W, H), False, sbase=6, dbase=6, srowpad=2, drowpad=18, sframepad=3, dframepad=35)
+    _apply(native, F, T[0], (3, 0, W - 2, H), False, sbase=3, dbase=7, srowpad=1)
+    _apply(native, F, T, (0, 0, W, H), True, sbase=5, srowpad=3)
 
 
 def test_apply_refusals(native):

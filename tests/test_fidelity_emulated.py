@@ -9,6 +9,7 @@ import pytest
 
 import emu_case as E
 import fidelity_ref as F
+import launch_plan as LP
 import stereo_source_ref as X
 
 ENTRY, WS = "v3d_eye_fidelity_batch", "v3d_eye_fidelity_ws_bytes"
@@ -89,6 +90,40 @@ def test_wide_rows(driver, tmp_path):
     _call(driver, tmp_path, _noisy(rng, sbs, 1, 3840, 9, MAPS[0]), sbs, 1, MAPS[0], 48, layout="sbs")
     sbs = rng.integers(0, 256, (1, 2, 2 * 8192, 3), dtype=np.uint8)
     _call(driver, tmp_path, _noisy(rng, sbs, 1, 8192, 1, MAPS[1]), sbs, 1, MAPS[1], 48, skew=15)
+
+
+def test_item_and_tile_stride(driver, tmp_path):
+    """the grid's stride in both stages (tests/launch_plan.py; tests/test_launch_plan_host.py holds the regimes): 1025 items for 1024
+    wave slots; 1026 items three waves across under a one-row SBS frame (a wave's second item in another column of waves, the
+    same SBS rows); 257 tiles for 256 workgroups, with noise, the identical eye (a wrong multiple of 2^20 if a tile is dropped or
+    doubled) and the inverted one (negative Q carried)"""
+    rng = np.random.default_rng(8200)
+    _, W, H = LP.EMU_STRIDE
+    sbs = rng.integers(0, 256, (1, H // 2, 12, 3), dtype=np.uint8)           # the lower half clamps to the last row
+    rec = _call(driver, tmp_path, _noisy(rng, sbs, 1, W, H, LP.EMU_MAP), sbs, 1, LP.EMU_MAP, 48, skew=1)
+    assert rec[0, 0] == W * H and 0 < rec[0, 3] < W * H and rec[0, 4] == 0
+    _, W, H = LP.EMU_TAPS
+    sbs = rng.integers(0, 256, (1, 1, 2 * W, 3), dtype=np.uint8)
+    rec = _call(driver, tmp_path, _noisy(rng, sbs, 0, W, H, LP.EMU_MAP), sbs, 0, LP.EMU_MAP, 48, layout="sbs")
+    assert 0 < rec[0, 3] < W * H and rec[0, 4] > 0
+    _, W, H = LP.EMU_TILES
+    sbs = rng.integers(0, 256, (1, H, 2 * W, 3), dtype=np.uint8)
+    n_win = LP.fidelity_plan(1, W, H, LP.EMU_MAP[0], LP.EMU_MAP[2]).nwy
+    rec = _call(driver, tmp_path, _noisy(rng, sbs, 1, W, H, LP.EMU_MAP), sbs, 1, LP.EMU_MAP, 48, skew=15)
+    assert rec[0, 4] == n_win and 0 < abs(rec[0, 5]) < n_win << 20
+    P = X.eye_plane(sbs[0], 1, W, H, *LP.EMU_MAP)[None]
+    assert _call(driver, tmp_path, P, sbs, 1, LP.EMU_MAP, 0)[0].tolist() == [W * H, 0, 0, 0, n_win, n_win << 20]
+    assert _call(driver, tmp_path, 255 - P, sbs, 1, LP.EMU_MAP, 100)[0, 5] < -(n_win << 16)
+
+
+def test_the_floor_of_eight_workgroups_a_frame(driver, tmp_path):
+    """260 frames of 33 items and 9 tiles: 8 workgroups launched in either stage, workgroup 0 walks on; 5 distinct frames repeated"""
+    rng = np.random.default_rng(260)
+    n, W, H = LP.EMU_FLOOR_FIDELITY
+    sbs = rng.integers(0, 256, (5, H, 2 * W, 3), dtype=np.uint8)
+    idx = np.arange(n) % 5
+    rec = _call(driver, tmp_path, _noisy(rng, sbs, 1, W, H, LP.EMU_MAP)[idx], sbs[idx], 1, LP.EMU_MAP, 48, rowpad=1, framepad=3)
+    assert len({tuple(r) for r in rec[:5].tolist()}) == 5 and np.array_equal(rec, rec[:5][idx])
 
 
 def test_three_frames_pitched_rows_and_padded_frames(driver, tmp_path):

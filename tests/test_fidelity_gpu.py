@@ -2,11 +2,29 @@
 55 of a wave's 64 lanes, 16 x 16, a map that does not enlarge), sizes that are no multiple of the cell, rows of cells that cross a
 wave's columns and an item's rows, ncx / ncy at the edges of a window's fit and beyond one tile of the window stage, both eyes, the
 eye as it lies in a full-SBS and in a full top-bottom output, batches with padded pitches and strides, the contents that reach the
-ends of the arithmetic, workspace and records that hold garbage, and the refusals."""
+ends of the arithmetic, workspace and records that hold garbage, and the refusals.
+
+Which shape reaches which route of csrc/v3d_fidelity.hip (tests/launch_plan.py restates the entry's plan, tests/test_launch_plan_host.py
+holds every line below against it):
+  k_fid_cells  one item per wave: SIZES and everything built on them; a second item for 128 of the 1024 waves: 8192 x 130 at
+               16 x 16 cells (test_wide_rows, 1152 items); the item stride proper (t[] carried over a second and a third item, fresh
+               taps per item): LP.STRIDE_SHAPES, 70 columns (two waves across, the second with 6, 7 or 15 live lanes) by as many
+               rows as give 2402 items, for every cell class and in both eyes for 4 x 2; a wave's next item in ANOTHER column of
+               waves under SBS rows that every target row shares: LP.EMU_TAPS, 130 x 2730 against a one-row SBS frame;
+  k_fid_ssim   one tile per workgroup: everything up to 200 x 120 (at most 36 tiles); the tile stride (q carried, the three LDS
+               planes refilled behind the barrier): LP.TILE_SHAPES, 136 x 8408 (33 x 2101 windows: two tiles across, 526 tiles =
+               two passes of the 256 workgroups and 14 tiles more), 9 x 8204 (one window across, 257 tiles: workgroup 0 alone walks
+               on) and both at twice the size under 2 x 2 cells; at the first two the identical eye (n_win << 20 exactly) and at
+               9 x 8204 the inverted one (a negative sum);
+  the floor of 8 workgroups a frame, both stages: LP.TILE_FLOOR_CASE, 260 frames of 200 x 152 (76 items, 10 tiles);
+  the frame stride of all three kernels (f += gridDim.y; scratch reused for a workgroup's second frame): LP.FRAMES_CASE, 65 538
+               frames of 5 x 3 (no window: k_fid_ssim is not launched) and LP.FRAMES_WINDOW_CASE, 65 538 frames of 8 x 8 (one window
+               each), 7 distinct frames repeated so that frame f and frame f + 65535 differ."""
 import numpy as np
 import pytest
 
 import fidelity_ref as F
+import launch_plan as LP
 import stereo_source_ref as X
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +68,7 @@ def _run(native, E, sbs, eye, m, thr, layout="alone", eye_phase=0, sbs_phase=0, 
     sd = torch.as_strided(sflat, (n, Hs, Ws, 3), (Hs * pitch, pitch, 3, 1), sbase)
     sd.copy_(torch.from_numpy(sbs))
     need = native.lib().v3d_eye_fidelity_ws_bytes(n, W, H, m[0], m[2])
-    assert need > 0
+    assert need == LP.fidelity_plan(n, W, H, m[0], m[2]).ws_bytes > 0
     ws = torch.full((need,), poison, dtype=torch.uint8, device="cuda")
     out = torch.full((n, F.FIELDS), poison * 0x0101010101010101 - (1 << 64 if poison > 127 else 0), dtype=torch.int64, device="cuda")
     got = native.eye_fidelity_batch(view, sd, eye, *m, thr, out=out, ws=ws)
@@ -124,6 +142,70 @@ def test_wide_rows(native):
     _check(native, F.V.disturbed(X.eye_plane(sbs[0], 1, 8192, 1, 65536, 0, 65536, 0)[None], 4), sbs, 1, (65536, 0, 65536, 0), 48, eye_phase=15)
     sbs = _sbs(5, 1, 2 * 512, 9)
     _check(native, F.V.disturbed(X.eye_plane(sbs[0], 0, 8192, 130, *MAPS["16x16"])[None], 6), sbs, 0, MAPS["16x16"], 24)
+
+
+def _tall(W, H, name, n=1, eye=1):
+    """as _scene, the SBS frames as tall as the map reaches, so that the rows a target blends keep moving down to the last item"""
+    key = ("tall", W, H, name, n, eye)
+    if key not in _cache:
+        m = MAPS[name]
+        sbs = _sbs(W + H + n, n, 2 * min((W * m[0] >> 16) + 2, 36), (H * m[2] >> 16) + 2)
+        E = F.V.disturbed(np.stack([X.eye_plane(s, eye, W, H, *m) for s in sbs]), W * H + n)
+        _cache[key] = sbs, E, F.fidelity_batch(E, sbs, eye, *m, 48)
+    return _cache[key]
+
+
+@pytest.mark.parametrize("name", list(MAPS))
+def test_item_stride(native, name):
+    """stage 1 at 2402 items for 1024 wave slots: every wave walks a second item, 354 of them a third"""
+    assert set(MAPS) == set(LP.FIDELITY_CLASSES) and all(MAPS[k] == LP.MAPS[k] for k in MAPS)
+    W, H = LP.STRIDE_SHAPES[name]
+    for eye in ((0, 1) if name == "4x2" else (1,)):
+        sbs, E, want = _tall(W, H, name, eye=eye)
+        assert 0 < want[0, 3] < want[0, 0] and want[0, 1] > 0
+        _check(native, E, sbs, eye, MAPS[name], 48, want)
+
+
+def test_item_stride_into_another_column_of_waves(native):
+    """LP.EMU_TAPS, the emulated twin's shape: three waves across and 1026 items, so a wave's second item lies one column of waves
+    further, and a one-row SBS frame, so both items blend the same rows: taps kept from the first item would be another column's"""
+    _, W, H = LP.EMU_TAPS
+    sbs = _sbs(9, 1, 2 * W, 1)
+    rec = _check(native, F.V.disturbed(X.eye_plane(sbs[0], 0, W, H, *LP.EMU_MAP)[None], 10), sbs, 0, LP.EMU_MAP, 48)
+    assert 0 < rec[0, 3] < W * H and rec[0, 4] > 256
+
+
+@pytest.mark.parametrize("W,H,name", LP.TILE_SHAPES)
+def test_tile_stride(native, W, H, name):
+    """stage 2 at more tiles than workgroups: 526 (two across: three passes, the last of 14) and 257 (workgroup 0 alone walks on)"""
+    sbs, E, want = _tall(W, H, name)
+    p = LP.fidelity_plan(1, W, H, MAPS[name][0], MAPS[name][2])
+    assert want[0, 4] == p.nwx * p.nwy and p.tile_passes >= 2 and 0 < abs(want[0, 5]) < want[0, 4] << 20
+    _check(native, E, sbs, 1, MAPS[name], 48, want, eye_phase=3, sbs_phase=1, rowpad=2)
+
+
+@pytest.mark.parametrize("W,H,name", LP.TILE_SHAPES[:2])
+def test_tile_stride_content(native, W, H, name):
+    """the identical eye: every window scores 2^20, so a dropped or a doubled tile shows as a wrong multiple; the inverted eye:
+    negative Q carried from tile to tile"""
+    m = MAPS[name]
+    sbs = _tall(W, H, name)[0]
+    P = X.eye_plane(sbs[0], 1, W, H, *m)[None]
+    ncx, ncy, n_win = native.fidelity_grid(W, H, m[0], m[2])
+    assert _check(native, P, sbs, 1, m, 0)[0].tolist() == [ncx * ncy, 0, 0, 0, n_win, n_win << 20]
+    if W < 100:
+        assert _check(native, 255 - P, sbs, 1, m, 100)[0, 5] < -(n_win << 16)
+
+
+@pytest.mark.parametrize("case,distinct", [(LP.TILE_FLOOR_CASE, 5), (LP.FRAMES_CASE, 7), (LP.FRAMES_WINDOW_CASE, 7)])
+def test_long_batches(native, case, distinct):
+    """the floor of 8 workgroups a frame in both stages, and more frames than the grid has rows (without windows: two launches;
+    with one window a frame: all three): `distinct` frames repeated in order, every record checked"""
+    n, W, H, name = case
+    sbs, E, want = _scene(W, H, name, n=distinct) if n > 65535 else _tall(W, H, name, n=distinct)
+    assert len({tuple(r) for r in want.tolist()}) == distinct and (n <= 65535 or 65535 % distinct)
+    idx = np.arange(n) % distinct
+    _check(native, E[idx], sbs[idx], 1, MAPS[name], 48, want[idx])
 
 
 def test_a_batch_equals_single_calls_whatever_the_buffers_held(native):

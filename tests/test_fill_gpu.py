@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import fill_ref as FR
+import launch_plan as LP
 
 pytestmark = pytest.mark.gpu
 
@@ -119,6 +120,22 @@ def test_bit_exact(native, W, H, layout):
     for name, (d, want) in cs.items():
         got = run_entry(native, d, layout)
         assert np.array_equal(got, want), f"{W}x{H} n={n} {layout} {name}: " + mismatch_report(got, want, "filled")
+
+
+@pytest.mark.parametrize("n,W,H", LP.FILL_BAND_CASES, ids=[f"n{c[0]}" for c in LP.FILL_BAND_CASES])
+def test_rows_per_workgroup_above_four(native, n, W, H):
+    """k_fill_rows takes clamp(ceil(n H / 2048), 4, 64) rows a workgroup (tests/launch_plan.py): 4 in every sized case above and in
+    the 1080p batch; here 5 and 64, over a height that neither divides, so that the last workgroup of a frame has a short band.
+    Seven distinct frames repeated in order (frames are independent: the sized cases hold that)"""
+    from conftest import mismatch_report
+    ps = patterns(7, H, W, n)
+    idx = np.arange(n) % 7
+    for name in ("runs", "empty-rows", "one-row"):
+        want = FR.fill(ps[name])
+        assert len({f.tobytes() for f in want}) > 1
+        for layout in ("dense", "strided"):
+            got = run_entry(native, ps[name][idx], layout)
+            assert np.array_equal(got, want[idx]), f"n={n} {layout} {name}: " + mismatch_report(got, want[idx], "filled")
 
 
 def test_1080p_batch_of_four(native):

@@ -59,6 +59,25 @@ def test_disp_to_depth_and_u16(native, oracle):
     assert (native.depth_to_u16(flat).cpu().numpy() == 0).all()
 
 
+def test_flat_kernels_past_their_grid_caps(native, oracle):
+    """k_bgr_to_gray, k_disp_to_depth and k_round_u16 launch at most 4096, 2048 and 4096 workgroups (tests/launch_plan.py,
+    LP.PRE_CASES); the cases above stay below them.  One size past each cap: two full passes of the grid and a partial third"""
+    import launch_plan as LP
+    rng = np.random.default_rng(9)
+    H, W = LP.PRE_CASES["v3d_bgr_to_gray"]
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    assert not mismatch_report(native.bgr_to_gray(native.to_device(img)).cpu().numpy(), oracle.bgr_to_gray(img), "gray")
+    H, W = LP.PRE_CASES["v3d_disp_to_depth"]
+    d = (rng.integers(-1, 64 * 16, (H, W))).astype(np.int16)
+    d[rng.random(d.shape) < 0.2] = -16
+    assert np.array_equal(native.disp_to_depth(native.to_device(d)).cpu().numpy(), oracle.disp_to_depth(d))
+    H, W = LP.PRE_CASES["v3d_round_to_u16"]
+    x = rng.uniform(-50, 70000, (H, W)).astype(np.float32)
+    x.reshape(-1)[-300:] = np.arange(0, 300) + 0.5
+    want = np.clip(np.rint(x), 0, 65535).astype(np.uint16)
+    assert np.array_equal(native.round_to_u16(native.to_device(x)).cpu().numpy().view(np.uint16), want)
+
+
 def test_sbs_to_gray_batch_equals_single(native, oracle):
     rng = np.random.default_rng(8)
     sbs = rng.integers(0, 256, (3, 21, 66, 3), dtype=np.uint8)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_plan as LP
 import stereo_ref as SR
 import temporal_ref as TR
 from conftest import mismatch_report
@@ -86,6 +87,32 @@ def test_cuts(native):
         assert list(native.temporal_cuts(_dev(g), 20).cpu().numpy()) == list(TR.cuts(g, 20)) == [0, 1, 0, 0]
 
 
+def test_cuts_where_a_lane_strides(native):
+    """LP.CUTS_CASE (tests/test_launch_plan_host.py holds its regime): 66 frames, so 32 workgroups a pair, of 515 x 255: a lane's
+    second step in the 16-byte loop when the clip is aligned (frames 3 elements apart: a stride of 16 k), 17 steps in the byte
+    loop when it is not (dense: 131 325 = 13 mod 16).  Every pair differs by 20 in every pixel, so a pixel left out or read twice
+    moves the pair across the threshold of 20; single pixels one level off sit in the 16-byte loop's first and second step, in
+    its 13-pixel tail and at both ends"""
+    T, W, H = LP.CUTS_CASE
+    g = np.zeros((T, H, W), np.uint8)
+    g[1::2] = 20
+    flat = g.reshape(T, -1)
+    flat[5, 16 * 8192 + 7] = flat[11, -1] = flat[21, 0] = flat[41, 70001] = 21
+    flat[31, 16 * 8200 + 3] = flat[51, -13] = 19
+    want = {c: TR.cuts(g, c) for c in (19, 20, 21)}
+    assert want[20].sum() == 8 and want[19].sum() == T - 1 and want[21].sum() == 0
+    rng = np.random.default_rng(66)
+    noisy = _gray_clip(rng, T, H, W, spread=12)
+    noisy[40:] = 255 - noisy[40:]
+    for pad in (3, 0):
+        gd = _strided(g, pad) if pad else _dev(g)
+        assert (gd.data_ptr() % 16 == 0 and gd.stride(0) % 16 == 0) == (pad == 3)
+        for c in (19, 20, 21):
+            assert not mismatch_report(native.temporal_cuts(gd, c).cpu().numpy(), want[c], f"strided grid pad {pad} c={c}")
+        nd = _strided(noisy, pad) if pad else _dev(noisy)
+        assert not mismatch_report(native.temporal_cuts(nd, 20).cpu().numpy(), TR.cuts(noisy, 20), f"scene change pad {pad}")
+
+
 @pytest.mark.timeout(300)
 def test_minmax_and_range(native):
     rng = np.random.default_rng(1)
@@ -109,7 +136,8 @@ def test_minmax_and_range(native):
 @pytest.mark.timeout(300)
 def test_range_normalisation(native, oracle):
     rng = np.random.default_rng(2)
-    for (n, H, W, pad) in ((1, 1, 1, 0), (4, 7, 255, 0), (5, 131, 257, 3), (3, 1080, 1920, 0)):
+    # the last: LP.RANGE_FLOOR_CASE, 64 blocks a frame (the floor) for the 127 its elements fill, in k_minmax and k_norm_u16 alike
+    for (n, H, W, pad) in ((1, 1, 1, 0), (4, 7, 255, 0), (5, 131, 257, 3), (3, 1080, 1920, 0), LP.RANGE_FLOOR_CASE + (0,)):
         d = (rng.random((n, H, W)) * 64).astype(np.float32)
         if n > 2:
             d[1] = 7.25                                     # constant frame -> 0

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import emu_case as E
+import launch_plan as LP
 import verify_ref as V
 
 ENTRY = "v3d_verify_eye_source_batch"
@@ -71,6 +72,31 @@ def test_wide_rows(driver, tmp_path):
     _call(driver, tmp_path, _noisy(rng, sbs, 1, 3840, 4, MAPS[0]), sbs, 1, MAPS[0], 48, layout="sbs")
     sbs = rng.integers(0, 256, (1, 2, 2 * 8192, 3), dtype=np.uint8)
     _call(driver, tmp_path, _noisy(rng, sbs, 1, 8192, 1, MAPS[1]), sbs, 1, MAPS[1], 48, skew=15)
+
+
+def test_item_stride(driver, tmp_path):
+    """the grid's stride over the items (tests/launch_plan.py; tests/test_launch_plan_host.py holds the regimes): 1025 items for
+    1024 wave slots, and 1026 items three waves across under a one-row SBS frame, where a wave's second item lies in another
+    column of waves and blends the same SBS rows as its first"""
+    rng = np.random.default_rng(8200)
+    _, W, H = LP.EMU_STRIDE
+    sbs = rng.integers(0, 256, (1, H // 2, 12, 3), dtype=np.uint8)           # the lower half clamps to the last row
+    counts = _call(driver, tmp_path, _noisy(rng, sbs, 1, W, H, LP.EMU_MAP), sbs, 1, LP.EMU_MAP, 48, skew=1)
+    assert 0 < counts[0] < W * H
+    _, W, H = LP.EMU_TAPS
+    sbs = rng.integers(0, 256, (1, 1, 2 * W, 3), dtype=np.uint8)
+    counts = _call(driver, tmp_path, _noisy(rng, sbs, 0, W, H, LP.EMU_MAP), sbs, 0, LP.EMU_MAP, 48, layout="sbs")
+    assert 0 < counts[0] < W * H
+
+
+def test_the_floor_of_eight_workgroups_a_frame(driver, tmp_path):
+    """260 frames of 33 items: 9 workgroups wanted, 8 launched, workgroup 0's first wave walks on; 5 distinct frames repeated"""
+    rng = np.random.default_rng(260)
+    n, W, H = LP.EMU_FLOOR_VERIFY
+    sbs = rng.integers(0, 256, (5, H, 2 * W, 3), dtype=np.uint8)
+    idx = np.arange(n) % 5
+    counts = _call(driver, tmp_path, _noisy(rng, sbs, 1, W, H, LP.EMU_MAP)[idx], sbs[idx], 1, LP.EMU_MAP, 48, rowpad=1, framepad=3)
+    assert len(set(counts[:5].tolist())) > 1 and np.array_equal(counts, counts[:5][idx])
 
 
 def test_three_frames_pitched_rows_and_padded_frames(driver, tmp_path):

@@ -1,9 +1,25 @@
 """v3d_verify_eye_source_batch on the GPU, bit-exact against tests/verify_ref.py: every size at which a cell is cut by the right or
 the bottom edge or a wave holds a part of a row, every cell size class, both eyes, the eye as it lies in a full-SBS and in a full
-top-bottom output, unaligned bases, pitched SBS rows, the threshold's edge, batches and the counters' overwrite."""
+top-bottom output, unaligned bases, pitched SBS rows, the threshold's edge, batches and the counters' overwrite.
+
+Which shape reaches which route of k_verify_eye (tests/launch_plan.py restates the entry's plan, tests/test_launch_plan_host.py holds
+every line below against it):
+  one item per wave, the grid as wide as the frame has items for: SIZES, the packed layouts, the wide rows and the pipeline test
+               (at most 128 items for 1024 wave slots; the pipeline's 1020 stay four short of them);
+  the item stride, n = 1 (a wave's second and third item, `count` carried from item to item, fresh VfTaps and bad_bands per
+               item): LP.STRIDE_SHAPES, 70 columns (two waves across, the second with 6, 7 or 15 live lanes) by as many rows as give
+               2402 items: two passes of the 256 workgroups and a third of 354 items, for every cell class, in both eyes for 4 x 2
+               and once inside a full-SBS buffer at an odd base with pitched SBS rows; in those shapes a wave's items lie in one
+               column of waves (1024 is even), so a wave's next item in ANOTHER column, under SBS rows that every target row shares:
+               LP.EMU_TAPS, 130 x 2730 (three waves across, 1026 items) against a one-row SBS frame;
+  2048 / n workgroups a frame: LP.PER32_CASE, 64 frames of 134 items for 32 workgroups, the second pass 6 items long;
+  the floor of 8 workgroups a frame: LP.FLOOR_CASE, 260 frames of 36 items = 9 workgroups wanted: workgroup 0 alone walks on;
+  the frame stride (f += gridDim.y, wave_count reused for a workgroup's second frame): LP.FRAMES_CASE, 65 538 frames of 5 x 3 for
+               a grid of 65 535 rows, 7 distinct frames repeated so that frame f and frame f + 65535 differ."""
 import numpy as np
 import pytest
 
+import launch_plan as LP
 import stereo_source_ref as X
 import verify_ref as V
 
@@ -102,6 +118,70 @@ def test_wide_rows(native):
     _check(native, _noisy(4, sbs, 1, 8192, 1, (65536, 0, 65536, 0)), sbs, 1, (65536, 0, 65536, 0), 48, eye_phase=15)
     sbs = _sbs(5, 1, 2 * 512, 2)
     _check(native, _noisy(6, sbs, 0, 8192, 1, MAPS["16x16"]), sbs, 0, MAPS["16x16"], 24)
+
+
+def _tall(W, H, name, n=1, eye=1):
+    """as _scene, the SBS frames as tall as the map reaches, so that the rows a target blends keep moving down to the last item"""
+    key = ("tall", W, H, name, n, eye)
+    if key not in _cache:
+        m = MAPS[name]
+        sbs = _sbs(W + H + n, n, 2 * min((W * m[0] >> 16) + 2, 36), (H * m[2] >> 16) + 2)
+        E = _noisy(W * H + n, sbs, eye, W, H, m)
+        _cache[key] = sbs, E, V.verify_batch(E, sbs, eye, *m, 48)
+    return _cache[key]
+
+
+def _check_known(native, E, sbs, eye, m, tau, known, **kw):
+    """_check against a reference computed before"""
+    got, c = _run(native, E, sbs, eye, m, tau, **kw)
+    assert np.array_equal(c, known[1]), (c, known[1])
+    assert np.array_equal(got, known[0]), f"{int((got != known[0]).sum())} bytes differ"
+
+
+@pytest.mark.parametrize("name", list(MAPS))
+def test_item_stride(native, name):
+    """2402 items for 1024 wave slots: every wave walks a second item, 354 of them a third; both verdicts occur in every pass"""
+    assert set(MAPS) == set(LP.VERIFY_CLASSES) and all(MAPS[k] == LP.MAPS[k] for k in MAPS)
+    W, H = LP.STRIDE_SHAPES[name]
+    cx, cy = V.cell(MAPS[name][0], MAPS[name][2])
+    for eye in ((0, 1) if name == "4x2" else (1,)):
+        sbs, E, known = _tall(W, H, name, eye=eye)
+        _check_known(native, E, sbs, eye, MAPS[name], 48, known)
+        changed = (known[0] != E).any(axis=3)[0]                # the pixels that a replaced cell changed
+        thirds = [changed[k * H // 3:(k + 1) * H // 3] for k in range(3)]
+        assert 0 < known[1][0] < -(-W // cx) * -(-H // cy) and all(t.any() and not t.all() for t in thirds)
+
+
+def test_item_stride_in_a_packed_output(native):
+    W, H = LP.STRIDE_SHAPES["3x5"]
+    sbs, E, known = _tall(W, H, "3x5")
+    _check_known(native, E, sbs, 1, MAPS["3x5"], 48, known, layout="sbs", eye_phase=1, sbs_phase=3, rowpad=5)
+
+
+def test_item_stride_into_another_column_of_waves(native):
+    """LP.EMU_TAPS, the emulated twin's shape: three waves across and 1026 items, so a wave's second item lies one column of waves
+    further, and a one-row SBS frame, so both items blend the same rows: taps kept from the first item would be another column's"""
+    _, W, H = LP.EMU_TAPS
+    sbs = _sbs(9, 1, 2 * W, 1)
+    counts = _check(native, _noisy(10, sbs, 0, W, H, LP.EMU_MAP), sbs, 0, LP.EMU_MAP, 48)
+    assert 0 < counts[0] < W * H
+
+
+@pytest.mark.parametrize("case,distinct", [(LP.FLOOR_CASE, 5), (LP.PER32_CASE, 5), (LP.FRAMES_CASE, 7)])
+def test_long_batches(native, case, distinct):
+    """the floor of 8 workgroups a frame, 2048 / n = 32 of them, and more frames than the grid has rows: `distinct` frames
+    repeated in order (frames are independent: test_a_batch_equals_single_calls...), every counter and every byte checked"""
+    n, W, H, name = case
+    if n > 65535:
+        sbs = _sbs(3, distinct, 2, 2)                           # the smallest SBS frame there is
+        E = _noisy(5, sbs, 1, W, H, MAPS[name], share=0.3)
+        known = V.verify_batch(E, sbs, 1, *MAPS[name], 48)
+        assert 65535 % distinct and len(set(known[1].tolist())) > 1            # frame f and frame f + 65535 differ
+    else:
+        sbs, E, known = _tall(W, H, name, n=distinct)
+    assert len({e.tobytes() for e in known[0]}) == distinct
+    idx = np.arange(n) % distinct
+    _check_known(native, E[idx], sbs[idx], 1, MAPS[name], 48, (known[0][idx], known[1][idx]))
 
 
 def test_threshold_edge(native):
