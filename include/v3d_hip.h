@@ -763,6 +763,34 @@ int v3d_eye_fidelity_batch(const uint8_t* eye_bgr, size_t eye_stride /* bytes */
                            int64_t ax, int64_t bx, int64_t ay, int64_t by, int bad_thr,
                            int64_t* out /* [n][V3D_FIDELITY_FIELDS] */, void* ws, void* stream);
 
+/* Source-fused eye (v3d_fuse.hip): the low band of a rendered eye taken from the stored eye of the SBS frame, the detail above the
+   stored eye's resolution kept from the render, IN PLACE (the convert CLI's --fuse-source, after the render and the verification).
+   No call site in the reference.  Bit-exact contract, all integers: tests/fuse_ref.py.
+   The eye image E, the SBS frames, the map and P = P(eye)[y][t] are exactly those of v3d_verify_eye_source_batch above: the same
+   u, v, clamps, fx, fy and rounding, the same addressing of an eye inside a full-SBS or full top-bottom output.
+   Per axis (coefficient a, offset b, Nd targets, Ns samples): q(t) = clamp(a t + b, 0, (Ns - 1) << 16) in 64 bits,
+   near(t) = (q + 32768) >> 16, lo = near(0), hi = near(Nd - 1); i0 = q >> 16, i1 = min(i0 + 1, Ns - 1), f = (q >> 8) & 255 as in P.
+   With a <= 65536 near never steps by more than 1: every sample of [lo, hi] owns at least one target.
+   Means plane, for j in [jlo, jhi], i in [ilo, ihi] and channel c:  A = sum of E[y][t][c] over the targets with near_y(y) = j and
+   near_x(t) = i, N their number (64-bit sums: under the clamps a first or last sample may own any share of the image);
+     M[j][i][c] = (2 A + N) / (2 N)        (/ floors).
+   Low band: LP[y][t][c] = P's bilinear formula ((...) + 32768) >> 16 with the same fx, fy over M in place of the stored eye, the
+   tap indices clamped once more to the populated range: clamp(i0, ilo, ihi), clamp(i1, ilo, ihi), and likewise for j.
+   Result: E[y][t][c] = clamp(E - LP + P, 0, 255).  Every payload byte of E is written; nothing else outside ws is.
+   Memory contract: E is read and written at its rows' payload bytes only (3W per row, any pitch, any byte offset), the SBS rows
+   are read at the payload bytes of the sampled eye's half only; neither needs any alignment.  ws: device scratch of
+   v3d_fuse_eye_source_ws_bytes(n, Ws, Hs) = n * Hs * (Ws/2) * 3 bytes rounded up to 16 (0 for n < 1, Ws odd or < 2, Hs < 1 or
+   Ws/2 > 8192), 16-byte aligned, any content on entry: it holds M, of which only the populated range is written and read.  Two
+   launches (the means of the whole eye, then the result: a single launch would read targets another workgroup has written
+   already), no allocation, no synchronisation.
+   V3D_ERR_ARG: everything v3d_verify_eye_source_batch refuses for the same arguments; a null ws or one that is not 16-byte
+   aligned.  V3D_ERR_UNSUPPORTED, looked at after every V3D_ERR_ARG: W > 8192 or Ws/2 > 8192; ax or ay above 65536 (the stored
+   eye is finer than the frame: a sample could own no target, and fusing has nothing to add).  A refused call enqueues nothing. */
+size_t v3d_fuse_eye_source_ws_bytes(int n, int Ws, int Hs);
+int v3d_fuse_eye_source_batch(uint8_t* eye_bgr, size_t eye_stride /* bytes */, int eye_pitch /* bytes */, int n, int W, int H,
+                              const uint8_t* sbs_bgr, size_t sbs_stride /* bytes */, int Ws, int Hs, int pitch, int eye /* 0 | 1 */,
+                              int64_t ax, int64_t bx, int64_t ay, int64_t by, void* ws, void* stream);
+
 const char* v3d_last_error(void);
 const char* v3d_version(void);
 

@@ -125,6 +125,8 @@ SIGNATURES = {
     "v3d_verify_eye_source_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64, ci, vp, vp]),
     "v3d_eye_fidelity_ws_bytes": (sz, [ci, ci, ci, i64, i64]),
     "v3d_eye_fidelity_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64, ci, vp, vp, vp]),
+    "v3d_fuse_eye_source_ws_bytes": (sz, [ci, ci, ci]),
+    "v3d_fuse_eye_source_batch": (ci, [vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, ci, i64, i64, i64, i64, vp, vp]),
     "v3d_last_error": (cs, []),
     "v3d_version": (cs, []),
 }
@@ -1229,3 +1231,33 @@ def to_device(a, device="cuda"):
     if not a.flags.writeable:          # e.g. a memory-mapped clip: torch wants a writable buffer
         a = a.copy()
     return torch.from_numpy(a).to(device)
+
+
+def fuse_eye_source_ws_bytes(n, Ws, Hs):
+    """the workspace of fuse_eye_source_batch for n SBS frames of Ws x Hs in bytes (v3d_fuse_eye_source_ws_bytes)"""
+    need = lib().v3d_fuse_eye_source_ws_bytes(int(n), int(Ws), int(Hs))
+    if not need:
+        raise NativeError(f"fuse_eye_source_batch: {n} SBS frames of {Ws}x{Hs} outside the entry's range (Ws even, Ws/2 <= 8192)")
+    return need
+
+
+def fuse_eye_source_batch(eye_bgr, sbs, eye, ax, bx, ay, by, ws=None):
+    """a rendered eye fused IN PLACE with the stored eye `eye` (0 | 1) of the SBS frames (v3d_fuse_eye_source_batch): eye_bgr u8
+    [n,H,W,3] on the device, usually a view of a packed output, and sbs u8 [n,Hs,Ws,3], both as for verify_eye_source_batch.  The
+    eye keeps its detail above the stored eye's resolution and takes everything below it from the stored eye: E - LP(E) + P.  ws:
+    a caller's uint8 scratch of v3d_fuse_eye_source_ws_bytes; None takes it from the caching allocator.  -> eye_bgr.
+    Bit-exact contract: tests/fuse_ref.py."""
+    p, fs, n, W, H, pitch = _bgr_frames(eye_bgr, "eye_bgr")
+    sp, ss, ns, Ws, Hs, spitch = _bgr_frames(sbs, "sbs")
+    if ns != n:
+        raise NativeError(f"sbs: {ns} frames for {n} eye images")
+    if eye not in (0, 1):
+        raise ValueError(f"eye must be 0 (left) or 1 (right), got {eye!r}")
+    need = fuse_eye_source_ws_bytes(n, Ws, Hs)
+    if ws is None:
+        ws = _scratch(need, eye_bgr.device)
+    elif ws.numel() < need:
+        raise NativeError(f"ws: {ws.numel()} bytes, fuse_eye_source_batch needs {need}")
+    _call("v3d_fuse_eye_source_batch", eye_bgr.device, p, fs, pitch, n, W, H, sp, ss, Ws, Hs, spitch, int(eye), int(ax), int(bx),
+          int(ay), int(by), _dev(ws, torch.uint8, "ws"))
+    return eye_bgr

@@ -23,7 +23,9 @@ eye's target of a pixel is x - round(K s d): the left eye is the 4K frame, the r
 --verify-source [TAU] then checks the rendered right eye against that stored eye, cell by cell, and replaces the cells whose mean
 colour is off by more than TAU with the stored eye's own samples (verify.py; only where the right eye lies unpacked in the output:
 full-sbs and full-tb); --fidelity-report [PATH] measures what came of it against the SBS frame's stored eyes (fidelity.py), and changes
-no output byte and no cache key.  These three are the plan's steps (verify.SourceStep): the conversion only iterates them.
+no output byte and no cache key.  --fuse-source, between the two, takes the right eye's low band from the stored eye and keeps only
+the render's detail above the stored eye's resolution (verify.SourceFuser).  These four are the plan's steps (verify.SourceStep):
+the conversion only iterates them.
 
 Data flow: depth PNGs are decoded ahead on reader threads, 4K frames stream from the decoder, CONVERT_BATCH frames at a time
 cross PCIe in one pinned copy, render in one launch and come back in one copy; 8-bit RGB PNGs are compressed on the writer
@@ -42,7 +44,7 @@ from .colour import DEFAULT_PROBES, ColourMatcher
 from .fidelity import FidelityMonitor, check_fidelity_report
 from .utils import (PngWriterPool, encode_png8, finish_sequence, get_video_info, iter_frames, prefetch_map, read_png16,
                     sibling_frames_dir)      # sibling_frames_dir is importable from here too
-from .verify import DEFAULT_VERIFY_TAU, VERIFY_LAYOUTS, VERIFY_TAU_MAX, SourceVerifier, check_source_rules, check_verify_source  # noqa: F401
+from .verify import DEFAULT_VERIFY_TAU, VERIFY_LAYOUTS, VERIFY_TAU_MAX, SourceFuser, SourceVerifier, check_fuse_source, check_source_rules, check_verify_source  # noqa: F401
 
 # V3D_PACK_*: codes 0 / 1 are V3D_STEREO_FULL_SBS / V3D_STEREO_HALF_SBS of v3d_render_stereo[_subpixel]_batch, codes >= 2 go to
 # v3d_render_stereo_packed_batch
@@ -249,6 +251,8 @@ class HipRenderBackend(HipBackend):
         With a `verify` entry (--verify-source: dict(tau)) the right eye of the staged output is checked in place against the
         (colour-matched) stored right eye right after the render, v3d_verify_eye_source_batch with the render's own map; its
         counters start their way to pinned memory before the frames' copy and are read after it (verify_counts).
+        With a `fuse` entry (--fuse-source) that right eye, verified or not, is then fused in place with the same stored eye under
+        the same map, v3d_fuse_eye_source_batch on a workspace of this backend's staging.
         With a `fidelity` entry (--fidelity-report: dict(bad_thr, ceiling)) the frames are rendered once more with fill_eyes 0 into
         a scratch output of this backend, and v3d_eye_fidelity_batch measures that right eye, the right eye of the staged output
         and, with `ceiling`, its left eye against the stored eyes; the staged output is only read.  With `ceiling` and a `match`
@@ -275,6 +279,9 @@ class HipRenderBackend(HipBackend):
                     nat.verify_eye_source_batch(right_eye_view(od[:n], layout, W, H), sd, 1, *source["q"], source["verify"]["tau"],
                                                 out=counts[:n])
                     self._verify = self._fetch_async([counts[:n]])
+                if source.get("fuse") is not None:
+                    ws = self._staging("fuse_ws_dev", (nat.fuse_eye_source_ws_bytes(cap, *sd.shape[2:0:-1]),), torch.uint8, False)
+                    nat.fuse_eye_source_batch(right_eye_view(od[:n], layout, W, H), sd, 1, *source["q"], ws=ws)
                 if fid is not None:
                     self._fidelity = self._measure_fidelity(fd, dd, sd, od[:n], (gain_left, gain_right, conv), layout, subpixel,
                                                             source["q"], fid, cap)
@@ -359,13 +366,13 @@ class StereoPlan:
     convergence / eye_split, parallax_gain scales it;
     fill_from_source: the SBS clip whose stored right eye fills the right eye's disocclusions (needs parallax="source": the holes
     of an invented parallax do not line up with the real eye); source_start_frame: its frame that depth frame 0 was made from;
-    match_colour and match_probes, verify_source (the threshold), fidelity_report (True: next to the manifest, or its path): the
+    match_colour and match_probes, verify_source (the threshold), fuse_source, fidelity_report (True: next to the manifest, or its path): the
     source-eye options, which make self.steps (verify.SourceStep) in the order of their entries in the render calls' source dict"""
 
     def __init__(self, max_shift: float = DEFAULT_MAX_SHIFT, convergence: float = DEFAULT_CONVERGENCE,
                  eye_split: float = DEFAULT_EYE_SPLIT, layout: str = "full-sbs", subpixel: bool = False, parallax: str = "invented",
                  parallax_gain: float = 1.0, fill_from_source: str = None, source_start_frame: int = 0, match_colour: str = None,
-                 match_probes: int = None, verify_source: int = None, fidelity_report=None):
+                 match_probes: int = None, verify_source: int = None, fidelity_report=None, fuse_source: bool = False):
         if parallax not in PARALLAX:
             raise ValueError(f"parallax must be one of {PARALLAX}, got {parallax!r}")
         check_source_rules(fill_from_source, parallax=parallax)
@@ -380,6 +387,10 @@ class StereoPlan:
         self.verify_source = None if verify_source is None else check_verify_source(verify_source, layout, parallax == "source", False)
         if self.verify_source is not None:
             self.steps.append(SourceVerifier(self.verify_source))
+        self.fuse_source = bool(fuse_source)
+        if self.fuse_source:
+            check_fuse_source(layout, parallax == "source", False)
+            self.steps.append(SourceFuser())
         self.fidelity_report = None if fidelity_report is None or fidelity_report is False else fidelity_report
         if self.fidelity_report is not None:
             check_fidelity_report(layout, parallax == "source", False)
@@ -429,7 +440,10 @@ class StereoPlan:
         if Ws % 2:
             raise ValueError(f"the SBS frames of --fill-from-source are {Ws} wide: not two eyes side by side")
         source = dict(frames=sbs_frames, fill_eyes=FILL_RIGHT_EYE, q=fill_map_q16(self.spatial_map, (Ws // 2, Hs), frame_size))
-        source.update((step.key, step.request()) for step in self.steps if step.on_surface or not surface)
+        for step in self.steps:
+            if step.on_surface or not surface:
+                step.check_map(source["q"])
+                source[step.key] = step.request()
         return {"source": source}
 
     def note(self, backend, src, indices, frame_size):
@@ -484,7 +498,8 @@ class DepthTo3DConverter:
         """NumPy surface: HxWx3 uint8 BGR + HxW uint16 depth -> the side-by-side BGR image (synchronous).  source: the SBS BGR
         frame the depth was made from; the right eye's disocclusions are sampled from its stored right eye (parallax="source" only);
         colour_table: u8 [3,256] (BGR), applied to that eye first, as --match-colour clip applies its table.  With verify_source
-        set and a source given, the right eye is verified against that stored eye as --verify-source does"""
+        set and a source given, the right eye is verified against that stored eye as --verify-source does, and with fuse_source set it
+        is then fused with it as --fuse-source does"""
         frame_bgr, depth_u16 = np.asarray(frame_bgr), np.asarray(depth_u16)
         if frame_bgr.shape[:2] != depth_u16.shape or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
             raise ValueError(f"frame {frame_bgr.shape} and depth {depth_u16.shape} disagree")
@@ -664,6 +679,12 @@ def main(argv=None, backend=None):
                              "stored eyes on the GPU -- error sums and SSIM of the right eye before the fill (depth + DIBR alone), of the "
                              "right eye as written, and of the left eye (how far the two releases differ) -- print a summary and write "
                              "<output>_fidelity.json next to the manifest (or to PATH).  No output changes")
+    parser.add_argument('--fuse-source', action='store_true',
+                        help="with --fill-from-source and --layout full-sbs or full-tb: take the right eye's low band (everything up to "
+                             "the SBS clip's resolution) from the clip's stored right eye and keep only the detail above it from the "
+                             "render: out = E - LP(E) + P, after --verify-source where both are given.  Filled holes and replaced cells "
+                             "gain the 4K frame's detail, and slightly wrong warps lose their wrong low frequencies.  Use it with "
+                             "--match-colour: the low band carries the SBS release's grading otherwise.  Default: off")
     from .align import add_guide_arguments, resolve_guide_start
     add_guide_arguments(parser, 'depth frame 0', 'the offset the upscale CLI used')
     args = parser.parse_args(argv)
@@ -674,10 +695,10 @@ def main(argv=None, backend=None):
         check_source_rules(args.fill_from_source, source_start_frame=args.source_start_frame)
         if args.verify_source is not None:
             check_verify_source(args.verify_source, args.layout, args.fill_from_source)
-        check_source_rules(args.fill_from_source, layout=args.layout, fidelity_report=args.fidelity_report)
+        check_source_rules(args.fill_from_source, layout=args.layout, fidelity_report=args.fidelity_report, fuse_source=args.fuse_source)
         conv = DepthTo3DConverter(device=args.device, backend=backend, **stereo_options(args), **png_options(args),
                                   **{k: getattr(args, k) for k in ("fill_from_source", "source_start_frame", "match_colour", "match_probes",
-                                                                     "verify_source", "fidelity_report")})
+                                                                     "verify_source", "fidelity_report", "fuse_source")})
         output_path = conv.process_conversion(args.video_4k, args.depth_4k, output_path=args.output,
                                               force_reprocess=args.force, guide_start_frame=args.guide_start_frame,
                                               max_frames=args.max_frames)
